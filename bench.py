@@ -9,11 +9,22 @@ teacher forward + hard-instance select + student forward + CE/distillation head 
 the flat gradient buffer] + fused Adam + EMA teacher.  Bags are resident in HBM before the timed region (8 distinct
 bags per rank = 328 MB > the 256 MB Infinity Cache, rotated).  Rank 0 prints ONE JSON line.
 
-The default one-GPU run also carries, inside the same JSON line (each with its own short, fixed step count):
+A plain run sets up, warms up, times the K steps, writes the last step's outputs if --dump-outputs DIR is given, and prints the line.
+--full adds every other measurement to the same line (--no-kernel-events, --no-repeats, --no-extras and --cpu-steps 0 leave parts out):
+  "roofline"         the projection launch bracketed by HIP events in an eager pass before the warm-up, and the stamped shader clock;
+  "region_repeats"   the timed region five more times right after it;
+  "cpu_baseline"     the oracle's train step on the host cores;
+and, on one GPU, each with its own short, fixed step count:
   "accumulate8"      the same step with --accumulation_steps 8 as ONE captured window (FusedTrainer.capture_window): ms per bag;
   "hbm_copy"         the on-box float4 stream-copy rate (GB/s read + written) beside the nominal 8 TB/s;
+  "reference_loop"   the reference trainer's loop body on the drop-in classes;
   "other_workloads"  c3 (MHIM(TransMIL) N=50k) and c5 (one bag N=200k D=1536, the sharded code path at world 1), each with its
-                     roofline figure and a one-step cpu_baseline.   --no-extras skips all three.
+                     roofline figure and a one-step cpu_baseline.
+
+--dump-outputs DIR: after the timed steps, rank 0 writes the state the last timed step left as DIR/<name>.npy (float32): the student's
+and the EMA teacher's state_dict entries (student.<key>, teacher.<key>), the Adam moments (adam_m.<key>, adam_v.<key>) and, where the
+timed steps were eager train_step calls, the last step's logits and losses (a hipGraph replay hands none back).  Bags, weights and
+draws are seeded: the same arguments give the same inputs in every run.
 """
 from __future__ import annotations
 
@@ -59,6 +70,12 @@ def parse():
                     help="c2 (default, BASELINE.json's metric): MHIM(ABMIL) N=10k D=1024, one bag per GPU per step; "
                          "c3: MHIM(TransMIL) N=50k D=1024 (replicas); c5: ONE bag N=200k D=1536 instance-sharded over the GPUs; "
                          "c2-dsmil: MHIM(DSMIL) N=10k D=1024 (scope row N1)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: projection-kernel roofline, region repeats, CPU baseline and, on one "
+                         "GPU, the accumulate8 / hbm_copy / reference_loop / other_workloads legs (off: only the timed steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the state the last timed step left (models, Adam moments, logits / losses of an "
+                         "eager step) as DIR/<name>.npy")
     return ap.parse_args()
 
 
@@ -200,6 +217,41 @@ def timed(a, world, dev, step):
     return dt
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, trainer, last=None):
+    """--dump-outputs: what the timed steps leave behind, as float32 DIR/<name>.npy.  The models and the Adam moments are updated in place
+    by every step (graph replays included), so they are the last timed step's result; ``last``: the (logits, losses) an eager step
+    returned.  Past DUMP_LIMIT_BYTES in all, every array above its even share is replaced by a fixed, seeded sample of its elements."""
+    import numpy as np
+    torch.cuda.synchronize()
+    arrays = {}
+    for role, model in (("student", trainer.s), ("teacher", trainer.t)):
+        if model is not None:
+            for k, v in model.state_dict().items():
+                arrays[f"{role}.{k}"] = v
+    fl = trainer.flat
+    params = dict(trainer.s.named_parameters())
+    for n in fl.train_names:
+        off, p = fl.offsets[n], params[n]
+        arrays[f"adam_m.{n}"] = fl.m[off:off + p.numel()].view_as(p)
+        arrays[f"adam_v.{n}"] = fl.v[off:off + p.numel()].view_as(p)
+    if last is not None:
+        arrays["logits"], arrays["losses"] = last
+    arrays = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    total = sum(v.nbytes for v in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        share = DUMP_LIMIT_BYTES // len(arrays) // 4
+        rng = np.random.default_rng(0)
+        for k in sorted(arrays):
+            if arrays[k].size > share:
+                arrays[k] = arrays[k].reshape(-1)[np.sort(rng.choice(arrays[k].size, share, replace=False))]
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(out_dir, f"{k}.npy"), np.ascontiguousarray(v, dtype=np.float32))
+
+
 def other_workload(a, world, rank, dev, embedded=False):
     """c3 / c5: parity-test configurations of BASELINE.json (not the headline metric).  Returns rank 0's result dict (None elsewhere);
     ``embedded``: called from the default c2 run with its own short step counts."""
@@ -227,6 +279,7 @@ def other_workload(a, world, rank, dev, embedded=False):
         bags = [torch.randn(n_total, d, device=dev, generator=g).abs_() for _ in range(2)]
         graphs = None if a.no_graph else [tr.capture(b, lab, warmup=2) for b in bags]
         step = (lambda i: tr.train_step(bags[i % 2], lab)) if graphs is None else (lambda i: graphs[i % 2].replay())
+        eager = graphs is None
         per_step, scaling, par = n_total * world, "weak", f"dp{world} (replicas, one bag per GPU per step)"
         name = (f"c3: MHIM(TransMIL/Nystrom)" if bl == "selfattn" else "MHIM(DSMIL)") + f" train step, one bag N={n_total} D={d} per GPU per step"
     else:
@@ -237,6 +290,7 @@ def other_workload(a, world, rank, dev, embedded=False):
         tr = ShardedBagTrainer(student, teacher, counts=[n] * world, seed=11, aux_alpha=0.5, mm=0.9997)
         bags = [torch.randn(n, d, device=dev, generator=g).abs_() for _ in range(2)]
         step = lambda i: tr.train_step(bags[i % 2], lab)
+        eager = True
         c5_launch = "eager"
         if bl == "selfattn":
             c5_launch = "eager (the sequence-parallel TransMIL step plans its exchanges on the host every step: sharded_transmil.py)"
@@ -245,6 +299,7 @@ def other_workload(a, world, rank, dev, embedded=False):
             try:
                 replays = [tr.capture(b, lab, warmup=2) for b in bags]
                 step = lambda i, replays=replays: replays[i % 2]()
+                eager = False
                 c5_launch = "hipGraph segments between the exchanges (graph | collective | graph ...), one set per resident shard"
             except Exception as e:  # noqa: BLE001 - reported in the JSON line
                 c5_launch = f"eager (segment capture failed: {type(e).__name__}: {str(e)[:160]})"
@@ -252,6 +307,8 @@ def other_workload(a, world, rank, dev, embedded=False):
         name = (f"c5: MHIM(ABMIL) train step on ONE bag N={n_total} D={d} sharded by rows" if bl == "attn" else
                 f"c3-sharded: MHIM(TransMIL/Nystrom) train step on ONE bag N={n_total} D={d} sharded by rows, sequence-parallel encoder")
     dt = timed(a, world, dev, step)
+    if rank == 0 and a.dump_outputs and not embedded:
+        dump_outputs(a.dump_outputs, tr, (tr.last["logits"], tr.last["losses"]) if eager and "logits" in tr.last else None)
     if rank == 0:
         algo = 3 * d * 4 + 4 * (1 + 2) + 8                   # three passes over X + score / ids, per instance per step
         extra = {"whole_step_hbm_roofline": {"algorithmic_bytes_per_instance": algo,
@@ -281,7 +338,7 @@ def other_workload(a, world, rank, dev, embedded=False):
                 extra["roofline"]["traffic"] = pj["step_traffic_bytes"]
                 extra["roofline"]["traffic_unit"] = "bytes per step (all launches)"
                 extra["roofline"]["traffic_source"] = f"profiles/{pmc_name}: read {pj['step_read_bytes'] / 1e6:.0f} MB + write {pj['step_write_bytes'] / 1e6:.0f} MB per step"
-        if world == 1 and a.cpu_steps > 0:
+        if world == 1 and a.full and a.cpu_steps > 0:
             extra["cpu_baseline"] = cpu_baseline_other(a.workload, base, n_total, d, bl)
         return {
             **extra,
@@ -572,7 +629,8 @@ def main():
     ev = []
     spin = [False]                             # (only in the dedicated eager pass: never under capture, never in a timed region)
     hook = None
-    if not a.no_kernel_events:
+    kernel_events = a.full and not a.no_kernel_events
+    if kernel_events:
         def hook(tag, M, N, K):
             if tag == "bag_project" and M >= N_INST and K == D_IN:                # the teacher + student projection launch
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -646,7 +704,7 @@ def main():
     events_from = "the timed region"
     ev_eager = None
     proj_ms = proj_empty_ms = None
-    if graphs is not None and not a.no_kernel_events:
+    if graphs is not None and kernel_events:
         # Host-side HIP event records cannot be placed between the nodes of a replayed hipGraph (ROCm rejects external
         # event nodes), so the dominant kernel is bracketed in an eager pass of the SAME steps right BEFORE the warm-up and the
         # timed region (it used to run after them; before, its ~8 ms of launches also settle the clocks that a 5 + 20-step run
@@ -683,11 +741,13 @@ def main():
     if graphs is None:
         ops.KERNEL_EVENT_HOOK = hook            # eager steps: the events of the timed steps themselves
     dt = timed(a, world, dev, step)
+    if rank == 0 and a.dump_outputs:
+        dump_outputs(a.dump_outputs, trainer, (trainer.last["logits"], trainer.last["losses"]) if graphs is None else None)
     # (round 6) the line calibrates itself: the SAME region - K steps between two synchronisations - five more times right
     # after the headline one.  `value` stays the first region (the contract: exactly K timed steps after W warm-up steps); the spread of the
     # repeats is what a claimed same-box gain has to exceed.
     repeats = None
-    if world == 1 and not a.no_repeats:
+    if world == 1 and a.full and not a.no_repeats:
         rep = []
         for _ in range(5):
             torch.cuda.synchronize()
@@ -707,7 +767,7 @@ def main():
     ops.KERNEL_EVENT_HOOK = None
 
     extras = {}
-    if world == 1 and not a.no_extras:
+    if world == 1 and a.full and not a.no_extras:
         extras = run_extras(a, dev, bags, labels)
 
     if rank == 0:
@@ -808,7 +868,7 @@ def main():
                                                     "bytes_per_launch": budget, "achieved_GBps": budget / (avg * 1e-3) / 1e9,
                                                     "frac_of_8TBps": budget / (avg * 1e-3) / 1e9 / HBM_PEAK_GBS},
                                "hbm_copy_peak_GBps_measured": (extras.get("hbm_copy") or {}).get("GBps")}
-        if world == 1 and not a.no_extras and "roofline" in out:
+        if world == 1 and a.full and not a.no_extras and "roofline" in out:
             clk = sustained_clock()
             if clk:
                 # the matrix pipe's ceiling at the clock the launch really holds (the dense peak is quoted at 2.4 GHz)
@@ -817,7 +877,7 @@ def main():
                 clk["mfma_issued_frac_at_this_clock"] = out["roofline"]["mfma_issued_TFLOPs"] / peak_here
                 out["roofline"]["sustained_clock_GHz"] = clk
         out.update(extras)
-        if world == 1 and a.cpu_steps > 0:
+        if world == 1 and a.full and a.cpu_steps > 0:
             out["cpu_baseline"] = cpu_baseline(a.cpu_steps, base)
         print(json.dumps(out), flush=True)
     if world > 1:

@@ -3,8 +3,8 @@
 ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 cd $ROOT
 O=gpurun_out/r03; mkdir -p $O
-python bench.py --steps 20 --warmup 5 > $O/bench_default.json 2> $O/bench_default.err
-python bench.py --no-extras --cpu-steps 0 > $O/bench_c2_400.json 2>/dev/null
+python bench.py --full --steps 20 --warmup 5 > $O/bench_default.json 2> $O/bench_default.err
+python bench.py --full --no-extras --cpu-steps 0 > $O/bench_c2_400.json 2>/dev/null
 LINES_OUT=40 tools/prof.sh r03 --steps 100 --warmup 20 --no-extras > $O/prof_c2.log 2>&1
 python tools/timeline.py gpurun_out/prof_r03/r03_results.db > $O/timeline_c2.txt 2>&1
 cp gpurun_out/prof_r03/summary.md $O/kernel_trace_c2.md

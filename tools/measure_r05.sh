@@ -7,8 +7,8 @@ O=gpurun_out/r05; mkdir -p $O
 PARTS=${@:-bench c2 pmc c3 c5 window}
 has() { [[ " $PARTS " == *" $1 "* ]]; }
 if has bench; then
-  python bench.py --steps 20 --warmup 5 > $O/bench_default.json 2> $O/bench_default.err
-  python bench.py --no-extras --cpu-steps 0 > $O/bench_c2_400.json 2>/dev/null
+  python bench.py --full --steps 20 --warmup 5 > $O/bench_default.json 2> $O/bench_default.err
+  python bench.py --full --no-extras --cpu-steps 0 > $O/bench_c2_400.json 2>/dev/null
   for w in c3 c5 c2-dsmil; do python bench.py --workload $w --cpu-steps 0 2>/dev/null | grep "^{" > $O/bench_$w.json; done
   python tools/exp_step_exec.py 2>/dev/null | grep "ms/step" > $O/step_exec.txt
 fi
