@@ -26,7 +26,7 @@ extern "C" {
 #endif
 
 /* bumped whenever an entry point or a struct changes shape; the ctypes binding (mhim_mil_amd/_lib.py ABI_VERSION) refuses any other value */
-#define MHIMX_VERSION 610
+#define MHIMX_VERSION 620
 
 /* activations (feature act: mhim.py:71-74 relu|gelu|none; scorer act: baseline.py:17-22 gelu|relu|tanh|none) */
 enum { MHIMX_ACT_NONE = 0, MHIMX_ACT_RELU = 1, MHIMX_ACT_GELU = 2, MHIMX_ACT_TANH = 3 };
@@ -869,6 +869,48 @@ int mhimx_window_layout_of(const mhimx_step_cfg* cfg, int32_t n_bags, int64_t N,
 int mhimx_window_run(void* stream, const mhimx_step_cfg* cfg, int32_t n_bags, const float* const* X, int64_t ldx, int64_t N,
                      const int64_t* const* labels_dev, const mhimx_step_counts* cnt, const mhimx_step_seeds* seeds, int64_t host_step, void* ws,
                      int64_t ws_bytes, int32_t update);
+
+/* ------------------------------------------------------------------------------------------
+ * Ragged multi-bag inference: the eval-mode forward of MHIM(ABMIL) for n_bags bags of DIFFERENT row counts in one call - a validation
+ * or test pass as one C call per chunk of bags instead of ~8 launches per bag from the host loop.
+ * replaces: modules/mhim.py:229-272 (forward_test, merge_test off) under engines/common_mil.py:56-68 (validate_func) and the per-bag
+ *           loop + criterion call of engines/base_engine.py:234-329 (main.py:273-292,407-410 run it on the student, the EMA teacher
+ *           and at test time; datasets/dataset_feat.py:93-111 yields a different N per slide).
+ * Per bag:  h = act(X W1^T + b1) (dropout is the identity in eval),  s = wc . da_act(h Wa^T),  z = softmax(s) h,
+ *           logits = z Wp^T + bp,  loss = cross entropy of the logits row.   Matrix products in the 3-term bf16 form (~2^-16), the
+ *           softmax, the head and the loss in fp32.
+ * Four launches whatever n_bags is (weight images, ragged projection, ragged scorer + pool partials, merge + head + loss + attention);
+ * the per-bag table travels by value: no host-to-device copy, no synchronisation, no allocation - a call can be captured in a graph.
+ * No workgroup waits for another.  A bag's row tiles, its pool partials (one per 256 rows) and their merge order depend on its own N
+ * alone: its outputs have the same bits wherever it stands in a call and whatever its neighbours are.
+ * Shapes: E = 512, A = 128, plain (not gated) scorer without biases, C <= 16, D % 256 == 0, every N >= 1; anything else returns < 0
+ * before any device call.  cfg->p: the six parameters of ONE model (student or teacher; the merge.* fields are not read).
+ * Workspace: mhimx_infer_ws_bytes (pure host arithmetic, no device needed; < 0 on a refused shape), 256-byte aligned; it holds the
+ * feature rows (2 KiB per row): the caller bounds a call by rows.
+ * ---------------------------------------------------------------------------------------- */
+#define MHIMX_INFER_MAX 32                        /* bags of one mhimx_infer_run                                                          */
+#define MHIMX_INFER_MAX_ROWS 4194304              /* rows of one bag, and of one call                                                     */
+typedef struct {
+  int64_t D, E, A, C;                             /* input_dim, mlp_dim, scorer width, classes                                            */
+  int32_t act, da_act;                            /* MHIMX_ACT_* of the feature / the scorer                                              */
+  mhimx_step_params p;                            /* w1, b1, wa, wc, wp, bp                                                               */
+} mhimx_infer_cfg;
+typedef struct {
+  const float* X; int64_t ldx;                    /* the bag [N, ldx >= D] fp32, 16-byte aligned rows (bags need not be contiguous)       */
+  int64_t N;                                      /* >= 1                                                                                 */
+} mhimx_infer_bag;
+typedef struct {                                  /* row_off[b] = N[0] + .. + N[b-1]                                                      */
+  float* logits;                                  /* [n_bags, C]                                                                          */
+  float* z;                                       /* [n_bags, E] pooled rows, optional (NULL)                                             */
+  float* stats;                                   /* [n_bags, 2] {max, sum_n e^{s_n - max}} of each bag's scores                          */
+  float* score;                                   /* [sum N] optional: raw scorer outputs, bag b's at row_off[b] (forward_test no_norm)   */
+  float* attn;                                    /* [sum N] optional: their softmax per bag (forward_test return_attn)                   */
+  float* loss;                                    /* [n_bags] optional (needs labels): cross entropy of each bag's logits                 */
+} mhimx_infer_out;
+int64_t mhimx_infer_ws_bytes(const mhimx_infer_cfg* cfg, int32_t n_bags, const mhimx_infer_bag* bags);
+/* labels_dev: int64 [n_bags] on the device, or NULL (a label outside [0, C) gives a NaN loss) */
+int mhimx_infer_run(void* stream, const mhimx_infer_cfg* cfg, int32_t n_bags, const mhimx_infer_bag* bags, const int64_t* labels_dev,
+                    const mhimx_infer_out* out, void* ws, int64_t ws_bytes);
 
 /* dst = src (float4 grid-stride stream copy): the on-box HBM copy rate bench.py reports beside the nominal 8 TB/s */
 int mhimx_stream_copy(void* stream, const float* src, float* dst, int64_t n_floats);

@@ -12,7 +12,7 @@ c_f32p = C.c_void_p
 c_i64p = C.c_void_p
 c_u8p = C.c_void_p
 
-ABI_VERSION = 610          # == MHIMX_VERSION of the include/mhimx.h this binding was written against
+ABI_VERSION = 620          # == MHIMX_VERSION of the include/mhimx.h this binding was written against
 
 ACT = {None: 0, "none": 0, "identity": 0, "relu": 1, "gelu": 2, "tanh": 3}
 PREC = {"f32": 0, "f16s": 1, "bf16x3": 2}
@@ -219,6 +219,24 @@ class WindowLayout(C.Structure):
 
 WINDOW_MAX = 8               # MHIMX_WINDOW_MAX
 
+
+class InferCfg(C.Structure):
+    """mhimx_infer_cfg: the eval-mode forward of ONE model (p: w1, b1, wa, wc, wp, bp) over bags of different row counts."""
+    _fields_ = [("D", C.c_int64), ("E", C.c_int64), ("A", C.c_int64), ("C", C.c_int64), ("act", C.c_int32), ("da_act", C.c_int32),
+                ("p", StepParams)]
+
+
+class InferBag(C.Structure):
+    _fields_ = [("X", c_f32p), ("ldx", C.c_int64), ("N", C.c_int64)]
+
+
+class InferOut(C.Structure):
+    _fields_ = [(n, c_f32p) for n in ("logits", "z", "stats", "score", "attn", "loss")]
+
+
+INFER_MAX = 32               # MHIMX_INFER_MAX
+INFER_MAX_ROWS = 4194304     # MHIMX_INFER_MAX_ROWS
+
 SYMBOLS = {
     "mhimx_last_error": (C.c_char_p, []),
     "mhimx_version": (C.c_int, []),
@@ -331,6 +349,8 @@ SYMBOLS = {
     "mhimx_step_project_ms": (C.c_int, [_P, _P, _I32]),
     "mhimx_window_layout_of": (C.c_int, [C.POINTER(StepCfg), _I32, _I64, C.POINTER(StepCounts), C.POINTER(WindowLayout)]),
     "mhimx_window_run": (C.c_int, [_P, C.POINTER(StepCfg), _I32, _P, _I64, _I64, _P, C.POINTER(StepCounts), C.POINTER(StepSeeds), _I64, _P, _I64, _I32]),   # (labels: void*[n])
+    "mhimx_infer_ws_bytes": (_I64, [C.POINTER(InferCfg), _I32, _P]),
+    "mhimx_infer_run": (C.c_int, [_P, C.POINTER(InferCfg), _I32, _P, _P, C.POINTER(InferOut), _P, _I64]),
     "mhimx_step_run_many": (C.c_int, [_P, C.POINTER(StepCfg), _I32, _P, _P, _P, _P, C.POINTER(StepCounts), C.POINTER(StepSeeds), _I64, _P, _I64]),
 }
 

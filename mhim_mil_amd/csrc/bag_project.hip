@@ -25,6 +25,7 @@
 //   * XCD-aware tile order: the four column tiles of one row tile run on the same XCD (X rows shared through its L2).
 #include <stdlib.h>
 #include "mma_tile.hpp"
+#include "infer_tab.hpp"
 
 namespace mhimx {
 
@@ -469,6 +470,218 @@ __global__ __launch_bounds__(PTHREADS, 2) void bag_project_kernel(mhimx_bag_proj
   if (m_tile == 1 && n_tile == 0 && lane == 0 && (wave == 0 || wave == 4))
     for (int i = 0; i < 8; ++i) H.H[(m0 + wave) * H.ldh + i] = (float)pf[i];
 #endif
+}
+
+// ------------------------------------------------------------------------------------------------------------------------
+// The RAGGED one-model projection of mhimx_infer_run (infer.hip; modules/mhim.py:229-272 forward_test, eval mode): the feature rows of up to
+// MHIMX_INFER_MAX bags of different row counts in one launch.  Row tiles are numbered bag-major from the by-value table (infer_tab.hpp), a
+// bag's last tile is partial; a tile lies inside ONE bag.  The tiling, the LDS image and the k loop are bag_project_kernel's lock-step
+// loop above; what is gone is everything eval mode does not need: the second model, dropout, d out / d pre, residual rows.
+// ------------------------------------------------------------------------------------------------------------------------
+constexpr int IBM = INFER_TILE_ROWS, IBN = 256, IBK = 32, ITHREADS = 512;
+constexpr int IA_BYTES = IBM * 128, IB_BYTES = IBN * 128, ISTAGE = IA_BYTES + IB_BYTES, INST = 3;      // 3 x 52 KiB
+constexpr int ITP = IBN + 4;                                                                          // epilogue tile pitch (floats)
+typedef __bf16 in_bf4 __attribute__((ext_vector_type(4)));
+typedef __bf16 in_bf2 __attribute__((ext_vector_type(2)));
+typedef float in_f2 __attribute__((ext_vector_type(2)));
+
+__global__ __launch_bounds__(ITHREADS, 2) void infer_project_kernel(InferTab tab, int D, const float* __restrict__ w1p,
+                                                                    const float* __restrict__ b1, int act, float* __restrict__ Hout) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wm = wave >> 2, wn = wave & 3;
+  constexpr int nN = IE / IBN;
+  // XCD-aware order: the two column tiles of a row tile run on the same XCD (its X rows are shared through that L2)
+  const int xcd = blockIdx.x & 7, sidx = blockIdx.x >> 3;
+  const int m_tile = (sidx / nN) * 8 + xcd, n_tile = sidx % nN;
+  if (m_tile >= tab.tiles) return;
+  int bag = 0;
+#pragma unroll
+  for (int b = 1; b < MHIMX_INFER_MAX; ++b)
+    if (b < tab.n && m_tile >= tab.tile0[b]) bag = b;
+  const float* X = tab.X[0];
+  int64_t ldx = tab.ldx[0], N = tab.N[0], orow0 = tab.row0[0];
+  int t0 = tab.tile0[0];
+  IT_PICK(X, X, bag) IT_PICK(ldx, ldx, bag) IT_PICK(N, N, bag) IT_PICK(orow0, row0, bag) IT_PICK(t0, tile0, bag)
+  const int64_t m0 = (int64_t)(m_tile - t0) * IBM;             // first row of the tile inside its bag
+  const int64_t n0 = (int64_t)n_tile * IBN;
+  const float* Xt = X + m0 * ldx;                              // uniform: the tile's first row
+
+  // ---- A (raw fp32 rows): two 16-byte units u = tid + 512 j (row u >> 3, slot u & 7; rows 0..127) and one 8-byte unit of rows 128..159
+  unsigned aoff[3];                                           // byte offsets from Xt (< 160 rows)
+  unsigned a_hi[3], a_lo[3];
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+    const int row = j < 2 ? (tid >> 3) + 64 * j : 128 + (tid >> 4);
+    const int slot = j < 2 ? (tid & 7) : ((tid & 15) >> 1);
+    const int sub = j < 2 ? 0 : (tid & 1) * 4;
+    int64_t mr = row;
+    if (m0 + mr >= N) mr = N - 1 - m0;                         // clamped rows feed accumulators that are never stored
+    aoff[j] = (unsigned)((mr * ldx + slot * 4 + (sub >> 1)) * 4);
+    const int sw = mt_swz(row), kg2 = (slot >> 1) * 2;
+    a_hi[j] = (unsigned)(row * 128 + ((kg2 ^ sw) << 4) + (slot & 1) * 8 + sub);
+    a_lo[j] = (unsigned)(row * 128 + (((kg2 + 1) ^ sw) << 4) + (slot & 1) * 8 + sub);
+  }
+  // ---- B (paired weights) by DMA: slot p = tid + 512 j of a [256 rows][8 x 16 B] tile, SOURCE slot swizzled
+  const unsigned boff = (unsigned)(((tid >> 3) * D + ((tid & 7) ^ mt_swz(tid >> 3)) * 4) * 4);
+  const char* bbase = reinterpret_cast<const char*>(w1p + n0 * D);
+  // `live` false (past the last k-step): the same four pieces are issued from ONE address into a stage nobody reads any more, so that every
+  // iteration has the same VMEM count and the hand-written vmcnt waits need no branch
+  auto issue_b = [&](int t, bool live) {
+    char* sb = smem + (t % INST) * ISTAGE + IA_BYTES + wave * 1024;
+    const int64_t k0 = (int64_t)t * IBK;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const char* bj = bbase + ((int64_t)j * 64 * D + k0) * 4;      // uniform
+      __builtin_amdgcn_global_load_lds((gptr_f)(live ? bj + boff : reinterpret_cast<const char*>(Xt)), (lptr_f)(sb + j * 8192), 16, 0, 0);
+    }
+  };
+  // the A loads of the loop are inline asm, waited for by hand (the compiler's wait-count pass would drain the DMA pieces issued behind them)
+  struct ARegs { f32x4 v0, v1; in_f2 v2; };
+  auto load_a_async = [&](int t, ARegs& r) {
+    const float* xk = Xt + (int64_t)t * IBK;                   // uniform: an SGPR pair
+    asm volatile("global_load_dwordx4 %0, %3, %6\n\tglobal_load_dwordx4 %1, %4, %6\n\tglobal_load_dwordx2 %2, %5, %6"
+                 : "=&v"(r.v0), "=&v"(r.v1), "=&v"(r.v2)
+                 : "v"(aoff[0]), "v"(aoff[1]), "v"(aoff[2]), "s"(xk)
+                 : "memory");
+  };
+  auto split4 = [&](const f32x4& v, char* hi_p, char* lo_p) {
+    in_bf4 hi, lo;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const __bf16 h = (__bf16)v[q];
+      hi[q] = h;
+      lo[q] = (__bf16)(v[q] - (float)h);
+    }
+    *reinterpret_cast<in_bf4*>(hi_p) = hi;
+    *reinterpret_cast<in_bf4*>(lo_p) = lo;
+  };
+  auto store_a = [&](int t, const ARegs& r) {                 // registers -> bf16 hi / lo -> the paired row image of stage t % 3
+    char* sa = smem + (t % INST) * ISTAGE;
+    split4(r.v0, sa + a_hi[0], sa + a_lo[0]);
+    split4(r.v1, sa + a_hi[1], sa + a_lo[1]);
+    in_bf2 hi, lo;
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+      const __bf16 h = (__bf16)r.v2[q];
+      hi[q] = h;
+      lo[q] = (__bf16)(r.v2[q] - (float)h);
+    }
+    *reinterpret_cast<in_bf2*>(sa + a_hi[2]) = hi;
+    *reinterpret_cast<in_bf2*>(sa + a_lo[2]) = lo;
+  };
+
+  // fragment addresses (stage 0): row r = lane & 15 of a 16-row block, k-group kg = lane >> 4 -> slots 2kg (hi), 2kg+1 (lo)
+  const int r16 = lane & 15, kg = lane >> 4;
+  const unsigned lds0 = (unsigned)(uintptr_t)(lptr_f)smem;
+  const int ra = wm * 80 + r16, rb = wn * 64 + r16;
+  const unsigned fa_hi = lds0 + ra * 128 + (((2 * kg) ^ mt_swz(ra)) << 4);
+  const unsigned fa_lo = lds0 + ra * 128 + (((2 * kg + 1) ^ mt_swz(ra)) << 4);
+  const unsigned fb_hi = lds0 + IA_BYTES + rb * 128 + (((2 * kg) ^ mt_swz(rb)) << 4);
+  const unsigned fb_lo = lds0 + IA_BYTES + rb * 128 + (((2 * kg + 1) ^ mt_swz(rb)) << 4);
+
+  f32x4 acc[NRA][NRB];
+#pragma unroll
+  for (int i = 0; i < NRA; ++i)
+#pragma unroll
+    for (int j = 0; j < NRB; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  const int nk = D / IBK;
+  ARegs rga, rgb;
+  // prologue: B(0), B(1) in flight, A(0) -> stage 0 (the compiler's wait in front of the conversion drains all three), A(1) in flight
+  issue_b(0, true);
+  issue_b(1, nk > 1);
+  {
+    ARegs r0;
+    const char* xb = reinterpret_cast<const char*>(Xt);
+    r0.v0 = *reinterpret_cast<const f32x4*>(xb + aoff[0]);
+    r0.v1 = *reinterpret_cast<const f32x4*>(xb + aoff[1]);
+    r0.v2 = *reinterpret_cast<const in_f2*>(xb + aoff[2]);
+    store_a(0, r0);
+  }
+  load_a_async(nk > 1 ? 1 : 0, rga);
+
+  // Iteration t (3-stage ring):  [barrier: tile t complete in stage t % 3]
+  //   reads g1(t) = {A lo, B hi};  A(t+2) loads -> the free register set;  B(t+2) DMA -> stage (t+2) % 3 (= (t-1) % 3: every wave is past its
+  //   reads);  20 MFMAs hi*lo of tile t-1 (operands still in registers);  reads g2(t) = {A hi, B lo};  20 MFMAs lo*hi of tile t;  wait until
+  //   only this iteration's 7 VMEM operations are in flight (A(t+1) is in its registers, B(t+1) has landed);  20 MFMAs hi*hi of tile t with
+  //   the split of A(t+1) and its LDS stores into stage (t+1) % 3 in their shadow.
+  f32x4 x[NFR];
+  auto body = [&](int t, ARegs& r_load, ARegs& r_use) {
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");        // my A(t) stores to LDS are done
+    __builtin_amdgcn_s_barrier();
+    const unsigned so = (unsigned)((t % INST) * ISTAGE);
+    MT_READ9(x, 5, 10, fa_lo + so, fb_hi + so);
+    load_a_async(t + 2 < nk ? t + 2 : nk - 1, r_load);
+    issue_b(t + 2, t + 2 < nk);
+    __builtin_amdgcn_sched_barrier(0);
+    if (t > 0) mt_term(x, 0, 14, acc);                        // hi*lo of tile t-1
+    __builtin_amdgcn_sched_barrier(0);
+    MT_WAIT9(0, x, 5, 10);
+    MT_READ9(x, 0, 14, fa_hi + so, fb_lo + so);
+    __builtin_amdgcn_sched_barrier(0);
+    mt_term(x, 5, 10, acc);                                   // lo*hi
+    __builtin_amdgcn_sched_barrier(0);
+    MT_WAIT9(0, x, 0, 14);
+    asm volatile("s_waitcnt vmcnt(7)" : "+v"(r_use.v0), "+v"(r_use.v1), "+v"(r_use.v2) : : "memory");
+    __builtin_amdgcn_sched_barrier(0);
+    mt_term(x, 0, 10, acc);                                   // hi*hi
+    if (t + 1 < nk) store_a(t + 1, r_use);
+#pragma unroll
+    for (int q = 0; q < 20; ++q) {
+      __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);      // one MFMA
+      __builtin_amdgcn_sched_group_barrier(0x002, 3, 0);      // three VALU
+      if (q % 3 == 2) __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);   // a DS write
+    }
+  };
+  int t = 0;
+#pragma unroll 1
+  for (; t + 1 < nk; t += 2) {
+    body(t, rgb, rga);
+    body(t + 1, rga, rgb);
+  }
+  if (t < nk) body(t, rgb, rga);
+  mt_term(x, 0, 14, acc);                                     // hi*lo of the last tile
+  asm volatile("s_waitcnt vmcnt(0)" : "+v"(rga.v0), "+v"(rga.v1), "+v"(rga.v2), "+v"(rgb.v0), "+v"(rgb.v1), "+v"(rgb.v2) : : "memory");
+
+  // ---- epilogue, two 80-row halves through LDS (the ring is free): bias, activation, 1 KiB row stores
+  float* tile = reinterpret_cast<float*>(smem);
+  const int c4 = (tid & 63) * 4, r0 = tid >> 6;               // this thread's 4 columns are fixed
+  const int64_t n = n0 + c4;
+  const f32x4 bias = b1 ? *reinterpret_cast<const f32x4*>(b1 + n) : f32x4{0.f, 0.f, 0.f, 0.f};
+  float* Hb = Hout + (orow0 + m0) * IE + n;
+  const int64_t rows_left = N - m0;
+#pragma unroll 1
+  for (int half = 0; half < 2; ++half) {
+    __syncthreads();                                          // fragment reads / the previous half's tile reads are over
+    if (wm == half) {
+      const int cl = lane & 15, rq = lane >> 4;
+#pragma unroll
+      for (int i = 0; i < NRA; ++i)
+#pragma unroll
+        for (int j = 0; j < NRB; ++j)
+#pragma unroll
+          for (int e = 0; e < 4; ++e) tile[(i * 16 + rq * 4 + e) * ITP + wn * 64 + j * 16 + cl] = acc[i][j][e];
+    }
+    __syncthreads();
+    for (int r = r0; r < 80; r += 8) {
+      const int m = half * 80 + r;
+      if (m >= rows_left) break;
+      const f32x4 a = *reinterpret_cast<const f32x4*>(tile + r * ITP + c4);
+      f32x4 v;
+#pragma unroll
+      for (int q = 0; q < 4; ++q) v[q] = act_fwd(a[q] + bias[q], act);
+      *reinterpret_cast<f32x4*>(Hb + (int64_t)m * IE) = v;
+    }
+  }
+}
+
+int infer_project(hipStream_t st, const InferTab& tab, int D, const float* w1p, const float* b1, int act, float* Hout) {
+  MHIMX_ONCE_PER_DEVICE(MHIMX_HIP(hipFuncSetAttribute((const void*)infer_project_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, INST * ISTAGE)));
+  hipLaunchKernelGGL(infer_project_kernel, dim3((unsigned)(8 * (IE / IBN) * cdiv(tab.tiles, 8))), dim3(ITHREADS), INST * ISTAGE, st, tab, D, w1p, b1,
+                     act, Hout);
+  MHIMX_LAUNCH_CHECK();
+  return 0;
 }
 
 int bag_project_ws(hipStream_t st, const mhimx_bag_project_args* bags, int n_bags);       // bag_project_ws.hip

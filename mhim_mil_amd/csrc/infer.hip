@@ -1,0 +1,352 @@
+// infer.hip — eval-mode MHIM(ABMIL) forward of up to MHIMX_INFER_MAX bags of DIFFERENT row counts in one call
+// (modules/mhim.py:229-272 forward_test with merge_test off, engines/common_mil.py:56-68, engines/base_engine.py:234-329):
+//
+//     h = act(X W1^T + b1),  s = wc . da_act(h Wa^T),  z = softmax(s) h,  logits = z Wp^T + bp,  loss = CE(logits, label)
+//
+// The library's first RAGGED launches.  Everything a kernel needs to know about a bag travels in one by-value table (InferTab: pointer,
+// pitch, rows, first row tile, first pool partial, row offset), so the call copies nothing to the device, waits for nothing and allocates
+// nothing: it can be captured in a graph.  Four launches whatever n_bags is:
+//   1  mhimx_prep_batch        the paired-plane image of W1 and the matrix-core fragment image of Wa (weights change between epochs)
+//   2  infer_project_kernel    (bag_project.hip, beside the kernel it is modelled on) 160 x 256 output tiles, row tiles numbered
+//                              bag-major, a bag's last tile partial; 3-term bf16, ONE model, no dropout / d out / d pre: feature rows -> ws
+//   3  infer_score_kernel      one workgroup per CHUNK of 256 rows of one bag: 32-row tiles through LDS, U = h Wa^T on the matrix
+//                              cores (3-term bf16), scores, the running log-sum-exp pool partial (max, sum, sum_r e^{s_r - max} h_r)
+//   4  infer_finalize_kernel   plane x = bag: block y = 0 merges the bag's partials in index order -> stats, z, logits, loss;
+//                              blocks y > 0 write the attention map from the same merged {max, sum}
+// No workgroup waits for another: tiles and chunks are independent, merging is the next launch's work.  A bag's tiles, chunks and
+// partial order depend on its own N alone, so its results have the same bits wherever it stands in a call.
+#include <math.h>
+
+#include "infer_tab.hpp"
+
+namespace mhimx {
+
+namespace {
+
+constexpr int IA = 128;
+constexpr int SC_ROWS = 32, SC_TILES = 8, SC_CHUNK = SC_ROWS * SC_TILES, SC_LD = IE + 4, SC_THREADS = 256;
+constexpr size_t SC_SMEM = (size_t)(SC_ROWS * SC_LD + 4 * SC_ROWS + 2 * SC_ROWS) * sizeof(float);
+constexpr int FIN_T = 512, FIN_ATTN_BLOCKS = 8, FIN_MAXC = 16;
+
+typedef __bf16 in_b8 __attribute__((ext_vector_type(8)));
+typedef float in_f16 __attribute__((ext_vector_type(16)));
+
+// ------------------------------------------------------------------------------------------------ 3. ragged scorer + pool partial
+MHIMX_DEV void sc_split(const f32x4& a, const f32x4& b, in_b8& hi, in_b8& lo) {
+  const float x[8] = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    const __bf16 h = (__bf16)x[i];
+    hi[i] = h;
+    lo[i] = (__bf16)(x[i] - (float)h);
+  }
+}
+// sum over the 32 lanes that share (lane >> 5); valid in lanes 16..31 and 48..63
+MHIMX_DEV float sc_sum32(float v) {
+  v += dpp_mov<0xB1, 0xf>(0.f, v);
+  v += dpp_mov<0x4E, 0xf>(0.f, v);
+  v += dpp_mov<0x141, 0xf>(0.f, v);
+  v += dpp_mov<0x140, 0xf>(0.f, v);
+  v += dpp_mov<0x142, 0xa>(0.f, v);
+  return v;
+}
+
+// blockIdx.x = pool partial = chunk of SC_CHUNK rows of ONE bag (the last chunk of a bag may be short).  Wave w owns scorer columns
+// [32 w, 32 w + 32): v_mfma_f32_32x32x16_bf16, A = the tile's rows from LDS split on the fly, B = the prep kind-4 image of Wa.
+__global__ __launch_bounds__(SC_THREADS, 2) void infer_score_kernel(InferTab tab, const float* __restrict__ Hin,
+                                                                    const float* __restrict__ wa_frag, const float* __restrict__ wc,
+                                                                    int act, float* __restrict__ s_out, float* __restrict__ pm,
+                                                                    float* __restrict__ pl, float* __restrict__ pz) {
+  extern __shared__ __attribute__((aligned(16))) float sc_sm[];
+  float* Hs = sc_sm;                          // [32][516]
+  float* sred = Hs + SC_ROWS * SC_LD;         // [4][32] per-wave partial scores
+  float* srow = sred + 4 * SC_ROWS;           // [32] scores
+  float* prow = srow + SC_ROWS;               // [32] e^{s - m}
+  const int part = blockIdx.x;
+  int bag = 0;
+#pragma unroll
+  for (int b = 1; b < MHIMX_INFER_MAX; ++b)
+    if (b < tab.n && part >= tab.part0[b]) bag = b;
+  int64_t N = tab.N[0], orow0 = tab.row0[0];
+  int p0 = tab.part0[0];
+  IT_PICK(N, N, bag) IT_PICK(orow0, row0, bag) IT_PICK(p0, part0, bag)
+  const int64_t c0 = (int64_t)(part - p0) * SC_CHUNK;           // first row of the chunk inside its bag
+  const int64_t M = (N - c0 < SC_CHUNK) ? N - c0 : SC_CHUNK;    // rows of the chunk (>= 1)
+  const float* T = Hin + (orow0 + c0) * IE;
+  float* so = s_out + orow0 + c0;
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int r32 = lane & 31, kg = lane >> 5;
+  const int n_col = 32 * wave + r32;
+  const float wn = wc[n_col];
+  const f32x4* fptr = reinterpret_cast<const f32x4*>(wa_frag + ((int64_t)wave * (IE / 16) * 64 + lane) * 8);   // + ks * 128 (hi), + 1 (lo)
+  const float* aptr = Hs + r32 * SC_LD + 8 * kg;
+
+  float m_run = -INFINITY, l_run = 0.f, z0 = 0.f, z1 = 0.f;
+  const int tiles = (int)((M + SC_ROWS - 1) / SC_ROWS);
+  for (int tile = 0; tile < tiles; ++tile) {
+    const int64_t row0 = (int64_t)tile * SC_ROWS;
+    // ---- rows -> LDS (rows past the chunk: zeros; their loads are clamped so that all 16 are in flight)
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+      const int f = tid + SC_THREADS * i, r = f >> 7, c4 = f & 127;
+      const int64_t nr = row0 + r;
+      f32x4 v = reinterpret_cast<const f32x4*>(T + (nr < M ? nr : M - 1) * IE)[c4];
+      if (nr >= M) v = f32x4{0.f, 0.f, 0.f, 0.f};
+      *reinterpret_cast<f32x4*>(Hs + r * SC_LD + 4 * c4) = v;
+    }
+    __syncthreads();
+    // ---- U tile on the matrix cores, one accumulator per bf16x3 term
+    in_f16 acc, acc2, acc3;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) { acc[i] = 0.f; acc2[i] = 0.f; acc3[i] = 0.f; }
+    {
+      f32x4 bh = fptr[0], bl = fptr[1];
+#pragma unroll 4
+      for (int ks = 0; ks < IE / 16; ++ks) {
+        const int kn = ks + 1 < IE / 16 ? ks + 1 : ks;
+        const f32x4 nbh = fptr[128 * kn], nbl = fptr[128 * kn + 1];
+        const f32x4 a0 = *reinterpret_cast<const f32x4*>(aptr + 16 * ks), a1 = *reinterpret_cast<const f32x4*>(aptr + 16 * ks + 4);
+        in_b8 ah, al;
+        sc_split(a0, a1, ah, al);
+        const in_b8 bh8 = __builtin_bit_cast(in_b8, bh), bl8 = __builtin_bit_cast(in_b8, bl);
+        acc2 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh8, acc2, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh8, acc, 0, 0, 0);
+        acc3 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl8, acc3, 0, 0, 0);
+        bh = nbh;
+        bl = nbl;
+      }
+    }
+    // ---- scores: acc[i] = U[row = 8 (i >> 2) + 4 kg + (i & 3)][n_col]
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+      const int row = 8 * (i >> 2) + 4 * kg + (i & 3);
+      const float u = acc[i] + (acc2[i] + acc3[i]);
+      const float v = sc_sum32(wn * act_fwd(u, act));
+      if (r32 == 31) sred[wave * SC_ROWS + row] = v;
+    }
+    __syncthreads();
+    if (tid < SC_ROWS) {
+      const int64_t nr = row0 + tid;
+      float s = (sred[tid] + sred[SC_ROWS + tid]) + (sred[2 * SC_ROWS + tid] + sred[3 * SC_ROWS + tid]);
+      if (nr >= M) s = -INFINITY;
+      else so[nr] = s;
+      srow[tid] = s;
+    }
+    __syncthreads();
+    // ---- log-sum-exp partial, running over the chunk's tiles (row 0 of every tile is a real row: the tile maximum is finite)
+    float mt = -INFINITY;
+#pragma unroll
+    for (int q = 0; q < SC_ROWS / 4; ++q) {
+      const f32x4 v = reinterpret_cast<const f32x4*>(srow)[q];
+      mt = fmaxf(fmaxf(mt, fmaxf(v[0], v[1])), fmaxf(v[2], v[3]));
+    }
+    const float m_new = fmaxf(m_run, mt);
+    const float scale = (m_run == -INFINITY) ? 0.f : __expf(m_run - m_new);
+    if (tid < SC_ROWS) prow[tid] = srow[tid] == -INFINITY ? 0.f : __expf(srow[tid] - m_new);
+    __syncthreads();
+    float lsum = 0.f, a0 = 0.f, a1 = 0.f;
+#pragma unroll
+    for (int q = 0; q < SC_ROWS / 4; ++q) {
+      const f32x4 p = reinterpret_cast<const f32x4*>(prow)[q];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const float* hr = Hs + (4 * q + j) * SC_LD;
+        lsum += p[j];
+        a0 += p[j] * hr[tid];
+        a1 += p[j] * hr[tid + SC_THREADS];
+      }
+    }
+    l_run = l_run * scale + lsum;
+    z0 = z0 * scale + a0;
+    z1 = z1 * scale + a1;
+    m_run = m_new;
+    __syncthreads();                           // the next tile overwrites Hs / srow
+  }
+  if (tid == 0) { pm[part] = m_run; pl[part] = l_run; }
+  pz[(int64_t)part * IE + tid] = z0;
+  pz[(int64_t)part * IE + tid + SC_THREADS] = z1;
+}
+
+// ------------------------------------------------------------------------------------------------ 4. merge + head + loss + attention
+// blockIdx.x = bag.  Every block of a bag derives {max, sum} from the bag's partials in the same fixed order.  blockIdx.y = 0: the pooled
+// row (thread e = column e, partials in index order), the predictor in fp32, the cross entropy.  blockIdx.y > 0: the attention map.
+__global__ __launch_bounds__(FIN_T) void infer_finalize_kernel(InferTab tab, const float* __restrict__ pm, const float* __restrict__ pl,
+                                                               const float* __restrict__ pz, const float* __restrict__ s,
+                                                               const float* __restrict__ wp, const float* __restrict__ bp, int C,
+                                                               const int64_t* __restrict__ labels, float* __restrict__ logits,
+                                                               float* __restrict__ z_out, float* __restrict__ stats,
+                                                               float* __restrict__ attn, float* __restrict__ loss) {
+  __shared__ float red[8];
+  __shared__ float wgt[FIN_T];
+  __shared__ float zs[IE];
+  __shared__ float lg[FIN_MAXC];
+  const int bag = blockIdx.x;
+  int64_t N = tab.N[0], orow0 = tab.row0[0];
+  int p0 = tab.part0[0];
+  IT_PICK(N, N, bag) IT_PICK(orow0, row0, bag) IT_PICK(p0, part0, bag)
+  const int G = (int)((N + SC_CHUNK - 1) / SC_CHUNK);
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  pm += p0; pl += p0; pz += (int64_t)p0 * IE;
+  float m = -INFINITY;
+  for (int b = tid; b < G; b += FIN_T) m = fmaxf(m, pm[b]);
+  m = wave_max(m);
+  if (lane == 0) red[wave] = m;
+  __syncthreads();
+  float mx = red[0];
+#pragma unroll
+  for (int w = 1; w < 8; ++w) mx = fmaxf(mx, red[w]);
+  __syncthreads();
+  float lp = 0.f;
+  for (int b = tid; b < G; b += FIN_T) lp += pl[b] * __expf(pm[b] - mx);
+  lp = wave_sum(lp);
+  if (lane == 0) red[wave] = lp;
+  __syncthreads();
+  float L = 0.f;
+#pragma unroll
+  for (int w = 0; w < 8; ++w) L += red[w];                    // fixed order: deterministic
+  const float invL = 1.f / L;
+  if (blockIdx.y > 0) {
+    if (attn) {
+      const float* sb = s + orow0;
+      float* ab = attn + orow0;
+      const int64_t step = (int64_t)(gridDim.y - 1) * FIN_T;
+      for (int64_t r = (int64_t)(blockIdx.y - 1) * FIN_T + tid; r < N; r += step) ab[r] = __expf(sb[r] - mx) * invL;
+    }
+    return;
+  }
+  if (tid == 0) { stats[2 * bag] = mx; stats[2 * bag + 1] = L; }
+  float acc = 0.f;                                            // column tid of the pooled row
+  for (int base = 0; base < G; base += FIN_T) {
+    __syncthreads();
+    wgt[tid] = base + tid < G ? __expf(pm[base + tid] - mx) : 0.f;
+    __syncthreads();
+    const int cnt = G - base < FIN_T ? G - base : FIN_T;
+#pragma unroll 8
+    for (int j = 0; j < cnt; ++j) acc += pz[(int64_t)(base + j) * IE + tid] * wgt[j];
+  }
+  const float zv = acc * invL;
+  zs[tid] = zv;
+  if (z_out) z_out[(int64_t)bag * IE + tid] = zv;
+  __syncthreads();
+  for (int c = wave; c < C; c += FIN_T / 64) {
+    float d = 0.f;
+#pragma unroll
+    for (int q = 0; q < IE / 64; ++q) d += zs[lane + 64 * q] * wp[(int64_t)c * IE + lane + 64 * q];
+    d = wave_sum(d);
+    if (lane == 0) {
+      const float v = d + (bp ? bp[c] : 0.f);
+      lg[c] = v;
+      logits[(int64_t)bag * C + c] = v;
+    }
+  }
+  if (!loss) return;
+  __syncthreads();
+  if (tid == 0) {
+    // torch.nn.CrossEntropyLoss on one row: log sum_c e^{x_c} - x_label (a label outside [0, C): NaN, where torch raises)
+    float cm = lg[0];
+    for (int c = 1; c < C; ++c) cm = fmaxf(cm, lg[c]);
+    float den = 0.f;
+    for (int c = 0; c < C; ++c) den += expf(lg[c] - cm);
+    const int64_t y = labels[bag];
+    loss[bag] = (y >= 0 && y < C) ? (cm + logf(den)) - lg[y] : NAN;
+  }
+}
+
+// ------------------------------------------------------------------------------------------------ host
+struct InferWs { int64_t w1p, wa_frag, H, s, pm, pl, pz, total; };
+
+int check_infer(const mhimx_infer_cfg* c, int32_t n_bags, const mhimx_infer_bag* bags) {
+  MHIMX_CHECK_ARG(c && bags, "infer: null configuration / bag list");
+  MHIMX_CHECK_ARG(n_bags >= 1 && n_bags <= MHIMX_INFER_MAX, "infer: 1..%d bags per call", MHIMX_INFER_MAX);
+  MHIMX_CHECK_ARG(c->E == IE && c->A == IA && c->C >= 1 && c->C <= FIN_MAXC && c->D > 0 && c->D % 256 == 0 && c->D <= (1 << 20),
+                  "infer: shapes outside the ragged ABMIL forward (E = 512, A = 128, 1 <= C <= %d, D %% 256 == 0)", FIN_MAXC);
+  MHIMX_CHECK_ARG(c->act >= MHIMX_ACT_NONE && c->act <= MHIMX_ACT_TANH && c->da_act >= MHIMX_ACT_NONE && c->da_act <= MHIMX_ACT_TANH,
+                  "infer: unknown activation");
+  int64_t rows = 0;
+  for (int b = 0; b < n_bags; ++b) {
+    const mhimx_infer_bag& g = bags[b];
+    MHIMX_CHECK_ARG(g.N >= 1 && g.N <= MHIMX_INFER_MAX_ROWS, "infer: bag %d: N must be in 1..%d", b, MHIMX_INFER_MAX_ROWS);
+    MHIMX_CHECK_ARG(g.ldx >= c->D && g.ldx % 4 == 0 && g.ldx <= (1 << 20), "infer: bag %d: row pitch below D or not a multiple of 4 floats", b);
+    rows += g.N;
+  }
+  MHIMX_CHECK_ARG(rows <= MHIMX_INFER_MAX_ROWS, "infer: more than %d rows in one call", MHIMX_INFER_MAX_ROWS);
+  return 0;
+}
+
+void infer_layout(const mhimx_infer_cfg* c, int32_t n_bags, const mhimx_infer_bag* bags, InferWs* w, InferTab* tab) {
+  int64_t rows = 0, tiles = 0, parts = 0;
+  for (int b = 0; b < n_bags; ++b) {
+    if (tab) {
+      tab->X[b] = bags[b].X; tab->ldx[b] = bags[b].ldx; tab->N[b] = bags[b].N;
+      tab->row0[b] = rows; tab->tile0[b] = (int32_t)tiles; tab->part0[b] = (int32_t)parts;
+    }
+    rows += bags[b].N;
+    tiles += cdiv(bags[b].N, INFER_TILE_ROWS);
+    parts += cdiv(bags[b].N, SC_CHUNK);
+  }
+  if (tab) { tab->n = n_bags; tab->tiles = (int32_t)tiles; tab->parts = (int32_t)parts; }
+  Arena ar(nullptr, 0);
+  w->w1p = ar.off; ar.take<float>(c->E * c->D);
+  w->wa_frag = ar.off; ar.take<float>(c->A * c->E);
+  w->H = ar.off; ar.take<float>(rows * c->E);
+  w->s = ar.off; ar.take<float>(rows);
+  w->pm = ar.off; ar.take<float>(parts);
+  w->pl = ar.off; ar.take<float>(parts);
+  w->pz = ar.off; ar.take<float>(parts * c->E);
+  w->total = ar.off;
+}
+
+}  // namespace
+
+}  // namespace mhimx
+
+extern "C" int64_t mhimx_infer_ws_bytes(const mhimx_infer_cfg* cfg, int32_t n_bags, const mhimx_infer_bag* bags) {
+  using namespace mhimx;
+  if (int r = check_infer(cfg, n_bags, bags)) return r;
+  InferWs w;
+  infer_layout(cfg, n_bags, bags, &w, nullptr);
+  return w.total;
+}
+
+extern "C" int mhimx_infer_run(void* stream, const mhimx_infer_cfg* cfg, int32_t n_bags, const mhimx_infer_bag* bags,
+                               const int64_t* labels_dev, const mhimx_infer_out* out, void* ws, int64_t ws_bytes) {
+  using namespace mhimx;
+  if (int r = check_infer(cfg, n_bags, bags)) return r;
+  const mhimx_step_params& P = cfg->p;
+  MHIMX_CHECK_ARG(P.w1 && P.b1 && P.wa && P.wc && P.wp && P.bp, "infer: null parameter");
+  MHIMX_CHECK_ARG(aligned16(P.w1) && aligned16(P.b1) && aligned16(P.wa), "infer: feature / scorer weights must be 16-byte aligned");
+  for (int b = 0; b < n_bags; ++b) MHIMX_CHECK_ARG(bags[b].X && aligned16(bags[b].X), "infer: bag %d: null or unaligned rows", b);
+  MHIMX_CHECK_ARG(out && out->logits && out->stats, "infer: logits and stats outputs are required");
+  MHIMX_CHECK_ARG(!out->loss || labels_dev, "infer: the loss output needs labels");
+  InferWs w;
+  InferTab tab = {};
+  infer_layout(cfg, n_bags, bags, &w, &tab);
+  MHIMX_CHECK_ARG(ws && (reinterpret_cast<uintptr_t>(ws) & 255) == 0, "infer: the workspace must be 256-byte aligned");
+  MHIMX_CHECK_ARG(ws_bytes >= w.total, "infer: workspace too small (%lld bytes, need %lld)", (long long)ws_bytes, (long long)w.total);
+  hipStream_t st = (hipStream_t)stream;
+  char* base = static_cast<char*>(ws);
+  float* w1p = reinterpret_cast<float*>(base + w.w1p);
+  float* wa_frag = reinterpret_cast<float*>(base + w.wa_frag);
+  float* H = reinterpret_cast<float*>(base + w.H);
+  float* s = out->score ? out->score : reinterpret_cast<float*>(base + w.s);
+  float* pm = reinterpret_cast<float*>(base + w.pm);
+  float* pl = reinterpret_cast<float*>(base + w.pl);
+  float* pz = reinterpret_cast<float*>(base + w.pz);
+  const int D = (int)cfg->D, C = (int)cfg->C;
+
+  // 1. weight images
+  mhimx_prep_job jobs[2] = {mhimx_prep_job{1, P.w1, w1p, cfg->E, cfg->D}, mhimx_prep_job{4, P.wa, wa_frag, cfg->A, cfg->E}};
+  if (int r = mhimx_prep_batch(stream, jobs, 2)) return r;
+  // 2. feature rows of every bag (bag_project.hip)
+  if (int r = infer_project(st, tab, D, w1p, P.b1, cfg->act, H)) return r;
+  // 3. scores + pool partials
+  MHIMX_ONCE_PER_DEVICE(MHIMX_HIP(hipFuncSetAttribute((const void*)infer_score_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SC_SMEM)));
+  hipLaunchKernelGGL(infer_score_kernel, dim3((unsigned)tab.parts), dim3(SC_THREADS), SC_SMEM, st, tab, H, wa_frag, P.wc, cfg->da_act, s, pm, pl, pz);
+  MHIMX_LAUNCH_CHECK();
+  // 4. merge, head, loss, attention
+  hipLaunchKernelGGL(infer_finalize_kernel, dim3((unsigned)n_bags, out->attn ? 1 + FIN_ATTN_BLOCKS : 1), dim3(FIN_T), 0, st, tab, pm, pl, pz, s, P.wp,
+                     P.bp, C, labels_dev, out->logits, out->z, out->stats, out->attn, out->loss);
+  MHIMX_LAUNCH_CHECK();
+  return 0;
+}

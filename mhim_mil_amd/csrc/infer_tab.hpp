@@ -1,0 +1,28 @@
+// infer_tab.hpp — the per-bag table of the ragged inference launches (mhimx_infer_run: infer.hip; its projection kernel: bag_project.hip).
+#pragma once
+#include "mma_tile.hpp"
+
+namespace mhimx {
+
+// Everything a kernel needs to know about a bag, as ONE by-value kernel argument: no host-to-device copy, nothing to wait for.
+struct InferTab {
+  const float* X[MHIMX_INFER_MAX];
+  int64_t ldx[MHIMX_INFER_MAX], N[MHIMX_INFER_MAX];
+  int64_t row0[MHIMX_INFER_MAX];                  // first row of the bag in the call's row space (feature rows, score, attn)
+  int32_t tile0[MHIMX_INFER_MAX];                 // first 160-row projection tile
+  int32_t part0[MHIMX_INFER_MAX];                 // first pool partial (= first 256-row scorer chunk)
+  int32_t n, tiles, parts, pad;
+};
+// (constant indices only: a dynamically indexed by-value argument is copied to scratch)
+#define IT_PICK(dst, field, b)                                   \
+  _Pragma("unroll") for (int q_ = 0; q_ < MHIMX_INFER_MAX; ++q_) \
+    if (q_ == (b)) dst = tab.field[q_];
+
+
+constexpr int INFER_TILE_ROWS = 160;              // rows of a projection tile (bag-major tile numbering: InferTab.tile0)
+constexpr int IE = 512;                           // feature width of the ragged path
+
+// the ragged one-model projection launch (bag_project.hip): Hout[row0[b] + m, :] = act(X_b[m, :] W1^T + b1) for every bag b of the table
+int infer_project(hipStream_t st, const InferTab& tab, int D, const float* w1p, const float* b1, int act, float* Hout);
+
+}  // namespace mhimx

@@ -107,6 +107,23 @@ class CommonMIL:
         return logits, label
 
 
+    def validate_many(self, args, model, bags, labels, criterion=None):
+        """validate_func for a LIST of bags -> (logits [n, C], per-bag cross entropy [n] | None).  The MHIM(ABMIL) models go through
+        MHIM.infer_many (one C call per chunk of bags where the model qualifies, the forward_test loop where it does not); the loss comes
+        back only for a plain CrossEntropyLoss - any other criterion is the caller's to apply to the logits."""
+        if args.model not in ("mhim", "mhim_pure"):
+            raise NotImplementedError(f"model {args.model!r} is outside the MHIM hot path")
+        if getattr(args, "baseline", "attn") == "dsmil" or not hasattr(model, "infer_many"):
+            rows = [self.validate_func(args, model=model, bag=b, label=labels[j:j + 1], criterion=criterion, batch_size=1, i=j, pos=None)[0]
+                    for j, b in enumerate(bags)]
+            return torch.cat([r.reshape(1, -1) for r in rows]), None
+        plain = (type(criterion) is torch.nn.CrossEntropyLoss and criterion.weight is None and criterion.label_smoothing == 0.0
+                 and criterion.reduction == "mean" and criterion.ignore_index < 0)
+        if plain:
+            return model.infer_many(bags, labels=labels)
+        return model.infer_many(bags), None
+
+
 def cosine_scheduler(base_value, final_value, epochs, niter_per_ep, warmup_epochs=0, start_warmup_value=0):
     """The reference's per-iteration cosine schedule (utils.py:199-210): used for `mm_sche` (EMA momentum mm -> 1,
     modules/__init__.py:177-181) and `mrh_sche` (HAM ratio mask_ratio_h -> 0, modules/__init__.py:72-75)."""

@@ -9,6 +9,7 @@ Same constructor arguments, same methods and return conventions, same state_dict
     MHIM.forward          (mhim.py:318-378) forward          -> (logit [1,C], cls_loss, ps, len_keep)
     MHIM.forward_test     (mhim.py:229-272) forward_test     -> logits | (logits, attn)
     MHIM.pure             (mhim.py:274-298) pure             -> (logits, 0, ps, ps) | logits
+    MHIM.infer_many       (forward_test over a LIST of bags of different sizes: mhimx_infer_run, one C call per chunk) -> logits [n,C], ..
 
 All math runs in libmhimx.so (hand-written gfx950 kernels behind the C-ABI); torch only owns
 parameters, device memory, the stream and autograd's graph bookkeeping.  There is no eager/CPU
@@ -924,6 +925,112 @@ class MHIM(nn.Module):
             act = H if T2 is None else torch.cat([H, T2], 0)
             return logits, [a, act]
         return logits, a
+
+    # ------------------------------------------------------------------ ragged multi-bag inference (csrc/infer.hip)
+    infer_row_cap = 262144     # rows of one mhimx_infer_run: its workspace holds the chunk's feature rows, 2 KiB each - 512 MiB at this cap
+                               # (a bag longer than the cap goes alone and the workspace grows to it).  Larger chunks are faster, not slower:
+                               # tools/exp_infer.py --row-cap, 64 bags / 386 276 rows: 65 536 -> 2.46 ms, 131 072 -> 2.14, uncapped -> 2.03
+
+    def _infer_bags(self, xs):
+        out = []
+        for x in xs:
+            if not x.is_cuda:
+                raise L.MhimxError("MHIM (mhimx): input bag must be a CUDA tensor; there is no CPU path")
+            if x.dim() == 3:
+                if x.shape[0] != 1:
+                    raise L.MhimxError("MHIM.infer_many: every list entry is ONE bag ([N, D] or [1, N, D])")
+                x = x[0]
+            if x.dtype != torch.float32:
+                x = x.float()
+            if x.stride(1) != 1:
+                x = x.contiguous()
+            out.append(x)
+        return out
+
+    def _infer_ok(self, xs):
+        """True when mhimx_infer_run takes these bags (csrc/infer.hip: check_infer and the call's own argument checks, mirrored: what they
+        would refuse takes the forward_test loop instead of raising)."""
+        if (self.training or self.baseline != "attn" or self.online_encoder.gated or self.merge_test or self._op_prec == "f32"
+                or ops.KERNEL_EVENT_HOOK is not None):
+            return False
+        att = self.online_encoder.attention.attention
+        if not (self.mlp_dim == 512 and att[0].weight.shape[0] == 128 and 1 <= self.n_classes <= 16 and self.input_dim % 256 == 0
+                and self.input_dim <= (1 << 20)):
+            return False
+        dev = self.feature[0].weight.device
+        ps = (self.feature[0].weight, self.feature[0].bias, att[0].weight, att[2].weight, self.predictor.weight, self.predictor.bias)
+        if any(not t.is_contiguous() or t.dtype != torch.float32 or t.device != dev for t in ps) or any(t.data_ptr() % 16 for t in ps[:3]):
+            return False
+        return all(x.dim() == 2 and x.shape[1] == self.input_dim and 1 <= x.shape[0] <= L.INFER_MAX_ROWS and x.device == dev
+                   and x.data_ptr() % 16 == 0 and x.stride(0) % 4 == 0 and self.input_dim <= x.stride(0) <= (1 << 20) for x in xs)
+
+    def _infer_cfg(self):
+        att = self.online_encoder.attention.attention
+        f, pr = self.feature[0], self.predictor
+        return L.InferCfg(D=self.input_dim, E=self.mlp_dim, A=att[0].weight.shape[0], C=self.n_classes,
+                          act=L.act_code(self.act, _FEATURE_ACTS), da_act=L.act_code(self.da_act, _SCORER_ACTS),
+                          p=ops.infer_params(f.weight.data, f.bias.data, att[0].weight.data, att[2].weight.data, pr.weight.data, pr.bias.data))
+
+    def infer_chunks(self, xs):
+        """Index ranges of the calls ``infer_many`` makes: at most L.INFER_MAX bags and ``infer_row_cap`` rows each (one bag at least)."""
+        chunks, lo, rows = [], 0, 0
+        for j, x in enumerate(xs):
+            n = int(x.shape[0])
+            if j > lo and (j - lo >= L.INFER_MAX or rows + n > self.infer_row_cap):
+                chunks.append((lo, j))
+                lo, rows = j, 0
+            rows += n
+        if lo < len(xs):
+            chunks.append((lo, len(xs)))
+        return chunks
+
+    @torch.no_grad()
+    def infer_many(self, xs, labels=None, return_attn=False, no_norm=False):
+        """forward_test over a LIST of bags of different row counts -> logits [n, C]; with ``return_attn`` also the list of per-bag
+        attention vectors [N_b] (raw scorer outputs with ``no_norm``), with ``labels`` (int64 [n], device) also the per-bag cross
+        entropy [n]: ``logits`` | ``(logits, attn)`` | ``(logits, loss)`` | ``(logits, attn, loss)``.
+        An eval-mode plain-ABMIL model without merge_test takes mhimx_infer_run - one C call (four launches) per chunk of bags, see
+        ``infer_chunks``; anything else loops over forward_test.  ``self.last["infer_native"]`` says which route ran."""
+        xs = self._infer_bags(xs)
+        n = len(xs)
+        if labels is not None:
+            labels = labels.reshape(-1).to(device=xs[0].device, dtype=torch.int64) if n else labels
+            if labels.numel() != n:
+                raise L.MhimxError(f"MHIM.infer_many: {labels.numel()} labels for {n} bags")
+        native = n > 0 and self._infer_ok(xs)
+        attns = []
+        if native:
+            cfg = self._infer_cfg()
+            chunks = self.infer_chunks(xs)
+            lg, ls = [], []
+            for lo, hi in chunks:
+                r = ops.infer_many(cfg, xs[lo:hi], labels=None if labels is None else labels[lo:hi].contiguous(),
+                                   want_attn=return_attn and not no_norm, want_score=return_attn and no_norm)
+                lg.append(r.logits)
+                ls.append(r.loss)
+                if return_attn:
+                    a = r.score if no_norm else r.attn
+                    attns += [a[r.offsets[j]:r.offsets[j + 1]] for j in range(hi - lo)]
+            self._step += n                       # (the stream position the forward_test loop leaves behind: one seed per bag)
+            logits = lg[0] if len(lg) == 1 else torch.cat(lg)
+            loss = None if labels is None else (ls[0] if len(ls) == 1 else torch.cat(ls))
+            self.last = {"infer_native": True, "infer_calls": len(chunks)}
+        else:
+            lg = []
+            for x in xs:
+                o = self.forward_test(x, return_attn=return_attn, no_norm=no_norm)
+                if self.baseline == "dsmil":
+                    raise L.MhimxError("MHIM.infer_many: DSMIL returns two logit rows per bag; use forward_test")
+                if return_attn:
+                    lg.append(o[0].reshape(1, -1))
+                    attns.append(o[1].reshape(-1) if torch.is_tensor(o[1]) else o[1])
+                else:
+                    lg.append(o.reshape(1, -1))
+            logits = torch.cat(lg) if lg else torch.empty((0, self.n_classes), device=self.feature[0].weight.device)
+            loss = None if labels is None else torch.nn.functional.cross_entropy(logits, labels, reduction="none")
+            self.last = {"infer_native": False, "infer_calls": 0}
+        out = (logits,) + ((attns,) if return_attn else ()) + ((loss,) if labels is not None else ())
+        return out[0] if len(out) == 1 else out
 
     # ------------------------------------------------------------------ TransMIL (selfattn) pieces
     def _encode(self, tok, return_attn=False, no_norm=False, has_cls=False):

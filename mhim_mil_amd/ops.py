@@ -939,6 +939,69 @@ def cls_metrics(logits, labels, n_classes, bin_metric=False, sample_idx=None):
     return out
 
 
+# ------------------------------------------------------------------------------------------- ragged multi-bag inference
+class InferResult:
+    """Outputs of one mhimx_infer_run: logits [n, C], z [n, E], stats [n, 2], score / attn [sum N] (bag b's rows at offsets[b] ..
+    offsets[b + 1]) or None, loss [n] or None."""
+    __slots__ = ("logits", "z", "stats", "score", "attn", "loss", "offsets")
+
+
+_INFER_WS = {}              # device index -> the cached workspace (grown on demand, like the step executor's)
+
+
+def infer_params(w1, b1, wa, wc, wp, bp):
+    for n, t in (("w1", w1), ("b1", b1), ("wa", wa), ("wc", wc), ("wp", wp), ("bp", bp)):
+        _chk(t, name=n)
+    return L.StepParams(w1=w1.data_ptr(), b1=b1.data_ptr(), wa=wa.data_ptr(), wc=wc.data_ptr(), wp=wp.data_ptr(), bp=bp.data_ptr())
+
+
+def infer_ws_bytes(cfg, xs):
+    """mhimx_infer_ws_bytes for the bags ``xs`` ([N, D] each): host arithmetic only."""
+    bags = (L.InferBag * len(xs))(*[L.InferBag(X=x.data_ptr(), ldx=x.stride(0), N=x.shape[0]) for x in xs])
+    return L.lib().mhimx_infer_ws_bytes(C.byref(cfg), len(xs), bags)
+
+
+def infer_many(cfg, xs, labels=None, want_attn=False, want_score=False, want_z=False, ws=None):
+    """The eval-mode MHIM(ABMIL) forward of up to L.INFER_MAX bags of different row counts in ONE C call (mhimx_infer_run).
+    cfg: L.InferCfg (its parameter tensors are kept alive by the caller); xs: [N_b, D] fp32 GPU tensors with unit column stride;
+    labels: int64 [n] on the device (then the per-bag cross entropy comes back too).  ``ws``: a uint8 workspace of the caller's
+    (tests poison it); default: one cached per device, grown on demand (inside a stream capture: a fresh one, owned by the graph's pool)."""
+    n = len(xs)
+    for x in xs:
+        if not (torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.stride(1) == 1):
+            raise L.MhimxError("infer_many: every bag must be a GPU fp32 matrix [N, D] with unit column stride")
+    _chk(labels, torch.int64, "labels")
+    if labels is not None and labels.numel() != n:
+        raise L.MhimxError(f"infer_many: {labels.numel()} labels for {n} bags")
+    bags = (L.InferBag * max(n, 1))(*[L.InferBag(X=x.data_ptr(), ldx=x.stride(0), N=x.shape[0]) for x in xs])
+    need = L.lib().mhimx_infer_ws_bytes(C.byref(cfg), n, bags)
+    if need < 0:
+        L.check(int(need), "mhimx_infer_ws_bytes")
+    dev = xs[0].device
+    if ws is None:
+        if torch.cuda.is_current_stream_capturing():
+            ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        else:
+            ws = _INFER_WS.get(dev.index)
+            if ws is None or ws.numel() < need:
+                # (poisoned when it is made: 0xFF bytes are NaNs - a launch that read workspace memory no launch of the call wrote shows up)
+                ws = _INFER_WS[dev.index] = torch.full((need,), 255, dtype=torch.uint8, device=dev)
+    r = InferResult()
+    rows = sum(int(x.shape[0]) for x in xs)
+    r.offsets = [0]
+    for x in xs:
+        r.offsets.append(r.offsets[-1] + int(x.shape[0]))
+    r.logits = torch.empty((n, int(cfg.C)), device=dev)
+    r.stats = torch.empty((n, 2), device=dev)
+    r.z = torch.empty((n, int(cfg.E)), device=dev) if want_z else None
+    r.score = torch.empty(rows, device=dev) if want_score else None
+    r.attn = torch.empty(rows, device=dev) if want_attn else None
+    r.loss = torch.empty(n, device=dev) if labels is not None else None
+    out = L.InferOut(logits=_p(r.logits), z=_p(r.z), stats=_p(r.stats), score=_p(r.score), attn=_p(r.attn), loss=_p(r.loss))
+    L.check(L.lib().mhimx_infer_run(_stream(), C.byref(cfg), n, bags, _p(labels), C.byref(out), _p(ws), ws.numel()), "mhimx_infer_run")
+    return r
+
+
 # ------------------------------------------------------------------------------------------- streamed Nystrom attention
 class NysOperands:
     """mhimx_nys: the packed to_qkv output qkv [T, 1536] (q | k | v, heads = 64-column groups), the landmark means lm [256, 1024]

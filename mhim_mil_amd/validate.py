@@ -70,11 +70,52 @@ def get_metric_val(args, bag_logit, bag_labels, model, status, early_stopping, e
     return [auc[0], acc[0], prec[0], rec[0], f1[0], ck[0], acc_micro[0], auc[1], acc[1], f1[1], ck[1], acc_micro[1]], loss_avg, rowd
 
 
-def validate(engine, args, model, loader, criterion=None, early_stopping=None, epoch=None, status="val"):
+def _validate_chunked(engine, args, model, loader, criterion, chunk):
+    """The loop of ``validate`` with ``chunk`` batches gathered per ``engine.validate_many`` call (MHIM.infer_many: one C call for bags
+    of different sizes).  Same lists, same per-bag loss terms added in loader order."""
+    logits_all, labels_all, loss_sum, count = [], [], None, 0
+
+    def flush(bags, labels):
+        nonlocal loss_sum, count
+        lab = torch.cat(labels)
+        logits, losses = engine.validate_many(args, model, bags, lab, criterion)
+        for j in range(len(bags)):
+            lg = logits[j:j + 1]
+            logits_all.append(lg)
+            labels_all.append(labels[j])
+            loss = losses[j] if losses is not None else criterion(lg, labels[j])
+            loss_sum = loss if loss_sum is None else loss_sum + loss
+            count += 1
+
+    bags, labels = [], []
+    with torch.no_grad():
+        for batch in loader:
+            bag, label = batch["input"], batch["target"]
+            dev = bag.device if bag.is_cuda else torch.device("cuda")
+            bags.append(bag.to(dev, non_blocking=True))
+            labels.append(label.to(dev, non_blocking=True).reshape(-1))
+            if labels[-1].numel() != 1:
+                raise ops.L.MhimxError("validate(chunk > 0): one bag and one label per batch (the reference's batch size 1)")
+            if len(bags) == chunk:
+                flush(bags, labels)
+                bags, labels = [], []
+        if bags:
+            flush(bags, labels)
+    return logits_all, labels_all, loss_sum, count
+
+
+def validate(engine, args, model, loader, criterion=None, early_stopping=None, epoch=None, status="val", chunk=0):
     """engines/base_engine.py:234-329 for the MHIM models.  ``loader`` yields dicts with 'input' (bag [1,N,D] or [N,D]) and
-    'target' ([1] int64) - the reference's batch layout (batch size 1).  Returns what BaseTrainer.validate returns."""
+    'target' ([1] int64) - the reference's batch layout (batch size 1).  Returns what BaseTrainer.validate returns.
+    ``chunk`` > 0: that many batches are gathered and go through ``engine.validate_many`` together (mhimx_infer_run: one C call per
+    chunk of bags of different sizes, the per-bag cross entropy computed on the device); 0: bag after bag through ``validate_func``."""
     model.eval()
     criterion = criterion or torch.nn.CrossEntropyLoss()
+    if chunk > 0:
+        logits_all, labels_all, loss_sum, count = _validate_chunked(engine, args, model, loader, criterion, int(chunk))
+        bag_logit, bag_labels = torch.cat(logits_all), torch.cat(labels_all)
+        loss_avg = float(loss_sum / count)
+        return list(get_metric_val(args, bag_logit, bag_labels, model, status, early_stopping, epoch, loss_avg))
     logits_all, labels_all, loss_sum, count = [], [], None, 0
     with torch.no_grad():
         for i, batch in enumerate(loader):
