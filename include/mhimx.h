@@ -851,6 +851,34 @@ int mhimx_step_run_many(void* stream, const mhimx_step_cfg* cfg, int32_t n_bags,
                         const int64_t* const* labels_dev, const mhimx_step_counts* cnt, const mhimx_step_seeds* seeds, int64_t host_step0,
                         void* ws, int64_t ws_bytes);
 
+/* The teacher-free ABMIL step ('mhim_pure': the first of the recipe's two trainings - its result is the teacher initialisation of the
+ * second - and BASELINE config c1) of one bag behind ONE call.
+ * replaces: engines/common_mil.py:32-37 (forward_func, model 'mhim_pure': model.pure(bag)), modules/mhim.py `pure` (feature -> dropout ->
+ *           attention pool -> predictor) and engines/base_engine.py:76-120 (criterion, loss.backward(), optimizer.step()) for one bag.
+ * Enqueue-only like mhimx_step_run (no allocation, no synchronisation, nothing read back; capturable).  Nine launches, the entry points
+ * above in the order mhim_mil_amd/engine.py issues them for FusedTrainer(model="mhim_pure") - same arguments, same bits given the same
+ * seed and tick:  mhimx_prep_batch (counters, the W1 paired-plane image, the scorer's fragment / transposed / transposed-fragment images)
+ * -> mhimx_bag_project (one head) -> mhimx_abmil_pool_fwd over all N rows (two launches) -> mhimx_head_fwd_bwd (no teacher row) ->
+ * mhimx_abmil_pool_bwd -> mhimx_rows_dpre_image + mhimx_bag_wgrad (rows = NULL) -> mhimx_optim_step (teacher = NULL; update = 0:
+ * mhimx_reduce_flush, the complete gradient in cfg->grad - the body of a data-parallel rank).
+ * cfg: a mhimx_step_cfg as it is.  NOT read (may be NULL / 0): teacher, the merge.* parameters (student.q, ln_w, ln_b, wkv, wq, wo, bo)
+ * and gradients (grad.ln_w .. grad.bo), k, attn2score, drop_p_teacher, merge_drop_p, merge_mm, temp_t, aux_alpha, p_teacher, mm_table,
+ * mm_len, ema_mm, q_out, time_project, side_stream.
+ * Shapes: E = 512, A = 128, plain scorer, C <= 4, D % 256 == 0, 64 <= N <= MHIMX_STEP_MAX_ROWS, ldx >= D, ldx % 4 == 0,
+ * N * ldx * 4 < 2^32; anything else returns < 0 before any device call.
+ * Workspace: mhimx_pure_step_layout_of(...).total bytes (pure host arithmetic), 256-byte aligned; no teacher rows, select buffers or Merge
+ * workspace and one projection weight image - 0.45 of mhimx_step_layout_of's at N x D = 512 x 1024, 0.53 at 10 000 x 1024, 0.54 at
+ * 200 000 x 1536 (counts of mhimx_step_counts_of(N, .03, .5, .9)).
+ * MHIMX_VERSION stays 620: the three entry points are additions - no existing entry point or struct changed shape, every binding written
+ * against 620 stays valid.  The layout's fields that have no meaning here (score, rows_all, H_teacher, z_teacher) are -1; H_student and dH are [N, E]. */
+int mhimx_pure_step_layout_of(const mhimx_step_cfg* cfg, int64_t N, mhimx_step_layout* out);
+/* drop_seed: the seed of the feature dropout's counter-hash stream (mixed with *cfg->tick on the device) */
+int mhimx_pure_step_run(void* stream, const mhimx_step_cfg* cfg, const float* X, int64_t ldx, int64_t N, const int64_t* label_dev,
+                        uint64_t drop_seed, int64_t host_step, void* ws, int64_t ws_bytes, int32_t update);
+/* n_bags consecutive complete pure steps (one update each) on one workspace of max_b layout.total bytes */
+int mhimx_pure_step_run_many(void* stream, const mhimx_step_cfg* cfg, int32_t n_bags, const float* const* X, const int64_t* ldx, const int64_t* N,
+                             const int64_t* const* labels_dev, const uint64_t* drop_seeds, int64_t host_step0, void* ws, int64_t ws_bytes);
+
 /* An accumulation window (--accumulation_steps n, base_engine.py:29,47-49,100-119: n bags share the weights, their gradients add up, ONE
  * optimiser step) with every launch over ALL its bags (round 6): one preparation, both projections of the n bags in one launch, the step's
  * middle (teacher scorer, select, Merge, student scorer, head, backward to the dPRE image) issued once with one grid plane per bag, ONE

@@ -218,6 +218,7 @@ class WindowLayout(C.Structure):
 
 
 WINDOW_MAX = 8               # MHIMX_WINDOW_MAX
+STEP_MAX_ROWS = 262144       # MHIMX_STEP_MAX_ROWS
 
 
 class InferCfg(C.Structure):
@@ -352,6 +353,9 @@ SYMBOLS = {
     "mhimx_infer_ws_bytes": (_I64, [C.POINTER(InferCfg), _I32, _P]),
     "mhimx_infer_run": (C.c_int, [_P, C.POINTER(InferCfg), _I32, _P, _P, C.POINTER(InferOut), _P, _I64]),
     "mhimx_step_run_many": (C.c_int, [_P, C.POINTER(StepCfg), _I32, _P, _P, _P, _P, C.POINTER(StepCounts), C.POINTER(StepSeeds), _I64, _P, _I64]),
+    "mhimx_pure_step_layout_of": (C.c_int, [C.POINTER(StepCfg), _I64, C.POINTER(StepLayout)]),
+    "mhimx_pure_step_run": (C.c_int, [_P, C.POINTER(StepCfg), _P, _I64, _I64, _P, C.c_uint64, _I64, _P, _I64, _I32]),
+    "mhimx_pure_step_run_many": (C.c_int, [_P, C.POINTER(StepCfg), _I32, _P, _P, _P, _P, _P, _I64, _P, _I64]),   # (drop_seeds: uint64[n])
 }
 
 _lib = None

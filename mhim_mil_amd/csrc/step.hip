@@ -831,3 +831,183 @@ extern "C" int mhimx_step_run_many(void* stream, const mhimx_step_cfg* cfg, int3
     if (int r = mhimx_step_run(stream, cfg, X[i], ldx[i], N[i], labels_dev[i], cnt + i, seeds + i, host_step0 + i, ws, ws_bytes, 1)) return r;
   return 0;
 }
+
+// ------------------------------------------------------------------------------------------------------------------------------------
+// mhimx_pure_step_run - the teacher-free ABMIL step ('mhim_pure': the first of the recipe's two trainings, and BASELINE config c1) of one
+// bag behind ONE C call.
+// replaces: engines/common_mil.py:32-37 (forward_func, model 'pure': model.pure(bag)) + modules/mhim.py `pure` + engines/base_engine.py:76-120
+//           (criterion, loss.backward(), optimizer.step()) for one bag - and, on this side of the boundary, the Python orchestration of
+//           FusedTrainer(model="mhim_pure") (_nat_prep / _nat_bag / _apply): the SAME entry points in the SAME order on the SAME arguments,
+//           so a step through this executor has the bits of a step through the Python path given the same seed and tick.
+//
+//   launch  1  mhimx_prep_batch         counters, the W1 paired-plane image, the scorer's fragment / transposed / transposed-fragment images
+//                                       (no teacher scorer launch exists for them to ride in)
+//           2  mhimx_bag_project        ONE head: feature rows, dropout, dact
+//         3,4  mhimx_abmil_pool_fwd     scorer + pool partials over all N rows (no row list) | finalize
+//           5  mhimx_head_fwd_bwd       predictor, CE and their gradients (no teacher row: no distillation term)
+//           6  mhimx_abmil_pool_bwd     one-pass rows backward
+//         7,8  rows_dpre_image | bag_wgrad   the projection's gradient pair over all N rows (rows = NULL)
+//           9  mhimx_optim_step         Adam (no EMA teacher; folds the split-K slab sum)      | update = 0: mhimx_reduce_flush
+// Workspace: no teacher rows, no select buffers, no Merge workspace, one projection weight image (include/mhimx.h states the ratio to
+// mhimx_step_layout_of's).
+// ------------------------------------------------------------------------------------------------------------------------------------
+namespace mhimx {
+namespace {
+
+struct PureBufs {
+  int64_t w1p, wa_frag, wa_t, wa_t_frag;
+  int64_t H, dact, s, stats, z, pool_ws, pool_ws_bytes;
+  int64_t logits, losses, g_z;
+  int64_t dH, img, ws_b, ws_b_bytes, wg_ws, wg_ws_floats;
+  int64_t total;
+};
+
+// what the pure step reads of a mhimx_step_cfg (mhimx.h lists what it does not): the teacher, every merge.* pointer and the select /
+// distillation scalars may be NULL / 0
+int check_pure_cfg(const mhimx_step_cfg* c, int64_t N) {
+  MHIMX_CHECK_ARG(c, "pure_step: null configuration");
+  MHIMX_CHECK_ARG(c->E == 512 && c->A == 128 && c->C >= 1 && c->C <= 4 && c->D > 0 && c->D % 256 == 0,
+                  "pure_step: shapes outside the single-pass ABMIL step (E = 512, A = 128, C <= 4, D %% 256 == 0)");
+  MHIMX_CHECK_ARG(N >= 64 && N <= MHIMX_STEP_MAX_ROWS, "pure_step: row count outside 64 <= N <= %d", MHIMX_STEP_MAX_ROWS);
+  const mhimx_step_params& s = c->student;
+  MHIMX_CHECK_ARG(s.w1 && s.b1 && s.wa && s.wc && s.wp && s.bp, "pure_step: null student parameter");
+  const mhimx_step_grads& g = c->grad;
+  MHIMX_CHECK_ARG(g.w1 && g.b1 && g.wa && g.wc && g.wp && g.bp, "pure_step: null gradient view");
+  MHIMX_CHECK_ARG(c->tick, "pure_step: the device dropout counter (tick) is required");
+  return 0;
+}
+
+void pure_layout(const mhimx_step_cfg* c, int64_t N, PureBufs* b) {
+  const int64_t D = c->D, E = c->E, A = c->A, F = sizeof(float);
+  Carve cv(nullptr);
+  b->w1p = cv.take_off(E * D * F);
+  b->wa_frag = cv.take_off(A * E * F);
+  b->wa_t = cv.take_off(E * A * F);
+  b->wa_t_frag = cv.take_off(E * A * F);
+  b->H = cv.take_off(N * E * F);
+  b->dact = cv.take_off(N * E * 2);
+  b->s = cv.take_off(N * F);
+  b->stats = cv.take_off(2 * F);
+  b->z = cv.take_off(E * F);
+  b->pool_ws_bytes = mhimx_abmil_pool_ws_bytes(N, E, A, 0);
+  b->pool_ws = cv.take_off(b->pool_ws_bytes);
+  b->logits = cv.take_off(16 * F);
+  b->losses = cv.take_off(4 * F);
+  b->g_z = cv.take_off(E * F);
+  b->dH = cv.take_off(N * E * F);
+  b->img = cv.take_off(mhimx_wgrad_image_bytes(N, E));
+  b->ws_b_bytes = (N + 31) / 32 * E * F;
+  b->ws_b = cv.take_off(b->ws_b_bytes);
+  b->wg_ws_floats = mhimx_wgrad_ws_floats(N, E, D);
+  b->wg_ws = cv.take_off(b->wg_ws_floats * F);
+  b->total = cv.off;
+}
+
+}  // namespace
+}  // namespace mhimx
+
+extern "C" int mhimx_pure_step_layout_of(const mhimx_step_cfg* cfg, int64_t N, mhimx_step_layout* out) {
+  MHIMX_CHECK_ARG(out, "pure_step_layout: null output");
+  if (int r = check_pure_cfg(cfg, N)) return r;
+  PureBufs b;
+  pure_layout(cfg, N, &b);
+  // (score, rows_all, H_teacher, z_teacher: the pure step has no teacher and no row list)
+  *out = mhimx_step_layout{b.total, b.logits, b.losses, -1, -1, -1, b.H, b.dact, -1, b.z, b.g_z, b.dH};
+  return 0;
+}
+
+extern "C" int mhimx_pure_step_run(void* stream, const mhimx_step_cfg* cfg, const float* X, int64_t ldx, int64_t N, const int64_t* label_dev,
+                                   uint64_t drop_seed, int64_t host_step, void* ws, int64_t ws_bytes, int32_t update) {
+  if (int r = check_pure_cfg(cfg, N)) return r;
+  MHIMX_CHECK_ARG(X && label_dev && ws && ldx >= cfg->D && ldx % 4 == 0 && N * ldx * 4 < ((int64_t)1 << 32) && aligned16(X),
+                  "pure_step: null bag / label / workspace, or a row pitch the weight-gradient product does not take");
+  MHIMX_CHECK_ARG(!update || (cfg->p && cfg->g && cfg->m && cfg->v && cfg->n_train > 0 && cfg->n_all >= cfg->n_train),
+                  "pure_step: update needs the flat optimiser buffers");
+  PureBufs b;
+  pure_layout(cfg, N, &b);
+  MHIMX_CHECK_ARG(ws_bytes >= b.total && (reinterpret_cast<uintptr_t>(ws) & 255) == 0, "pure_step: workspace too small (%lld < %lld) or not 256-byte aligned",
+                  (long long)ws_bytes, (long long)b.total);
+  const mhimx_step_cfg& c = *cfg;
+  const mhimx_step_params& S = c.student;
+  const int64_t D = c.D, E = c.E, A = c.A, C = c.C;
+  Carve cv(ws);
+  float* w1p = cv.at<float>(b.w1p);
+  float* wa_frag = cv.at<float>(b.wa_frag);
+  float* wa_t = cv.at<float>(b.wa_t);
+  float* wa_t_frag = cv.at<float>(b.wa_t_frag);
+  float* H = cv.at<float>(b.H);
+  void* dact = cv.at<char>(b.dact);
+  float* dH = cv.at<float>(b.dH);
+  const uint64_t* tick = c.tick;
+
+  // ---- 1. counters and every weight image of the step
+  {
+    mhimx_prep_job jobs[6];
+    int n = 0;
+    jobs[n++] = mhimx_prep_job{3, nullptr, reinterpret_cast<float*>(c.tick), 1, 1};
+    if (c.opt_step) jobs[n++] = mhimx_prep_job{3, nullptr, reinterpret_cast<float*>(c.opt_step), 1, 1};
+    jobs[n++] = mhimx_prep_job{1, S.w1, w1p, E, D};
+    jobs[n++] = mhimx_prep_job{4, S.wa, wa_frag, A, E};
+    jobs[n++] = mhimx_prep_job{0, S.wa, wa_t, A, E};
+    jobs[n++] = mhimx_prep_job{5, S.wa, wa_t_frag, A, E};
+    if (int r = mhimx_prep_batch(stream, jobs, n)) return r;
+  }
+
+  // ---- 2. the feature rows of all N bag rows (mhim.py `pure`: feature -> dropout)
+  {
+    mhimx_bag_project_args a = {};
+    a.X = X; a.ldx = ldx; a.N = N; a.D = D; a.E = E; a.act = c.act; a.n_heads = 1; a.drop_tick = tick;
+    a.head[0].wp = w1p; a.head[0].bias = S.b1; a.head[0].H = H; a.head[0].ldh = E; a.head[0].dact = dact; a.head[0].drop_p = c.drop_p_student;
+    a.head[0].drop_seed = drop_seed;
+    if (int r = mhimx_bag_project(stream, &a)) return r;
+  }
+
+  // ---- 3, 4. scorer + softmax pool over every row
+  mhimx_scorer sc = {};
+  sc.E = E; sc.A = A; sc.act = c.da_act; sc.prec = MHIMX_PREC_BF16X3; sc.wa = S.wa; sc.wc = S.wc; sc.wa_frag = wa_frag;
+  mhimx_pool_io io = {};
+  io.T1 = H; io.M1 = N; io.s = cv.at<float>(b.s); io.stats = cv.at<float>(b.stats); io.z = cv.at<float>(b.z);
+  io.ws = cv.at<char>(b.pool_ws); io.ws_bytes = b.pool_ws_bytes;
+  if (int r = mhimx_abmil_pool_fwd(stream, &sc, &io)) return r;
+
+  // ---- 5. head: predictor, CE and their gradients
+  float* g_z = cv.at<float>(b.g_z);
+  if (int r = mhimx_head_fwd_bwd(stream, io.z, nullptr, S.wp, S.bp, label_dev, E, C, 1.f, c.main_alpha, 0.f, 1.f, cv.at<float>(b.logits), cv.at<float>(b.losses),
+                                 g_z, c.grad.wp, c.grad.bp, 0, nullptr, nullptr))
+    return r;
+
+  // ---- 6..8. backward
+  mhimx_reduce_list lst;
+  memset(&lst, 0, sizeof(lst));
+  {
+    mhimx_scorer sc_b = sc;
+    sc_b.wa_frag = nullptr;
+    mhimx_pool_grad pg = {};
+    pg.g_z = g_z; pg.dT1 = dH; pg.d_wa = c.grad.wa; pg.d_wc = c.grad.wc; pg.wa_t = wa_t; pg.accumulate = 0; pg.splits = 8; pg.defer = &lst; pg.wa_t_frag = wa_t_frag;
+    if (int r = mhimx_abmil_pool_bwd(stream, &sc_b, &io, &pg)) return r;
+  }
+  if (int r = mhimx_rows_dpre_image(stream, dH, dact, nullptr, N, E, cv.at<char>(b.img), c.grad.b1, 0, cv.at<char>(b.ws_b), b.ws_b_bytes, &lst)) return r;
+  {
+    mhimx_bag_wgrad_args g = {};
+    g.img = cv.at<char>(b.img); g.X = X; g.ldx = ldx; g.n_bag_rows = N; g.rows = nullptr; g.L = N; g.E = E; g.D = D;
+    g.C = c.grad.w1; g.ldc = D;
+    g.accumulate = 0; g.ws = cv.at<float>(b.wg_ws); g.ws_floats = b.wg_ws_floats; g.defer = &lst; g.ride_tail = update ? 1 : 0;
+    if (int r = mhimx_bag_wgrad(stream, &g)) return r;
+  }
+  if (!update) return mhimx_reduce_flush(stream, &lst);
+
+  // ---- 9. Adam; the weight gradient's split-K slab sum is folded into the update
+  mhimx_optim_args o = {};
+  o.p = c.p; o.g = c.g; o.m = c.m; o.v = c.v; o.teacher = nullptr; o.n_train = c.n_train; o.n_all = c.n_all; o.step = host_step; o.step_dev = c.opt_step;
+  o.lr = c.lr; o.lr_table = c.lr_table; o.lr_len = c.lr_len; o.beta1 = c.beta1; o.beta2 = c.beta2; o.eps = c.eps; o.weight_decay = c.weight_decay;
+  o.grad_scale = 1.f; o.zero_grad = 1; o.fold = &lst;
+  return mhimx_optim_step(stream, &o);
+}
+
+extern "C" int mhimx_pure_step_run_many(void* stream, const mhimx_step_cfg* cfg, int32_t n_bags, const float* const* X, const int64_t* ldx, const int64_t* N,
+                                        const int64_t* const* labels_dev, const uint64_t* drop_seeds, int64_t host_step0, void* ws, int64_t ws_bytes) {
+  MHIMX_CHECK_ARG(n_bags >= 1 && X && ldx && N && labels_dev && drop_seeds, "pure_step_run_many: null arguments");
+  for (int32_t i = 0; i < n_bags; ++i)
+    if (int r = mhimx_pure_step_run(stream, cfg, X[i], ldx[i], N[i], labels_dev[i], drop_seeds[i], host_step0 + i, ws, ws_bytes, 1)) return r;
+  return 0;
+}

@@ -483,7 +483,7 @@ class FusedTrainer:
         finally:
             s.merge_enable = merge_on
         self._micro += 1
-        self.last = {"logits": logits, "losses": losses, "patch_num": ps, "keep_num": keep_num}
+        self.last = {"logits": logits, "losses": losses, "patch_num": ps, "keep_num": keep_num, "exec": False}
         return logits, losses
 
     def _nat_ok(self, x, i=None):
@@ -503,6 +503,16 @@ class FusedTrainer:
         # QueryChain's scratch (mhimx_step_cfg.q_out), then the all-reduce and mhimx_optim_step as always - unless the eager step overlaps
         # its all-reduce with the backward (the mid-backward hook lives in the Python orchestration)
         hooked = (self.overlap_comm and self.comm is None and self.world > 1 and self.accum == 1 and not self._capturing and self._split > 0)
+        if self.model_kind == "mhim_pure":
+            # mhimx_pure_step_run.  Decided on the model's kind, baseline and scorer form BEFORE anything of s.merge or
+            # attention.attention[...] is touched: a pure model is built with merge_enable=False (s.merge is an Identity) and may be gated,
+            # TransMIL or DSMIL.  Accumulation windows, clipping, injected draws and prec="f32" keep the Python orchestration.
+            if not (self.use_executor and self.accum == 1 and not window and not hooked and not self.clip_grad and perm is None
+                    and ids_shuffle is None and s.training and s.baseline == "attn" and not s.online_encoder.gated and s._op_prec != "f32"
+                    and s._feature_prec(x.shape[0]) == "bf16x3" and x.dim() == 2):
+                return False
+            return self.pure_exec_shapes_ok(x.shape[0], x.shape[1], x.stride(0), x.stride(1), x.data_ptr(), E=s.mlp_dim,
+                                            A=s.online_encoder.attention.attention[0].weight.shape[0], C=s.n_classes, max_rows=self.exec_max_rows)
         if not (self.use_executor and self.model_kind == "mhim" and (self.accum == 1 or window) and not hooked and perm is None
                 and ids_shuffle is None and self.ride_prep and s.training and s.n_classes <= 4 and s._op_prec != "f32"
                 and s.merge.k * 8 <= 48 and x.shape[1] % 256 == 0 and x.stride(0) % 4 == 0 and x.shape[0] * x.stride(0) * 4 < (1 << 32)):
@@ -523,13 +533,22 @@ class FusedTrainer:
             return False
         return 1 <= c[0] and c[3] >= 1 and 1 <= c[4] <= 32768
 
+    @staticmethod
+    def pure_exec_shapes_ok(N, D, pitch, inner, ptr, E=512, A=128, C=2, max_rows=262144):
+        """The tensor-free part of _exec_ok's pure branch - csrc/step.hip check_pure_cfg and mhimx_pure_step_run's own argument checks,
+        mirrored: a bag the call would refuse takes the Python path instead of raising.  (N, D): the bag's shape; pitch, inner: its strides
+        in floats; ptr: its address."""
+        return bool(E == 512 and A == 128 and 1 <= C <= 4 and D > 0 and D % 256 == 0 and 64 <= N <= max_rows and inner == 1 and pitch >= D
+                    and pitch % 4 == 0 and N * pitch * 4 < (1 << 32) and ptr % 16 == 0)
+
     def _exec_cfg(self):
         """The mhimx_step_cfg of this trainer: parameter / gradient pointers into the flat buffers (stable for the trainer's lifetime), the
         model's hyper-parameters; the optimiser's scalars are refreshed on every call."""
         s, t, fl = self.s, self.t, self.flat
         L = mh.L
         ex = self._exec
-        key = (s.feature[0].weight.data_ptr(), t.feature[0].weight.data_ptr(), fl.grad.data_ptr())
+        mhim = self.model_kind == "mhim"             # ('mhim_pure': no teacher, no merge.* fields - mhimx_pure_step_run reads neither)
+        key = (s.feature[0].weight.data_ptr(), t.feature[0].weight.data_ptr() if mhim else 0, fl.grad.data_ptr())
         if ex is None or ex["key"] != key:
             P = lambda tns: tns.data_ptr()
             def params(m, with_merge):
@@ -544,16 +563,25 @@ class FusedTrainer:
             gv = fl.grad_views
             pre = "online_encoder.attention.attention."
             grads = L.StepGrads(w1=P(gv["feature.0.weight"]), b1=P(gv["feature.0.bias"]), wa=P(gv[pre + "0.weight"]), wc=P(gv[pre + "2.weight"]),
-                                wp=P(gv["predictor.weight"]), bp=P(gv["predictor.bias"]), ln_w=P(gv["merge.norm.weight"]), ln_b=P(gv["merge.norm.bias"]),
-                                wkv=P(gv["merge.attn.to_kv.weight"]), wq=P(gv["merge.attn.to_q.weight"]), wo=P(gv["merge.attn.to_out.0.weight"]),
-                                bo=P(gv["merge.attn.to_out.0.bias"]))
-            cfg = L.StepCfg(D=s.input_dim, E=s.mlp_dim, A=s.online_encoder.attention.attention[0].weight.shape[0], C=s.n_classes, k=s.merge.k,
+                                wp=P(gv["predictor.weight"]), bp=P(gv["predictor.bias"]))
+            if mhim:
+                grads.ln_w, grads.ln_b = P(gv["merge.norm.weight"]), P(gv["merge.norm.bias"])
+                grads.wkv, grads.wq = P(gv["merge.attn.to_kv.weight"]), P(gv["merge.attn.to_q.weight"])
+                grads.wo, grads.bo = P(gv["merge.attn.to_out.0.weight"]), P(gv["merge.attn.to_out.0.bias"])
+            cfg = L.StepCfg(D=s.input_dim, E=s.mlp_dim, A=s.online_encoder.attention.attention[0].weight.shape[0], C=s.n_classes,
+                            k=s.merge.k if mhim else 0,
                             act=L.act_code(s.act, mh._FEATURE_ACTS), da_act=L.act_code(s.da_act, mh._SCORER_ACTS),
-                            student=params(s, True), teacher=params(t, False), grad=grads,
+                            student=params(s, mhim), teacher=params(t, False) if mhim else L.StepParams(), grad=grads,
                             p=P(fl.student), g=P(fl.grad), m=P(fl.m), v=P(fl.v), n_train=fl.n_train, n_all=fl.n_all,
                             tick=P(self.tick), opt_step=P(self.opt_step))
             ex = self._exec = {"key": key, "cfg": cfg, "layouts": {}, "ws": None}
         cfg = ex["cfg"]
+        cfg.lr, cfg.beta1, cfg.beta2, cfg.eps, cfg.weight_decay, cfg.ema_mm = self.lr, self.betas[0], self.betas[1], self.eps, self.wd, self.mm
+        cfg.lr_table, cfg.lr_len = (None, 0) if self.lr_table is None else (self.lr_table.data_ptr(), self.lr_table.numel())
+        cfg.drop_p_student = float(s.dropout_p)
+        cfg.main_alpha = float(self.main_alpha)
+        if not mhim:
+            return ex
         if self.step_dag:
             if self._side is None or self._side.device != fl.student.device:
                 self._side = torch.cuda.Stream(device=fl.student.device)
@@ -569,13 +597,10 @@ class FusedTrainer:
         cfg.time_project = int(bool(getattr(self, "time_project", False)))
         cfg.attn2score = int(bool(t.attn2score))
         cfg.drop_p_teacher = float(t.dropout_p if t.training else 0.0)
-        cfg.drop_p_student = float(s.dropout_p)
         cfg.merge_drop_p, cfg.merge_mm = float(s.merge.dropout), float(s.merge.g_q_mm)
-        cfg.temp_t, cfg.main_alpha, cfg.aux_alpha = float(s.temp_t), float(self.main_alpha), float(self.aux_alpha)
+        cfg.temp_t, cfg.aux_alpha = float(s.temp_t), float(self.aux_alpha)
         cfg.p_teacher = None if fl.same_teacher else fl.teacher.data_ptr()
-        cfg.lr, cfg.beta1, cfg.beta2, cfg.eps, cfg.weight_decay, cfg.ema_mm = self.lr, self.betas[0], self.betas[1], self.eps, self.wd, self.mm
         cfg.mm_table, cfg.mm_len = (None, 0) if self.mm_table is None else (self.mm_table.data_ptr(), self.mm_table.numel())
-        cfg.lr_table, cfg.lr_len = (None, 0) if self.lr_table is None else (self.lr_table.data_ptr(), self.lr_table.numel())
         return ex
 
     def _exec_window_ok(self, xs, labels, i=None):
@@ -662,6 +687,13 @@ class FusedTrainer:
         """(counts, layout) of a bag of N rows at iteration i - cached: they follow from N and the HAM ratio alone."""
         import ctypes as C
         L = mh.L
+        if self.model_kind == "mhim_pure":              # (no counts: every row takes part)
+            ent = ex["layouts"].get(("pure", N))
+            if ent is None:
+                lay = L.StepLayout()
+                L.check(L.lib().mhimx_pure_step_layout_of(C.byref(ex["cfg"]), N, C.byref(lay)), "mhimx_pure_step_layout_of")
+                ent = ex["layouts"][("pure", N)] = (None, lay)
+            return ent
         k, n_sel, len_keep, Lk, R = self.s.v2_counts(N, i)
         key = (N, k, n_sel, Lk)
         ent = ex["layouts"].get(key)
@@ -673,7 +705,7 @@ class FusedTrainer:
         return ent
 
     def _exec_step(self, x, label, i):
-        """forward_backward (+ the update, inside train_step) of one bag as ONE call of mhimx_step_run."""
+        """forward_backward (+ the update, inside train_step) of one bag as ONE call of mhimx_step_run ('mhim_pure': mhimx_pure_step_run)."""
         import ctypes as C
         L = mh.L
         s, t, fl = self.s, self.t, self.flat
@@ -689,6 +721,28 @@ class FusedTrainer:
             ws = ex["ws"]
             if ws is None or ws.numel() < lay.total or ws.device != x.device:
                 ws = ex["ws"] = torch.full((int(lay.total * 1.25),), 255, dtype=torch.uint8, device=x.device)      # (poisoned: see _exec_window)
+
+        def view(off, n, dtype=torch.float32):
+            return ws[off:off + n * dtype.itemsize].view(dtype)
+
+        if self.model_kind == "mhim_pure":
+            # ONE seed per bag - the feature dropout's, drawn exactly where _nat_heads draws it: the model's seed stream then stands where
+            # the Python path leaves it
+            seed = s._next_seed()
+            update = bool(self._fold_now)
+            L.check(L.lib().mhimx_pure_step_run(ops._stream(), C.byref(ex["cfg"]), x.data_ptr(), x.stride(0), N, label.data_ptr(), seed,
+                                                fl.step + int(update), ws.data_ptr(), ws.numel(), int(update)), "mhimx_pure_step_run")
+            if update:
+                fl.step += 1
+            logits, losses = view(lay.logits, s.n_classes), view(lay.losses, 3)
+            self.last = {"logits": logits, "losses": losses, "patch_num": N, "keep_num": N, "rows": None, "score": None, "R": 0, "tokens": None,
+                         "H_student": view(lay.H_student, N * s.mlp_dim).view(N, s.mlp_dim), "H_teacher": None, "ws": ws, "exec": True}
+            if update:
+                ops.step_images(None)
+                self._micro = 0
+            else:
+                self._micro += 1
+            return logits, losses
         seeds = L.StepSeeds(drop_teacher=t._next_seed(teacher=True), drop_student=s._next_seed(), select=s._next_seed(), mca=s._next_seed())
         update = bool(self._fold_now)
         L.check(L.lib().mhimx_step_run(ops._stream(), C.byref(ex["cfg"]), x.data_ptr(), x.stride(0), N, label.data_ptr(), C.byref(cnt), C.byref(seeds),
@@ -696,16 +750,12 @@ class FusedTrainer:
         if update:                                      # (only a step that was enqueued counts: a refused call leaves host and device counters equal)
             fl.step += 1
         km, E = s.merge.k, s.mlp_dim
-
-        def view(off, n, dtype=torch.float32):
-            return ws[off:off + n * dtype.itemsize].view(dtype)
-
         Hs = view(lay.H_student, (N + km) * E).view(N + km, E)
         logits, losses = view(lay.logits, s.n_classes), view(lay.losses, 3)
         rows_all = view(lay.rows_all, cnt.len_keep + km, torch.int64)
         self.last = {"logits": logits, "losses": losses, "patch_num": N, "keep_num": cnt.Lk + km, "rows": rows_all[:cnt.len_keep],
                      "score": view(lay.score, N), "R": cnt.R, "tokens": Hs[N:], "H_student": Hs[:N],
-                     "H_teacher": view(lay.H_teacher, N * E).view(N, E), "ws": ws}
+                     "H_teacher": view(lay.H_teacher, N * E).view(N, E), "ws": ws, "exec": True}
         if self._chain is not None:                    # this rank's term of the chain: the tokens its Merge produced
             self._chain.tokens = self._chain_tokens = Hs[N:]
         if update:
@@ -750,6 +800,19 @@ class FusedTrainer:
         ld = (C.c_int64 * n)(*[x.stride(0) for x in xs])
         Ns = (C.c_int64 * n)(*[x.shape[0] for x in xs])
         lab = (C.c_void_p * n)(*[l.data_ptr() for l in labels])
+        lay = plans[-1][1]
+        if self.model_kind == "mhim_pure":
+            drop_seeds = (C.c_uint64 * n)(*[self.s._next_seed() for _ in range(n)])
+            L.check(L.lib().mhimx_pure_step_run_many(ops._stream(), C.byref(ex["cfg"]), n, Xp, ld, Ns, lab, drop_seeds, self.flat.step + 1, ws.data_ptr(),
+                                                     ws.numel()), "mhimx_pure_step_run_many")
+            self.flat.step += n
+            ops.step_images(None)
+            N, E = xs[-1].shape[0], self.s.mlp_dim
+            logits, losses = ws[lay.logits:lay.logits + 4 * self.s.n_classes].view(torch.float32), ws[lay.losses:lay.losses + 12].view(torch.float32)
+            self.last = {"logits": logits, "losses": losses, "patch_num": N, "keep_num": N, "rows": None, "score": None, "R": 0, "tokens": None,
+                         "H_student": ws[lay.H_student:lay.H_student + N * E * 4].view(torch.float32).view(N, E), "H_teacher": None, "ws": ws,
+                         "exec": True}
+            return logits, losses
         cnts = (L.StepCounts * n)(*[p[0] for p in plans])
         seeds = (L.StepSeeds * n)()
         for j in range(n):
@@ -759,7 +822,6 @@ class FusedTrainer:
                                             ws.numel()), "mhimx_step_run_many")
         self.flat.step += n
         ops.step_images(None)
-        lay = plans[-1][1]
         return ws[lay.logits:lay.logits + 4 * self.s.n_classes].view(torch.float32), ws[lay.losses:lay.losses + 12].view(torch.float32)
 
     def _forward_backward_nat(self, x, label, perm, ids_shuffle, i):
@@ -912,7 +974,7 @@ class FusedTrainer:
         # (kept for inspection / parity tests: under graph replay these are the static buffers the replay rewrites)
         self.last = {"logits": logits, "losses": losses, "patch_num": ps, "keep_num": keep_num, "rows": plan.rows,
                      "score": score, "R": plan.R, "tokens": Hbuf[ps:] if mhim else None,
-                     "H_student": Hbuf[:ps], "H_teacher": heads[0].out if mhim else None}
+                     "H_student": Hbuf[:ps], "H_teacher": heads[0].out if mhim else None, "exec": False}
         return logits, losses
 
     # ------------------------------------------------------------------------------------------------- accumulation windows
@@ -1089,7 +1151,7 @@ class FusedTrainer:
         self._backward_into_flat([lb, li, B], [g_lb, g_li, g_B])
         logits = 0.5 * (lb.detach() + li.detach())
         self._micro += 1
-        self.last = {"logits": logits, "losses": losses, "patch_num": x.shape[0], "keep_num": keep_num}
+        self.last = {"logits": logits, "losses": losses, "patch_num": x.shape[0], "keep_num": keep_num, "exec": False}
         return logits, losses
 
     def _selfattn_forward_backward(self, x, label, plan, teacher_feat, keep_num, first):
@@ -1112,7 +1174,7 @@ class FusedTrainer:
             d_wp=gv["predictor.weight"], d_bp=gv["predictor.bias"], accumulate=True)
         self._backward_into_flat([z], [g_z])
         self._micro += 1
-        self.last = {"logits": logits, "losses": losses, "patch_num": x.shape[0], "keep_num": keep_num}
+        self.last = {"logits": logits, "losses": losses, "patch_num": x.shape[0], "keep_num": keep_num, "exec": False}
         return logits, losses
 
     def _backward_into_flat(self, outs, g_outs):
