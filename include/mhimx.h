@@ -899,6 +899,49 @@ int mhimx_window_run(void* stream, const mhimx_step_cfg* cfg, int32_t n_bags, co
                      int64_t ws_bytes, int32_t update);
 
 /* ------------------------------------------------------------------------------------------
+ * Ragged accumulation window of the teacher-free ABMIL model: ONE optimiser update over n_bags bags of DIFFERENT row counts in one call.
+ * replaces: engines/base_engine.py:29-51,76-120 (--accumulation_steps, options.py:64: every bag's loss divided by the window's length
+ *           (:102), the gradients of the window's bags added up, one optimizer.step(); the last window of an epoch may be shorter, :30,50-51)
+ *           around engines/common_mil.py:32-37 and modules/mhim.py `pure`, with the loader's different N per slide
+ *           (datasets/dataset_feat.py:93-111).  For bags b = 0 .. n-1:
+ *     h_b = dropout_b(act(X_b W1^T + b1)),  s_b = wc . da_act(h_b Wa^T),  z_b = softmax(s_b) h_b,  logits_b = z_b Wp^T + bp
+ *     loss_b = main_alpha CE(logits_b, label_b) / n,   g = sum_b d loss_b / d theta for theta in {W1, b1, Wa, wc, Wp, bp}
+ *     update = 1: ONE Adam step on g (the flat gradient is cleared);  update = 0: g is left in cfg->grad (overwritten, not added to).
+ * Nine launches whatever n_bags and the sizes are (csrc/pure_window.hip lists them); the per-bag table travels by value: no allocation, no
+ * synchronisation, no host-to-device copy, nothing read back - capturable.  No floating-point atomics and no workgroup that waits for
+ * another: every sum has a fixed order, two runs of a window give the same bits; what is written per bag (feature rows, d out / d pre,
+ * scores, stats, z, logits, losses) depends on that bag's N, seed and the tick alone.
+ * cfg: a mhimx_step_cfg as mhimx_pure_step_run reads it (same fields read, same fields ignored).  *cfg->tick and *cfg->opt_step advance ONCE
+ * per window.  Bag b's keep-mask is the function of (drop_seed_b, tick, row inside the bag, column) mhimx_bag_project uses: element for
+ * element the mask mhimx_pure_step_run draws for that bag with the same seed at the same tick value.
+ * Shapes: E = 512, A = 128, plain scorer without biases, C <= 4, D % 256 == 0; 1 <= n_bags <= MHIMX_PURE_WINDOW_MAX; per bag
+ * 1 <= N <= MHIMX_STEP_MAX_ROWS, ldx >= D, ldx % 4 == 0, N * ldx * 4 < 2^32, 16-byte aligned rows.  Every bag starts at a multiple of 32 in
+ * the call's row space (layout.row0); the row space - sum_b ceil(N_b / 32) * 32 rows - holds at most MHIMX_PURE_WINDOW_MAX_ROWS rows: the
+ * workspace takes 5 716 bytes per row of it (feature rows 2 048, fp16 d out / d pre 1 024, fp32 dPRE rows 2 048, scorer gradient rows 512,
+ * scores and per-tile / per-chunk partials 84), 3.0 GB at the cap, besides at most 33 MB + 9 E D floats of images and split-K slabs.
+ * Anything else returns < 0 before any device call, mhimx_last_error names the bag.
+ * MHIMX_VERSION stays 620: additions only.
+ * ---------------------------------------------------------------------------------------- */
+#define MHIMX_PURE_WINDOW_MAX 32                  /* = MHIMX_INFER_MAX: the by-value bag table is the inference call's                    */
+#define MHIMX_PURE_WINDOW_MAX_ROWS 524288         /* rows of one call's row space                                                         */
+typedef struct {
+  const float* X; int64_t ldx, N;                 /* the bag [N, ldx >= D] fp32 (bags need not be contiguous)                             */
+  const int64_t* label_dev;                       /* int64 [1] on the device                                                              */
+  uint64_t drop_seed;                             /* seed of this bag's feature-dropout stream (mixed with *cfg->tick on the device)      */
+} mhimx_pure_window_bag;
+typedef struct {                                  /* byte offsets inside the workspace, valid until the next call on it                   */
+  int64_t total, rows;                            /* bytes; rows of the call's row space                                                  */
+  int64_t logits, losses;                         /* float [n, C], float [n, 3] = {main_alpha ce, ce, 0} per bag, NOT scaled by 1 / n     */
+  int64_t H, dact, s, stats, z, g_z;              /* [rows, E] f32, [rows, E] f16, [rows], [n, 2] {max, sum}, [n, E], [n, E]              */
+  int64_t row0[MHIMX_PURE_WINDOW_MAX];            /* first row of bag b in H / dact / s (a multiple of 32)                                */
+} mhimx_pure_window_layout;
+/* pure host arithmetic: works without a device */
+int mhimx_pure_window_layout_of(const mhimx_step_cfg* cfg, int32_t n_bags, const mhimx_pure_window_bag* bags, mhimx_pure_window_layout* out);
+/* host_step: the Adam step after this update when cfg->opt_step is NULL */
+int mhimx_pure_window_run(void* stream, const mhimx_step_cfg* cfg, int32_t n_bags, const mhimx_pure_window_bag* bags, int64_t host_step,
+                          void* ws, int64_t ws_bytes, int32_t update);
+
+/* ------------------------------------------------------------------------------------------
  * Ragged multi-bag inference: the eval-mode forward of MHIM(ABMIL) for n_bags bags of DIFFERENT row counts in one call - a validation
  * or test pass as one C call per chunk of bags instead of ~8 launches per bag from the host loop.
  * replaces: modules/mhim.py:229-272 (forward_test, merge_test off) under engines/common_mil.py:56-68 (validate_func) and the per-bag

@@ -238,6 +238,21 @@ class InferOut(C.Structure):
 INFER_MAX = 32               # MHIMX_INFER_MAX
 INFER_MAX_ROWS = 4194304     # MHIMX_INFER_MAX_ROWS
 
+PURE_WINDOW_MAX = 32         # MHIMX_PURE_WINDOW_MAX
+PURE_WINDOW_MAX_ROWS = 524288   # MHIMX_PURE_WINDOW_MAX_ROWS (rows of the call's row space: every bag rounded up to a multiple of 32)
+
+
+class PureWindowBag(C.Structure):
+    """mhimx_pure_window_bag: one bag of a ragged accumulation window of the teacher-free ABMIL model."""
+    _fields_ = [("X", c_f32p), ("ldx", C.c_int64), ("N", C.c_int64), ("label_dev", C.c_void_p), ("drop_seed", C.c_uint64)]
+
+
+class PureWindowLayout(C.Structure):
+    """mhimx_pure_window_layout: byte offsets inside the workspace; bag b's rows of H / dact / s start at row0[b]."""
+    _fields_ = [(n, C.c_int64) for n in ("total", "rows", "logits", "losses", "H", "dact", "s", "stats", "z", "g_z")] + [
+        ("row0", C.c_int64 * PURE_WINDOW_MAX)]
+
+
 SYMBOLS = {
     "mhimx_last_error": (C.c_char_p, []),
     "mhimx_version": (C.c_int, []),
@@ -356,6 +371,8 @@ SYMBOLS = {
     "mhimx_pure_step_layout_of": (C.c_int, [C.POINTER(StepCfg), _I64, C.POINTER(StepLayout)]),
     "mhimx_pure_step_run": (C.c_int, [_P, C.POINTER(StepCfg), _P, _I64, _I64, _P, C.c_uint64, _I64, _P, _I64, _I32]),
     "mhimx_pure_step_run_many": (C.c_int, [_P, C.POINTER(StepCfg), _I32, _P, _P, _P, _P, _P, _I64, _P, _I64]),   # (drop_seeds: uint64[n])
+    "mhimx_pure_window_layout_of": (C.c_int, [C.POINTER(StepCfg), _I32, _P, C.POINTER(PureWindowLayout)]),
+    "mhimx_pure_window_run": (C.c_int, [_P, C.POINTER(StepCfg), _I32, _P, _I64, _P, _I64, _I32]),
 }
 
 _lib = None

@@ -485,8 +485,13 @@ typedef __bf16 in_bf4 __attribute__((ext_vector_type(4)));
 typedef __bf16 in_bf2 __attribute__((ext_vector_type(2)));
 typedef float in_f2 __attribute__((ext_vector_type(2)));
 
-__global__ __launch_bounds__(ITHREADS, 2) void infer_project_kernel(InferTab tab, int D, const float* __restrict__ w1p,
-                                                                    const float* __restrict__ b1, int act, float* __restrict__ Hout) {
+// TRAIN (mhimx_pure_window_run, pure_window.hip): the same tile walk and k loop; the epilogue is bag_project_kernel's - per-bag counter
+// dropout (row key = row INSIDE the bag: a bag's mask is the one mhimx_bag_project draws for it alone with the same seed and tick) and the
+// fp16 d out / d pre rows - and the rows between a bag's N and the next multiple of 32 (the call's row space starts every bag at a
+// multiple of 32) are written as zero rows, so that no later launch of the window reads workspace memory nobody wrote.
+template <bool TRAIN>
+MHIMX_DEV void infer_project_body(const InferTab& tab, int D, const float* __restrict__ w1p, const float* __restrict__ b1, int act,
+                                  float* __restrict__ Hout, const PureWinDrop& dr) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave >> 2, wn = wave & 3;
@@ -651,6 +656,62 @@ __global__ __launch_bounds__(ITHREADS, 2) void infer_project_kernel(InferTab tab
   const f32x4 bias = b1 ? *reinterpret_cast<const f32x4*>(b1 + n) : f32x4{0.f, 0.f, 0.f, 0.f};
   float* Hb = Hout + (orow0 + m0) * IE + n;
   const int64_t rows_left = N - m0;
+  if constexpr (TRAIN) {
+    uint64_t seed = dr.seed[0];
+#pragma unroll
+    for (int q_ = 0; q_ < MHIMX_INFER_MAX; ++q_)
+      if (q_ == bag) seed = dr.seed[q_];
+    uint32_t* rkeys = reinterpret_cast<uint32_t*>(smem + 80 * ITP * 4);
+    const bool hashed = dr.drop_p > 0.f;
+    const uint64_t dseed = hashed ? eff_seed(seed, dr.tick) : 0;
+    const uint32_t thr16 = (uint32_t)(dr.drop_p * 65536.f + 0.5f);
+    const float inv_keep = 65536.f / (float)(65536u - thr16);
+    _Float16* db = dr.dact + (orow0 + m0) * IE + n;
+    const int64_t rows_pad = ((N + 31) & ~(int64_t)31) - m0;   // the bag's rows up to the next multiple of 32: zero rows
+#pragma unroll 1
+    for (int half = 0; half < 2; ++half) {
+      __syncthreads();
+      if (wm == half) {
+        const int cl = lane & 15, rq = lane >> 4;
+#pragma unroll
+        for (int i = 0; i < NRA; ++i)
+#pragma unroll
+          for (int j = 0; j < NRB; ++j)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) tile[(i * 16 + rq * 4 + e) * ITP + wn * 64 + j * 16 + cl] = acc[i][j][e];
+      }
+      if (hashed && tid < 80) rkeys[tid] = drop_row_key(dseed, (uint64_t)(m0 + half * 80 + tid));
+      __syncthreads();
+      for (int r = r0; r < 80; r += 8) {
+        const int m = half * 80 + r;
+        if (m >= rows_pad) break;
+        f32x4 v = f32x4{0.f, 0.f, 0.f, 0.f};
+        pj_h4 d = pj_h4{(_Float16)0.f, (_Float16)0.f, (_Float16)0.f, (_Float16)0.f};
+        if (m < rows_left) {
+          const f32x4 a = *reinterpret_cast<const f32x4*>(tile + r * ITP + c4);
+          float ks[4] = {1.f, 1.f, 1.f, 1.f};
+          if (hashed) {
+            const uint32_t rk = rkeys[r];
+            const uint32_t h0 = pj_pair_hash(rk, (uint32_t)(n >> 1)), h1 = pj_pair_hash(rk, (uint32_t)(n >> 1) + 1u);
+            ks[0] = (h0 & 0xffffu) >= thr16 ? inv_keep : 0.f;
+            ks[1] = (h0 >> 16) >= thr16 ? inv_keep : 0.f;
+            ks[2] = (h1 & 0xffffu) >= thr16 ? inv_keep : 0.f;
+            ks[3] = (h1 >> 16) >= thr16 ? inv_keep : 0.f;
+          }
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            float y, gq;
+            act_fwd_grad(a[q] + bias[q], act, y, gq);
+            v[q] = y * ks[q];
+            d[q] = (_Float16)(gq * ks[q]);
+          }
+        }
+        *reinterpret_cast<pj_h4*>(db + (int64_t)m * IE) = d;
+        *reinterpret_cast<f32x4*>(Hb + (int64_t)m * IE) = v;
+      }
+    }
+    return;
+  }
 #pragma unroll 1
   for (int half = 0; half < 2; ++half) {
     __syncthreads();                                          // fragment reads / the previous half's tile reads are over
@@ -674,6 +735,23 @@ __global__ __launch_bounds__(ITHREADS, 2) void infer_project_kernel(InferTab tab
       *reinterpret_cast<f32x4*>(Hb + (int64_t)m * IE) = v;
     }
   }
+}
+
+__global__ __launch_bounds__(ITHREADS, 2) void infer_project_kernel(InferTab tab, int D, const float* __restrict__ w1p,
+                                                                    const float* __restrict__ b1, int act, float* __restrict__ Hout) {
+  infer_project_body<false>(tab, D, w1p, b1, act, Hout, PureWinDrop{});
+}
+__global__ __launch_bounds__(ITHREADS, 2) void pure_window_project_kernel(InferTab tab, PureWinDrop dr, int D, const float* __restrict__ w1p,
+                                                                          const float* __restrict__ b1, int act, float* __restrict__ Hout) {
+  infer_project_body<true>(tab, D, w1p, b1, act, Hout, dr);
+}
+
+int pure_window_project(hipStream_t st, const InferTab& tab, const PureWinDrop& dr, int D, const float* w1p, const float* b1, int act, float* Hout) {
+  MHIMX_ONCE_PER_DEVICE(MHIMX_HIP(hipFuncSetAttribute((const void*)pure_window_project_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, INST * ISTAGE)));
+  hipLaunchKernelGGL(pure_window_project_kernel, dim3((unsigned)(8 * (IE / IBN) * cdiv(tab.tiles, 8))), dim3(ITHREADS), INST * ISTAGE, st, tab, dr, D,
+                     w1p, b1, act, Hout);
+  MHIMX_LAUNCH_CHECK();
+  return 0;
 }
 
 int infer_project(hipStream_t st, const InferTab& tab, int D, const float* w1p, const float* b1, int act, float* Hout) {

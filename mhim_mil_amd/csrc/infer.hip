@@ -299,6 +299,14 @@ void infer_layout(const mhimx_infer_cfg* c, int32_t n_bags, const mhimx_infer_ba
 
 }  // namespace
 
+int infer_score(hipStream_t st, const InferTab& tab, const float* H, const float* wa_frag, const float* wc, int act, float* s, float* pm, float* pl,
+                float* pz) {
+  MHIMX_ONCE_PER_DEVICE(MHIMX_HIP(hipFuncSetAttribute((const void*)infer_score_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SC_SMEM)));
+  hipLaunchKernelGGL(infer_score_kernel, dim3((unsigned)tab.parts), dim3(SC_THREADS), SC_SMEM, st, tab, H, wa_frag, wc, act, s, pm, pl, pz);
+  MHIMX_LAUNCH_CHECK();
+  return 0;
+}
+
 }  // namespace mhimx
 
 extern "C" int64_t mhimx_infer_ws_bytes(const mhimx_infer_cfg* cfg, int32_t n_bags, const mhimx_infer_bag* bags) {
@@ -341,9 +349,7 @@ extern "C" int mhimx_infer_run(void* stream, const mhimx_infer_cfg* cfg, int32_t
   // 2. feature rows of every bag (bag_project.hip)
   if (int r = infer_project(st, tab, D, w1p, P.b1, cfg->act, H)) return r;
   // 3. scores + pool partials
-  MHIMX_ONCE_PER_DEVICE(MHIMX_HIP(hipFuncSetAttribute((const void*)infer_score_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SC_SMEM)));
-  hipLaunchKernelGGL(infer_score_kernel, dim3((unsigned)tab.parts), dim3(SC_THREADS), SC_SMEM, st, tab, H, wa_frag, P.wc, cfg->da_act, s, pm, pl, pz);
-  MHIMX_LAUNCH_CHECK();
+  if (int r = infer_score(st, tab, H, wa_frag, P.wc, cfg->da_act, s, pm, pl, pz)) return r;
   // 4. merge, head, loss, attention
   hipLaunchKernelGGL(infer_finalize_kernel, dim3((unsigned)n_bags, out->attn ? 1 + FIN_ATTN_BLOCKS : 1), dim3(FIN_T), 0, st, tab, pm, pl, pz, s, P.wp,
                      P.bp, C, labels_dev, out->logits, out->z, out->stats, out->attn, out->loss);

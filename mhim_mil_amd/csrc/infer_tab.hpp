@@ -22,6 +22,19 @@ struct InferTab {
 constexpr int INFER_TILE_ROWS = 160;              // rows of a projection tile (bag-major tile numbering: InferTab.tile0)
 constexpr int IE = 512;                           // feature width of the ragged path
 
+// what the TRAIN-mode ragged projection (mhimx_pure_window_run) needs beyond the table: every bag's dropout seed, the device tick the
+// seeds are mixed with, the dropout probability and the fp16 d out / d pre rows (row space of the call, like the feature rows)
+struct PureWinDrop {
+  uint64_t seed[MHIMX_INFER_MAX];
+  const uint64_t* tick;
+  _Float16* dact;
+  float drop_p, pad;
+};
+int pure_window_project(hipStream_t st, const InferTab& tab, const PureWinDrop& dr, int D, const float* w1p, const float* b1, int act, float* Hout);
+// the ragged scorer + pool-partial launch of infer.hip (one workgroup per 256-row chunk of one bag; InferTab.part0 / .parts / .row0)
+int infer_score(hipStream_t st, const InferTab& tab, const float* H, const float* wa_frag, const float* wc, int act, float* s, float* pm, float* pl,
+                float* pz);
+
 // the ragged one-model projection launch (bag_project.hip): Hout[row0[b] + m, :] = act(X_b[m, :] W1^T + b1) for every bag b of the table
 int infer_project(hipStream_t st, const InferTab& tab, int D, const float* w1p, const float* b1, int act, float* Hout);
 

@@ -360,6 +360,9 @@ class FusedTrainer:
         # MHIMX_WINDOW_BATCHED=0: the bags on HIP streams, as rounds 3-5 had it
         self.window_batched = _WINDOW_BATCHED
         self._rows_cache = {}
+        # 'mhim_pure' accumulation windows as ONE call (mhimx_pure_window_run): rows of the call's row space (every bag rounded up to a
+        # multiple of 32) a window may have - its workspace takes 5.7 KB per row (1.5 GB at this cap); include/mhimx.h allows twice as many
+        self.pure_window_row_cap = 262144
 
     def _dist(self):
         return torch.distributed.is_available() and torch.distributed.is_initialized()
@@ -540,6 +543,101 @@ class FusedTrainer:
         in floats; ptr: its address."""
         return bool(E == 512 and A == 128 and 1 <= C <= 4 and D > 0 and D % 256 == 0 and 64 <= N <= max_rows and inner == 1 and pitch >= D
                     and pitch % 4 == 0 and N * pitch * 4 < (1 << 32) and ptr % 16 == 0)
+
+    @staticmethod
+    def pure_window_shapes_ok(bags, D, E=512, A=128, C=2, max_rows=262144, row_cap=524288, max_bags=32):
+        """csrc/pure_window.hip check_pw and mhimx_pure_window_run's own argument checks, mirrored and tensor-free: a window the call would
+        refuse takes the bag-after-bag route instead of raising.  ``bags``: one (N, D, pitch, inner, ptr) per bag - shape, strides in floats,
+        address; ``D``: the model's input width."""
+        if not (E == 512 and A == 128 and 1 <= C <= 4 and D > 0 and D % 256 == 0 and D <= (1 << 20) and 1 <= len(bags) <= max_bags):
+            return False
+        rows = 0
+        for N, Db, pitch, inner, ptr in bags:
+            if not (Db == D and 1 <= N <= max_rows and inner == 1 and pitch >= D and pitch % 4 == 0 and N * pitch * 4 < (1 << 32)
+                    and ptr != 0 and ptr % 16 == 0):
+                return False
+            rows += (N + 31) // 32 * 32
+        return rows <= row_cap
+
+    def _pure_window_ok(self, xs, labels):
+        """True when mhimx_pure_window_run takes this window.  Decided before any seed is drawn or counter touched."""
+        s = self.s
+        if ops.KERNEL_EVENT_HOOK is not None or not xs:
+            return False
+        if not (self.use_executor and self.model_kind == "mhim_pure" and self.world == 1 and self._micro == 0 and s.training
+                and s.baseline == "attn" and not s.online_encoder.gated and s._op_prec != "f32" and len(labels) == len(xs)):
+            return False
+        dev = xs[0].device
+        if not all(torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.device == dev
+                   and s._feature_prec(x.shape[0]) == "bf16x3" for x in xs):
+            return False
+        if not all(torch.is_tensor(l) and l.is_cuda and l.dtype == torch.int64 and l.numel() == 1 and l.device == dev for l in labels):
+            return False
+        return self.pure_window_shapes_ok([(x.shape[0], x.shape[1], x.stride(0), x.stride(1), x.data_ptr()) for x in xs], s.input_dim,
+                                          E=s.mlp_dim, A=s.online_encoder.attention.attention[0].weight.shape[0], C=s.n_classes,
+                                          max_rows=self.exec_max_rows, row_cap=min(self.pure_window_row_cap, mh.L.PURE_WINDOW_MAX_ROWS),
+                                          max_bags=mh.L.PURE_WINDOW_MAX)
+
+    def _exec_pure_window(self, xs, labels, update):
+        """One accumulation window of the teacher-free model - 1 .. accumulation_steps bags of any row counts, every loss scaled by
+        1 / len(bags) - as ONE call of mhimx_pure_window_run.  Returns ([logits per bag], [losses per bag]); self.last keeps the layout,
+        the workspace and every bag's views."""
+        L = mh.L
+        s, fl = self.s, self.flat
+        n = len(xs)
+        ex = self._exec_cfg()
+        table = ops.pure_window_bags(xs, labels, [0] * n)
+        lay = ops.pure_window_layout(ex["cfg"], table, n)
+        dev = xs[0].device
+        if torch.cuda.is_current_stream_capturing():
+            ws = torch.empty(lay.total, dtype=torch.uint8, device=dev)
+        else:
+            ws = ex.get("ws_pw")
+            if ws is None or ws.numel() < lay.total or ws.device != dev:
+                ws = ex["ws_pw"] = torch.full((int(lay.total * 1.25),), 255, dtype=torch.uint8, device=dev)      # (poisoned: see _exec_window)
+        for j in range(n):                                          # ONE seed per bag, in bag order: the feature dropout's
+            table[j].drop_seed = s._next_seed()
+        inside = bool(update and not self.clip_grad)                # (clipping needs the norm of the final gradient: the update stays outside)
+        ops.pure_window_run(ex["cfg"], table, n, fl.step + int(inside), ws, inside)
+        E, Cc = s.mlp_dim, s.n_classes
+
+        def view(off, cnt_, dtype=torch.float32):
+            return ws[off:off + cnt_ * dtype.itemsize].view(dtype)
+
+        lg, ls = view(lay.logits, n * Cc).view(n, Cc), view(lay.losses, n * 3).view(n, 3)
+        H = view(lay.H, lay.rows * E).view(lay.rows, E)
+        dact = view(lay.dact, lay.rows * E, torch.float16).view(lay.rows, E)
+        per = []
+        for j, x in enumerate(xs):
+            r0, N = int(lay.row0[j]), x.shape[0]
+            per.append({"logits": lg[j], "losses": ls[j], "patch_num": N, "keep_num": N, "row0": r0, "H_student": H[r0:r0 + N],
+                        "dact": dact[r0:r0 + N]})
+        logits, losses = [p["logits"] for p in per], [p["losses"] for p in per]
+        self.last = {"logits": logits, "losses": losses, "patch_num": per[-1]["patch_num"], "keep_num": per[-1]["keep_num"], "rows": None,
+                     "score": None, "R": 0, "tokens": None, "H_student": per[-1]["H_student"], "H_teacher": None, "bags": per, "layout": lay,
+                     "ws": ws, "exec": True}
+        self._micro = n
+        if inside:
+            fl.step += 1
+            ops.step_images(None)
+            self._micro = 0
+        elif update:
+            self.update()
+        return logits, losses
+
+    def _pure_window_step(self, bags, labels, i, perms, shuffles, update):
+        """window_step of a 'mhim_pure' trainer with accumulation_steps > 1: the native ragged window when it takes the bags (a SHORTER last
+        window too: 1 <= len(bags) <= accumulation_steps, scaled by 1 / len(bags) - base_engine.py:30,50-51,102), else today's bag-after-bag
+        route, which scales by 1 / accumulation_steps and so needs exactly that many bags."""
+        k = len(bags)
+        assert 1 <= k <= self.accum and len(labels) == k, "window_step takes at most accumulation_steps bags"
+        xs = [self.s._check_x(b) for b in bags]
+        if perms is None and shuffles is None and self._pure_window_ok(xs, labels):
+            return self._exec_pure_window(xs, labels, update)
+        assert k == self.accum, "window_step takes exactly accumulation_steps bags"
+        outs = [self.train_step(b, l, i=i, **({} if perms is None else {"perm": perms[j], "ids_shuffle": shuffles[j]}))
+                for j, (b, l) in enumerate(zip(bags, labels))]
+        return [o[0] for o in outs], [o[1] for o in outs]
 
     def _exec_cfg(self):
         """The mhimx_step_cfg of this trainer: parameter / gradient pointers into the flat buffers (stable for the trainer's lifetime), the
@@ -1021,6 +1119,8 @@ class FusedTrainer:
         Each bag's loss is scaled by 1 / accumulation_steps in the head kernel (base_engine.py:102).  Capturable (``capture_window``).
         Returns ([logits per bag], [losses per bag])."""
         k = len(bags)
+        if self.model_kind == "mhim_pure" and self.accum > 1:
+            return self._pure_window_step(bags, labels, i, perms, shuffles, update)
         assert k == self.accum and len(labels) == k, "window_step takes exactly accumulation_steps bags"
         xs = [self.s._check_x(b) for b in bags]
         if not self.window_ok(xs, i) or perms is not None or self.world > 1:
@@ -1103,7 +1203,10 @@ class FusedTrainer:
         window's streams; ``graph.replay()`` runs prep, the k bags, the slab sum, Adam + EMA."""
         if self.world > 1:
             raise mh.L.MhimxError("capture_window: one process (data-parallel ranks exchange gradients between windows: use capture())")
-        if not self.window_ok([self.s._check_x(b) for b in bags], kw.get("i")):
+        if self.model_kind == "mhim_pure" and self.accum > 1:
+            if not self._pure_window_ok([self.s._check_x(b) for b in bags], labels):
+                raise mh.L.MhimxError("capture_window: mhimx_pure_window_run does not take these bags / this model")
+        elif not self.window_ok([self.s._check_x(b) for b in bags], kw.get("i")):
             raise mh.L.MhimxError("capture_window: these bags / this model do not take the single-pass ABMIL step")
         self._capturing = True
         try:

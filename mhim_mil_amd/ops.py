@@ -1002,6 +1002,28 @@ def infer_many(cfg, xs, labels=None, want_attn=False, want_score=False, want_z=F
     return r
 
 
+# ------------------------------------------------------------------------------------------- ragged pure accumulation window
+def pure_window_bags(xs, labels, seeds):
+    """The by-value bag table of mhimx_pure_window_run: xs [N_b, D] fp32 GPU matrices with unit column stride, labels int64 [1] device
+    tensors, seeds the bags' dropout seeds."""
+    n = len(xs)
+    return (L.PureWindowBag * max(n, 1))(*[L.PureWindowBag(X=x.data_ptr(), ldx=x.stride(0), N=x.shape[0], label_dev=l.data_ptr(), drop_seed=int(sd))
+                                           for x, l, sd in zip(xs, labels, seeds)])
+
+
+def pure_window_layout(cfg, bags, n):
+    """mhimx_pure_window_layout_of: host arithmetic only (no device needed)."""
+    lay = L.PureWindowLayout()
+    L.check(L.lib().mhimx_pure_window_layout_of(C.byref(cfg), n, bags, C.byref(lay)), "mhimx_pure_window_layout_of")
+    return lay
+
+
+def pure_window_run(cfg, bags, n, host_step, ws, update):
+    """ONE optimiser update (update = False: the summed gradient only) over the n bags of the table as one C call."""
+    L.check(L.lib().mhimx_pure_window_run(_stream(), C.byref(cfg), n, bags, int(host_step), ws.data_ptr(), ws.numel(), int(bool(update))),
+            "mhimx_pure_window_run")
+
+
 # ------------------------------------------------------------------------------------------- streamed Nystrom attention
 class NysOperands:
     """mhimx_nys: the packed to_qkv output qkv [T, 1536] (q | k | v, heads = 64-column groups), the landmark means lm [256, 1024]
