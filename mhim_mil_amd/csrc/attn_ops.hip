@@ -904,8 +904,7 @@ extern "C" int mhimx_pinv_init_bwd(void* stream, const float* dz, const float* z
 extern "C" int mhimx_resconv(void* stream, const float* v, int64_t ldv, const float* w, int64_t KS, int64_t dh, int64_t T, int64_t C,
                              float* out, int64_t ldo, int32_t accumulate, int32_t flip) {
   MHIMX_CHECK_ARG(v && w && out && KS % 2 == 1 && C % dh == 0, "resconv: bad args");
-  static const bool strips = getenv("MHIMX_RESCONV_STRIPS") != nullptr;  // (experiments: the register-sliding strips)
-  if (KS == 33 && !strips && C % RT_CH == 0 && ldv % 4 == 0 && ((uintptr_t)v & 15) == 0) {
+  if (KS == 33 && C % RT_CH == 0 && ldv % 4 == 0 && ((uintptr_t)v & 15) == 0) {
     hipLaunchKernelGGL(resconv_tile_kernel<33>, dim3((unsigned)cdiv(T, RT_ROWS), (unsigned)(C / RT_CH)), dim3(256), 0, (hipStream_t)stream, v, ldv,
                        w, (int)dh, T, (int)C, out, ldo, accumulate, flip);
     MHIMX_LAUNCH_CHECK();

@@ -1,4 +1,4 @@
-// bag_project_ws.hip — the bag projection of bag_project.hip (teacher + student, ONE pass over the raw fp32 bag, 3-term bf16) with
+// bag_project_ws.hip — the kernel of mhimx_bag_project (teacher + student, ONE pass over the raw fp32 bag, 3-term bf16: bag_project.hip) with
 // SPECIALISED waves and a ping-pong of the two consumer waves of every SIMD:
 //
 //   8 consumer waves (2 (M) x 4 (N) of 80 x 64 outputs, as in bag_project.hip) touch no global memory in the k loop: a k-step is a
@@ -8,7 +8,8 @@
 //   4 producer waves (one per SIMD) own the whole global -> LDS stream: the raw fp32 rows of X through registers (split to bf16 hi / lo on
 //     the way, the paired 128-byte row image), the paired weight planes by LDS-DMA.  Their waits on memory stall nobody's MFMA issue.
 //
-// Why (round 3 measurements on bag_project.hip): in its lock-step loop all eight waves read LDS, then all eight
+// Why (round 3 measurements on the uniform 8-wave form bag_project.hip keeps for its ragged kernels): in its lock-step loop
+// all eight waves read LDS, then all eight
 // issue MFMAs (MFMA-only loop 27 us, everything but the MFMAs 33 us, together 55 us); a ping-pong of UNspecialised waves hid the
 // fragment reads (no-global-traffic loop 35 us) but its load phase - reads + split + stores + four DMA issues (~60-100 cycles each) + the
 // wait on the landing data - was 1.8x the MFMA phase and set the pace (71 us, no gain).  The global stream alone needs ~26 us of the
@@ -372,9 +373,7 @@ __global__ __launch_bounds__(WTHREADS) void bag_project_ws_kernel(mhimx_bag_proj
   // ---------------------------------------------------------------- producers' state (256 threads own the global -> LDS stream)
   // (a lean instruction stream matters: a producer wave shares its SIMD's issue with two consumer waves - the first version spent ~250
   // instructions per k-step here, mostly 64-bit address arithmetic and unpacked conversions, and its slot outlasted the 60-MFMA phase)
-#ifndef PW_PROD_PRIO
-#define PW_PROD_PRIO 1
-#endif
+  constexpr int PW_PROD_PRIO = 1;
   const int pt = tid - 64 * W_CONS, pw = wave - W_CONS;
   const unsigned lds0 = (unsigned)(uintptr_t)(lptr_f)smem;
   // A: 160 rows x 8 sixteen-byte units per k-step = 1280 units, five per thread: unit u = pt + 256 j -> row u >> 3, slot u & 7
@@ -563,7 +562,6 @@ __global__ __launch_bounds__(WTHREADS) void bag_project_ws_kernel(mhimx_bag_proj
         const uchar4 mk = *reinterpret_cast<const uchar4*>(H.drop_mask + m * g.E + n);
         ks[0] = mk.x ? inv_keep : 0.f; ks[1] = mk.y ? inv_keep : 0.f; ks[2] = mk.z ? inv_keep : 0.f; ks[3] = mk.w ? inv_keep : 0.f;
       }
-#ifndef PW_EPI_NOHASH
       else if (hashed) {
         const uint32_t rk = rkeys[r];
         const uint32_t h0 = pw_pair_hash(rk, (uint32_t)(n >> 1)), h1 = pw_pair_hash(rk, (uint32_t)(n >> 1) + 1u);
@@ -572,18 +570,6 @@ __global__ __launch_bounds__(WTHREADS) void bag_project_ws_kernel(mhimx_bag_proj
         ks[2] = (h1 & 0xffffu) >= thr16 ? inv_keep : 0.f;
         ks[3] = (h1 >> 16) >= thr16 ? inv_keep : 0.f;
       }
-#endif
-#ifdef PW_EPI_NOACT
-      if (dact) {
-        pw_h4 d;
-        for (int q = 0; q < 4; ++q) { d[q] = (_Float16)(v[q] * ks[q]); v[q] = v[q] * ks[q]; }
-#ifdef MHIMX_PROJ_WT2
-        st_b8_wt(dact + m * g.E + n, __builtin_bit_cast(f32x2_wt, d));
-#else
-        *reinterpret_cast<pw_h4*>(dact + m * g.E + n) = d;
-#endif
-      } else
-#endif
       if (dact) {
         pw_h4 d;
 #pragma unroll
@@ -593,11 +579,7 @@ __global__ __launch_bounds__(WTHREADS) void bag_project_ws_kernel(mhimx_bag_proj
           v[q] = y * ks[q];
           d[q] = (_Float16)(gq * ks[q]);
         }
-#ifdef MHIMX_PROJ_WT2
-        st_b8_wt(dact + m * g.E + n, __builtin_bit_cast(f32x2_wt, d));
-#else
         *reinterpret_cast<pw_h4*>(dact + m * g.E + n) = d;
-#endif
       } else {
 #pragma unroll
         for (int q = 0; q < 4; ++q) v[q] = act_fwd(v[q], g.act) * ks[q];
@@ -608,11 +590,7 @@ __global__ __launch_bounds__(WTHREADS) void bag_project_ws_kernel(mhimx_bag_proj
         rq2 = ld_res(r + 3 * (W_CONS + W_PROD));
         v[0] += rr[0]; v[1] += rr[1]; v[2] += rr[2]; v[3] += rr[3];
       }
-#if defined(MHIMX_PROJ_WT) || defined(MHIMX_PROJ_WT2)
-      st_f4_wt(H.H + m * H.ldh + n, f32x4{v[0], v[1], v[2], v[3]});
-#else
       *reinterpret_cast<f32x4*>(H.H + m * H.ldh + n) = f32x4{v[0], v[1], v[2], v[3]};
-#endif
     }
     PE_MARK(3);
   }
@@ -815,9 +793,6 @@ __global__ __launch_bounds__(WTHREADS) void bag_project_ws_kernel(mhimx_bag_proj
       MT_WAIT9(0, x, 0, 14);
     };
     auto compute_phase = [&]() {
-#ifdef PW_NOMMA
-      return;
-#endif
       mt_term(x, 5, 10, acc);                                               // lo*hi
       mt_term(x, 0, 14, acc);                                               // hi*lo
       mt_term(x, 0, 10, acc);                                               // hi*hi
@@ -825,9 +800,6 @@ __global__ __launch_bounds__(WTHREADS) void bag_project_ws_kernel(mhimx_bag_proj
     slot_end();                                                             // ---- tile 0 complete (producers' prologue)
 #ifdef PW_PROF
     pf_t1 = __builtin_readcyclecounter();
-#endif
-#ifdef PW_G1_PRIO
-    if (wm != 0) __builtin_amdgcn_s_setprio(PW_G1_PRIO);
 #endif
     const bool late = wm != 0;                                              // group 1 runs the same loop one slot later
     if (late) slot_end();
@@ -840,9 +812,6 @@ __global__ __launch_bounds__(WTHREADS) void bag_project_ws_kernel(mhimx_bag_proj
       so = so == 2 * WSTAGE ? 0u : so + WSTAGE;
     }
     if (!late) slot_end();
-#ifdef PW_G1_PRIO
-    __builtin_amdgcn_s_setprio(0);
-#endif
 #ifdef PW_PROF
     pf_t2 = __builtin_readcyclecounter();
 #endif
@@ -928,14 +897,9 @@ int bag_project_ws(hipStream_t st, const mhimx_bag_project_args* bags, int n_bag
   ProjBags pb = {};
   pb.n_bags = n_bags;
   pb.tiles_per_bag = (int)(8 * cdiv(nM, 8));
-  {
-    // half of a steady-state tile's life in shader cycles: k-step ~2.5 k, prologue + epilogue ~22 k (profiles/r05_store_path.md);
-    // MHIMX_PROJ_STAGGER=0 switches the offset off, another value replaces the estimate
-    static const int stagger_env = [] { const char* e = getenv("MHIMX_PROJ_STAGGER"); return e ? atoi(e) : -1; }();
-    pb.stagger = stagger_env >= 0 ? stagger_env : (int)((g.D / WBK) * 1250 + 11000);
-    static const int spread_env = [] { const char* e = getenv("MHIMX_PROJ_SPREAD"); return e ? atoi(e) : 1; }();
-    pb.stagger_spread = spread_env;         // (c3 same-box: 8.523 -> 8.479 ms against the one half-tile offset, which itself measured 0 to -1 %)
-  }
+  // half of a steady-state tile's life in shader cycles: k-step ~2.5 k, prologue + epilogue ~22 k (profiles/r05_store_path.md)
+  pb.stagger = (int)((g.D / WBK) * 1250 + 11000);
+  pb.stagger_spread = 1;                    // (c3 same-box: 8.523 -> 8.479 ms against the one half-tile offset, which itself measured 0 to -1 %)
   for (int b = 0; b < n_bags; ++b) {
     pb.X[b] = bags[b].X;
     for (int h = 0; h < g.n_heads; ++h) {
@@ -945,10 +909,9 @@ int bag_project_ws(hipStream_t st, const mhimx_bag_project_args* bags, int n_bag
     }
   }
   // persistent workgroups (one per CU; the grid stays a multiple of 8: XCD mapping) unless the launch is scored (its epilogue pairs workgroups
-  // through a gate: every tile needs its partner resident) or MHIMX_PROJ_PERSIST=0 asks for one workgroup per tile
-  static const bool persist = [] { const char* e = getenv("MHIMX_PROJ_PERSIST"); return !(e && e[0] == '0'); }();
+  // through a gate: every tile needs its partner resident)
   unsigned nblocks = (unsigned)(nN * pb.tiles_per_bag * n_bags);
-  if (persist && !g.score0 && nblocks > W_CUS) nblocks = W_CUS;
+  if (!g.score0 && nblocks > W_CUS) nblocks = W_CUS;
   dim3 grid(nblocks);
   bool plain = !g.score0 && g.act == MHIMX_ACT_NONE;
   for (int b = 0; b < n_bags && plain; ++b)
@@ -956,8 +919,7 @@ int bag_project_ws(hipStream_t st, const mhimx_bag_project_args* bags, int n_bag
       const mhimx_proj_head& q = bags[b].head[h];
       if (q.drop_p > 0.f || q.drop_mask || q.resid || q.dact) plain = false;
     }
-  static const bool plain_ok = [] { const char* e = getenv("MHIMX_PROJ_PLAIN"); return !(e && e[0] == '0'); }();
-  if (plain && plain_ok) hipLaunchKernelGGL(bag_project_ws_kernel<3>, grid, dim3(WTHREADS), WNST * WSTAGE, st, g, pb, sc);
+  if (plain) hipLaunchKernelGGL(bag_project_ws_kernel<3>, grid, dim3(WTHREADS), WNST * WSTAGE, st, g, pb, sc);
   else if (g.score0 && g.head[0].H) hipLaunchKernelGGL(bag_project_ws_kernel<2>, grid, dim3(WTHREADS), WNST * WSTAGE, st, g, pb, sc);
   else if (g.score0) hipLaunchKernelGGL(bag_project_ws_kernel<1>, grid, dim3(WTHREADS), WNST * WSTAGE, st, g, pb, sc);
   else hipLaunchKernelGGL(bag_project_ws_kernel<0>, grid, dim3(WTHREADS), WNST * WSTAGE, st, g, pb, sc);

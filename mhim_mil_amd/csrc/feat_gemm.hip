@@ -152,16 +152,10 @@ __global__ __launch_bounds__(FTHREADS) void feat_gemm_kernel(mhimx_gemm_nt_args 
   auto step = [&](f32x4 (&cur)[NFR], f32x4 (&nxt)[NFR], int t) {      // needs t + 1 < nk
     wait_tiles((nk - 1 < t + 3 ? nk - 1 : t + 2) - (t + 1));          // tile t+1 landed (tiles younger than it may fly on)
     __builtin_amdgcn_s_barrier();
-#ifndef FG_NODMA
     if (t + 3 < nk) issue(t + 3);
-#endif
-#ifndef FG_NOLDS
     read_tile(nxt, t + 1);                                            // in flight under the 60 MFMAs below
-#endif
     __builtin_amdgcn_sched_barrier(0);
-#ifndef FG_NOMMA
     fg_mma(cur, acc);
-#endif
     __builtin_amdgcn_sched_barrier(0);
     FG_WAIT18(nxt);
   };
@@ -169,16 +163,10 @@ __global__ __launch_bounds__(FTHREADS) void feat_gemm_kernel(mhimx_gemm_nt_args 
   auto hot = [&](f32x4 (&cur)[NFR], f32x4 (&nxt)[NFR], int t) {
     asm volatile("s_waitcnt vmcnt(9)" ::: "memory");
     __builtin_amdgcn_s_barrier();
-#ifndef FG_NODMA
     issue(t + 3);
-#endif
-#ifndef FG_NOLDS
     read_tile(nxt, t + 1);
-#endif
     __builtin_amdgcn_sched_barrier(0);
-#ifndef FG_NOMMA
     fg_mma(cur, acc);
-#endif
     __builtin_amdgcn_sched_barrier(0);
     FG_WAIT18(nxt);
   };
@@ -254,9 +242,6 @@ __global__ __launch_bounds__(FTHREADS) void feat_gemm_kernel(mhimx_gemm_nt_args 
     f32x4* c = reinterpret_cast<f32x4*>(g.C + m * g.ldc + n);
     f32x4 o = f32x4{v[0], v[1], v[2], v[3]};
     if (g.accumulate) { const f32x4 old = *c; o += old; }
-#ifdef FG_NOSTORE
-    if (v[0] == 1.2345e-30f)
-#endif
     *c = o;
   }
 }

@@ -13,7 +13,6 @@
 // 16-byte aligned rows.
 #include <string.h>
 
-#include <stdlib.h>
 #include "common.hpp"
 #include "mca2_rows.hpp"
 #include "prep_jobs.hpp"
@@ -264,12 +263,7 @@ __global__ __launch_bounds__(64 * NW) void gemm_nt_dma_kernel(mhimx_gemm_nt_args
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
     __builtin_amdgcn_s_barrier();                      // tile t landed for every wave; everyone left tile t-1
-#ifndef MHIMX_DBG_NODMA
     if (t + NSTAGE - 1 < nk) issue((int64_t)(t + NSTAGE - 1) * DBK, (t + NSTAGE - 1) % NSTAGE);
-#endif
-#ifdef MHIMX_DBG_NOCOMPUTE
-    continue;
-#endif
     const unsigned so = (unsigned)((t % NSTAGE) * STAGE_BYTES);
     f4 x[NRD], y[NRD];
     lds_read<NRD>(x, fa, so, 0u);                         // ks = 0
@@ -691,16 +685,11 @@ int gemm_tn_dma(hipStream_t st, const mhimx_gemm_tn_args& g0, int64_t ws_floats_
   int rows_blocks = 0;
   if (rows_ride) {
     rows_blocks = (int)align_up(rider->w.T, 8);
-    // (a bag-batched launch - common.hpp: every bag of the window brings its own product and row tiles - sizes each bag's product for its share
-    // of two rounds of the chip, at least 8 slabs)
-    const int nbags = cur_batch().n > 0 ? cur_batch().n : 1;
-    int64_t room = (nbags > 1 ? 512 / nbags : 256) - rows_blocks;
-    if (nbags > 1 && room < 8 * tiles) room = 8 * tiles;
-    int cap = (int)(room / tiles) / 8 * 8;
-    // (MEASURED, 8 bags: with the rows riding every workgroup of the launch takes the rows pass's LDS - one per CU, 768 workgroups, three rounds,
-    // 131 us; apart, the product keeps its own slab count and the rows pass is a launch of two rounds.  MHIMX_WINDOW_ROWS_RIDE=1: together)
-    static const bool batched_ride = getenv("MHIMX_WINDOW_ROWS_RIDE") != nullptr && atoi(getenv("MHIMX_WINDOW_ROWS_RIDE")) != 0;
-    if (cap < 8 || rows_blocks > 128 || (nbags > 1 && !batched_ride)) rows_blocks = 0;      // no room for the product beside the rows: they do not ride
+    const int cap = (int)((256 - rows_blocks) / tiles) / 8 * 8;
+    // In a bag-batched launch (common.hpp: every bag of the window brings its own product and row tiles) the rows never ride.  MEASURED, 8 bags:
+    // with the rows riding every workgroup of the launch takes the rows pass's LDS - one per CU, 768 workgroups, three rounds, 131 us; apart, the
+    // product keeps its own slab count and the rows pass is a launch of two rounds.
+    if (cap < 8 || rows_blocks > 128 || cur_batch().n > 1) rows_blocks = 0;      // no room for the product beside the rows: they do not ride
     else if (splits > cap) splits = cap;
   }
   if (size_only) { rows_blocks = 0; rider = nullptr; }

@@ -20,7 +20,6 @@
 // Built for E = 512, 8 heads x 64, k <= 6 (J <= 48), R <= 32768 (the merge of the row-tile partials walks chunks of 256 tiles); other
 // shapes take mca.hip's general path.
 #include <math.h>
-#include <stdlib.h>
 #include <string.h>
 
 #include "mca2_rows.hpp"
@@ -315,8 +314,6 @@ static int merge2_side_of(const mhimx_merge* m, const float* X, int64_t R, const
 // tokens' gradient rows - instead of the stage being a 14 us launch of its own between the pool backward and the rows pass.
 int merge2_bwd_park(const mhimx_merge* m, const float* X, int64_t R, const float* dz, float* dX, const mhimx_merge_grad* gr, void* ws, int64_t ws_bytes) {
   if (!gr->defer || gr->defer->pre.pending != 0) return 0;
-  static const bool ride = getenv("MHIMX_MERGE_PRE_RIDE") == nullptr || atoi(getenv("MHIMX_MERGE_PRE_RIDE")) != 0;
-  if (!ride) return 0;
   Merge2Side sd;
   if (int r = merge2_side_of(m, X, R, dz, dX, gr, ws, ws_bytes, &sd)) return r;
   static_assert(sizeof(Merge2Side) <= sizeof(gr->defer->pre.blob), "Merge2Side must fit mhimx_reduce_list.pre");
@@ -341,13 +338,12 @@ int merge2_bwd(hipStream_t st, const mhimx_merge* m, const float* X, int64_t R, 
   // (round 5) The pool backward's scorer-weight-gradient GEMM waits in the list; it feeds the optimiser only.  Round 2-4: launched here with
   // this backward's parameter-only first stage riding (16.6 us), THEN the rows pass (23.9 us on 31 CUs).  Now: the first stage as a small
   // launch of its own (it is all the rows pass waits for), then ONE launch of rows pass + product - the row tiles' 31 CUs beside the
-  // product's 224: what was 40.5 us of serial chain is the longer of the two.  MHIMX_MERGE_BWD_FUSE=0: the round-4 order.
-  static const bool fuse_rows = getenv("MHIMX_MERGE_BWD_FUSE") == nullptr || atoi(getenv("MHIMX_MERGE_BWD_FUSE")) != 0;
+  // product's 224: what was 40.5 us of serial chain is the longer of the two.  (A first stage that found no ride: the round-4 order.)
   if (gr->defer && gr->defer->parked.pending) {
     mhimx_gemm_tn_args pg;
     memcpy(&pg, gr->defer->parked.blob, sizeof(pg));
     gr->defer->parked.pending = 0;
-    if (fuse_rows && pre_done) {
+    if (pre_done) {
       const int rc = gemm_tn_rider(st, pg, &sd, 4);
       if (rc < 0) return rc;
       rows_done = rc == 1;
@@ -375,8 +371,7 @@ int merge2_bwd(hipStream_t st, const mhimx_merge* m, const float* X, int64_t R, 
     MHIMX_LAUNCH_CHECK();
   }
   // the parameter-gradient tail: U [J, E] takes the place of the fp32 copy of aq (not needed any more)
-  static const bool no_ride = getenv("MHIMX_MERGE_NO_RIDE") != nullptr;      // (experiments: the tail as three launches of its own)
-  if (!no_ride && gr->defer && gr->defer->side.pending == 0) {
+  if (gr->defer && gr->defer->side.pending == 0) {
     // deferred: the three stages ride in later launches of this backward (mhimx_rows_dpre, the weight-gradient mhimx_gemm_tn,
     // mhimx_reduce_flush); whatever did not get a ride is launched by mhimx_reduce_flush before the reductions
     memcpy(gr->defer->side.blob, &sd, sizeof(sd));

@@ -1,7 +1,6 @@
 // mca2_prep.hpp — the pieces of the projection-free Merge (mca2.hip) that the step's preparation launch (gemm_dma.hip) shares: workspace
 // layout, fragment-image stores, and the parameter-only kernel body (gq = LN(q), Q, aq and its images).
 #pragma once
-#include <stdlib.h>
 
 #include "mma_tile.hpp"
 
@@ -40,8 +39,6 @@ MHIMX_DEV void bag_move(Merge2Ws& w, const BagBatch& bb) {
 // LayerNorm reductions and matrix-core steps of every wave and double the CUs at work (c2: 970 rows, 31 -> 61 workgroups).  Long row
 // lists keep 32 rows (the per-tile pooled partials are [48, 512] floats each: twice the tiles = twice that traffic).
 inline int m2_tile_rows(int64_t R) {
-  static const int forced = getenv("MHIMX_MERGE_TILE") ? atoi(getenv("MHIMX_MERGE_TILE")) : 0;
-  if (forced == 16 || forced == 32) return forced;
   return R <= 4096 ? 16 : 32;
 }
 

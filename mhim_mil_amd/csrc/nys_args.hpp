@@ -1,5 +1,5 @@
 // nys_args.hpp - the kernel argument block shared by the two translation units of the streamed Nystrom attention
-// (nys_flash.hip: landmark-column kernels, 8 waves; nys_flash_tok.hip: token-column kernels, 4 waves).
+// (nys_flash.hip: landmark-column kernels, 8 waves; nys_flash_tok.hip: token-owning kernels, 8 waves).
 #pragma once
 #include "mma_tile.hpp"
 
@@ -29,7 +29,6 @@ struct NyArgs {
 
 
 // token-column kernels (nys_flash_tok.hip): enqueue only
-int nytok_out_fwd(hipStream_t st, const NyArgs& g);
 int nytok_out_bwd_q(hipStream_t st, const NyArgs& g);
 int nytok_a3v_bwd_t(hipStream_t st, const NyArgs& g, int mode);
 

@@ -26,7 +26,6 @@
 // Sums across the four waves (softmax statistics, partial outputs) go through LDS in a FIXED order: results are run-to-run identical.
 // Measured and not kept (round 3): two image buffers with ONE barrier per tile and the two waves of a SIMD staging the next tile at
 // opposite ends of the iteration (one wave's split / store work under the other's products): a3v forward 108.3 -> 105.9 us per entry.
-#include <stdlib.h>
 #include <string.h>
 
 #include "nys_args.hpp"
@@ -656,9 +655,7 @@ static int ny_base(const mhimx_nys* a, NyArgs& g, const char* who) {
   const int64_t tiles = a->T / NY_TT;
   // one workgroup per CU: 64 chunks (two per CU; the landmark-column kernels would fit) measured SLOWER - a3v forward + merge 146 vs
   // 125 us, out backward 365 vs 341 us: twice the partials to write and merge, and these kernels are not latency-bound
-  static const int lch = getenv("MHIMX_NYS_LMCH") ? atoi(getenv("MHIMX_NYS_LMCH")) : NY_MAXCH;   // (experiments; <= NY_MAXCH)
-  const int per = lch < 1 ? 1 : (lch > NY_MAXCH ? NY_MAXCH : lch);
-  g.nch = (int)(tiles < per ? tiles : per);
+  g.nch = (int)(tiles < NY_MAXCH ? tiles : NY_MAXCH);
   return 0;
 }
 
@@ -687,8 +684,6 @@ extern "C" int mhimx_nys_out_fwd(void* stream, const mhimx_nys* a, const float* 
   if (int e = ny_base(a, g, "nys_out_fwd")) return e;
   MHIMX_CHECK_ARG(a->q && a->kl && w2 && out && aligned16(a->q) && aligned16(a->kl) && aligned16(out) && ldo % 4 == 0, "nys_out_fwd: null / unaligned operands");
   g.w2 = w2; g.out = out; g.ldo = ldo; g.lse1_o = lse1; g.accumulate = accumulate;
-  static const bool v1 = getenv("MHIMX_NYS_OUT_V1") != nullptr;         // (experiments: the landmark-split form with cross-wave sums)
-  if (v1) return nytok_out_fwd((hipStream_t)stream, g);
   MHIMX_ONCE_PER_DEVICE(MHIMX_HIP(hipFuncSetAttribute((const void*)ny_out_fwd_tok8_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, NY_SM_OUT8)));
   const int64_t tiles = g.T / NY_TT;
   g.nch = (int)(tiles < NY_TOKCH ? tiles : NY_TOKCH);                    // 128 KB of LDS: one workgroup per CU

@@ -1,16 +1,14 @@
-// nys_flash_tok.hip - the TOKEN-COLUMN kernels of the streamed Nystrom attention (see nys_flash.hip for the scheme): out forward, its
-// token-side backward (dq), the token-side backward of a3v (dk, dv) and the cls row.  Their products contract over the landmarks, so
-// the waves' partial outputs are summed through LDS: 4 waves x 64 landmarks (1 wave per SIMD, 3 barriers per 32-token half) measured
-// faster here than 8 x 32 (twice the partials to write and read per output: 196 vs 140 us for the out forward at T = 50 176), the
-// opposite of the landmark-column kernels, which have no cross-wave step at all.
+// nys_flash_tok.hip - the TOKEN-COLUMN kernels of the streamed Nystrom attention (see nys_flash.hip for the scheme): the token-side
+// backward of out (dq), the token-side backward of a3v (dk, dv) and the cls row, all in the token-owning form: a wave owns 16 tokens and
+// ALL 256 landmarks, so there is no cross-wave sum and no barrier in the loop.  (The landmark-split form these replaced - 4 waves x 64
+// landmarks, the waves' partial outputs summed through LDS with 3 barriers per 32-token half - measured 281 vs 156 us for dk / dv and
+// 199 vs 103 us for dq at T = 50 176.)
 #include "nys_args.hpp"
 
 namespace mhimx {
 namespace nytok {
 
-constexpr int NY_THREADS = 256;
 MHIMX_DEV float ny_kgsum(float v) { v += __shfl_xor(v, 16); v += __shfl_xor(v, 32); return v; }
-MHIMX_DEV float ny_kgmax(float v) { v = fmaxf(v, __shfl_xor(v, 16)); v = fmaxf(v, __shfl_xor(v, 32)); return v; }
 
 MHIMX_DEV void ny_split8(const float (&v)[8], f32x4& hi_o, f32x4& lo_o) {
   bf8 hi, lo;
@@ -28,447 +26,10 @@ MHIMX_DEV void ny_split44(const f32x4& a, const f32x4& b, f32x4& hi, f32x4& lo) 
   ny_split8(v, hi, lo);
 }
 
-// ---- token tile: thread = (token pair p = tid >> 3, dim octet g = tid & 7); r[0..1] = token 2p dims 8g..8g+7, r[2..3] = token 2p+1
-MHIMX_DEV void ny_load(const float* base, int64_t ld, int64_t t0, int tid, f32x4 (&r)[4]) {
-  const float* p = base + (t0 + 2 * (tid >> 3)) * ld + 8 * (tid & 7);
-  r[0] = *reinterpret_cast<const f32x4*>(p);
-  r[1] = *reinterpret_cast<const f32x4*>(p + 4);
-  r[2] = *reinterpret_cast<const f32x4*>(p + ld);
-  r[3] = *reinterpret_cast<const f32x4*>(p + ld + 4);
-}
-// RM image: fragment (tb, ks, hl) at ((tb*2 + ks)*2 + hl) KiB, lane (token & 15, dim octet & 3) x 16 B
-MHIMX_DEV void ny_store_rm(char* img, int tid, const f32x4 (&r)[4]) {
-  const int g = tid & 7, t = 2 * (tid >> 3);
-  f32x4 hi, lo;
-#pragma unroll
-  for (int e = 0; e < 2; ++e) {
-    ny_split44(r[2 * e], r[2 * e + 1], hi, lo);
-    char* p = img + ((((t + e) >> 4) * 2 + (g >> 2)) * 2) * 1024 + ((g & 3) * 16 + (((t + e) & 15) ^ g)) * 16;   // ^ (octet + 4 ks): nys_flash.hip
-    *reinterpret_cast<f32x4*>(p) = hi;
-    *reinterpret_cast<f32x4*>(p + 1024) = lo;
-  }
-}
-MHIMX_DEV f32x4 ny_frag(const char* img, int blk, int step, int hl, int lane) {      // RM images only (the swizzle of ny_store_rm)
-  return *reinterpret_cast<const f32x4*>(img + (((blk * 2 + step) * 2 + hl) * 64 + (lane ^ ((lane >> 4) + 4 * step))) * 16);
-}
-
-// ---- landmark-side fragments (global fp32 -> registers), M = [256, 64] of this head with row pitch ldm, the wave's landmarks at lm0
-struct NyFrag { f32x4 h[4][2], l[4][2]; };
-// LM: [lb][ks] : lane (c, kg) holds M[lm0 + 16 lb + c][32 ks + 8 kg .. +7]
-MHIMX_DEV void ny_lm_frags(const float* M, int64_t ldm, int lm0, int lane, NyFrag& f) {
-  const int c = lane & 15, kg = lane >> 4;
-#pragma unroll
-  for (int lb = 0; lb < 4; ++lb)
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-      const float* p = M + (int64_t)(lm0 + 16 * lb + c) * ldm + 32 * ks + 8 * kg;
-      ny_split44(*reinterpret_cast<const f32x4*>(p), *reinterpret_cast<const f32x4*>(p + 4), f.h[lb][ks], f.l[lb][ks]);
-    }
-}
-// LT: [db][s] : lane (c, kg) holds M[lm0 + 32 s + 16 blk + 4 kg + i][16 db + c] at slot 4 blk + i
-MHIMX_DEV void ny_lt_frags(const float* M, int64_t ldm, int lm0, int lane, NyFrag& f) {
-  const int c = lane & 15, kg = lane >> 4;
-#pragma unroll
-  for (int db = 0; db < 4; ++db)
-#pragma unroll
-    for (int s = 0; s < 2; ++s) {
-      float v[8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) v[j] = M[(int64_t)(lm0 + 32 * s + 16 * (j >> 2) + 4 * kg + (j & 3)) * ldm + 16 * db + c];
-      ny_split8(v, f.h[db][s], f.l[db][s]);
-    }
-}
-
-// c[j] += a x b[j], j < NB, 3 bf16 terms, term-major (NB independent MFMAs between two on the same accumulator)
-template <int NB>
-MHIMX_DEV void ny_mma_a(const f32x4& ah, const f32x4& al, const f32x4 (&bh)[NB], const f32x4 (&bl)[NB], f32x4 (&c)[NB]) {
-#pragma unroll
-  for (int j = 0; j < NB; ++j) c[j] = mt_mfma(al, bh[j], c[j]);
-#pragma unroll
-  for (int j = 0; j < NB; ++j) c[j] = mt_mfma(ah, bl[j], c[j]);
-#pragma unroll
-  for (int j = 0; j < NB; ++j) c[j] = mt_mfma(ah, bh[j], c[j]);
-}
-MHIMX_DEV void ny_mma1(const f32x4& ah, const f32x4& al, const f32x4& bh, const f32x4& bl, f32x4& c) {
-  c = mt_mfma(al, bh, c);
-  c = mt_mfma(ah, bl, c);
-  c = mt_mfma(ah, bh, c);
-}
-
 MHIMX_DEV void ny_chunk(const NyArgs& g, int ch, int& t_begin, int& t_end) {
   const int64_t tiles = g.T / NY_TT;
   t_begin = (int)(tiles * ch / g.nch);
   t_end = (int)(tiles * (ch + 1) / g.nch);
-}
-
-// ---- cross-wave sums of a [64 d][32 token] output: wave w's partial at part[w][token][NY_P68] (an accumulator's four values are
-// four consecutive d of one token: one 16-byte store; the reader takes 16 bytes per wave).  Conflict-free both ways: a store phase
-// is 8 lanes = 8 consecutive tokens (68 floats apart: 4 banks), a load phase 8 lanes = the 8 d-octets of one token.  The scalar
-// [w][d][36] form (64 + 64 four-byte LDS operations per thread and matrix, the reads four-way conflicted) was 18 % of these kernels.
-constexpr int NY_P68 = 68;
-constexpr int NY_PART_F = 4 * 32 * NY_P68;                    // floats of one matrix's partials
-MHIMX_DEV void ny_part_put(float* part, int w, int c, int kg, const f32x4 (&o)[4][2]) {
-#pragma unroll
-  for (int db = 0; db < 4; ++db)
-#pragma unroll
-    for (int tb = 0; tb < 2; ++tb) *reinterpret_cast<f32x4*>(part + (w * 32 + 16 * tb + c) * NY_P68 + 16 * db + 4 * kg) = o[db][tb];
-}
-MHIMX_DEV f32x4 ny_part_sum(const float* part, int tk, int d) {
-  const float* p = part + tk * NY_P68 + d;
-  return ((*reinterpret_cast<const f32x4*>(p) + *reinterpret_cast<const f32x4*>(p + 32 * NY_P68)) + *reinterpret_cast<const f32x4*>(p + 64 * NY_P68)) +
-         *reinterpret_cast<const f32x4*>(p + 96 * NY_P68);
-}
-
-#define NYT_ZERO(a, n1, n2)                \
-  _Pragma("unroll") for (int _i = 0; _i < n1; ++_i) _Pragma("unroll") for (int _j = 0; _j < n2; ++_j) a[_i][_j] = f32x4{0.f, 0.f, 0.f, 0.f}
-
-// ===========================================================================================================================
-// forward 2: out = softmax_m(q k~^T) w2.   token-column: S^T[lb][tb] = LM(k~) x RM(q); softmax over all 256 landmarks = over the
-// lane's rows, its k-octet lanes and the four waves (LDS); o^T[db][tb] = LT(w2) x P^T, summed over the waves through LDS.
-// ===========================================================================================================================
-__global__ __launch_bounds__(NY_THREADS) void ny_out_fwd_kernel(NyArgs g) {
-  extern __shared__ __attribute__((aligned(16))) char sm[];
-  float* red = reinterpret_cast<float*>(sm + NY_IMG);          // [2][4][64]
-  float* part = red + 512;                                     // [4][64 d][68]
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, c = lane & 15, kg = lane >> 4;
-  const int h = blockIdx.y, ch = blockIdx.x, lm0 = 64 * w;
-  int t_begin, t_end;
-  ny_chunk(g, ch, t_begin, t_end);
-  NyFrag kf, wt;
-  ny_lm_frags(g.kl + h * NY_D, g.ldl, lm0, lane, kf);
-  ny_lt_frags(g.w2 + (int64_t)h * NY_PART, NY_D, lm0, lane, wt);
-  const float* qb = g.q + h * NY_D;
-  f32x4 rq[4];
-  ny_load(qb, g.ld, (int64_t)t_begin * NY_TT, tid, rq);
-  for (int t = t_begin; t < t_end; ++t) {
-    __syncthreads();
-    ny_store_rm(sm, tid, rq);
-    __syncthreads();
-    if (t + 1 < t_end) ny_load(qb, g.ld, (int64_t)(t + 1) * NY_TT, tid, rq);
-    f32x4 s[4][4];                                            // [lb][tb]
-    NYT_ZERO(s, 4, 4);
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-      f32x4 bh[4], bl[4];
-#pragma unroll
-      for (int tb = 0; tb < 4; ++tb) { bh[tb] = ny_frag(sm, tb, ks, 0, lane); bl[tb] = ny_frag(sm, tb, ks, 1, lane); }
-#pragma unroll
-      for (int lb = 0; lb < 4; ++lb) ny_mma_a<4>(kf.h[lb][ks], kf.l[lb][ks], bh, bl, s[lb]);
-    }
-    float mx[4];
-#pragma unroll
-    for (int tb = 0; tb < 4; ++tb) {
-      float v = s[0][tb][0];
-#pragma unroll
-      for (int lb = 0; lb < 4; ++lb)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) v = fmaxf(v, s[lb][tb][i]);
-      v = ny_kgmax(v);
-      if (kg == 0) red[w * 64 + 16 * tb + c] = v;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int tb = 0; tb < 4; ++tb) {
-      const int tk = 16 * tb + c;
-      mx[tb] = fmaxf(fmaxf(red[tk], red[64 + tk]), fmaxf(red[128 + tk], red[192 + tk]));
-      float sum = 0.f;
-#pragma unroll
-      for (int lb = 0; lb < 4; ++lb)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const float p = NY_EXP2((s[lb][tb][i] - mx[tb]) * g.sl2e);
-          s[lb][tb][i] = p;
-          sum += p;
-        }
-      sum = ny_kgsum(sum);
-      if (kg == 0) red[256 + w * 64 + tk] = sum;
-    }
-    f32x4 o[4][4];                                            // [db][tb]
-    NYT_ZERO(o, 4, 4);
-#pragma unroll
-    for (int sx = 0; sx < 2; ++sx) {
-      f32x4 ph[4], pl[4];
-#pragma unroll
-      for (int tb = 0; tb < 4; ++tb) ny_split44(s[2 * sx][tb], s[2 * sx + 1][tb], ph[tb], pl[tb]);
-#pragma unroll
-      for (int db = 0; db < 4; ++db) ny_mma_a<4>(wt.h[db][sx], wt.l[db][sx], ph, pl, o[db]);
-    }
-#pragma unroll
-    for (int db = 0; db < 4; ++db)
-#pragma unroll
-      for (int tb = 0; tb < 4; ++tb)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) part[(w * 64 + 16 * db + 4 * kg + i) * NY_P68 + 16 * tb + c] = o[db][tb][i];
-    __syncthreads();
-    {
-      const int tk = tid >> 2, qd = tid & 3;
-      const float L = ((red[256 + tk] + red[320 + tk]) + red[384 + tk]) + red[448 + tk];
-      const float inv = 1.f / L;
-      const int64_t row = (int64_t)t * NY_TT + tk;
-      float* op = g.out + row * g.ldo + h * NY_D + 16 * qd;
-#pragma unroll
-      for (int x4 = 0; x4 < 4; ++x4) {
-        f32x4 v;
-#pragma unroll
-        for (int x = 0; x < 4; ++x) {
-          const int d = 16 * qd + 4 * x4 + x;
-          v[x] = (((part[d * NY_P68 + tk] + part[(64 + d) * NY_P68 + tk]) + part[(128 + d) * NY_P68 + tk]) + part[(192 + d) * NY_P68 + tk]) * inv;
-        }
-        if (g.accumulate) v += *reinterpret_cast<const f32x4*>(op + 4 * x4);
-        *reinterpret_cast<f32x4*>(op + 4 * x4) = v;
-      }
-      if (qd == 0 && g.lse1_o) {
-        const float M = fmaxf(fmaxf(red[tk], red[64 + tk]), fmaxf(red[128 + tk], red[192 + tk]));
-        g.lse1_o[(int64_t)h * g.T + row] = M * g.sl2e + log2f(L);
-      }
-    }
-  }
-}
-
-// ===========================================================================================================================
-// backward of out, token side: dq (and delta = sum_m P dP, saved for the landmark-side kernel).  token-column, 32-token halves:
-// S^T = LM(k~) x RM(q), dP^T = LM(w2) x RM(dout), P = exp2(S sl2e - lse1), dS = scale P (dP - delta), dq^T = LT(k~) x dS^T.
-// ===========================================================================================================================
-__global__ __launch_bounds__(NY_THREADS) void ny_out_bwd_q_kernel(NyArgs g) {
-  extern __shared__ __attribute__((aligned(16))) char sm[];
-  float* red = reinterpret_cast<float*>(sm + 2 * NY_IMG);      // [4][32]
-  float* part = red + 128;                                     // [4][32 tok][68]
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, c = lane & 15, kg = lane >> 4;
-  const int h = blockIdx.y, ch = blockIdx.x, lm0 = 64 * w;
-  int t_begin, t_end;
-  ny_chunk(g, ch, t_begin, t_end);
-  NyFrag kf, wf, kt;
-  ny_lm_frags(g.kl + h * NY_D, g.ldl, lm0, lane, kf);
-  ny_lm_frags(g.w2 + (int64_t)h * NY_PART, NY_D, lm0, lane, wf);
-  ny_lt_frags(g.kl + h * NY_D, g.ldl, lm0, lane, kt);
-  const float* qb = g.q + h * NY_D;
-  const float* gb = g.dout + h * NY_D;
-  const float* lse = g.lse1 + (int64_t)h * g.T;
-  f32x4 rq[4], rg[4];
-  ny_load(qb, g.ld, (int64_t)t_begin * NY_TT, tid, rq);
-  ny_load(gb, g.ldd, (int64_t)t_begin * NY_TT, tid, rg);
-  for (int t = t_begin; t < t_end; ++t) {
-    __syncthreads();
-    ny_store_rm(sm, tid, rq);
-    ny_store_rm(sm + NY_IMG, tid, rg);
-    __syncthreads();
-    if (t + 1 < t_end) {
-      ny_load(qb, g.ld, (int64_t)(t + 1) * NY_TT, tid, rq);
-      ny_load(gb, g.ldd, (int64_t)(t + 1) * NY_TT, tid, rg);
-    }
-    for (int hf = 0; hf < 2; ++hf) {
-      f32x4 s[4][2], dp[4][2];                                // [lb][tb2]
-      NYT_ZERO(s, 4, 2);
-      NYT_ZERO(dp, 4, 2);
-#pragma unroll
-      for (int ks = 0; ks < 2; ++ks) {
-        f32x4 bh[2], bl[2], eh[2], el[2];
-#pragma unroll
-        for (int tb = 0; tb < 2; ++tb) {
-          bh[tb] = ny_frag(sm, 2 * hf + tb, ks, 0, lane); bl[tb] = ny_frag(sm, 2 * hf + tb, ks, 1, lane);
-          eh[tb] = ny_frag(sm + NY_IMG, 2 * hf + tb, ks, 0, lane); el[tb] = ny_frag(sm + NY_IMG, 2 * hf + tb, ks, 1, lane);
-        }
-#pragma unroll
-        for (int lb = 0; lb < 4; ++lb) {
-          ny_mma_a<2>(kf.h[lb][ks], kf.l[lb][ks], bh, bl, s[lb]);
-          ny_mma_a<2>(wf.h[lb][ks], wf.l[lb][ks], eh, el, dp[lb]);
-        }
-      }
-      const int64_t tok0 = (int64_t)t * NY_TT + 32 * hf;
-#pragma unroll
-      for (int tb = 0; tb < 2; ++tb) {
-        const float ls = lse[tok0 + 16 * tb + c];
-        float dl = 0.f;
-#pragma unroll
-        for (int lb = 0; lb < 4; ++lb)
-#pragma unroll
-          for (int i = 0; i < 4; ++i) {
-            const float p = NY_EXP2(s[lb][tb][i] * g.sl2e - ls);
-            s[lb][tb][i] = p;
-            dl += p * dp[lb][tb][i];
-          }
-        dl = ny_kgsum(dl);
-        if (kg == 0) red[w * 32 + 16 * tb + c] = dl;
-      }
-      __syncthreads();
-      f32x4 o[4][2];                                          // [db][tb2]
-      NYT_ZERO(o, 4, 2);
-#pragma unroll
-      for (int tb = 0; tb < 2; ++tb) {
-        const int tk = 16 * tb + c;
-        const float dl = ((red[tk] + red[32 + tk]) + red[64 + tk]) + red[96 + tk];
-        if (w == 0 && kg == 0) g.delta[(int64_t)h * g.T + tok0 + tk] = dl;
-#pragma unroll
-        for (int lb = 0; lb < 4; ++lb)
-#pragma unroll
-          for (int i = 0; i < 4; ++i) s[lb][tb][i] = g.scale * s[lb][tb][i] * (dp[lb][tb][i] - dl);
-      }
-#pragma unroll
-      for (int sx = 0; sx < 2; ++sx) {
-        f32x4 ph[2], pl[2];
-#pragma unroll
-        for (int tb = 0; tb < 2; ++tb) ny_split44(s[2 * sx][tb], s[2 * sx + 1][tb], ph[tb], pl[tb]);
-#pragma unroll
-        for (int db = 0; db < 4; ++db) ny_mma_a<2>(kt.h[db][sx], kt.l[db][sx], ph, pl, o[db]);
-      }
-      ny_part_put(part, w, c, kg, o);
-      __syncthreads();
-      {
-        const int tk = tid >> 3, d0 = 8 * (tid & 7);
-        float* op = g.out + (tok0 + tk) * g.ldo + h * NY_D + d0;
-#pragma unroll
-        for (int x4 = 0; x4 < 2; ++x4) *reinterpret_cast<f32x4*>(op + 4 * x4) = ny_part_sum(part, tk, d0 + 4 * x4);
-      }
-    }
-  }
-}
-
-// ===========================================================================================================================
-// backward of a3v, token side: dk and dv.  token-column, 32-token halves:  S3^T = LM(q~) x RM(k), dP3^T = LM(da3v) x RM(v),
-// P = exp2(S sl2e - lse3[lm]), dS = scale P (dP - delta3[lm]);  dv^T = LT(da3v) x P^T,  dk^T = LT(q~) x dS^T.
-// MODE 1 (the cls row, no gradients): r[token] = sum_lm u[lm] P[lm, token].
-// ===========================================================================================================================
-template <int MODE>
-__global__ __launch_bounds__(NY_THREADS) void ny_a3v_bwd_t_kernel(NyArgs g) {
-  extern __shared__ __attribute__((aligned(16))) char sm[];
-  float* lmst = reinterpret_cast<float*>(sm + 2 * NY_IMG);     // lse3[256] | delta3 or u [256]
-  float* part = lmst + 512;                                    // MODE 0: [4][32 tok][68] ; MODE 1: red [4][64]
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, c = lane & 15, kg = lane >> 4;
-  const int h = blockIdx.y, ch = blockIdx.x, lm0 = 64 * w;
-  int t_begin, t_end;
-  ny_chunk(g, ch, t_begin, t_end);
-  lmst[tid] = g.lse3[h * NY_M + tid];
-  lmst[256 + tid] = MODE == 0 ? g.delta3[h * NY_M + tid] : g.u[h * NY_M + tid];
-  NyFrag qf;
-  ny_lm_frags(g.ql + h * NY_D, g.ldl, lm0, lane, qf);
-  const float* kb = g.k + h * NY_D;
-  const float* vb = g.v + h * NY_D;
-  if constexpr (MODE == 1) {
-    f32x4 rk[4];
-    ny_load(kb, g.ld, (int64_t)t_begin * NY_TT, tid, rk);
-    for (int t = t_begin; t < t_end; ++t) {
-      __syncthreads();
-      ny_store_rm(sm, tid, rk);
-      __syncthreads();
-      if (t + 1 < t_end) ny_load(kb, g.ld, (int64_t)(t + 1) * NY_TT, tid, rk);
-      f32x4 s[4][4];                                          // [lb][tb]
-      NYT_ZERO(s, 4, 4);
-#pragma unroll
-      for (int ks = 0; ks < 2; ++ks) {
-        f32x4 bh[4], bl[4];
-#pragma unroll
-        for (int tb = 0; tb < 4; ++tb) { bh[tb] = ny_frag(sm, tb, ks, 0, lane); bl[tb] = ny_frag(sm, tb, ks, 1, lane); }
-#pragma unroll
-        for (int lb = 0; lb < 4; ++lb) ny_mma_a<4>(qf.h[lb][ks], qf.l[lb][ks], bh, bl, s[lb]);
-      }
-      float r[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int lb = 0; lb < 4; ++lb) {
-        const f32x4 ls = *reinterpret_cast<const f32x4*>(lmst + lm0 + 16 * lb + 4 * kg);
-        const f32x4 uu = *reinterpret_cast<const f32x4*>(lmst + 256 + lm0 + 16 * lb + 4 * kg);
-#pragma unroll
-        for (int tb = 0; tb < 4; ++tb)
-#pragma unroll
-          for (int i = 0; i < 4; ++i) r[tb] += uu[i] * NY_EXP2(s[lb][tb][i] * g.sl2e - ls[i]);
-      }
-#pragma unroll
-      for (int tb = 0; tb < 4; ++tb) {
-        const float v = ny_kgsum(r[tb]);
-        if (kg == 0) part[w * 64 + 16 * tb + c] = v;
-      }
-      __syncthreads();
-      if (tid < 64) g.out[(int64_t)h * g.T + (int64_t)t * NY_TT + tid] = ((part[tid] + part[64 + tid]) + part[128 + tid]) + part[192 + tid];
-    }
-    return;
-  } else {
-    NyFrag af, qt, at;
-    ny_lm_frags(g.da3v + (int64_t)h * NY_PART, NY_D, lm0, lane, af);
-    ny_lt_frags(g.ql + h * NY_D, g.ldl, lm0, lane, qt);
-    ny_lt_frags(g.da3v + (int64_t)h * NY_PART, NY_D, lm0, lane, at);
-    f32x4 rk[4], rv[4];
-    ny_load(kb, g.ld, (int64_t)t_begin * NY_TT, tid, rk);
-    ny_load(vb, g.ld, (int64_t)t_begin * NY_TT, tid, rv);
-    for (int t = t_begin; t < t_end; ++t) {
-      __syncthreads();
-      ny_store_rm(sm, tid, rk);
-      ny_store_rm(sm + NY_IMG, tid, rv);
-      __syncthreads();
-      if (t + 1 < t_end) {
-        ny_load(kb, g.ld, (int64_t)(t + 1) * NY_TT, tid, rk);
-        ny_load(vb, g.ld, (int64_t)(t + 1) * NY_TT, tid, rv);
-      }
-      for (int hf = 0; hf < 2; ++hf) {
-        f32x4 s[4][2], dp[4][2];                              // [lb][tb2]
-        NYT_ZERO(s, 4, 2);
-        NYT_ZERO(dp, 4, 2);
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-          f32x4 bh[2], bl[2], eh[2], el[2];
-#pragma unroll
-          for (int tb = 0; tb < 2; ++tb) {
-            bh[tb] = ny_frag(sm, 2 * hf + tb, ks, 0, lane); bl[tb] = ny_frag(sm, 2 * hf + tb, ks, 1, lane);
-            eh[tb] = ny_frag(sm + NY_IMG, 2 * hf + tb, ks, 0, lane); el[tb] = ny_frag(sm + NY_IMG, 2 * hf + tb, ks, 1, lane);
-          }
-#pragma unroll
-          for (int lb = 0; lb < 4; ++lb) {
-            ny_mma_a<2>(qf.h[lb][ks], qf.l[lb][ks], bh, bl, s[lb]);
-            ny_mma_a<2>(af.h[lb][ks], af.l[lb][ks], eh, el, dp[lb]);
-          }
-        }
-#pragma unroll
-        for (int lb = 0; lb < 4; ++lb) {
-          const f32x4 ls = *reinterpret_cast<const f32x4*>(lmst + lm0 + 16 * lb + 4 * kg);
-          const f32x4 dl = *reinterpret_cast<const f32x4*>(lmst + 256 + lm0 + 16 * lb + 4 * kg);
-#pragma unroll
-          for (int tb = 0; tb < 2; ++tb)
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-              const float p = NY_EXP2(s[lb][tb][i] * g.sl2e - ls[i]);
-              s[lb][tb][i] = p;
-              dp[lb][tb][i] = g.scale * p * (dp[lb][tb][i] - dl[i]);
-            }
-        }
-        f32x4 ov[4][2], ok[4][2];                               // [db][tb2]
-        NYT_ZERO(ov, 4, 2);
-        NYT_ZERO(ok, 4, 2);
-#pragma unroll
-        for (int sx = 0; sx < 2; ++sx) {
-          f32x4 ph[2], pl[2];
-#pragma unroll
-          for (int tb = 0; tb < 2; ++tb) ny_split44(s[2 * sx][tb], s[2 * sx + 1][tb], ph[tb], pl[tb]);
-#pragma unroll
-          for (int db = 0; db < 4; ++db) ny_mma_a<2>(at.h[db][sx], at.l[db][sx], ph, pl, ov[db]);
-        }
-        __syncthreads();                                      // the previous half's partials have been read
-        ny_part_put(part, w, c, kg, ov);
-#pragma unroll
-        for (int sx = 0; sx < 2; ++sx) {
-          f32x4 sh[2], sl[2];
-#pragma unroll
-          for (int tb = 0; tb < 2; ++tb) ny_split44(dp[2 * sx][tb], dp[2 * sx + 1][tb], sh[tb], sl[tb]);
-#pragma unroll
-          for (int db = 0; db < 4; ++db) ny_mma_a<2>(qt.h[db][sx], qt.l[db][sx], sh, sl, ok[db]);
-        }
-        const int tk = tid >> 3, d0 = 8 * (tid & 7);
-        const int64_t row = (int64_t)t * NY_TT + 32 * hf + tk;
-        float* okp = g.out + row * g.ldo + h * NY_D + d0;
-        float* ovp = g.out2 + row * g.ldo2 + h * NY_D + d0;
-        __syncthreads();
-#pragma unroll
-        for (int x4 = 0; x4 < 2; ++x4) {
-          f32x4 b = ny_part_sum(part, tk, d0 + 4 * x4);
-          if (g.accumulate) b += *reinterpret_cast<const f32x4*>(ovp + 4 * x4);
-          *reinterpret_cast<f32x4*>(ovp + 4 * x4) = b;
-        }
-        // dk through the SAME partials (its products were issued above, under the dv exchange)
-        __syncthreads();
-        ny_part_put(part, w, c, kg, ok);
-        __syncthreads();
-#pragma unroll
-        for (int x4 = 0; x4 < 2; ++x4) *reinterpret_cast<f32x4*>(okp + 4 * x4) = ny_part_sum(part, tk, d0 + 4 * x4);
-      }
-    }
-  }
 }
 
 // ===========================================================================================================================
@@ -847,69 +408,39 @@ __global__ __launch_bounds__(NY8_THREADS) void ny_cls_row8_kernel(NyArgs g) {
   }
 }
 
-constexpr int NY_SM_OUT_FWD = NY_IMG + 512 * 4 + 4 * 64 * NY_P68 * 4;
-constexpr int NY_SM_BWD_Q = 2 * NY_IMG + 128 * 4 + NY_PART_F * 4;
-constexpr int NY_SM_A3_T = 2 * NY_IMG + 512 * 4 + NY_PART_F * 4;
-constexpr int NY_SM_CLS = 2 * NY_IMG + 512 * 4 + 256 * 4;
-
 }  // namespace nytok
 
-int nytok_out_fwd(hipStream_t st, const NyArgs& g) {
-  using namespace nytok;
-  MHIMX_ONCE_PER_DEVICE(MHIMX_HIP(hipFuncSetAttribute((const void*)ny_out_fwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, NY_SM_OUT_FWD)));
-  hipLaunchKernelGGL(ny_out_fwd_kernel, dim3(g.nch, NY_H), dim3(NY_THREADS), NY_SM_OUT_FWD, st, g);
-  MHIMX_LAUNCH_CHECK();
-  return 0;
-}
 // The two backward kernels write per-token outputs only (no per-chunk partials), so their chunking is free.  One workgroup per CU
-// (the landmark fragments fill 256 VGPRs + 155 / 205 AGPRs: one wave per SIMD): 64 chunks measured 9.48 vs 9.43 ms per c3 step.
+// (128 KB of LDS): 64 chunks measured 9.48 vs 9.43 ms per c3 step.
 static NyArgs ny_tok_chunks(const NyArgs& g0) {
   NyArgs g = g0;
-  static const int per = getenv("MHIMX_NYS_TOKCH") ? atoi(getenv("MHIMX_NYS_TOKCH")) : NY_TOKCH;
   const int64_t tiles = g.T / NY_TT;
-  g.nch = (int)(tiles < per ? tiles : per);
+  g.nch = (int)(tiles < NY_TOKCH ? tiles : NY_TOKCH);
   return g;
 }
 int nytok_out_bwd_q(hipStream_t st, const NyArgs& g0) {
   using namespace nytok;
   const NyArgs g = ny_tok_chunks(g0);
-  static const bool v1 = getenv("MHIMX_NYS_BWD_Q_V1") != nullptr;       // (experiments: the landmark-split form with cross-wave sums)
-  if (!v1) {
-    MHIMX_ONCE_PER_DEVICE(MHIMX_HIP(hipFuncSetAttribute((const void*)ny_out_bwd_q8_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * NY_PLANE)));
-    hipLaunchKernelGGL(ny_out_bwd_q8_kernel, dim3(g.nch, NY_H), dim3(NY8_THREADS), 4 * NY_PLANE, st, g);
-    MHIMX_LAUNCH_CHECK();
-    return 0;
-  }
-  MHIMX_ONCE_PER_DEVICE(MHIMX_HIP(hipFuncSetAttribute((const void*)ny_out_bwd_q_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, NY_SM_BWD_Q)));
-  hipLaunchKernelGGL(ny_out_bwd_q_kernel, dim3(g.nch, NY_H), dim3(NY_THREADS), NY_SM_BWD_Q, st, g);
+  MHIMX_ONCE_PER_DEVICE(MHIMX_HIP(hipFuncSetAttribute((const void*)ny_out_bwd_q8_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * NY_PLANE)));
+  hipLaunchKernelGGL(ny_out_bwd_q8_kernel, dim3(g.nch, NY_H), dim3(NY8_THREADS), 4 * NY_PLANE, st, g);
   MHIMX_LAUNCH_CHECK();
   return 0;
 }
 int nytok_a3v_bwd_t(hipStream_t st, const NyArgs& g0, int mode) {
   using namespace nytok;
-  const NyArgs g = mode == 0 ? ny_tok_chunks(g0) : g0;
-  static const bool v1 = getenv("MHIMX_NYS_BWD_T_V1") != nullptr;       // (experiments: the landmark-split form with cross-wave sums)
-  if (mode == 0 && !v1) {
+  if (mode == 0) {
+    const NyArgs g = ny_tok_chunks(g0);
     MHIMX_ONCE_PER_DEVICE(MHIMX_HIP(hipFuncSetAttribute((const void*)ny_a3v_bwd_t8_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, NY_SM_A3_T8)));
     hipLaunchKernelGGL(ny_a3v_bwd_t8_kernel, dim3(g.nch, NY_H), dim3(NY8_THREADS), NY_SM_A3_T8, st, g);
     MHIMX_LAUNCH_CHECK();
     return 0;
   }
-  MHIMX_ONCE_PER_DEVICE(MHIMX_HIP(hipFuncSetAttribute((const void*)ny_a3v_bwd_t_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, NY_SM_A3_T));
-                        MHIMX_HIP(hipFuncSetAttribute((const void*)ny_a3v_bwd_t_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, NY_SM_CLS)));
-  if (mode == 1 && !v1) {
-    constexpr int sm_cls = 2 * NY_PLANE + 2 * NY_M * 4;
-    NyArgs gc = g0;                                            // 66 KB of LDS, 84 VGPRs: two workgroups per CU
-    static const int cls_ch = getenv("MHIMX_NYS_CLSCH") ? atoi(getenv("MHIMX_NYS_CLSCH")) : 64;
-    const int64_t tiles = gc.T / NY_TT;
-    gc.nch = (int)(tiles < cls_ch ? tiles : cls_ch);
-    MHIMX_ONCE_PER_DEVICE(MHIMX_HIP(hipFuncSetAttribute((const void*)ny_cls_row8_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, sm_cls)));
-    hipLaunchKernelGGL(ny_cls_row8_kernel, dim3(gc.nch, NY_H), dim3(NY8_THREADS), sm_cls, st, gc);
-    MHIMX_LAUNCH_CHECK();
-    return 0;
-  }
-  if (mode == 0) hipLaunchKernelGGL(ny_a3v_bwd_t_kernel<0>, dim3(g.nch, NY_H), dim3(NY_THREADS), NY_SM_A3_T, st, g);
-  else hipLaunchKernelGGL(ny_a3v_bwd_t_kernel<1>, dim3(g.nch, NY_H), dim3(NY_THREADS), NY_SM_CLS, st, g);
+  constexpr int sm_cls = 2 * NY_PLANE + 2 * NY_M * 4, cls_ch = 64;
+  NyArgs gc = g0;                                            // 66 KB of LDS, 84 VGPRs: two workgroups per CU
+  const int64_t tiles = gc.T / NY_TT;
+  gc.nch = (int)(tiles < cls_ch ? tiles : cls_ch);
+  MHIMX_ONCE_PER_DEVICE(MHIMX_HIP(hipFuncSetAttribute((const void*)ny_cls_row8_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, sm_cls)));
+  hipLaunchKernelGGL(ny_cls_row8_kernel, dim3(gc.nch, NY_H), dim3(NY8_THREADS), sm_cls, st, gc);
   MHIMX_LAUNCH_CHECK();
   return 0;
 }

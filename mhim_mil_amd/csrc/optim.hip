@@ -1,7 +1,6 @@
 // optim.hip — the bag-level tail of a train step: predictor + losses (+ their gradients) in one launch,
 // and the fused Adam + EMA-teacher update over flat parameter buffers.
 #include <math.h>
-#include <stdlib.h>
 
 #include "common.hpp"
 
@@ -478,11 +477,10 @@ extern "C" int mhimx_head_fwd_bwd(void* stream, const float* z, const float* t, 
                                   float* d_bp, int32_t accumulate, const float* g_logits_in, const float* g_cl_in) {
   MHIMX_CHECK_ARG(z && wp && logits && losses && g_z, "head: null args");
   MHIMX_CHECK_ARG(C > 0 && C <= 16 && E > 0, "head: bad dims");
-  static const bool slow_head = getenv("MHIMX_HEAD_GENERIC") != nullptr;
-  if (!slow_head && C <= 4 && E <= 2 * HEAD_THREADS)
+  if (C <= 4 && E <= 2 * HEAD_THREADS)
     hipLaunchKernelGGL(head_fast_kernel<2>, bgrid(1), dim3(HEAD_THREADS), 0, (hipStream_t)stream, z, t, wp, bp, label_dev, (int)E, (int)C,
                      temp_t, main_alpha, aux_alpha, inv_accum, logits, losses, g_z, d_wp, d_bp, accumulate, g_logits_in, g_cl_in, cur_batch());
-  else if (!slow_head && C <= 4 && E <= 4 * HEAD_THREADS)
+  else if (C <= 4 && E <= 4 * HEAD_THREADS)
     hipLaunchKernelGGL(head_fast_kernel<4>, bgrid(1), dim3(HEAD_THREADS), 0, (hipStream_t)stream, z, t, wp, bp, label_dev, (int)E, (int)C,
                      temp_t, main_alpha, aux_alpha, inv_accum, logits, losses, g_z, d_wp, d_bp, accumulate, g_logits_in, g_cl_in, cur_batch());
   else if (cur_batch().n > 0)

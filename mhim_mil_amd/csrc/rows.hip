@@ -984,8 +984,7 @@ int abmil_pool_fwd(hipStream_t st, const mhimx_scorer* sc, mhimx_pool_io* io) {
       M2RowsFwd mfbuf;
       const void* mf = nullptr;
       io->rode_merge = 0;
-      static const bool ride_ok = getenv("MHIMX_MERGE_FWD_RIDE") == nullptr || atoi(getenv("MHIMX_MERGE_FWD_RIDE")) != 0;
-      if (io->ride_merge && ride_ok) {
+      if (io->ride_merge) {
         const int rc = merge2_fwd_rows_args(reinterpret_cast<const mhimx_merge*>(io->ride_merge), io->ride_X, io->ride_R, io->ride_ws, io->ride_ws_bytes,
                                             &mfbuf);
         if (rc < 0) return rc;

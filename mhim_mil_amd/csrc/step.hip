@@ -32,7 +32,6 @@
 // the 3-15 us of launches a branch takes off the chain: c2 0.300 -> 0.317 (forward fork alone) / 0.333 (backward alone) / 0.341 ms (both).
 // The trainer therefore passes no side stream unless MHIMX_STEP_DAG=1; the form stays as the measured answer to "run the step as a DAG".
 #include <math.h>
-#include <stdlib.h>
 #include <string.h>
 
 #include "common.hpp"
@@ -86,12 +85,6 @@ int dag_edge(hipEvent_t ev, hipStream_t from, hipStream_t to) {
   MHIMX_HIP(hipEventRecord(ev, from));
   MHIMX_HIP(hipStreamWaitEvent(to, ev, 0));
   return 0;
-}
-
-// MHIMX_FUSE_DPRE=0: the rows' gradient goes to memory in fp32 and mhimx_rows_dpre_image makes the whole image, as rounds 3-5 had it
-bool fuse_dpre() {
-  static const bool on = getenv("MHIMX_FUSE_DPRE") == nullptr || atoi(getenv("MHIMX_FUSE_DPRE")) != 0;
-  return on;
 }
 
 struct Carve {
@@ -172,7 +165,7 @@ void layout(const mhimx_step_cfg* c, int64_t N, const mhimx_step_counts* n, Step
   b->wo_t = cv.take_off(I * E * F);
   b->q_old = cv.take_off(k * E * F);
   if (n_bags > 1) {
-    b->wg_ws_floats = mhimx_wgrad_multi_ws_floats(fuse_dpre() && N <= 16384 ? (n->Lk + k + 31) / 32 * 32 + n->R : n->len_keep, E, D, n_bags);
+    b->wg_ws_floats = mhimx_wgrad_multi_ws_floats(N <= 16384 ? (n->Lk + k + 31) / 32 * 32 + n->R : n->len_keep, E, D, n_bags);
     b->wg_ws = cv.take_off(b->wg_ws_floats * F);
   }
   b->bag0 = cv.off;
@@ -180,7 +173,7 @@ void layout(const mhimx_step_cfg* c, int64_t N, const mhimx_step_counts* n, Step
   b->merge_ws = cv.take_off(b->merge_ws_bytes);
   // (round 6) up to 16 384 rows the stay rows' share of the projection's dPRE image is written by the scorer backward itself
   // (mhimx_pool_grad.img): the image is ordered [rows that stay, tile for tile of that launch | rows to merge from P0 on]
-  b->fuse_img = fuse_dpre() && N <= 16384;
+  b->fuse_img = N <= 16384;
   b->P0 = b->fuse_img ? (n->Lk + k + 31) / 32 * 32 : 0;
   b->L_img = b->fuse_img ? b->P0 + n->R : n->len_keep;
   b->H_t = cv.take_off(N * E * F);
@@ -289,12 +282,9 @@ extern "C" int mhimx_step_run(void* stream, const mhimx_step_cfg* cfg, const flo
   int64_t* rows_all = cv.at<int64_t>(b.rows_all);
   float* dH = cv.at<float>(b.dH);
   const uint64_t* tick = c.tick;
-  // the DAG form (header comment): a second stream and its fork / join events.  MHIMX_STEP_DAG=0: the chain, whatever the caller passes
-  static const bool dag_on = getenv("MHIMX_STEP_DAG") == nullptr || atoi(getenv("MHIMX_STEP_DAG")) != 0;      // (the caller decides: side_stream)
-  static const bool dag_fwd = getenv("MHIMX_STEP_DAG_FWD") == nullptr || atoi(getenv("MHIMX_STEP_DAG_FWD")) != 0;
-  static const bool dag_bwd = getenv("MHIMX_STEP_DAG_BWD") == nullptr || atoi(getenv("MHIMX_STEP_DAG_BWD")) != 0;
+  // the DAG form (header comment): a second stream and its fork / join events.  The caller decides: side_stream
   const hipStream_t main_st = (hipStream_t)stream, side_st = (hipStream_t)c.side_stream;
-  const bool dag = dag_on && c.side_stream != nullptr && c.side_stream != stream;
+  const bool dag = c.side_stream != nullptr && c.side_stream != stream;
   hipEvent_t* ev = nullptr;
   if (dag)
     if (int r = g_dag_events.get(&ev)) return r;
@@ -401,15 +391,14 @@ extern "C" int mhimx_step_run(void* stream, const mhimx_step_cfg* cfg, const flo
   mw.drop_p = c.merge_drop_p; mw.drop_seed = seeds->mca; mw.x_rows = rows_all; mw.prepared = 1;
   // ---- 6..11. the student's forward.  Its scorer over the rows that stay and Merge's rows pass are independent: ONE launch runs both (the Merge
   //      row tiles ride at its front), the Merge tail then makes the tokens, and the pool's finalize launch scores those k rows itself
-  //      (mhimx_pool_io.phase; MHIMX_SPLIT_POOL=0: Merge, then the scorer over [stay | tokens], as rounds 2-4 had it)
+  //      (mhimx_pool_io.phase; more than 6 tokens: Merge, then the scorer over [stay | tokens], as rounds 2-4 had it)
   mhimx_scorer sc_s = sc_t;
   sc_s.wa = S.wa; sc_s.wc = S.wc; sc_s.wa_frag = wa_frag_s;
   mhimx_pool_io io_s = {};
   io_s.T1 = Hbuf; io_s.M1 = Lk + k; io_s.s = cv.at<float>(b.s_s); io_s.stats = cv.at<float>(b.stats_s); io_s.z = cv.at<float>(b.z_s);
   io_s.ws = cv.at<char>(b.pool_ws_s); io_s.ws_bytes = b.pool_ws_s_bytes; io_s.rows1 = rows_all + R;
-  static const bool split_pool = getenv("MHIMX_SPLIT_POOL") == nullptr || atoi(getenv("MHIMX_SPLIT_POOL")) != 0;
   io_s.tail_row0 = -1;
-  if (dag && dag_fwd && split_pool && k <= 6) {
+  if (dag && k <= 6) {
     // two branches: the scorer over the rows that stay (side) || Merge's whole chain (main); they meet at the finalize that scores the tokens
     if (int r = dag_edge(ev[0], main_st, side_st)) return r;
     io_s.phase = 1; io_s.tail_tokens = (int32_t)k;
@@ -419,7 +408,7 @@ extern "C" int mhimx_step_run(void* stream, const mhimx_step_cfg* cfg, const flo
     io_s.phase = 2; io_s.tail_wa_t = wa_t; io_s.tail_row0 = N;
     if (int r = mhimx_abmil_pool_fwd(stream, &sc_s, &io_s)) return r;
     io_s.phase = 0;
-  } else if (split_pool && k <= 6) {
+  } else if (k <= 6) {
     io_s.phase = 1; io_s.tail_tokens = (int32_t)k;
     io_s.ride_merge = &mw; io_s.ride_X = Hbuf; io_s.ride_R = R; io_s.ride_ws = merge_ws; io_s.ride_ws_bytes = b.merge_ws_bytes;
     if (int r = mhimx_abmil_pool_fwd(stream, &sc_s, &io_s)) return r;
@@ -459,20 +448,18 @@ extern "C" int mhimx_step_run(void* stream, const mhimx_step_cfg* cfg, const flo
   }
   mhimx_reduce_list lst_main;                    // (DAG form: what the main branch queues - the bias partials, the weight gradient's slab sum)
   memset(&lst_main, 0, sizeof(lst_main));
-  const bool dagb = dag && dag_bwd;
-  mhimx_reduce_list* lm = dagb ? &lst_main : &lst;
-  if (dagb) {
+  mhimx_reduce_list* lm = dag ? &lst_main : &lst;
+  if (dag) {
     // side branch, first half: the parked scorer-weight-gradient product (its inputs are the pool backward's) and the reductions queued so far
     if (int r = dag_edge(ev[2], main_st, side_st)) return r;
     // (the chain runs the product beside the Merge rows backward's tiles and sizes it for the CUs they leave - when the first stage rode:
     // the same slab count here keeps the chain's summation order)
-    static const bool fuse_rows = getenv("MHIMX_MERGE_BWD_FUSE") == nullptr || atoi(getenv("MHIMX_MERGE_BWD_FUSE")) != 0;
-    if (lst.parked.pending && lst.pre.pending == 2 && fuse_rows) lst.parked.reserved = (int32_t)merge2_rows_tiles(R) + 1;
+    if (lst.parked.pending && lst.pre.pending == 2) lst.parked.reserved = (int32_t)merge2_rows_tiles(R) + 1;
     if (int r = mhimx_reduce_flush(side_st, &lst)) return r;
   }
   // main: the Merge rows backward (DAG form: a launch of its own - the product it used to share a launch with is on the side branch)
   if (int r = mhimx_merge_bwd(stream, &mwb, Hbuf, R, dH + N * E, dH, &mg, merge_ws, b.merge_ws_bytes)) return r;
-  if (dagb) {
+  if (dag) {
     // side branch, second half: the Merge parameter-gradient tail reads what the rows backward wrote (the pooled-row partials U)
     if (int r = dag_edge(ev[3], main_st, side_st)) return r;
     if (int r = mhimx_reduce_flush(side_st, &lst)) return r;      // (the tail's stages as launches, the last one inside the reduction launch)
@@ -488,7 +475,7 @@ extern "C" int mhimx_step_run(void* stream, const mhimx_step_cfg* cfg, const flo
     g.accumulate = 0; g.ws = cv.at<float>(b.wg_ws); g.ws_floats = b.wg_ws_floats; g.defer = lm; g.ride_tail = update ? 1 : 0;
     if (int r = mhimx_bag_wgrad(stream, &g)) return r;
   }
-  if (dagb)
+  if (dag)
     if (int r = dag_edge(ev[4], side_st, main_st)) return r;
   if (!update) return mhimx_reduce_flush(stream, lm);
 
@@ -643,8 +630,7 @@ extern "C" int mhimx_window_run(void* stream, const mhimx_step_cfg* cfg, int32_t
     mhimx_bag_project_args pa[MHIMX_WINDOW_MAX];
     // the launch projects the bags LAST to FIRST: the middle's planes are dispatched bag 0 first, and its first readers then find the rows
     // written most recently (the window's 400 MB of feature rows do not fit the 256 MB Infinity Cache).  Same bits; 0.5 % of a window,
-    // same box, twice (MHIMX_WINDOW_PROJ_REV=0: first to last)
-    static const bool proj_rev = getenv("MHIMX_WINDOW_PROJ_REV") == nullptr || atoi(getenv("MHIMX_WINDOW_PROJ_REV")) != 0;
+    // same box, twice
     for (int i = 0; i < n_bags; ++i) {
       mhimx_bag_project_args a = {};
       a.X = X[i]; a.ldx = ldx; a.N = N; a.D = D; a.E = E; a.act = c.act; a.n_heads = 2; a.drop_tick = tick;
@@ -652,7 +638,7 @@ extern "C" int mhimx_window_run(void* stream, const mhimx_step_cfg* cfg, int32_t
       a.head[0].drop_seed = seeds[i].drop_teacher;
       a.head[1].wp = w1p_s; a.head[1].bias = S.b1; a.head[1].H = reinterpret_cast<float*>(bag(b.Hbuf, i)); a.head[1].ldh = E; a.head[1].dact = bag(b.dact, i);
       a.head[1].drop_p = c.drop_p_student; a.head[1].drop_seed = seeds[i].drop_student;
-      pa[proj_rev ? n_bags - 1 - i : i] = a;
+      pa[n_bags - 1 - i] = a;
     }
     if (int r = mhimx_bag_project_multi(stream, pa, n_bags)) return r;
   }

@@ -17,13 +17,10 @@
 //     consecutive 16-byte slots — no bank conflicts, no swizzle.  The column slot of column c is (c % 4) * (cols/4) + c / 4, i.e. an
 //     MFMA tile covers every 4th column: the four tiles of a lane are four CONSECUTIVE output columns (one 16-byte store each).
 //   * dPRE^T tiles go L2 -> LDS by direct DMA, 16 KiB linear per k-step.
-//   * workgroup tile 128 (E) x 256 (D), 8 waves as 2 x 4, 64 x 64 per wave = 48 MFMAs against 16 ds_read_b128 per k-step;
-//     one s_barrier per k-step; the schedule of bag_project.hip (MFMAs of tile t-1 under the reads of tile t).  Both operands are
-//     requested THREE k-steps ahead (144 KB in flight per CU: at ~2 us of loaded-memory latency two tiles ahead starve the ~70 KB/us a
-//     CU can ingest): the image in a 5-deep LDS ring, X in three rotating register sets in front of a 2-deep LDS ring.
+//   * workgroup tile 128 (E) x 256 (D); one s_barrier per k-step; the operands are requested ahead of their use in 3-deep LDS rings
+//     (144 KB per CU: at ~2 us of loaded-memory latency less starves the ~70 KB/us a CU can ingest).
 //   * 16 reduction slabs x 16 output tiles = 256 workgroups (one per CU); the tiles of a slab run on ONE XCD (its X rows and dPRE
 //     tiles are shared through that L2); the slab sum is a job of the step's deferred reduction launch, as before.
-#include <stdlib.h>
 #include <string.h>
 
 #include "mma_tile.hpp"
@@ -34,8 +31,6 @@ namespace mhimx {
 
 constexpr int WBI = 128, WBN = 256, WBK = 32, WTHREADS = 512;
 constexpr int WA_BYTES = WBI * 128, WB_BYTES = WBN * 128;                                         // 16 KiB, 32 KiB per k-step
-constexpr int WNA = 5, WNB = 2;                      // ring depths: dPRE^T image tiles (DMA, three tiles ahead), X tiles (through registers)
-constexpr int WRING = WNA * WA_BYTES + WNB * WB_BYTES;                                            // 144 KiB
 constexpr int W_MAX_CHUNK = 3072;                                                                 // rows of one slab (row table: 12 KiB)
 constexpr int WNF = 16;                              // fragments of a k-step: x[0..3] A hi, x[4..7] A lo, x[8..11] B hi, x[12..15] B lo
 
@@ -137,220 +132,17 @@ struct WgradBags {            // the bags of one launch (bag_wgrad_ws_kernel): b
   int spb;
 };
 
-__global__ __launch_bounds__(WTHREADS) void bag_wgrad_kernel(WgradArgs g, int side_blocks, Merge2Side side) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  if ((int)blockIdx.x < side_blocks) {          // a parked Merge-backward tail rides along (stage 2, 256 of the 512 threads): its few
-    if (threadIdx.x < M2_THREADS) merge2_side_stage(2, (int)blockIdx.x, reinterpret_cast<float*>(smem), side);   // short workgroups go first
-    return;
-  }
-  const unsigned bx = blockIdx.x - (unsigned)side_blocks;      // (side_blocks % 8 == 0: the XCD of a tile does not move)
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wm = wave >> 2, wn = wave & 3;
-  const int nJ = (int)(g.D / WBN), nIT = (int)(g.E / WBI), nT = nIT * nJ;
-  const int xcd = bx & 7, sidx = bx >> 3;
-  const int slab = (sidx / nT) * 8 + xcd, tile = sidx % nT;
-  if (slab >= g.splits) return;
-  const int itile = tile / nJ;
-  const int64_t i0 = (int64_t)itile * WBI, n0 = (int64_t)(tile % nJ) * WBN;
-  const int ks0 = slab * g.kps;
-  const int nk = (ks0 + g.kps < g.ksteps ? ks0 + g.kps : g.ksteps) - ks0;       // >= 1 by the host's choice of splits
-
-  // byte offsets of this slab's X rows (a bag is < 4 GiB); rows past L repeat the last one (their dPRE image rows are zero)
-  unsigned* rowtab = reinterpret_cast<unsigned*>(smem + WRING);
-
-  // ---- X: wave -> (row octet o of the k-step, column half ch); lane -> (rows 4 half .. 4 half + 3 of the octet, columns 4c .. 4c+3)
-  const int oct = wave & 3, ch = wave >> 2, half = lane >> 5, c = lane & 31;
-  const unsigned colb = (unsigned)((n0 + ch * 128 + 4 * c) * 4);
-  const unsigned rt_lds = (unsigned)(uintptr_t)(lptr_f)rowtab + (unsigned)((oct * 8 + half * 4) * 4);    // + t * 128
-  struct XRegs { f32x4 v[4]; };
-  typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-  auto load_x_async = [&](const u32x4& ro, XRegs& r) {
-    asm volatile("global_load_dwordx4 %0, %4, %8\n\tglobal_load_dwordx4 %1, %5, %8\n\t"
-                 "global_load_dwordx4 %2, %6, %8\n\tglobal_load_dwordx4 %3, %7, %8"
-                 : "=&v"(r.v[0]), "=&v"(r.v[1]), "=&v"(r.v[2]), "=&v"(r.v[3])
-                 : "v"(ro[0] + colb), "v"(ro[1] + colb), "v"(ro[2] + colb), "v"(ro[3] + colb), "s"(g.X)
-                 : "memory");
-  };
-  // LDS slot of this lane's two columns after the half-wave swap: column 4c + j, j = s + 2 half (s = 0, 1) -> slot j * 64 + ch * 32 + c
-  const unsigned xs0 = (unsigned)(WNA * WA_BYTES + ((oct * 2) * 256 + (2 * half) * 64 + ch * 32 + c) * 16);
-  auto store_x = [&](int t, XRegs& r) {
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      float a0 = r.v[q][0], a1 = r.v[q][1], a2 = r.v[q][2], a3 = r.v[q][3];
-      wg_swap(a0, a2);
-      wg_swap(a1, a3);
-      r.v[q] = f32x4{a0, a1, a2, a3};
-    }
-    char* sb = smem + (t % WNB) * WB_BYTES + xs0;
-#pragma unroll
-    for (int s = 0; s < 2; ++s) {
-      const float kv[8] = {r.v[0][s], r.v[1][s], r.v[2][s], r.v[3][s], r.v[0][s + 2], r.v[1][s + 2], r.v[2][s + 2], r.v[3][s + 2]};
-      f32x4 hi, lo;
-      wg_split8(kv, hi, lo);
-      *reinterpret_cast<f32x4*>(sb + s * 1024) = hi;
-      *reinterpret_cast<f32x4*>(sb + s * 1024 + 4096) = lo;
-    }
-  };
-  // ---- dPRE^T image tiles by DMA: 16 KiB linear, 2 x 16 B per thread.  `live` false: the pieces come from ONE address (a stage nobody
-  // reads any more) so that every iteration has the same VMEM count and the hand-written vmcnt waits need no branch.
-  const char* abase = g.img + ((int64_t)ks0 * nIT + itile) * WA_BYTES + tid * 16;
-  auto issue_a = [&](int t, bool live) {
-    char* sa = smem + (t % WNA) * WA_BYTES + wave * 1024;
-    const char* src = live ? abase + (int64_t)t * nIT * WA_BYTES : g.img;
-    __builtin_amdgcn_global_load_lds((gptr_f)src, (lptr_f)sa, 16, 0, 0);
-    __builtin_amdgcn_global_load_lds((gptr_f)(live ? src + 8192 : src), (lptr_f)(sa + 8192), 16, 0, 0);
-  };
-
-  issue_a(0, true);                                           // (before the row table: it does not depend on it)
-  for (int q = tid; q < nk * WBK; q += WTHREADS) {
-    int64_t l = (int64_t)ks0 * WBK + q;
-    if (l >= g.L) l = g.L - 1;
-    rowtab[q] = (unsigned)((g.rows ? g.rows[l] : l) * g.ldx * 4);
-  }
-  __syncthreads();
-  // fragment addresses (stage 0): slot r = lane & 15 of a 16-slot block, k-octet kg = lane >> 4
-  const int r16 = lane & 15, kg = lane >> 4;
-  const unsigned lds0 = (unsigned)(uintptr_t)(lptr_f)smem;
-  const unsigned fa_hi = lds0 + ((kg * 2) * 128 + 16 * wm + r16) * 16, fa_lo = fa_hi + 2048;
-  const unsigned fb_hi = lds0 + WNA * WA_BYTES + ((kg * 2) * 256 + 16 * wn + r16) * 16, fb_lo = fb_hi + 4096;
-
-  f32x4 acc[4][4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-  // prologue: image tile 0, X(0) -> stage 0 (plain loads: the compiler's wait drains both); then, in the loop's own order,
-  // {X(1), image 1}, {X(2), image 2} in flight; row offsets of tile 3 in registers
-  XRegs rg0, rg1, rg2;
-  auto row_offsets = [&](int t) { return *reinterpret_cast<const u32x4*>(reinterpret_cast<const char*>(rowtab) + (oct * 8 + half * 4) * 4 + (t < nk ? t : nk - 1) * 128); };
-  {
-    const u32x4 r0o = row_offsets(0);
-    XRegs r0;
-    const char* xb = reinterpret_cast<const char*>(g.X);
-#pragma unroll
-    for (int q = 0; q < 4; ++q) r0.v[q] = *reinterpret_cast<const f32x4*>(xb + r0o[q] + colb);
-    store_x(0, r0);
-  }
-  load_x_async(row_offsets(1), rg1);
-  issue_a(1, nk > 1);
-  load_x_async(row_offsets(2), rg2);
-  issue_a(2, nk > 2);
-  u32x4 ro = row_offsets(3);
-
-  f32x4 x[WNF];
-#ifdef WG_NOREAD
-  for (int q = 0; q < WNF; ++q) x[q] = f32x4{1.f, 2.f, 3.f, 4.f};
-#endif
-  // Iteration t:  [barrier: tile t complete in its stages]  X(t+3) loads -> the free register set, image DMA(t+3) -> stage (t+3)%5
-  // (tile t-2's: every wave is past its reads); reads g1 = {A lo, B hi}; row offsets of tile t+4; 16 MFMAs hi*lo of tile t-1 (operands
-  // still in registers); reads g2 = {A hi, B lo}; 16 MFMAs lo*hi; wait until only the last two iterations' 12 VMEM operations are in
-  // flight (X(t+1) is in its registers, image t+1 has landed); 16 MFMAs hi*hi with the swap / split / LDS stores of X(t+1) into stage
-  // (t+1)%2 (tile t-1's) in their shadow.
-  auto body = [&](int t, XRegs& r_load, XRegs& r_use) {
-    asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(ro) : : "memory");       // my X(t) stores are done; the row offsets are here
-    __builtin_amdgcn_s_barrier();
-    const unsigned soa = (unsigned)((t % WNA) * WA_BYTES), sob = (unsigned)((t % WNB) * WB_BYTES);
-#ifndef WG_NOX
-    load_x_async(ro, r_load);
-#endif
-#ifndef WG_NODMA
-    issue_a(t + 3, t + 3 < nk);
-#endif
-#ifndef WG_NOREAD
-    WG_READ8(x, 4, 8, fa_lo + soa, fb_hi + sob);
-#endif
-    {
-      const unsigned ra = rt_lds + (unsigned)((t + 4 < nk ? t + 4 : nk - 1) * 128);
-      asm volatile("ds_read_b128 %0, %1" : "=&v"(ro) : "v"(ra) : "memory");
-    }
-    __builtin_amdgcn_sched_barrier(0);
-#ifndef WG_NOMMA
-    if (t > 0) wg_term(x, 0, 12, acc);                        // hi*lo of tile t-1
-#endif
-    __builtin_amdgcn_sched_barrier(0);
-#ifndef WG_NOREAD
-    WG_WAIT8(0, x, 4, 8);
-    WG_READ8(x, 0, 12, fa_hi + soa, fb_lo + sob);
-#endif
-    __builtin_amdgcn_sched_barrier(0);
-#ifndef WG_NOMMA
-    wg_term(x, 4, 8, acc);                                    // lo*hi
-#endif
-    __builtin_amdgcn_sched_barrier(0);
-#ifndef WG_NOREAD
-    WG_WAIT8(0, x, 0, 12);
-#endif
-#if defined(WG_NOX) && defined(WG_NODMA)
-#elif defined(WG_NOX)
-    asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-#elif defined(WG_NODMA)
-    asm volatile("s_waitcnt vmcnt(8)" : "+v"(r_use.v[0]), "+v"(r_use.v[1]), "+v"(r_use.v[2]), "+v"(r_use.v[3]) : : "memory");
-#else
-    asm volatile("s_waitcnt vmcnt(12)" : "+v"(r_use.v[0]), "+v"(r_use.v[1]), "+v"(r_use.v[2]), "+v"(r_use.v[3]) : : "memory");
-#endif
-    __builtin_amdgcn_sched_barrier(0);
-#ifndef WG_NOMMA
-    wg_term(x, 0, 8, acc);                                    // hi*hi
-#endif
-#if !defined(WG_NOX) && !defined(WG_NOSTORE)
-    if (t + 1 < nk) store_x(t + 1, r_use);
-#endif
-#if !defined(WG_NOINTERLEAVE) && !defined(WG_NOMMA) && !defined(WG_NOX) && !defined(WG_NOSTORE)
-#pragma unroll
-    for (int q = 0; q < 16; ++q) {
-      __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);      // one MFMA
-      __builtin_amdgcn_sched_group_barrier(0x002, 4, 0);      // four VALU
-      if (q % 4 == 3) __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);   // a DS write
-    }
-#endif
-  };
-  int t = 0;
-#pragma unroll 1
-  for (; t + 2 < nk; t += 3) {
-    body(t, rg0, rg1);
-    body(t + 1, rg1, rg2);
-    body(t + 2, rg2, rg0);
-  }
-  if (t < nk) body(t, rg0, rg1);
-  if (t + 1 < nk) body(t + 1, rg1, rg2);
-#ifndef WG_NOMMA
-  wg_term(x, 0, 12, acc);                                     // hi*lo of the last tile
-#endif
-  asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)"
-               : "+v"(rg0.v[0]), "+v"(rg0.v[1]), "+v"(rg0.v[2]), "+v"(rg0.v[3]), "+v"(rg1.v[0]), "+v"(rg1.v[1]), "+v"(rg1.v[2]), "+v"(rg1.v[3]),
-                 "+v"(rg2.v[0]), "+v"(rg2.v[1]), "+v"(rg2.v[2]), "+v"(rg2.v[3]), "+v"(ro)
-               :
-               : "memory");
-
-#ifdef WG_NOEPI
-  {
-    float sacc = 0.f;
-    for (int i = 0; i < 4; ++i)
-      for (int j = 0; j < 4; ++j) sacc += acc[i][j][0] + acc[i][j][1] + acc[i][j][2] + acc[i][j][3];
-    if (sacc != 1.2345e-30f) return;
-  }
-#endif
-  // ---- epilogue: tile (ja, jb) of a lane is row 4 (16 wm + 4 (lane >> 4) + e) + ja, column 4 (16 wn + (lane & 15)) + jb: 16-byte stores
-  float* out = g.out + (int64_t)slab * g.E * g.D;
-#pragma unroll
-  for (int ja = 0; ja < 4; ++ja)
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const int64_t i = i0 + 4 * (16 * wm + 4 * kg + e) + ja;
-      const int64_t n = n0 + 4 * (16 * wn + r16);
-      *reinterpret_cast<f32x4*>(out + i * g.D + n) = f32x4{acc[ja][0][e], acc[ja][1][e], acc[ja][2][e], acc[ja][3][e]};
-    }
-}
-
 // ---------------------------------------------------------------------------------------------------------------------------
-// The same product with SPECIALISED waves.  In bag_wgrad_kernel every wave loads, splits, stores, reads fragments and multiplies; the
-// counters say its waves wait 46 % of their time with the matrix pipe 44 % busy (two waves per SIMD in lock-step phases: when one
+// The product with SPECIALISED waves.  With eight uniform waves (every wave loads, splits, stores, reads fragments and multiplies) the
+// counters said the waves wait 46 % of their time with the matrix pipe 44 % busy (two waves per SIMD in lock-step phases: when one
 // waits on memory so does the other).  Here waves 0-3 (one per SIMD) are PRODUCERS - X loads, half-wave swap, bf16 split, LDS stores,
 // the image DMA - and waves 4-7 CONSUMERS that touch no global memory in the loop: 64 x 128 outputs each (32 accumulator tiles), 24
 // fragment reads and 96 MFMAs per k-step, fragments of tile t+1 requested while tile t multiplies.  A producer's instructions issue in
 // the shadow of its SIMD's consumer MFMAs; fragment reads per MFMA drop by a quarter (96 KB instead of 128 KB per k-step per CU).
 // One s_barrier per k-step: it publishes tile t+2 and retires tile t; 3-deep rings for both operands (144 KB).
+// MEASURED: ~5 % faster than the uniform form; a third form (these producers + 8 ping-pong consumer waves, 768 threads: what took the
+// projection from 73 to 63 us) measured the SAME as this one (34.7 vs 34.5 us same-box; consumers alone 27.8, producers alone 27.8, both
+// 37: ~13 us of the launch are the row table, the first tiles and the 33 MB of slab stores, outside the loop either form pipelines).
 // ---------------------------------------------------------------------------------------------------------------------------
 constexpr int SNA = 3, SNB = 3, SRING = SNA * WA_BYTES + SNB * WB_BYTES;
 
@@ -404,16 +196,6 @@ __global__ __launch_bounds__(WTHREADS) void bag_wgrad_ws_kernel(WgradArgs g, Wgr
   __syncthreads();
   const unsigned lds0 = (unsigned)(uintptr_t)(lptr_f)smem;
 
-#if defined(WG_PROD_PRIO) || defined(WG_CONS_PRIO)
-#ifndef WG_PROD_PRIO
-#define WG_PROD_PRIO 0
-#endif
-#ifndef WG_CONS_PRIO
-#define WG_CONS_PRIO 0
-#endif
-  if (wave < 4) __builtin_amdgcn_s_setprio(WG_PROD_PRIO);
-  else __builtin_amdgcn_s_setprio(WG_CONS_PRIO);
-#endif
   if (wave < 4) {
     // =========================================================== producers: wave = row octet of the k-step
     const int oct = wave, half = lane >> 5, c = lane & 31;
@@ -594,12 +376,8 @@ __global__ __launch_bounds__(WTHREADS) void bag_wgrad_ws_kernel(WgradArgs g, Wgr
       for (int e = 0; e < 4; ++e) {
         const int64_t i = i0 + 4 * (16 * wm + 4 * kg + e) + ja;
         const int64_t n = n0 + 4 * (16 * (2 * wn + cb) + r16);
-#ifdef MHIMX_SLAB_WT
-        st_f4_wt(out + i * g.D + n, f32x4{acc[ja][4 * cb + 0][e], acc[ja][4 * cb + 1][e], acc[ja][4 * cb + 2][e], acc[ja][4 * cb + 3][e]});
-#else
         *reinterpret_cast<f32x4*>(out + i * g.D + n) =
             f32x4{acc[ja][4 * cb + 0][e], acc[ja][4 * cb + 1][e], acc[ja][4 * cb + 2][e], acc[ja][4 * cb + 3][e]};
-#endif
       }
 #ifdef WG_PROF
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -613,201 +391,13 @@ __global__ __launch_bounds__(WTHREADS) void bag_wgrad_ws_kernel(WgradArgs g, Wgr
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
-// Specialised waves AND a ping-pong of the consumers (the form of bag_project_ws.hip): 4 producer waves (one per SIMD: the X loads,
-// half-wave swap, bf16 split, LDS stores and the image DMA, half of a k-step's work in each of its two slots) and 8 consumer waves as
-// 2 x 4 of 64 x 64 outputs that only read fragments and issue MFMAs.  Consumers cw and cw + 4 share a SIMD and run half a k-step apart:
-// slot 2s: group 0 reads the 16 fragments of tile s | group 1 issues the 48 MFMAs of tile s-1;  slot 2s+1: the other way round - the
-// matrix pipe of every SIMD always has a wave feeding it and the fragment reads run under the partner's MFMAs (bag_wgrad_ws_kernel's four
-// consumers interleave their own reads with their own MFMAs: every fragment wait stalls that SIMD's matrix pipe).  A workgroup barrier
-// after each slot; 3-deep rings: in k-step s the producers store X(s+1) (stage of tile s-2), issue the DMA of image s+2 (stage of tile
-// s-1: both groups are past it) and request X(s+4); at its end they wait until X(s+2) is in registers and image s+1 has landed.
-// ---------------------------------------------------------------------------------------------------------------------------
-constexpr int PP_THREADS = 768;
-__global__ __launch_bounds__(PP_THREADS) void bag_wgrad_pp_kernel(WgradArgs g, int side_blocks, Merge2Side side) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  if ((int)blockIdx.x < side_blocks) {
-    if (threadIdx.x < M2_THREADS) merge2_side_stage(2, (int)blockIdx.x, reinterpret_cast<float*>(smem), side);
-    return;
-  }
-  const unsigned bx = blockIdx.x - (unsigned)side_blocks;
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int nJ = (int)(g.D / WBN), nIT = (int)(g.E / WBI), nT = nIT * nJ;
-  const int xcd = bx & 7, sidx = bx >> 3;
-  const int slab = (sidx / nT) * 8 + xcd, tile = sidx % nT;
-  if (slab >= g.splits) return;
-  const int itile = tile / nJ;
-  const int64_t i0 = (int64_t)itile * WBI, n0 = (int64_t)(tile % nJ) * WBN;
-  const int ks0 = slab * g.kps;
-  const int nk = (ks0 + g.kps < g.ksteps ? ks0 + g.kps : g.ksteps) - ks0;
-  unsigned* rowtab = reinterpret_cast<unsigned*>(smem + SRING);
-  for (int q = tid; q < nk * WBK; q += PP_THREADS) {
-    int64_t l = (int64_t)ks0 * WBK + q;
-    if (l >= g.L) l = g.L - 1;
-    rowtab[q] = (unsigned)((g.rows ? g.rows[l] : l) * g.ldx * 4);
-  }
-  __syncthreads();
-  const unsigned lds0 = (unsigned)(uintptr_t)(lptr_f)smem;
-  auto slot_end = [&]() {
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
-  };
-
-  if (wave < 4) {
-    // =========================================================== producers: wave = row octet of the k-step
-    const int oct = wave, half = lane >> 5, c = lane & 31;
-    const unsigned colb0 = (unsigned)((n0 + 4 * c) * 4), colb1 = colb0 + 128 * 4;
-    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-    struct XSet { f32x4 v[8]; };                               // [column half][row of the lane's four]
-    auto row_offsets = [&](int t) {
-      return *reinterpret_cast<const u32x4*>(reinterpret_cast<const char*>(rowtab) + (oct * 8 + half * 4) * 4 + (t < nk ? t : nk - 1) * 128);
-    };
-    auto load_half = [&](const u32x4& ro, unsigned colb, f32x4* d) {          // four rows of one column half
-      asm volatile("global_load_dwordx4 %0, %4, %8\n\tglobal_load_dwordx4 %1, %5, %8\n\tglobal_load_dwordx4 %2, %6, %8\n\t"
-                   "global_load_dwordx4 %3, %7, %8"
-                   : "=&v"(d[0]), "=&v"(d[1]), "=&v"(d[2]), "=&v"(d[3])
-                   : "v"(ro[0] + colb), "v"(ro[1] + colb), "v"(ro[2] + colb), "v"(ro[3] + colb), "s"(g.X)
-                   : "memory");
-    };
-    const unsigned xs0 = (unsigned)(SNA * WA_BYTES + ((oct * 2) * 256 + (2 * half) * 64 + c) * 16);
-    auto store_half = [&](int t, int ch, const f32x4* d) {
-      char* sb = smem + (t % SNB) * WB_BYTES + xs0;
-      float a[4][4];
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        a[q][0] = d[q][0]; a[q][1] = d[q][1]; a[q][2] = d[q][2]; a[q][3] = d[q][3];
-        wg_swap(a[q][0], a[q][2]);
-        wg_swap(a[q][1], a[q][3]);
-      }
-#pragma unroll
-      for (int sx = 0; sx < 2; ++sx) {
-        const float kv[8] = {a[0][sx], a[1][sx], a[2][sx], a[3][sx], a[0][sx + 2], a[1][sx + 2], a[2][sx + 2], a[3][sx + 2]};
-        f32x4 hi, lo;
-        wg_split8(kv, hi, lo);
-        *reinterpret_cast<f32x4*>(sb + ch * 512 + sx * 1024) = hi;
-        *reinterpret_cast<f32x4*>(sb + ch * 512 + sx * 1024 + 4096) = lo;
-      }
-    };
-    const char* abase = g.img + ((int64_t)ks0 * nIT + itile) * WA_BYTES + (wave * 64 + lane) * 16;
-    auto issue_a = [&](int t, bool live) {                     // 16 KiB by 256 threads: four 4 KiB pieces
-      char* sa = smem + (t % SNA) * WA_BYTES + wave * 1024;
-      const char* src = live ? abase + (int64_t)t * nIT * WA_BYTES : g.img;
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-        __builtin_amdgcn_global_load_lds((gptr_f)(live ? src + j * 4096 : src), (lptr_f)(sa + j * 4096), 16, 0, 0);
-    };
-#define PP_ALL(s) "+v"(s.v[0]), "+v"(s.v[1]), "+v"(s.v[2]), "+v"(s.v[3]), "+v"(s.v[4]), "+v"(s.v[5]), "+v"(s.v[6]), "+v"(s.v[7])
-    // prologue: images 0 and 1 requested, X(0) -> stage 0 (plain loads: the compiler's wait drains the DMA pieces too), X(1), X(2), X(3)
-    // requested into the three register sets, X(1) waited for
-    XSet sa_, sb_, sc_;
-    issue_a(0, true);
-    issue_a(1, nk > 1);
-    {
-      const char* xb = reinterpret_cast<const char*>(g.X);
-      const u32x4 ro = row_offsets(0);
-      XSet r0;
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        r0.v[q] = *reinterpret_cast<const f32x4*>(xb + ro[q] + colb0);
-        r0.v[4 + q] = *reinterpret_cast<const f32x4*>(xb + ro[q] + colb1);
-      }
-      store_half(0, 0, &r0.v[0]);
-      store_half(0, 1, &r0.v[4]);
-    }
-    { const u32x4 ro = row_offsets(1); load_half(ro, colb0, &sa_.v[0]); load_half(ro, colb1, &sa_.v[4]); }
-    { const u32x4 ro = row_offsets(2); load_half(ro, colb0, &sb_.v[0]); load_half(ro, colb1, &sb_.v[4]); }
-    { const u32x4 ro = row_offsets(3); load_half(ro, colb0, &sc_.v[0]); load_half(ro, colb1, &sc_.v[4]); }
-    asm volatile("s_waitcnt vmcnt(16)" : PP_ALL(sa_) : : "memory");          // X(1) is here (the images are older: landed)
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    slot_end();                                               // ---- tile 0 complete
-    // k-step s: r = X(s+1) (arrived), r_next = X(s+2) (in flight, waited for at the end)
-    auto kstep = [&](int s, XSet& r, XSet& r_next) {
-      const bool st_ok = s + 1 < nk;
-      const u32x4 ro = row_offsets(s + 4);
-      // ---- slot 2s: the image DMA first (the end-of-k-step wait leaves everything younger than it in flight), column half 0
-#ifdef PPW_NOPROD
-      slot_end(); slot_end(); return;
-#endif
-      issue_a(s + 2, s + 2 < nk);
-      if (st_ok) store_half(s + 1, 0, &r.v[0]);
-      __builtin_amdgcn_sched_barrier(0);
-      load_half(ro, colb0, &r.v[0]);                          // X(s+4), column half 0 (issued after the split read the registers)
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      slot_end();
-      // ---- slot 2s+1: column half 1
-      if (st_ok) store_half(s + 1, 1, &r.v[4]);
-      __builtin_amdgcn_sched_barrier(0);
-      load_half(ro, colb1, &r.v[4]);
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      // in flight, oldest first: X(s+2) [8] | image s+1 [4], X(s+3) [8] | image s+2 [4], X(s+4) [8]: leave the 20 youngest
-      asm volatile("s_waitcnt vmcnt(20)" : PP_ALL(r_next) : : "memory");
-      slot_end();
-    };
-    // (the remainder k-steps sit INSIDE the rotation loop: separate tail copies are laid out where tools/asm_lint.py's linear scan cannot
-    // see the waits that precede them)
-#pragma unroll 1
-    for (int s = 0; s < nk; s += 3) {
-      kstep(s, sa_, sb_);
-      if (s + 1 < nk) kstep(s + 1, sb_, sc_);
-      if (s + 2 < nk) kstep(s + 2, sc_, sa_);
-    }
-    slot_end();                                               // slot 2 nk: group 1's last compute phase
-    asm volatile("s_waitcnt vmcnt(0)" : PP_ALL(sa_), PP_ALL(sb_), PP_ALL(sc_) : : "memory");
-#undef PP_ALL
-    return;
-  }
-
-  // =============================================================== consumers: 2 x 4 waves of 64 (E) x 64 (D)
-  const int cw = wave - 4, wm = cw >> 2, wn = cw & 3;
-  const int r16 = lane & 15, kg = lane >> 4;
-  const unsigned fa_hi = lds0 + ((kg * 2) * 128 + 16 * wm + r16) * 16, fa_lo = fa_hi + 2048;
-  const unsigned fb_hi = lds0 + SNA * WA_BYTES + ((kg * 2) * 256 + 16 * wn + r16) * 16, fb_lo = fb_hi + 4096;
-  f32x4 acc[4][4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-  f32x4 x[WNF];
-  slot_end();                                                 // ---- tile 0 complete (producers' prologue)
-  const bool late = wm != 0;                                  // group 1 runs the same loop one slot later
-  if (late) slot_end();
-#pragma unroll 1
-  for (int s = 0; s < nk; ++s) {
-    const unsigned soa = (unsigned)((s % SNA) * WA_BYTES), sob = (unsigned)((s % SNB) * WB_BYTES);
-    WG_READ8(x, 4, 8, fa_lo + soa, fb_hi + sob);
-    WG_READ8(x, 0, 12, fa_hi + soa, fb_lo + sob);
-    WG_WAIT8(0, x, 4, 8);
-    WG_WAIT8(0, x, 0, 12);
-    slot_end();
-#ifndef PPW_NOMMA
-    wg_term(x, 4, 8, acc);                                    // lo*hi
-    wg_term(x, 0, 12, acc);                                   // hi*lo
-    wg_term(x, 0, 8, acc);                                    // hi*hi
-#endif
-    slot_end();
-  }
-  if (!late) slot_end();
-  // ---- epilogue: tile (ja, jb) of a lane is row 4 (16 wm + 4 (lane >> 4) + e) + ja, column 4 (16 wn + (lane & 15)) + jb: 16-byte stores
-  float* out = g.out + (int64_t)slab * g.E * g.D;
-#pragma unroll
-  for (int ja = 0; ja < 4; ++ja)
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const int64_t i = i0 + 4 * (16 * wm + 4 * kg + e) + ja;
-      const int64_t n = n0 + 4 * (16 * wn + r16);
-      *reinterpret_cast<f32x4*>(out + i * g.D + n) = f32x4{acc[ja][0][e], acc[ja][1][e], acc[ja][2][e], acc[ja][3][e]};
-    }
-}
-
-// ---------------------------------------------------------------------------------------------------------------------------
-// BOTH operands as images (round 4).  The kernels above read X raw and split it on its way into LDS: four E-side tiles do that work for
+// BOTH operands as images (round 4).  The kernel above reads X raw and splits it on its way into LDS: four E-side tiles do that work for
 // every X element, and it is half of the loop (stamped: the consumers alone and the producers alone take the same time).  Here the bag
 // has been laid down ONCE as the D-side operand image (prep job kind 9: per 32-row k-step and 256-column block one 32 KiB tile, byte for
-// byte the LDS stage of the kernels above), by workgroups that ride in a launch of the forward that leaves the chip idle, and dPRE^T's
+// byte the LDS stage of the kernel above), by workgroups that ride in a launch of the forward that leaves the chip idle, and dPRE^T's
 // image is in BAG order (rows that did not take part: zeros) - so a k-step is 48 KiB of linear LDS-DMA, nothing goes through registers,
-// every wave only reads fragments and multiplies.  8 waves as 2 x 4 of 64 x 64 (bag_wgrad_kernel's consumer schedule: the hi*lo term of
-// tile t-1 under the first fragment reads of tile t), 3 stages of [A 16 KiB | B 32 KiB]: tile t+2 is requested when tile t-1 retires.
+// every wave only reads fragments and multiplies.  8 waves as 2 x 4 of 64 x 64 = 48 MFMAs against 16 ds_read_b128 per k-step (the hi*lo
+// term of tile t-1 under the first fragment reads of tile t), 3 stages of [A 16 KiB | B 32 KiB]: tile t+2 is requested when tile t-1 retires.
 // ---------------------------------------------------------------------------------------------------------------------------
 constexpr int DNS = 3, DSTAGE = WA_BYTES + WB_BYTES, DRING = DNS * DSTAGE;                        // 144 KiB
 
@@ -852,45 +442,24 @@ __global__ __launch_bounds__(WTHREADS) void bag_wgrad_dma_kernel(WgradArgs g, co
 #pragma unroll
     for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
   f32x4 x[WNF];
-#if defined(WGD_NOREAD) || defined(WGD_HALFREAD)
-  for (int q = 0; q < WNF; ++q) x[q] = f32x4{1.f, 2.f, 3.f, 4.f};
-#endif
 #pragma unroll 1
   for (int t = 0; t < nk; ++t) {
-#ifndef WGD_NODMA
     asm volatile("s_waitcnt vmcnt(6)" ::: "memory");           // my pieces of tile t have landed (tile t+1's six may be in flight)
-#endif
     __builtin_amdgcn_s_barrier();                              // ... and everybody's; every wave is past its reads of tile t-1
     const unsigned so = (unsigned)((t % DNS) * DSTAGE);
-#ifndef WGD_NODMA
     issue(t + 2, t + 2 < nk);                                  // -> the stage of tile t-1
-#endif
-#ifndef WGD_NOREAD
     WG_READ8(x, 4, 8, fa_lo + so, fb_hi + so);
-#endif
     __builtin_amdgcn_sched_barrier(0);
-#ifndef WGD_NOMMA
     if (t > 0) wg_term(x, 0, 12, acc);                         // hi*lo of tile t-1 (operands still in registers)
-#endif
     __builtin_amdgcn_sched_barrier(0);
-#ifndef WGD_NOREAD
     WG_WAIT8(0, x, 4, 8);
-#ifndef WGD_HALFREAD
     WG_READ8(x, 0, 12, fa_hi + so, fb_lo + so);
-#endif
-#endif
     __builtin_amdgcn_sched_barrier(0);
-#ifndef WGD_NOMMA
     wg_term(x, 4, 8, acc);                                     // lo*hi
-#endif
     __builtin_amdgcn_sched_barrier(0);
-#ifndef WGD_NOREAD
     WG_WAIT8(0, x, 0, 12);
-#endif
     __builtin_amdgcn_sched_barrier(0);
-#ifndef WGD_NOMMA
     wg_term(x, 0, 8, acc);                                     // hi*hi
-#endif
   }
   wg_term(x, 0, 12, acc);                                      // hi*lo of the last tile
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");             // (the last dummy pieces: nothing may land after the workgroup's LDS is handed on)
@@ -959,13 +528,8 @@ __global__ __launch_bounds__(256) void rows_dpre_image_kernel(const float* __res
       const float kv[8] = {gv[0][j], gv[1][j], gv[2][j], gv[3][j], gv[4][j], gv[5][j], gv[6][j], gv[7][j]};
       f32x4 hi, lo;
       wg_split8(kv, hi, lo);
-#ifdef MHIMX_IMG_WT
-      st_f4_wt(reinterpret_cast<float*>(tile + j * 512), hi);
-      st_f4_wt(reinterpret_cast<float*>(tile + j * 512 + 2048), lo);
-#else
       *reinterpret_cast<f32x4*>(tile + j * 512) = hi;
       *reinterpret_cast<f32x4*>(tile + j * 512 + 2048) = lo;
-#endif
     }
   }
   if (part) {                                                   // the four octets' column sums -> one partial row per k-step
@@ -1092,8 +656,7 @@ static int bag_wgrad_impl(void* stream, const mhimx_bag_wgrad_args* bags, int n_
   }
   MHIMX_CHECK_ARG(a->ws_floats >= (int64_t)g.splits * a->E * a->D, "bag_wgrad: workspace too small (%lld floats)", (long long)((int64_t)g.splits * a->E * a->D));
   g.out = a->ws;
-  const size_t smem = WRING + (size_t)g.kps * WBK * 4;
-  MHIMX_ONCE_PER_DEVICE(MHIMX_HIP(hipFuncSetAttribute((const void*)bag_wgrad_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, WRING + W_MAX_CHUNK * 4)));
+  const size_t smem = SRING + (size_t)g.kps * WBK * 4;
   Merge2Side side = {};
   int side_blocks = 0;
   mhimx_reduce_list* defer = a->defer;
@@ -1105,12 +668,10 @@ static int bag_wgrad_impl(void* stream, const mhimx_bag_wgrad_args* bags, int n_
   }
   const int64_t tiles = (a->E / WBI) * (a->D / WBN);
   dim3 grid((unsigned)(8 * tiles * cdiv(g.splits, 8) + side_blocks));
-  static const bool ws_form = getenv("MHIMX_WGRAD_UNIFORM") == nullptr;
-  static const bool pp_form = ws_form && getenv("MHIMX_WGRAD_PP") != nullptr;
   WgradTail tail = {};
   MHIMX_CHECK_ARG(!a->ximg || (n_bags == 1 && !a->rows && aligned16(a->ximg) && a->L == a->n_bag_rows),
                   "bag_wgrad: the bag image (ximg) goes with a bag-ordered dPRE image: one bag, no row list, L = n_bag_rows");
-  if (a->ride_tail && defer && ((ws_form && !pp_form) || a->ximg) && n_bags == 1 && (defer->n > 0 || defer->side.pending == 3)) {
+  if (a->ride_tail && defer && n_bags == 1 && (defer->n > 0 || defer->side.pending == 3)) {
     // the reductions queued so far and (behind the stage-2 gate) the tail's last stage: trailing workgroups of this launch
     for (int i = 0; i < defer->n; ++i) {
       const mhimx_reduce_job& j = defer->j[i];
@@ -1126,30 +687,18 @@ static int bag_wgrad_impl(void* stream, const mhimx_bag_wgrad_args* bags, int n_
     }
     grid.x += (unsigned)(tail.n_reduce + tail.stage3);
   }
-  // The specialised-wave form (bag_wgrad_ws_kernel, ~5 % faster) is the default again.  It was opt-in for a while: with two processes
-  // time-slicing one GPU it ended in a GPU memory access fault on the long TransMIL-shaped launches (tools/two_proc_c3.sh: 3 of 6 runs
-  // died).  Cause: its last asm wait named 6 of the 24 prefetch registers, so the compiler handed the other 18 out again while the
-  // (unused, clamped) last prefetch loads were still in flight, and their data landed on the row offsets of the next asm loads - only
-  // when latency was stretched.  Fixed there, checked by tools/asm_lint.py (tests/test_isa_lint_cpu.py); 12 of 12 two-process runs
-  // finish.  MHIMX_WGRAD_UNIFORM=1 selects the uniform kernel (experiments).
-  // Round 3: bag_wgrad_pp_kernel (specialised waves + ping-pong consumers, 768 threads: what took the projection from 73 to 63 us)
-  // measures the SAME as the specialised-wave kernel here (34.7 vs 34.5 us same-box; consumers alone 27.8, producers alone 27.8, both 37:
-  // ~13 us of the launch are the row table, the first tiles and the 33 MB of slab stores, outside the loop either form pipelines), so the
-  // round-2 kernel stays the default; MHIMX_WGRAD_PP=1 selects the ping-pong form, MHIMX_WGRAD_UNIFORM=1 the uniform one.
-  MHIMX_CHECK_ARG(n_bags == 1 || (ws_form && !pp_form), "bag_wgrad_multi: only the default (specialised-wave) kernel takes several bags");
+  // bag_wgrad_ws_kernel was opt-in for a while: with two processes time-slicing one GPU it ended in a GPU memory access fault on the long
+  // TransMIL-shaped launches (tools/two_proc_c3.sh: 3 of 6 runs died).  Cause: its last asm wait named 6 of the 24 prefetch registers, so
+  // the compiler handed the other 18 out again while the (unused, clamped) last prefetch loads were still in flight, and their data landed
+  // on the row offsets of the next asm loads - only when latency was stretched.  Fixed there, checked by tools/asm_lint.py
+  // (tests/test_isa_lint_cpu.py); 12 of 12 two-process runs finish.
   if (a->ximg) {                                               // both operands as images: nothing but linear DMA and fragments in the loop
     MHIMX_ONCE_PER_DEVICE(MHIMX_HIP(hipFuncSetAttribute((const void*)bag_wgrad_dma_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, DRING)));
     hipLaunchKernelGGL(bag_wgrad_dma_kernel, grid, dim3(WTHREADS), DRING, (hipStream_t)stream, g, (const char*)a->ximg, side_blocks, side, tail);
-  } else if (pp_form) {
-    const size_t smem2 = SRING + (size_t)g.kps * WBK * 4;
-    MHIMX_ONCE_PER_DEVICE(MHIMX_HIP(hipFuncSetAttribute((const void*)bag_wgrad_pp_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, SRING + W_MAX_CHUNK * 4)));
-    hipLaunchKernelGGL(bag_wgrad_pp_kernel, grid, dim3(PP_THREADS), smem2, (hipStream_t)stream, g, side_blocks, side);
-  } else if (ws_form) {
-    const size_t smem2 = SRING + (size_t)g.kps * WBK * 4;
+  } else {
     MHIMX_ONCE_PER_DEVICE(MHIMX_HIP(hipFuncSetAttribute((const void*)bag_wgrad_ws_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, SRING + W_MAX_CHUNK * 4)));
-    hipLaunchKernelGGL(bag_wgrad_ws_kernel, grid, dim3(WTHREADS), smem2, (hipStream_t)stream, g, mb, side_blocks, side, tail);
-  } else
-  hipLaunchKernelGGL(bag_wgrad_kernel, grid, dim3(WTHREADS), smem, (hipStream_t)stream, g, side_blocks, side);
+    hipLaunchKernelGGL(bag_wgrad_ws_kernel, grid, dim3(WTHREADS), smem, (hipStream_t)stream, g, mb, side_blocks, side, tail);
+  }
   MHIMX_LAUNCH_CHECK();
   if (!defer_push(defer, reduce_job_slabs(a->ws, g.splits, a->E, a->D, a->ldc, a->C, a->accumulate))) {
     const int rc = reduce_slabs_now((hipStream_t)stream, a->ws, a->C, a->E, a->D, a->ldc, g.splits, a->accumulate);

@@ -257,7 +257,6 @@ def finish_tail(grad, student, n_train, scale, chain=None):
 # weight-gradient launch becomes a launch of its own (8 x 17.8 us), and the window on 4 streams is bound by how the graph's branches
 # overlap (average concurrency 1.7, profiles/r03_window_timeline.md), not by kernel time.  Opt-in until the tail rides elsewhere.
 _STEP_IMAGES = os.environ.get("MHIMX_STEP_IMAGES", "1") != "0"       # TransMIL: the step's weight images in the preparation launch
-_FOREACH_GRADS = os.environ.get("MHIMX_FOREACH_GRADS", "1") != "0"   # autograd's per-parameter gradient adds as ONE multi-tensor launch
 _WINDOW_BATCHED = os.environ.get("MHIMX_WINDOW_BATCHED", "1") != "0"      # (round 6) mhimx_window_run for windows of same-shaped bags
 _WINDOW_WGRAD = os.environ.get("MHIMX_WINDOW_WGRAD", "0") != "0"
 _WINDOW_PROJECT = os.environ.get("MHIMX_WINDOW_PROJECT", "0") != "0"
@@ -341,8 +340,6 @@ class FusedTrainer:
         self._clip_ws = torch.empty(1024, device=dev) if self.clip_grad else None
         self._g_extra = None
         self._fold_now, self._fold_list = False, None      # (train_step: the backward's last reductions inside the update kernel)
-        self.fold_reductions = os.environ.get("MHIMX_FOLD_REDUCTIONS", "1") != "0"
-        self.ride_prep = os.environ.get("MHIMX_RIDE_PREP", "1") != "0"   # the student-side preparation jobs in the teacher's scorer launch
         self._graph_pool = None
         self._cap_stream = None
         self._side = None                  # the step executor's second stream (mhimx_step_cfg.side_stream: the step as a DAG), made on first use
@@ -517,7 +514,7 @@ class FusedTrainer:
             return self.pure_exec_shapes_ok(x.shape[0], x.shape[1], x.stride(0), x.stride(1), x.data_ptr(), E=s.mlp_dim,
                                             A=s.online_encoder.attention.attention[0].weight.shape[0], C=s.n_classes, max_rows=self.exec_max_rows)
         if not (self.use_executor and self.model_kind == "mhim" and (self.accum == 1 or window) and not hooked and perm is None
-                and ids_shuffle is None and self.ride_prep and s.training and s.n_classes <= 4 and s._op_prec != "f32"
+                and ids_shuffle is None and s.training and s.n_classes <= 4 and s._op_prec != "f32"
                 and s.merge.k * 8 <= 48 and x.shape[1] % 256 == 0 and x.stride(0) % 4 == 0 and x.shape[0] * x.stride(0) * 4 < (1 << 32)):
             return False
         # (csrc/step.hip:check_cfg and mhimx_step_run's own argument checks, mirrored: a bag they would refuse takes the Python path instead
@@ -880,7 +877,7 @@ class FusedTrainer:
         xs = [self.s._check_x(b) for b in bags]
         if self._micro != 0:
             raise L.MhimxError("run_steps: called inside an accumulation window (a fresh update is required)")
-        if self.clip_grad or not self.fold_reductions or self.accum != 1 or self.world != 1 or not all(self._exec_ok(x, it) and self._nat_ok(x, it) for x, it in zip(xs, its)):
+        if self.clip_grad or self.accum != 1 or self.world != 1 or not all(self._exec_ok(x, it) and self._nat_ok(x, it) for x, it in zip(xs, its)):
             out = None
             for b, l, it in zip(bags, labels, its):
                 out = self.train_step(b, l, i=it)
@@ -932,7 +929,7 @@ class FusedTrainer:
             if torch.is_tensor(tns) and not (tns.is_cuda and tns.dtype == torch.int64 and tns.is_contiguous() and tns.device == x.device):
                 raise mh.L.MhimxError(f"{nm}: expected a contiguous int64 tensor on the bag's device ({x.device}), got {tns.dtype} on {tns.device}")
         with ops.pinned_stream():                              # (one bag, one stream: the launches' stream is looked up once)
-            res = self._nat_prep([x], i, with_opt_tick=first, split=self.ride_prep)
+            res = self._nat_prep([x], i, with_opt_tick=first, split=True)       # (the student-side preparation jobs ride in the teacher's scorer launch)
             prep_t, preps = res[0], res[1]
             preps[0]["_ride_jobs"] = res[2] if len(res) > 2 else None
             hook = self._mid_hook if (first and self.overlap_comm and self.comm is None and self.world > 1 and self.accum == 1
@@ -1285,9 +1282,6 @@ class FusedTrainer:
         ADDS every parameter's gradient in a launch of its own (~30 launches of ~5 us, most of them for a few hundred floats, strung
         along the backward's chain); here .grad is empty during the backward - autograd just keeps the tensors our backward functions
         return - and ONE multi-tensor add moves them all into the buffer (which is zero after every update)."""
-        if not _FOREACH_GRADS:
-            torch.autograd.backward(outs, g_outs)
-            return
         fl = self.flat
         pd = getattr(self, "_train_params", None)
         if pd is None:
@@ -1565,7 +1559,7 @@ class FusedTrainer:
 
     def train_step(self, bag, label, **kw):
         # (a step that is followed by its update right here may leave its last reductions to the update kernel: _nat_bag)
-        self._fold_now = self.fold_reductions and self.accum == 1 and self.world == 1 and not self.clip_grad
+        self._fold_now = self.accum == 1 and self.world == 1 and not self.clip_grad
         try:
             out = self.forward_backward(bag, label, **kw)
         finally:

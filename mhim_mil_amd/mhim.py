@@ -37,7 +37,6 @@ from . import ops
 
 _FEATURE_ACTS = ("relu", "gelu")
 _SCORER_ACTS = ("relu", "gelu", "tanh")
-_SPLIT_POOL = os.environ.get("MHIMX_SPLIT_POOL", "1") != "0"      # the student's pool forward in two calls around the Merge tail (ops.abmil_pool_fwd_split)
 
 
 # ----------------------------------------------------------------------------------------------- holders
@@ -637,7 +636,7 @@ class MHIM(nn.Module):
             if q_param is None:
                 q_param = self.merge.global_q_mm.data.view(self.merge.k, -1)
             k = self.merge.k
-            if _SPLIT_POOL and "merge_ws" in prep and k <= 6 and rows_all.numel() - plan.R > k:
+            if "merge_ws" in prep and k <= 6 and rows_all.numel() - plan.R > k:
                 # (round 5) the student's scorer over the rows that stay does not need the tokens, and Merge's rows pass does not need the
                 # scorer: ONE launch runs both (the Merge row tiles at its front); then the Merge tail makes the tokens, and the pool's
                 # finalize launch scores those k rows itself (mhimx_pool_io.phase) - the scorer launch is off the serial chain

@@ -341,7 +341,6 @@ _CHAIN = os.environ.get("MHIMX_PINV_CHAIN", "1") != "0"
 # checks pass with it) and MEASURED EQUAL: the chain launches of a c3 step total 27.66 ms over 29 steps either way (profiles/r05_pinv_levels.md)
 # - a stage's cost follows its outputs and hand-over (two products and five images per stage cost 7-8 us, one product 5 us), not its count.
 _PINV3 = os.environ.get("MHIMX_PINV_LEVELS", "4") == "3"
-_OUT_PROJ = os.environ.get("MHIMX_NYS_OUT_PROJ", "1") != "0"
 _CTRS = {}
 
 
@@ -529,53 +528,10 @@ def _landmark_pinv_backward(lm, scale, a2, z0, stats, chain, dz, dlm, accumulate
 
 # The pseudo-inverse chain (24 dependent launches of 128 workgroups forward, 24 pairs backward: ~8-13 us each, latency-bound) depends on
 # the landmark means alone; the streamed token passes beside it (a3 v forward; its backward) fill the chip with thousands of workgroups.
-# They are independent, so the chain runs on a SIDE stream (a second branch of the captured hipGraph) and joins where its result is
-# needed.  MEASURED (round 3, c3, same box, hipGraph replay): 11.07 ms with the fork against 10.88 ms on one stream - six fork / join pairs
-# per step cost more in cross-queue signalling (~60 us each on this ROCm build) than the overlapped launches save, so the fork is OPT-IN
-# (MHIMX_NYS_FORK=1); the accumulation window of the ABMIL trainer forks once per 8 bags and gains 1.7x from the same mechanism.
-_FORK = os.environ.get("MHIMX_NYS_FORK", "0") != "0"
-_CONV_FIRST = os.environ.get("MHIMX_NYS_CONV_FIRST", "1") != "0"
-_SIDE = {}
-
-
-class _Side:
-    """with _Side(device) as f: ... work on the side stream ...;  f.join(tensors): the current stream waits for it (the tensors made on
-    the side stream are handed to the caching allocator as used by the current one)."""
-
-    def __init__(self, dev):
-        self.on = _FORK and dev.type == "cuda"
-        if self.on:
-            key = (dev.index, torch.cuda.current_stream(dev).cuda_stream)
-            self.side = _SIDE.get(key)
-            if self.side is None:
-                self.side = _SIDE[key] = torch.cuda.Stream(dev)
-            self.cur = torch.cuda.current_stream(dev)
-
-    def __enter__(self):
-        if self.on:
-            self.side.wait_stream(self.cur)
-            self.ctx = torch.cuda.stream(self.side)
-            self.ctx.__enter__()
-        return self
-
-    def __exit__(self, *a):
-        if self.on:
-            self.ctx.__exit__(*a)
-
-    def join(self, tensors=()):
-        if self.on:
-            self.cur.wait_stream(self.side)
-            for t in tensors:
-                if torch.is_tensor(t):
-                    t.record_stream(self.cur)
-
-
-def _flat(x):
-    for t in x:
-        if isinstance(t, (list, tuple)):
-            yield from _flat(t)
-        else:
-            yield t
+# They are independent, but the chain runs inline on the one stream.  MEASURED (round 3, c3, same box, hipGraph replay): 11.07 ms with the
+# chain on a side stream (a second branch of the captured hipGraph) against 10.88 ms on one stream - six fork / join pairs per step cost
+# more in cross-queue signalling (~60 us each on this ROCm build) than the overlapped launches save; the accumulation window of the ABMIL
+# trainer forks once per 8 bags and gains 1.7x from the same mechanism.
 
 
 def _core_forward(qkv, conv_w, l, scale):
@@ -587,22 +543,15 @@ def _core_forward(qkv, conv_w, l, scale):
     L.check(lib.mhimx_landmark_mean(_st(), _ptr(qkv), ld, T, l, 2 * INNER, _ptr(lm)), "landmark_mean")
     ql, kl = Op(lm, 0, DH, 2 * INNER, m, DH), Op(lm, INNER, DH, 2 * INNER, m, DH)
     no = ops.NysOperands(qkv, lm, scale)
-    with _Side(dev) as fork:                                           # the landmark-only chain beside the token pass
-        a2, z, z0, stats, chain = _landmark_pinv_forward(lm, scale)
+    a2, z, z0, stats, chain = _landmark_pinv_forward(lm, scale)        # the landmark-only chain
     a3v, lse3 = ops.nys_a3v_fwd(no)                                    # softmax_n(q~ k^T) v   nystrom:116,131,133
-    fork.join(_flat((a2, z, z0, stats, chain)))
     w2 = torch.empty((HEADS, m, DH), device=dev)
     _heads_mm("nn", batched(z), batched(a3v), batched(w2), HEADS)     # pinv (a3 v)
     wc = conv_w.reshape(HEADS, -1).contiguous()
-    if _CONV_FIRST:
-        out = torch.empty((T, INNER), device=dev)
-        L.check(lib.mhimx_resconv(_st(), _ptr(qkv, 2 * INNER), ld, _ptr(wc), wc.shape[1], DH, T, INNER, _ptr(out), INNER, 0, 0),
-                "resconv")                                            # out = res_conv(v)   nystrom:135-136 (written FIRST: the
-        out, lse1 = ops.nys_out_fwd(no, w2, out, accumulate=True)      # attention adds to it in its epilogue - one pass over out less)
-    else:
-        out, lse1 = ops.nys_out_fwd(no, w2)                            # softmax_m(q k~^T) (pinv a3 v) -> [T, (h d)]
-        L.check(lib.mhimx_resconv(_st(), _ptr(qkv, 2 * INNER), ld, _ptr(wc), wc.shape[1], DH, T, INNER, _ptr(out), INNER, 1, 0),
-                "resconv")                                            # out += res_conv(v)   nystrom:135-136
+    out = torch.empty((T, INNER), device=dev)
+    L.check(lib.mhimx_resconv(_st(), _ptr(qkv, 2 * INNER), ld, _ptr(wc), wc.shape[1], DH, T, INNER, _ptr(out), INNER, 0, 0),
+            "resconv")                                                # out = res_conv(v)   nystrom:135-136 (written FIRST: the
+    out, lse1 = ops.nys_out_fwd(no, w2, out, accumulate=True)          # attention adds to it in its epilogue - one pass over out less)
     return out, (qkv, lm, a2, z, z0, stats, chain, a3v, w2, wc, lse1, lse3, no.ws, l, scale, conv_w.shape)
 
 
@@ -628,13 +577,11 @@ def _core_backward(saved, dout):
     dz = torch.empty_like(z)
     _heads_mm("nt", batched(dw2), batched(a3v), batched(dz), HEADS)    # dz = dw2 a3v^T
     dlm2 = torch.empty_like(dlm)
-    with _Side(dev) as fork:                                           # the pseudo-inverse's backward beside the token-side backward
-        _landmark_pinv_backward(lm, scale, a2, z0, stats, chain, dz, dlm2, accumulate=False)
+    _landmark_pinv_backward(lm, scale, a2, z0, stats, chain, dz, dlm2, accumulate=False)
     da3v = torch.empty_like(a3v)
     _heads_mm("tn", batched(z), batched(dw2), batched(da3v), HEADS)    # da3v = z^T dw2
     # a3v = a3 v: dk, dv +=, the S3 term of dq~
     ops.nys_a3v_bwd(no, a3v, da3v, lse3, dqkv, dlm, accumulate_dv=True)
-    fork.join((dlm2,))
     L.check(lib.mhimx_axpby(_st(), _ptr(dlm2), _ptr(dlm), dlm.numel(), 1.0, 1.0), "axpby")      # + the attn2 terms
     L.check(lib.mhimx_landmark_mean_bwd(_st(), _ptr(dlm), T, l, 2 * INNER, _ptr(dqkv), ld, 1), "landmark_mean_bwd")
     return dqkv, dwc.reshape(wshape)
@@ -704,7 +651,7 @@ class TransLayerFn(torch.autograd.Function):
         else:
             ops.gemm_nt(xn, w_qkv, out=qkv[pad:], prec=_PREC)
         out, saved = _core_forward(qkv, conv_w, l, scale)
-        proj = n >= 2048 and _PREC == "bf16x3" and _OUT_PROJ
+        proj = n >= 2048 and _PREC == "bf16x3"
         if proj:                              # to_out on the projection kernel too (bias + its own dropout stream in the epilogue; 154 -> ~85 us)
             y = ops.bag_project(out[pad:], [ops.ProjHead(ops.pair_planes(w_out), b_out, drop_p=drop_p, drop_seed=seed, resid=x)], act=0,
                                 drop_tick=tick if drop_p > 0 else None)[0].out                           # y = x + dropout(to_out(.)): one launch

@@ -114,15 +114,10 @@ def _state(tr):
 def _same_state(tr_c, tr_p, steps, lr=1e-3):
     """Round 6: up to 16 384 rows the executor's scorer backward writes the stay rows' share of the dPRE image itself (mhimx_pool_grad.img) and
     the image is ordered [stay | merge]: the projection's weight / bias gradient is the same sum in another order, so the two paths' parameters
-    agree to rounding - which Adam turns into up to ~2 lr on an element whose gradient is at rounding level - and no longer bit for bit
-    (MHIMX_FUSE_DPRE=0 in the environment: the old route, bit-identical again).  Counters stay exact."""
-    import os
+    agree to rounding - which Adam turns into up to ~2 lr on an element whose gradient is at rounding level - and no longer bit for bit.
+    Counters stay exact."""
     sc, sp = _state(tr_c), _state(tr_p)
     assert torch.equal(sc[4], sp[4]) and torch.equal(sc[5], sp[5])
-    if os.environ.get("MHIMX_FUSE_DPRE", "1") == "0":
-        for a, b in zip(sc[:4], sp[:4]):
-            assert torch.equal(a, b)
-        return
     for name, a, b in zip(("student", "teacher", "m", "v"), sc[:4], sp[:4]):
         d = (a - b).abs()
         assert float(d.mean()) <= 4e-6 * steps and float(d.max()) <= 2.2 * lr * steps, (name, float(d.mean()), float(d.max()))

@@ -1,6 +1,5 @@
 """Time the streamed Nystrom attention entry points on their own at the c3 size (T = 50 176 tokens): forward pair and the two backward
-entry points (each = one token-column kernel + one landmark-column kernel + small reductions).  Environment switches select kernel
-forms (MHIMX_NYS_BWD_T_V1, MHIMX_NYS_BWD_Q_V1, MHIMX_NYS_STAGGER ...): run once per setting."""
+entry points (each = one token-owning kernel + one landmark-column kernel + small reductions)."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
