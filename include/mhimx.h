@@ -942,6 +942,63 @@ int mhimx_pure_window_run(void* stream, const mhimx_step_cfg* cfg, int32_t n_bag
                           void* ws, int64_t ws_bytes, int32_t update);
 
 /* ------------------------------------------------------------------------------------------
+ * Ragged accumulation window of the full MHIM(ABMIL) model: ONE optimiser update over n_bags bags of DIFFERENT row counts in one call -
+ * teacher, HAM select, Merge, student, distillation, EMA teacher (the recipe's second training under --accumulation_steps).
+ * replaces: engines/base_engine.py:29-51,76-167 (the accumulation window: every bag's loss divided by the window's length, the gradients
+ *           added up, one optimizer.step(), the per-parameter EMA; a shorter last window, :30,50-51) around engines/common_mil.py:14-48
+ *           (forward_func: model_ema.forward_teacher -> model(bag, score, teacher_feat)), i.e. modules/mhim.py:181-227 (forward_teacher),
+ *           :109-179 (get_mask), :318-378 (forward) and their autograd, with the loader's different N per slide
+ *           (datasets/dataset_feat.py:93-111).
+ * The contract of mhimx_window_run without its one-shape rule: every bag's loss is scaled by 1 / n_bags; every bag attends with the window's
+ * FIRST global queries and the queries' EMA is chained over the n token sets afterwards (q <- mm^n q + (1 - mm) sum_b mm^(n-1-b) z_b,
+ * DESIGN.md section 2 (ix)); update = 1: one Adam + EMA-teacher step on the summed gradient; update = 0: the summed gradient is left in
+ * cfg->grad (overwritten, not added to); *cfg->tick and *cfg->opt_step advance ONCE per window.
+ * Per bag: the keep-masks of both feature dropouts and the select / Merge draws are the functions of (seed, tick, row inside the bag, ..)
+ * mhimx_step_run uses - the same seeds at the same tick value give the same masks, element for element.  What is written per bag (feature
+ * rows, score, rows_all, tokens, logits, losses, z) depends on that bag and the window's starting state alone, not on its neighbours.
+ * Enqueue-only and capturable: no allocation, no synchronisation, no host-to-device copy (the bag table travels by value).  No
+ * floating-point atomics, no workgroup that waits for another: every sum has a fixed order, two runs give the same bits.
+ * Launches: 12 window-wide + 13 per bag of up to 16 384 rows (csrc/ragged_window.hip lists them) - both projections, the teacher's scorer
+ * and the projection's weight gradient run once over the call's row space; the per-bag middle is a loop over the entry points above.
+ * cfg: mhimx_step_run's (E = 512, A = 128, C <= 4, 8 k <= 48, D % 256 == 0), with q_out, side_stream and time_project NULL / 0.
+ * 1 <= n_bags <= MHIMX_RAGGED_WINDOW_MAX; per bag the checks mhimx_step_run makes (64 <= N <= MHIMX_STEP_MAX_ROWS, the cnt conditions,
+ * ldx >= D, ldx % 4 == 0, N * ldx * 4 < 2^32, 16-byte aligned rows).  Bag b owns a slot of 32 * ceil((N_b + k) / 32) rows of the call's row
+ * space from layout.row0[b] on: its N feature rows, then the k Merge tokens (rows N .. N+k-1 of H_student), then zero rows.  The row space
+ * holds at most MHIMX_RAGGED_WINDOW_MAX_ROWS rows: the workspace takes 7 265 bytes per row of it - teacher and student feature rows 2 x 2 048,
+ * fp16 d out / d pre 1 024, the student rows' gradient 2 048 (it becomes the fp32 dPRE rows in place), the row list 8, raw and instance
+ * scores 2 x 4, class projections 16, the kept-row map 1, the bias gradient's per-tile partials 64 - and 2 056 per 256-row pool partial of
+ * the teacher: 7 273 per row, 3.8 GB at the cap; besides the weight images (2 E D floats + 3.3 MB), at most 8 E D floats of split-K slabs and ONE
+ * per-bag scratch sized for the largest bag (select, Merge and pool workspaces).
+ * Anything else returns < 0 before any device call, and mhimx_last_error names the bag.
+ * MHIMX_VERSION stays 620: additions only.
+ * ---------------------------------------------------------------------------------------- */
+#define MHIMX_RAGGED_WINDOW_MAX 32                /* = MHIMX_INFER_MAX: the by-value bag table is the inference call's                    */
+#define MHIMX_RAGGED_WINDOW_MAX_ROWS 524288       /* rows of one call's row space (next to MHIMX_PURE_WINDOW_MAX_ROWS)                    */
+typedef struct {
+  const float* X; int64_t ldx, N;                 /* [N, ldx >= D] fp32, 16-byte aligned rows                                            */
+  const int64_t* label_dev;                       /* int64 [1] on the device                                                              */
+  mhimx_step_counts cnt;                          /* mhimx_step_counts_of(N, ...) of THIS bag                                             */
+  mhimx_step_seeds seeds;                         /* this bag's four streams                                                              */
+} mhimx_ragged_window_bag;
+typedef struct {                                  /* byte offsets inside the workspace, valid until the next call on it                   */
+  int64_t total, rows;                            /* bytes; rows of the call's row space                                                  */
+  int64_t logits, losses;                         /* float [n, 16] (C used), float [n, 4] = {main ce + aux cl, ce, cl, -} per bag, NOT scaled */
+  int64_t score;                                  /* float [rows]: the teacher's instance score (bag b: row0[b] .. + N_b)                 */
+  int64_t rows_all;                               /* int64 [rows]: bag b's [rows to merge (R) | rows that stay (Lk) | N .. N+k-1] at row0[b] */
+  int64_t H_teacher, H_student;                   /* float [rows, E] (student: rows N .. N+k-1 of a slot are the merged tokens)           */
+  int64_t dact;                                   /* fp16 [rows, E]: d out / d pre of the student's projection                            */
+  int64_t dpre;                                   /* float [rows, E]: after the call the fp32 dPRE rows (kept rows; every other row zero)  */
+  int64_t z_teacher, z_student;                   /* float [n, E] each                                                                    */
+  int64_t row0[MHIMX_RAGGED_WINDOW_MAX];          /* first row of bag b's slot (a multiple of 32)                                         */
+} mhimx_ragged_window_layout;
+/* pure host arithmetic: works without a device */
+int mhimx_ragged_window_layout_of(const mhimx_step_cfg* cfg, int32_t n_bags, const mhimx_ragged_window_bag* bags,
+                                  mhimx_ragged_window_layout* out);
+/* host_step: the Adam step after this update when cfg->opt_step is NULL */
+int mhimx_ragged_window_run(void* stream, const mhimx_step_cfg* cfg, int32_t n_bags, const mhimx_ragged_window_bag* bags, int64_t host_step,
+                            void* ws, int64_t ws_bytes, int32_t update);
+
+/* ------------------------------------------------------------------------------------------
  * Ragged multi-bag inference: the eval-mode forward of MHIM(ABMIL) for n_bags bags of DIFFERENT row counts in one call - a validation
  * or test pass as one C call per chunk of bags instead of ~8 launches per bag from the host loop.
  * replaces: modules/mhim.py:229-272 (forward_test, merge_test off) under engines/common_mil.py:56-68 (validate_func) and the per-bag

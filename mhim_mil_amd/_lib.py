@@ -253,6 +253,21 @@ class PureWindowLayout(C.Structure):
         ("row0", C.c_int64 * PURE_WINDOW_MAX)]
 
 
+RAGGED_WINDOW_MAX = 32          # MHIMX_RAGGED_WINDOW_MAX
+RAGGED_WINDOW_MAX_ROWS = 524288    # MHIMX_RAGGED_WINDOW_MAX_ROWS (rows of the call's row space: every bag's N + merge_k rounded up to a multiple of 32)
+
+
+class RaggedWindowBag(C.Structure):
+    """mhimx_ragged_window_bag: one bag of a ragged accumulation window of the full MHIM(ABMIL) model."""
+    _fields_ = [("X", c_f32p), ("ldx", C.c_int64), ("N", C.c_int64), ("label_dev", C.c_void_p), ("cnt", StepCounts), ("seeds", StepSeeds)]
+
+
+class RaggedWindowLayout(C.Structure):
+    """mhimx_ragged_window_layout: byte offsets inside the workspace; bag b's slot of the row space starts at row0[b]."""
+    _fields_ = [(n, C.c_int64) for n in ("total", "rows", "logits", "losses", "score", "rows_all", "H_teacher", "H_student", "dact", "dpre",
+                                        "z_teacher", "z_student")] + [("row0", C.c_int64 * RAGGED_WINDOW_MAX)]
+
+
 SYMBOLS = {
     "mhimx_last_error": (C.c_char_p, []),
     "mhimx_version": (C.c_int, []),
@@ -373,6 +388,8 @@ SYMBOLS = {
     "mhimx_pure_step_run_many": (C.c_int, [_P, C.POINTER(StepCfg), _I32, _P, _P, _P, _P, _P, _I64, _P, _I64]),   # (drop_seeds: uint64[n])
     "mhimx_pure_window_layout_of": (C.c_int, [C.POINTER(StepCfg), _I32, _P, C.POINTER(PureWindowLayout)]),
     "mhimx_pure_window_run": (C.c_int, [_P, C.POINTER(StepCfg), _I32, _P, _I64, _P, _I64, _I32]),
+    "mhimx_ragged_window_layout_of": (C.c_int, [C.POINTER(StepCfg), _I32, _P, C.POINTER(RaggedWindowLayout)]),
+    "mhimx_ragged_window_run": (C.c_int, [_P, C.POINTER(StepCfg), _I32, _P, _I64, _P, _I64, _I32]),
 }
 
 _lib = None

@@ -168,6 +168,149 @@ __global__ __launch_bounds__(SC_THREADS, 2) void infer_score_kernel(InferTab tab
   pz[(int64_t)part * IE + tid + SC_THREADS] = z1;
 }
 
+// infer_score_kernel + the class projections (mhimx_ragged_window_run's teacher, ragged_window.hip; a kernel of its own so that the
+// one above keeps its code): while a tile's rows are LDS-resident, the class projections h_r . Wp_c the
+// pseudo score needs (scoring.py:37-58) are taken from the same copy - 8 lanes per row, lane `seg` the 16-byte groups seg, seg + 8, .. of the
+// row, the 8 partial sums added in a fixed xor tree - and written as cproj[row of the row space][4] (C <= 4; columns >= C are zero).
+__global__ __launch_bounds__(SC_THREADS, 2) void infer_score_cproj_kernel(InferTab tab, const float* __restrict__ Hin,
+                                                                          const float* __restrict__ wa_frag, const float* __restrict__ wc,
+                                                                          int act, float* __restrict__ s_out, float* __restrict__ pm,
+                                                                          float* __restrict__ pl, float* __restrict__ pz,
+                                                                          const float* __restrict__ wp, int C, float* __restrict__ cproj) {
+  extern __shared__ __attribute__((aligned(16))) float sc_sm[];
+  float* Hs = sc_sm;                          // [32][516]
+  float* sred = Hs + SC_ROWS * SC_LD;         // [4][32] per-wave partial scores
+  float* srow = sred + 4 * SC_ROWS;           // [32] scores
+  float* prow = srow + SC_ROWS;               // [32] e^{s - m}
+  const int part = blockIdx.x;
+  int bag = 0;
+#pragma unroll
+  for (int b = 1; b < MHIMX_INFER_MAX; ++b)
+    if (b < tab.n && part >= tab.part0[b]) bag = b;
+  int64_t N = tab.N[0], orow0 = tab.row0[0];
+  int p0 = tab.part0[0];
+  IT_PICK(N, N, bag) IT_PICK(orow0, row0, bag) IT_PICK(p0, part0, bag)
+  const int64_t c0 = (int64_t)(part - p0) * SC_CHUNK;           // first row of the chunk inside its bag
+  const int64_t M = (N - c0 < SC_CHUNK) ? N - c0 : SC_CHUNK;    // rows of the chunk (>= 1)
+  const float* T = Hin + (orow0 + c0) * IE;
+  float* so = s_out + orow0 + c0;
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int r32 = lane & 31, kg = lane >> 5;
+  const int n_col = 32 * wave + r32;
+  const float wn = wc[n_col];
+  const f32x4* fptr = reinterpret_cast<const f32x4*>(wa_frag + ((int64_t)wave * (IE / 16) * 64 + lane) * 8);   // + ks * 128 (hi), + 1 (lo)
+  const float* aptr = Hs + r32 * SC_LD + 8 * kg;
+
+  float m_run = -INFINITY, l_run = 0.f, z0 = 0.f, z1 = 0.f;
+  const int tiles = (int)((M + SC_ROWS - 1) / SC_ROWS);
+  for (int tile = 0; tile < tiles; ++tile) {
+    const int64_t row0 = (int64_t)tile * SC_ROWS;
+    // ---- rows -> LDS (rows past the chunk: zeros; their loads are clamped so that all 16 are in flight)
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+      const int f = tid + SC_THREADS * i, r = f >> 7, c4 = f & 127;
+      const int64_t nr = row0 + r;
+      f32x4 v = reinterpret_cast<const f32x4*>(T + (nr < M ? nr : M - 1) * IE)[c4];
+      if (nr >= M) v = f32x4{0.f, 0.f, 0.f, 0.f};
+      *reinterpret_cast<f32x4*>(Hs + r * SC_LD + 4 * c4) = v;
+    }
+    __syncthreads();
+    // ---- U tile on the matrix cores, one accumulator per bf16x3 term
+    in_f16 acc, acc2, acc3;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) { acc[i] = 0.f; acc2[i] = 0.f; acc3[i] = 0.f; }
+    {
+      f32x4 bh = fptr[0], bl = fptr[1];
+#pragma unroll 4
+      for (int ks = 0; ks < IE / 16; ++ks) {
+        const int kn = ks + 1 < IE / 16 ? ks + 1 : ks;
+        const f32x4 nbh = fptr[128 * kn], nbl = fptr[128 * kn + 1];
+        const f32x4 a0 = *reinterpret_cast<const f32x4*>(aptr + 16 * ks), a1 = *reinterpret_cast<const f32x4*>(aptr + 16 * ks + 4);
+        in_b8 ah, al;
+        sc_split(a0, a1, ah, al);
+        const in_b8 bh8 = __builtin_bit_cast(in_b8, bh), bl8 = __builtin_bit_cast(in_b8, bl);
+        acc2 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh8, acc2, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh8, acc, 0, 0, 0);
+        acc3 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl8, acc3, 0, 0, 0);
+        bh = nbh;
+        bl = nbl;
+      }
+    }
+    // ---- scores: acc[i] = U[row = 8 (i >> 2) + 4 kg + (i & 3)][n_col]
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+      const int row = 8 * (i >> 2) + 4 * kg + (i & 3);
+      const float u = acc[i] + (acc2[i] + acc3[i]);
+      const float v = sc_sum32(wn * act_fwd(u, act));
+      if (r32 == 31) sred[wave * SC_ROWS + row] = v;
+    }
+    __syncthreads();
+    if (tid < SC_ROWS) {
+      const int64_t nr = row0 + tid;
+      float s = (sred[tid] + sred[SC_ROWS + tid]) + (sred[2 * SC_ROWS + tid] + sred[3 * SC_ROWS + tid]);
+      if (nr >= M) s = -INFINITY;
+      else so[nr] = s;
+      srow[tid] = s;
+    }
+    {
+      const int row = tid >> 3, seg = tid & 7;
+      float cp[4] = {0.f, 0.f, 0.f, 0.f};
+      const f32x4* hr = reinterpret_cast<const f32x4*>(Hs + row * SC_LD);
+      const f32x4* w4 = reinterpret_cast<const f32x4*>(wp);
+#pragma unroll 4
+      for (int g = 0; g < IE / 32; ++g) {
+        const f32x4 h = hr[seg + 8 * g];
+#pragma unroll
+        for (int c = 0; c < 4; ++c)
+          if (c < C) {
+            const f32x4 w = w4[c * (IE / 4) + seg + 8 * g];
+            cp[c] += (h[0] * w[0] + h[1] * w[1]) + (h[2] * w[2] + h[3] * w[3]);
+          }
+      }
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        cp[c] += __shfl_xor(cp[c], 1);
+        cp[c] += __shfl_xor(cp[c], 2);
+        cp[c] += __shfl_xor(cp[c], 4);
+      }
+      if (seg == 0 && row0 + row < M) *reinterpret_cast<f32x4*>(cproj + (orow0 + c0 + row0 + row) * 4) = f32x4{cp[0], cp[1], cp[2], cp[3]};
+    }
+    __syncthreads();
+    // ---- log-sum-exp partial, running over the chunk's tiles (row 0 of every tile is a real row: the tile maximum is finite)
+    float mt = -INFINITY;
+#pragma unroll
+    for (int q = 0; q < SC_ROWS / 4; ++q) {
+      const f32x4 v = reinterpret_cast<const f32x4*>(srow)[q];
+      mt = fmaxf(fmaxf(mt, fmaxf(v[0], v[1])), fmaxf(v[2], v[3]));
+    }
+    const float m_new = fmaxf(m_run, mt);
+    const float scale = (m_run == -INFINITY) ? 0.f : __expf(m_run - m_new);
+    if (tid < SC_ROWS) prow[tid] = srow[tid] == -INFINITY ? 0.f : __expf(srow[tid] - m_new);
+    __syncthreads();
+    float lsum = 0.f, a0 = 0.f, a1 = 0.f;
+#pragma unroll
+    for (int q = 0; q < SC_ROWS / 4; ++q) {
+      const f32x4 p = reinterpret_cast<const f32x4*>(prow)[q];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const float* hr = Hs + (4 * q + j) * SC_LD;
+        lsum += p[j];
+        a0 += p[j] * hr[tid];
+        a1 += p[j] * hr[tid + SC_THREADS];
+      }
+    }
+    l_run = l_run * scale + lsum;
+    z0 = z0 * scale + a0;
+    z1 = z1 * scale + a1;
+    m_run = m_new;
+    __syncthreads();                           // the next tile overwrites Hs / srow
+  }
+  if (tid == 0) { pm[part] = m_run; pl[part] = l_run; }
+  pz[(int64_t)part * IE + tid] = z0;
+  pz[(int64_t)part * IE + tid + SC_THREADS] = z1;
+}
+
 // ------------------------------------------------------------------------------------------------ 4. merge + head + loss + attention
 // blockIdx.x = bag.  Every block of a bag derives {max, sum} from the bag's partials in the same fixed order.  blockIdx.y = 0: the pooled
 // row (thread e = column e, partials in index order), the predictor in fp32, the cross entropy.  blockIdx.y > 0: the attention map.
@@ -303,6 +446,17 @@ int infer_score(hipStream_t st, const InferTab& tab, const float* H, const float
                 float* pz) {
   MHIMX_ONCE_PER_DEVICE(MHIMX_HIP(hipFuncSetAttribute((const void*)infer_score_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SC_SMEM)));
   hipLaunchKernelGGL(infer_score_kernel, dim3((unsigned)tab.parts), dim3(SC_THREADS), SC_SMEM, st, tab, H, wa_frag, wc, act, s, pm, pl, pz);
+  MHIMX_LAUNCH_CHECK();
+  return 0;
+}
+
+// the same launch + the class projections cproj [rows of the row space][4] = h . Wp_c (wp [C, 512], C <= 4, 16-byte aligned)
+int infer_score_cproj(hipStream_t st, const InferTab& tab, const float* H, const float* wa_frag, const float* wc, int act, float* s, float* pm,
+                      float* pl, float* pz, const float* wp, int C, float* cproj) {
+  MHIMX_CHECK_ARG(wp && cproj && C >= 1 && C <= 4 && aligned16(wp) && aligned16(cproj), "infer_score_cproj: predictor weight [C <= 4, 512] / output");
+  MHIMX_ONCE_PER_DEVICE(MHIMX_HIP(hipFuncSetAttribute((const void*)infer_score_cproj_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SC_SMEM)));
+  hipLaunchKernelGGL(infer_score_cproj_kernel, dim3((unsigned)tab.parts), dim3(SC_THREADS), SC_SMEM, st, tab, H, wa_frag, wc, act, s, pm, pl, pz, wp, C,
+                     cproj);
   MHIMX_LAUNCH_CHECK();
   return 0;
 }

@@ -35,6 +35,17 @@ int pure_window_project(hipStream_t st, const InferTab& tab, const PureWinDrop& 
 int infer_score(hipStream_t st, const InferTab& tab, const float* H, const float* wa_frag, const float* wc, int act, float* s, float* pm, float* pl,
                 float* pz);
 
+// the same launch + the class projections of the pseudo score, cproj [rows of the row space][4] = h . Wp_c (C <= 4), taken while the rows are
+// LDS-resident (mhimx_ragged_window_run's teacher)
+int infer_score_cproj(hipStream_t st, const InferTab& tab, const float* H, const float* wa_frag, const float* wc, int act, float* s, float* pm,
+                      float* pl, float* pz, const float* wp, int C, float* cproj);
+// pure_window.hip's split-K rule, d W1 = sum_b dPRE_b^T X_b launch (pw_tn_kernel<true>) and index-order reduction launch as host calls
+int pw_split_k(int steps, int want_max, int div, int32_t* S, int32_t* per);
+int pw_wgrad_bagx(hipStream_t st, const InferTab& tab, const float* dpre, int D, int steps, int S, int per, float* slabs);
+int pw_reduce(hipStream_t st, int n, const float* const* parts, const int32_t* G, const int64_t* W, float* const* out);
+// step.hip: the checks mhimx_step_run makes on (cfg, N, counts)
+int step_check_cfg(const mhimx_step_cfg* c, int64_t N, const mhimx_step_counts* n);
+
 // the ragged one-model projection launch (bag_project.hip): Hout[row0[b] + m, :] = act(X_b[m, :] W1^T + b1) for every bag b of the table
 int infer_project(hipStream_t st, const InferTab& tab, int D, const float* w1p, const float* b1, int act, float* Hout);
 

@@ -546,6 +546,33 @@ void pw_layout(const mhimx_step_cfg* c, int32_t n_bags, const mhimx_pure_window_
 
 }  // namespace
 
+// ---- for mhimx_ragged_window_run (ragged_window.hip): the split-K rule, the d W1 launch and the reduction launch of this file as host calls
+// split-K slabs for `steps` 32-row k-steps: steps / div of them, 1 .. want_max, never an empty one.  Returns the slabs to make ROOM for (a
+// count that never shrinks when the window grows); *S <= room are written, *per k-steps each.
+int pw_split_k(int steps, int want_max, int div, int32_t* S, int32_t* per) {
+  int s = steps / div;
+  s = s < 1 ? 1 : (s > want_max ? want_max : s);
+  *per = (int32_t)cdiv(steps, s);
+  *S = (int32_t)cdiv(steps, *per);
+  return s;
+}
+// slabs[z][512][D] = sum over the k-steps of slab z of dpre[rows, 512]^T X_b[rows, D]: launch 7 of the header over the table's row space
+int pw_wgrad_bagx(hipStream_t st, const InferTab& tab, const float* dpre, int D, int steps, int S, int per, float* slabs) {
+  hipLaunchKernelGGL(pw_tn_kernel<true>, dim3((unsigned)(D / TN_BN), IE / TN_BM, (unsigned)S), dim3(TN_T), 0, st, tab, dpre, IE, nullptr, 0, steps, per, slabs,
+                     IE, D);
+  MHIMX_LAUNCH_CHECK();
+  return 0;
+}
+// out_j[i] = sum_{g < G_j} parts_j[g W_j + i], j < n <= 6, in index order: launch 8 of the header
+int pw_reduce(hipStream_t st, int n, const float* const* parts, const int32_t* G, const int64_t* W, float* const* out) {
+  MHIMX_CHECK_ARG(n >= 1 && n <= RED_JOBS, "pw_reduce: 1..%d jobs", RED_JOBS);
+  PwRed r = {};
+  for (int j = 0; j < n; ++j) { r.parts[j] = parts[j]; r.G[j] = G[j]; r.W[j] = W[j]; r.out[j] = out[j]; }
+  hipLaunchKernelGGL(pw_reduce_kernel, dim3(RED_BLOCKS, RED_JOBS), dim3(RED_T), 0, st, r);
+  MHIMX_LAUNCH_CHECK();
+  return 0;
+}
+
 }  // namespace mhimx
 
 extern "C" int mhimx_pure_window_layout_of(const mhimx_step_cfg* cfg, int32_t n_bags, const mhimx_pure_window_bag* bags,

@@ -225,6 +225,8 @@ void layout(const mhimx_step_cfg* c, int64_t N, const mhimx_step_counts* n, Step
 
 }  // namespace
 
+int step_check_cfg(const mhimx_step_cfg* c, int64_t N, const mhimx_step_counts* n) { return check_cfg(c, N, n); }      // (ragged_window.hip)
+
 }  // namespace mhimx
 
 using namespace mhimx;

@@ -360,6 +360,10 @@ class FusedTrainer:
         # 'mhim_pure' accumulation windows as ONE call (mhimx_pure_window_run): rows of the call's row space (every bag rounded up to a
         # multiple of 32) a window may have - its workspace takes 5.7 KB per row (1.5 GB at this cap); include/mhimx.h allows twice as many
         self.pure_window_row_cap = 262144
+        # 'mhim' accumulation windows of different-sized bags as ONE call (mhimx_ragged_window_run): rows of the call's row space (every
+        # bag's N + merge_k rounded up to a multiple of 32) a window may have - its workspace takes 7.3 KB per row (1.9 GB at this cap);
+        # include/mhimx.h allows twice as many
+        self.ragged_window_row_cap = 262144
 
     def _dist(self):
         return torch.distributed.is_available() and torch.distributed.is_initialized()
@@ -768,7 +772,104 @@ class FusedTrainer:
                         "score": view(bg.score, j, N), "R": cnt.R, "tokens": Hs[N:], "H_student": Hs[:N],
                         "H_teacher": view(bg.H_teacher, j, N * E).view(N, E)})
             logits.append(lg); losses.append(ls)
-        self.last = dict(per[-1], logits=logits, losses=losses, bags=per, ws=ws)
+        self.last = dict(per[-1], logits=logits, losses=losses, bags=per, ws=ws, exec="mhimx_window_run")
+        self._micro = n
+        if inside:
+            fl.step += 1
+            ops.step_images(None)
+            self._micro = 0
+        elif update:
+            self.update()
+        return logits, losses
+
+    # ------------------------------------------------------------------------------------------------- the ragged window behind the C-ABI
+    @staticmethod
+    def ragged_window_shapes_ok(bags, D, k, E=512, A=128, C=2, max_rows=262144, row_cap=524288, max_bags=32):
+        """csrc/ragged_window.hip check_rw (csrc/step.hip check_cfg per bag) and mhimx_ragged_window_run's own argument checks, mirrored and
+        tensor-free: a window the call would refuse takes today's route instead of raising.  ``bags``: one (N, D, pitch, inner, ptr,
+        (k_top, n_sel, len_keep, Lk, R)) per bag - shape, strides in floats, address, its counts; ``D``: the model's input width; ``k``:
+        merge_k."""
+        if not (E == 512 and A == 128 and 1 <= C <= 4 and k >= 1 and 8 * k <= 48 and D > 0 and D % 256 == 0 and D <= (1 << 20)
+                and 1 <= len(bags) <= max_bags):
+            return False
+        rows = 0
+        for N, Db, pitch, inner, ptr, cnt in bags:
+            k_top, n_sel, len_keep, Lk, R = cnt
+            if not (Db == D and 64 <= N <= max_rows and 1 <= k_top <= (4096 if N <= 16384 else 16384) and 1 <= n_sel <= k_top
+                    and len_keep == N - n_sel and Lk >= 1 and 1 <= R <= 32768 and Lk + R == len_keep):
+                return False
+            if not (inner == 1 and pitch >= D and pitch % 4 == 0 and N * pitch * 4 < (1 << 32) and ptr != 0 and ptr % 16 == 0):
+                return False
+            rows += (N + k + 31) // 32 * 32
+        return rows <= row_cap
+
+    def _ragged_window_ok(self, xs, labels, i=None):
+        """True when mhimx_ragged_window_run takes this window: 1 .. accumulation_steps bags that each take the step executor, one process,
+        device-drawn subsets, no mid-run ratio schedule, merge_k <= 6.  Decided before any seed is drawn or counter touched."""
+        s = self.s
+        if ops.KERNEL_EVENT_HOOK is not None or not xs or self.model_kind != "mhim":
+            return False
+        if not (self.use_executor and self.accum > 1 and 1 <= len(xs) <= self.accum and len(labels) == len(xs) and self.world == 1
+                and self._chain is None and not self.step_dag and not getattr(self, "time_project", False) and self._micro == 0
+                and s.baseline == "attn" and s.mrh_sche is None and s._op_prec != "f32" and s.merge_enable and s.merge.k <= 6):
+            return False
+        dev = xs[0].device
+        if not all(torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.device == dev for x in xs):
+            return False
+        if not all(torch.is_tensor(l) and l.is_cuda and l.dtype == torch.int64 and l.numel() == 1 and l.device == dev for l in labels):
+            return False
+        if not all(self._nat_ok(x, i) and self._exec_ok(x, i, window=True) for x in xs):
+            return False
+        return self.ragged_window_shapes_ok(
+            [(x.shape[0], x.shape[1], x.stride(0), x.stride(1), x.data_ptr(), s.v2_counts(x.shape[0], i)) for x in xs], s.input_dim, s.merge.k,
+            E=s.mlp_dim, A=s.online_encoder.attention.attention[0].weight.shape[0], C=s.n_classes, max_rows=self.exec_max_rows,
+            row_cap=min(self.ragged_window_row_cap, mh.L.RAGGED_WINDOW_MAX_ROWS), max_bags=mh.L.RAGGED_WINDOW_MAX)
+
+    def _exec_ragged_window(self, xs, labels, i, update):
+        """One accumulation window of different-sized bags - 1 .. accumulation_steps of them, every loss scaled by 1 / len(bags) - as ONE
+        call of mhimx_ragged_window_run.  Returns ([logits per bag], [losses per bag]); self.last["bags"] holds each bag's views."""
+        L = mh.L
+        s, t, fl = self.s, self.t, self.flat
+        n = len(xs)
+        ex = self._exec_cfg()
+        table = (L.RaggedWindowBag * n)()
+        for j, (x, l) in enumerate(zip(xs, labels)):
+            k_top, n_sel, len_keep, Lk, R = s.v2_counts(x.shape[0], i)
+            table[j].X, table[j].ldx, table[j].N, table[j].label_dev = x.data_ptr(), x.stride(0), x.shape[0], l.data_ptr()
+            table[j].cnt = L.StepCounts(k_top=k_top, n_sel=n_sel, len_keep=len_keep, Lk=Lk, R=R)
+        lay = ops.ragged_window(ex["cfg"], table, n, layout_only=True)
+        dev = xs[0].device
+        if torch.cuda.is_current_stream_capturing():
+            ws = torch.empty(lay.total, dtype=torch.uint8, device=dev)
+        else:
+            ws = ex.get("ws_rw")
+            if ws is None or ws.numel() < lay.total or ws.device != dev:
+                ws = ex["ws_rw"] = torch.full((int(lay.total * 1.25),), 255, dtype=torch.uint8, device=dev)      # (poisoned: see _exec_window)
+        # (bag after bag - both dropout streams, the select's, Merge's - the order the stream form draws them in for such a window: the
+        # two routes make the same draws)
+        for j in range(n):
+            table[j].seeds = L.StepSeeds(drop_teacher=t._next_seed(teacher=True), drop_student=s._next_seed(), select=s._next_seed(),
+                                         mca=s._next_seed())
+        inside = bool(update and not self.clip_grad)              # (clipping needs the norm of the final gradient: the update stays outside)
+        ops.ragged_window(ex["cfg"], table, n, fl.step + int(inside), ws, inside)
+        km, E, Cc = s.merge.k, s.mlp_dim, s.n_classes
+
+        def view(off, cnt_, dtype=torch.float32):
+            return ws[off:off + cnt_ * dtype.itemsize].view(dtype)
+
+        lg, ls = view(lay.logits, n * 16).view(n, 16), view(lay.losses, n * 4).view(n, 4)
+        Hs, Ht = view(lay.H_student, lay.rows * E).view(lay.rows, E), view(lay.H_teacher, lay.rows * E).view(lay.rows, E)
+        dact = view(lay.dact, lay.rows * E, torch.float16).view(lay.rows, E)
+        score, rows_all = view(lay.score, lay.rows), view(lay.rows_all, lay.rows, torch.int64)
+        zt, zs = view(lay.z_teacher, n * E).view(n, E), view(lay.z_student, n * E).view(n, E)
+        per = []
+        for j, x in enumerate(xs):
+            r0, N, cnt = int(lay.row0[j]), x.shape[0], table[j].cnt
+            per.append({"logits": lg[j, :Cc], "losses": ls[j, :3], "patch_num": N, "keep_num": cnt.Lk + km, "rows": rows_all[r0:r0 + cnt.len_keep],
+                        "score": score[r0:r0 + N], "R": cnt.R, "tokens": Hs[r0 + N:r0 + N + km], "H_student": Hs[r0:r0 + N],
+                        "H_teacher": Ht[r0:r0 + N], "dact": dact[r0:r0 + N], "z_teacher": zt[j], "z_student": zs[j], "row0": r0})
+        logits, losses = [p_["logits"] for p_ in per], [p_["losses"] for p_ in per]
+        self.last = dict(per[-1], logits=logits, losses=losses, bags=per, layout=lay, table=table, ws=ws, exec="mhimx_ragged_window_run")
         self._micro = n
         if inside:
             fl.step += 1
@@ -1114,12 +1215,21 @@ class FusedTrainer:
           window ends with the same chain of EMA steps on the tokens those forwards produced (oracle ``train_window(q_ema="window")``;
           differs from the reference's bag-after-bag order in second order of 1 - merge_mm).
         Each bag's loss is scaled by 1 / accumulation_steps in the head kernel (base_engine.py:102).  Capturable (``capture_window``).
+        Full windows of same-shaped bags take mhimx_window_run; windows of DIFFERENT-sized bags (1 .. accumulation_steps of them: a shorter last window
+        is scaled by its own length) take mhimx_ragged_window_run; injected draws, several processes, a kernel event hook, a ratio
+        schedule, prec="f32", merge_k > 6 and MHIMX_STEP_EXEC=0 keep the stream form below.  ``self.last["exec"]`` names the route.
         Returns ([logits per bag], [losses per bag])."""
         k = len(bags)
         if self.model_kind == "mhim_pure" and self.accum > 1:
             return self._pure_window_step(bags, labels, i, perms, shuffles, update)
-        assert k == self.accum and len(labels) == k, "window_step takes exactly accumulation_steps bags"
         xs = [self.s._check_x(b) for b in bags]
+        # bags of different sizes (or a same-shaped window mhimx_window_run does not take), a shorter last window too: ONE call of
+        # mhimx_ragged_window_run, every loss scaled by 1 / len(bags) (base_engine.py:30,50-51,102)
+        # (a full window of same-shaped bags keeps its routes: mhimx_window_run, or the stream form where that call does not take it)
+        one_shape = k == self.accum and all(x.shape == xs[0].shape and x.stride() == xs[0].stride() for x in xs)
+        if not one_shape and perms is None and shuffles is None and self._ragged_window_ok(xs, labels, i):
+            return self._exec_ragged_window(xs, labels, i, update)
+        assert k == self.accum and len(labels) == k, "window_step takes exactly accumulation_steps bags"
         if not self.window_ok(xs, i) or perms is not None or self.world > 1:
             outs = [self.train_step(b, l, i=i, **({} if perms is None else {"perm": perms[j], "ids_shuffle": shuffles[j]}))
                     for j, (b, l) in enumerate(zip(bags, labels))]
@@ -1203,6 +1313,8 @@ class FusedTrainer:
         if self.model_kind == "mhim_pure" and self.accum > 1:
             if not self._pure_window_ok([self.s._check_x(b) for b in bags], labels):
                 raise mh.L.MhimxError("capture_window: mhimx_pure_window_run does not take these bags / this model")
+        elif self._ragged_window_ok([self.s._check_x(b) for b in bags], labels, kw.get("i")):
+            pass                                    # (window_step decides between mhimx_window_run and mhimx_ragged_window_run)
         elif not self.window_ok([self.s._check_x(b) for b in bags], kw.get("i")):
             raise mh.L.MhimxError("capture_window: these bags / this model do not take the single-pass ABMIL step")
         self._capturing = True

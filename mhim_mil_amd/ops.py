@@ -1024,6 +1024,19 @@ def pure_window_run(cfg, bags, n, host_step, ws, update):
             "mhimx_pure_window_run")
 
 
+# ------------------------------------------------------------------------------------------- ragged MHIM accumulation window
+def ragged_window(cfg, bags, n, host_step=0, ws=None, update=False, layout_only=False):
+    """mhimx_ragged_window_layout_of (host arithmetic only) and, unless ``layout_only``, mhimx_ragged_window_run: ONE optimiser update
+    (update = False: the summed gradient only) of the full MHIM(ABMIL) model over the n bags of the by-value table ``bags``
+    (_lib.RaggedWindowBag * n: rows, pitch, N, label, this bag's counts and seeds) as one C call.  Returns the layout."""
+    lay = L.RaggedWindowLayout()
+    L.check(L.lib().mhimx_ragged_window_layout_of(C.byref(cfg), n, bags, C.byref(lay)), "mhimx_ragged_window_layout_of")
+    if not layout_only:
+        L.check(L.lib().mhimx_ragged_window_run(_stream(), C.byref(cfg), n, bags, int(host_step), ws.data_ptr(), ws.numel(), int(bool(update))),
+                "mhimx_ragged_window_run")
+    return lay
+
+
 # ------------------------------------------------------------------------------------------- streamed Nystrom attention
 class NysOperands:
     """mhimx_nys: the packed to_qkv output qkv [T, 1536] (q | k | v, heads = 64-column groups), the landmark means lm [256, 1024]
