@@ -1040,6 +1040,36 @@ int64_t mhimx_infer_ws_bytes(const mhimx_infer_cfg* cfg, int32_t n_bags, const m
 int mhimx_infer_run(void* stream, const mhimx_infer_cfg* cfg, int32_t n_bags, const mhimx_infer_bag* bags, const int64_t* labels_dev,
                     const mhimx_infer_out* out, void* ws, int64_t ws_bytes);
 
+/* ------------------------------------------------------------------------------------------
+ * Half-precision feature bags in the three ragged calls: the bags' rows as fp16 or bf16, read where they lie - no widened copy.
+ * replaces: datasets/dataset_feat.py:86-93 (the bag is whatever dtype torch.load finds in the slide's feature file - extractors that
+ *           ran under autocast store fp16 / bf16) under engines/base_engine.py:77,271 (the --amp autocast regions of the train and the
+ *           validation loop, options.py:173-178), without the fp32 copy of the bag a caller of the fp32 entry points has to make first.
+ * x_dtype: ONE element type for all bags of a call.  The X field of every bag entry then points to elements of that type (the struct
+ * field keeps its `const float*` spelling: cast), and ldx counts elements.  Everything else - cfg, outputs, workspace, layouts,
+ * launches, determinism, capturability - is the fp32 call's: mhimx_infer_ws_bytes and the two *_layout_of functions do not depend on
+ * the element type (the workspace holds no copy of X; they apply the fp32 pitch rule, which every pitch that is valid here passes
+ * while N * ldx < 2^30).
+ * Same bits as the fp32 call on the widened rows: only the two kernels that read X change (the ragged projection, the d W1 = sum_b
+ * dPRE_b^T X_b launch); they load half the bytes, widen to fp32 in registers - exact for every fp16 and bf16 value, subnormals
+ * included - and run the fp32 kernels' bf16 hi / lo split, k loop, three MFMA terms and epilogue unchanged.  (For bf16 rows the lo
+ * plane is identically zero; all three terms are kept.)  x_dtype = MHIMX_X_F32 IS the fp32 entry point: same checks, messages, bits.
+ * Checks for the 2-byte types, before any device call, mhimx_last_error names the bag: x_dtype in 0..2; X 16-byte aligned; ldx >= D,
+ * ldx % 8 == 0 (16-byte rows), ldx <= 2^20; in the two window calls N * ldx * 2 < 2^32 (the fp32 form's bound in bytes of the
+ * actual element).  inf / NaN elements propagate as they do from fp32 rows.
+ * Not covered: the single-bag executors (mhimx_step_run, mhimx_pure_step_run, mhimx_window_run) read fp32 rows only.
+ * MHIMX_VERSION stays 620: additions only.
+ * ---------------------------------------------------------------------------------------- */
+#define MHIMX_X_F32 0
+#define MHIMX_X_F16 1
+#define MHIMX_X_BF16 2
+int mhimx_infer_run_x(void* stream, const mhimx_infer_cfg* cfg, int32_t n_bags, const mhimx_infer_bag* bags, const int64_t* labels_dev,
+                      const mhimx_infer_out* out, void* ws, int64_t ws_bytes, int32_t x_dtype);
+int mhimx_pure_window_run_x(void* stream, const mhimx_step_cfg* cfg, int32_t n_bags, const mhimx_pure_window_bag* bags, int64_t host_step,
+                            void* ws, int64_t ws_bytes, int32_t update, int32_t x_dtype);
+int mhimx_ragged_window_run_x(void* stream, const mhimx_step_cfg* cfg, int32_t n_bags, const mhimx_ragged_window_bag* bags,
+                              int64_t host_step, void* ws, int64_t ws_bytes, int32_t update, int32_t x_dtype);
+
 /* dst = src (float4 grid-stride stream copy): the on-box HBM copy rate bench.py reports beside the nominal 8 TB/s */
 int mhimx_stream_copy(void* stream, const float* src, float* dst, int64_t n_floats);
 

@@ -237,6 +237,7 @@ class InferOut(C.Structure):
 
 INFER_MAX = 32               # MHIMX_INFER_MAX
 INFER_MAX_ROWS = 4194304     # MHIMX_INFER_MAX_ROWS
+X_F32, X_F16, X_BF16 = 0, 1, 2   # MHIMX_X_*: the element type of the bags' rows in the three *_run_x calls
 
 PURE_WINDOW_MAX = 32         # MHIMX_PURE_WINDOW_MAX
 PURE_WINDOW_MAX_ROWS = 524288   # MHIMX_PURE_WINDOW_MAX_ROWS (rows of the call's row space: every bag rounded up to a multiple of 32)
@@ -382,14 +383,17 @@ SYMBOLS = {
     "mhimx_window_run": (C.c_int, [_P, C.POINTER(StepCfg), _I32, _P, _I64, _I64, _P, C.POINTER(StepCounts), C.POINTER(StepSeeds), _I64, _P, _I64, _I32]),   # (labels: void*[n])
     "mhimx_infer_ws_bytes": (_I64, [C.POINTER(InferCfg), _I32, _P]),
     "mhimx_infer_run": (C.c_int, [_P, C.POINTER(InferCfg), _I32, _P, _P, C.POINTER(InferOut), _P, _I64]),
+    "mhimx_infer_run_x": (C.c_int, [_P, C.POINTER(InferCfg), _I32, _P, _P, C.POINTER(InferOut), _P, _I64, _I32]),
     "mhimx_step_run_many": (C.c_int, [_P, C.POINTER(StepCfg), _I32, _P, _P, _P, _P, C.POINTER(StepCounts), C.POINTER(StepSeeds), _I64, _P, _I64]),
     "mhimx_pure_step_layout_of": (C.c_int, [C.POINTER(StepCfg), _I64, C.POINTER(StepLayout)]),
     "mhimx_pure_step_run": (C.c_int, [_P, C.POINTER(StepCfg), _P, _I64, _I64, _P, C.c_uint64, _I64, _P, _I64, _I32]),
     "mhimx_pure_step_run_many": (C.c_int, [_P, C.POINTER(StepCfg), _I32, _P, _P, _P, _P, _P, _I64, _P, _I64]),   # (drop_seeds: uint64[n])
     "mhimx_pure_window_layout_of": (C.c_int, [C.POINTER(StepCfg), _I32, _P, C.POINTER(PureWindowLayout)]),
     "mhimx_pure_window_run": (C.c_int, [_P, C.POINTER(StepCfg), _I32, _P, _I64, _P, _I64, _I32]),
+    "mhimx_pure_window_run_x": (C.c_int, [_P, C.POINTER(StepCfg), _I32, _P, _I64, _P, _I64, _I32, _I32]),
     "mhimx_ragged_window_layout_of": (C.c_int, [C.POINTER(StepCfg), _I32, _P, C.POINTER(RaggedWindowLayout)]),
     "mhimx_ragged_window_run": (C.c_int, [_P, C.POINTER(StepCfg), _I32, _P, _I64, _P, _I64, _I32]),
+    "mhimx_ragged_window_run_x": (C.c_int, [_P, C.POINTER(StepCfg), _I32, _P, _I64, _P, _I64, _I32, _I32]),
 }
 
 _lib = None

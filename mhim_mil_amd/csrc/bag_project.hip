@@ -61,7 +61,13 @@ typedef float in_f2 __attribute__((ext_vector_type(2)));
 // dropout (row key = row INSIDE the bag: a bag's mask is the one mhimx_bag_project draws for it alone with the same seed and tick) and the
 // fp16 d out / d pre rows - and the rows between a bag's N and the next multiple of 32 (the call's row space starts every bag at a
 // multiple of 32) are written as zero rows, so that no later launch of the window reads workspace memory nobody wrote.
-template <bool TRAIN>
+//
+// XT: the element type of the bags' rows (mhimx.h MHIMX_X_*: 0 fp32, 1 fp16, 2 bf16; tab.X then points to 2-byte elements and ldx counts
+// them).  A half row is loaded as half the bytes per unit (8 / 8 / 4 instead of 16 / 16 / 8: still three VMEM operations per k-step, so the
+// waits and the DMA ring are the fp32 form's), widened to fp32 in registers - exact for every fp16 and bf16 value, subnormals included - and
+// handed to the same split (XRow / x_widen: infer_tab.hpp): the LDS image, and with it every bit behind it, is that of the fp32 kernel on
+// the widened rows.
+template <bool TRAIN, int XT>
 MHIMX_DEV void infer_project_body(const InferTab& tab, int D, const float* __restrict__ w1p, const float* __restrict__ b1, int act,
                                   float* __restrict__ Hout, const PureWinDrop& dr) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -82,9 +88,11 @@ MHIMX_DEV void infer_project_body(const InferTab& tab, int D, const float* __res
   IT_PICK(X, X, bag) IT_PICK(ldx, ldx, bag) IT_PICK(N, N, bag) IT_PICK(orow0, row0, bag) IT_PICK(t0, tile0, bag)
   const int64_t m0 = (int64_t)(m_tile - t0) * IBM;             // first row of the tile inside its bag
   const int64_t n0 = (int64_t)n_tile * IBN;
-  const float* Xt = X + m0 * ldx;                              // uniform: the tile's first row
+  typedef typename XRow<XT>::elt XE;
+  const XE* Xt = reinterpret_cast<const XE*>(X) + m0 * ldx;    // uniform: the tile's first row
 
-  // ---- A (raw fp32 rows): two 16-byte units u = tid + 512 j (row u >> 3, slot u & 7; rows 0..127) and one 8-byte unit of rows 128..159
+  // ---- A (raw rows): two units of 4 elements u = tid + 512 j (row u >> 3, slot u & 7; rows 0..127) and one unit of 2 elements of rows
+  // 128..159 - 16 / 16 / 8 bytes of fp32, 8 / 8 / 4 bytes of fp16 / bf16
   unsigned aoff[3];                                           // byte offsets from Xt (< 160 rows)
   unsigned a_hi[3], a_lo[3];
 #pragma unroll
@@ -94,7 +102,7 @@ MHIMX_DEV void infer_project_body(const InferTab& tab, int D, const float* __res
     const int sub = j < 2 ? 0 : (tid & 1) * 4;
     int64_t mr = row;
     if (m0 + mr >= N) mr = N - 1 - m0;                         // clamped rows feed accumulators that are never stored
-    aoff[j] = (unsigned)((mr * ldx + slot * 4 + (sub >> 1)) * 4);
+    aoff[j] = (unsigned)((mr * ldx + slot * 4 + (sub >> 1)) * (int)sizeof(XE));
     const int sw = mt_swz(row), kg2 = (slot >> 1) * 2;
     a_hi[j] = (unsigned)(row * 128 + ((kg2 ^ sw) << 4) + (slot & 1) * 8 + sub);
     a_lo[j] = (unsigned)(row * 128 + (((kg2 + 1) ^ sw) << 4) + (slot & 1) * 8 + sub);
@@ -114,13 +122,19 @@ MHIMX_DEV void infer_project_body(const InferTab& tab, int D, const float* __res
     }
   };
   // the A loads of the loop are inline asm, waited for by hand (the compiler's wait-count pass would drain the DMA pieces issued behind them)
-  struct ARegs { f32x4 v0, v1; in_f2 v2; };
+  struct ARegs { typename XRow<XT>::v4 v0, v1; typename XRow<XT>::v2 v2; };
   auto load_a_async = [&](int t, ARegs& r) {
-    const float* xk = Xt + (int64_t)t * IBK;                   // uniform: an SGPR pair
-    asm volatile("global_load_dwordx4 %0, %3, %6\n\tglobal_load_dwordx4 %1, %4, %6\n\tglobal_load_dwordx2 %2, %5, %6"
-                 : "=&v"(r.v0), "=&v"(r.v1), "=&v"(r.v2)
-                 : "v"(aoff[0]), "v"(aoff[1]), "v"(aoff[2]), "s"(xk)
-                 : "memory");
+    const XE* xk = Xt + (int64_t)t * IBK;                      // uniform: an SGPR pair
+    if constexpr (XT == 0)
+      asm volatile("global_load_dwordx4 %0, %3, %6\n\tglobal_load_dwordx4 %1, %4, %6\n\tglobal_load_dwordx2 %2, %5, %6"
+                   : "=&v"(r.v0), "=&v"(r.v1), "=&v"(r.v2)
+                   : "v"(aoff[0]), "v"(aoff[1]), "v"(aoff[2]), "s"(xk)
+                   : "memory");
+    else
+      asm volatile("global_load_dwordx2 %0, %3, %6\n\tglobal_load_dwordx2 %1, %4, %6\n\tglobal_load_dword %2, %5, %6"
+                   : "=&v"(r.v0), "=&v"(r.v1), "=&v"(r.v2)
+                   : "v"(aoff[0]), "v"(aoff[1]), "v"(aoff[2]), "s"(xk)
+                   : "memory");
   };
   auto split4 = [&](const f32x4& v, char* hi_p, char* lo_p) {
     in_bf4 hi, lo;
@@ -135,14 +149,15 @@ MHIMX_DEV void infer_project_body(const InferTab& tab, int D, const float* __res
   };
   auto store_a = [&](int t, const ARegs& r) {                 // registers -> bf16 hi / lo -> the paired row image of stage t % 3
     char* sa = smem + (t % INST) * ISTAGE;
-    split4(r.v0, sa + a_hi[0], sa + a_lo[0]);
-    split4(r.v1, sa + a_hi[1], sa + a_lo[1]);
+    split4(x_widen<XT>(r.v0), sa + a_hi[0], sa + a_lo[0]);
+    split4(x_widen<XT>(r.v1), sa + a_hi[1], sa + a_lo[1]);
+    const in_f2 v2 = x_widen<XT>(r.v2);
     in_bf2 hi, lo;
 #pragma unroll
     for (int q = 0; q < 2; ++q) {
-      const __bf16 h = (__bf16)r.v2[q];
+      const __bf16 h = (__bf16)v2[q];
       hi[q] = h;
-      lo[q] = (__bf16)(r.v2[q] - (float)h);
+      lo[q] = (__bf16)(v2[q] - (float)h);
     }
     *reinterpret_cast<in_bf2*>(sa + a_hi[2]) = hi;
     *reinterpret_cast<in_bf2*>(sa + a_lo[2]) = lo;
@@ -171,9 +186,9 @@ MHIMX_DEV void infer_project_body(const InferTab& tab, int D, const float* __res
   {
     ARegs r0;
     const char* xb = reinterpret_cast<const char*>(Xt);
-    r0.v0 = *reinterpret_cast<const f32x4*>(xb + aoff[0]);
-    r0.v1 = *reinterpret_cast<const f32x4*>(xb + aoff[1]);
-    r0.v2 = *reinterpret_cast<const in_f2*>(xb + aoff[2]);
+    r0.v0 = *reinterpret_cast<const typename XRow<XT>::v4*>(xb + aoff[0]);
+    r0.v1 = *reinterpret_cast<const typename XRow<XT>::v4*>(xb + aoff[1]);
+    r0.v2 = *reinterpret_cast<const typename XRow<XT>::v2*>(xb + aoff[2]);
     store_a(0, r0);
   }
   load_a_async(nk > 1 ? 1 : 0, rga);
@@ -311,14 +326,45 @@ MHIMX_DEV void infer_project_body(const InferTab& tab, int D, const float* __res
 
 __global__ __launch_bounds__(ITHREADS, 2) void infer_project_kernel(InferTab tab, int D, const float* __restrict__ w1p,
                                                                     const float* __restrict__ b1, int act, float* __restrict__ Hout) {
-  infer_project_body<false>(tab, D, w1p, b1, act, Hout, PureWinDrop{});
+  infer_project_body<false, 0>(tab, D, w1p, b1, act, Hout, PureWinDrop{});
 }
 __global__ __launch_bounds__(ITHREADS, 2) void pure_window_project_kernel(InferTab tab, PureWinDrop dr, int D, const float* __restrict__ w1p,
                                                                           const float* __restrict__ b1, int act, float* __restrict__ Hout) {
-  infer_project_body<true>(tab, D, w1p, b1, act, Hout, dr);
+  infer_project_body<true, 0>(tab, D, w1p, b1, act, Hout, dr);
+}
+// the same two kernels over fp16 (XT = 1) / bf16 (XT = 2) rows: mhimx_infer_run_x, mhimx_pure_window_run_x, mhimx_ragged_window_run_x
+template <int XT>
+__global__ __launch_bounds__(ITHREADS, 2) void infer_project_x_kernel(InferTab tab, int D, const float* __restrict__ w1p,
+                                                                      const float* __restrict__ b1, int act, float* __restrict__ Hout) {
+  infer_project_body<false, XT>(tab, D, w1p, b1, act, Hout, PureWinDrop{});
+}
+template <int XT>
+__global__ __launch_bounds__(ITHREADS, 2) void pure_window_project_x_kernel(InferTab tab, PureWinDrop dr, int D, const float* __restrict__ w1p,
+                                                                            const float* __restrict__ b1, int act, float* __restrict__ Hout) {
+  infer_project_body<true, XT>(tab, D, w1p, b1, act, Hout, dr);
+}
+template <int XT>
+static int pure_window_project_x(hipStream_t st, const InferTab& tab, const PureWinDrop& dr, int D, const float* w1p, const float* b1, int act,
+                                 float* Hout) {
+  MHIMX_ONCE_PER_DEVICE(MHIMX_HIP(hipFuncSetAttribute((const void*)pure_window_project_x_kernel<XT>, hipFuncAttributeMaxDynamicSharedMemorySize, INST * ISTAGE)));
+  hipLaunchKernelGGL(pure_window_project_x_kernel<XT>, dim3((unsigned)(8 * (IE / IBN) * cdiv(tab.tiles, 8))), dim3(ITHREADS), INST * ISTAGE, st, tab, dr,
+                     D, w1p, b1, act, Hout);
+  MHIMX_LAUNCH_CHECK();
+  return 0;
+}
+template <int XT>
+static int infer_project_x(hipStream_t st, const InferTab& tab, int D, const float* w1p, const float* b1, int act, float* Hout) {
+  MHIMX_ONCE_PER_DEVICE(MHIMX_HIP(hipFuncSetAttribute((const void*)infer_project_x_kernel<XT>, hipFuncAttributeMaxDynamicSharedMemorySize, INST * ISTAGE)));
+  hipLaunchKernelGGL(infer_project_x_kernel<XT>, dim3((unsigned)(8 * (IE / IBN) * cdiv(tab.tiles, 8))), dim3(ITHREADS), INST * ISTAGE, st, tab, D, w1p,
+                     b1, act, Hout);
+  MHIMX_LAUNCH_CHECK();
+  return 0;
 }
 
+// (tab.pad: the element type of the bags' rows, MHIMX_X_*; the entry points have checked it)
 int pure_window_project(hipStream_t st, const InferTab& tab, const PureWinDrop& dr, int D, const float* w1p, const float* b1, int act, float* Hout) {
+  if (tab.pad == MHIMX_X_F16) return pure_window_project_x<1>(st, tab, dr, D, w1p, b1, act, Hout);
+  if (tab.pad == MHIMX_X_BF16) return pure_window_project_x<2>(st, tab, dr, D, w1p, b1, act, Hout);
   MHIMX_ONCE_PER_DEVICE(MHIMX_HIP(hipFuncSetAttribute((const void*)pure_window_project_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, INST * ISTAGE)));
   hipLaunchKernelGGL(pure_window_project_kernel, dim3((unsigned)(8 * (IE / IBN) * cdiv(tab.tiles, 8))), dim3(ITHREADS), INST * ISTAGE, st, tab, dr, D,
                      w1p, b1, act, Hout);
@@ -327,6 +373,8 @@ int pure_window_project(hipStream_t st, const InferTab& tab, const PureWinDrop& 
 }
 
 int infer_project(hipStream_t st, const InferTab& tab, int D, const float* w1p, const float* b1, int act, float* Hout) {
+  if (tab.pad == MHIMX_X_F16) return infer_project_x<1>(st, tab, D, w1p, b1, act, Hout);
+  if (tab.pad == MHIMX_X_BF16) return infer_project_x<2>(st, tab, D, w1p, b1, act, Hout);
   MHIMX_ONCE_PER_DEVICE(MHIMX_HIP(hipFuncSetAttribute((const void*)infer_project_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, INST * ISTAGE)));
   hipLaunchKernelGGL(infer_project_kernel, dim3((unsigned)(8 * (IE / IBN) * cdiv(tab.tiles, 8))), dim3(ITHREADS), INST * ISTAGE, st, tab, D, w1p, b1,
                      act, Hout);

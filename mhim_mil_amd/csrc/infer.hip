@@ -399,7 +399,9 @@ __global__ __launch_bounds__(FIN_T) void infer_finalize_kernel(InferTab tab, con
 // ------------------------------------------------------------------------------------------------ host
 struct InferWs { int64_t w1p, wa_frag, H, s, pm, pl, pz, total; };
 
-int check_infer(const mhimx_infer_cfg* c, int32_t n_bags, const mhimx_infer_bag* bags) {
+// xdt: the element type of the bags' rows (MHIMX_X_*); the 2-byte types have their own pitch rule (16-byte rows: 8 elements)
+int check_infer(const mhimx_infer_cfg* c, int32_t n_bags, const mhimx_infer_bag* bags, int32_t xdt = MHIMX_X_F32) {
+  MHIMX_CHECK_ARG(xdt >= MHIMX_X_F32 && xdt <= MHIMX_X_BF16, "infer: x_dtype %d is none of MHIMX_X_F32 / F16 / BF16", xdt);
   MHIMX_CHECK_ARG(c && bags, "infer: null configuration / bag list");
   MHIMX_CHECK_ARG(n_bags >= 1 && n_bags <= MHIMX_INFER_MAX, "infer: 1..%d bags per call", MHIMX_INFER_MAX);
   MHIMX_CHECK_ARG(c->E == IE && c->A == IA && c->C >= 1 && c->C <= FIN_MAXC && c->D > 0 && c->D % 256 == 0 && c->D <= (1 << 20),
@@ -410,7 +412,11 @@ int check_infer(const mhimx_infer_cfg* c, int32_t n_bags, const mhimx_infer_bag*
   for (int b = 0; b < n_bags; ++b) {
     const mhimx_infer_bag& g = bags[b];
     MHIMX_CHECK_ARG(g.N >= 1 && g.N <= MHIMX_INFER_MAX_ROWS, "infer: bag %d: N must be in 1..%d", b, MHIMX_INFER_MAX_ROWS);
-    MHIMX_CHECK_ARG(g.ldx >= c->D && g.ldx % 4 == 0 && g.ldx <= (1 << 20), "infer: bag %d: row pitch below D or not a multiple of 4 floats", b);
+    if (xdt == MHIMX_X_F32)
+      MHIMX_CHECK_ARG(g.ldx >= c->D && g.ldx % 4 == 0 && g.ldx <= (1 << 20), "infer: bag %d: row pitch below D or not a multiple of 4 floats", b);
+    else
+      MHIMX_CHECK_ARG(g.ldx >= c->D && g.ldx % 8 == 0 && g.ldx <= (1 << 20),
+                      "infer: bag %d: row pitch below D or not a multiple of 8 two-byte elements", b);
     rows += g.N;
   }
   MHIMX_CHECK_ARG(rows <= MHIMX_INFER_MAX_ROWS, "infer: more than %d rows in one call", MHIMX_INFER_MAX_ROWS);
@@ -473,8 +479,13 @@ extern "C" int64_t mhimx_infer_ws_bytes(const mhimx_infer_cfg* cfg, int32_t n_ba
 
 extern "C" int mhimx_infer_run(void* stream, const mhimx_infer_cfg* cfg, int32_t n_bags, const mhimx_infer_bag* bags,
                                const int64_t* labels_dev, const mhimx_infer_out* out, void* ws, int64_t ws_bytes) {
+  return mhimx_infer_run_x(stream, cfg, n_bags, bags, labels_dev, out, ws, ws_bytes, MHIMX_X_F32);
+}
+
+extern "C" int mhimx_infer_run_x(void* stream, const mhimx_infer_cfg* cfg, int32_t n_bags, const mhimx_infer_bag* bags,
+                                 const int64_t* labels_dev, const mhimx_infer_out* out, void* ws, int64_t ws_bytes, int32_t x_dtype) {
   using namespace mhimx;
-  if (int r = check_infer(cfg, n_bags, bags)) return r;
+  if (int r = check_infer(cfg, n_bags, bags, x_dtype)) return r;
   const mhimx_step_params& P = cfg->p;
   MHIMX_CHECK_ARG(P.w1 && P.b1 && P.wa && P.wc && P.wp && P.bp, "infer: null parameter");
   MHIMX_CHECK_ARG(aligned16(P.w1) && aligned16(P.b1) && aligned16(P.wa), "infer: feature / scorer weights must be 16-byte aligned");
@@ -484,6 +495,7 @@ extern "C" int mhimx_infer_run(void* stream, const mhimx_infer_cfg* cfg, int32_t
   InferWs w;
   InferTab tab = {};
   infer_layout(cfg, n_bags, bags, &w, &tab);
+  tab.pad = x_dtype;                           // read by the projection launch alone: the only reader of X
   MHIMX_CHECK_ARG(ws && (reinterpret_cast<uintptr_t>(ws) & 255) == 0, "infer: the workspace must be 256-byte aligned");
   MHIMX_CHECK_ARG(ws_bytes >= w.total, "infer: workspace too small (%lld bytes, need %lld)", (long long)ws_bytes, (long long)w.total);
   hipStream_t st = (hipStream_t)stream;

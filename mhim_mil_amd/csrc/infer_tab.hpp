@@ -11,13 +11,36 @@ struct InferTab {
   int64_t row0[MHIMX_INFER_MAX];                  // first row of the bag in the call's row space (feature rows, score, attn)
   int32_t tile0[MHIMX_INFER_MAX];                 // first 160-row projection tile
   int32_t part0[MHIMX_INFER_MAX];                 // first pool partial (= first 256-row scorer chunk)
-  int32_t n, tiles, parts, pad;
+  int32_t n, tiles, parts, pad;                   // pad: the element type of the rows X points to (mhimx.h MHIMX_X_*; 0 = fp32)
 };
 // (constant indices only: a dynamically indexed by-value argument is copied to scratch)
 #define IT_PICK(dst, field, b)                                   \
   _Pragma("unroll") for (int q_ = 0; q_ < MHIMX_INFER_MAX; ++q_) \
     if (q_ == (b)) dst = tab.field[q_];
 
+// The element type XT (MHIMX_X_*) of the bags' rows in the two kernels that read X (infer_project_body: bag_project.hip; pw_tn_body:
+// pure_window.hip): what 4 / 2 consecutive elements are loaded as, and their widening to fp32 - exact for every fp16 and bf16 value,
+// subnormals included (v_cvt_f32_f16 honours fp16 denormals; a bf16 IS the upper half of an fp32).  XT = 0 is the identity.
+typedef float x_f2 __attribute__((ext_vector_type(2)));
+typedef unsigned x_u2 __attribute__((ext_vector_type(2)));
+typedef _Float16 x_h2 __attribute__((ext_vector_type(2)));
+template <int XT> struct XRow { typedef float elt; typedef f32x4 v4; typedef x_f2 v2; };
+template <> struct XRow<1> { typedef _Float16 elt; typedef x_u2 v4; typedef unsigned v2; };
+template <> struct XRow<2> { typedef unsigned short elt; typedef x_u2 v4; typedef unsigned v2; };
+template <int XT> MHIMX_DEV x_f2 x_widen(unsigned w) {          // two 2-byte elements of one dword
+  if constexpr (XT == 1) {
+    const x_h2 h = __builtin_bit_cast(x_h2, w);
+    return x_f2{(float)h[0], (float)h[1]};
+  } else {
+    return x_f2{__builtin_bit_cast(float, w << 16), __builtin_bit_cast(float, w & 0xffff0000u)};
+  }
+}
+template <int XT> MHIMX_DEV f32x4 x_widen(const x_u2& w) {
+  const x_f2 a = x_widen<XT>(w[0]), b = x_widen<XT>(w[1]);
+  return f32x4{a[0], a[1], b[0], b[1]};
+}
+template <int XT> MHIMX_DEV const f32x4& x_widen(const f32x4& v) { return v; }
+template <int XT> MHIMX_DEV const x_f2& x_widen(const x_f2& v) { return v; }
 
 constexpr int INFER_TILE_ROWS = 160;              // rows of a projection tile (bag-major tile numbering: InferTab.tile0)
 constexpr int IE = 512;                           // feature width of the ragged path

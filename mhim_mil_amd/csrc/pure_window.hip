@@ -312,105 +312,20 @@ __global__ __launch_bounds__(PW_T, 2) void pw_pool_bwd_kernel(InferTab tab, cons
 // 2 x 2, 64 x 64 per wave = 2 x 2 blocks of v_mfma_f32_32x32x16_bf16 in the 3-term bf16 form.  Both operands come in as fp32 rows (16-byte
 // coalesced loads one k-step ahead), are split to bf16 hi / lo and written to LDS TRANSPOSED (a column's 32 k-values contiguous), so that a
 // fragment is one 16-byte LDS read.  BAGX: B = the bags' X, each where it lies: the k-step's bag from the table, rows past its N clamped
-// (their A rows are zero rows).
+// (their A rows are zero rows).  XT (BAGX only; MHIMX_X_*): fp16 / bf16 bag rows come in as 8-byte loads of 4 elements and are widened to fp32
+// (x_widen: exact) in front of the same split - the LDS image is that of the fp32 kernel on the widened rows.
 template <bool BAGX>
 __global__ __launch_bounds__(TN_T, 2) void pw_tn_kernel(InferTab tab, const float* __restrict__ A, int lda, const float* __restrict__ B, int ldb,
                                                         int steps, int steps_per, float* __restrict__ slabs, int M, int Nc) {
-  __shared__ __attribute__((aligned(16))) char lds[4][TN_BM * TN_PITCH];      // A hi, A lo, B hi, B lo
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wm = wave >> 1, wn = wave & 1;
-  const int m0 = blockIdx.y * TN_BM, n0 = blockIdx.x * TN_BN, z = blockIdx.z;
-  const int ks0 = z * steps_per, ks1 = ks0 + steps_per < steps ? ks0 + steps_per : steps;
-  const int c4 = tid & 31, rg = tid >> 5;                     // this thread's 4 columns and 4 rows (4 rg .. 4 rg + 3) of a k-step
-  f32x4 ra[4], rb[4];
-  auto load = [&](int ks) {
-    const int64_t row = (int64_t)ks * 32 + 4 * rg;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) ra[j] = *reinterpret_cast<const f32x4*>(A + (row + j) * lda + m0 + 4 * c4);
-    if constexpr (BAGX) {
-      const int64_t k0 = (int64_t)ks * 32;
-      int bag = 0;
-#pragma unroll
-      for (int b = 1; b < MHIMX_INFER_MAX; ++b)
-        if (b < tab.n && k0 >= tab.row0[b]) bag = b;
-      const float* X = tab.X[0];
-      int64_t ldx = tab.ldx[0], N = tab.N[0], orow0 = tab.row0[0];
-      IT_PICK(X, X, bag) IT_PICK(ldx, ldx, bag) IT_PICK(N, N, bag) IT_PICK(orow0, row0, bag)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        int64_t rin = row + j - orow0;
-        if (rin >= N) rin = N - 1;
-        rb[j] = *reinterpret_cast<const f32x4*>(X + rin * ldx + n0 + 4 * c4);
-      }
-    } else {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) rb[j] = *reinterpret_cast<const f32x4*>(B + (row + j) * ldb + n0 + 4 * c4);
-    }
-  };
-  auto store = [&](const f32x4 (&r)[4], char* hi_p, char* lo_p) {
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      pw_b4 hi, lo;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const __bf16 h = (__bf16)r[j][q];
-        hi[j] = h;
-        lo[j] = (__bf16)(r[j][q] - (float)h);
-      }
-      const int off = (4 * c4 + q) * TN_PITCH + 8 * rg;
-      *reinterpret_cast<pw_b4*>(hi_p + off) = hi;
-      *reinterpret_cast<pw_b4*>(lo_p + off) = lo;
-    }
-  };
-  pw_f16 acc[2][2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
-  const int r32 = lane & 31, kg = lane >> 5;
-  if (ks0 < ks1) load(ks0);
-#pragma unroll 1
-  for (int ks = ks0; ks < ks1; ++ks) {
-    __syncthreads();                                          // the previous k-step's fragment reads are over
-    store(ra, lds[0], lds[1]);
-    store(rb, lds[2], lds[3]);
-    __syncthreads();
-    if (ks + 1 < ks1) load(ks + 1);
-#pragma unroll
-    for (int k2 = 0; k2 < 2; ++k2) {
-      pw_b8 ah[2], al[2], bh[2], bl[2];
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        const int ao = (wm * 64 + i * 32 + r32) * TN_PITCH + 32 * k2 + 16 * kg;
-        const int bo = (wn * 64 + i * 32 + r32) * TN_PITCH + 32 * k2 + 16 * kg;
-        ah[i] = *reinterpret_cast<const pw_b8*>(lds[0] + ao);
-        al[i] = *reinterpret_cast<const pw_b8*>(lds[1] + ao);
-        bh[i] = *reinterpret_cast<const pw_b8*>(lds[2] + bo);
-        bl[i] = *reinterpret_cast<const pw_b8*>(lds[3] + bo);
-      }
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[i], bh[j], acc[i][j], 0, 0, 0);
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bl[j], acc[i][j], 0, 0, 0);
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bh[j], acc[i][j], 0, 0, 0);
-        }
-    }
-  }
-  float* out = slabs + (int64_t)z * M * Nc;
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        const int row = m0 + wm * 64 + i * 32 + 8 * (e >> 2) + 4 * kg + (e & 3);
-        const int col = n0 + wn * 64 + j * 32 + r32;
-        out[(int64_t)row * Nc + col] = acc[i][j][e];
-      }
+  constexpr int XT = MHIMX_X_F32;
+#include "pw_tn_body.hpp"
+}
+// d W1 over fp16 (XT = 1) / bf16 (XT = 2) bags
+template <int XT>
+__global__ __launch_bounds__(TN_T, 2) void pw_tn_x_kernel(InferTab tab, const float* __restrict__ A, int lda, const float* __restrict__ B, int ldb,
+                                                          int steps, int steps_per, float* __restrict__ slabs, int M, int Nc) {
+  constexpr bool BAGX = true;                                   // (B / ldb: unused - the argument list of pw_tn_kernel)
+#include "pw_tn_body.hpp"
 }
 
 // ------------------------------------------------------------------------------------------------ 8. every partial buffer, in index order
@@ -464,7 +379,9 @@ struct PwLay {
   int32_t steps, sa, sa_per, s1, s1_per;
 };
 
-int check_pw(const mhimx_step_cfg* c, int32_t n_bags, const mhimx_pure_window_bag* bags) {
+// xdt: the element type of the bags' rows (MHIMX_X_*); the 2-byte types have their own pitch rule (16-byte rows: 8 elements)
+int check_pw(const mhimx_step_cfg* c, int32_t n_bags, const mhimx_pure_window_bag* bags, int32_t xdt = MHIMX_X_F32) {
+  MHIMX_CHECK_ARG(xdt >= MHIMX_X_F32 && xdt <= MHIMX_X_BF16, "pure_window: x_dtype %d is none of MHIMX_X_F32 / F16 / BF16", xdt);
   MHIMX_CHECK_ARG(c && bags, "pure_window: null configuration / bag list");
   MHIMX_CHECK_ARG(n_bags >= 1 && n_bags <= MHIMX_PURE_WINDOW_MAX, "pure_window: 1..%d bags per window (got %d)", MHIMX_PURE_WINDOW_MAX, n_bags);
   MHIMX_CHECK_ARG(c->E == IE && c->A == PW_A && c->C >= 1 && c->C <= PW_MAXC && c->D > 0 && c->D % 256 == 0 && c->D <= (1 << 20),
@@ -482,8 +399,14 @@ int check_pw(const mhimx_step_cfg* c, int32_t n_bags, const mhimx_pure_window_ba
   for (int b = 0; b < n_bags; ++b) {
     const mhimx_pure_window_bag& q = bags[b];
     MHIMX_CHECK_ARG(q.N >= 1 && q.N <= MHIMX_STEP_MAX_ROWS, "pure_window: bag %d: N must be in 1..%d", b, MHIMX_STEP_MAX_ROWS);
-    MHIMX_CHECK_ARG(q.ldx >= c->D && q.ldx % 4 == 0, "pure_window: bag %d: row pitch below D or not a multiple of 4 floats", b);
-    MHIMX_CHECK_ARG(q.N * q.ldx * 4 < ((int64_t)1 << 32), "pure_window: bag %d: N * ldx * 4 must stay below 2^32", b);
+    if (xdt == MHIMX_X_F32) {
+      MHIMX_CHECK_ARG(q.ldx >= c->D && q.ldx % 4 == 0, "pure_window: bag %d: row pitch below D or not a multiple of 4 floats", b);
+      MHIMX_CHECK_ARG(q.N * q.ldx * 4 < ((int64_t)1 << 32), "pure_window: bag %d: N * ldx * 4 must stay below 2^32", b);
+    } else {
+      MHIMX_CHECK_ARG(q.ldx >= c->D && q.ldx % 8 == 0 && q.ldx <= (1 << 20),
+                      "pure_window: bag %d: row pitch below D, above 2^20 or not a multiple of 8 two-byte elements", b);
+      MHIMX_CHECK_ARG(q.N * q.ldx * 2 < ((int64_t)1 << 32), "pure_window: bag %d: N * ldx * 2 must stay below 2^32", b);
+    }
     rows += align_up(q.N, PW_ROWS);
   }
   MHIMX_CHECK_ARG(rows <= MHIMX_PURE_WINDOW_MAX_ROWS, "pure_window: %lld rows in the window's row space, at most %d", (long long)rows,
@@ -558,6 +481,13 @@ int pw_split_k(int steps, int want_max, int div, int32_t* S, int32_t* per) {
 }
 // slabs[z][512][D] = sum over the k-steps of slab z of dpre[rows, 512]^T X_b[rows, D]: launch 7 of the header over the table's row space
 int pw_wgrad_bagx(hipStream_t st, const InferTab& tab, const float* dpre, int D, int steps, int S, int per, float* slabs) {
+  if (tab.pad != MHIMX_X_F32) {                                 // (tab.pad: the element type of the bags' rows; the entry points have checked it)
+    const dim3 grid((unsigned)(D / TN_BN), IE / TN_BM, (unsigned)S);
+    if (tab.pad == MHIMX_X_F16) hipLaunchKernelGGL(pw_tn_x_kernel<1>, grid, dim3(TN_T), 0, st, tab, dpre, IE, nullptr, 0, steps, per, slabs, IE, D);
+    else hipLaunchKernelGGL(pw_tn_x_kernel<2>, grid, dim3(TN_T), 0, st, tab, dpre, IE, nullptr, 0, steps, per, slabs, IE, D);
+    MHIMX_LAUNCH_CHECK();
+    return 0;
+  }
   hipLaunchKernelGGL(pw_tn_kernel<true>, dim3((unsigned)(D / TN_BN), IE / TN_BM, (unsigned)S), dim3(TN_T), 0, st, tab, dpre, IE, nullptr, 0, steps, per, slabs,
                      IE, D);
   MHIMX_LAUNCH_CHECK();
@@ -590,8 +520,13 @@ extern "C" int mhimx_pure_window_layout_of(const mhimx_step_cfg* cfg, int32_t n_
 
 extern "C" int mhimx_pure_window_run(void* stream, const mhimx_step_cfg* cfg, int32_t n_bags, const mhimx_pure_window_bag* bags,
                                      int64_t host_step, void* ws, int64_t ws_bytes, int32_t update) {
+  return mhimx_pure_window_run_x(stream, cfg, n_bags, bags, host_step, ws, ws_bytes, update, MHIMX_X_F32);
+}
+
+extern "C" int mhimx_pure_window_run_x(void* stream, const mhimx_step_cfg* cfg, int32_t n_bags, const mhimx_pure_window_bag* bags,
+                                       int64_t host_step, void* ws, int64_t ws_bytes, int32_t update, int32_t x_dtype) {
   using namespace mhimx;
-  if (int r = check_pw(cfg, n_bags, bags)) return r;
+  if (int r = check_pw(cfg, n_bags, bags, x_dtype)) return r;
   for (int b = 0; b < n_bags; ++b) {
     MHIMX_CHECK_ARG(bags[b].X && aligned16(bags[b].X), "pure_window: bag %d: null or unaligned rows", b);
     MHIMX_CHECK_ARG(bags[b].label_dev, "pure_window: bag %d: null label", b);
@@ -601,6 +536,7 @@ extern "C" int mhimx_pure_window_run(void* stream, const mhimx_step_cfg* cfg, in
   PwLay w;
   InferTab tab = {};
   pw_layout(cfg, n_bags, bags, &w, &tab, nullptr);
+  tab.pad = x_dtype;                           // read by the two launches that read X: the projection (2) and d W1 (7)
   MHIMX_CHECK_ARG(ws && (reinterpret_cast<uintptr_t>(ws) & 255) == 0, "pure_window: the workspace must be 256-byte aligned");
   MHIMX_CHECK_ARG(ws_bytes >= w.total, "pure_window: workspace too small (%lld bytes, need %lld)", (long long)ws_bytes, (long long)w.total);
   const mhimx_step_cfg& c = *cfg;
@@ -649,9 +585,7 @@ extern "C" int mhimx_pure_window_run(void* stream, const mhimx_step_cfg* cfg, in
                      F(w.slab_a), PW_A, IE);
   MHIMX_LAUNCH_CHECK();
   // ---- 7. d W1 = sum_b dPRE_b^T X_b
-  hipLaunchKernelGGL(pw_tn_kernel<true>, dim3((unsigned)(D / TN_BN), IE / TN_BM, (unsigned)w.s1), dim3(TN_T), 0, st, tab, F(w.dpre), IE, nullptr, 0, w.steps,
-                     w.s1_per, F(w.slab_1), IE, D);
-  MHIMX_LAUNCH_CHECK();
+  if (int r = pw_wgrad_bagx(st, tab, F(w.dpre), D, w.steps, w.s1, w.s1_per, F(w.slab_1))) return r;
   // ---- 8. the partial buffers, in index order, into the gradient views
   {
     PwRed r = {};

@@ -240,7 +240,9 @@ struct RwLay {
 
 int64_t slot_rows(int64_t N, int64_t k) { return align_up(N + k, RW_ROWS); }
 
-int check_rw(const mhimx_step_cfg* c, int32_t n_bags, const mhimx_ragged_window_bag* bags) {
+// xdt: the element type of the bags' rows (MHIMX_X_*); the 2-byte types have their own pitch rule (16-byte rows: 8 elements)
+int check_rw(const mhimx_step_cfg* c, int32_t n_bags, const mhimx_ragged_window_bag* bags, int32_t xdt = MHIMX_X_F32) {
+  MHIMX_CHECK_ARG(xdt >= MHIMX_X_F32 && xdt <= MHIMX_X_BF16, "ragged_window: x_dtype %d is none of MHIMX_X_F32 / F16 / BF16", xdt);
   MHIMX_CHECK_ARG(c && bags, "ragged_window: null configuration / bag list");
   MHIMX_CHECK_ARG(n_bags >= 1 && n_bags <= RW_MAX, "ragged_window: 1..%d bags per window (got %d)", RW_MAX, n_bags);
   MHIMX_CHECK_ARG(!c->q_out && !c->side_stream && !c->time_project, "ragged_window: q_out / side_stream / time_project are single-step options");
@@ -252,8 +254,14 @@ int check_rw(const mhimx_step_cfg* c, int32_t n_bags, const mhimx_ragged_window_
       const std::string why = last_error();
       return fail(-1, "ragged_window: bag %d (N = %lld): %s", b, (long long)q.N, why.c_str());
     }
-    MHIMX_CHECK_ARG(q.ldx >= c->D && q.ldx % 4 == 0, "ragged_window: bag %d: row pitch below D or not a multiple of 4 floats", b);
-    MHIMX_CHECK_ARG(q.N * q.ldx * 4 < ((int64_t)1 << 32), "ragged_window: bag %d: N * ldx * 4 must stay below 2^32", b);
+    if (xdt == MHIMX_X_F32) {
+      MHIMX_CHECK_ARG(q.ldx >= c->D && q.ldx % 4 == 0, "ragged_window: bag %d: row pitch below D or not a multiple of 4 floats", b);
+      MHIMX_CHECK_ARG(q.N * q.ldx * 4 < ((int64_t)1 << 32), "ragged_window: bag %d: N * ldx * 4 must stay below 2^32", b);
+    } else {
+      MHIMX_CHECK_ARG(q.ldx >= c->D && q.ldx % 8 == 0 && q.ldx <= (1 << 20),
+                      "ragged_window: bag %d: row pitch below D, above 2^20 or not a multiple of 8 two-byte elements", b);
+      MHIMX_CHECK_ARG(q.N * q.ldx * 2 < ((int64_t)1 << 32), "ragged_window: bag %d: N * ldx * 2 must stay below 2^32", b);
+    }
     rows += slot_rows(q.N, c->k);
     MHIMX_CHECK_ARG(rows <= MHIMX_RAGGED_WINDOW_MAX_ROWS, "ragged_window: bag %d: %lld rows in the window's row space up to this bag, at most %d", b,
                     (long long)rows, MHIMX_RAGGED_WINDOW_MAX_ROWS);
@@ -359,7 +367,12 @@ extern "C" int mhimx_ragged_window_layout_of(const mhimx_step_cfg* cfg, int32_t 
 
 extern "C" int mhimx_ragged_window_run(void* stream, const mhimx_step_cfg* cfg, int32_t n_bags, const mhimx_ragged_window_bag* bags,
                                        int64_t host_step, void* ws, int64_t ws_bytes, int32_t update) {
-  if (int r = check_rw(cfg, n_bags, bags)) return r;
+  return mhimx_ragged_window_run_x(stream, cfg, n_bags, bags, host_step, ws, ws_bytes, update, MHIMX_X_F32);
+}
+
+extern "C" int mhimx_ragged_window_run_x(void* stream, const mhimx_step_cfg* cfg, int32_t n_bags, const mhimx_ragged_window_bag* bags,
+                                         int64_t host_step, void* ws, int64_t ws_bytes, int32_t update, int32_t x_dtype) {
+  if (int r = check_rw(cfg, n_bags, bags, x_dtype)) return r;
   for (int b = 0; b < n_bags; ++b) {
     MHIMX_CHECK_ARG(bags[b].X && aligned16(bags[b].X), "ragged_window: bag %d: null or unaligned rows", b);
     MHIMX_CHECK_ARG(bags[b].label_dev, "ragged_window: bag %d: null label", b);
@@ -370,6 +383,7 @@ extern "C" int mhimx_ragged_window_run(void* stream, const mhimx_step_cfg* cfg, 
   InferTab tab = {};
   RwCnt cn = {};
   rw_layout(cfg, n_bags, bags, &w, &tab, &cn, nullptr);
+  tab.pad = x_dtype;                           // read by the launches that read X: both projections and d W1
   MHIMX_CHECK_ARG(ws && (reinterpret_cast<uintptr_t>(ws) & 255) == 0, "ragged_window: the workspace must be 256-byte aligned");
   MHIMX_CHECK_ARG(ws_bytes >= w.total, "ragged_window: workspace too small (%lld bytes, need %lld)", (long long)ws_bytes, (long long)w.total);
   const mhimx_step_cfg& c = *cfg;

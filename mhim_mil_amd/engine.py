@@ -546,22 +546,27 @@ class FusedTrainer:
                     and pitch % 4 == 0 and N * pitch * 4 < (1 << 32) and ptr % 16 == 0)
 
     @staticmethod
-    def pure_window_shapes_ok(bags, D, E=512, A=128, C=2, max_rows=262144, row_cap=524288, max_bags=32):
-        """csrc/pure_window.hip check_pw and mhimx_pure_window_run's own argument checks, mirrored and tensor-free: a window the call would
-        refuse takes the bag-after-bag route instead of raising.  ``bags``: one (N, D, pitch, inner, ptr) per bag - shape, strides in floats,
-        address; ``D``: the model's input width."""
+    def pure_window_shapes_ok(bags, D, E=512, A=128, C=2, max_rows=262144, row_cap=524288, max_bags=32, elem=4):
+        """csrc/pure_window.hip check_pw and mhimx_pure_window_run_x's own argument checks, mirrored and tensor-free: a window the call would
+        refuse takes the bag-after-bag route instead of raising.  ``bags``: one (N, D, pitch, inner, ptr) per bag - shape, strides in
+        elements, address; ``D``: the model's input width; ``elem``: bytes of an element of the bags' rows (4: fp32; 2: fp16 / bf16, whose
+        pitch is a multiple of 8 elements and at most 2^20)."""
+        if elem not in (2, 4):
+            return False
+        unit = 16 // elem
         if not (E == 512 and A == 128 and 1 <= C <= 4 and D > 0 and D % 256 == 0 and D <= (1 << 20) and 1 <= len(bags) <= max_bags):
             return False
         rows = 0
         for N, Db, pitch, inner, ptr in bags:
-            if not (Db == D and 1 <= N <= max_rows and inner == 1 and pitch >= D and pitch % 4 == 0 and N * pitch * 4 < (1 << 32)
-                    and ptr != 0 and ptr % 16 == 0):
+            if not (Db == D and 1 <= N <= max_rows and inner == 1 and pitch >= D and pitch % unit == 0 and N * pitch * elem < (1 << 32)
+                    and (elem == 4 or pitch <= (1 << 20)) and ptr != 0 and ptr % 16 == 0):
                 return False
             rows += (N + 31) // 32 * 32
         return rows <= row_cap
 
     def _pure_window_ok(self, xs, labels):
-        """True when mhimx_pure_window_run takes this window.  Decided before any seed is drawn or counter touched."""
+        """True when mhimx_pure_window_run_x takes this window (fp32 bags, or fp16 / bf16 bags of ONE dtype).  Decided before any seed is drawn
+        or counter touched."""
         s = self.s
         if ops.KERNEL_EVENT_HOOK is not None or not xs:
             return False
@@ -569,15 +574,15 @@ class FusedTrainer:
                 and s.baseline == "attn" and not s.online_encoder.gated and s._op_prec != "f32" and len(labels) == len(xs)):
             return False
         dev = xs[0].device
-        if not all(torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.device == dev
-                   and s._feature_prec(x.shape[0]) == "bf16x3" for x in xs):
+        if not all(torch.is_tensor(x) and x.is_cuda and x.dtype == xs[0].dtype and x.dim() == 2 and x.device == dev
+                   and s._feature_prec(x.shape[0]) == "bf16x3" for x in xs) or xs[0].dtype not in ops._X_DTYPES:
             return False
         if not all(torch.is_tensor(l) and l.is_cuda and l.dtype == torch.int64 and l.numel() == 1 and l.device == dev for l in labels):
             return False
         return self.pure_window_shapes_ok([(x.shape[0], x.shape[1], x.stride(0), x.stride(1), x.data_ptr()) for x in xs], s.input_dim,
                                           E=s.mlp_dim, A=s.online_encoder.attention.attention[0].weight.shape[0], C=s.n_classes,
                                           max_rows=self.exec_max_rows, row_cap=min(self.pure_window_row_cap, mh.L.PURE_WINDOW_MAX_ROWS),
-                                          max_bags=mh.L.PURE_WINDOW_MAX)
+                                          max_bags=mh.L.PURE_WINDOW_MAX, elem=xs[0].element_size())
 
     def _exec_pure_window(self, xs, labels, update):
         """One accumulation window of the teacher-free model - 1 .. accumulation_steps bags of any row counts, every loss scaled by
@@ -599,7 +604,7 @@ class FusedTrainer:
         for j in range(n):                                          # ONE seed per bag, in bag order: the feature dropout's
             table[j].drop_seed = s._next_seed()
         inside = bool(update and not self.clip_grad)                # (clipping needs the norm of the final gradient: the update stays outside)
-        ops.pure_window_run(ex["cfg"], table, n, fl.step + int(inside), ws, inside)
+        ops.pure_window_run(ex["cfg"], table, n, fl.step + int(inside), ws, inside, x_dtype=ops.x_dtype_of(xs))
         E, Cc = s.mlp_dim, s.n_classes
 
         def view(off, cnt_, dtype=torch.float32):
@@ -616,7 +621,7 @@ class FusedTrainer:
         logits, losses = [p["logits"] for p in per], [p["losses"] for p in per]
         self.last = {"logits": logits, "losses": losses, "patch_num": per[-1]["patch_num"], "keep_num": per[-1]["keep_num"], "rows": None,
                      "score": None, "R": 0, "tokens": None, "H_student": per[-1]["H_student"], "H_teacher": None, "bags": per, "layout": lay,
-                     "ws": ws, "exec": True}
+                     "ws": ws, "exec": True, "x_dtype": xs[0].dtype}
         self._micro = n
         if inside:
             fl.step += 1
@@ -626,12 +631,26 @@ class FusedTrainer:
             self.update()
         return logits, losses
 
+    @staticmethod
+    def _half_bags(bags):
+        """The window's bags as contiguous [N, D] matrices in THEIR dtype when all of them are fp16, or all bf16, device tensors (what
+        mhimx_pure_window_run_x / mhimx_ragged_window_run_x read where it lies); None for every other window."""
+        if not bags or not all(torch.is_tensor(b) and b.is_cuda and b.dtype == bags[0].dtype for b in bags) \
+                or bags[0].dtype not in (torch.float16, torch.bfloat16):
+            return None
+        xs = [b[0] if b.dim() == 3 and b.shape[0] == 1 else b for b in bags]
+        return [x.contiguous() for x in xs] if all(x.dim() == 2 for x in xs) else None
+
     def _pure_window_step(self, bags, labels, i, perms, shuffles, update):
         """window_step of a 'mhim_pure' trainer with accumulation_steps > 1: the native ragged window when it takes the bags (a SHORTER last
         window too: 1 <= len(bags) <= accumulation_steps, scaled by 1 / len(bags) - base_engine.py:30,50-51,102), else today's bag-after-bag
         route, which scales by 1 / accumulation_steps and so needs exactly that many bags."""
         k = len(bags)
         assert 1 <= k <= self.accum and len(labels) == k, "window_step takes at most accumulation_steps bags"
+        # (a window of fp16 / bf16 bags goes into the native call as it is; every other route reads fp32 rows: widened as always)
+        xs = self._half_bags(bags) if perms is None and shuffles is None else None
+        if xs is not None and self._pure_window_ok(xs, labels):
+            return self._exec_pure_window(xs, labels, update)
         xs = [self.s._check_x(b) for b in bags]
         if perms is None and shuffles is None and self._pure_window_ok(xs, labels):
             return self._exec_pure_window(xs, labels, update)
@@ -784,11 +803,15 @@ class FusedTrainer:
 
     # ------------------------------------------------------------------------------------------------- the ragged window behind the C-ABI
     @staticmethod
-    def ragged_window_shapes_ok(bags, D, k, E=512, A=128, C=2, max_rows=262144, row_cap=524288, max_bags=32):
-        """csrc/ragged_window.hip check_rw (csrc/step.hip check_cfg per bag) and mhimx_ragged_window_run's own argument checks, mirrored and
+    def ragged_window_shapes_ok(bags, D, k, E=512, A=128, C=2, max_rows=262144, row_cap=524288, max_bags=32, elem=4):
+        """csrc/ragged_window.hip check_rw (csrc/step.hip check_cfg per bag) and mhimx_ragged_window_run_x's own argument checks, mirrored and
         tensor-free: a window the call would refuse takes today's route instead of raising.  ``bags``: one (N, D, pitch, inner, ptr,
-        (k_top, n_sel, len_keep, Lk, R)) per bag - shape, strides in floats, address, its counts; ``D``: the model's input width; ``k``:
-        merge_k."""
+        (k_top, n_sel, len_keep, Lk, R)) per bag - shape, strides in elements, address, its counts; ``D``: the model's input width; ``k``:
+        merge_k; ``elem``: bytes of an element of the bags' rows (4: fp32; 2: fp16 / bf16, whose pitch is a multiple of 8 elements and at
+        most 2^20)."""
+        if elem not in (2, 4):
+            return False
+        unit = 16 // elem
         if not (E == 512 and A == 128 and 1 <= C <= 4 and k >= 1 and 8 * k <= 48 and D > 0 and D % 256 == 0 and D <= (1 << 20)
                 and 1 <= len(bags) <= max_bags):
             return False
@@ -798,7 +821,8 @@ class FusedTrainer:
             if not (Db == D and 64 <= N <= max_rows and 1 <= k_top <= (4096 if N <= 16384 else 16384) and 1 <= n_sel <= k_top
                     and len_keep == N - n_sel and Lk >= 1 and 1 <= R <= 32768 and Lk + R == len_keep):
                 return False
-            if not (inner == 1 and pitch >= D and pitch % 4 == 0 and N * pitch * 4 < (1 << 32) and ptr != 0 and ptr % 16 == 0):
+            if not (inner == 1 and pitch >= D and pitch % unit == 0 and N * pitch * elem < (1 << 32) and (elem == 4 or pitch <= (1 << 20))
+                    and ptr != 0 and ptr % 16 == 0):
                 return False
             rows += (N + k + 31) // 32 * 32
         return rows <= row_cap
@@ -814,7 +838,8 @@ class FusedTrainer:
                 and s.baseline == "attn" and s.mrh_sche is None and s._op_prec != "f32" and s.merge_enable and s.merge.k <= 6):
             return False
         dev = xs[0].device
-        if not all(torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.device == dev for x in xs):
+        if not all(torch.is_tensor(x) and x.is_cuda and x.dtype == xs[0].dtype and x.dim() == 2 and x.device == dev for x in xs) \
+                or xs[0].dtype not in ops._X_DTYPES:
             return False
         if not all(torch.is_tensor(l) and l.is_cuda and l.dtype == torch.int64 and l.numel() == 1 and l.device == dev for l in labels):
             return False
@@ -823,7 +848,7 @@ class FusedTrainer:
         return self.ragged_window_shapes_ok(
             [(x.shape[0], x.shape[1], x.stride(0), x.stride(1), x.data_ptr(), s.v2_counts(x.shape[0], i)) for x in xs], s.input_dim, s.merge.k,
             E=s.mlp_dim, A=s.online_encoder.attention.attention[0].weight.shape[0], C=s.n_classes, max_rows=self.exec_max_rows,
-            row_cap=min(self.ragged_window_row_cap, mh.L.RAGGED_WINDOW_MAX_ROWS), max_bags=mh.L.RAGGED_WINDOW_MAX)
+            row_cap=min(self.ragged_window_row_cap, mh.L.RAGGED_WINDOW_MAX_ROWS), max_bags=mh.L.RAGGED_WINDOW_MAX, elem=xs[0].element_size())
 
     def _exec_ragged_window(self, xs, labels, i, update):
         """One accumulation window of different-sized bags - 1 .. accumulation_steps of them, every loss scaled by 1 / len(bags) - as ONE
@@ -851,7 +876,7 @@ class FusedTrainer:
             table[j].seeds = L.StepSeeds(drop_teacher=t._next_seed(teacher=True), drop_student=s._next_seed(), select=s._next_seed(),
                                          mca=s._next_seed())
         inside = bool(update and not self.clip_grad)              # (clipping needs the norm of the final gradient: the update stays outside)
-        ops.ragged_window(ex["cfg"], table, n, fl.step + int(inside), ws, inside)
+        ops.ragged_window(ex["cfg"], table, n, fl.step + int(inside), ws, inside, x_dtype=ops.x_dtype_of(xs))
         km, E, Cc = s.merge.k, s.mlp_dim, s.n_classes
 
         def view(off, cnt_, dtype=torch.float32):
@@ -869,7 +894,8 @@ class FusedTrainer:
                         "score": score[r0:r0 + N], "R": cnt.R, "tokens": Hs[r0 + N:r0 + N + km], "H_student": Hs[r0:r0 + N],
                         "H_teacher": Ht[r0:r0 + N], "dact": dact[r0:r0 + N], "z_teacher": zt[j], "z_student": zs[j], "row0": r0})
         logits, losses = [p_["logits"] for p_ in per], [p_["losses"] for p_ in per]
-        self.last = dict(per[-1], logits=logits, losses=losses, bags=per, layout=lay, table=table, ws=ws, exec="mhimx_ragged_window_run")
+        self.last = dict(per[-1], logits=logits, losses=losses, bags=per, layout=lay, table=table, ws=ws, exec="mhimx_ragged_window_run",
+                         x_dtype=xs[0].dtype)
         self._micro = n
         if inside:
             fl.step += 1
@@ -1222,6 +1248,10 @@ class FusedTrainer:
         k = len(bags)
         if self.model_kind == "mhim_pure" and self.accum > 1:
             return self._pure_window_step(bags, labels, i, perms, shuffles, update)
+        # (a window of fp16 / bf16 bags goes into mhimx_ragged_window_run_x as it is; every other route reads fp32 rows: widened as always)
+        xs = self._half_bags(bags) if perms is None and shuffles is None else None
+        if xs is not None and not (k == self.accum and all(x.shape == xs[0].shape for x in xs)) and self._ragged_window_ok(xs, labels, i):
+            return self._exec_ragged_window(xs, labels, i, update)
         xs = [self.s._check_x(b) for b in bags]
         # bags of different sizes (or a same-shaped window mhimx_window_run does not take), a shorter last window too: ONE call of
         # mhimx_ragged_window_run, every loss scaled by 1 / len(bags) (base_engine.py:30,50-51,102)

@@ -11,7 +11,10 @@ time (0.73 ms from pinned memory), so the MI355X-first feeder has two modes:
   double buffer while the current step computes (events in both directions: compute waits for its bag, the copy waits until
   the buffer's previous step has finished).
 
-Sources are tensors / arrays already in memory or paths of ``torch.save``d feature matrices ([N, D] float).
+Sources are tensors / arrays already in memory or paths of ``torch.save``d feature matrices ([N, D] float).  ``dtype``: what the bags
+are delivered as - fp32 by default; ``dtype=None`` keeps what each source holds where that is fp16, bf16 or fp32 (anything else becomes
+fp32): feature files written under autocast then take half the HBM (resident) and half the PCIe time (streaming), and the ragged native
+calls (mhimx_infer_run_x, mhimx_pure_window_run_x, mhimx_ragged_window_run_x) read them as they are.
 
 ``BagLoader`` is the same feeder behind the reference's LOADER seam: it yields the batch dictionaries the reference's train /
 validate loops unpack (datasets/dataset_feat.py:93-111 through a batch_size-1 DataLoader and datasets/data_utils.PrefetchLoader,
@@ -25,7 +28,10 @@ from typing import Iterable, Sequence
 import torch
 
 
-def _load(src):
+_KEPT = (torch.float16, torch.bfloat16, torch.float32)
+
+
+def _load(src, dtype=torch.float32):
     if isinstance(src, (str, bytes)) or hasattr(src, "__fspath__"):
         try:
             t = torch.load(src, weights_only=True)              # dataset_feat.py:86-89
@@ -38,20 +44,23 @@ def _load(src):
         t = t[0]
     if t.dim() != 2:
         raise ValueError(f"a bag is a [N, D] feature matrix, got shape {tuple(t.shape)}")
-    return t.float().contiguous()
+    if dtype is None:
+        dtype = t.dtype if t.dtype in _KEPT else torch.float32
+    return t.to(dtype).contiguous()
 
 
 class BagFeeder:
     """Iterates (bag [N,D] on the device, label [1] int64 on the device, index) over ``order`` (default: all bags in turn)."""
 
-    def __init__(self, bags: Sequence, labels: Sequence[int], device="cuda", resident=True, order: Iterable[int] | None = None):
+    def __init__(self, bags: Sequence, labels: Sequence[int], device="cuda", resident=True, order: Iterable[int] | None = None,
+                 dtype=torch.float32):
         if len(bags) != len(labels):
             raise ValueError("one label per bag")
         self.device = torch.device(device)
         self.resident = bool(resident)
         self.labels = [torch.tensor([int(l)], device=self.device) for l in labels]
         self.order = list(range(len(bags))) if order is None else list(order)
-        host = [_load(b) for b in bags]
+        host = [_load(b, dtype) for b in bags]
         if self.resident:
             self.dev = [h.to(self.device) for h in host]           # one copy, then the bags never move again
             self.host = None
@@ -60,7 +69,9 @@ class BagFeeder:
             rows, width = max(h.shape[0] for h in host), host[0].shape[1]
             if any(h.shape[1] != width for h in host):
                 raise ValueError("all bags must share the feature width D")
-            self._buf = [torch.empty((rows, width), device=self.device) for _ in range(2)]
+            if any(h.dtype != host[0].dtype for h in host):
+                raise ValueError("streaming bags share ONE double buffer: all bags must have the same dtype (pass dtype=...)")
+            self._buf = [torch.empty((rows, width), dtype=host[0].dtype, device=self.device) for _ in range(2)]
             self._copy = torch.cuda.Stream(device=self.device)
             self._landed = [torch.cuda.Event() for _ in range(2)]
             self._released = [torch.cuda.Event() for _ in range(2)]
@@ -104,8 +115,8 @@ class BagLoader:
     """The reference's loader contract over a BagFeeder (PrefetchLoader stand-in: batches arrive on the device)."""
 
     def __init__(self, bags: Sequence, labels: Sequence[int], device="cuda", resident=True, order: Iterable[int] | None = None,
-                 names: Sequence[str] | None = None, return_id=False):
-        self.feeder = BagFeeder(bags, labels, device=device, resident=resident, order=order)
+                 names: Sequence[str] | None = None, return_id=False, dtype=torch.float32):
+        self.feeder = BagFeeder(bags, labels, device=device, resident=resident, order=order, dtype=dtype)
         self.names = list(names) if names is not None else [str(i) for i in range(len(bags))]
         self.return_id = bool(return_id)
         self.device = self.feeder.device

@@ -930,7 +930,9 @@ class MHIM(nn.Module):
                                # (a bag longer than the cap goes alone and the workspace grows to it).  Larger chunks are faster, not slower:
                                # tools/exp_infer.py --row-cap, 64 bags / 386 276 rows: 65 536 -> 2.46 ms, 131 072 -> 2.14, uncapped -> 2.03
 
-    def _infer_bags(self, xs):
+    def _infer_bags(self, xs, keep_half=False):
+        """The list entries as [N, D] matrices with unit column stride; fp32 unless ``keep_half``: then fp16 / bf16 bags stay what they are
+        (mhimx_infer_run_x reads them where they lie)."""
         out = []
         for x in xs:
             if not x.is_cuda:
@@ -939,7 +941,7 @@ class MHIM(nn.Module):
                 if x.shape[0] != 1:
                     raise L.MhimxError("MHIM.infer_many: every list entry is ONE bag ([N, D] or [1, N, D])")
                 x = x[0]
-            if x.dtype != torch.float32:
+            if x.dtype != torch.float32 and not (keep_half and x.dtype in (torch.float16, torch.bfloat16)):
                 x = x.float()
             if x.stride(1) != 1:
                 x = x.contiguous()
@@ -947,8 +949,9 @@ class MHIM(nn.Module):
         return out
 
     def _infer_ok(self, xs):
-        """True when mhimx_infer_run takes these bags (csrc/infer.hip: check_infer and the call's own argument checks, mirrored: what they
-        would refuse takes the forward_test loop instead of raising)."""
+        """True when mhimx_infer_run_x takes these bags (csrc/infer.hip: check_infer and the call's own argument checks, mirrored: what they
+        would refuse takes the forward_test loop instead of raising).  One dtype per call - fp32, fp16 or bf16; the row pitch of a 2-byte
+        bag is a multiple of 8 elements (16-byte rows)."""
         if (self.training or self.baseline != "attn" or self.online_encoder.gated or self.merge_test or self._op_prec == "f32"
                 or ops.KERNEL_EVENT_HOOK is not None):
             return False
@@ -960,8 +963,12 @@ class MHIM(nn.Module):
         ps = (self.feature[0].weight, self.feature[0].bias, att[0].weight, att[2].weight, self.predictor.weight, self.predictor.bias)
         if any(not t.is_contiguous() or t.dtype != torch.float32 or t.device != dev for t in ps) or any(t.data_ptr() % 16 for t in ps[:3]):
             return False
+        kinds = {x.dtype for x in xs}
+        if len(kinds) != 1 or not kinds <= {torch.float32, torch.float16, torch.bfloat16}:
+            return False
+        unit = 16 // xs[0].element_size()                       # elements of a 16-byte unit: the pitch rule of check_infer
         return all(x.dim() == 2 and x.shape[1] == self.input_dim and 1 <= x.shape[0] <= L.INFER_MAX_ROWS and x.device == dev
-                   and x.data_ptr() % 16 == 0 and x.stride(0) % 4 == 0 and self.input_dim <= x.stride(0) <= (1 << 20) for x in xs)
+                   and x.data_ptr() % 16 == 0 and x.stride(0) % unit == 0 and self.input_dim <= x.stride(0) <= (1 << 20) for x in xs)
 
     def _infer_cfg(self):
         att = self.online_encoder.attention.attention
@@ -988,9 +995,13 @@ class MHIM(nn.Module):
         """forward_test over a LIST of bags of different row counts -> logits [n, C]; with ``return_attn`` also the list of per-bag
         attention vectors [N_b] (raw scorer outputs with ``no_norm``), with ``labels`` (int64 [n], device) also the per-bag cross
         entropy [n]: ``logits`` | ``(logits, attn)`` | ``(logits, loss)`` | ``(logits, attn, loss)``.
-        An eval-mode plain-ABMIL model without merge_test takes mhimx_infer_run - one C call (four launches) per chunk of bags, see
-        ``infer_chunks``; anything else loops over forward_test.  ``self.last["infer_native"]`` says which route ran."""
-        xs = self._infer_bags(xs)
+        An eval-mode plain-ABMIL model without merge_test takes mhimx_infer_run_x - one C call (four launches) per chunk of bags, see
+        ``infer_chunks``; anything else loops over forward_test.  ``self.last["infer_native"]`` says which route ran.
+        A list of fp16 bags, or of bf16 bags, that the native route takes goes in as it is (no widened copy; same bits as on the widened
+        bags); a list of mixed dtypes, and every model outside the native route, gets ``x.float()`` first."""
+        xs = self._infer_bags(xs, keep_half=True)
+        if any(x.dtype != torch.float32 for x in xs) and not self._infer_ok(xs):
+            xs = [x.float() for x in xs]
         n = len(xs)
         if labels is not None:
             labels = labels.reshape(-1).to(device=xs[0].device, dtype=torch.int64) if n else labels

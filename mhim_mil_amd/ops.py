@@ -961,15 +961,36 @@ def infer_ws_bytes(cfg, xs):
     return L.lib().mhimx_infer_ws_bytes(C.byref(cfg), len(xs), bags)
 
 
+_X_DTYPES = {torch.float32: L.X_F32, torch.float16: L.X_F16, torch.bfloat16: L.X_BF16}
+
+
+def x_dtype_of(xs, who="bags"):
+    """MHIMX_X_* of a list of bags for the *_run_x calls: fp32, fp16 or bf16, ONE dtype per call (anything else, or a mixed list: MhimxError)."""
+    kinds = {x.dtype for x in xs}
+    if len(kinds) > 1:
+        raise L.MhimxError(f"{who}: bags of mixed dtypes ({', '.join(sorted(str(k) for k in kinds))}): one element type per call")
+    for k in kinds:
+        if k not in _X_DTYPES:
+            raise L.MhimxError(f"{who}: bags must be fp32, fp16 or bf16 (got {k})")
+        return _X_DTYPES[k]
+    return L.X_F32
+
+
+def _x_name(name, x_dtype):
+    return name if x_dtype == L.X_F32 else name + "_x"
+
+
 def infer_many(cfg, xs, labels=None, want_attn=False, want_score=False, want_z=False, ws=None):
-    """The eval-mode MHIM(ABMIL) forward of up to L.INFER_MAX bags of different row counts in ONE C call (mhimx_infer_run).
-    cfg: L.InferCfg (its parameter tensors are kept alive by the caller); xs: [N_b, D] fp32 GPU tensors with unit column stride;
+    """The eval-mode MHIM(ABMIL) forward of up to L.INFER_MAX bags of different row counts in ONE C call (mhimx_infer_run_x).
+    cfg: L.InferCfg (its parameter tensors are kept alive by the caller); xs: [N_b, D] GPU tensors with unit column stride, all fp32, all
+    fp16 or all bf16 (half bags are read where they lie: same bits as the call on their ``.float()``);
     labels: int64 [n] on the device (then the per-bag cross entropy comes back too).  ``ws``: a uint8 workspace of the caller's
     (tests poison it); default: one cached per device, grown on demand (inside a stream capture: a fresh one, owned by the graph's pool)."""
     n = len(xs)
+    xdt = x_dtype_of(xs, "infer_many")
     for x in xs:
-        if not (torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.stride(1) == 1):
-            raise L.MhimxError("infer_many: every bag must be a GPU fp32 matrix [N, D] with unit column stride")
+        if not (torch.is_tensor(x) and x.is_cuda and x.dim() == 2 and x.stride(1) == 1):
+            raise L.MhimxError("infer_many: every bag must be a GPU fp32 / fp16 / bf16 matrix [N, D] with unit column stride")
     _chk(labels, torch.int64, "labels")
     if labels is not None and labels.numel() != n:
         raise L.MhimxError(f"infer_many: {labels.numel()} labels for {n} bags")
@@ -998,15 +1019,18 @@ def infer_many(cfg, xs, labels=None, want_attn=False, want_score=False, want_z=F
     r.attn = torch.empty(rows, device=dev) if want_attn else None
     r.loss = torch.empty(n, device=dev) if labels is not None else None
     out = L.InferOut(logits=_p(r.logits), z=_p(r.z), stats=_p(r.stats), score=_p(r.score), attn=_p(r.attn), loss=_p(r.loss))
-    L.check(L.lib().mhimx_infer_run(_stream(), C.byref(cfg), n, bags, _p(labels), C.byref(out), _p(ws), ws.numel()), "mhimx_infer_run")
+    L.check(L.lib().mhimx_infer_run_x(_stream(), C.byref(cfg), n, bags, _p(labels), C.byref(out), _p(ws), ws.numel(), xdt),
+            _x_name("mhimx_infer_run", xdt))
     return r
 
 
 # ------------------------------------------------------------------------------------------- ragged pure accumulation window
 def pure_window_bags(xs, labels, seeds):
-    """The by-value bag table of mhimx_pure_window_run: xs [N_b, D] fp32 GPU matrices with unit column stride, labels int64 [1] device
-    tensors, seeds the bags' dropout seeds."""
+    """The by-value bag table of mhimx_pure_window_run(_x): xs [N_b, D] GPU matrices with unit column stride - all fp32, all fp16 or all
+    bf16 (a mixed list: MhimxError; pass ``x_dtype_of(xs)`` to pure_window_run) -, labels int64 [1] device tensors, seeds the bags' dropout
+    seeds."""
     n = len(xs)
+    x_dtype_of(xs, "pure_window_bags")
     return (L.PureWindowBag * max(n, 1))(*[L.PureWindowBag(X=x.data_ptr(), ldx=x.stride(0), N=x.shape[0], label_dev=l.data_ptr(), drop_seed=int(sd))
                                            for x, l, sd in zip(xs, labels, seeds)])
 
@@ -1018,22 +1042,23 @@ def pure_window_layout(cfg, bags, n):
     return lay
 
 
-def pure_window_run(cfg, bags, n, host_step, ws, update):
-    """ONE optimiser update (update = False: the summed gradient only) over the n bags of the table as one C call."""
-    L.check(L.lib().mhimx_pure_window_run(_stream(), C.byref(cfg), n, bags, int(host_step), ws.data_ptr(), ws.numel(), int(bool(update))),
-            "mhimx_pure_window_run")
+def pure_window_run(cfg, bags, n, host_step, ws, update, x_dtype=L.X_F32):
+    """ONE optimiser update (update = False: the summed gradient only) over the n bags of the table as one C call.  ``x_dtype``: what the
+    table's rows are (``x_dtype_of`` of the tensors it was made from)."""
+    L.check(L.lib().mhimx_pure_window_run_x(_stream(), C.byref(cfg), n, bags, int(host_step), ws.data_ptr(), ws.numel(), int(bool(update)),
+                                            int(x_dtype)), _x_name("mhimx_pure_window_run", x_dtype))
 
 
 # ------------------------------------------------------------------------------------------- ragged MHIM accumulation window
-def ragged_window(cfg, bags, n, host_step=0, ws=None, update=False, layout_only=False):
+def ragged_window(cfg, bags, n, host_step=0, ws=None, update=False, layout_only=False, x_dtype=L.X_F32):
     """mhimx_ragged_window_layout_of (host arithmetic only) and, unless ``layout_only``, mhimx_ragged_window_run: ONE optimiser update
     (update = False: the summed gradient only) of the full MHIM(ABMIL) model over the n bags of the by-value table ``bags``
-    (_lib.RaggedWindowBag * n: rows, pitch, N, label, this bag's counts and seeds) as one C call.  Returns the layout."""
+    (_lib.RaggedWindowBag * n: rows, pitch, N, label, this bag's counts and seeds) as one C call.  ``x_dtype``: what the table's rows are (``x_dtype_of`` of the tensors it was made from).  Returns the layout."""
     lay = L.RaggedWindowLayout()
     L.check(L.lib().mhimx_ragged_window_layout_of(C.byref(cfg), n, bags, C.byref(lay)), "mhimx_ragged_window_layout_of")
     if not layout_only:
-        L.check(L.lib().mhimx_ragged_window_run(_stream(), C.byref(cfg), n, bags, int(host_step), ws.data_ptr(), ws.numel(), int(bool(update))),
-                "mhimx_ragged_window_run")
+        L.check(L.lib().mhimx_ragged_window_run_x(_stream(), C.byref(cfg), n, bags, int(host_step), ws.data_ptr(), ws.numel(), int(bool(update)),
+                                                  int(x_dtype)), _x_name("mhimx_ragged_window_run", x_dtype))
     return lay
 
 
