@@ -310,8 +310,9 @@ static int merge2_side_of(const mhimx_merge* m, const float* X, int64_t R, const
 }
 
 // (round 5) Park the backward's FIRST stage (parameters x dz: merge2_bwd_pre) on the step's list BEFORE the pool backward runs: the pool
-// backward's one-pass rows launch (scorer_fused_bwd_kernel) then gives it a ride behind a gate on the tile(s) that produce dz - the merged
-// tokens' gradient rows - instead of the stage being a 14 us launch of its own between the pool backward and the rows pass.
+// backward's one-pass rows launch (scorer_fused_bwd_kernel) then gives it a ride behind a gate on the block(s) that produce dz - the merged
+// tokens' gradient rows: that launch's token block - instead of the stage being a 14 us launch of its own between the pool backward and
+// the rows pass.
 int merge2_bwd_park(const mhimx_merge* m, const float* X, int64_t R, const float* dz, float* dX, const mhimx_merge_grad* gr, void* ws, int64_t ws_bytes) {
   if (!gr->defer || gr->defer->pre.pending != 0) return 0;
   Merge2Side sd;

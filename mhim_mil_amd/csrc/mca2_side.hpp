@@ -310,7 +310,8 @@ constexpr int M2_SIDE_LDS = M2_GRADS1_LDS;                   // floats: the larg
 constexpr int M2_BWD_PRE_BLOCKS = 64, M2_BWD_PRE_LDS = 6 * M2_E + 6 * 64;
 // gate (optional): the stage rides in the launch that PRODUCES dz (scorer_fused_bwd_kernel): it requests everything that does not depend on
 // dz, then waits until `gate_target` workgroups have announced their rows of dz (write-through stores + one relaxed agent-scope add each)
-// and reads dz past the caches.  A bounded spin: the riders are the launch's LAST workgroups, so the producers are resident or done.
+// and reads dz past the caches.  A bounded spin: the riders are the launch's LAST workgroups, so the producers (the token block, dispatched
+// first, and the tile blocks) are resident or done.
 constexpr unsigned M2_GATE_SPINS = 1u << 22;
 MHIMX_DEV void merge2_bwd_pre_body(int block, float* lds, const float* __restrict__ dz, const float* __restrict__ wo_t,
                                    const float* __restrict__ wkv, int k, float drop_p, uint64_t seed0, const uint64_t* __restrict__ tick,

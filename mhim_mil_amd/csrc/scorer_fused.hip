@@ -331,6 +331,167 @@ constexpr size_t SB_SMEM_IMG = SB_SMEM + (size_t)SF_ROWS * SB_DLD;
 // a's lanes 32..63 <-> b's lanes 0..31 (wgrad.hip's wg_swap: inline asm - the builtin of this compiler drops its second result)
 MHIMX_DEV void sb_swap(float& a, float& b) { asm("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(a), "+v"(b)); }
 
+// acc = du tile (Ds: [32][SB_LD] in LDS) x Wa as the 3-term bf16 product; wave w owns columns [128 w, 128 w + 128).  One body for the tile
+// blocks and the token block: a row's result does not depend on where in the 32-row tile it sits, so both give the same bits.
+MHIMX_DEV void sb_product(sf_f32x16 (&acc)[4], const float* Ds, const float* __restrict__ wat, const float* __restrict__ wat_frag, int wave, int lane) {
+  const int r32 = lane & 31, kg = lane >> 5;
+#pragma unroll
+  for (int nt = 0; nt < 4; ++nt)
+#pragma unroll
+    for (int i = 0; i < 16; ++i) acc[nt][i] = 0.f;
+  const float* aptr = Ds + r32 * SB_LD + 8 * kg;
+  if (wat_frag) {
+    const float* fptr = wat_frag + ((int64_t)(4 * wave) * (SF_A / 16) * 64 + lane) * 8;     // + (nt * 8 + ks) * 512 floats
+    sf_f4 bh_[4], bl_[4];
+#pragma unroll
+    for (int nt = 0; nt < 4; ++nt) {
+      bh_[nt] = *reinterpret_cast<const sf_f4*>(fptr + (nt * 8) * 512);
+      bl_[nt] = *reinterpret_cast<const sf_f4*>(fptr + (nt * 8) * 512 + 4);
+    }
+#pragma unroll 1
+    for (int ks = 0; ks < SF_A / 16; ++ks) {
+      const sf_f4 a0 = *reinterpret_cast<const sf_f4*>(aptr + 16 * ks), a1 = *reinterpret_cast<const sf_f4*>(aptr + 16 * ks + 4);
+      sf_b8 ah, al;
+      sf_split(a0, a1, ah, al);
+      sf_f4 nh[4], nl[4];
+      const int kn = ks + 1 < SF_A / 16 ? ks + 1 : ks;
+#pragma unroll
+      for (int nt = 0; nt < 4; ++nt) {
+        nh[nt] = *reinterpret_cast<const sf_f4*>(fptr + (nt * 8 + kn) * 512);
+        nl[nt] = *reinterpret_cast<const sf_f4*>(fptr + (nt * 8 + kn) * 512 + 4);
+      }
+      // term-major: the three MFMAs into acc[nt] are three others apart (no dependent back-to-back issue)
+#pragma unroll
+      for (int nt = 0; nt < 4; ++nt) acc[nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, __builtin_bit_cast(sf_b8, bh_[nt]), acc[nt], 0, 0, 0);
+#pragma unroll
+      for (int nt = 0; nt < 4; ++nt) acc[nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, __builtin_bit_cast(sf_b8, bl_[nt]), acc[nt], 0, 0, 0);
+#pragma unroll
+      for (int nt = 0; nt < 4; ++nt) acc[nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, __builtin_bit_cast(sf_b8, bh_[nt]), acc[nt], 0, 0, 0);
+#pragma unroll
+      for (int nt = 0; nt < 4; ++nt) {
+        bh_[nt] = nh[nt];
+        bl_[nt] = nl[nt];
+      }
+    }
+  } else {
+#pragma unroll 1
+    for (int ks = 0; ks < SF_A / 16; ++ks) {
+      const sf_f4 a0 = *reinterpret_cast<const sf_f4*>(aptr + 16 * ks), a1 = *reinterpret_cast<const sf_f4*>(aptr + 16 * ks + 4);
+      sf_b8 ah, al;
+      sf_split(a0, a1, ah, al);
+#pragma unroll
+      for (int nt = 0; nt < 4; ++nt) {
+        const float* bp = wat + (int64_t)(128 * wave + 32 * nt + r32) * SF_A + 16 * ks + 8 * kg;
+        sf_b8 bh, bl;
+        sf_split(*reinterpret_cast<const sf_f4*>(bp), *reinterpret_cast<const sf_f4*>(bp + 4), bh, bl);
+        acc[nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, acc[nt], 0, 0, 0);
+        acc[nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, acc[nt], 0, 0, 0);
+        acc[nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, acc[nt], 0, 0, 0);
+      }
+    }
+  }
+}
+
+// The token block of a gated launch (block 0): the riders' dz - the gate rows (destination row >= gate_row0) among the list's last 32
+// positions, today the k merged tokens at its end - and nothing else.  It runs the tile's arithmetic for those rows over the virtual tile
+// [max(0, M - 32), M) (same lane layout of the row dots, same du, same product), stores them past the caches and announces them ONCE.  It
+// takes no d out / d pre rows and writes no image, no du and no partial: those stay with the tile blocks, whose sums keep their bits.
+// With it the riders' wait ends after one short block dispatched FIRST instead of behind the whole chain of the tile dispatched LAST.
+MHIMX_DEV void sb_token_block(float* sb_sm, const float* __restrict__ T, int64_t M, const float* __restrict__ u_pre,
+                              const float* __restrict__ s_in, float c0, float mx, float invL, float wca, int act,
+                              const float* __restrict__ wat, const float* __restrict__ wat_frag, float* __restrict__ dT,
+                              const int64_t* __restrict__ rows, int64_t gate_row0, unsigned* gate) {
+  float* Ds = sb_sm;                           // (the tile's carve-up: sb_sm + ... in the kernel below)
+  float* gzs = Ds + SF_ROWS * SB_LD;
+  float* an_s = gzs + SF_E;
+  float* gs_s = an_s + SF_ROWS;
+  int64_t* ridx = reinterpret_cast<int64_t*>(gs_s + 2 * SF_ROWS + 2 * SF_A + 8);
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int r32 = lane & 31, kg = lane >> 5;
+  const int a_col = tid & (SF_A - 1), half = tid >> 7;
+  const int64_t row0 = M > SF_ROWS ? M - SF_ROWS : 0;
+  // destination row of each position, -1: not this block's (in front of the gate, or past the list)
+  if (tid < SF_ROWS) {
+    const int64_t n = row0 + tid;
+    const int64_t dr = n < M ? (rows ? rows[n] : n) : -1;
+    ridx[tid] = dr >= gate_row0 ? dr : -1;
+  }
+  __syncthreads();
+  // ---- 1. row dots (8 lanes per row, as the tile); the score and the pre-activations are requested with the row
+  float up[SF_ROWS / 2];
+  {
+    const int r = tid >> 3, seg = tid & 7;
+    const int64_t dr = ridx[r];
+    const sf_f4* gr = reinterpret_cast<const sf_f4*>(gzs) + seg;
+    sf_f4 tv[16];
+    float sn = 0.f;
+    if (dr >= 0) {
+      const sf_f4* tr = reinterpret_cast<const sf_f4*>(T + dr * SF_E) + seg;
+#pragma unroll
+      for (int q = 0; q < 16; ++q) tv[q] = tr[8 * q];
+      sn = s_in[row0 + r];
+    } else {
+#pragma unroll
+      for (int q = 0; q < 16; ++q) tv[q] = sf_f4{0.f, 0.f, 0.f, 0.f};
+    }
+#pragma unroll
+    for (int k = 0; k < SF_ROWS / 2; ++k) {
+      const int rr = half + 2 * k;
+      up[k] = ridx[rr] >= 0 ? u_pre[(row0 + rr) * SF_A + a_col] : 0.f;
+    }
+    float d = 0.f;
+#pragma unroll
+    for (int q = 0; q < 16; ++q) {
+      const sf_f4 g = gr[8 * q];
+      d += tv[q][0] * g[0] + tv[q][1] * g[1] + tv[q][2] * g[2] + tv[q][3] * g[3];
+    }
+    d += dpp_mov<0xB1, 0xf>(0.f, d);
+    d += dpp_mov<0x4E, 0xf>(0.f, d);
+    d += dpp_mov<0x141, 0xf>(0.f, d);
+    if (seg == 0) {
+      const float an = dr >= 0 ? __expf(sn - mx) * invL : 0.f;
+      an_s[r] = an;
+      gs_s[r] = an * (d - c0);
+    }
+  }
+  __syncthreads();
+  // ---- 2. du tile (LDS only: the rows' du in memory is their tile block's)
+#pragma unroll
+  for (int k = 0; k < SF_ROWS / 2; ++k) {
+    const int r = half + 2 * k;
+    float d = 0.f;
+    if (ridx[r] >= 0) {
+      float ya, ga;
+      act_fwd_grad(up[k], act, ya, ga);
+      d = gs_s[r] * wca * ga;
+    }
+    Ds[r * SB_LD + a_col] = d;
+  }
+  __syncthreads();
+  // ---- 3. dT rows = du Wa + attn g_z
+  sf_f32x16 acc[4];
+  sb_product(acc, Ds, wat, wat_frag, wave, lane);
+#pragma unroll
+  for (int nt = 0; nt < 4; ++nt) {
+    const int e = 128 * wave + 32 * nt + r32;
+    const float ge = gzs[e];
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+      const int row = 8 * (i >> 2) + 4 * kg + (i & 3);
+      const int64_t dr = ridx[row];
+      const float v = acc[nt][i] + an_s[row] * ge;
+      if (dr >= 0) __hip_atomic_store(dT + dr * SF_E + e, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+  }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");             // this wave's write-through stores are acknowledged before the barrier
+  __syncthreads();
+  if (wave == 0) {
+    const bool mine = lane < SF_ROWS && ridx[lane < SF_ROWS ? lane : 0] >= 0;
+    const unsigned cnt = (unsigned)__builtin_popcountll(__builtin_amdgcn_ballot_w64(mine));
+    if (lane == 0 && cnt) __hip_atomic_fetch_add(gate, cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
+
 __global__ __launch_bounds__(SF_THREADS, 2) void scorer_fused_bwd_kernel(
     const float* __restrict__ T, int64_t M, const float* __restrict__ u_pre, const float* __restrict__ s_in,
     const float* __restrict__ stats, const float* __restrict__ g_z, const float* __restrict__ z, const float* __restrict__ wc, int act,
@@ -347,14 +508,17 @@ __global__ __launch_bounds__(SF_THREADS, 2) void scorer_fused_bwd_kernel(
     MHIMX_BAG(dbc_part); MHIMX_BAG(rows); MHIMX_BAG(wat); MHIMX_BAG(wat_frag); MHIMX_BAG(img); MHIMX_BAG(dact); MHIMX_BAG(img_part);
     bag_move(pre, bb);
   }
-  if ((int)blockIdx.x >= n_main) {
-    // (the LAST blocks of the grid: every producer of dz is resident or done when one of these starts; they request their weights, then
-    // wait for pre.k announced rows)
-    merge2_bwd_pre_body((int)blockIdx.x - n_main, sb_sm, pre.dz, pre.wo_t, pre.wkv, pre.k, pre.drop_p, pre.oseed, pre.tick, pre.d_bo, pre.accumulate,
+  // a gated launch is [token block | n_main tile blocks | riders], an ungated one its n_main tile blocks
+  const bool gated = gate_row0 >= 0;
+  const int bx = (int)blockIdx.x - (gated ? 1 : 0);            // tile block: first tile of its walk, row of its d_wc / d_bc partials
+  if (bx >= n_main) {
+    // (the LAST blocks of the grid: every producer of dz - the token block, dispatched FIRST, and any tile block with a gate row in front of
+    // the list's last 32 positions - is resident or done when one of these starts; they request their weights, then wait for pre.k
+    // announced rows)
+    merge2_bwd_pre_body(bx - n_main, sb_sm, pre.dz, pre.wo_t, pre.wkv, pre.k, pre.drop_p, pre.oseed, pre.tick, pre.d_bo, pre.accumulate,
                         pre.w, pre.rep, pre.w.gate + 1, (unsigned)pre.k);
     return;
   }
-  const bool gated = gate_row0 >= 0;
   float* Ds = sb_sm;                           // [32][132] du tile (A operand)
   float* gzs = Ds + SF_ROWS * SB_LD;           // [512]
   float* an_s = gzs + SF_E;                    // [32] attn
@@ -379,9 +543,14 @@ __global__ __launch_bounds__(SF_THREADS, 2) void scorer_fused_bwd_kernel(
   const float mx = stats[0], invL = 1.f / stats[1];
   const int a_col = tid & (SF_A - 1), half = tid >> 7;           // du / d_wc column of this thread
   const float wca = wc[a_col];
+  if (gated && bx < 0) {
+    sb_token_block(sb_sm, T, M, u_pre, s_in, c0, mx, invL, wca, act, wat, wat_frag, dT, rows, gate_row0, pre.w.gate + 1);
+    return;
+  }
   float dwc_run = 0.f, dbc_run = 0.f;
+  const int64_t tok_n0 = M > SF_ROWS ? M - SF_ROWS : 0;          // gated: the gate rows at list positions >= tok_n0 are the token block's
 
-  for (int tile = blockIdx.x; tile < tiles; tile += n_main) {
+  for (int tile = bx; tile < tiles; tile += n_main) {
     const int64_t row0 = (int64_t)tile * SF_ROWS;
     if (rows) {
       if (tid < SF_ROWS) { const int64_t n = row0 + tid; ridx[tid] = rows[n < M ? n : M - 1]; }
@@ -393,7 +562,8 @@ __global__ __launch_bounds__(SF_THREADS, 2) void scorer_fused_bwd_kernel(
       for (int q = 0; q < SF_ROWS / 4; ++q) {
         const int r = wave + 4 * q;
         const int64_t n = row0 + r;
-        const int64_t src = rows ? ridx[r] : (n < M ? n : M - 1);
+        // (a position behind img_rows - a merged token, source row N + j - has no d out / d pre row, and its value is masked below: row 0)
+        const int64_t src = n < img_rows ? (rows ? ridx[r] : n) : 0;
         __builtin_amdgcn_global_load_lds((gptr_f)(reinterpret_cast<const char*>(dact + src * SF_E) + lane * 16), (lptr_f)(dact_s + r * SB_DLD), 16, 0, 0);
       }
     }
@@ -455,61 +625,7 @@ __global__ __launch_bounds__(SF_THREADS, 2) void scorer_fused_bwd_kernel(
     __syncthreads();
     // ---- 3. dT tile = du Wa (+ attn g_z): wave w owns columns [128 w, 128 w + 128)
     sf_f32x16 acc[4];
-#pragma unroll
-    for (int nt = 0; nt < 4; ++nt)
-#pragma unroll
-      for (int i = 0; i < 16; ++i) acc[nt][i] = 0.f;
-    const float* aptr = Ds + r32 * SB_LD + 8 * kg;
-    if (wat_frag) {
-      const float* fptr = wat_frag + ((int64_t)(4 * wave) * (SF_A / 16) * 64 + lane) * 8;     // + (nt * 8 + ks) * 512 floats
-      sf_f4 bh_[4], bl_[4];
-#pragma unroll
-      for (int nt = 0; nt < 4; ++nt) {
-        bh_[nt] = *reinterpret_cast<const sf_f4*>(fptr + (nt * 8) * 512);
-        bl_[nt] = *reinterpret_cast<const sf_f4*>(fptr + (nt * 8) * 512 + 4);
-      }
-#pragma unroll 1
-      for (int ks = 0; ks < SF_A / 16; ++ks) {
-        const sf_f4 a0 = *reinterpret_cast<const sf_f4*>(aptr + 16 * ks), a1 = *reinterpret_cast<const sf_f4*>(aptr + 16 * ks + 4);
-        sf_b8 ah, al;
-        sf_split(a0, a1, ah, al);
-        sf_f4 nh[4], nl[4];
-        const int kn = ks + 1 < SF_A / 16 ? ks + 1 : ks;
-#pragma unroll
-        for (int nt = 0; nt < 4; ++nt) {
-          nh[nt] = *reinterpret_cast<const sf_f4*>(fptr + (nt * 8 + kn) * 512);
-          nl[nt] = *reinterpret_cast<const sf_f4*>(fptr + (nt * 8 + kn) * 512 + 4);
-        }
-        // term-major: the three MFMAs into acc[nt] are three others apart (no dependent back-to-back issue)
-#pragma unroll
-        for (int nt = 0; nt < 4; ++nt) acc[nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, __builtin_bit_cast(sf_b8, bh_[nt]), acc[nt], 0, 0, 0);
-#pragma unroll
-        for (int nt = 0; nt < 4; ++nt) acc[nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, __builtin_bit_cast(sf_b8, bl_[nt]), acc[nt], 0, 0, 0);
-#pragma unroll
-        for (int nt = 0; nt < 4; ++nt) acc[nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, __builtin_bit_cast(sf_b8, bh_[nt]), acc[nt], 0, 0, 0);
-#pragma unroll
-        for (int nt = 0; nt < 4; ++nt) {
-          bh_[nt] = nh[nt];
-          bl_[nt] = nl[nt];
-        }
-      }
-    } else {
-#pragma unroll 1
-      for (int ks = 0; ks < SF_A / 16; ++ks) {
-        const sf_f4 a0 = *reinterpret_cast<const sf_f4*>(aptr + 16 * ks), a1 = *reinterpret_cast<const sf_f4*>(aptr + 16 * ks + 4);
-        sf_b8 ah, al;
-        sf_split(a0, a1, ah, al);
-#pragma unroll
-        for (int nt = 0; nt < 4; ++nt) {
-          const float* bp = wat + (int64_t)(128 * wave + 32 * nt + r32) * SF_A + 16 * ks + 8 * kg;
-          sf_b8 bh, bl;
-          sf_split(*reinterpret_cast<const sf_f4*>(bp), *reinterpret_cast<const sf_f4*>(bp + 4), bh, bl);
-          acc[nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, acc[nt], 0, 0, 0);
-          acc[nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, acc[nt], 0, 0, 0);
-          acc[nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, acc[nt], 0, 0, 0);
-        }
-      }
-    }
+    sb_product(acc, Ds, wat, wat_frag, wave, lane);
     if (img) {
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");           // this wave's DMA rows have landed ...
       __syncthreads();                                           // ... and everyone's
@@ -526,8 +642,9 @@ __global__ __launch_bounds__(SF_THREADS, 2) void scorer_fused_bwd_kernel(
           const float v = acc[nt][i] + an_s[row] * ge;
           if (has_tail && n >= img_rows && n < M) {
             const int64_t dr = rows ? ridx[row] : n;
-            if (gated && dr >= gate_row0) __hip_atomic_store(dT + dr * SF_E + e, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            else dT[dr * SF_E + e] = v;
+            if (gated && dr >= gate_row0) {
+              if (n < tok_n0) __hip_atomic_store(dT + dr * SF_E + e, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // (else: the token block's)
+            } else dT[dr * SF_E + e] = v;
           }
           const float d = (float)*reinterpret_cast<const _Float16*>(dact_s + row * SB_DLD + 2 * e);
           val[i] = n < img_rows ? v * d : 0.f;
@@ -573,9 +690,11 @@ __global__ __launch_bounds__(SF_THREADS, 2) void scorer_fused_bwd_kernel(
         if (n < M) {
           const int64_t dr = rows ? ridx[row] : n;
           const float v = acc[nt][i] + an_s[row] * ge;
-          // (a row of the riding stage's dz: past the caches - its readers sit on other XCDs of this same launch)
-          if (gated && dr >= gate_row0) __hip_atomic_store(dT + dr * SF_E + e, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          else dT[dr * SF_E + e] = v;
+          // (a row of the riding stage's dz: past the caches - its readers sit on other XCDs of this same launch; among the list's last 32
+          // positions it is the token block's to store and to announce)
+          if (gated && dr >= gate_row0) {
+            if (n < tok_n0) __hip_atomic_store(dT + dr * SF_E + e, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          } else dT[dr * SF_E + e] = v;
         }
       }
     }
@@ -585,15 +704,15 @@ __global__ __launch_bounds__(SF_THREADS, 2) void scorer_fused_bwd_kernel(
     if (gated && wave == 0) {
       // the tile's rows of dz, counted once per row: their number is added to the gate (the riders wait for pre.k rows in all)
       const int64_t n = row0 + lane;
-      const bool mine = lane < SF_ROWS && n < M && (rows ? ridx[lane < SF_ROWS ? lane : 0] : n) >= gate_row0;
+      const bool mine = lane < SF_ROWS && n < M && (rows ? ridx[lane < SF_ROWS ? lane : 0] : n) >= gate_row0 && n < tok_n0;
       const unsigned cnt = (unsigned)__builtin_popcountll(__builtin_amdgcn_ballot_w64(mine));
       if (lane == 0 && cnt) __hip_atomic_fetch_add(pre.w.gate + 1, cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
   }
   dwc_s[half * SF_A + a_col] = dwc_run;
   __syncthreads();
-  if (tid < SF_A) dwc_part[(int64_t)blockIdx.x * SF_A + tid] = dwc_s[tid] + dwc_s[SF_A + tid];
-  if (tid == 0) dbc_part[blockIdx.x] = dbc_run;
+  if (tid < SF_A) dwc_part[(int64_t)bx * SF_A + tid] = dwc_s[tid] + dwc_s[SF_A + tid];
+  if (tid == 0) dbc_part[bx] = dbc_run;
 }
 
 #ifdef MHIMX_SF_PROF
@@ -651,15 +770,17 @@ int scorer_fused_bwd(hipStream_t st, const float* T, int64_t M, const float* u_p
   const int grid = tiles < max_parts ? tiles : max_parts;
   static_assert(SB_SMEM >= M2_BWD_PRE_LDS * sizeof(float), "the riding Merge stage's LDS is the backward's");
   static_assert(SF_THREADS == M2_THREADS, "the riding Merge stage is written for 256 threads");
+  MHIMX_CHECK_ARG(!pre_side || gate_row0 >= 0, "scorer backward: a riding Merge stage needs the first row of its dz in dT");
   Merge2Side pre = {};
-  int ride = 0;
+  int front = 0, ride = 0;
   if (pre_side) {
     pre = *reinterpret_cast<const Merge2Side*>(pre_side);
+    front = 1;                                 // the token block
     ride = M2_BWD_PRE_BLOCKS;
   } else {
     gate_row0 = -1;
   }
-  hipLaunchKernelGGL(scorer_fused_bwd_kernel, bgrid(grid + ride), dim3(SF_THREADS), img ? SB_SMEM_IMG : SB_SMEM, st, T, M, u_pre, s_in, stats, g_z, z, wc, act, wa_t,
+  hipLaunchKernelGGL(scorer_fused_bwd_kernel, bgrid(front + grid + ride), dim3(SF_THREADS), img ? SB_SMEM_IMG : SB_SMEM, st, T, M, u_pre, s_in, stats, g_z, z, wc, act, wa_t,
                      wa_t_frag, du, dT, dwc_part, dbc_part, tiles, rows, grid, pre, gate_row0, (char*)img, (const _Float16*)img_dact, img_part, img_rows, cur_batch());
   MHIMX_LAUNCH_CHECK();
   return grid;

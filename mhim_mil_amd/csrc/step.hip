@@ -12,7 +12,8 @@
 //        6..9  mhimx_merge_fwd          rows pass | partial merge | O | to_out + EMA of the global queries
 //       10,11  mhimx_abmil_pool_fwd     student scorer over [stay | tokens] | finalize
 //          12  mhimx_head_fwd_bwd       predictor, CE, distillation, their gradients
-//          13  mhimx_abmil_pool_bwd     one-pass rows backward (the Merge backward's first stage rides behind its gate)
+//          13  mhimx_abmil_pool_bwd     one-pass rows backward: [token block | row tiles | the Merge backward's first stage, riding]; the
+//                                       token block (block 0) makes the k tokens' gradient rows alone and opens the riders' gate
 //          14  mhimx_merge_bwd          rows backward + the parked scorer-weight-gradient product in one launch
 //       15,16  rows_dpre_image | bag_wgrad   the projection's gradient pair (the Merge tail and the last reductions ride)
 //          17  mhimx_optim_step         Adam + EMA teacher (folds the split-K slab sum)
