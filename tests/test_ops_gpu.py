@@ -169,9 +169,15 @@ def _scorer_params(seed, E, A, gated, bias):
 @pytest.mark.parametrize("act,gated,bias,A", [("relu", False, False, 128), ("gelu", False, False, 128),
                                                ("tanh", False, True, 128), ("tanh", True, True, 384),
                                                ("relu", True, False, 128)])
-@pytest.mark.parametrize("prec", ["f32", "f16s"])
+@pytest.mark.parametrize("prec", ["f32", "f16s", "bf16x3"])
 def test_pool_fwd_bwd(act, gated, bias, A, prec):
-    """Scorer + softmax pool (two token segments) forward and backward vs fp64 autograd of the oracle."""
+    """Scorer + softmax pool (two token segments) forward and backward vs fp64 autograd of the oracle.
+
+    bf16x3 is the production precision (gated / A = 384: the row-pass form behind the three-term GEMM).  Its factors come from a CPU model
+    of the three-term product on these inputs (T and the weights split into bf16 hi / lo, hi hi + lo hi + hi lo rounded to fp32, injected
+    into the fp64 forward / backward): the scores land at 1.0 - 1.8 x the f = 1 bound (max|s| is 5 - 8 here and the bound's atol is
+    absolute), so the forward takes f = 4 - the first of 1, 2, 4 with 2 x headroom over the model, and the f16s row's; the gradients move
+    by at most 0.45 of the f = 1 bound, which they keep."""
     ops = _ops()
     E, M1, M2, Cc = 512, 777, 5, 2
     T1, T2 = rnd(21, (M1, E)).abs(), rnd(22, (M2, E), std=0.5)
@@ -190,6 +196,7 @@ def test_pool_fwd_bwd(act, gated, bias, A, prec):
     sc = ops.ScorerW(d(wa), d(wc), {"relu": 1, "gelu": 2, "tanh": 3}[act], ba=d(ba), wb=d(wb), bb=d(bb), bc=d(bc), prec=prec)
     st = ops.abmil_pool_fwd(sc, d(T1), d(T2), wp=d(wp))
     f = 1.0 if prec == "f32" else 4.0
+    fg = 4.0 if prec == "f16s" else 1.0
     np.testing.assert_allclose(st.s.cpu().numpy(), s.detach().float().numpy(), atol=2e-5 * f, rtol=1e-5 * f)
     np.testing.assert_allclose(st.z.cpu().numpy(), z.detach().float().numpy(), atol=3e-6 * f, rtol=1e-5 * f)
     np.testing.assert_allclose(ops.softmax_from_stats(st.s, st.stats).cpu().numpy(), attn.detach().float().numpy(),
@@ -198,11 +205,11 @@ def test_pool_fwd_bwd(act, gated, bias, A, prec):
     np.testing.assert_allclose(st.cproj.cpu().numpy(), cp_ref.numpy(), atol=2e-5, rtol=1e-5)
     g = ops.abmil_pool_bwd(sc, st, d(gz), ops.transpose(d(wa)), ops.transpose(d(wb)) if gated else None, need_bias=bias,
                            splits=4)
-    gtol = dict(rtol=2e-4 * f, atol=0)
+    gtol = dict(rtol=2e-4 * fg, atol=0)
 
     def close(name, got, ref):
         ref = ref.float().numpy()
-        np.testing.assert_allclose(got.cpu().numpy().reshape(ref.shape), ref, atol=3e-5 * f * (np.abs(ref).max() + 1e-30),
+        np.testing.assert_allclose(got.cpu().numpy().reshape(ref.shape), ref, atol=3e-5 * fg * (np.abs(ref).max() + 1e-30),
                                    rtol=gtol["rtol"], err_msg=name)
 
     close("dT1", g["dT1"], leaves["T1"].grad)
@@ -549,7 +556,7 @@ def test_deferred_reductions_match_immediate():
 def test_fused_scorer_backward_and_transposed_fragment_image():
     """prep kind 5 (fragment image of the transpose, made from the untransposed weight) == kind 4 of the transposed weight;
     the one-pass scorer backward with that image == the same kernel splitting Wa^T on the fly, bit for bit (the fp64
-    comparison of the fused backward is test_pool_fwd_bwd's)."""
+    comparisons of the fused backward are tests/test_scorer_pool_oracle_gpu.py's, section C)."""
     ops = _ops()
     E, A, M = 512, 128, 3001
     wa, wc, _, ba, _, bc = _scorer_params(61, E, A, False, True)
