@@ -1070,6 +1070,59 @@ int mhimx_pure_window_run_x(void* stream, const mhimx_step_cfg* cfg, int32_t n_b
 int mhimx_ragged_window_run_x(void* stream, const mhimx_step_cfg* cfg, int32_t n_bags, const mhimx_ragged_window_bag* bags,
                               int64_t host_step, void* ws, int64_t ws_bytes, int32_t update, int32_t x_dtype);
 
+/* ------------------------------------------------------------------------------------------
+ * Ragged multi-bag inference for MHIM(DSMIL): the eval-mode forward of the reference's second MHIM baseline for
+ * n_bags bags of DIFFERENT row counts in one call - a DSMIL validation or test pass as one C call per chunk of bags instead of about
+ * a dozen launches per bag (a one-workgroup column max, a host-side gather of the critical rows and a second pass of the q network
+ * among them) from the host loop.
+ * replaces: modules/mhim.py:229-272 (forward_test, baseline == 'dsmil', merge_test off) over mhim_modules/baseline.py:112-194
+ *           (BClassifier, DSMIL) under engines/common_mil.py:56-68 (validate_func, its 0.5 * logits[0] + 0.5 * logits[1] mix of
+ *           :66-67 included) and the per-bag loop + criterion call of engines/base_engine.py:234-329.
+ * Per bag:  h = act(X W1^T + b1),  classes = h Wi^T + bi,  V = relu(h Wv^T + bv),  Q = tanh(relu(h Wq0^T + bq0) Wq2^T + bq2),
+ *           crit[c] = arg max_m classes[m, c] (lowest row on equal values: mhimx_colmax's rule),  logits_ins[c] = classes[crit[c], c],
+ *           q_max[c] = Q[crit[c]],  a = Q q_max^T / sqrt(128),  A = softmax over the rows,  B = A^T V,
+ *           logits_bag[o] = sum_{c,e} fcc.weight[o, c, e] B[c, e] + fcc.bias[o],  logits = 0.5 logits_bag + 0.5 logits_ins,
+ *           loss = cross entropy of the logits row.
+ *           Instance score (attn), the rule of the DSMIL module: cls_attn: max_c classes[m, c]; otherwise max_c A[m, c], or with
+ *           no_norm max_c a[m, c].
+ *           The four wide products run in the 3-term bf16 form (~2^-16); classes, a, the softmax, B's sums, fcc and the loss in fp32.
+ * Seven launches whatever n_bags is (weight images; ragged projection X -> h; the same kernel h -> V; per-row Q / classes with the
+ * per-chunk arg-max partials; per-bag critical rows; per-chunk softmax-pool partials; merge + fcc + mix + loss + attention).  The
+ * properties are those of mhimx_infer_run: enqueue-only and capturable, no allocation / synchronisation / host-to-device copy, no
+ * floating-point atomics, no workgroup waits for another, and a bag's tiles, chunks and merge order depend on its own N alone - its
+ * outputs have the same bits wherever it stands in a call.
+ * Shapes: E = 512, q width 128, 1 <= C <= 16, D % 256 == 0, every N >= 1, at most MHIMX_INFER_MAX bags; the checks on the bag table
+ * and x_dtype are those of mhimx_infer_run_x.  Anything else returns < 0 before any device call; mhimx_last_error names the bag.
+ * Workspace: mhimx_infer_dsmil_ws_bytes (pure host arithmetic; < 0 on a refused shape), 256-byte aligned: about 4.6 KiB per row
+ * (h 2048 + V 2048 + Q 512 + classes 64), the per-chunk partials (C x 2 KiB per 256 rows) and the four weight images.
+ * MHIMX_VERSION stays 620: additions only.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct {
+  int64_t D, E, C;                                /* input_dim, mlp_dim (512), classes                                                    */
+  int32_t act;                                    /* MHIMX_ACT_* of the feature layer                                                     */
+  int32_t cls_attn, no_norm;                      /* the instance-score rule (the model's attn2score; forward_test's no_norm)             */
+  int32_t pad;
+  const float *w1, *b1;                           /* feature.0.{weight [E, D], bias [E]}                                                  */
+  const float *wi, *bi;                           /* i_classifier.0.{weight [C, E], bias [C]}                                             */
+  const float *wq0, *bq0;                         /* b_classifier.q.0.{weight [128, E], bias [128]}                                       */
+  const float *wq2, *bq2;                         /* b_classifier.q.2.{weight [128, 128], bias [128]}                                     */
+  const float *wv, *bv;                           /* b_classifier.v.1.{weight [E, E], bias [E]}                                           */
+  const float *wfcc, *bfcc;                       /* b_classifier.fcc.{weight [C, C, E], bias [C]}                                        */
+} mhimx_infer_dsmil_cfg;
+typedef struct {                                  /* row_off[b] = N[0] + .. + N[b-1]                                                      */
+  float* logits_bag;                              /* [n_bags, C]                                                                          */
+  float* logits_ins;                              /* [n_bags, C] max-instance logits                                                      */
+  float* logits;                                  /* [n_bags, C] 0.5 logits_bag + 0.5 logits_ins                                          */
+  float* B;                                       /* [n_bags, C, E] optional (NULL)                                                       */
+  int64_t* crit;                                  /* [n_bags, C] optional: the critical row of each class inside its bag                  */
+  float* attn;                                    /* [sum N] optional: the instance score, bag b's at row_off[b]                          */
+  float* loss;                                    /* [n_bags] optional (needs labels): cross entropy of each bag's mixed logits           */
+} mhimx_infer_dsmil_out;
+int64_t mhimx_infer_dsmil_ws_bytes(const mhimx_infer_dsmil_cfg* cfg, int32_t n_bags, const mhimx_infer_bag* bags);
+/* labels_dev: int64 [n_bags] on the device, or NULL (a label outside [0, C) gives a NaN loss); x_dtype: MHIMX_X_* */
+int mhimx_infer_dsmil_run(void* stream, const mhimx_infer_dsmil_cfg* cfg, int32_t n_bags, const mhimx_infer_bag* bags,
+                          const int64_t* labels_dev, const mhimx_infer_dsmil_out* out, void* ws, int64_t ws_bytes, int32_t x_dtype);
+
 /* dst = src (float4 grid-stride stream copy): the on-box HBM copy rate bench.py reports beside the nominal 8 TB/s */
 int mhimx_stream_copy(void* stream, const float* src, float* dst, int64_t n_floats);
 

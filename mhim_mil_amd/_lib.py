@@ -235,6 +235,17 @@ class InferOut(C.Structure):
     _fields_ = [(n, c_f32p) for n in ("logits", "z", "stats", "score", "attn", "loss")]
 
 
+class InferDsmilCfg(C.Structure):
+    """mhimx_infer_dsmil_cfg: the eval-mode forward of ONE MHIM(DSMIL) model over bags of different row counts (its twelve parameters:
+    feature.0, i_classifier.0, b_classifier.q.0 / q.2 / v.1 / fcc)."""
+    _fields_ = [("D", C.c_int64), ("E", C.c_int64), ("C", C.c_int64), ("act", C.c_int32), ("cls_attn", C.c_int32), ("no_norm", C.c_int32),
+                ("pad", C.c_int32)] + [(n, c_f32p) for n in ("w1", "b1", "wi", "bi", "wq0", "bq0", "wq2", "bq2", "wv", "bv", "wfcc", "bfcc")]
+
+
+class InferDsmilOut(C.Structure):
+    _fields_ = [(n, c_f32p) for n in ("logits_bag", "logits_ins", "logits", "B")] + [("crit", C.c_void_p)] + [(n, c_f32p) for n in ("attn", "loss")]
+
+
 INFER_MAX = 32               # MHIMX_INFER_MAX
 INFER_MAX_ROWS = 4194304     # MHIMX_INFER_MAX_ROWS
 X_F32, X_F16, X_BF16 = 0, 1, 2   # MHIMX_X_*: the element type of the bags' rows in the three *_run_x calls
@@ -384,6 +395,8 @@ SYMBOLS = {
     "mhimx_infer_ws_bytes": (_I64, [C.POINTER(InferCfg), _I32, _P]),
     "mhimx_infer_run": (C.c_int, [_P, C.POINTER(InferCfg), _I32, _P, _P, C.POINTER(InferOut), _P, _I64]),
     "mhimx_infer_run_x": (C.c_int, [_P, C.POINTER(InferCfg), _I32, _P, _P, C.POINTER(InferOut), _P, _I64, _I32]),
+    "mhimx_infer_dsmil_ws_bytes": (_I64, [C.POINTER(InferDsmilCfg), _I32, _P]),
+    "mhimx_infer_dsmil_run": (C.c_int, [_P, C.POINTER(InferDsmilCfg), _I32, _P, _P, C.POINTER(InferDsmilOut), _P, _I64, _I32]),
     "mhimx_step_run_many": (C.c_int, [_P, C.POINTER(StepCfg), _I32, _P, _P, _P, _P, C.POINTER(StepCounts), C.POINTER(StepSeeds), _I64, _P, _I64]),
     "mhimx_pure_step_layout_of": (C.c_int, [C.POINTER(StepCfg), _I64, C.POINTER(StepLayout)]),
     "mhimx_pure_step_run": (C.c_int, [_P, C.POINTER(StepCfg), _P, _I64, _I64, _P, C.c_uint64, _I64, _P, _I64, _I32]),

@@ -1,0 +1,575 @@
+// infer_dsmil.hip — eval-mode MHIM(DSMIL) forward of up to MHIMX_INFER_MAX bags of DIFFERENT row counts in one call
+// (modules/mhim.py:229-272 forward_test with baseline == 'dsmil' and merge_test off, over mhim_modules/baseline.py:112-194 BClassifier / DSMIL,
+// under engines/common_mil.py:56-68 with the 0.5 * logits[0] + 0.5 * logits[1] mix of :66-67):
+//
+//     h = act(X W1^T + b1),  classes = h Wi^T + bi,  V = relu(h Wv^T + bv),  Q = tanh(relu(h Wq0^T + bq0) Wq2^T + bq2)
+//     crit[c] = arg max_m classes[m,c],  q_max[c] = Q[crit[c]],  A = softmax_m(Q q_max^T / sqrt(128)),  B = A^T V,
+//     logits_bag = fcc(B),  logits_ins = max_m classes,  logits = 0.5 logits_bag + 0.5 logits_ins,  loss = CE(logits, label)
+//
+// The sibling of infer.hip: the same by-value bag table (InferTab), so the call copies nothing to the device, waits for nothing and
+// allocates nothing, and can be captured in a graph.  Seven launches whatever n_bags is:
+//   1  mhimx_prep_batch        paired-plane images of W1 and of v.1.weight, matrix-core fragment images (kind 4) of q.0.weight [128,512]
+//                              and q.2.weight [128,128] (the kind-4 job takes any K % 16 == 0: no new kind)
+//   2  infer_project_kernel    (bag_project.hip) X -> h, all three element types
+//   3  infer_project_kernel    again over a second table whose "bags" are the h rows in the workspace (pitch 512, fp32, D = 512): h -> V
+//   4  dsmil_rows_kernel       one workgroup per CHUNK of 256 rows of one bag, 32-row tiles through LDS: U1 = relu(h q0^T + b) on the matrix
+//                              cores (3-term bf16), U1 through LDS into Q = tanh(U1 q2^T + b) (K = 128), classes in fp32 FMAs; per row Q,
+//                              classes[16] and max_c classes, per chunk and class the (max, arg-max) partial
+//   5  dsmil_crit_kernel       grid = bags: merges the chunk partials (lowest row on equal values - colmax_kernel's rule, rows.hip) -> crit,
+//                              logits_ins, and the C rows Q[crit[c]] as q_max: q(h[crit]) IS that row of Q, no second q-network pass
+//   6  dsmil_pool_kernel       one workgroup per chunk: a = Q q_max^T / sqrt(128) in fp32, per class the log-sum-exp partial
+//                              {max, sum, sum_m e^{a - max} V[m,:]}
+//   7  dsmil_finalize_kernel   plane x = bag: block y = 0 merges the partials in index order -> B, fcc, the mix, the loss; blocks y > 0
+//                              write the instance score when it is not max_c classes (they recompute a from Q and q_max)
+// No workgroup waits for another and there are no floating-point atomics.  A bag's tiles, chunks and merge order depend on its own N
+// alone, so its results have the same bits wherever it stands in a call.
+#include <limits.h>
+#include <math.h>
+
+#include "infer_tab.hpp"
+
+namespace mhimx {
+
+namespace {
+
+constexpr int DQ = 128, DS_MAXC = 16;
+constexpr int DR_ROWS = 32, DR_CHUNK = 256, DR_LD = IE + 4, DR_ULD = DQ + 4, DR_THREADS = 256;
+constexpr size_t DR_SMEM = (size_t)(DR_ROWS * DR_LD + DR_ROWS * DS_MAXC) * sizeof(float);
+constexpr int DP_THREADS = 256, DF_T = 512, DF_ATTN_BLOCKS = 8;
+constexpr float DS_SCALE = 0.08838834764831845f;   // 1 / sqrt(128)
+static_assert(DR_ROWS * DR_ULD <= DR_ROWS * DR_LD, "the U1 tile reuses the feature tile's LDS");
+
+typedef __bf16 ds_b8 __attribute__((ext_vector_type(8)));
+typedef float ds_f16 __attribute__((ext_vector_type(16)));
+
+MHIMX_DEV void ds_split(const f32x4& a, const f32x4& b, ds_b8& hi, ds_b8& lo) {
+  const float x[8] = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    const __bf16 h = (__bf16)x[i];
+    hi[i] = h;
+    lo[i] = (__bf16)(x[i] - (float)h);
+  }
+}
+
+// acc += A[32 rows of LDS, K] B^T for one wave's 32 columns: v_mfma_f32_32x32x16_bf16, A split on the fly, B a prep kind-4 image
+// (infer_score_kernel's k loop); returns the three bf16x3 terms added.  aptr = tile + (lane & 31) * ld + 8 * (lane >> 5).
+template <int K>
+MHIMX_DEV ds_f16 ds_mma(const float* aptr, const f32x4* fptr) {
+  ds_f16 acc, acc2, acc3;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) { acc[i] = 0.f; acc2[i] = 0.f; acc3[i] = 0.f; }
+  f32x4 bh = fptr[0], bl = fptr[1];
+#pragma unroll 4
+  for (int ks = 0; ks < K / 16; ++ks) {
+    const int kn = ks + 1 < K / 16 ? ks + 1 : ks;
+    const f32x4 nbh = fptr[128 * kn], nbl = fptr[128 * kn + 1];
+    const f32x4 a0 = *reinterpret_cast<const f32x4*>(aptr + 16 * ks), a1 = *reinterpret_cast<const f32x4*>(aptr + 16 * ks + 4);
+    ds_b8 ah, al;
+    ds_split(a0, a1, ah, al);
+    const ds_b8 bh8 = __builtin_bit_cast(ds_b8, bh), bl8 = __builtin_bit_cast(ds_b8, bl);
+    acc2 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh8, acc2, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh8, acc, 0, 0, 0);
+    acc3 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl8, acc3, 0, 0, 0);
+    bh = nbh;
+    bl = nbl;
+  }
+#pragma unroll
+  for (int i = 0; i < 16; ++i) acc[i] += acc2[i] + acc3[i];
+  return acc;
+}
+
+// a[c] = Q[m,:] . q_max[c,:] / sqrt(128), fp32 in a fixed order (qs: [CT][128] in LDS; classes past C hold zeros).  The pool launch
+// and the attention blocks of the finalize launch share it: the same bits.
+template <int CT>
+MHIMX_DEV void ds_scores(const float* __restrict__ qrow, const float* qs, float (&a)[CT]) {
+#pragma unroll
+  for (int c = 0; c < CT; ++c) a[c] = 0.f;
+#pragma unroll 4
+  for (int j = 0; j < DQ / 4; ++j) {
+    const f32x4 q = reinterpret_cast<const f32x4*>(qrow)[j];
+#pragma unroll
+    for (int c = 0; c < CT; ++c) {
+      const f32x4 w = reinterpret_cast<const f32x4*>(qs + c * DQ)[j];
+      a[c] = fmaf(q[3], w[3], fmaf(q[2], w[2], fmaf(q[1], w[1], fmaf(q[0], w[0], a[c]))));
+    }
+  }
+#pragma unroll
+  for (int c = 0; c < CT; ++c) a[c] *= DS_SCALE;
+}
+
+#define DS_LOCATE_PART(part)                                        \
+  int bag = 0;                                                      \
+  _Pragma("unroll") for (int b = 1; b < MHIMX_INFER_MAX; ++b)       \
+    if (b < tab.n && (part) >= tab.part0[b]) bag = b;               \
+  int64_t N = tab.N[0], orow0 = tab.row0[0];                        \
+  int p0 = tab.part0[0];                                            \
+  IT_PICK(N, N, bag) IT_PICK(orow0, row0, bag) IT_PICK(p0, part0, bag)
+
+// ------------------------------------------------------------------------------------------------ 4. per-row Q, classes, arg-max partials
+// blockIdx.x = chunk of DR_CHUNK rows of ONE bag (the last chunk of a bag may be short).  Wave w owns columns [32 w, 32 w + 32) of U1 and of Q.
+__global__ __launch_bounds__(DR_THREADS, 2) void dsmil_rows_kernel(InferTab tab, const float* __restrict__ Hin, const float* __restrict__ q0_frag,
+                                                                   const float* __restrict__ bq0, const float* __restrict__ q2_frag,
+                                                                   const float* __restrict__ bq2, const float* __restrict__ wi,
+                                                                   const float* __restrict__ bi, int C, float* __restrict__ Qout,
+                                                                   float* __restrict__ cls, float* __restrict__ score,
+                                                                   float* __restrict__ pmax, int32_t* __restrict__ parg) {
+  extern __shared__ __attribute__((aligned(16))) float dr_sm[];
+  float* Hs = dr_sm;                          // [32][516] feature rows; then [32][132] U1 (the feature rows are dead by then)
+  float* Us = dr_sm;
+  float* cs = Hs + DR_ROWS * DR_LD;           // [32][16] classes of the tile (rows past the chunk: -inf)
+  const int part = blockIdx.x;
+  DS_LOCATE_PART(part)
+  const int64_t c0 = (int64_t)(part - p0) * DR_CHUNK;           // first row of the chunk inside its bag
+  const int64_t M = (N - c0 < DR_CHUNK) ? N - c0 : DR_CHUNK;    // rows of the chunk (>= 1)
+  const float* T = Hin + (orow0 + c0) * IE;
+  const int64_t grow0 = orow0 + c0;                             // first row of the chunk in the call's row space
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int r32 = lane & 31, kg = lane >> 5;
+  const int n_col = 32 * wave + r32;
+  const float b0 = bq0[n_col], b2 = bq2[n_col];
+  const f32x4* f0 = reinterpret_cast<const f32x4*>(q0_frag + ((int64_t)wave * (IE / 16) * 64 + lane) * 8);
+  const f32x4* f2 = reinterpret_cast<const f32x4*>(q2_frag + ((int64_t)wave * (DQ / 16) * 64 + lane) * 8);
+  const int crow = tid >> 3, seg = tid & 7;                     // classes: 8 lanes per row
+
+  float best = -INFINITY;                                       // threads < C: running (max, arg-max) of class tid over the chunk
+  int arg = (int)c0;
+  const int tiles = (int)((M + DR_ROWS - 1) / DR_ROWS);
+  for (int tile = 0; tile < tiles; ++tile) {
+    const int64_t row0 = (int64_t)tile * DR_ROWS;
+    // ---- rows -> LDS (rows past the chunk: zeros; their loads are clamped so that all 16 are in flight)
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+      const int f = tid + DR_THREADS * i, r = f >> 7, c4 = f & 127;
+      const int64_t nr = row0 + r;
+      f32x4 v = reinterpret_cast<const f32x4*>(T + (nr < M ? nr : M - 1) * IE)[c4];
+      if (nr >= M) v = f32x4{0.f, 0.f, 0.f, 0.f};
+      *reinterpret_cast<f32x4*>(Hs + r * DR_LD + 4 * c4) = v;
+    }
+    __syncthreads();
+    // ---- U1 tile on the matrix cores
+    const ds_f16 u1 = ds_mma<IE>(Hs + r32 * DR_LD + 8 * kg, f0);
+    // ---- classes = h Wi^T + bi: lane `seg` takes the 16-byte groups seg, seg + 8, .. of the row, the 8 partial sums added in a fixed xor tree
+    {
+      float cp[DS_MAXC];
+#pragma unroll
+      for (int c = 0; c < DS_MAXC; ++c) cp[c] = 0.f;
+      const f32x4* hr = reinterpret_cast<const f32x4*>(Hs + crow * DR_LD);
+      const f32x4* w4 = reinterpret_cast<const f32x4*>(wi);
+#pragma unroll 2
+      for (int g = 0; g < IE / 32; ++g) {
+        const f32x4 h = hr[seg + 8 * g];
+#pragma unroll
+        for (int c = 0; c < DS_MAXC; ++c)
+          if (c < C) {
+            const f32x4 w = w4[c * (IE / 4) + seg + 8 * g];
+            cp[c] = fmaf(h[3], w[3], fmaf(h[2], w[2], fmaf(h[1], w[1], fmaf(h[0], w[0], cp[c]))));
+          }
+      }
+      const bool live = row0 + crow < M;
+      float rmax = -INFINITY;
+#pragma unroll
+      for (int c = 0; c < DS_MAXC; ++c) {
+        cp[c] += __shfl_xor(cp[c], 1);
+        cp[c] += __shfl_xor(cp[c], 2);
+        cp[c] += __shfl_xor(cp[c], 4);
+        if (c < C) {
+          cp[c] += bi[c];
+          rmax = fmaxf(rmax, cp[c]);
+        }
+      }
+      if (seg == 0) {
+        if (live) {
+          f32x4* o = reinterpret_cast<f32x4*>(cls + (grow0 + row0 + crow) * DS_MAXC);
+#pragma unroll
+          for (int q = 0; q < 4; ++q) o[q] = f32x4{cp[4 * q], cp[4 * q + 1], cp[4 * q + 2], cp[4 * q + 3]};
+          if (score) score[grow0 + row0 + crow] = rmax;
+        }
+        f32x4* o = reinterpret_cast<f32x4*>(cs + crow * DS_MAXC);
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+          o[q] = live ? f32x4{cp[4 * q], cp[4 * q + 1], cp[4 * q + 2], cp[4 * q + 3]} : f32x4{-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+      }
+    }
+    __syncthreads();                           // every read of the feature tile is done; the tile's classes are in LDS
+    // ---- U1 = relu(. + b) -> LDS: u1[i] = U1[row = 8 (i >> 2) + 4 kg + (i & 3)][n_col]
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+      const int row = 8 * (i >> 2) + 4 * kg + (i & 3);
+      const float u = u1[i] + b0;
+      Us[row * DR_ULD + n_col] = u > 0.f ? u : 0.f;
+    }
+    if (tid < C) {                             // rows in index order, strictly greater: the lowest row wins on equal values
+      for (int r = 0; r < DR_ROWS; ++r) {
+        const float v = cs[r * DS_MAXC + tid];
+        if (v > best) { best = v; arg = (int)(c0 + row0) + r; }
+      }
+    }
+    __syncthreads();
+    // ---- Q = tanh(U1 q2^T + b), K = 128
+    const ds_f16 q = ds_mma<DQ>(Us + r32 * DR_ULD + 8 * kg, f2);
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+      const int row = 8 * (i >> 2) + 4 * kg + (i & 3);
+      if (row0 + row < M) Qout[(grow0 + row0 + row) * DQ + n_col] = tanh_fast(q[i] + b2);
+    }
+    __syncthreads();                           // the next tile overwrites Hs / cs
+  }
+  if (tid < C) {
+    pmax[(int64_t)part * DS_MAXC + tid] = best;
+    parg[(int64_t)part * DS_MAXC + tid] = arg;
+  }
+}
+
+// ------------------------------------------------------------------------------------------------ 5. critical rows
+// blockIdx.x = bag.  Wave w merges the chunk partials of classes w, w + 4, ..: the maximum, and among equal values the lowest row - the rule
+// of colmax_kernel (rows.hip), so that this route and the module's name the same row.  Then the C rows Q[crit[c]] are copied as q_max.
+__global__ __launch_bounds__(256) void dsmil_crit_kernel(InferTab tab, const float* __restrict__ pmax, const int32_t* __restrict__ parg,
+                                                         const float* __restrict__ Q, int C, float* __restrict__ qmax,
+                                                         float* __restrict__ logits_ins, int64_t* __restrict__ crit) {
+  __shared__ int s_arg[DS_MAXC];
+  const int bag = blockIdx.x;
+  int64_t N = tab.N[0], orow0 = tab.row0[0];
+  int p0 = tab.part0[0];
+  IT_PICK(N, N, bag) IT_PICK(orow0, row0, bag) IT_PICK(p0, part0, bag)
+  const int G = (int)((N + DR_CHUNK - 1) / DR_CHUNK);
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  for (int c = wave; c < C; c += 4) {
+    float best = -INFINITY;
+    int arg = INT_MAX;
+    for (int g = lane; g < G; g += 64) {
+      const float v = pmax[(int64_t)(p0 + g) * DS_MAXC + c];
+      const int a = parg[(int64_t)(p0 + g) * DS_MAXC + c];
+      if (v > best || (v == best && a < arg)) { best = v; arg = a; }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const float ov = __shfl_xor(best, o, 64);
+      const int oi = __shfl_xor(arg, o, 64);
+      if (ov > best || (ov == best && oi < arg)) { best = ov; arg = oi; }
+    }
+    if (lane == 0) {
+      s_arg[c] = arg;
+      logits_ins[(int64_t)bag * C + c] = best;
+      if (crit) crit[(int64_t)bag * C + c] = arg;
+    }
+  }
+  __syncthreads();
+  for (int i = tid; i < C * DQ; i += 256) {
+    const int c = i >> 7, j = i & (DQ - 1);
+    qmax[((int64_t)bag * DS_MAXC + c) * DQ + j] = Q[(orow0 + s_arg[c]) * DQ + j];
+  }
+}
+
+// ------------------------------------------------------------------------------------------------ 6. softmax-pool partials
+// blockIdx.x = chunk.  Thread t scores row t of the chunk against the C critical queries; the chunk's {max, sum} per class; then thread t owns
+// columns t and t + 256 of the [C, 512] accumulator sum_m e^{a[m,c] - max_c} V[m,:], rows in index order.  CT: C rounded up to 2 / 4 / 8 / 16.
+template <int CT>
+__global__ __launch_bounds__(DP_THREADS) void dsmil_pool_kernel(InferTab tab, const float* __restrict__ Q, const float* __restrict__ V,
+                                                                const float* __restrict__ qmax, int C, float* __restrict__ pm,
+                                                                float* __restrict__ pl, float* __restrict__ pB) {
+  __shared__ __attribute__((aligned(16))) float qs[CT * DQ];
+  __shared__ __attribute__((aligned(16))) float ps[DR_CHUNK * CT];
+  __shared__ float redm[CT][4], reds[CT][4];
+  const int part = blockIdx.x;
+  DS_LOCATE_PART(part)
+  const int64_t c0 = (int64_t)(part - p0) * DR_CHUNK;
+  const int M = (int)((N - c0 < DR_CHUNK) ? N - c0 : DR_CHUNK);
+  const int64_t grow0 = orow0 + c0;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  for (int i = tid; i < CT * DQ; i += DP_THREADS) qs[i] = (i >> 7) < C ? qmax[(int64_t)bag * DS_MAXC * DQ + i] : 0.f;
+  __syncthreads();
+  const bool live = tid < M;
+  float a[CT];
+  ds_scores<CT>(Q + (grow0 + (live ? tid : 0)) * DQ, qs, a);
+#pragma unroll
+  for (int c = 0; c < CT; ++c) {
+    if (!live) a[c] = -INFINITY;
+    const float m = wave_max(a[c]);
+    if (lane == 0) redm[c][wave] = m;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int c = 0; c < CT; ++c) {
+    const float mx = fmaxf(fmaxf(redm[c][0], redm[c][1]), fmaxf(redm[c][2], redm[c][3]));   // row 0 of a chunk is a real row: finite
+    const float p = live ? __expf(a[c] - mx) : 0.f;
+    ps[tid * CT + c] = p;
+    const float s = wave_sum(p);
+    if (lane == 0) reds[c][wave] = s;
+  }
+  __syncthreads();
+  if (tid < C) {
+    pm[(int64_t)part * DS_MAXC + tid] = fmaxf(fmaxf(redm[tid][0], redm[tid][1]), fmaxf(redm[tid][2], redm[tid][3]));
+    pl[(int64_t)part * DS_MAXC + tid] = (reds[tid][0] + reds[tid][1]) + (reds[tid][2] + reds[tid][3]);
+  }
+  float acc0[CT], acc1[CT];
+#pragma unroll
+  for (int c = 0; c < CT; ++c) { acc0[c] = 0.f; acc1[c] = 0.f; }
+  const float* Vb = V + grow0 * IE + tid;
+#pragma unroll 4
+  for (int m = 0; m < M; ++m) {
+    const float v0 = Vb[(int64_t)m * IE], v1 = Vb[(int64_t)m * IE + DP_THREADS];
+#pragma unroll
+    for (int c = 0; c < CT; ++c) {
+      const float p = ps[m * CT + c];
+      acc0[c] = fmaf(p, v0, acc0[c]);
+      acc1[c] = fmaf(p, v1, acc1[c]);
+    }
+  }
+#pragma unroll
+  for (int c = 0; c < CT; ++c)
+    if (c < C) {
+      float* o = pB + ((int64_t)part * C + c) * IE + tid;
+      o[0] = acc0[c];
+      o[DP_THREADS] = acc1[c];
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ 7. merge + fcc + mix + loss + attention
+// blockIdx.x = bag.  Every block of a bag derives each class's {max, sum} from the bag's partials in the same fixed order.  blockIdx.y = 0:
+// B (thread e = column e, partials in index order), the fcc head in fp32, the mix, the cross entropy.  blockIdx.y > 0: the instance score
+// max_c A[m,c] (no_norm: max_c a[m,c]).
+template <int CT>
+__global__ __launch_bounds__(DF_T) void dsmil_finalize_kernel(InferTab tab, const float* __restrict__ pm, const float* __restrict__ pl,
+                                                              const float* __restrict__ pB, const float* __restrict__ Q,
+                                                              const float* __restrict__ qmax, const float* __restrict__ wfcc,
+                                                              const float* __restrict__ bfcc, int C, int no_norm,
+                                                              const int64_t* __restrict__ labels, const float* __restrict__ logits_ins,
+                                                              float* __restrict__ logits_bag, float* __restrict__ logits,
+                                                              float* __restrict__ B_out, float* __restrict__ attn, float* __restrict__ loss) {
+  __shared__ float red[8];
+  __shared__ float wgt[DF_T];
+  __shared__ float smx[CT], sinv[CT];
+  __shared__ float lg[DS_MAXC];
+  __shared__ __attribute__((aligned(16))) float big[CT * IE];  // y = 0: B [C][512]; y > 0: q_max [CT][128]
+  const int bag = blockIdx.x;
+  int64_t N = tab.N[0], orow0 = tab.row0[0];
+  int p0 = tab.part0[0];
+  IT_PICK(N, N, bag) IT_PICK(orow0, row0, bag) IT_PICK(p0, part0, bag)
+  const int G = (int)((N + DR_CHUNK - 1) / DR_CHUNK);
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  pm += (int64_t)p0 * DS_MAXC; pl += (int64_t)p0 * DS_MAXC; pB += (int64_t)p0 * C * IE;
+  for (int c = 0; c < C; ++c) {
+    float m = -INFINITY;
+    for (int b = tid; b < G; b += DF_T) m = fmaxf(m, pm[(int64_t)b * DS_MAXC + c]);
+    m = wave_max(m);
+    if (lane == 0) red[wave] = m;
+    __syncthreads();
+    float mx = red[0];
+#pragma unroll
+    for (int w = 1; w < 8; ++w) mx = fmaxf(mx, red[w]);
+    __syncthreads();
+    float lp = 0.f;
+    for (int b = tid; b < G; b += DF_T) lp += pl[(int64_t)b * DS_MAXC + c] * __expf(pm[(int64_t)b * DS_MAXC + c] - mx);
+    lp = wave_sum(lp);
+    if (lane == 0) red[wave] = lp;
+    __syncthreads();
+    float Ls = 0.f;
+#pragma unroll
+    for (int w = 0; w < 8; ++w) Ls += red[w];                 // fixed order: deterministic
+    if (tid == 0) { smx[c] = mx; sinv[c] = 1.f / Ls; }
+    __syncthreads();
+  }
+  if (blockIdx.y > 0) {
+    if (!attn) return;
+    for (int i = tid; i < CT * DQ; i += DF_T) big[i] = (i >> 7) < C ? qmax[(int64_t)bag * DS_MAXC * DQ + i] : 0.f;
+    __syncthreads();
+    float mxr[CT], ivr[CT];
+#pragma unroll
+    for (int c = 0; c < CT; ++c) { mxr[c] = c < C ? smx[c] : 0.f; ivr[c] = c < C ? sinv[c] : 0.f; }
+    float* ab = attn + orow0;
+    const int64_t step = (int64_t)(gridDim.y - 1) * DF_T;
+    for (int64_t r = (int64_t)(blockIdx.y - 1) * DF_T + tid; r < N; r += step) {
+      float a[CT];
+      ds_scores<CT>(Q + (orow0 + r) * DQ, big, a);
+      float best = -INFINITY;
+#pragma unroll
+      for (int c = 0; c < CT; ++c)
+        if (c < C) best = fmaxf(best, no_norm ? a[c] : __expf(a[c] - mxr[c]) * ivr[c]);
+      ab[r] = best;
+    }
+    return;
+  }
+  for (int c = 0; c < C; ++c) {
+    const float mx = smx[c];
+    float acc = 0.f;                                          // column tid of B[c]
+    for (int base = 0; base < G; base += DF_T) {
+      __syncthreads();
+      wgt[tid] = base + tid < G ? __expf(pm[(int64_t)(base + tid) * DS_MAXC + c] - mx) : 0.f;
+      __syncthreads();
+      const int cnt = G - base < DF_T ? G - base : DF_T;
+#pragma unroll 8
+      for (int j = 0; j < cnt; ++j) acc += pB[((int64_t)(base + j) * C + c) * IE + tid] * wgt[j];
+    }
+    const float bv = acc * sinv[c];
+    big[c * IE + tid] = bv;
+    if (B_out) B_out[((int64_t)bag * C + c) * IE + tid] = bv;
+  }
+  __syncthreads();
+  // fcc: Conv1d(C, C, kernel = E) on [1, C, E] = a [C, C * E] dot
+  for (int o = wave; o < C; o += DF_T / 64) {
+    float d = 0.f;
+    for (int c = 0; c < C; ++c) {
+      const float* w = wfcc + ((int64_t)o * C + c) * IE;
+#pragma unroll
+      for (int q = 0; q < IE / 64; ++q) d += big[c * IE + lane + 64 * q] * w[lane + 64 * q];
+    }
+    d = wave_sum(d);
+    if (lane == 0) {
+      const float lb = d + bfcc[o];
+      const float mix = 0.5f * lb + 0.5f * logits_ins[(int64_t)bag * C + o];
+      logits_bag[(int64_t)bag * C + o] = lb;
+      logits[(int64_t)bag * C + o] = mix;
+      lg[o] = mix;
+    }
+  }
+  if (!loss) return;
+  __syncthreads();
+  if (tid == 0) {
+    // torch.nn.CrossEntropyLoss on one row: log sum_c e^{x_c} - x_label (a label outside [0, C): NaN, where torch raises)
+    float cm = lg[0];
+    for (int c = 1; c < C; ++c) cm = fmaxf(cm, lg[c]);
+    float den = 0.f;
+    for (int c = 0; c < C; ++c) den += expf(lg[c] - cm);
+    const int64_t y = labels[bag];
+    loss[bag] = (y >= 0 && y < C) ? (cm + logf(den)) - lg[y] : NAN;
+  }
+}
+
+// ------------------------------------------------------------------------------------------------ host
+struct DsmilWs { int64_t w1p, vp, q0f, q2f, H, V, Q, cls, pmax, parg, qmax, pm, pl, pB, total; };
+
+// the checks of mhimx_infer_run_x on the bag table and the element type (infer.hip: check_infer), and this call's own shape rules
+int check_dsmil(const mhimx_infer_dsmil_cfg* c, int32_t n_bags, const mhimx_infer_bag* bags, int32_t xdt) {
+  MHIMX_CHECK_ARG(xdt >= MHIMX_X_F32 && xdt <= MHIMX_X_BF16, "infer_dsmil: x_dtype %d is none of MHIMX_X_F32 / F16 / BF16", xdt);
+  MHIMX_CHECK_ARG(c && bags, "infer_dsmil: null configuration / bag list");
+  MHIMX_CHECK_ARG(n_bags >= 1 && n_bags <= MHIMX_INFER_MAX, "infer_dsmil: 1..%d bags per call (got %d)", MHIMX_INFER_MAX, n_bags);
+  MHIMX_CHECK_ARG(c->E == IE && c->C >= 1 && c->C <= DS_MAXC && c->D > 0 && c->D % 256 == 0 && c->D <= (1 << 20),
+                  "infer_dsmil: shapes outside the ragged DSMIL forward (E = 512, q width 128, 1 <= C <= %d, D %% 256 == 0)", DS_MAXC);
+  MHIMX_CHECK_ARG(c->act >= MHIMX_ACT_NONE && c->act <= MHIMX_ACT_TANH, "infer_dsmil: unknown activation");
+  int64_t rows = 0;
+  for (int b = 0; b < n_bags; ++b) {
+    const mhimx_infer_bag& g = bags[b];
+    MHIMX_CHECK_ARG(g.N >= 1 && g.N <= MHIMX_INFER_MAX_ROWS, "infer_dsmil: bag %d: N must be in 1..%d", b, MHIMX_INFER_MAX_ROWS);
+    if (xdt == MHIMX_X_F32)
+      MHIMX_CHECK_ARG(g.ldx >= c->D && g.ldx % 4 == 0 && g.ldx <= (1 << 20),
+                      "infer_dsmil: bag %d: row pitch below D or not a multiple of 4 floats", b);
+    else
+      MHIMX_CHECK_ARG(g.ldx >= c->D && g.ldx % 8 == 0 && g.ldx <= (1 << 20),
+                      "infer_dsmil: bag %d: row pitch below D or not a multiple of 8 two-byte elements", b);
+    rows += g.N;
+  }
+  MHIMX_CHECK_ARG(rows <= MHIMX_INFER_MAX_ROWS, "infer_dsmil: more than %d rows in one call", MHIMX_INFER_MAX_ROWS);
+  return 0;
+}
+
+void dsmil_layout(const mhimx_infer_dsmil_cfg* c, int32_t n_bags, const mhimx_infer_bag* bags, DsmilWs* w, InferTab* tab) {
+  int64_t rows = 0, tiles = 0, parts = 0;
+  for (int b = 0; b < n_bags; ++b) {
+    if (tab) {
+      tab->X[b] = bags[b].X; tab->ldx[b] = bags[b].ldx; tab->N[b] = bags[b].N;
+      tab->row0[b] = rows; tab->tile0[b] = (int32_t)tiles; tab->part0[b] = (int32_t)parts;
+    }
+    rows += bags[b].N;
+    tiles += cdiv(bags[b].N, INFER_TILE_ROWS);
+    parts += cdiv(bags[b].N, DR_CHUNK);
+  }
+  if (tab) { tab->n = n_bags; tab->tiles = (int32_t)tiles; tab->parts = (int32_t)parts; }
+  Arena ar(nullptr, 0);
+  w->w1p = ar.off; ar.take<float>(c->E * c->D);
+  w->vp = ar.off; ar.take<float>(c->E * c->E);
+  w->q0f = ar.off; ar.take<float>(DQ * c->E);
+  w->q2f = ar.off; ar.take<float>(DQ * DQ);
+  w->H = ar.off; ar.take<float>(rows * c->E);
+  w->V = ar.off; ar.take<float>(rows * c->E);
+  w->Q = ar.off; ar.take<float>(rows * DQ);
+  w->cls = ar.off; ar.take<float>(rows * DS_MAXC);
+  w->pmax = ar.off; ar.take<float>(parts * DS_MAXC);
+  w->parg = ar.off; ar.take<int32_t>(parts * DS_MAXC);
+  w->qmax = ar.off; ar.take<float>((int64_t)n_bags * DS_MAXC * DQ);
+  w->pm = ar.off; ar.take<float>(parts * DS_MAXC);
+  w->pl = ar.off; ar.take<float>(parts * DS_MAXC);
+  w->pB = ar.off; ar.take<float>(parts * c->C * c->E);
+  w->total = ar.off;
+}
+
+template <int CT>
+int dsmil_tail(hipStream_t st, const InferTab& tab, const mhimx_infer_dsmil_cfg* cfg, const float* Q, const float* V, const float* qmax, float* pm,
+               float* pl, float* pB, const int64_t* labels, const float* logits_ins, const mhimx_infer_dsmil_out* out, bool attn_blocks) {
+  const int C = (int)cfg->C;
+  hipLaunchKernelGGL(dsmil_pool_kernel<CT>, dim3((unsigned)tab.parts), dim3(DP_THREADS), 0, st, tab, Q, V, qmax, C, pm, pl, pB);
+  MHIMX_LAUNCH_CHECK();
+  hipLaunchKernelGGL(dsmil_finalize_kernel<CT>, dim3((unsigned)tab.n, attn_blocks ? 1 + DF_ATTN_BLOCKS : 1), dim3(DF_T), 0, st, tab, pm, pl, pB, Q,
+                     qmax, cfg->wfcc, cfg->bfcc, C, (int)(cfg->no_norm != 0), labels, logits_ins, out->logits_bag, out->logits, out->B,
+                     attn_blocks ? out->attn : nullptr, out->loss);
+  MHIMX_LAUNCH_CHECK();
+  return 0;
+}
+
+}  // namespace
+
+}  // namespace mhimx
+
+extern "C" int64_t mhimx_infer_dsmil_ws_bytes(const mhimx_infer_dsmil_cfg* cfg, int32_t n_bags, const mhimx_infer_bag* bags) {
+  using namespace mhimx;
+  if (int r = check_dsmil(cfg, n_bags, bags, MHIMX_X_F32)) return r;
+  DsmilWs w;
+  dsmil_layout(cfg, n_bags, bags, &w, nullptr);
+  return w.total;
+}
+
+extern "C" int mhimx_infer_dsmil_run(void* stream, const mhimx_infer_dsmil_cfg* cfg, int32_t n_bags, const mhimx_infer_bag* bags,
+                                     const int64_t* labels_dev, const mhimx_infer_dsmil_out* out, void* ws, int64_t ws_bytes,
+                                     int32_t x_dtype) {
+  using namespace mhimx;
+  if (int r = check_dsmil(cfg, n_bags, bags, x_dtype)) return r;
+  MHIMX_CHECK_ARG(cfg->w1 && cfg->b1 && cfg->wi && cfg->bi && cfg->wq0 && cfg->bq0 && cfg->wq2 && cfg->bq2 && cfg->wv && cfg->bv && cfg->wfcc &&
+                      cfg->bfcc,
+                  "infer_dsmil: null parameter");
+  MHIMX_CHECK_ARG(aligned16(cfg->w1) && aligned16(cfg->b1) && aligned16(cfg->wi) && aligned16(cfg->wq0) && aligned16(cfg->wq2) &&
+                      aligned16(cfg->wv) && aligned16(cfg->bv),
+                  "infer_dsmil: the feature, i_classifier, q and v weights must be 16-byte aligned");
+  for (int b = 0; b < n_bags; ++b) MHIMX_CHECK_ARG(bags[b].X && aligned16(bags[b].X), "infer_dsmil: bag %d: null or unaligned rows", b);
+  MHIMX_CHECK_ARG(out && out->logits_bag && out->logits_ins && out->logits, "infer_dsmil: the three logits outputs are required");
+  MHIMX_CHECK_ARG(!out->loss || labels_dev, "infer_dsmil: the loss output needs labels");
+  DsmilWs w;
+  InferTab tab = {};
+  dsmil_layout(cfg, n_bags, bags, &w, &tab);
+  tab.pad = x_dtype;                           // read by the first projection launch alone: the only reader of X
+  MHIMX_CHECK_ARG(ws && (reinterpret_cast<uintptr_t>(ws) & 255) == 0, "infer_dsmil: the workspace must be 256-byte aligned");
+  MHIMX_CHECK_ARG(ws_bytes >= w.total, "infer_dsmil: workspace too small (%lld bytes, need %lld)", (long long)ws_bytes, (long long)w.total);
+  hipStream_t st = (hipStream_t)stream;
+  char* base = static_cast<char*>(ws);
+  auto F = [&](int64_t off) { return reinterpret_cast<float*>(base + off); };
+  float *w1p = F(w.w1p), *vp = F(w.vp), *q0f = F(w.q0f), *q2f = F(w.q2f), *H = F(w.H), *V = F(w.V), *Q = F(w.Q), *cls = F(w.cls);
+  float *pmax = F(w.pmax), *qmax = F(w.qmax), *pm = F(w.pm), *pl = F(w.pl), *pB = F(w.pB);
+  int32_t* parg = reinterpret_cast<int32_t*>(base + w.parg);
+  const int D = (int)cfg->D, C = (int)cfg->C;
+
+  // 1. weight images
+  mhimx_prep_job jobs[4] = {mhimx_prep_job{1, cfg->w1, w1p, cfg->E, cfg->D}, mhimx_prep_job{1, cfg->wv, vp, cfg->E, cfg->E},
+                            mhimx_prep_job{4, cfg->wq0, q0f, DQ, cfg->E}, mhimx_prep_job{4, cfg->wq2, q2f, DQ, DQ}};
+  if (int r = mhimx_prep_batch(stream, jobs, 4)) return r;
+  // 2. feature rows of every bag (bag_project.hip)
+  if (int r = infer_project(st, tab, D, w1p, cfg->b1, cfg->act, H)) return r;
+  // 3. V = relu(h Wv^T + bv): the same launch over the feature rows as fp32 "bags" of pitch 512
+  InferTab tabv = tab;
+  for (int b = 0; b < n_bags; ++b) { tabv.X[b] = H + tab.row0[b] * IE; tabv.ldx[b] = IE; }
+  tabv.pad = MHIMX_X_F32;
+  if (int r = infer_project(st, tabv, IE, vp, cfg->bv, MHIMX_ACT_RELU, V)) return r;
+  // 4. Q, classes, arg-max partials (the instance score too when it is max_c classes)
+  MHIMX_ONCE_PER_DEVICE(MHIMX_HIP(hipFuncSetAttribute((const void*)dsmil_rows_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)DR_SMEM)));
+  hipLaunchKernelGGL(dsmil_rows_kernel, dim3((unsigned)tab.parts), dim3(DR_THREADS), DR_SMEM, st, tab, H, q0f, cfg->bq0, q2f, cfg->bq2, cfg->wi,
+                     cfg->bi, C, Q, cls, cfg->cls_attn ? out->attn : nullptr, pmax, parg);
+  MHIMX_LAUNCH_CHECK();
+  // 5. critical rows, max-instance logits, q_max
+  hipLaunchKernelGGL(dsmil_crit_kernel, dim3((unsigned)n_bags), dim3(256), 0, st, tab, pmax, parg, Q, C, qmax, out->logits_ins, out->crit);
+  MHIMX_LAUNCH_CHECK();
+  // 6. + 7. pool partials; merge, fcc, mix, loss, attention
+  const bool attn_blocks = out->attn && !cfg->cls_attn;
+  if (C <= 2) return dsmil_tail<2>(st, tab, cfg, Q, V, qmax, pm, pl, pB, labels_dev, out->logits_ins, out, attn_blocks);
+  if (C <= 4) return dsmil_tail<4>(st, tab, cfg, Q, V, qmax, pm, pl, pB, labels_dev, out->logits_ins, out, attn_blocks);
+  if (C <= 8) return dsmil_tail<8>(st, tab, cfg, Q, V, qmax, pm, pl, pB, labels_dev, out->logits_ins, out, attn_blocks);
+  return dsmil_tail<16>(st, tab, cfg, Q, V, qmax, pm, pl, pB, labels_dev, out->logits_ins, out, attn_blocks);
+}

@@ -108,12 +108,13 @@ class CommonMIL:
 
 
     def validate_many(self, args, model, bags, labels, criterion=None):
-        """validate_func for a LIST of bags -> (logits [n, C], per-bag cross entropy [n] | None).  The MHIM(ABMIL) models go through
-        MHIM.infer_many (one C call per chunk of bags where the model qualifies, the forward_test loop where it does not); the loss comes
-        back only for a plain CrossEntropyLoss - any other criterion is the caller's to apply to the logits."""
+        """validate_func for a LIST of bags -> (logits [n, C], per-bag cross entropy [n] | None).  The MHIM models go through
+        MHIM.infer_many (one C call per chunk of bags where the model qualifies - ABMIL and DSMIL -, the forward_test loop where it does
+        not; for DSMIL the logits are validate_func's 0.5 / 0.5 mix either way); the loss comes back only for a plain CrossEntropyLoss -
+        any other criterion is the caller's to apply to the logits."""
         if args.model not in ("mhim", "mhim_pure"):
             raise NotImplementedError(f"model {args.model!r} is outside the MHIM hot path")
-        if getattr(args, "baseline", "attn") == "dsmil" or not hasattr(model, "infer_many"):
+        if not hasattr(model, "infer_many"):
             rows = [self.validate_func(args, model=model, bag=b, label=labels[j:j + 1], criterion=criterion, batch_size=1, i=j, pos=None)[0]
                     for j, b in enumerate(bags)]
             return torch.cat([r.reshape(1, -1) for r in rows]), None

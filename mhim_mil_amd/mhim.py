@@ -949,20 +949,33 @@ class MHIM(nn.Module):
         return out
 
     def _infer_ok(self, xs):
-        """True when mhimx_infer_run_x takes these bags (csrc/infer.hip: check_infer and the call's own argument checks, mirrored: what they
-        would refuse takes the forward_test loop instead of raising).  One dtype per call - fp32, fp16 or bf16; the row pitch of a 2-byte
-        bag is a multiple of 8 elements (16-byte rows)."""
-        if (self.training or self.baseline != "attn" or self.online_encoder.gated or self.merge_test or self._op_prec == "f32"
-                or ops.KERNEL_EVENT_HOOK is not None):
-            return False
-        att = self.online_encoder.attention.attention
-        if not (self.mlp_dim == 512 and att[0].weight.shape[0] == 128 and 1 <= self.n_classes <= 16 and self.input_dim % 256 == 0
-                and self.input_dim <= (1 << 20)):
+        """True when mhimx_infer_run_x (ABMIL) / mhimx_infer_dsmil_run (DSMIL) takes these bags (csrc/infer.hip: check_infer,
+        csrc/infer_dsmil.hip: check_dsmil, and the calls' own argument checks, mirrored: what they would refuse takes the forward_test loop
+        instead of raising).  One dtype per call - fp32, fp16 or bf16; the row pitch of a 2-byte bag is a multiple of 8 elements (16-byte
+        rows)."""
+        if self.training or self.merge_test or self._op_prec == "f32" or ops.KERNEL_EVENT_HOOK is not None:
             return False
         dev = self.feature[0].weight.device
-        ps = (self.feature[0].weight, self.feature[0].bias, att[0].weight, att[2].weight, self.predictor.weight, self.predictor.bias)
-        if any(not t.is_contiguous() or t.dtype != torch.float32 or t.device != dev for t in ps) or any(t.data_ptr() % 16 for t in ps[:3]):
-            return False
+        if self.baseline == "dsmil":                            # mhimx_infer_dsmil_run (csrc/infer_dsmil.hip: check_dsmil), mirrored
+            if not (self.mlp_dim == 512 and DS.QDIM == 128 and 1 <= self.n_classes <= 16 and self.input_dim % 256 == 0
+                    and self.input_dim <= (1 << 20)):
+                return False
+            ps = self._infer_dsmil_params()
+            if tuple(ps[4].shape) != (128, 512) or tuple(ps[6].shape) != (128, 128) or tuple(ps[8].shape) != (512, 512):
+                return False
+            if (any(not t.is_contiguous() or t.dtype != torch.float32 or t.device != dev for t in ps)
+                    or any(ps[j].data_ptr() % 16 for j in (0, 1, 2, 4, 6, 8, 9))):
+                return False
+        else:
+            if self.baseline != "attn" or self.online_encoder.gated:
+                return False
+            att = self.online_encoder.attention.attention
+            if not (self.mlp_dim == 512 and att[0].weight.shape[0] == 128 and 1 <= self.n_classes <= 16 and self.input_dim % 256 == 0
+                    and self.input_dim <= (1 << 20)):
+                return False
+            ps = (self.feature[0].weight, self.feature[0].bias, att[0].weight, att[2].weight, self.predictor.weight, self.predictor.bias)
+            if any(not t.is_contiguous() or t.dtype != torch.float32 or t.device != dev for t in ps) or any(t.data_ptr() % 16 for t in ps[:3]):
+                return False
         kinds = {x.dtype for x in xs}
         if len(kinds) != 1 or not kinds <= {torch.float32, torch.float16, torch.bfloat16}:
             return False
@@ -977,12 +990,33 @@ class MHIM(nn.Module):
                           act=L.act_code(self.act, _FEATURE_ACTS), da_act=L.act_code(self.da_act, _SCORER_ACTS),
                           p=ops.infer_params(f.weight.data, f.bias.data, att[0].weight.data, att[2].weight.data, pr.weight.data, pr.bias.data))
 
+    def _infer_dsmil_params(self):
+        """The twelve tensors of mhimx_infer_dsmil_cfg, in its order."""
+        f, enc = self.feature[0], self.online_encoder
+        ic, bc = enc.i_classifier[0], enc.b_classifier
+        return (f.weight.data, f.bias.data, ic.weight.data, ic.bias.data, bc.q[0].weight.data, bc.q[0].bias.data, bc.q[2].weight.data,
+                bc.q[2].bias.data, bc.v[1].weight.data, bc.v[1].bias.data, bc.fcc.weight.data, bc.fcc.bias.data)
+
+    def _infer_dsmil_cfg(self, no_norm=False):
+        return ops.infer_dsmil_cfg(self.input_dim, self.mlp_dim, self.n_classes, L.act_code(self.act, _FEATURE_ACTS),
+                                   self.online_encoder.cls_attn, no_norm, self._infer_dsmil_params())
+
+    def infer_rows_per_call(self):
+        """Row cap of one native call.  ABMIL: ``infer_row_cap`` (its workspace: 2060 bytes per row).  DSMIL keeps h, V, Q and the classes
+        of every row (4673 + 8 C bytes per row with the per-chunk partials) and two more weight images: its cap is the row count whose
+        workspace is no larger than the ABMIL call's at ``infer_row_cap`` - a little under half of it."""
+        if getattr(self, "baseline", "attn") != "dsmil":
+            return self.infer_row_cap
+        return max(1, (self.infer_row_cap * 2060 - (4 << 20)) // (4673 + 8 * self.n_classes))   # (4 MiB: images, 32 bags' last chunks)
+
     def infer_chunks(self, xs):
-        """Index ranges of the calls ``infer_many`` makes: at most L.INFER_MAX bags and ``infer_row_cap`` rows each (one bag at least)."""
+        """Index ranges of the calls ``infer_many`` makes: at most L.INFER_MAX bags and ``infer_rows_per_call()`` rows each (one bag at
+        least)."""
         chunks, lo, rows = [], 0, 0
+        cap = self.infer_rows_per_call()
         for j, x in enumerate(xs):
             n = int(x.shape[0])
-            if j > lo and (j - lo >= L.INFER_MAX or rows + n > self.infer_row_cap):
+            if j > lo and (j - lo >= L.INFER_MAX or rows + n > cap):
                 chunks.append((lo, j))
                 lo, rows = j, 0
             rows += n
@@ -996,7 +1030,10 @@ class MHIM(nn.Module):
         attention vectors [N_b] (raw scorer outputs with ``no_norm``), with ``labels`` (int64 [n], device) also the per-bag cross
         entropy [n]: ``logits`` | ``(logits, attn)`` | ``(logits, loss)`` | ``(logits, attn, loss)``.
         An eval-mode plain-ABMIL model without merge_test takes mhimx_infer_run_x - one C call (four launches) per chunk of bags, see
-        ``infer_chunks``; anything else loops over forward_test.  ``self.last["infer_native"]`` says which route ran.
+        ``infer_chunks``; an eval-mode DSMIL model without merge_test takes mhimx_infer_dsmil_run (seven launches per chunk) and returns
+        the MIXED logits 0.5 * bag + 0.5 * max-instance of validate_func, with ``self.last["infer_parts"] = (logits_bag, logits_ins, B)``
+        and the DSMIL instance score as the attention; anything else loops over forward_test (DSMIL: the same mix).
+        ``self.last["infer_native"]`` says which route ran.
         A list of fp16 bags, or of bf16 bags, that the native route takes goes in as it is (no widened copy; same bits as on the widened
         bags); a list of mixed dtypes, and every model outside the native route, gets ``x.float()`` first."""
         xs = self._infer_bags(xs, keep_half=True)
@@ -1009,7 +1046,42 @@ class MHIM(nn.Module):
                 raise L.MhimxError(f"MHIM.infer_many: {labels.numel()} labels for {n} bags")
         native = n > 0 and self._infer_ok(xs)
         attns = []
-        if native:
+        if self.baseline == "dsmil":
+            # the MIXED logits 0.5 * bag + 0.5 * max-instance (what validate_func makes of forward_test's pair, common_mil.py:66-67);
+            # the pair itself and B: self.last["infer_parts"]
+            if native:
+                cfg = self._infer_dsmil_cfg(no_norm)
+                chunks = self.infer_chunks(xs)
+                rs = []
+                for lo, hi in chunks:
+                    r = ops.infer_dsmil_many(cfg, xs[lo:hi], labels=None if labels is None else labels[lo:hi].contiguous(),
+                                             want_attn=return_attn, want_B=True)
+                    rs.append(r)
+                    if return_attn:
+                        attns += [r.attn[r.offsets[j]:r.offsets[j + 1]] for j in range(hi - lo)]
+                self._step += n                   # (the stream position the forward_test loop leaves behind: one seed per bag)
+                cat = lambda ts: ts[0] if len(ts) == 1 else torch.cat(ts)
+                logits = cat([r.logits for r in rs])
+                loss = None if labels is None else cat([r.loss for r in rs])
+                self.last = {"infer_native": True, "infer_calls": len(chunks),
+                             "infer_parts": (cat([r.logits_bag for r in rs]), cat([r.logits_ins for r in rs]), cat([r.B for r in rs]))}
+            else:
+                lb, li, Bs = [], [], []
+                for x in xs:
+                    o = self.forward_test(x, return_attn=return_attn, no_norm=no_norm)
+                    lb.append(o[0][0].reshape(1, -1))
+                    li.append(o[0][1].reshape(1, -1))
+                    if return_attn:
+                        attns.append(o[1].reshape(-1))
+                    else:
+                        Bs.append(o[1])
+                dev = self.feature[0].weight.device
+                lb = torch.cat(lb) if lb else torch.empty((0, self.n_classes), device=dev)
+                li = torch.cat(li) if li else torch.empty((0, self.n_classes), device=dev)
+                logits = 0.5 * lb + 0.5 * li
+                loss = None if labels is None else torch.nn.functional.cross_entropy(logits, labels, reduction="none")
+                self.last = {"infer_native": False, "infer_calls": 0, "infer_parts": (lb, li, torch.cat(Bs) if Bs else None)}
+        elif native:
             cfg = self._infer_cfg()
             chunks = self.infer_chunks(xs)
             lg, ls = [], []
@@ -1029,8 +1101,6 @@ class MHIM(nn.Module):
             lg = []
             for x in xs:
                 o = self.forward_test(x, return_attn=return_attn, no_norm=no_norm)
-                if self.baseline == "dsmil":
-                    raise L.MhimxError("MHIM.infer_many: DSMIL returns two logit rows per bag; use forward_test")
                 if return_attn:
                     lg.append(o[0].reshape(1, -1))
                     attns.append(o[1].reshape(-1) if torch.is_tensor(o[1]) else o[1])

@@ -1024,6 +1024,75 @@ def infer_many(cfg, xs, labels=None, want_attn=False, want_score=False, want_z=F
     return r
 
 
+class InferDsmilResult:
+    """Outputs of one mhimx_infer_dsmil_run: logits_bag / logits_ins / logits (their 0.5 / 0.5 mix) [n, C], B [n, C, E] or None, crit
+    int64 [n, C] or None, attn [sum N] (bag b's rows at offsets[b] .. offsets[b + 1]) or None, loss [n] or None."""
+    __slots__ = ("logits_bag", "logits_ins", "logits", "B", "crit", "attn", "loss", "offsets")
+
+
+_DSMIL_PARAMS = ("w1", "b1", "wi", "bi", "wq0", "bq0", "wq2", "bq2", "wv", "bv", "wfcc", "bfcc")
+
+
+def infer_dsmil_cfg(D, E, Cc, act, cls_attn, no_norm, params):
+    """mhimx_infer_dsmil_cfg; ``params``: the twelve tensors in the order feature.0.{weight, bias}, i_classifier.0.*, b_classifier.q.0.*,
+    q.2.*, v.1.*, fcc.* (kept alive by the caller)."""
+    if len(params) != len(_DSMIL_PARAMS):
+        raise L.MhimxError(f"infer_dsmil_cfg: {len(_DSMIL_PARAMS)} parameter tensors, got {len(params)}")
+    for n, t in zip(_DSMIL_PARAMS, params):
+        _chk(t, name=n)
+    return L.InferDsmilCfg(D=int(D), E=int(E), C=int(Cc), act=int(act), cls_attn=int(bool(cls_attn)), no_norm=int(bool(no_norm)),
+                           **{n: t.data_ptr() for n, t in zip(_DSMIL_PARAMS, params)})
+
+
+def infer_dsmil_ws_bytes(cfg, xs):
+    """mhimx_infer_dsmil_ws_bytes for the bags ``xs`` ([N, D] each): host arithmetic only."""
+    bags = (L.InferBag * max(len(xs), 1))(*[L.InferBag(X=x.data_ptr(), ldx=x.stride(0), N=x.shape[0]) for x in xs])
+    return L.lib().mhimx_infer_dsmil_ws_bytes(C.byref(cfg), len(xs), bags)
+
+
+def infer_dsmil_many(cfg, xs, labels=None, want_attn=False, want_B=False, want_crit=False, ws=None):
+    """The eval-mode MHIM(DSMIL) forward of up to L.INFER_MAX bags of different row counts in ONE C call (mhimx_infer_dsmil_run).
+    cfg: L.InferDsmilCfg (its parameter tensors are kept alive by the caller); xs, labels, ws: as ``infer_many`` takes them (half bags are
+    read where they lie; the workspace cache is shared with it)."""
+    n = len(xs)
+    xdt = x_dtype_of(xs, "infer_dsmil_many")
+    for x in xs:
+        if not (torch.is_tensor(x) and x.is_cuda and x.dim() == 2 and x.stride(1) == 1):
+            raise L.MhimxError("infer_dsmil_many: every bag must be a GPU fp32 / fp16 / bf16 matrix [N, D] with unit column stride")
+    _chk(labels, torch.int64, "labels")
+    if labels is not None and labels.numel() != n:
+        raise L.MhimxError(f"infer_dsmil_many: {labels.numel()} labels for {n} bags")
+    bags = (L.InferBag * max(n, 1))(*[L.InferBag(X=x.data_ptr(), ldx=x.stride(0), N=x.shape[0]) for x in xs])
+    need = L.lib().mhimx_infer_dsmil_ws_bytes(C.byref(cfg), n, bags)
+    if need < 0:
+        L.check(int(need), "mhimx_infer_dsmil_ws_bytes")
+    dev = xs[0].device
+    if ws is None:
+        if torch.cuda.is_current_stream_capturing():
+            ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        else:
+            ws = _INFER_WS.get(dev.index)
+            if ws is None or ws.numel() < need:
+                ws = _INFER_WS[dev.index] = torch.full((need,), 255, dtype=torch.uint8, device=dev)
+    r = InferDsmilResult()
+    r.offsets = [0]
+    for x in xs:
+        r.offsets.append(r.offsets[-1] + int(x.shape[0]))
+    Cc, E = int(cfg.C), int(cfg.E)
+    r.logits_bag = torch.empty((n, Cc), device=dev)
+    r.logits_ins = torch.empty((n, Cc), device=dev)
+    r.logits = torch.empty((n, Cc), device=dev)
+    r.B = torch.empty((n, Cc, E), device=dev) if want_B else None
+    r.crit = torch.empty((n, Cc), device=dev, dtype=torch.int64) if want_crit else None
+    r.attn = torch.empty(r.offsets[-1], device=dev) if want_attn else None
+    r.loss = torch.empty(n, device=dev) if labels is not None else None
+    out = L.InferDsmilOut(logits_bag=_p(r.logits_bag), logits_ins=_p(r.logits_ins), logits=_p(r.logits), B=_p(r.B), crit=_p(r.crit),
+                          attn=_p(r.attn), loss=_p(r.loss))
+    L.check(L.lib().mhimx_infer_dsmil_run(_stream(), C.byref(cfg), n, bags, _p(labels), C.byref(out), _p(ws), ws.numel(), xdt),
+            "mhimx_infer_dsmil_run")
+    return r
+
+
 # ------------------------------------------------------------------------------------------- ragged pure accumulation window
 def pure_window_bags(xs, labels, seeds):
     """The by-value bag table of mhimx_pure_window_run(_x): xs [N_b, D] GPU matrices with unit column stride - all fp32, all fp16 or all
