@@ -85,7 +85,7 @@ MHIMX_DEV void infer_project_body(const InferTab& tab, int D, const float* __res
   const float* X = tab.X[0];
   int64_t ldx = tab.ldx[0], N = tab.N[0], orow0 = tab.row0[0];
   int t0 = tab.tile0[0];
-  IT_PICK(X, X, bag) IT_PICK(ldx, ldx, bag) IT_PICK(N, N, bag) IT_PICK(orow0, row0, bag) IT_PICK(t0, tile0, bag)
+  RG_PICK(X, tab.X, bag) RG_PICK(ldx, tab.ldx, bag) RG_PICK(N, tab.N, bag) RG_PICK(orow0, tab.row0, bag) RG_PICK(t0, tab.tile0, bag)
   const int64_t m0 = (int64_t)(m_tile - t0) * IBM;             // first row of the tile inside its bag
   const int64_t n0 = (int64_t)n_tile * IBN;
   typedef typename XRow<XT>::elt XE;

@@ -33,51 +33,11 @@ namespace mhimx {
 namespace {
 
 constexpr int DQ = 128, DS_MAXC = 16;
-constexpr int DR_ROWS = 32, DR_CHUNK = 256, DR_LD = IE + 4, DR_ULD = DQ + 4, DR_THREADS = 256;
-constexpr size_t DR_SMEM = (size_t)(DR_ROWS * DR_LD + DR_ROWS * DS_MAXC) * sizeof(float);
-constexpr int DP_THREADS = 256, DF_T = 512, DF_ATTN_BLOCKS = 8;
+constexpr int DR_ULD = DQ + 4;
+constexpr size_t DR_SMEM = (size_t)(RG_ROWS * RG_LD + RG_ROWS * DS_MAXC) * sizeof(float);
+constexpr int DP_THREADS = 256, DF_ATTN_BLOCKS = 8;
 constexpr float DS_SCALE = 0.08838834764831845f;   // 1 / sqrt(128)
-static_assert(DR_ROWS * DR_ULD <= DR_ROWS * DR_LD, "the U1 tile reuses the feature tile's LDS");
-
-typedef __bf16 ds_b8 __attribute__((ext_vector_type(8)));
-typedef float ds_f16 __attribute__((ext_vector_type(16)));
-
-MHIMX_DEV void ds_split(const f32x4& a, const f32x4& b, ds_b8& hi, ds_b8& lo) {
-  const float x[8] = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    const __bf16 h = (__bf16)x[i];
-    hi[i] = h;
-    lo[i] = (__bf16)(x[i] - (float)h);
-  }
-}
-
-// acc += A[32 rows of LDS, K] B^T for one wave's 32 columns: v_mfma_f32_32x32x16_bf16, A split on the fly, B a prep kind-4 image
-// (infer_score_kernel's k loop); returns the three bf16x3 terms added.  aptr = tile + (lane & 31) * ld + 8 * (lane >> 5).
-template <int K>
-MHIMX_DEV ds_f16 ds_mma(const float* aptr, const f32x4* fptr) {
-  ds_f16 acc, acc2, acc3;
-#pragma unroll
-  for (int i = 0; i < 16; ++i) { acc[i] = 0.f; acc2[i] = 0.f; acc3[i] = 0.f; }
-  f32x4 bh = fptr[0], bl = fptr[1];
-#pragma unroll 4
-  for (int ks = 0; ks < K / 16; ++ks) {
-    const int kn = ks + 1 < K / 16 ? ks + 1 : ks;
-    const f32x4 nbh = fptr[128 * kn], nbl = fptr[128 * kn + 1];
-    const f32x4 a0 = *reinterpret_cast<const f32x4*>(aptr + 16 * ks), a1 = *reinterpret_cast<const f32x4*>(aptr + 16 * ks + 4);
-    ds_b8 ah, al;
-    ds_split(a0, a1, ah, al);
-    const ds_b8 bh8 = __builtin_bit_cast(ds_b8, bh), bl8 = __builtin_bit_cast(ds_b8, bl);
-    acc2 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh8, acc2, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh8, acc, 0, 0, 0);
-    acc3 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl8, acc3, 0, 0, 0);
-    bh = nbh;
-    bl = nbl;
-  }
-#pragma unroll
-  for (int i = 0; i < 16; ++i) acc[i] += acc2[i] + acc3[i];
-  return acc;
-}
+static_assert(RG_ROWS * DR_ULD <= RG_ROWS * RG_LD, "the U1 tile reuses the feature tile's LDS");
 
 // a[c] = Q[m,:] . q_max[c,:] / sqrt(128), fp32 in a fixed order (qs: [CT][128] in LDS; classes past C hold zeros).  The pool launch
 // and the attention blocks of the finalize launch share it: the same bits.
@@ -98,17 +58,9 @@ MHIMX_DEV void ds_scores(const float* __restrict__ qrow, const float* qs, float 
   for (int c = 0; c < CT; ++c) a[c] *= DS_SCALE;
 }
 
-#define DS_LOCATE_PART(part)                                        \
-  int bag = 0;                                                      \
-  _Pragma("unroll") for (int b = 1; b < MHIMX_INFER_MAX; ++b)       \
-    if (b < tab.n && (part) >= tab.part0[b]) bag = b;               \
-  int64_t N = tab.N[0], orow0 = tab.row0[0];                        \
-  int p0 = tab.part0[0];                                            \
-  IT_PICK(N, N, bag) IT_PICK(orow0, row0, bag) IT_PICK(p0, part0, bag)
-
 // ------------------------------------------------------------------------------------------------ 4. per-row Q, classes, arg-max partials
-// blockIdx.x = chunk of DR_CHUNK rows of ONE bag (the last chunk of a bag may be short).  Wave w owns columns [32 w, 32 w + 32) of U1 and of Q.
-__global__ __launch_bounds__(DR_THREADS, 2) void dsmil_rows_kernel(InferTab tab, const float* __restrict__ Hin, const float* __restrict__ q0_frag,
+// blockIdx.x = chunk of RG_CHUNK rows of ONE bag (the last chunk of a bag may be short).  Wave w owns columns [32 w, 32 w + 32) of U1 and of Q.
+__global__ __launch_bounds__(RG_T, 2) void dsmil_rows_kernel(InferTab tab, const float* __restrict__ Hin, const float* __restrict__ q0_frag,
                                                                    const float* __restrict__ bq0, const float* __restrict__ q2_frag,
                                                                    const float* __restrict__ bq2, const float* __restrict__ wi,
                                                                    const float* __restrict__ bi, int C, float* __restrict__ Qout,
@@ -117,11 +69,11 @@ __global__ __launch_bounds__(DR_THREADS, 2) void dsmil_rows_kernel(InferTab tab,
   extern __shared__ __attribute__((aligned(16))) float dr_sm[];
   float* Hs = dr_sm;                          // [32][516] feature rows; then [32][132] U1 (the feature rows are dead by then)
   float* Us = dr_sm;
-  float* cs = Hs + DR_ROWS * DR_LD;           // [32][16] classes of the tile (rows past the chunk: -inf)
+  float* cs = Hs + RG_ROWS * RG_LD;           // [32][16] classes of the tile (rows past the chunk: -inf)
   const int part = blockIdx.x;
-  DS_LOCATE_PART(part)
-  const int64_t c0 = (int64_t)(part - p0) * DR_CHUNK;           // first row of the chunk inside its bag
-  const int64_t M = (N - c0 < DR_CHUNK) ? N - c0 : DR_CHUNK;    // rows of the chunk (>= 1)
+  RG_BAG_OF(part, part0)
+  const int64_t c0 = (int64_t)(part - p0) * RG_CHUNK;           // first row of the chunk inside its bag
+  const int64_t M = (N - c0 < RG_CHUNK) ? N - c0 : RG_CHUNK;    // rows of the chunk (>= 1)
   const float* T = Hin + (orow0 + c0) * IE;
   const int64_t grow0 = orow0 + c0;                             // first row of the chunk in the call's row space
 
@@ -135,27 +87,27 @@ __global__ __launch_bounds__(DR_THREADS, 2) void dsmil_rows_kernel(InferTab tab,
 
   float best = -INFINITY;                                       // threads < C: running (max, arg-max) of class tid over the chunk
   int arg = (int)c0;
-  const int tiles = (int)((M + DR_ROWS - 1) / DR_ROWS);
+  const int tiles = (int)((M + RG_ROWS - 1) / RG_ROWS);
   for (int tile = 0; tile < tiles; ++tile) {
-    const int64_t row0 = (int64_t)tile * DR_ROWS;
+    const int64_t row0 = (int64_t)tile * RG_ROWS;
     // ---- rows -> LDS (rows past the chunk: zeros; their loads are clamped so that all 16 are in flight)
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
-      const int f = tid + DR_THREADS * i, r = f >> 7, c4 = f & 127;
+      const int f = tid + RG_T * i, r = f >> 7, c4 = f & 127;
       const int64_t nr = row0 + r;
       f32x4 v = reinterpret_cast<const f32x4*>(T + (nr < M ? nr : M - 1) * IE)[c4];
       if (nr >= M) v = f32x4{0.f, 0.f, 0.f, 0.f};
-      *reinterpret_cast<f32x4*>(Hs + r * DR_LD + 4 * c4) = v;
+      *reinterpret_cast<f32x4*>(Hs + r * RG_LD + 4 * c4) = v;
     }
     __syncthreads();
     // ---- U1 tile on the matrix cores
-    const ds_f16 u1 = ds_mma<IE>(Hs + r32 * DR_LD + 8 * kg, f0);
+    const f32x16 u1 = rg_mma3<IE>(Hs + r32 * RG_LD + 8 * kg, f0);
     // ---- classes = h Wi^T + bi: lane `seg` takes the 16-byte groups seg, seg + 8, .. of the row, the 8 partial sums added in a fixed xor tree
     {
       float cp[DS_MAXC];
 #pragma unroll
       for (int c = 0; c < DS_MAXC; ++c) cp[c] = 0.f;
-      const f32x4* hr = reinterpret_cast<const f32x4*>(Hs + crow * DR_LD);
+      const f32x4* hr = reinterpret_cast<const f32x4*>(Hs + crow * RG_LD);
       const f32x4* w4 = reinterpret_cast<const f32x4*>(wi);
 #pragma unroll 2
       for (int g = 0; g < IE / 32; ++g) {
@@ -201,14 +153,14 @@ __global__ __launch_bounds__(DR_THREADS, 2) void dsmil_rows_kernel(InferTab tab,
       Us[row * DR_ULD + n_col] = u > 0.f ? u : 0.f;
     }
     if (tid < C) {                             // rows in index order, strictly greater: the lowest row wins on equal values
-      for (int r = 0; r < DR_ROWS; ++r) {
+      for (int r = 0; r < RG_ROWS; ++r) {
         const float v = cs[r * DS_MAXC + tid];
         if (v > best) { best = v; arg = (int)(c0 + row0) + r; }
       }
     }
     __syncthreads();
     // ---- Q = tanh(U1 q2^T + b), K = 128
-    const ds_f16 q = ds_mma<DQ>(Us + r32 * DR_ULD + 8 * kg, f2);
+    const f32x16 q = rg_mma3<DQ>(Us + r32 * DR_ULD + 8 * kg, f2);
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
       const int row = 8 * (i >> 2) + 4 * kg + (i & 3);
@@ -230,10 +182,8 @@ __global__ __launch_bounds__(256) void dsmil_crit_kernel(InferTab tab, const flo
                                                          float* __restrict__ logits_ins, int64_t* __restrict__ crit) {
   __shared__ int s_arg[DS_MAXC];
   const int bag = blockIdx.x;
-  int64_t N = tab.N[0], orow0 = tab.row0[0];
-  int p0 = tab.part0[0];
-  IT_PICK(N, N, bag) IT_PICK(orow0, row0, bag) IT_PICK(p0, part0, bag)
-  const int G = (int)((N + DR_CHUNK - 1) / DR_CHUNK);
+  RG_BAG(bag)
+  const int G = rg_parts(N);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   for (int c = wave; c < C; c += 4) {
     float best = -INFINITY;
@@ -270,12 +220,12 @@ __global__ __launch_bounds__(DP_THREADS) void dsmil_pool_kernel(InferTab tab, co
                                                                 const float* __restrict__ qmax, int C, float* __restrict__ pm,
                                                                 float* __restrict__ pl, float* __restrict__ pB) {
   __shared__ __attribute__((aligned(16))) float qs[CT * DQ];
-  __shared__ __attribute__((aligned(16))) float ps[DR_CHUNK * CT];
+  __shared__ __attribute__((aligned(16))) float ps[RG_CHUNK * CT];
   __shared__ float redm[CT][4], reds[CT][4];
   const int part = blockIdx.x;
-  DS_LOCATE_PART(part)
-  const int64_t c0 = (int64_t)(part - p0) * DR_CHUNK;
-  const int M = (int)((N - c0 < DR_CHUNK) ? N - c0 : DR_CHUNK);
+  RG_BAG_OF(part, part0)
+  const int64_t c0 = (int64_t)(part - p0) * RG_CHUNK;
+  const int M = (int)((N - c0 < RG_CHUNK) ? N - c0 : RG_CHUNK);
   const int64_t grow0 = orow0 + c0;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   for (int i = tid; i < CT * DQ; i += DP_THREADS) qs[i] = (i >> 7) < C ? qmax[(int64_t)bag * DS_MAXC * DQ + i] : 0.f;
@@ -331,7 +281,7 @@ __global__ __launch_bounds__(DP_THREADS) void dsmil_pool_kernel(InferTab tab, co
 // B (thread e = column e, partials in index order), the fcc head in fp32, the mix, the cross entropy.  blockIdx.y > 0: the instance score
 // max_c A[m,c] (no_norm: max_c a[m,c]).
 template <int CT>
-__global__ __launch_bounds__(DF_T) void dsmil_finalize_kernel(InferTab tab, const float* __restrict__ pm, const float* __restrict__ pl,
+__global__ __launch_bounds__(RG_FIN_T) void dsmil_finalize_kernel(InferTab tab, const float* __restrict__ pm, const float* __restrict__ pl,
                                                               const float* __restrict__ pB, const float* __restrict__ Q,
                                                               const float* __restrict__ qmax, const float* __restrict__ wfcc,
                                                               const float* __restrict__ bfcc, int C, int no_norm,
@@ -339,48 +289,31 @@ __global__ __launch_bounds__(DF_T) void dsmil_finalize_kernel(InferTab tab, cons
                                                               float* __restrict__ logits_bag, float* __restrict__ logits,
                                                               float* __restrict__ B_out, float* __restrict__ attn, float* __restrict__ loss) {
   __shared__ float red[8];
-  __shared__ float wgt[DF_T];
+  __shared__ float wgt[RG_FIN_T];
   __shared__ float smx[CT], sinv[CT];
   __shared__ float lg[DS_MAXC];
   __shared__ __attribute__((aligned(16))) float big[CT * IE];  // y = 0: B [C][512]; y > 0: q_max [CT][128]
   const int bag = blockIdx.x;
-  int64_t N = tab.N[0], orow0 = tab.row0[0];
-  int p0 = tab.part0[0];
-  IT_PICK(N, N, bag) IT_PICK(orow0, row0, bag) IT_PICK(p0, part0, bag)
-  const int G = (int)((N + DR_CHUNK - 1) / DR_CHUNK);
+  RG_BAG(bag)
+  const int G = rg_parts(N);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   pm += (int64_t)p0 * DS_MAXC; pl += (int64_t)p0 * DS_MAXC; pB += (int64_t)p0 * C * IE;
   for (int c = 0; c < C; ++c) {
-    float m = -INFINITY;
-    for (int b = tid; b < G; b += DF_T) m = fmaxf(m, pm[(int64_t)b * DS_MAXC + c]);
-    m = wave_max(m);
-    if (lane == 0) red[wave] = m;
-    __syncthreads();
-    float mx = red[0];
-#pragma unroll
-    for (int w = 1; w < 8; ++w) mx = fmaxf(mx, red[w]);
-    __syncthreads();
-    float lp = 0.f;
-    for (int b = tid; b < G; b += DF_T) lp += pl[(int64_t)b * DS_MAXC + c] * __expf(pm[(int64_t)b * DS_MAXC + c] - mx);
-    lp = wave_sum(lp);
-    if (lane == 0) red[wave] = lp;
-    __syncthreads();
-    float Ls = 0.f;
-#pragma unroll
-    for (int w = 0; w < 8; ++w) Ls += red[w];                 // fixed order: deterministic
+    float mx, Ls;
+    rg_merge_stats(pm + c, pl + c, G, DS_MAXC, red, mx, Ls);
     if (tid == 0) { smx[c] = mx; sinv[c] = 1.f / Ls; }
     __syncthreads();
   }
   if (blockIdx.y > 0) {
     if (!attn) return;
-    for (int i = tid; i < CT * DQ; i += DF_T) big[i] = (i >> 7) < C ? qmax[(int64_t)bag * DS_MAXC * DQ + i] : 0.f;
+    for (int i = tid; i < CT * DQ; i += RG_FIN_T) big[i] = (i >> 7) < C ? qmax[(int64_t)bag * DS_MAXC * DQ + i] : 0.f;
     __syncthreads();
     float mxr[CT], ivr[CT];
 #pragma unroll
     for (int c = 0; c < CT; ++c) { mxr[c] = c < C ? smx[c] : 0.f; ivr[c] = c < C ? sinv[c] : 0.f; }
     float* ab = attn + orow0;
-    const int64_t step = (int64_t)(gridDim.y - 1) * DF_T;
-    for (int64_t r = (int64_t)(blockIdx.y - 1) * DF_T + tid; r < N; r += step) {
+    const int64_t step = (int64_t)(gridDim.y - 1) * RG_FIN_T;
+    for (int64_t r = (int64_t)(blockIdx.y - 1) * RG_FIN_T + tid; r < N; r += step) {
       float a[CT];
       ds_scores<CT>(Q + (orow0 + r) * DQ, big, a);
       float best = -INFINITY;
@@ -394,11 +327,11 @@ __global__ __launch_bounds__(DF_T) void dsmil_finalize_kernel(InferTab tab, cons
   for (int c = 0; c < C; ++c) {
     const float mx = smx[c];
     float acc = 0.f;                                          // column tid of B[c]
-    for (int base = 0; base < G; base += DF_T) {
+    for (int base = 0; base < G; base += RG_FIN_T) {
       __syncthreads();
       wgt[tid] = base + tid < G ? __expf(pm[(int64_t)(base + tid) * DS_MAXC + c] - mx) : 0.f;
       __syncthreads();
-      const int cnt = G - base < DF_T ? G - base : DF_T;
+      const int cnt = G - base < RG_FIN_T ? G - base : RG_FIN_T;
 #pragma unroll 8
       for (int j = 0; j < cnt; ++j) acc += pB[((int64_t)(base + j) * C + c) * IE + tid] * wgt[j];
     }
@@ -408,7 +341,7 @@ __global__ __launch_bounds__(DF_T) void dsmil_finalize_kernel(InferTab tab, cons
   }
   __syncthreads();
   // fcc: Conv1d(C, C, kernel = E) on [1, C, E] = a [C, C * E] dot
-  for (int o = wave; o < C; o += DF_T / 64) {
+  for (int o = wave; o < C; o += RG_FIN_T / 64) {
     float d = 0.f;
     for (int c = 0; c < C; ++c) {
       const float* w = wfcc + ((int64_t)o * C + c) * IE;
@@ -442,7 +375,7 @@ struct DsmilWs { int64_t w1p, vp, q0f, q2f, H, V, Q, cls, pmax, parg, qmax, pm, 
 
 // the checks of mhimx_infer_run_x on the bag table and the element type (infer.hip: check_infer), and this call's own shape rules
 int check_dsmil(const mhimx_infer_dsmil_cfg* c, int32_t n_bags, const mhimx_infer_bag* bags, int32_t xdt) {
-  MHIMX_CHECK_ARG(xdt >= MHIMX_X_F32 && xdt <= MHIMX_X_BF16, "infer_dsmil: x_dtype %d is none of MHIMX_X_F32 / F16 / BF16", xdt);
+  if (int r = rg_check_xdt("infer_dsmil", xdt)) return r;
   MHIMX_CHECK_ARG(c && bags, "infer_dsmil: null configuration / bag list");
   MHIMX_CHECK_ARG(n_bags >= 1 && n_bags <= MHIMX_INFER_MAX, "infer_dsmil: 1..%d bags per call (got %d)", MHIMX_INFER_MAX, n_bags);
   MHIMX_CHECK_ARG(c->E == IE && c->C >= 1 && c->C <= DS_MAXC && c->D > 0 && c->D % 256 == 0 && c->D <= (1 << 20),
@@ -450,32 +383,18 @@ int check_dsmil(const mhimx_infer_dsmil_cfg* c, int32_t n_bags, const mhimx_infe
   MHIMX_CHECK_ARG(c->act >= MHIMX_ACT_NONE && c->act <= MHIMX_ACT_TANH, "infer_dsmil: unknown activation");
   int64_t rows = 0;
   for (int b = 0; b < n_bags; ++b) {
-    const mhimx_infer_bag& g = bags[b];
-    MHIMX_CHECK_ARG(g.N >= 1 && g.N <= MHIMX_INFER_MAX_ROWS, "infer_dsmil: bag %d: N must be in 1..%d", b, MHIMX_INFER_MAX_ROWS);
-    if (xdt == MHIMX_X_F32)
-      MHIMX_CHECK_ARG(g.ldx >= c->D && g.ldx % 4 == 0 && g.ldx <= (1 << 20),
-                      "infer_dsmil: bag %d: row pitch below D or not a multiple of 4 floats", b);
-    else
-      MHIMX_CHECK_ARG(g.ldx >= c->D && g.ldx % 8 == 0 && g.ldx <= (1 << 20),
-                      "infer_dsmil: bag %d: row pitch below D or not a multiple of 8 two-byte elements", b);
-    rows += g.N;
+    if (int r = rg_check_bag("infer_dsmil", b, bags[b].N, bags[b].ldx, c->D, xdt, RgRules{MHIMX_INFER_MAX_ROWS, false})) return r;
+    rows += bags[b].N;
   }
   MHIMX_CHECK_ARG(rows <= MHIMX_INFER_MAX_ROWS, "infer_dsmil: more than %d rows in one call", MHIMX_INFER_MAX_ROWS);
   return 0;
 }
 
 void dsmil_layout(const mhimx_infer_dsmil_cfg* c, int32_t n_bags, const mhimx_infer_bag* bags, DsmilWs* w, InferTab* tab) {
-  int64_t rows = 0, tiles = 0, parts = 0;
-  for (int b = 0; b < n_bags; ++b) {
-    if (tab) {
-      tab->X[b] = bags[b].X; tab->ldx[b] = bags[b].ldx; tab->N[b] = bags[b].N;
-      tab->row0[b] = rows; tab->tile0[b] = (int32_t)tiles; tab->part0[b] = (int32_t)parts;
-    }
-    rows += bags[b].N;
-    tiles += cdiv(bags[b].N, INFER_TILE_ROWS);
-    parts += cdiv(bags[b].N, DR_CHUNK);
-  }
-  if (tab) { tab->n = n_bags; tab->tiles = (int32_t)tiles; tab->parts = (int32_t)parts; }
+  RgCount n;
+  for (int b = 0; b < n_bags; ++b) rg_tab_add(tab, n, b, bags[b].X, bags[b].ldx, bags[b].N, bags[b].N);
+  rg_tab_close(tab, n, n_bags);
+  const int64_t rows = n.rows, parts = n.parts;
   Arena ar(nullptr, 0);
   w->w1p = ar.off; ar.take<float>(c->E * c->D);
   w->vp = ar.off; ar.take<float>(c->E * c->E);
@@ -500,7 +419,7 @@ int dsmil_tail(hipStream_t st, const InferTab& tab, const mhimx_infer_dsmil_cfg*
   const int C = (int)cfg->C;
   hipLaunchKernelGGL(dsmil_pool_kernel<CT>, dim3((unsigned)tab.parts), dim3(DP_THREADS), 0, st, tab, Q, V, qmax, C, pm, pl, pB);
   MHIMX_LAUNCH_CHECK();
-  hipLaunchKernelGGL(dsmil_finalize_kernel<CT>, dim3((unsigned)tab.n, attn_blocks ? 1 + DF_ATTN_BLOCKS : 1), dim3(DF_T), 0, st, tab, pm, pl, pB, Q,
+  hipLaunchKernelGGL(dsmil_finalize_kernel<CT>, dim3((unsigned)tab.n, attn_blocks ? 1 + DF_ATTN_BLOCKS : 1), dim3(RG_FIN_T), 0, st, tab, pm, pl, pB, Q,
                      qmax, cfg->wfcc, cfg->bfcc, C, (int)(cfg->no_norm != 0), labels, logits_ins, out->logits_bag, out->logits, out->B,
                      attn_blocks ? out->attn : nullptr, out->loss);
   MHIMX_LAUNCH_CHECK();
@@ -537,8 +456,7 @@ extern "C" int mhimx_infer_dsmil_run(void* stream, const mhimx_infer_dsmil_cfg* 
   InferTab tab = {};
   dsmil_layout(cfg, n_bags, bags, &w, &tab);
   tab.pad = x_dtype;                           // read by the first projection launch alone: the only reader of X
-  MHIMX_CHECK_ARG(ws && (reinterpret_cast<uintptr_t>(ws) & 255) == 0, "infer_dsmil: the workspace must be 256-byte aligned");
-  MHIMX_CHECK_ARG(ws_bytes >= w.total, "infer_dsmil: workspace too small (%lld bytes, need %lld)", (long long)ws_bytes, (long long)w.total);
+  if (int r = rg_check_ws("infer_dsmil", ws, ws_bytes, w.total)) return r;
   hipStream_t st = (hipStream_t)stream;
   char* base = static_cast<char*>(ws);
   auto F = [&](int64_t off) { return reinterpret_cast<float*>(base + off); };
@@ -560,7 +478,7 @@ extern "C" int mhimx_infer_dsmil_run(void* stream, const mhimx_infer_dsmil_cfg* 
   if (int r = infer_project(st, tabv, IE, vp, cfg->bv, MHIMX_ACT_RELU, V)) return r;
   // 4. Q, classes, arg-max partials (the instance score too when it is max_c classes)
   MHIMX_ONCE_PER_DEVICE(MHIMX_HIP(hipFuncSetAttribute((const void*)dsmil_rows_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)DR_SMEM)));
-  hipLaunchKernelGGL(dsmil_rows_kernel, dim3((unsigned)tab.parts), dim3(DR_THREADS), DR_SMEM, st, tab, H, q0f, cfg->bq0, q2f, cfg->bq2, cfg->wi,
+  hipLaunchKernelGGL(dsmil_rows_kernel, dim3((unsigned)tab.parts), dim3(RG_T), DR_SMEM, st, tab, H, q0f, cfg->bq0, q2f, cfg->bq2, cfg->wi,
                      cfg->bi, C, Q, cls, cfg->cls_attn ? out->attn : nullptr, pmax, parg);
   MHIMX_LAUNCH_CHECK();
   // 5. critical rows, max-instance logits, q_max

@@ -12,14 +12,14 @@
 //   1  mhimx_prep_batch              counters, the W1 paired-plane image, the Wa fragment image
 //   2  pure_window_project_kernel    (bag_project.hip) infer_project_kernel's tile walk in train mode: per-bag dropout, fp16 d out / d pre, zero
 //                                    padding rows
-//   3  infer_score_kernel            (infer.hip, as it is) scores + one pool partial per 256 rows of a bag
+//   3  infer_score_kernel<false>     (infer.hip, as it is) scores + one pool partial per 256 rows of a bag
 //   4  pw_head_kernel                plane = bag: merge of the partials in index order, predictor, CE and their gradients: g_logits, g_z, z.g_z,
 //                                    the bag's d Wp / d bp partial
 //   5  pw_pool_bwd_kernel            one workgroup per 32-row tile of the row space: U = h Wa^T again on the matrix cores (3-term bf16), d s,
 //                                    d U (kept as fp32 rows for launch 6) and the tile's d wc partial, d h = p g_z + d U Wa (fp32), the epilogue
 //                                    multiplies by d out / d pre and writes fp32 dPRE rows and the tile's column sums (d b1 partial)
-//   6  pw_tn_kernel<false>           d Wa = dU^T H over the whole row space: 128 x 128 tiles, split-K slabs, 3-term bf16 on the matrix cores
-//   7  pw_tn_kernel<true>            d W1 = sum_b dPRE_b^T X_b: the same kernel, the X side read from each bag where it lies (a k-step = 32 rows
+//   6  pw_tn_kernel<false, 0>        d Wa = dU^T H over the whole row space: 128 x 128 tiles, split-K slabs, 3-term bf16 on the matrix cores
+//   7  pw_tn_kernel<true, XT>        d W1 = sum_b dPRE_b^T X_b: the same kernel, the X side read from each bag where it lies (a k-step = 32 rows
 //                                    of ONE bag, found from the table)
 //   8  pw_reduce_kernel              every partial buffer (slabs, per-tile and per-bag partials) summed in index order into cfg->grad
 //   9  mhimx_optim_step              Adam (update = 1)
@@ -34,78 +34,45 @@ namespace mhimx {
 
 namespace {
 
-constexpr int PW_A = 128, PW_ROWS = 32, PW_T = 256, PW_LD = IE + 4, PW_DUP = PW_ROWS + 4, PW_MAXC = 4;
-constexpr int PW_CHUNK = 256;                                   // rows of a pool partial (infer.hip SC_CHUNK)
+constexpr int PW_A = 128, PW_ROWS = RG_ROWS, PW_T = RG_T, PW_LD = RG_LD, PW_DUP = PW_ROWS + 4, PW_MAXC = 4;
 constexpr size_t PW_BWD_SMEM = (size_t)(PW_ROWS * PW_LD + IE + 3 * PW_ROWS + 2 * PW_A) * sizeof(float);
-constexpr int HEAD_T = 512;
 constexpr int TN_T = 256, TN_BM = 128, TN_BN = 128, TN_PITCH = 80;   // bytes of one column's 32 bf16 k-values (+ 16 of padding)
 constexpr int RED_JOBS = 6, RED_T = 256, RED_BLOCKS = 256, RED_WIDE_G = 64;
 
-typedef __bf16 pw_b8 __attribute__((ext_vector_type(8)));
 typedef __bf16 pw_b4 __attribute__((ext_vector_type(4)));
-typedef float pw_f16 __attribute__((ext_vector_type(16)));
 
 struct PwLabels { const int64_t* p[MHIMX_INFER_MAX]; };
-#define PW_PICK(dst, arr, b)                                     \
-  _Pragma("unroll") for (int q_ = 0; q_ < MHIMX_INFER_MAX; ++q_) \
-    if (q_ == (b)) dst = arr[q_];
-
-MHIMX_DEV void pw_split(const f32x4& a, const f32x4& b, pw_b8& hi, pw_b8& lo) {
-  const float x[8] = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    const __bf16 h = (__bf16)x[i];
-    hi[i] = h;
-    lo[i] = (__bf16)(x[i] - (float)h);
-  }
-}
 
 // ------------------------------------------------------------------------------------------------ 4. merge + head + CE + their gradients
 // blockIdx.x = bag.  infer_finalize_kernel's merge (partials in index order) and predictor, then the backward of the head:
 // g_logits = main_alpha (softmax - onehot) / n, g_z = Wp^T g_logits, zg = z . g_z, the bag's d Wp / d bp partial.
-__global__ __launch_bounds__(HEAD_T) void pw_head_kernel(InferTab tab, PwLabels lab, const float* __restrict__ pm, const float* __restrict__ pl,
+__global__ __launch_bounds__(RG_FIN_T) void pw_head_kernel(InferTab tab, PwLabels lab, const float* __restrict__ pm, const float* __restrict__ pl,
                                                          const float* __restrict__ pz, const float* __restrict__ wp, const float* __restrict__ bp,
                                                          int C, float main_alpha, float inv_n, float* __restrict__ logits,
                                                          float* __restrict__ losses, float* __restrict__ z_out, float* __restrict__ stats,
                                                          float* __restrict__ g_z, float* __restrict__ zg, float* __restrict__ dwp_part,
                                                          float* __restrict__ dbp_part) {
   __shared__ float red[8];
-  __shared__ float wgt[HEAD_T];
+  __shared__ float wgt[RG_FIN_T];
   __shared__ float zs[IE];
   __shared__ float lg[PW_MAXC], gl[PW_MAXC];
   const int bag = blockIdx.x;
-  int64_t N = tab.N[0];
-  int p0 = tab.part0[0];
+  RG_BAG(bag)
   const int64_t* label = lab.p[0];
-  IT_PICK(N, N, bag) IT_PICK(p0, part0, bag) PW_PICK(label, lab.p, bag)
-  const int G = (int)((N + PW_CHUNK - 1) / PW_CHUNK);
+  RG_PICK(label, lab.p, bag)
+  const int G = rg_parts(N);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   pm += p0; pl += p0; pz += (int64_t)p0 * IE;
-  float m = -INFINITY;
-  for (int b = tid; b < G; b += HEAD_T) m = fmaxf(m, pm[b]);
-  m = wave_max(m);
-  if (lane == 0) red[wave] = m;
-  __syncthreads();
-  float mx = red[0];
-#pragma unroll
-  for (int w = 1; w < 8; ++w) mx = fmaxf(mx, red[w]);
-  __syncthreads();
-  float lp = 0.f;
-  for (int b = tid; b < G; b += HEAD_T) lp += pl[b] * __expf(pm[b] - mx);
-  lp = wave_sum(lp);
-  if (lane == 0) red[wave] = lp;
-  __syncthreads();
-  float L = 0.f;
-#pragma unroll
-  for (int w = 0; w < 8; ++w) L += red[w];                    // fixed order: deterministic
+  float mx, L;
+  rg_merge_stats(pm, pl, G, 1, red, mx, L);
   const float invL = 1.f / L;
   if (tid == 0) { stats[2 * bag] = mx; stats[2 * bag + 1] = L; }
   float acc = 0.f;                                            // column tid of the pooled row
-  for (int base = 0; base < G; base += HEAD_T) {
+  for (int base = 0; base < G; base += RG_FIN_T) {
     __syncthreads();
     wgt[tid] = base + tid < G ? __expf(pm[base + tid] - mx) : 0.f;
     __syncthreads();
-    const int cnt = G - base < HEAD_T ? G - base : HEAD_T;
+    const int cnt = G - base < RG_FIN_T ? G - base : RG_FIN_T;
 #pragma unroll 8
     for (int j = 0; j < cnt; ++j) acc += pz[(int64_t)(base + j) * IE + tid] * wgt[j];
   }
@@ -113,7 +80,7 @@ __global__ __launch_bounds__(HEAD_T) void pw_head_kernel(InferTab tab, PwLabels 
   zs[tid] = zv;
   z_out[(int64_t)bag * IE + tid] = zv;
   __syncthreads();
-  for (int c = wave; c < C; c += HEAD_T / 64) {
+  for (int c = wave; c < C; c += RG_FIN_T / 64) {
     float d = 0.f;
 #pragma unroll
     for (int q = 0; q < IE / 64; ++q) d += zs[lane + 64 * q] * wp[(int64_t)c * IE + lane + 64 * q];
@@ -181,12 +148,9 @@ __global__ __launch_bounds__(PW_T, 2) void pw_pool_bwd_kernel(InferTab tab, cons
   float* wcp = spare + PW_ROWS;               // [2][128] d wc halves
   const int tile = blockIdx.x;
   const int64_t r0 = (int64_t)tile * PW_ROWS;
-  int bag = 0;
-#pragma unroll
-  for (int b = 1; b < MHIMX_INFER_MAX; ++b)
-    if (b < tab.n && r0 >= tab.row0[b]) bag = b;
+  RG_FIND_BAG(r0, row0)
   int64_t N = tab.N[0], orow0 = tab.row0[0];
-  IT_PICK(N, N, bag) IT_PICK(orow0, row0, bag)
+  RG_PICK(N, tab.N, bag) RG_PICK(orow0, tab.row0, bag)       // (not RG_BAG: with the unused p0 picked too the kernel does not keep its code)
   const int64_t left = N - (r0 - orow0);
   const int M = left < PW_ROWS ? (int)left : PW_ROWS;          // real rows of the tile (>= 1)
   const float mx = stats[2 * bag], invL = 1.f / stats[2 * bag + 1], zgb = zg[bag];
@@ -222,8 +186,8 @@ __global__ __launch_bounds__(PW_T, 2) void pw_pool_bwd_kernel(InferTab tab, cons
     for (int q = 0; q < IE / 64; ++q) v += wave_sum(__fmul_rn(Hs[r * PW_LD + lane + 64 * q], gzs[lane + 64 * q]));   // (never contracted)
     if (lane == 0) dsr[r] = prow[r] * (v - zgb);
   }
-  // ---- U tile on the matrix cores, one accumulator per bf16x3 term (infer_score_kernel's loop)
-  pw_f16 acc, acc2, acc3;
+  // ---- U tile on the matrix cores, one accumulator per bf16x3 term (infer_score_kernel's loop; own text: rg_mma3 moved this kernel's code)
+  f32x16 acc, acc2, acc3;
 #pragma unroll
   for (int i = 0; i < 16; ++i) { acc[i] = 0.f; acc2[i] = 0.f; acc3[i] = 0.f; }
   {
@@ -233,9 +197,9 @@ __global__ __launch_bounds__(PW_T, 2) void pw_pool_bwd_kernel(InferTab tab, cons
       const int kn = ks + 1 < IE / 16 ? ks + 1 : ks;
       const f32x4 nbh = fptr[128 * kn], nbl = fptr[128 * kn + 1];
       const f32x4 a0 = *reinterpret_cast<const f32x4*>(aptr + 16 * ks), a1 = *reinterpret_cast<const f32x4*>(aptr + 16 * ks + 4);
-      pw_b8 ah, al;
-      pw_split(a0, a1, ah, al);
-      const pw_b8 bh8 = __builtin_bit_cast(pw_b8, bh), bl8 = __builtin_bit_cast(pw_b8, bl);
+      bf8 ah, al;
+      rg_split(a0, a1, ah, al);
+      const bf8 bh8 = __builtin_bit_cast(bf8, bh), bl8 = __builtin_bit_cast(bf8, bl);
       acc2 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh8, acc2, 0, 0, 0);
       acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh8, acc, 0, 0, 0);
       acc3 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl8, acc3, 0, 0, 0);
@@ -313,19 +277,111 @@ __global__ __launch_bounds__(PW_T, 2) void pw_pool_bwd_kernel(InferTab tab, cons
 // coalesced loads one k-step ahead), are split to bf16 hi / lo and written to LDS TRANSPOSED (a column's 32 k-values contiguous), so that a
 // fragment is one 16-byte LDS read.  BAGX: B = the bags' X, each where it lies: the k-step's bag from the table, rows past its N clamped
 // (their A rows are zero rows).  XT (BAGX only; MHIMX_X_*): fp16 / bf16 bag rows come in as 8-byte loads of 4 elements and are widened to fp32
-// (x_widen: exact) in front of the same split - the LDS image is that of the fp32 kernel on the widened rows.
-template <bool BAGX>
+// (x_widen: exact) in front of the same split - the LDS image is that of the fp32 kernel on the widened rows (B / ldb: unused there).
+template <bool BAGX, int XT>
 __global__ __launch_bounds__(TN_T, 2) void pw_tn_kernel(InferTab tab, const float* __restrict__ A, int lda, const float* __restrict__ B, int ldb,
                                                         int steps, int steps_per, float* __restrict__ slabs, int M, int Nc) {
-  constexpr int XT = MHIMX_X_F32;
-#include "pw_tn_body.hpp"
-}
-// d W1 over fp16 (XT = 1) / bf16 (XT = 2) bags
-template <int XT>
-__global__ __launch_bounds__(TN_T, 2) void pw_tn_x_kernel(InferTab tab, const float* __restrict__ A, int lda, const float* __restrict__ B, int ldb,
-                                                          int steps, int steps_per, float* __restrict__ slabs, int M, int Nc) {
-  constexpr bool BAGX = true;                                   // (B / ldb: unused - the argument list of pw_tn_kernel)
-#include "pw_tn_body.hpp"
+  __shared__ __attribute__((aligned(16))) char lds[4][TN_BM * TN_PITCH];      // A hi, A lo, B hi, B lo
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wm = wave >> 1, wn = wave & 1;
+  const int m0 = blockIdx.y * TN_BM, n0 = blockIdx.x * TN_BN, z = blockIdx.z;
+  const int ks0 = z * steps_per, ks1 = ks0 + steps_per < steps ? ks0 + steps_per : steps;
+  const int c4 = tid & 31, rg = tid >> 5;                     // this thread's 4 columns and 4 rows (4 rg .. 4 rg + 3) of a k-step
+  typedef typename XRow<XT>::v4 XV4;
+  f32x4 ra[4];
+  XV4 rb[4];
+  auto load = [&](int ks) {
+    const int64_t row = (int64_t)ks * 32 + 4 * rg;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) ra[j] = *reinterpret_cast<const f32x4*>(A + (row + j) * lda + m0 + 4 * c4);
+    if constexpr (BAGX) {
+      const int64_t k0 = (int64_t)ks * 32;
+      RG_FIND_BAG(k0, row0)
+      const float* X = tab.X[0];
+      int64_t ldx = tab.ldx[0], N = tab.N[0], orow0 = tab.row0[0];
+      RG_PICK(X, tab.X, bag) RG_PICK(ldx, tab.ldx, bag) RG_PICK(N, tab.N, bag) RG_PICK(orow0, tab.row0, bag)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        int64_t rin = row + j - orow0;
+        if (rin >= N) rin = N - 1;
+        rb[j] = *reinterpret_cast<const XV4*>(reinterpret_cast<const typename XRow<XT>::elt*>(X) + rin * ldx + n0 + 4 * c4);
+      }
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) rb[j] = *reinterpret_cast<const XV4*>(B + (row + j) * ldb + n0 + 4 * c4);
+    }
+  };
+  auto store = [&](const f32x4 (&r)[4], char* hi_p, char* lo_p) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      pw_b4 hi, lo;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const __bf16 h = (__bf16)r[j][q];
+        hi[j] = h;
+        lo[j] = (__bf16)(r[j][q] - (float)h);
+      }
+      const int off = (4 * c4 + q) * TN_PITCH + 8 * rg;
+      *reinterpret_cast<pw_b4*>(hi_p + off) = hi;
+      *reinterpret_cast<pw_b4*>(lo_p + off) = lo;
+    }
+  };
+  f32x16 acc[2][2];
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+  const int r32 = lane & 31, kg = lane >> 5;
+  if (ks0 < ks1) load(ks0);
+#pragma unroll 1
+  for (int ks = ks0; ks < ks1; ++ks) {
+    __syncthreads();                                          // the previous k-step's fragment reads are over
+    store(ra, lds[0], lds[1]);
+    if constexpr (XT == 0) {
+      store(rb, lds[2], lds[3]);
+    } else {
+      f32x4 rw[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) rw[j] = x_widen<XT>(rb[j]);
+      store(rw, lds[2], lds[3]);
+    }
+    __syncthreads();
+    if (ks + 1 < ks1) load(ks + 1);
+#pragma unroll
+    for (int k2 = 0; k2 < 2; ++k2) {
+      bf8 ah[2], al[2], bh[2], bl[2];
+#pragma unroll
+      for (int i = 0; i < 2; ++i) {
+        const int ao = (wm * 64 + i * 32 + r32) * TN_PITCH + 32 * k2 + 16 * kg;
+        const int bo = (wn * 64 + i * 32 + r32) * TN_PITCH + 32 * k2 + 16 * kg;
+        ah[i] = *reinterpret_cast<const bf8*>(lds[0] + ao);
+        al[i] = *reinterpret_cast<const bf8*>(lds[1] + ao);
+        bh[i] = *reinterpret_cast<const bf8*>(lds[2] + bo);
+        bl[i] = *reinterpret_cast<const bf8*>(lds[3] + bo);
+      }
+#pragma unroll
+      for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[i], bh[j], acc[i][j], 0, 0, 0);
+          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bl[j], acc[i][j], 0, 0, 0);
+          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bh[j], acc[i][j], 0, 0, 0);
+        }
+    }
+  }
+  float* out = slabs + (int64_t)z * M * Nc;
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+      for (int e = 0; e < 16; ++e) {
+        const int row = m0 + wm * 64 + i * 32 + 8 * (e >> 2) + 4 * kg + (e & 3);
+        const int col = n0 + wn * 64 + j * 32 + r32;
+        out[(int64_t)row * Nc + col] = acc[i][j][e];
+      }
 }
 
 // ------------------------------------------------------------------------------------------------ 8. every partial buffer, in index order
@@ -381,7 +437,7 @@ struct PwLay {
 
 // xdt: the element type of the bags' rows (MHIMX_X_*); the 2-byte types have their own pitch rule (16-byte rows: 8 elements)
 int check_pw(const mhimx_step_cfg* c, int32_t n_bags, const mhimx_pure_window_bag* bags, int32_t xdt = MHIMX_X_F32) {
-  MHIMX_CHECK_ARG(xdt >= MHIMX_X_F32 && xdt <= MHIMX_X_BF16, "pure_window: x_dtype %d is none of MHIMX_X_F32 / F16 / BF16", xdt);
+  if (int r = rg_check_xdt("pure_window", xdt)) return r;
   MHIMX_CHECK_ARG(c && bags, "pure_window: null configuration / bag list");
   MHIMX_CHECK_ARG(n_bags >= 1 && n_bags <= MHIMX_PURE_WINDOW_MAX, "pure_window: 1..%d bags per window (got %d)", MHIMX_PURE_WINDOW_MAX, n_bags);
   MHIMX_CHECK_ARG(c->E == IE && c->A == PW_A && c->C >= 1 && c->C <= PW_MAXC && c->D > 0 && c->D % 256 == 0 && c->D <= (1 << 20),
@@ -397,17 +453,8 @@ int check_pw(const mhimx_step_cfg* c, int32_t n_bags, const mhimx_pure_window_ba
   MHIMX_CHECK_ARG(c->tick, "pure_window: the device dropout counter (tick) is required");
   int64_t rows = 0;
   for (int b = 0; b < n_bags; ++b) {
-    const mhimx_pure_window_bag& q = bags[b];
-    MHIMX_CHECK_ARG(q.N >= 1 && q.N <= MHIMX_STEP_MAX_ROWS, "pure_window: bag %d: N must be in 1..%d", b, MHIMX_STEP_MAX_ROWS);
-    if (xdt == MHIMX_X_F32) {
-      MHIMX_CHECK_ARG(q.ldx >= c->D && q.ldx % 4 == 0, "pure_window: bag %d: row pitch below D or not a multiple of 4 floats", b);
-      MHIMX_CHECK_ARG(q.N * q.ldx * 4 < ((int64_t)1 << 32), "pure_window: bag %d: N * ldx * 4 must stay below 2^32", b);
-    } else {
-      MHIMX_CHECK_ARG(q.ldx >= c->D && q.ldx % 8 == 0 && q.ldx <= (1 << 20),
-                      "pure_window: bag %d: row pitch below D, above 2^20 or not a multiple of 8 two-byte elements", b);
-      MHIMX_CHECK_ARG(q.N * q.ldx * 2 < ((int64_t)1 << 32), "pure_window: bag %d: N * ldx * 2 must stay below 2^32", b);
-    }
-    rows += align_up(q.N, PW_ROWS);
+    if (int r = rg_check_bag("pure_window", b, bags[b].N, bags[b].ldx, c->D, xdt, RgRules{MHIMX_STEP_MAX_ROWS, true})) return r;
+    rows += align_up(bags[b].N, PW_ROWS);
   }
   MHIMX_CHECK_ARG(rows <= MHIMX_PURE_WINDOW_MAX_ROWS, "pure_window: %lld rows in the window's row space, at most %d", (long long)rows,
                   MHIMX_PURE_WINDOW_MAX_ROWS);
@@ -415,32 +462,19 @@ int check_pw(const mhimx_step_cfg* c, int32_t n_bags, const mhimx_pure_window_ba
 }
 
 void pw_layout(const mhimx_step_cfg* c, int32_t n_bags, const mhimx_pure_window_bag* bags, PwLay* w, InferTab* tab, int64_t* row0_out) {
-  int64_t rows = 0, tiles = 0, parts = 0;
+  RgCount cnt;
   for (int b = 0; b < n_bags; ++b) {
-    if (tab) {
-      tab->X[b] = bags[b].X; tab->ldx[b] = bags[b].ldx; tab->N[b] = bags[b].N;
-      tab->row0[b] = rows; tab->tile0[b] = (int32_t)tiles; tab->part0[b] = (int32_t)parts;
-    }
-    if (row0_out) row0_out[b] = rows;
-    rows += align_up(bags[b].N, PW_ROWS);
-    tiles += cdiv(bags[b].N, INFER_TILE_ROWS);
-    parts += cdiv(bags[b].N, PW_CHUNK);
+    if (row0_out) row0_out[b] = cnt.rows;
+    rg_tab_add(tab, cnt, b, bags[b].X, bags[b].ldx, bags[b].N, align_up(bags[b].N, PW_ROWS));
   }
-  if (tab) { tab->n = n_bags; tab->tiles = (int32_t)tiles; tab->parts = (int32_t)parts; }
+  rg_tab_close(tab, cnt, n_bags);
+  const int64_t rows = cnt.rows, parts = cnt.parts;
   const int64_t E = c->E, D = c->D, A = c->A, C = c->C, n = n_bags;
   w->rows = rows;
   w->steps = (int32_t)(rows / PW_ROWS);
   // split-K slabs: enough workgroups to fill the part (4 output tiles for d Wa, 4 D / 128 for d W1), never an empty slab
-  // (room for `s` slabs - a count that never shrinks when the window grows, so the workspace is monotone in rows; S <= s are written)
-  auto split = [&](int want_max, int div, int32_t* S, int32_t* per) {
-    int s = w->steps / div;
-    s = s < 1 ? 1 : (s > want_max ? want_max : s);
-    *per = (int32_t)cdiv(w->steps, s);
-    *S = (int32_t)cdiv(w->steps, *per);
-    return s;
-  };
-  const int sa_room = split(64, 4, &w->sa, &w->sa_per);
-  const int s1_room = split(8, 8, &w->s1, &w->s1_per);
+  const int sa_room = pw_split_k(w->steps, 64, 4, &w->sa, &w->sa_per);
+  const int s1_room = pw_split_k(w->steps, 8, 8, &w->s1, &w->s1_per);
   Arena ar(nullptr, 0);
   w->w1p = ar.off; ar.take<float>(E * D);
   w->wa_frag = ar.off; ar.take<float>(A * E);
@@ -469,7 +503,7 @@ void pw_layout(const mhimx_step_cfg* c, int32_t n_bags, const mhimx_pure_window_
 
 }  // namespace
 
-// ---- for mhimx_ragged_window_run (ragged_window.hip): the split-K rule, the d W1 launch and the reduction launch of this file as host calls
+// ---- for mhimx_ragged_window_run (ragged_window.hip) and this file's own layout / run: the split-K rule, the d W1 launch and the reduction launch as host calls
 // split-K slabs for `steps` 32-row k-steps: steps / div of them, 1 .. want_max, never an empty one.  Returns the slabs to make ROOM for (a
 // count that never shrinks when the window grows); *S <= room are written, *per k-steps each.
 int pw_split_k(int steps, int want_max, int div, int32_t* S, int32_t* per) {
@@ -483,12 +517,12 @@ int pw_split_k(int steps, int want_max, int div, int32_t* S, int32_t* per) {
 int pw_wgrad_bagx(hipStream_t st, const InferTab& tab, const float* dpre, int D, int steps, int S, int per, float* slabs) {
   if (tab.pad != MHIMX_X_F32) {                                 // (tab.pad: the element type of the bags' rows; the entry points have checked it)
     const dim3 grid((unsigned)(D / TN_BN), IE / TN_BM, (unsigned)S);
-    if (tab.pad == MHIMX_X_F16) hipLaunchKernelGGL(pw_tn_x_kernel<1>, grid, dim3(TN_T), 0, st, tab, dpre, IE, nullptr, 0, steps, per, slabs, IE, D);
-    else hipLaunchKernelGGL(pw_tn_x_kernel<2>, grid, dim3(TN_T), 0, st, tab, dpre, IE, nullptr, 0, steps, per, slabs, IE, D);
+    if (tab.pad == MHIMX_X_F16) hipLaunchKernelGGL((pw_tn_kernel<true, 1>), grid, dim3(TN_T), 0, st, tab, dpre, IE, nullptr, 0, steps, per, slabs, IE, D);
+    else hipLaunchKernelGGL((pw_tn_kernel<true, 2>), grid, dim3(TN_T), 0, st, tab, dpre, IE, nullptr, 0, steps, per, slabs, IE, D);
     MHIMX_LAUNCH_CHECK();
     return 0;
   }
-  hipLaunchKernelGGL(pw_tn_kernel<true>, dim3((unsigned)(D / TN_BN), IE / TN_BM, (unsigned)S), dim3(TN_T), 0, st, tab, dpre, IE, nullptr, 0, steps, per, slabs,
+  hipLaunchKernelGGL((pw_tn_kernel<true, 0>), dim3((unsigned)(D / TN_BN), IE / TN_BM, (unsigned)S), dim3(TN_T), 0, st, tab, dpre, IE, nullptr, 0, steps, per, slabs,
                      IE, D);
   MHIMX_LAUNCH_CHECK();
   return 0;
@@ -537,8 +571,7 @@ extern "C" int mhimx_pure_window_run_x(void* stream, const mhimx_step_cfg* cfg, 
   InferTab tab = {};
   pw_layout(cfg, n_bags, bags, &w, &tab, nullptr);
   tab.pad = x_dtype;                           // read by the two launches that read X: the projection (2) and d W1 (7)
-  MHIMX_CHECK_ARG(ws && (reinterpret_cast<uintptr_t>(ws) & 255) == 0, "pure_window: the workspace must be 256-byte aligned");
-  MHIMX_CHECK_ARG(ws_bytes >= w.total, "pure_window: workspace too small (%lld bytes, need %lld)", (long long)ws_bytes, (long long)w.total);
+  if (int r = rg_check_ws("pure_window", ws, ws_bytes, w.total)) return r;
   const mhimx_step_cfg& c = *cfg;
   const mhimx_step_params& S = c.student;
   hipStream_t st = (hipStream_t)stream;
@@ -571,7 +604,7 @@ extern "C" int mhimx_pure_window_run_x(void* stream, const mhimx_step_cfg* cfg, 
   {
     PwLabels lab = {};
     for (int b = 0; b < n_bags; ++b) lab.p[b] = bags[b].label_dev;
-    hipLaunchKernelGGL(pw_head_kernel, dim3((unsigned)n_bags), dim3(HEAD_T), 0, st, tab, lab, pm, pl, pz, S.wp, S.bp, C, c.main_alpha,
+    hipLaunchKernelGGL(pw_head_kernel, dim3((unsigned)n_bags), dim3(RG_FIN_T), 0, st, tab, lab, pm, pl, pz, S.wp, S.bp, C, c.main_alpha,
                        1.f / (float)n_bags, F(w.logits), F(w.losses), F(w.z), F(w.stats), F(w.g_z), F(w.zg), F(w.dwp_part), F(w.dbp_part));
     MHIMX_LAUNCH_CHECK();
   }
@@ -581,30 +614,21 @@ extern "C" int mhimx_pure_window_run_x(void* stream, const mhimx_step_cfg* cfg, 
                      S.wa, S.wc, c.da_act, F(w.dU), F(w.dpre), F(w.db1_part), F(w.dwc_part));
   MHIMX_LAUNCH_CHECK();
   // ---- 6. d Wa = dU^T H
-  hipLaunchKernelGGL(pw_tn_kernel<false>, dim3(IE / TN_BN, PW_A / TN_BM, (unsigned)w.sa), dim3(TN_T), 0, st, tab, F(w.dU), PW_A, H, IE, w.steps, w.sa_per,
+  hipLaunchKernelGGL((pw_tn_kernel<false, 0>), dim3(IE / TN_BN, PW_A / TN_BM, (unsigned)w.sa), dim3(TN_T), 0, st, tab, F(w.dU), PW_A, H, IE, w.steps, w.sa_per,
                      F(w.slab_a), PW_A, IE);
   MHIMX_LAUNCH_CHECK();
   // ---- 7. d W1 = sum_b dPRE_b^T X_b
   if (int r = pw_wgrad_bagx(st, tab, F(w.dpre), D, w.steps, w.s1, w.s1_per, F(w.slab_1))) return r;
   // ---- 8. the partial buffers, in index order, into the gradient views
   {
-    PwRed r = {};
-    int j = 0;
-    auto job = [&](const float* parts, int G, int64_t W, float* out) { r.parts[j] = parts; r.G[j] = G; r.W[j] = W; r.out[j] = out; ++j; };
-    job(F(w.slab_1), w.s1, (int64_t)c.E * c.D, c.grad.w1);
-    job(F(w.slab_a), w.sa, (int64_t)c.A * c.E, c.grad.wa);
-    job(F(w.db1_part), w.steps, c.E, c.grad.b1);
-    job(F(w.dwc_part), w.steps, c.A, c.grad.wc);
-    job(F(w.dwp_part), n_bags, (int64_t)C * c.E, c.grad.wp);
-    job(F(w.dbp_part), n_bags, C, c.grad.bp);
-    hipLaunchKernelGGL(pw_reduce_kernel, dim3(RED_BLOCKS, RED_JOBS), dim3(RED_T), 0, st, r);
-    MHIMX_LAUNCH_CHECK();
+    const float* parts[RED_JOBS] = {F(w.slab_1), F(w.slab_a), F(w.db1_part), F(w.dwc_part), F(w.dwp_part), F(w.dbp_part)};
+    const int32_t G[RED_JOBS] = {w.s1, w.sa, w.steps, w.steps, n_bags, n_bags};
+    const int64_t W[RED_JOBS] = {(int64_t)c.E * c.D, (int64_t)c.A * c.E, c.E, c.A, (int64_t)C * c.E, C};
+    float* out[RED_JOBS] = {c.grad.w1, c.grad.wa, c.grad.b1, c.grad.wc, c.grad.wp, c.grad.bp};
+    if (int r = pw_reduce(st, RED_JOBS, parts, G, W, out)) return r;
   }
   if (!update) return 0;
   // ---- 9. Adam
-  mhimx_optim_args o = {};
-  o.p = c.p; o.g = c.g; o.m = c.m; o.v = c.v; o.teacher = nullptr; o.n_train = c.n_train; o.n_all = c.n_all; o.step = host_step; o.step_dev = c.opt_step;
-  o.lr = c.lr; o.lr_table = c.lr_table; o.lr_len = c.lr_len; o.beta1 = c.beta1; o.beta2 = c.beta2; o.eps = c.eps; o.weight_decay = c.weight_decay;
-  o.grad_scale = 1.f; o.zero_grad = 1;
+  const mhimx_optim_args o = optim_args_of(c, host_step, false);
   return mhimx_optim_step(stream, &o);
 }

@@ -17,8 +17,8 @@
 //                                     same buffer first and are overwritten: TWO launches of the existing body, not a two-head instantiation)
 //      4  rw_pad_kernel               zero rows between a bag's 32-row boundary and the end of its slot (feature rows of both models,
 //                                     d out / d pre), the kept-row map cleared
-//      5  infer_score_kernel / infer_score_cproj_kernel   (infer.hip) the teacher's scores + one pool partial per 256 rows; attn2score = 1:
-//                                     the variant that also takes the class projections h . Wp_c while the rows are LDS-resident
+//      5  infer_score_kernel<false> / <true>   (infer.hip) the teacher's scores + one pool partial per 256 rows; attn2score = 1:
+//                                     the instantiation that also takes the class projections h . Wp_c while the rows are LDS-resident
 //      6  rw_finalize_kernel          plane = bag: the partials merged in index order -> {max, sum}, z_teacher; every row's instance score
 //                                     (attention, or the pseudo score of scoring.py:37-58 with its bp[0] quirk)
 //   B. the middle, bag after bag: mhimx_step_run's entry points in its order with pointers into the bag's slot (13 launches per bag of up
@@ -38,7 +38,7 @@
 //      1  rw_keep_kernel             the kept-row map: keep[row0_b + rows_all_b[j]] = 1, j < len_keep_b
 //      2  rw_dpre_kernel             one workgroup per 32-row tile of the row space: dPRE = dH * d out / d pre on kept rows, zero rows
 //                                    elsewhere (masked, padding and token rows), IN PLACE on the gradient rows; the tile's column sums
-//      3  pw_tn_kernel<true>         (pure_window.hip, as it is) d W1 = sum_b dPRE_b^T X_b over the row space: masked rows ride as zero
+//      3  pw_tn_kernel<true, XT>     (pure_window.hip, as it is) d W1 = sum_b dPRE_b^T X_b over the row space: masked rows ride as zero
 //                                    rows (<= n_sel / N of wasted k-steps, 1.5 % at the default ratios) instead of a gather
 //      4  pw_reduce_kernel           (pure_window.hip) d W1's slabs and d b1's per-tile partials in index order
 //      5  rw_q_chain_kernel          q <- mm^n q + (1 - mm) sum_b mm^(n-1-b) z_b on the bags' tokens
@@ -53,18 +53,14 @@ namespace mhimx {
 
 namespace {
 
-constexpr int RW_ROWS = 32, RW_T = 256, RW_CHUNK = 256;          // tile of the row space; rows of a pool partial (infer.hip SC_CHUNK)
-constexpr int FIN_T = 512, FIN_SCORE_BLOCKS = 8;
-constexpr int RW_MAX = MHIMX_RAGGED_WINDOW_MAX;
-static_assert(MHIMX_RAGGED_WINDOW_MAX == MHIMX_INFER_MAX, "the by-value bag table is the inference call's");
+constexpr int RW_ROWS = RG_ROWS, RW_T = 256;                     // tile of the row space
+constexpr int FIN_SCORE_BLOCKS = 8;
+constexpr int RW_MAX = MHIMX_RAGGED_WINDOW_MAX;                  // (= MHIMX_INFER_MAX: the by-value bag table is the inference call's)
 
 typedef _Float16 rw_h4 __attribute__((ext_vector_type(4)));
 
-// per-bag counts the window-wide launches need beyond the table (constant indices only: IT_PICK's rule)
+// per-bag counts the window-wide launches need beyond the table (constant indices only: RG_PICK's rule)
 struct RwCnt { int32_t len_keep[RW_MAX]; int32_t slot[RW_MAX]; };
-#define RW_PICK(dst, arr, b)                          \
-  _Pragma("unroll") for (int q_ = 0; q_ < RW_MAX; ++q_) \
-    if (q_ == (b)) dst = arr[q_];
 
 // ------------------------------------------------------------------------------------------------ A4. zero rows of a slot, kept-row map
 // blockIdx.x = bag.  The ragged projection zeroes a bag's rows up to the next multiple of 32; a slot of 32 * ceil((N + k) / 32) rows may
@@ -74,7 +70,7 @@ __global__ __launch_bounds__(RW_T) void rw_pad_kernel(InferTab tab, RwCnt cn, fl
   const int bag = blockIdx.x;
   int64_t N = tab.N[0], orow0 = tab.row0[0];
   int slot = cn.slot[0];
-  IT_PICK(N, N, bag) IT_PICK(orow0, row0, bag) RW_PICK(slot, cn.slot, bag)
+  RG_PICK(N, tab.N, bag) RG_PICK(orow0, tab.row0, bag) RG_PICK(slot, cn.slot, bag)
   for (int r = threadIdx.x + blockIdx.y * RW_T; r < slot; r += RW_T * gridDim.y) keep[orow0 + r] = 0;
   if (blockIdx.y != 0) return;
   const int64_t p0 = (N + 31) & ~(int64_t)31;
@@ -94,44 +90,27 @@ __global__ __launch_bounds__(RW_T) void rw_pad_kernel(InferTab tab, RwCnt cn, fl
 // blockIdx.y = 0: the pooled row z_teacher, stats.  blockIdx.y > 0: every row's instance score - the attention weight (attn2score = 0) or
 // mhimx_pseudo_score's arithmetic, score_n = 1 / sum_c exp(cam_c - max_c cam), cam_c = attn_n cproj[n, c] + bp[0] (scoring.py:37-58, the
 // class-0 bias for every class: :54).
-__global__ __launch_bounds__(FIN_T) void rw_finalize_kernel(InferTab tab, const float* __restrict__ pm, const float* __restrict__ pl,
+__global__ __launch_bounds__(RG_FIN_T) void rw_finalize_kernel(InferTab tab, const float* __restrict__ pm, const float* __restrict__ pl,
                                                             const float* __restrict__ pz, const float* __restrict__ s,
                                                             const float* __restrict__ cproj, const float* __restrict__ bp, int C,
                                                             int attn2score, float* __restrict__ z_out, float* __restrict__ stats,
                                                             float* __restrict__ score) {
   __shared__ float red[8];
-  __shared__ float wgt[FIN_T];
+  __shared__ float wgt[RG_FIN_T];
   const int bag = blockIdx.x;
-  int64_t N = tab.N[0], orow0 = tab.row0[0];
-  int p0 = tab.part0[0];
-  IT_PICK(N, N, bag) IT_PICK(orow0, row0, bag) IT_PICK(p0, part0, bag)
-  const int G = (int)((N + RW_CHUNK - 1) / RW_CHUNK);
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  RG_BAG(bag)
+  const int G = rg_parts(N);
+  const int tid = threadIdx.x;
   pm += p0; pl += p0; pz += (int64_t)p0 * IE;
-  float m = -INFINITY;
-  for (int b = tid; b < G; b += FIN_T) m = fmaxf(m, pm[b]);
-  m = wave_max(m);
-  if (lane == 0) red[wave] = m;
-  __syncthreads();
-  float mx = red[0];
-#pragma unroll
-  for (int w = 1; w < 8; ++w) mx = fmaxf(mx, red[w]);
-  __syncthreads();
-  float lp = 0.f;
-  for (int b = tid; b < G; b += FIN_T) lp += pl[b] * __expf(pm[b] - mx);
-  lp = wave_sum(lp);
-  if (lane == 0) red[wave] = lp;
-  __syncthreads();
-  float L = 0.f;
-#pragma unroll
-  for (int w = 0; w < 8; ++w) L += red[w];                    // fixed order: deterministic
+  float mx, L;
+  rg_merge_stats(pm, pl, G, 1, red, mx, L);
   const float invL = 1.f / L;
   if (blockIdx.y > 0) {
     const float* sb = s + orow0;
     float* ob = score + orow0;
     const float b0 = attn2score ? bp[0] : 0.f;
-    const int64_t step = (int64_t)(gridDim.y - 1) * FIN_T;
-    for (int64_t r = (int64_t)(blockIdx.y - 1) * FIN_T + tid; r < N; r += step) {
+    const int64_t step = (int64_t)(gridDim.y - 1) * RG_FIN_T;
+    for (int64_t r = (int64_t)(blockIdx.y - 1) * RG_FIN_T + tid; r < N; r += step) {
       const float an = __expf(sb[r] - mx) * invL;
       if (!attn2score) { ob[r] = an; continue; }
       const f32x4 cp = *reinterpret_cast<const f32x4*>(cproj + (orow0 + r) * 4);
@@ -149,11 +128,11 @@ __global__ __launch_bounds__(FIN_T) void rw_finalize_kernel(InferTab tab, const 
   }
   if (tid == 0) { stats[2 * bag] = mx; stats[2 * bag + 1] = L; }
   float acc = 0.f;                                            // column tid of the pooled row
-  for (int base = 0; base < G; base += FIN_T) {
+  for (int base = 0; base < G; base += RG_FIN_T) {
     __syncthreads();
     wgt[tid] = base + tid < G ? __expf(pm[base + tid] - mx) : 0.f;
     __syncthreads();
-    const int cnt = G - base < FIN_T ? G - base : FIN_T;
+    const int cnt = G - base < RG_FIN_T ? G - base : RG_FIN_T;
 #pragma unroll 8
     for (int j = 0; j < cnt; ++j) acc += pz[(int64_t)(base + j) * IE + tid] * wgt[j];
   }
@@ -167,7 +146,7 @@ __global__ __launch_bounds__(RW_T) void rw_keep_kernel(InferTab tab, RwCnt cn, c
   const int bag = blockIdx.x;
   int64_t N = tab.N[0], orow0 = tab.row0[0];
   int len_keep = cn.len_keep[0];
-  IT_PICK(N, N, bag) IT_PICK(orow0, row0, bag) RW_PICK(len_keep, cn.len_keep, bag)
+  RG_PICK(N, tab.N, bag) RG_PICK(orow0, tab.row0, bag) RG_PICK(len_keep, cn.len_keep, bag)
   const int64_t* rows = rows_all + orow0;
   for (int j = threadIdx.x + blockIdx.y * RW_T; j < len_keep; j += RW_T * gridDim.y) {
     const int64_t r = rows[j];
@@ -242,7 +221,7 @@ int64_t slot_rows(int64_t N, int64_t k) { return align_up(N + k, RW_ROWS); }
 
 // xdt: the element type of the bags' rows (MHIMX_X_*); the 2-byte types have their own pitch rule (16-byte rows: 8 elements)
 int check_rw(const mhimx_step_cfg* c, int32_t n_bags, const mhimx_ragged_window_bag* bags, int32_t xdt = MHIMX_X_F32) {
-  MHIMX_CHECK_ARG(xdt >= MHIMX_X_F32 && xdt <= MHIMX_X_BF16, "ragged_window: x_dtype %d is none of MHIMX_X_F32 / F16 / BF16", xdt);
+  if (int r = rg_check_xdt("ragged_window", xdt)) return r;
   MHIMX_CHECK_ARG(c && bags, "ragged_window: null configuration / bag list");
   MHIMX_CHECK_ARG(n_bags >= 1 && n_bags <= RW_MAX, "ragged_window: 1..%d bags per window (got %d)", RW_MAX, n_bags);
   MHIMX_CHECK_ARG(!c->q_out && !c->side_stream && !c->time_project, "ragged_window: q_out / side_stream / time_project are single-step options");
@@ -254,14 +233,7 @@ int check_rw(const mhimx_step_cfg* c, int32_t n_bags, const mhimx_ragged_window_
       const std::string why = last_error();
       return fail(-1, "ragged_window: bag %d (N = %lld): %s", b, (long long)q.N, why.c_str());
     }
-    if (xdt == MHIMX_X_F32) {
-      MHIMX_CHECK_ARG(q.ldx >= c->D && q.ldx % 4 == 0, "ragged_window: bag %d: row pitch below D or not a multiple of 4 floats", b);
-      MHIMX_CHECK_ARG(q.N * q.ldx * 4 < ((int64_t)1 << 32), "ragged_window: bag %d: N * ldx * 4 must stay below 2^32", b);
-    } else {
-      MHIMX_CHECK_ARG(q.ldx >= c->D && q.ldx % 8 == 0 && q.ldx <= (1 << 20),
-                      "ragged_window: bag %d: row pitch below D, above 2^20 or not a multiple of 8 two-byte elements", b);
-      MHIMX_CHECK_ARG(q.N * q.ldx * 2 < ((int64_t)1 << 32), "ragged_window: bag %d: N * ldx * 2 must stay below 2^32", b);
-    }
+    if (int r = rg_check_bag("ragged_window", b, q.N, q.ldx, c->D, xdt, RgRules{0, true})) return r;      // (N: step_check_cfg has checked it)
     rows += slot_rows(q.N, c->k);
     MHIMX_CHECK_ARG(rows <= MHIMX_RAGGED_WINDOW_MAX_ROWS, "ragged_window: bag %d: %lld rows in the window's row space up to this bag, at most %d", b,
                     (long long)rows, MHIMX_RAGGED_WINDOW_MAX_ROWS);
@@ -279,19 +251,13 @@ int check_rw(const mhimx_step_cfg* c, int32_t n_bags, const mhimx_ragged_window_
 
 void rw_layout(const mhimx_step_cfg* c, int32_t n_bags, const mhimx_ragged_window_bag* bags, RwLay* w, InferTab* tab, RwCnt* cn, int64_t* row0_out) {
   const int64_t E = c->E, D = c->D, A = c->A, k = c->k, n = n_bags, I = 512;
-  int64_t rows = 0, tiles = 0, parts = 0;
+  RgCount cnt;
   int64_t merge_b = 0, sel_b = 0, pool_b = 0, perm_n = 0, ids_n = 0, rows_n = 0, M_max = 0;
   for (int b = 0; b < n_bags; ++b) {
     const mhimx_ragged_window_bag& q = bags[b];
-    if (tab) {
-      tab->X[b] = q.X; tab->ldx[b] = q.ldx; tab->N[b] = q.N;
-      tab->row0[b] = rows; tab->tile0[b] = (int32_t)tiles; tab->part0[b] = (int32_t)parts;
-    }
     if (cn) { cn->len_keep[b] = (int32_t)q.cnt.len_keep; cn->slot[b] = (int32_t)slot_rows(q.N, k); }
-    if (row0_out) row0_out[b] = rows;
-    rows += slot_rows(q.N, k);
-    tiles += cdiv(q.N, INFER_TILE_ROWS);
-    parts += cdiv(q.N, RW_CHUNK);
+    if (row0_out) row0_out[b] = cnt.rows;
+    rg_tab_add(tab, cnt, b, q.X, q.ldx, q.N, slot_rows(q.N, k));
     const int64_t M = q.cnt.Lk + k;
     auto up = [](int64_t& a, int64_t v) { if (v > a) a = v; };
     up(merge_b, mhimx_merge_ws_bytes(q.cnt.R, E, k, 8, 64));
@@ -300,7 +266,8 @@ void rw_layout(const mhimx_step_cfg* c, int32_t n_bags, const mhimx_ragged_windo
     up(M_max, M);
     if (q.N > 16384) { up(perm_n, q.cnt.k_top); up(ids_n, q.N); up(rows_n, q.cnt.len_keep); }
   }
-  if (tab) { tab->n = n_bags; tab->tiles = (int32_t)tiles; tab->parts = (int32_t)parts; }
+  rg_tab_close(tab, cnt, n_bags);
+  const int64_t rows = cnt.rows, parts = cnt.parts;
   w->rows = rows;
   w->steps = (int32_t)(rows / RW_ROWS);
   const int s1_room = pw_split_k(w->steps, 8, 8, &w->s1, &w->s1_per);
@@ -384,8 +351,7 @@ extern "C" int mhimx_ragged_window_run_x(void* stream, const mhimx_step_cfg* cfg
   RwCnt cn = {};
   rw_layout(cfg, n_bags, bags, &w, &tab, &cn, nullptr);
   tab.pad = x_dtype;                           // read by the launches that read X: both projections and d W1
-  MHIMX_CHECK_ARG(ws && (reinterpret_cast<uintptr_t>(ws) & 255) == 0, "ragged_window: the workspace must be 256-byte aligned");
-  MHIMX_CHECK_ARG(ws_bytes >= w.total, "ragged_window: workspace too small (%lld bytes, need %lld)", (long long)ws_bytes, (long long)w.total);
+  if (int r = rg_check_ws("ragged_window", ws, ws_bytes, w.total)) return r;
   const mhimx_step_cfg& c = *cfg;
   const mhimx_step_params &S = c.student, &T = c.teacher;
   const int64_t D = c.D, E = c.E, A = c.A, C = c.C, k = c.k, I = 512;
@@ -440,7 +406,7 @@ extern "C" int mhimx_ragged_window_run_x(void* stream, const mhimx_step_cfg* cfg
     if (int r = infer_score_cproj(st, tab, H_t, wa_frag_t, T.wc, c.da_act, s_t, F(w.pm), F(w.pl), F(w.pz), T.wp, (int)C, cproj)) return r;
   } else if (int r = infer_score(st, tab, H_t, wa_frag_t, T.wc, c.da_act, s_t, F(w.pm), F(w.pl), F(w.pz)))
     return r;
-  hipLaunchKernelGGL(rw_finalize_kernel, dim3((unsigned)n_bags, 1 + FIN_SCORE_BLOCKS), dim3(FIN_T), 0, st, tab, F(w.pm), F(w.pl), F(w.pz), s_t, cproj, T.bp,
+  hipLaunchKernelGGL(rw_finalize_kernel, dim3((unsigned)n_bags, 1 + FIN_SCORE_BLOCKS), dim3(RG_FIN_T), 0, st, tab, F(w.pm), F(w.pl), F(w.pz), s_t, cproj, T.bp,
                      (int)C, (int)c.attn2score, F(w.z_t), F(w.stats_t), score_all);
   MHIMX_LAUNCH_CHECK();
 
@@ -553,9 +519,6 @@ extern "C" int mhimx_ragged_window_run_x(void* stream, const mhimx_step_cfg* cfg
     MHIMX_LAUNCH_CHECK();
   }
   if (!update) return 0;
-  mhimx_optim_args o = {};
-  o.p = c.p; o.g = c.g; o.m = c.m; o.v = c.v; o.teacher = c.p_teacher; o.n_train = c.n_train; o.n_all = c.n_all; o.step = host_step; o.step_dev = c.opt_step;
-  o.lr = c.lr; o.lr_table = c.lr_table; o.lr_len = c.lr_len; o.beta1 = c.beta1; o.beta2 = c.beta2; o.eps = c.eps; o.weight_decay = c.weight_decay;
-  o.grad_scale = 1.f; o.ema_mm = c.ema_mm; o.mm_table = c.mm_table; o.mm_len = c.mm_len; o.zero_grad = 1;
+  const mhimx_optim_args o = optim_args_of(c, host_step, true);
   return mhimx_optim_step(stream, &o);
 }

@@ -483,10 +483,8 @@ extern "C" int mhimx_step_run(void* stream, const mhimx_step_cfg* cfg, const flo
   if (!update) return mhimx_reduce_flush(stream, lm);
 
   // ---- 17. Adam + EMA teacher; the weight gradient's split-K slab sum is folded into the update
-  mhimx_optim_args o = {};
-  o.p = c.p; o.g = c.g; o.m = c.m; o.v = c.v; o.teacher = c.p_teacher; o.n_train = c.n_train; o.n_all = c.n_all; o.step = host_step; o.step_dev = c.opt_step;
-  o.lr = c.lr; o.lr_table = c.lr_table; o.lr_len = c.lr_len; o.beta1 = c.beta1; o.beta2 = c.beta2; o.eps = c.eps; o.weight_decay = c.weight_decay;
-  o.grad_scale = 1.f; o.ema_mm = c.ema_mm; o.mm_table = c.mm_table; o.mm_len = c.mm_len; o.zero_grad = 1; o.fold = lm;
+  mhimx_optim_args o = optim_args_of(c, host_step, true);
+  o.fold = lm;
   return mhimx_optim_step(stream, &o);
 }
 
@@ -789,10 +787,8 @@ extern "C" int mhimx_window_run(void* stream, const mhimx_step_cfg* cfg, int32_t
     return 0;
   }
   // ---- 17. Adam + EMA teacher on g + the bags' slabs; the weight gradient's split-K slab sum is folded into the update
-  mhimx_optim_args o = {};
-  o.p = c.p; o.g = c.g; o.m = c.m; o.v = c.v; o.teacher = c.p_teacher; o.n_train = c.n_train; o.n_all = c.n_all; o.step = host_step; o.step_dev = c.opt_step;
-  o.lr = c.lr; o.lr_table = c.lr_table; o.lr_len = c.lr_len; o.beta1 = c.beta1; o.beta2 = c.beta2; o.eps = c.eps; o.weight_decay = c.weight_decay;
-  o.grad_scale = 1.f; o.ema_mm = c.ema_mm; o.mm_table = c.mm_table; o.mm_len = c.mm_len; o.zero_grad = 1; o.fold = &lst_w;
+  mhimx_optim_args o = optim_args_of(c, host_step, true);
+  o.fold = &lst_w;
   o.g_extra = slab0; o.n_extra = n_bags; o.extra_pitch = BS / 4; o.extra_lo = g_lo; o.extra_only = 1;
   return mhimx_optim_step(stream, &o);
 }
@@ -986,10 +982,8 @@ extern "C" int mhimx_pure_step_run(void* stream, const mhimx_step_cfg* cfg, cons
   if (!update) return mhimx_reduce_flush(stream, &lst);
 
   // ---- 9. Adam; the weight gradient's split-K slab sum is folded into the update
-  mhimx_optim_args o = {};
-  o.p = c.p; o.g = c.g; o.m = c.m; o.v = c.v; o.teacher = nullptr; o.n_train = c.n_train; o.n_all = c.n_all; o.step = host_step; o.step_dev = c.opt_step;
-  o.lr = c.lr; o.lr_table = c.lr_table; o.lr_len = c.lr_len; o.beta1 = c.beta1; o.beta2 = c.beta2; o.eps = c.eps; o.weight_decay = c.weight_decay;
-  o.grad_scale = 1.f; o.zero_grad = 1; o.fold = &lst;
+  mhimx_optim_args o = optim_args_of(c, host_step, false);
+  o.fold = &lst;
   return mhimx_optim_step(stream, &o);
 }
 

@@ -1,9 +1,10 @@
 """Per-kernel resource table of a build: VGPRs, SGPRs, scratch (private segment), LDS, kernarg bytes - from the metadata notes of the code
 objects in a build directory's .o files.   python tools/kernel_meta.py mhim_mil_amd/build [other/build]  (two: only the kernels that differ)
 
-    python tools/kernel_meta.py --diff A/build B/build
+    python tools/kernel_meta.py --diff A/build B/build [--map OLD=NEW ...]
 the proof step of a "no existing kernel changed" claim: the kernels present in only one of the two builds, and the kernels whose
-disassembly (llvm-objdump -d without addresses and raw bytes, per symbol, end-of-function padding dropped) differs."""
+disassembly (llvm-objdump -d without addresses and raw bytes, per symbol, end-of-function padding dropped) differs.  --map OLD=NEW (repeatable) follows a renamed kernel: the one kernel only in A whose mangled name contains OLD
+and the one only in B whose name contains NEW are compared, and counted, like a kernel present in both."""
 import os, re, subprocess, sys, tempfile
 LLVM = "/opt/rocm/lib/llvm/bin"
 
@@ -51,15 +52,27 @@ def disasm(bdir):
 
 
 if sys.argv[1] == "--diff":
-    a, b = disasm(sys.argv[2]), disasm(sys.argv[3])
-    for k in sorted(set(a) - set(b)):
-        print("only in", sys.argv[2], k)
-    for k in sorted(set(b) - set(a)):
-        print("only in", sys.argv[3], k)
-    changed = [k for k in sorted(set(a) & set(b)) if a[k] != b[k]]
+    args, maps = sys.argv[2:], []
+    while "--map" in args:                                    # --map OLD=NEW: a kernel renamed between the two builds
+        i = args.index("--map")
+        maps.append(args[i + 1].split("=", 1))
+        del args[i:i + 2]
+    a, b = disasm(args[0]), disasm(args[1])
+    pairs = {k: k for k in set(a) & set(b)}
+    for old, new in maps:
+        ka, kb = [k for k in set(a) - set(b) if old in k], [k for k in set(b) - set(a) if new in k]
+        if len(ka) != 1 or len(kb) != 1:
+            sys.exit(f"--map {old}={new}: needs one kernel on each side, found {ka} and {kb}")
+        pairs[ka[0]] = kb[0]
+        print("mapped", ka[0], "->", kb[0])
+    for k in sorted(set(a) - set(pairs)):
+        print("only in", args[0], k)
+    for k in sorted(set(b) - set(pairs.values())):
+        print("only in", args[1], k)
+    changed = [k for k in sorted(pairs) if a[k] != b[pairs[k]]]
     for k in changed:
-        print("differs", k, f"({len(a[k])} vs {len(b[k])} instructions)")
-    print(f"{len(set(a) & set(b)) - len(changed)} kernels identical, {len(changed)} differ")
+        print("differs", k, f"({len(a[k])} vs {len(b[pairs[k]])} instructions)")
+    print(f"{len(pairs) - len(changed)} kernels identical, {len(changed)} differ")
     sys.exit(1 if changed else 0)
 a = meta(sys.argv[1])
 b = meta(sys.argv[2]) if len(sys.argv) > 2 else None
