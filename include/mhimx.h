@@ -687,6 +687,8 @@ int mhimx_colsum(void* stream, const float* X, int64_t M, int64_t E, float* out,
  *  g_z[E], d_wp[C,E], d_bp[C] (of `loss`).  t may be NULL (aux term skipped, common_mil.py:24).
  *  Autograd form: label_dev == NULL and g_logits_in[C] / g_cl_in[1] (device) carry the upstream gradients
  *  of an externally computed criterion (the reference's trainer applies nn.CrossEntropyLoss itself).
+ *  Then ce = 0, losses[3] = {a * cl, 0, cl} and g_z = Wp^T g_logits_in + a * inv_accum * d cl/dz with a = g_cl_in[0]
+ *  (aux_alpha without g_cl_in; g_logits_in NULL: zeros, so d_wp = d_bp = 0); g_logits_in is taken as given (not scaled).
  * ---------------------------------------------------------------------------------------- */
 int mhimx_head_fwd_bwd(void* stream, const float* z, const float* t, const float* wp, const float* bp,
                        const int64_t* label_dev, int64_t E, int64_t C, float temp_t, float main_alpha,

@@ -25,6 +25,16 @@ MHIMX_DEV float blk_max(float v, float* red) {
   return fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
 }
 
+// a product rounded on its own: never contracted into the addition that follows.  The predictor's weight gradient is gl * z, and an
+// accumulating launch adds exactly that rounded value to what the buffer holds (one fp32 addition per element) - the bits of writing
+// the gradient and summing it afterwards, as the slab routes of the accumulation windows do
+// (the pragma holds under hipcc's default -ffp-contract=fast-honor-pragmas; a build line with a plain -ffp-contract=fast would ignore it -
+// build.py says so beside FLAGS - and test_head_accumulate_and_null_gradients then fails)
+MHIMX_DEV float mul_rounded(float a, float b) {
+#pragma clang fp contract(off)
+  return a * b;
+}
+
 // One block.  C <= 16 classes.
 __global__ __launch_bounds__(HEAD_THREADS) void head_kernel(const float* __restrict__ z, const float* __restrict__ t,
                                                             const float* __restrict__ wp, const float* __restrict__ bp,
@@ -93,7 +103,7 @@ __global__ __launch_bounds__(HEAD_THREADS) void head_kernel(const float* __restr
     g_z[e] = g;
     if (d_wp)
       for (int c = 0; c < C; ++c) {
-        const float v = gl[c] * z[e];
+        const float v = mul_rounded(gl[c], z[e]);
         d_wp[c * E + e] = accumulate ? d_wp[c * E + e] + v : v;
       }
   }
@@ -239,7 +249,7 @@ __global__ __launch_bounds__(HEAD_THREADS) void head_fast_kernel(const float* __
 #pragma unroll
       for (int c = 0; c < 4; ++c)
         if (c < C) {
-          const float v = gl[c] * zv[q];
+          const float v = mul_rounded(gl[c], zv[q]);
           d_wp[c * E + e] = accumulate ? dw_old[c][q] + v : v;
         }
     }

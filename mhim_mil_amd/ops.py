@@ -888,10 +888,12 @@ def adam_ema(p, g, m, v, teacher, n_train, step, lr=2e-4, beta1=0.9, beta2=0.999
 
 
 def optim_step(p, g, m, v, teacher, n_train, step, lr=2e-4, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=1e-5, grad_scale=1.0,
-               ema_mm=0.9997, zero_grad=True, step_dev=None, mm_table=None, lr_table=None, g_extra=None, clip_norm=None, ws=None, fold=None):
+               ema_mm=0.9997, zero_grad=True, step_dev=None, mm_table=None, lr_table=None, g_extra=None, clip_norm=None, ws=None, fold=None,
+               extra_lo=0, extra_only=False):
     """mhimx_optim_step: fused Adam + EMA with the optional device-side pieces - ``lr_table`` (per-update schedule), ``g_extra``
-    ([S, pitch] gradient slabs added to g first), ``clip_norm`` (clip_grad_norm_; ``ws``: >= 1024 floats), ``fold`` (a ReduceList: its
-    split-K slab sums into g are performed by the update kernel itself, the rest is flushed first)."""
+    ([S, pitch] gradient slabs added to g first; ``extra_lo`` / ``extra_only``: the slabs cover [extra_lo, n_train) only / are the
+    whole gradient there), ``clip_norm`` (clip_grad_norm_; ``ws``: >= 1024 floats), ``fold`` (a ReduceList: its split-K slab sums
+    into g are performed by the update kernel itself, the rest is flushed first)."""
     _chk(g_extra, name="g_extra"); _chk(lr_table, name="lr_table"); _chk(mm_table, name="mm_table")
     if clip_norm and ws is None:
         ws = torch.empty(1024, device=p.device)
@@ -901,7 +903,7 @@ def optim_step(p, g, m, v, teacher, n_train, step, lr=2e-4, beta1=0.9, beta2=0.9
                     ema_mm=float(ema_mm), mm_table=_p(mm_table), mm_len=0 if mm_table is None else mm_table.numel(),
                     zero_grad=int(bool(zero_grad)), g_extra=_p(g_extra), n_extra=0 if g_extra is None else g_extra.shape[0],
                     extra_pitch=0 if g_extra is None else g_extra.stride(0), clip_norm=float(clip_norm or 0.0), ws=_p(ws),
-                    ws_floats=0 if ws is None else ws.numel(), fold=_dp(fold))
+                    ws_floats=0 if ws is None else ws.numel(), fold=_dp(fold), extra_lo=int(extra_lo), extra_only=int(bool(extra_only)))
     L.check(L.lib().mhimx_optim_step(_stream(), C.byref(a)), "mhimx_optim_step")
     if fold is not None:
         fold.keep.clear()                      # (the slabs were read by the launch just enqueued; stream order protects them)
