@@ -518,33 +518,42 @@ class FusedTrainer:
                 return False
             return self.pure_exec_shapes_ok(x.shape[0], x.shape[1], x.stride(0), x.stride(1), x.data_ptr(), E=s.mlp_dim,
                                             A=s.online_encoder.attention.attention[0].weight.shape[0], C=s.n_classes, max_rows=self.exec_max_rows)
-        if not (self.use_executor and self.model_kind == "mhim" and (self.accum == 1 or window) and not hooked and perm is None
-                and ids_shuffle is None and s.training and s.n_classes <= 4 and s._op_prec != "f32"
-                and s.merge.k * 8 <= 48 and x.shape[1] % 256 == 0 and x.stride(0) % 4 == 0 and x.shape[0] * x.stride(0) * 4 < (1 << 32)):
-            return False
-        # (csrc/step.hip:check_cfg and mhimx_step_run's own argument checks, mirrored: a bag they would refuse takes the Python path instead
-        # of raising - ADVICE r5)
         mg = s.merge
-        att = s.online_encoder.attention.attention
-        if not (s.mlp_dim == 512 and att[0].weight.shape[0] == 128 and x.data_ptr() % 16 == 0 and x.stride(0) >= x.shape[1] and x.stride(1) == 1
-                and mg.attn.to_q.weight.shape[0] == 512 and mg.attn.to_kv.weight.shape[0] == 1024 and 64 <= x.shape[0] <= self.exec_max_rows):
+        if not (self.use_executor and self.model_kind == "mhim" and (self.accum == 1 or window) and not hooked and perm is None
+                and ids_shuffle is None and s.training and s._op_prec != "f32"
+                and mg.attn.to_q.weight.shape[0] == 512 and mg.attn.to_kv.weight.shape[0] == 1024):
             return False
         c = s.v2_counts(x.shape[0], i)
         if c is None:
             return False
         # up to 16 384 rows: both random subsets drawn inside the one-workgroup select; above (round 6): the multi-workgroup select with the
         # draws as keyed permutations - the launches MHIM.student_rows issues for such bags
-        if not (s.device_draw_ok(x.shape[0], i) if x.shape[0] <= 16384 else (s.baseline == "attn" and c[0] <= 16384)):
+        if not (s.device_draw_ok(x.shape[0], i) if x.shape[0] <= 16384 else s.baseline == "attn"):
             return False
-        return 1 <= c[0] and c[3] >= 1 and 1 <= c[4] <= 32768
+        return self.step_exec_shapes_ok(x.shape[0], x.shape[1], x.stride(0), x.stride(1), x.data_ptr(), c, mg.k, E=s.mlp_dim,
+                                        A=s.online_encoder.attention.attention[0].weight.shape[0], C=s.n_classes, max_rows=self.exec_max_rows)
+
+    @staticmethod
+    def _step_counts_ok(N, cnt, max_rows):
+        """csrc/step.hip check_cfg's rule for a bag's row count and its (k_top, n_sel, len_keep, Lk, R)."""
+        k_top, n_sel, len_keep, Lk, R = cnt
+        return bool(64 <= N <= max_rows and 1 <= k_top <= (4096 if N <= 16384 else 16384) and 1 <= n_sel <= k_top
+                    and len_keep == N - n_sel and Lk >= 1 and 1 <= R <= 32768 and Lk + R == len_keep)
+
+    @staticmethod
+    def step_exec_shapes_ok(N, D, pitch, inner, ptr, counts, k, E=512, A=128, C=2, max_rows=262144):
+        """The tensor-free part of _exec_ok's mhim branch - csrc/step.hip check_cfg and mhimx_step_run's own argument checks, mirrored: a
+        bag the call would refuse takes the Python path instead of raising.  (N, D): the bag's shape; pitch, inner: its
+        strides in floats; ptr: its address; counts: its (k_top, n_sel, len_keep, Lk, R); k: merge_k."""
+        return bool(ops.model_dims_ok(E, A, C, D) and 1 <= k and 8 * k <= 48 and FusedTrainer._step_counts_ok(N, counts, max_rows)
+                    and ops.bag_rows_ok(N, D, pitch, inner, ptr, 4, 0, True))
 
     @staticmethod
     def pure_exec_shapes_ok(N, D, pitch, inner, ptr, E=512, A=128, C=2, max_rows=262144):
         """The tensor-free part of _exec_ok's pure branch - csrc/step.hip check_pure_cfg and mhimx_pure_step_run's own argument checks,
         mirrored: a bag the call would refuse takes the Python path instead of raising.  (N, D): the bag's shape; pitch, inner: its strides
         in floats; ptr: its address."""
-        return bool(E == 512 and A == 128 and 1 <= C <= 4 and D > 0 and D % 256 == 0 and 64 <= N <= max_rows and inner == 1 and pitch >= D
-                    and pitch % 4 == 0 and N * pitch * 4 < (1 << 32) and ptr % 16 == 0)
+        return bool(ops.model_dims_ok(E, A, C, D) and 64 <= N <= max_rows and ops.bag_rows_ok(N, D, pitch, inner, ptr, 4, 0, True))
 
     @staticmethod
     def pure_window_shapes_ok(bags, D, E=512, A=128, C=2, max_rows=262144, row_cap=524288, max_bags=32, elem=4):
@@ -552,15 +561,11 @@ class FusedTrainer:
         refuse takes the bag-after-bag route instead of raising.  ``bags``: one (N, D, pitch, inner, ptr) per bag - shape, strides in
         elements, address; ``D``: the model's input width; ``elem``: bytes of an element of the bags' rows (4: fp32; 2: fp16 / bf16, whose
         pitch is a multiple of 8 elements and at most 2^20)."""
-        if elem not in (2, 4):
-            return False
-        unit = 16 // elem
-        if not (E == 512 and A == 128 and 1 <= C <= 4 and D > 0 and D % 256 == 0 and D <= (1 << 20) and 1 <= len(bags) <= max_bags):
+        if not (ops.model_dims_ok(E, A, C, D) and D <= (1 << 20) and 1 <= len(bags) <= max_bags):
             return False
         rows = 0
         for N, Db, pitch, inner, ptr in bags:
-            if not (Db == D and 1 <= N <= max_rows and inner == 1 and pitch >= D and pitch % unit == 0 and N * pitch * elem < (1 << 32)
-                    and (elem == 4 or pitch <= (1 << 20)) and ptr != 0 and ptr % 16 == 0):
+            if not (Db == D and ops.bag_rows_ok(N, D, pitch, inner, ptr, elem, max_rows, True)):
                 return False
             rows += (N + 31) // 32 * 32
         return rows <= row_cap
@@ -578,7 +583,7 @@ class FusedTrainer:
         if not all(torch.is_tensor(x) and x.is_cuda and x.dtype == xs[0].dtype and x.dim() == 2 and x.device == dev
                    and s._feature_prec(x.shape[0]) == "bf16x3" for x in xs) or xs[0].dtype not in ops._X_DTYPES:
             return False
-        if not all(torch.is_tensor(l) and l.is_cuda and l.dtype == torch.int64 and l.numel() == 1 and l.device == dev for l in labels):
+        if not ops.window_labels_ok(labels, dev):
             return False
         return self.pure_window_shapes_ok([(x.shape[0], x.shape[1], x.stride(0), x.stride(1), x.data_ptr()) for x in xs], s.input_dim,
                                           E=s.mlp_dim, A=s.online_encoder.attention.attention[0].weight.shape[0], C=s.n_classes,
@@ -589,48 +594,70 @@ class FusedTrainer:
         """One accumulation window of the teacher-free model - 1 .. accumulation_steps bags of any row counts, every loss scaled by
         1 / len(bags) - as ONE call of mhimx_pure_window_run.  Returns ([logits per bag], [losses per bag]); self.last keeps the layout,
         the workspace and every bag's views."""
-        L = mh.L
         s, fl = self.s, self.flat
         n = len(xs)
         ex = self._exec_cfg()
         table = ops.pure_window_bags(xs, labels, [0] * n)
         lay = ops.pure_window_layout(ex["cfg"], table, n)
-        dev = xs[0].device
-        if torch.cuda.is_current_stream_capturing():
-            ws = torch.empty(lay.total, dtype=torch.uint8, device=dev)
-        else:
-            ws = ex.get("ws_pw")
-            if ws is None or ws.numel() < lay.total or ws.device != dev:
-                ws = ex["ws_pw"] = torch.full((int(lay.total * 1.25),), 255, dtype=torch.uint8, device=dev)      # (poisoned: see _exec_window)
+        ws = ops.workspace(ex, "ws_pw", lay.total, xs[0].device)
         for j in range(n):                                          # ONE seed per bag, in bag order: the feature dropout's
             table[j].drop_seed = s._next_seed()
         inside = bool(update and not self.clip_grad)                # (clipping needs the norm of the final gradient: the update stays outside)
         ops.pure_window_run(ex["cfg"], table, n, fl.step + int(inside), ws, inside, x_dtype=ops.x_dtype_of(xs))
-        E, Cc = s.mlp_dim, s.n_classes
-
-        def view(off, cnt_, dtype=torch.float32):
-            return ws[off:off + cnt_ * dtype.itemsize].view(dtype)
-
-        lg, ls = view(lay.logits, n * Cc).view(n, Cc), view(lay.losses, n * 3).view(n, 3)
-        H = view(lay.H, lay.rows * E).view(lay.rows, E)
-        dact = view(lay.dact, lay.rows * E, torch.float16).view(lay.rows, E)
+        E, Cc, view = s.mlp_dim, s.n_classes, ops.ws_view
+        lg, ls = view(ws, lay.logits, n * Cc).view(n, Cc), view(ws, lay.losses, n * 3).view(n, 3)
+        H = view(ws, lay.H, lay.rows * E).view(lay.rows, E)
+        dact = view(ws, lay.dact, lay.rows * E, torch.float16).view(lay.rows, E)
         per = []
         for j, x in enumerate(xs):
             r0, N = int(lay.row0[j]), x.shape[0]
             per.append({"logits": lg[j], "losses": ls[j], "patch_num": N, "keep_num": N, "row0": r0, "H_student": H[r0:r0 + N],
                         "dact": dact[r0:r0 + N]})
         logits, losses = [p["logits"] for p in per], [p["losses"] for p in per]
-        self.last = {"logits": logits, "losses": losses, "patch_num": per[-1]["patch_num"], "keep_num": per[-1]["keep_num"], "rows": None,
-                     "score": None, "R": 0, "tokens": None, "H_student": per[-1]["H_student"], "H_teacher": None, "bags": per, "layout": lay,
-                     "ws": ws, "exec": True, "x_dtype": xs[0].dtype}
+        self.last = dict(self._last_pure(logits, losses, per[-1]["H_student"]), bags=per, layout=lay, ws=ws, exec=True, x_dtype=xs[0].dtype)
+        self._window_done(n, inside, update)
+        return logits, losses
+
+    @staticmethod
+    def _last_pure(logits, losses, H):
+        """self.last of a teacher-free bag with the feature rows H [N, E]: no row list, no score, no tokens, no teacher."""
+        N = H.shape[0]
+        return {"logits": logits, "losses": losses, "patch_num": N, "keep_num": N, "rows": None, "score": None, "R": 0, "tokens": None,
+                "H_student": H, "H_teacher": None}
+
+    def _last_full(self, ws, lay, N, cnt, logits, losses, base=0, r0=0):
+        """self.last of a bag of the full model: views of the workspace at the layout's offsets; ``base``: the bag's byte offset in a
+        same-shape window, ``r0``: its first row in a ragged window's row space."""
+        view, km, E = ops.ws_view, self.s.merge.k, self.s.mlp_dim
+        Hs = view(ws, base + lay.H_student + 4 * E * r0, (N + km) * E).view(N + km, E)
+        return {"logits": logits, "losses": losses, "patch_num": N, "keep_num": cnt.Lk + km,
+                "rows": view(ws, base + lay.rows_all + 8 * r0, cnt.len_keep, torch.int64), "score": view(ws, base + lay.score + 4 * r0, N),
+                "R": cnt.R, "tokens": Hs[N:], "H_student": Hs[:N], "H_teacher": view(ws, base + lay.H_teacher + 4 * E * r0, N * E).view(N, E)}
+
+    def _step_seeds(self):
+        """A bag's four draws in the single-bag order: both dropout streams, the select's, Merge's."""
+        s, t = self.s, self.t
+        return mh.L.StepSeeds(drop_teacher=t._next_seed(teacher=True), drop_student=s._next_seed(), select=s._next_seed(), mca=s._next_seed())
+
+    def _window_done(self, n, inside, update):
+        """The host's bookkeeping behind a window call of n bags: ``inside`` - the call made the update; else ``update`` makes it now."""
         self._micro = n
         if inside:
-            fl.step += 1
+            self.flat.step += 1
             ops.step_images(None)
             self._micro = 0
         elif update:
             self.update()
-        return logits, losses
+
+    def _steps_done(self, updated, n=1):
+        """Its single-bag twin, behind a call of n bags that each made their update (``updated``) or one bag that did not.  Only a step
+        that was enqueued counts: a refused call leaves host and device counters equal."""
+        if updated:
+            self.flat.step += n
+            ops.step_images(None)
+            self._micro = 0
+        else:
+            self._micro += 1
 
     @staticmethod
     def _half_bags(bags):
@@ -733,14 +760,13 @@ class FusedTrainer:
         x0 = xs[0]
         if not (x0.dim() == 2 and x0.shape[0] <= 16384 and all(x.shape == x0.shape and x.stride() == x0.stride() and x.device == x0.device for x in xs)):
             return False
-        if not all(torch.is_tensor(l) and l.is_cuda and l.dtype == torch.int64 and l.numel() == 1 and l.device == x0.device for l in labels):
+        if not ops.window_labels_ok(labels, x0.device):
             return False
         return all(self._exec_ok(x, i, window=True) for x in xs)
 
     def _exec_window(self, xs, labels, i, update):
         """One accumulation window as ONE call of mhimx_window_run: every launch between the projections and the weight gradient covers all
         the bags (include/mhimx.h).  Returns ([logits per bag], [losses per bag]); self.last["bags"] holds each bag's views."""
-        import ctypes as C
         L = mh.L
         s, t, fl = self.s, self.t, self.flat
         n = len(xs)
@@ -751,19 +777,9 @@ class FusedTrainer:
         ent = ex["layouts"].get(key)
         if ent is None:
             cnt = L.StepCounts(k_top=k, n_sel=n_sel, len_keep=len_keep, Lk=Lk, R=R)
-            lay = L.WindowLayout()
-            L.check(L.lib().mhimx_window_layout_of(C.byref(ex["cfg"]), n, N, C.byref(cnt), C.byref(lay)), "mhimx_window_layout_of")
-            ent = ex["layouts"][key] = (cnt, lay)
+            ent = ex["layouts"][key] = (cnt, ops.window_layout(ex["cfg"], n, N, cnt))
         cnt, lay = ent
-        dev = xs[0].device
-        if torch.cuda.is_current_stream_capturing():
-            ws = torch.empty(lay.total, dtype=torch.uint8, device=dev)
-        else:
-            ws = ex.get("ws_win")
-            if ws is None or ws.numel() < lay.total or ws.device != dev:
-                # (poisoned once, when it is made: 0xFF bytes are NaNs - a launch that read workspace memory no launch of the window wrote
-                # would show up in every eager test instead of depending on what the allocator's block held before)
-                ws = ex["ws_win"] = torch.full((lay.total,), 255, dtype=torch.uint8, device=dev)
+        ws = ops.workspace(ex, "ws_win", lay.total, xs[0].device, slack=1.0)      # (exactly the window's bytes: its layout is cached by shape)
         # (the order the stream form with MHIMX_WINDOW_PROJECT=1 draws them in: every bag's dropout streams at the projection, then bag
         # after bag the select's and Merge's - the two forms of a window make the same draws)
         seeds = (L.StepSeeds * n)()
@@ -771,35 +787,16 @@ class FusedTrainer:
             seeds[j].drop_teacher, seeds[j].drop_student = t._next_seed(teacher=True), s._next_seed()
         for j in range(n):
             seeds[j].select, seeds[j].mca = s._next_seed(), s._next_seed()
-        Xp = (C.c_void_p * n)(*[x.data_ptr() for x in xs])
-        Lp = (C.c_void_p * n)(*[l.data_ptr() for l in labels])
         inside = bool(update and not self.clip_grad)              # (clipping needs the norm of the final gradient: the update stays outside)
-        L.check(L.lib().mhimx_window_run(ops._stream(), C.byref(ex["cfg"]), n, Xp, xs[0].stride(0), N, Lp, C.byref(cnt), seeds,
-                                         fl.step + int(inside), ws.data_ptr(), ws.numel(), int(inside)), "mhimx_window_run")
-        km, E = s.merge.k, s.mlp_dim
+        ops.window_run(ex["cfg"], xs, labels, cnt, seeds, fl.step + int(inside), ws, inside)
         bg = lay.bag
-
-        def view(off, j, cnt_, dtype=torch.float32):
-            o = off + j * lay.bag_stride
-            return ws[o:o + cnt_ * dtype.itemsize].view(dtype)
-
-        per, logits, losses = [], [], []
+        per = []
         for j in range(n):
-            Hs = view(bg.H_student, j, (N + km) * E).view(N + km, E)
-            lg, ls = view(bg.logits, j, s.n_classes), view(bg.losses, j, 3)
-            rows_all = view(bg.rows_all, j, cnt.len_keep + km, torch.int64)
-            per.append({"logits": lg, "losses": ls, "patch_num": N, "keep_num": cnt.Lk + km, "rows": rows_all[:cnt.len_keep],
-                        "score": view(bg.score, j, N), "R": cnt.R, "tokens": Hs[N:], "H_student": Hs[:N],
-                        "H_teacher": view(bg.H_teacher, j, N * E).view(N, E)})
-            logits.append(lg); losses.append(ls)
+            base = j * lay.bag_stride
+            per.append(self._last_full(ws, bg, N, cnt, ops.ws_view(ws, base + bg.logits, s.n_classes), ops.ws_view(ws, base + bg.losses, 3), base=base))
+        logits, losses = [p["logits"] for p in per], [p["losses"] for p in per]
         self.last = dict(per[-1], logits=logits, losses=losses, bags=per, ws=ws, exec="mhimx_window_run")
-        self._micro = n
-        if inside:
-            fl.step += 1
-            ops.step_images(None)
-            self._micro = 0
-        elif update:
-            self.update()
+        self._window_done(n, inside, update)
         return logits, losses
 
     # ------------------------------------------------------------------------------------------------- the ragged window behind the C-ABI
@@ -810,20 +807,11 @@ class FusedTrainer:
         (k_top, n_sel, len_keep, Lk, R)) per bag - shape, strides in elements, address, its counts; ``D``: the model's input width; ``k``:
         merge_k; ``elem``: bytes of an element of the bags' rows (4: fp32; 2: fp16 / bf16, whose pitch is a multiple of 8 elements and at
         most 2^20)."""
-        if elem not in (2, 4):
-            return False
-        unit = 16 // elem
-        if not (E == 512 and A == 128 and 1 <= C <= 4 and k >= 1 and 8 * k <= 48 and D > 0 and D % 256 == 0 and D <= (1 << 20)
-                and 1 <= len(bags) <= max_bags):
+        if not (ops.model_dims_ok(E, A, C, D) and k >= 1 and 8 * k <= 48 and D <= (1 << 20) and 1 <= len(bags) <= max_bags):
             return False
         rows = 0
         for N, Db, pitch, inner, ptr, cnt in bags:
-            k_top, n_sel, len_keep, Lk, R = cnt
-            if not (Db == D and 64 <= N <= max_rows and 1 <= k_top <= (4096 if N <= 16384 else 16384) and 1 <= n_sel <= k_top
-                    and len_keep == N - n_sel and Lk >= 1 and 1 <= R <= 32768 and Lk + R == len_keep):
-                return False
-            if not (inner == 1 and pitch >= D and pitch % unit == 0 and N * pitch * elem < (1 << 32) and (elem == 4 or pitch <= (1 << 20))
-                    and ptr != 0 and ptr % 16 == 0):
+            if not (Db == D and FusedTrainer._step_counts_ok(N, cnt, max_rows) and ops.bag_rows_ok(N, D, pitch, inner, ptr, elem, 0, True)):
                 return False
             rows += (N + k + 31) // 32 * 32
         return rows <= row_cap
@@ -842,7 +830,7 @@ class FusedTrainer:
         if not all(torch.is_tensor(x) and x.is_cuda and x.dtype == xs[0].dtype and x.dim() == 2 and x.device == dev for x in xs) \
                 or xs[0].dtype not in ops._X_DTYPES:
             return False
-        if not all(torch.is_tensor(l) and l.is_cuda and l.dtype == torch.int64 and l.numel() == 1 and l.device == dev for l in labels):
+        if not ops.window_labels_ok(labels, dev):
             return False
         if not all(self._nat_ok(x, i) and self._exec_ok(x, i, window=True) for x in xs):
             return False
@@ -855,7 +843,7 @@ class FusedTrainer:
         """One accumulation window of different-sized bags - 1 .. accumulation_steps of them, every loss scaled by 1 / len(bags) - as ONE
         call of mhimx_ragged_window_run.  Returns ([logits per bag], [losses per bag]); self.last["bags"] holds each bag's views."""
         L = mh.L
-        s, t, fl = self.s, self.t, self.flat
+        s, fl = self.s, self.flat
         n = len(xs)
         ex = self._exec_cfg()
         table = (L.RaggedWindowBag * n)()
@@ -864,129 +852,66 @@ class FusedTrainer:
             table[j].X, table[j].ldx, table[j].N, table[j].label_dev = x.data_ptr(), x.stride(0), x.shape[0], l.data_ptr()
             table[j].cnt = L.StepCounts(k_top=k_top, n_sel=n_sel, len_keep=len_keep, Lk=Lk, R=R)
         lay = ops.ragged_window(ex["cfg"], table, n, layout_only=True)
-        dev = xs[0].device
-        if torch.cuda.is_current_stream_capturing():
-            ws = torch.empty(lay.total, dtype=torch.uint8, device=dev)
-        else:
-            ws = ex.get("ws_rw")
-            if ws is None or ws.numel() < lay.total or ws.device != dev:
-                ws = ex["ws_rw"] = torch.full((int(lay.total * 1.25),), 255, dtype=torch.uint8, device=dev)      # (poisoned: see _exec_window)
+        ws = ops.workspace(ex, "ws_rw", lay.total, xs[0].device)
         # (bag after bag - both dropout streams, the select's, Merge's - the order the stream form draws them in for such a window: the
         # two routes make the same draws)
         for j in range(n):
-            table[j].seeds = L.StepSeeds(drop_teacher=t._next_seed(teacher=True), drop_student=s._next_seed(), select=s._next_seed(),
-                                         mca=s._next_seed())
+            table[j].seeds = self._step_seeds()
         inside = bool(update and not self.clip_grad)              # (clipping needs the norm of the final gradient: the update stays outside)
         ops.ragged_window(ex["cfg"], table, n, fl.step + int(inside), ws, inside, x_dtype=ops.x_dtype_of(xs))
-        km, E, Cc = s.merge.k, s.mlp_dim, s.n_classes
-
-        def view(off, cnt_, dtype=torch.float32):
-            return ws[off:off + cnt_ * dtype.itemsize].view(dtype)
-
-        lg, ls = view(lay.logits, n * 16).view(n, 16), view(lay.losses, n * 4).view(n, 4)
-        Hs, Ht = view(lay.H_student, lay.rows * E).view(lay.rows, E), view(lay.H_teacher, lay.rows * E).view(lay.rows, E)
-        dact = view(lay.dact, lay.rows * E, torch.float16).view(lay.rows, E)
-        score, rows_all = view(lay.score, lay.rows), view(lay.rows_all, lay.rows, torch.int64)
-        zt, zs = view(lay.z_teacher, n * E).view(n, E), view(lay.z_student, n * E).view(n, E)
+        E, Cc, view = s.mlp_dim, s.n_classes, ops.ws_view
+        lg, ls = view(ws, lay.logits, n * 16).view(n, 16), view(ws, lay.losses, n * 4).view(n, 4)
+        dact = view(ws, lay.dact, lay.rows * E, torch.float16).view(lay.rows, E)
+        zt, zs = view(ws, lay.z_teacher, n * E).view(n, E), view(ws, lay.z_student, n * E).view(n, E)
         per = []
         for j, x in enumerate(xs):
-            r0, N, cnt = int(lay.row0[j]), x.shape[0], table[j].cnt
-            per.append({"logits": lg[j, :Cc], "losses": ls[j, :3], "patch_num": N, "keep_num": cnt.Lk + km, "rows": rows_all[r0:r0 + cnt.len_keep],
-                        "score": score[r0:r0 + N], "R": cnt.R, "tokens": Hs[r0 + N:r0 + N + km], "H_student": Hs[r0:r0 + N],
-                        "H_teacher": Ht[r0:r0 + N], "dact": dact[r0:r0 + N], "z_teacher": zt[j], "z_student": zs[j], "row0": r0})
+            r0, N = int(lay.row0[j]), x.shape[0]
+            per.append(dict(self._last_full(ws, lay, N, table[j].cnt, lg[j, :Cc], ls[j, :3], r0=r0), dact=dact[r0:r0 + N], z_teacher=zt[j],
+                            z_student=zs[j], row0=r0))
         logits, losses = [p_["logits"] for p_ in per], [p_["losses"] for p_ in per]
         self.last = dict(per[-1], logits=logits, losses=losses, bags=per, layout=lay, table=table, ws=ws, exec="mhimx_ragged_window_run",
                          x_dtype=xs[0].dtype)
-        self._micro = n
-        if inside:
-            fl.step += 1
-            ops.step_images(None)
-            self._micro = 0
-        elif update:
-            self.update()
+        self._window_done(n, inside, update)
         return logits, losses
 
     def _exec_plan(self, ex, N, i):
         """(counts, layout) of a bag of N rows at iteration i - cached: they follow from N and the HAM ratio alone."""
-        import ctypes as C
-        L = mh.L
-        if self.model_kind == "mhim_pure":              # (no counts: every row takes part)
-            ent = ex["layouts"].get(("pure", N))
-            if ent is None:
-                lay = L.StepLayout()
-                L.check(L.lib().mhimx_pure_step_layout_of(C.byref(ex["cfg"]), N, C.byref(lay)), "mhimx_pure_step_layout_of")
-                ent = ex["layouts"][("pure", N)] = (None, lay)
-            return ent
-        k, n_sel, len_keep, Lk, R = self.s.v2_counts(N, i)
-        key = (N, k, n_sel, Lk)
+        pure = self.model_kind == "mhim_pure"              # (no counts: every row takes part)
+        c = None if pure else self.s.v2_counts(N, i)
+        key = ("pure", N) if pure else (N, c[0], c[1], c[3])
         ent = ex["layouts"].get(key)
         if ent is None:
-            cnt = L.StepCounts(k_top=k, n_sel=n_sel, len_keep=len_keep, Lk=Lk, R=R)
-            lay = L.StepLayout()
-            L.check(L.lib().mhimx_step_layout_of(C.byref(ex["cfg"]), N, C.byref(cnt), C.byref(lay)), "mhimx_step_layout_of")
-            ent = ex["layouts"][key] = (cnt, lay)
+            cnt = None if pure else mh.L.StepCounts(k_top=c[0], n_sel=c[1], len_keep=c[2], Lk=c[3], R=c[4])
+            ent = ex["layouts"][key] = (cnt, ops.step_layout(ex["cfg"], N, cnt))
         return ent
+
+    def _last_step(self, ws, lay, N, cnt):
+        """self.last of a single-bag call: the bag's dictionary (``cnt`` None: the teacher-free form), the workspace, the route."""
+        logits, losses = ops.ws_view(ws, lay.logits, self.s.n_classes), ops.ws_view(ws, lay.losses, 3)
+        if cnt is None:
+            bag = self._last_pure(logits, losses, ops.ws_view(ws, lay.H_student, N * self.s.mlp_dim).view(N, self.s.mlp_dim))
+        else:
+            bag = self._last_full(ws, lay, N, cnt, logits, losses)
+        return dict(bag, ws=ws, exec=True)
 
     def _exec_step(self, x, label, i):
         """forward_backward (+ the update, inside train_step) of one bag as ONE call of mhimx_step_run ('mhim_pure': mhimx_pure_step_run)."""
-        import ctypes as C
-        L = mh.L
-        s, t, fl = self.s, self.t, self.flat
-        if not (torch.is_tensor(label) and label.is_cuda and label.dtype == torch.int64 and label.is_contiguous() and label.device == x.device):
-            raise L.MhimxError(f"label: expected a contiguous int64 tensor on the bag's device ({x.device})")
+        ops.check_label(label, x.device, f"label: expected a contiguous int64 tensor on the bag's device ({x.device})")
         ex = self._exec_cfg()
         N = x.shape[0]
         cnt, lay = self._exec_plan(ex, N, i)
         # a captured step owns its workspace (the graph's memory pool); eager steps share one that only grows
-        if torch.cuda.is_current_stream_capturing():
-            ws = torch.empty(lay.total, dtype=torch.uint8, device=x.device)
-        else:
-            ws = ex["ws"]
-            if ws is None or ws.numel() < lay.total or ws.device != x.device:
-                ws = ex["ws"] = torch.full((int(lay.total * 1.25),), 255, dtype=torch.uint8, device=x.device)      # (poisoned: see _exec_window)
-
-        def view(off, n, dtype=torch.float32):
-            return ws[off:off + n * dtype.itemsize].view(dtype)
-
-        if self.model_kind == "mhim_pure":
-            # ONE seed per bag - the feature dropout's, drawn exactly where _nat_heads draws it: the model's seed stream then stands where
-            # the Python path leaves it
-            seed = s._next_seed()
-            update = bool(self._fold_now)
-            L.check(L.lib().mhimx_pure_step_run(ops._stream(), C.byref(ex["cfg"]), x.data_ptr(), x.stride(0), N, label.data_ptr(), seed,
-                                                fl.step + int(update), ws.data_ptr(), ws.numel(), int(update)), "mhimx_pure_step_run")
-            if update:
-                fl.step += 1
-            logits, losses = view(lay.logits, s.n_classes), view(lay.losses, 3)
-            self.last = {"logits": logits, "losses": losses, "patch_num": N, "keep_num": N, "rows": None, "score": None, "R": 0, "tokens": None,
-                         "H_student": view(lay.H_student, N * s.mlp_dim).view(N, s.mlp_dim), "H_teacher": None, "ws": ws, "exec": True}
-            if update:
-                ops.step_images(None)
-                self._micro = 0
-            else:
-                self._micro += 1
-            return logits, losses
-        seeds = L.StepSeeds(drop_teacher=t._next_seed(teacher=True), drop_student=s._next_seed(), select=s._next_seed(), mca=s._next_seed())
+        ws = ops.workspace(ex, "ws", lay.total, x.device)
+        # 'mhim_pure': ONE seed per bag - the feature dropout's, drawn exactly where _nat_heads draws it: the model's seed stream then
+        # stands where the Python path leaves it
+        seeds = self.s._next_seed() if cnt is None else self._step_seeds()
         update = bool(self._fold_now)
-        L.check(L.lib().mhimx_step_run(ops._stream(), C.byref(ex["cfg"]), x.data_ptr(), x.stride(0), N, label.data_ptr(), C.byref(cnt), C.byref(seeds),
-                                       fl.step + int(update), ws.data_ptr(), ws.numel(), int(update)), "mhimx_step_run")
-        if update:                                      # (only a step that was enqueued counts: a refused call leaves host and device counters equal)
-            fl.step += 1
-        km, E = s.merge.k, s.mlp_dim
-        Hs = view(lay.H_student, (N + km) * E).view(N + km, E)
-        logits, losses = view(lay.logits, s.n_classes), view(lay.losses, 3)
-        rows_all = view(lay.rows_all, cnt.len_keep + km, torch.int64)
-        self.last = {"logits": logits, "losses": losses, "patch_num": N, "keep_num": cnt.Lk + km, "rows": rows_all[:cnt.len_keep],
-                     "score": view(lay.score, N), "R": cnt.R, "tokens": Hs[N:], "H_student": Hs[:N],
-                     "H_teacher": view(lay.H_teacher, N * E).view(N, E), "ws": ws, "exec": True}
-        if self._chain is not None:                    # this rank's term of the chain: the tokens its Merge produced
-            self._chain.tokens = self._chain_tokens = Hs[N:]
-        if update:
-            ops.step_images(None)
-            self._micro = 0
-        else:
-            self._micro += 1
-        return logits, losses
+        ops.step_run(ex["cfg"], x, label, cnt, seeds, self.flat.step + int(update), ws, update)
+        self.last = self._last_step(ws, lay, N, cnt)
+        if self._chain is not None and cnt is not None:     # this rank's term of the chain: the tokens its Merge produced
+            self._chain.tokens = self._chain_tokens = self.last["tokens"]
+        self._steps_done(update)
+        return self.last["logits"], self.last["losses"]
 
     def run_steps(self, bags, labels, i=None):
         """len(bags) consecutive complete train steps (one update each) as ONE call of mhimx_step_run_many (SURVEY 7 H4 "run_steps"): the
@@ -994,7 +919,6 @@ class FusedTrainer:
         reference's loop counts them - base_engine.py:78) or a sequence with one entry per bag.  Returns the last bag's (logits, losses).
         What the executor's in-launch update does not do - gradient clipping (base_engine.py:115-119), unfolded reductions, accumulation -
         goes bag by bag through train_step, which does."""
-        import ctypes as C
         L = mh.L
         n = len(bags)
         if n == 0 or len(labels) != n:
@@ -1011,41 +935,19 @@ class FusedTrainer:
                 out = self.train_step(b, l, i=it)
             return out
         for x, l in zip(xs, labels):
-            if not (torch.is_tensor(l) and l.is_cuda and l.dtype == torch.int64 and l.is_contiguous() and l.device == x.device and l.numel() >= 1):
-                raise L.MhimxError(f"run_steps: every label must be a contiguous int64 tensor on its bag's device ({x.device})")
+            ops.check_label(l, x.device, f"run_steps: every label must be a contiguous int64 tensor on its bag's device ({x.device})", nonempty=True)
         ex = self._exec_cfg()
         plans = [self._exec_plan(ex, x.shape[0], it) for x, it in zip(xs, its)]
-        total = max(p[1].total for p in plans)
-        ws = ex["ws"]
-        if ws is None or ws.numel() < total or ws.device != xs[0].device:
-            ws = ex["ws"] = torch.empty(int(total * 1.25), dtype=torch.uint8, device=xs[0].device)
-        Xp = (C.c_void_p * n)(*[x.data_ptr() for x in xs])
-        ld = (C.c_int64 * n)(*[x.stride(0) for x in xs])
-        Ns = (C.c_int64 * n)(*[x.shape[0] for x in xs])
-        lab = (C.c_void_p * n)(*[l.data_ptr() for l in labels])
-        lay = plans[-1][1]
-        if self.model_kind == "mhim_pure":
-            drop_seeds = (C.c_uint64 * n)(*[self.s._next_seed() for _ in range(n)])
-            L.check(L.lib().mhimx_pure_step_run_many(ops._stream(), C.byref(ex["cfg"]), n, Xp, ld, Ns, lab, drop_seeds, self.flat.step + 1, ws.data_ptr(),
-                                                     ws.numel()), "mhimx_pure_step_run_many")
-            self.flat.step += n
-            ops.step_images(None)
-            N, E = xs[-1].shape[0], self.s.mlp_dim
-            logits, losses = ws[lay.logits:lay.logits + 4 * self.s.n_classes].view(torch.float32), ws[lay.losses:lay.losses + 12].view(torch.float32)
-            self.last = {"logits": logits, "losses": losses, "patch_num": N, "keep_num": N, "rows": None, "score": None, "R": 0, "tokens": None,
-                         "H_student": ws[lay.H_student:lay.H_student + N * E * 4].view(torch.float32).view(N, E), "H_teacher": None, "ws": ws,
-                         "exec": True}
-            return logits, losses
-        cnts = (L.StepCounts * n)(*[p[0] for p in plans])
-        seeds = (L.StepSeeds * n)()
-        for j in range(n):
-            seeds[j] = L.StepSeeds(drop_teacher=self.t._next_seed(teacher=True), drop_student=self.s._next_seed(), select=self.s._next_seed(),
-                                   mca=self.s._next_seed())
-        L.check(L.lib().mhimx_step_run_many(ops._stream(), C.byref(ex["cfg"]), n, Xp, ld, Ns, lab, cnts, seeds, self.flat.step + 1, ws.data_ptr(),
-                                            ws.numel()), "mhimx_step_run_many")
-        self.flat.step += n
-        ops.step_images(None)
-        return ws[lay.logits:lay.logits + 4 * self.s.n_classes].view(torch.float32), ws[lay.losses:lay.losses + 12].view(torch.float32)
+        ws = ops.workspace(ex, "ws", max(p[1].total for p in plans), xs[0].device)
+        cnt, lay = plans[-1]
+        pure = cnt is None
+        seeds = [self.s._next_seed() if pure else self._step_seeds() for _ in range(n)]
+        ops.step_run_many(ex["cfg"], xs, labels, None if pure else [p[0] for p in plans], seeds, self.flat.step + 1, ws)
+        self._steps_done(True, n)
+        last = self._last_step(ws, lay, xs[-1].shape[0], cnt)
+        if pure:                                            # (the full model's run_steps leaves self.last as it found it)
+            self.last = last
+        return last["logits"], last["losses"]
 
     def _forward_backward_nat(self, x, label, perm, ids_shuffle, i):
         """The single-pass ABMIL step: ONE projection launch computes the teacher's and the student's feature rows from the raw bag

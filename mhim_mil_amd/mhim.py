@@ -979,9 +979,8 @@ class MHIM(nn.Module):
         kinds = {x.dtype for x in xs}
         if len(kinds) != 1 or not kinds <= {torch.float32, torch.float16, torch.bfloat16}:
             return False
-        unit = 16 // xs[0].element_size()                       # elements of a 16-byte unit: the pitch rule of check_infer
-        return all(x.dim() == 2 and x.shape[1] == self.input_dim and 1 <= x.shape[0] <= L.INFER_MAX_ROWS and x.device == dev
-                   and x.data_ptr() % 16 == 0 and x.stride(0) % unit == 0 and self.input_dim <= x.stride(0) <= (1 << 20) for x in xs)
+        return all(x.dim() == 2 and x.device == dev for x in xs) and ops.infer_bags_ok(
+            [(x.shape[0], x.shape[1], x.stride(0), x.stride(1), x.data_ptr()) for x in xs], self.input_dim, xs[0].element_size())
 
     def _infer_cfg(self):
         att = self.online_encoder.attention.attention

@@ -941,6 +941,59 @@ def cls_metrics(logits, labels, n_classes, bin_metric=False, sample_idx=None):
     return out
 
 
+# ------------------------------------------------------------------------------------------- native calls: the shared host pieces
+def workspace(cache, key, total, dev, slack=1.25):
+    """The uint8 workspace of a native call that needs ``total`` bytes on ``dev``.  Inside a stream capture: a fresh one (the graph's
+    memory pool owns it).  Otherwise ``cache[key]``, which only grows (``slack`` times what is asked) and is poisoned once, when it is
+    made: 0xFF bytes are NaNs - a launch that read workspace memory no launch of the call wrote shows up in every eager test instead of
+    depending on what the allocator's block held before."""
+    if torch.cuda.is_current_stream_capturing():
+        return torch.empty(total, dtype=torch.uint8, device=dev)
+    ws = cache.get(key)
+    if ws is None or ws.numel() < total or ws.device != dev:
+        ws = cache[key] = torch.full((int(total * slack),), 255, dtype=torch.uint8, device=dev)
+    return ws
+
+
+def ws_view(ws, off, count, dtype=torch.float32):
+    """``count`` elements of ``dtype`` at byte ``off`` of a workspace (the layout structs' offsets)."""
+    return ws[off:off + count * dtype.itemsize].view(dtype)
+
+
+def window_labels_ok(labels, dev):
+    """A window's labels: one int64 device tensor of one element per bag."""
+    return all(torch.is_tensor(l) and l.is_cuda and l.dtype == torch.int64 and l.numel() == 1 and l.device == dev for l in labels)
+
+
+def check_label(label, dev, message, nonempty=False):
+    """The label of a single-bag entry point: a contiguous int64 tensor on the bag's device, else MhimxError(message)."""
+    if not (torch.is_tensor(label) and label.is_cuda and label.dtype == torch.int64 and label.is_contiguous() and label.device == dev
+            and (not nonempty or label.numel() >= 1)):
+        raise L.MhimxError(message)
+
+
+def model_dims_ok(E, A, C, D, c_max=4):
+    """The model rule of every native call: E = 512, scorer width 128, 1 .. c_max classes, D a multiple of 256."""
+    return bool(E == 512 and A == 128 and 1 <= C <= c_max and D > 0 and D % 256 == 0)
+
+
+def bag_rows_ok(N, D, pitch, inner, ptr, elem, max_n, window):
+    """csrc/infer_tab.hpp rg_check_bag with RgRules{max_n, window}, and the calls' pointer rule, mirrored: rows of ``elem``-byte elements
+    (4: fp32; 2: fp16 / bf16) with unit inner stride, a pitch (in elements) >= D that is a multiple of 16 bytes, a non-null 16-byte
+    aligned address.  ``max_n``: the most rows of a bag (0: the caller checks N).  ``window``: the step and window calls bound
+    N * pitch * elem below 2^32 and cap the pitch at 2^20 only for the 2-byte types; the inference calls cap it for every type."""
+    if elem not in (2, 4):
+        return False
+    capped = not (window and elem == 4)
+    return bool((not max_n or 1 <= N <= max_n) and inner == 1 and pitch >= D and pitch % (16 // elem) == 0
+                and (not capped or pitch <= (1 << 20)) and (not window or N * pitch * elem < (1 << 32)) and ptr != 0 and ptr % 16 == 0)
+
+
+def infer_bags_ok(bags, D, elem):
+    """What mhimx_infer_run_x / mhimx_infer_dsmil_run ask of every bag, tensor-free: ``bags``: one (N, D, pitch, inner, ptr) per bag."""
+    return all(Db == D and bag_rows_ok(N, D, pitch, inner, ptr, elem, L.INFER_MAX_ROWS, False) for N, Db, pitch, inner, ptr in bags)
+
+
 # ------------------------------------------------------------------------------------------- ragged multi-bag inference
 class InferResult:
     """Outputs of one mhimx_infer_run: logits [n, C], z [n, E], stats [n, 2], score / attn [sum N] (bag b's rows at offsets[b] ..
@@ -982,38 +1035,40 @@ def _x_name(name, x_dtype):
     return name if x_dtype == L.X_F32 else name + "_x"
 
 
+def _infer_front(who, ws_bytes_fn, cfg, xs, labels, ws):
+    """What ops.infer_many and ops.infer_dsmil_many do before their outputs: dtype, bag and label checks, the bag table, the workspace
+    (the caller's, or the one cached per device) and the bags' row offsets.  ``who`` names the wrapper in the messages; ``ws_bytes_fn``:
+    the call's workspace query.  Returns (n, x_dtype, table, ws, device, offsets)."""
+    n = len(xs)
+    xdt = x_dtype_of(xs, who)
+    for x in xs:
+        if not (torch.is_tensor(x) and x.is_cuda and x.dim() == 2 and x.stride(1) == 1):
+            raise L.MhimxError(f"{who}: every bag must be a GPU fp32 / fp16 / bf16 matrix [N, D] with unit column stride")
+    _chk(labels, torch.int64, "labels")
+    if labels is not None and labels.numel() != n:
+        raise L.MhimxError(f"{who}: {labels.numel()} labels for {n} bags")
+    bags = (L.InferBag * max(n, 1))(*[L.InferBag(X=x.data_ptr(), ldx=x.stride(0), N=x.shape[0]) for x in xs])
+    need = getattr(L.lib(), ws_bytes_fn)(C.byref(cfg), n, bags)
+    if need < 0:
+        L.check(int(need), ws_bytes_fn)
+    dev = xs[0].device
+    if ws is None:
+        ws = workspace(_INFER_WS, dev.index, need, dev, slack=1.0)
+    offsets = [0]
+    for x in xs:
+        offsets.append(offsets[-1] + int(x.shape[0]))
+    return n, xdt, bags, ws, dev, offsets
+
+
 def infer_many(cfg, xs, labels=None, want_attn=False, want_score=False, want_z=False, ws=None):
     """The eval-mode MHIM(ABMIL) forward of up to L.INFER_MAX bags of different row counts in ONE C call (mhimx_infer_run_x).
     cfg: L.InferCfg (its parameter tensors are kept alive by the caller); xs: [N_b, D] GPU tensors with unit column stride, all fp32, all
     fp16 or all bf16 (half bags are read where they lie: same bits as the call on their ``.float()``);
     labels: int64 [n] on the device (then the per-bag cross entropy comes back too).  ``ws``: a uint8 workspace of the caller's
     (tests poison it); default: one cached per device, grown on demand (inside a stream capture: a fresh one, owned by the graph's pool)."""
-    n = len(xs)
-    xdt = x_dtype_of(xs, "infer_many")
-    for x in xs:
-        if not (torch.is_tensor(x) and x.is_cuda and x.dim() == 2 and x.stride(1) == 1):
-            raise L.MhimxError("infer_many: every bag must be a GPU fp32 / fp16 / bf16 matrix [N, D] with unit column stride")
-    _chk(labels, torch.int64, "labels")
-    if labels is not None and labels.numel() != n:
-        raise L.MhimxError(f"infer_many: {labels.numel()} labels for {n} bags")
-    bags = (L.InferBag * max(n, 1))(*[L.InferBag(X=x.data_ptr(), ldx=x.stride(0), N=x.shape[0]) for x in xs])
-    need = L.lib().mhimx_infer_ws_bytes(C.byref(cfg), n, bags)
-    if need < 0:
-        L.check(int(need), "mhimx_infer_ws_bytes")
-    dev = xs[0].device
-    if ws is None:
-        if torch.cuda.is_current_stream_capturing():
-            ws = torch.empty(need, dtype=torch.uint8, device=dev)
-        else:
-            ws = _INFER_WS.get(dev.index)
-            if ws is None or ws.numel() < need:
-                # (poisoned when it is made: 0xFF bytes are NaNs - a launch that read workspace memory no launch of the call wrote shows up)
-                ws = _INFER_WS[dev.index] = torch.full((need,), 255, dtype=torch.uint8, device=dev)
+    n, xdt, bags, ws, dev, offsets = _infer_front("infer_many", "mhimx_infer_ws_bytes", cfg, xs, labels, ws)
     r = InferResult()
-    rows = sum(int(x.shape[0]) for x in xs)
-    r.offsets = [0]
-    for x in xs:
-        r.offsets.append(r.offsets[-1] + int(x.shape[0]))
+    r.offsets, rows = offsets, offsets[-1]
     r.logits = torch.empty((n, int(cfg.C)), device=dev)
     r.stats = torch.empty((n, 2), device=dev)
     r.z = torch.empty((n, int(cfg.E)), device=dev) if want_z else None
@@ -1056,30 +1111,9 @@ def infer_dsmil_many(cfg, xs, labels=None, want_attn=False, want_B=False, want_c
     """The eval-mode MHIM(DSMIL) forward of up to L.INFER_MAX bags of different row counts in ONE C call (mhimx_infer_dsmil_run).
     cfg: L.InferDsmilCfg (its parameter tensors are kept alive by the caller); xs, labels, ws: as ``infer_many`` takes them (half bags are
     read where they lie; the workspace cache is shared with it)."""
-    n = len(xs)
-    xdt = x_dtype_of(xs, "infer_dsmil_many")
-    for x in xs:
-        if not (torch.is_tensor(x) and x.is_cuda and x.dim() == 2 and x.stride(1) == 1):
-            raise L.MhimxError("infer_dsmil_many: every bag must be a GPU fp32 / fp16 / bf16 matrix [N, D] with unit column stride")
-    _chk(labels, torch.int64, "labels")
-    if labels is not None and labels.numel() != n:
-        raise L.MhimxError(f"infer_dsmil_many: {labels.numel()} labels for {n} bags")
-    bags = (L.InferBag * max(n, 1))(*[L.InferBag(X=x.data_ptr(), ldx=x.stride(0), N=x.shape[0]) for x in xs])
-    need = L.lib().mhimx_infer_dsmil_ws_bytes(C.byref(cfg), n, bags)
-    if need < 0:
-        L.check(int(need), "mhimx_infer_dsmil_ws_bytes")
-    dev = xs[0].device
-    if ws is None:
-        if torch.cuda.is_current_stream_capturing():
-            ws = torch.empty(need, dtype=torch.uint8, device=dev)
-        else:
-            ws = _INFER_WS.get(dev.index)
-            if ws is None or ws.numel() < need:
-                ws = _INFER_WS[dev.index] = torch.full((need,), 255, dtype=torch.uint8, device=dev)
+    n, xdt, bags, ws, dev, offsets = _infer_front("infer_dsmil_many", "mhimx_infer_dsmil_ws_bytes", cfg, xs, labels, ws)
     r = InferDsmilResult()
-    r.offsets = [0]
-    for x in xs:
-        r.offsets.append(r.offsets[-1] + int(x.shape[0]))
+    r.offsets = offsets
     Cc, E = int(cfg.C), int(cfg.E)
     r.logits_bag = torch.empty((n, Cc), device=dev)
     r.logits_ins = torch.empty((n, Cc), device=dev)
@@ -1093,6 +1127,61 @@ def infer_dsmil_many(cfg, xs, labels=None, want_attn=False, want_B=False, want_c
     L.check(L.lib().mhimx_infer_dsmil_run(_stream(), C.byref(cfg), n, bags, _p(labels), C.byref(out), _p(ws), ws.numel(), xdt),
             "mhimx_infer_dsmil_run")
     return r
+
+
+# ------------------------------------------------------------------------------------------- single-bag steps, the same-shape window
+def step_layout(cfg, N, cnt=None):
+    """mhimx_step_layout_of for a bag of N rows with the counts ``cnt`` (None: mhimx_pure_step_layout_of - every row takes part): host
+    arithmetic only."""
+    lay = L.StepLayout()
+    if cnt is None:
+        L.check(L.lib().mhimx_pure_step_layout_of(C.byref(cfg), N, C.byref(lay)), "mhimx_pure_step_layout_of")
+    else:
+        L.check(L.lib().mhimx_step_layout_of(C.byref(cfg), N, C.byref(cnt), C.byref(lay)), "mhimx_step_layout_of")
+    return lay
+
+
+def step_run(cfg, x, label, cnt, seeds, host_step, ws, update):
+    """One bag's forward + backward (+ the update) as one C call: mhimx_step_run (``seeds``: its StepSeeds), or, with ``cnt`` None,
+    mhimx_pure_step_run (``seeds``: the feature dropout's one seed)."""
+    if cnt is None:
+        L.check(L.lib().mhimx_pure_step_run(_stream(), C.byref(cfg), x.data_ptr(), x.stride(0), x.shape[0], label.data_ptr(), seeds,
+                                            int(host_step), ws.data_ptr(), ws.numel(), int(bool(update))), "mhimx_pure_step_run")
+    else:
+        L.check(L.lib().mhimx_step_run(_stream(), C.byref(cfg), x.data_ptr(), x.stride(0), x.shape[0], label.data_ptr(), C.byref(cnt),
+                                       C.byref(seeds), int(host_step), ws.data_ptr(), ws.numel(), int(bool(update))), "mhimx_step_run")
+
+
+def step_run_many(cfg, xs, labels, cnts, seeds, host_step, ws):
+    """len(xs) complete steps, bag after bag on one workspace, as one C call: mhimx_step_run_many (``cnts`` / ``seeds``: one StepCounts /
+    StepSeeds per bag), or, with ``cnts`` None, mhimx_pure_step_run_many (``seeds``: one dropout seed per bag)."""
+    n = len(xs)
+    Xp = (C.c_void_p * n)(*[x.data_ptr() for x in xs])
+    ld = (C.c_int64 * n)(*[x.stride(0) for x in xs])
+    Ns = (C.c_int64 * n)(*[x.shape[0] for x in xs])
+    lab = (C.c_void_p * n)(*[l.data_ptr() for l in labels])
+    if cnts is None:
+        L.check(L.lib().mhimx_pure_step_run_many(_stream(), C.byref(cfg), n, Xp, ld, Ns, lab, (C.c_uint64 * n)(*seeds), int(host_step),
+                                                 ws.data_ptr(), ws.numel()), "mhimx_pure_step_run_many")
+    else:
+        L.check(L.lib().mhimx_step_run_many(_stream(), C.byref(cfg), n, Xp, ld, Ns, lab, (L.StepCounts * n)(*cnts), (L.StepSeeds * n)(*seeds),
+                                            int(host_step), ws.data_ptr(), ws.numel()), "mhimx_step_run_many")
+
+
+def window_layout(cfg, n, N, cnt):
+    """mhimx_window_layout_of: n bags of N rows each with the counts ``cnt`` (host arithmetic only)."""
+    lay = L.WindowLayout()
+    L.check(L.lib().mhimx_window_layout_of(C.byref(cfg), n, N, C.byref(cnt), C.byref(lay)), "mhimx_window_layout_of")
+    return lay
+
+
+def window_run(cfg, xs, labels, cnt, seeds, host_step, ws, update):
+    """mhimx_window_run: one accumulation window of len(xs) bags of ONE shape and pitch (``seeds``: a StepSeeds array, one per bag)."""
+    n = len(xs)
+    Xp = (C.c_void_p * n)(*[x.data_ptr() for x in xs])
+    Lp = (C.c_void_p * n)(*[l.data_ptr() for l in labels])
+    L.check(L.lib().mhimx_window_run(_stream(), C.byref(cfg), n, Xp, xs[0].stride(0), xs[0].shape[0], Lp, C.byref(cnt), seeds, int(host_step),
+                                     ws.data_ptr(), ws.numel(), int(bool(update))), "mhimx_window_run")
 
 
 # ------------------------------------------------------------------------------------------- ragged pure accumulation window
