@@ -1125,6 +1125,33 @@ int64_t mhimx_infer_dsmil_ws_bytes(const mhimx_infer_dsmil_cfg* cfg, int32_t n_b
 int mhimx_infer_dsmil_run(void* stream, const mhimx_infer_dsmil_cfg* cfg, int32_t n_bags, const mhimx_infer_bag* bags,
                           const int64_t* labels_dev, const mhimx_infer_dsmil_out* out, void* ws, int64_t ws_bytes, int32_t x_dtype);
 
+/* ------------------------------------------------------------------------------------------
+ * Top-k instances of many score vectors: the k most (largest) or least attended instances of every bag of a ragged inference call,
+ * from the call's own attention / score buffer, in one launch chain whatever n_segs is.
+ * replaces: CLAM/create_heatmaps.py:53 (torch.topk of a slide's attention scores for review and heat maps) and the per-bag ranking of
+ *           mhim_modules/masking.py:62 (the hard-instance candidates), run per bag from a host loop over the vectors
+ *           modules/mhim.py:229-272 (forward_test, return_attn) returns; torch.topk's tie order is implementation-defined.
+ * Segment b is score[row0 .. row0 + N) (the rows of bag b in mhimx_infer_out.attn / .score / mhimx_infer_dsmil_out.attn: row0 =
+ * row_off[b]; any table of non-negative offsets will do, in any order, with gaps, without alignment).  k_b = min(k, N_b).
+ *  idx[b, j], j < k_b: the index INSIDE the segment of its j-th instance in the select's order - the tie contract of "Hard-instance
+ *                      select" above: value descending (ascending if !largest), then index ascending;
+ *  val[b, j] = score[row0_b + idx[b, j]], the same bits (val may be NULL);   j >= k_b: idx = -1, val = 0.
+ * NaN and -0.0 scores are outside the contract.
+ * One launch when every N <= 16384 (one workgroup per segment, scores read once), seven when a segment is larger (its digit
+ * histograms, counts and candidates on a (chunk, segment) grid, per-segment state in the workspace).  The table travels by value: no
+ * host-to-device copy, no synchronisation, no allocation, capturable in a graph; no workgroup waits for another; integer work only - a
+ * segment's result has the same bits wherever it stands in a call and whatever its neighbours are.
+ * 1 <= n_segs <= MHIMX_INFER_MAX, every N in 1..MHIMX_INFER_MAX_ROWS, 1 <= k <= MHIMX_TOPK_MAX_K; anything else returns < 0 before
+ * any device call and mhimx_last_error names the call and the segment.  Workspace: mhimx_topk_many_ws_bytes (pure host arithmetic;
+ * < 0 on a refused shape), 256-byte aligned; it needs no initialisation.
+ * MHIMX_VERSION stays 620: additions only.
+ * ---------------------------------------------------------------------------------------- */
+#define MHIMX_TOPK_MAX_K 4096
+typedef struct { int64_t row0, N; } mhimx_topk_seg;   /* segment b = score[row0 .. row0 + N) */
+int64_t mhimx_topk_many_ws_bytes(int32_t n_segs, const mhimx_topk_seg* segs, int64_t k);
+int mhimx_topk_many(void* stream, const float* score, int32_t n_segs, const mhimx_topk_seg* segs, int64_t k, int32_t largest,
+                    int64_t* idx /* [n_segs, k] */, float* val /* [n_segs, k] or NULL */, void* ws, int64_t ws_bytes);
+
 /* dst = src (float4 grid-stride stream copy): the on-box HBM copy rate bench.py reports beside the nominal 8 TB/s */
 int mhimx_stream_copy(void* stream, const float* src, float* dst, int64_t n_floats);
 

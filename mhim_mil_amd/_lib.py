@@ -250,6 +250,14 @@ INFER_MAX = 32               # MHIMX_INFER_MAX
 INFER_MAX_ROWS = 4194304     # MHIMX_INFER_MAX_ROWS
 X_F32, X_F16, X_BF16 = 0, 1, 2   # MHIMX_X_*: the element type of the bags' rows in the three *_run_x calls
 
+TOPK_MAX_K = 4096            # MHIMX_TOPK_MAX_K
+
+
+class TopkSeg(C.Structure):
+    """mhimx_topk_seg: segment b of a mhimx_topk_many call is score[row0 .. row0 + N)."""
+    _fields_ = [("row0", C.c_int64), ("N", C.c_int64)]
+
+
 PURE_WINDOW_MAX = 32         # MHIMX_PURE_WINDOW_MAX
 PURE_WINDOW_MAX_ROWS = 524288   # MHIMX_PURE_WINDOW_MAX_ROWS (rows of the call's row space: every bag rounded up to a multiple of 32)
 
@@ -397,6 +405,8 @@ SYMBOLS = {
     "mhimx_infer_run_x": (C.c_int, [_P, C.POINTER(InferCfg), _I32, _P, _P, C.POINTER(InferOut), _P, _I64, _I32]),
     "mhimx_infer_dsmil_ws_bytes": (_I64, [C.POINTER(InferDsmilCfg), _I32, _P]),
     "mhimx_infer_dsmil_run": (C.c_int, [_P, C.POINTER(InferDsmilCfg), _I32, _P, _P, C.POINTER(InferDsmilOut), _P, _I64, _I32]),
+    "mhimx_topk_many_ws_bytes": (_I64, [_I32, _P, _I64]),
+    "mhimx_topk_many": (C.c_int, [_P, _P, _I32, _P, _I64, _I32, _P, _P, _P, _I64]),
     "mhimx_step_run_many": (C.c_int, [_P, C.POINTER(StepCfg), _I32, _P, _P, _P, _P, C.POINTER(StepCounts), C.POINTER(StepSeeds), _I64, _P, _I64]),
     "mhimx_pure_step_layout_of": (C.c_int, [C.POINTER(StepCfg), _I64, C.POINTER(StepLayout)]),
     "mhimx_pure_step_run": (C.c_int, [_P, C.POINTER(StepCfg), _P, _I64, _I64, _P, C.c_uint64, _I64, _P, _I64, _I32]),

@@ -21,6 +21,7 @@ Nystrom) composes the encoder from kernel-backed auto
 """
 from __future__ import annotations
 
+import itertools
 import math
 import os
 from typing import Optional
@@ -1035,6 +1036,17 @@ class MHIM(nn.Module):
         ``self.last["infer_native"]`` says which route ran.
         A list of fp16 bags, or of bf16 bags, that the native route takes goes in as it is (no widened copy; same bits as on the widened
         bags); a list of mixed dtypes, and every model outside the native route, gets ``x.float()`` first."""
+        logits, attns, loss, _ = self._infer_run(xs, labels, return_attn, no_norm)
+        out = (logits,) + ((attns,) if return_attn else ()) + ((loss,) if labels is not None else ())
+        return out[0] if len(out) == 1 else out
+
+    def _infer_run(self, xs, labels, return_attn, no_norm, topk=None):
+        """``infer_many``'s routes -> (logits, per-bag attention list, loss | None, top-k | None).  ``topk`` = (k, largest): the per-bag
+        vectors are not handed out but ranked - on the native routes one ops.topk_many per chunk, on the chunk's own attention / score
+        buffer with the chunk's offsets; on the forward_test loop the bags' vectors packed into one vector per L.INFER_MAX bags - and the
+        fourth result is (idx [n, k], val [n, k])."""
+        return_attn = return_attn or topk is not None
+        tk = []                                   # (idx, val) of every ops.topk_many call, in bag order
         xs = self._infer_bags(xs, keep_half=True)
         if any(x.dtype != torch.float32 for x in xs) and not self._infer_ok(xs):
             xs = [x.float() for x in xs]
@@ -1056,7 +1068,9 @@ class MHIM(nn.Module):
                     r = ops.infer_dsmil_many(cfg, xs[lo:hi], labels=None if labels is None else labels[lo:hi].contiguous(),
                                              want_attn=return_attn, want_B=True)
                     rs.append(r)
-                    if return_attn:
+                    if topk is not None:
+                        tk.append(ops.topk_many(r.attn, r.offsets, *topk))
+                    elif return_attn:
                         attns += [r.attn[r.offsets[j]:r.offsets[j + 1]] for j in range(hi - lo)]
                 self._step += n                   # (the stream position the forward_test loop leaves behind: one seed per bag)
                 cat = lambda ts: ts[0] if len(ts) == 1 else torch.cat(ts)
@@ -1089,7 +1103,9 @@ class MHIM(nn.Module):
                                    want_attn=return_attn and not no_norm, want_score=return_attn and no_norm)
                 lg.append(r.logits)
                 ls.append(r.loss)
-                if return_attn:
+                if topk is not None:
+                    tk.append(ops.topk_many(r.score if no_norm else r.attn, r.offsets, *topk))
+                elif return_attn:
                     a = r.score if no_norm else r.attn
                     attns += [a[r.offsets[j]:r.offsets[j + 1]] for j in range(hi - lo)]
             self._step += n                       # (the stream position the forward_test loop leaves behind: one seed per bag)
@@ -1108,8 +1124,35 @@ class MHIM(nn.Module):
             logits = torch.cat(lg) if lg else torch.empty((0, self.n_classes), device=self.feature[0].weight.device)
             loss = None if labels is None else torch.nn.functional.cross_entropy(logits, labels, reduction="none")
             self.last = {"infer_native": False, "infer_calls": 0}
-        out = (logits,) + ((attns,) if return_attn else ()) + ((loss,) if labels is not None else ())
-        return out[0] if len(out) == 1 else out
+        if topk is None:
+            return logits, attns, loss, None
+        for lo in range(0, len(attns), L.INFER_MAX):            # (the forward_test loop's vectors; the native routes left none)
+            part = [a.reshape(-1).float() for a in attns[lo:lo + L.INFER_MAX]]
+            tk.append(ops.topk_many(torch.cat(part).contiguous(), [0] + list(itertools.accumulate(a.numel() for a in part)), *topk))
+        dev = self.feature[0].weight.device
+        idx = torch.cat([t[0] for t in tk]) if tk else torch.empty((0, topk[0]), dtype=torch.int64, device=dev)
+        val = torch.cat([t[1] for t in tk]) if tk else torch.empty((0, topk[0]), device=dev)
+        return logits, [], loss, (idx, val)
+
+    @torch.no_grad()
+    def infer_topk(self, xs, k, largest=True, no_norm=False, labels=None):
+        """The k most (least, if not ``largest``) attended instances of every bag of a LIST of bags: ``(logits [n, C], idx [n, k],
+        val [n, k])``, plus ``loss [n]`` with ``labels``; rows in the bag order of ``xs``.  What is ranked is exactly the per-bag vector
+        ``infer_many(xs, return_attn=True, no_norm=no_norm)`` returns (attention, raw scorer outputs with ``no_norm``, the DSMIL
+        instance score), under the select's tie contract: value descending (ascending), then index ascending.  idx[b, j] is a row of
+        bag b; behind min(k, N_b): idx = -1, val = 0.  Routes and bookkeeping (``_step``, ``self.last``) are ``infer_many``'s; on the
+        native routes each chunk adds ONE mhimx_topk_many call on the chunk's own attention buffer.  ``self.last["infer_topk"] = (idx,
+        val)``.  A model whose forward_test attention is not one vector of N_b entries per bag is refused."""
+        k = int(k)
+        if not 1 <= k <= L.TOPK_MAX_K:
+            raise L.MhimxError(f"MHIM.infer_topk: k={k} must be in 1..{L.TOPK_MAX_K}")
+        if self.merge_test:
+            raise L.MhimxError("MHIM.infer_topk: merge_test scores N + k tokens, not the N rows of the bag")
+        if self.baseline == "selfattn":
+            raise L.MhimxError("MHIM.infer_topk: TransMIL returns one attention map per layer, not one vector of N entries per bag")
+        logits, _, loss, (idx, val) = self._infer_run(xs, labels, True, no_norm, topk=(k, bool(largest)))
+        self.last["infer_topk"] = (idx, val)
+        return (logits, idx, val) + ((loss,) if labels is not None else ())
 
     # ------------------------------------------------------------------ TransMIL (selfattn) pieces
     def _encode(self, tok, return_attn=False, no_norm=False, has_cls=False):

@@ -1129,6 +1129,61 @@ def infer_dsmil_many(cfg, xs, labels=None, want_attn=False, want_B=False, want_c
     return r
 
 
+# ------------------------------------------------------------------------------------------- top-k instances of many score vectors
+_TOPK_WS = {}               # device index -> the cached workspace
+
+
+def topk_segs(offsets):
+    """The (row0, N) pairs of a mhimx_topk_many call: ``offsets`` is the ``offsets`` list of an InferResult / InferDsmilResult (n + 1
+    row offsets: segment b = [offsets[b], offsets[b + 1])) or already a list of (row0, N) pairs (any order, gaps allowed)."""
+    offsets = list(offsets)
+    if offsets and not isinstance(offsets[0], (tuple, list)):
+        return [(int(a), int(b) - int(a)) for a, b in zip(offsets[:-1], offsets[1:])]
+    return [(int(r), int(n)) for r, n in offsets]
+
+
+def topk_segs_ok(segs, k):
+    """csrc/topk.hip topk_check, mirrored (tensor-free): 1 .. L.INFER_MAX segments, every N in 1 .. L.INFER_MAX_ROWS, every row0 >= 0,
+    1 <= k <= L.TOPK_MAX_K.  ``segs``: (row0, N) pairs."""
+    return bool(1 <= len(segs) <= L.INFER_MAX and 1 <= k <= L.TOPK_MAX_K
+                and all(1 <= n <= L.INFER_MAX_ROWS and r >= 0 for r, n in segs))
+
+
+def topk_many_ws_bytes(segs, k):
+    """mhimx_topk_many_ws_bytes for (row0, N) pairs: host arithmetic only (< 0: a refused table)."""
+    tab = (L.TopkSeg * max(len(segs), 1))(*[L.TopkSeg(row0=r, N=n) for r, n in segs])
+    return L.lib().mhimx_topk_many_ws_bytes(len(segs), tab, int(k))
+
+
+def topk_many(score, offsets, k, largest=True, want_values=True, ws=None):
+    """The k largest (smallest if not ``largest``) entries of up to L.INFER_MAX segments of the fp32 device vector ``score`` in ONE C call
+    (mhimx_topk_many), under the select's tie contract: value descending (ascending), then index ascending.  ``offsets``: see
+    ``topk_segs``.  Returns (idx int64 [n, k] - indices INSIDE each segment, -1 behind min(k, N_b) -, val fp32 [n, k] - the scores' own
+    bits, 0 behind - or None).  ``ws``: a uint8 workspace of the caller's (tests poison it); default: one cached per device (inside a
+    stream capture: a fresh one, owned by the graph's pool).  More than L.INFER_MAX segments: MhimxError - the caller chunks."""
+    _chk(score, name="score")
+    if score is None or score.dim() != 1:
+        raise L.MhimxError("topk_many: score must be a 1-D fp32 GPU vector")
+    segs = topk_segs(offsets)
+    n = len(segs)
+    if n > L.INFER_MAX:
+        raise L.MhimxError(f"topk_many: {n} segments in one call (at most {L.INFER_MAX}): chunk the table")
+    if any(r + max(m, 0) > score.numel() for r, m in segs):
+        raise L.MhimxError(f"topk_many: a segment ends behind the score vector ({score.numel()} entries)")
+    tab = (L.TopkSeg * max(n, 1))(*[L.TopkSeg(row0=r, N=m) for r, m in segs])
+    need = L.lib().mhimx_topk_many_ws_bytes(n, tab, int(k))
+    if need < 0:
+        L.check(int(need), "mhimx_topk_many_ws_bytes")
+    dev = score.device
+    if ws is None:
+        ws = workspace(_TOPK_WS, dev.index, need, dev, slack=1.0)
+    idx = torch.empty((n, int(k)), dtype=torch.int64, device=dev)
+    val = torch.empty((n, int(k)), device=dev) if want_values else None
+    L.check(L.lib().mhimx_topk_many(_stream(), _p(score), n, tab, int(k), int(bool(largest)), _p(idx), _p(val), _p(ws), ws.numel()),
+            "mhimx_topk_many")
+    return idx, val
+
+
 # ------------------------------------------------------------------------------------------- single-bag steps, the same-shape window
 def step_layout(cfg, N, cnt=None):
     """mhimx_step_layout_of for a bag of N rows with the counts ``cnt`` (None: mhimx_pure_step_layout_of - every row takes part): host
