@@ -537,6 +537,26 @@ int mhimx_compose_ids(void* stream, const int64_t* a, const int64_t* b, int64_t*
  * alone (every rank of a sharded bag computes the same list).  Every element lands in a prefix of length m with probability m / n. */
 int mhimx_random_perm(void* stream, int64_t n, uint64_t seed, const uint64_t* tick, const int64_t* src, int64_t* out);
 
+/* The production select of MANY score vectors of different lengths in one call: the row lists of every bag of a ragged accumulation
+ * window or of a validation chunk (modules/mhim.py:341 per slide: masking.py:9-88 + merge.py:158-176).  Bag b ranks
+ * score[row0 .. row0 + N) with largest = 1 and writes rows_out[out0 .. out0 + N - n_sel).  For every bag the bits written are those
+ *   mhimx_select_rows(score + row0, N, k, n_sel, 1, seed, tick, merge_R, rows_out + out0, NULL, ..., merge_first)
+ * writes, for every argument set that call accepts (tie contract, the device draws from seed + *tick, n_sel == k, n_sel == 0,
+ * merge_R == 0, merge_R == N - n_sel), wherever the bag stands in the table, whatever its neighbours, row0 and out0 are: no alignment,
+ * gaps and any bag order allowed.  Bags of up to 16 384 rows (k <= 4096): ONE launch for all of them, one workgroup per bag, the table by
+ * value - no host-to-device copy, no synchronisation, no allocation, capturable in a graph.  A bag above 16 384 rows (k <= 16384, the
+ * bags mhimx_select_rows refuses): per bag, on the same stream, out of ws, the sequence mhimx_random_perm(k, seed + 0x51ED270B),
+ * mhimx_select_mask, mhimx_random_perm(N - n_sel, seed ^ 0x3C6EF372FE94F82B, src = ids) and, with merge_first, the [merge | stay] swap.
+ * 1 <= n_bags <= MHIMX_INFER_MAX; N in 1..MHIMX_STEP_MAX_ROWS; k in 1..min(N, 4096) up to 16 384 rows, 1..min(N, 16384) above; n_sel in
+ * 0..k; merge_R in 0..N - n_sel; row0, out0 >= 0; no two output ranges overlap; score, bags, rows_out non-null (tick may be NULL, as in
+ * mhimx_select_rows); ws 256-byte aligned, mhimx_select_rows_many_ws_bytes bytes (pure host arithmetic: 256 when every bag is small, else
+ * sized for the largest large bag; no initialisation needed).  Anything else returns < 0 before any device call and mhimx_last_error
+ * names the call and the bag.  MHIMX_VERSION stays 620: additions only. */
+typedef struct { int64_t row0, N, k, n_sel, merge_R, out0; uint64_t seed; } mhimx_select_bag;   /* 56 bytes */
+int64_t mhimx_select_rows_many_ws_bytes(int32_t n_bags, const mhimx_select_bag* bags);
+int mhimx_select_rows_many(void* stream, const float* score, int32_t n_bags, const mhimx_select_bag* bags, const uint64_t* tick,
+                           int64_t* rows_out, void* ws, int64_t ws_bytes, int32_t merge_first);
+
 /* ------------------------------------------------------------------------------------------
  * Merge / MCA                                                   
  * replaces: mhim_modules/merge.py:43-65 (MCA.forward), :131-144 (Merge.merge), :127-129 (EMA).
@@ -960,8 +980,9 @@ int mhimx_pure_window_run(void* stream, const mhimx_step_cfg* cfg, int32_t n_bag
  * rows, score, rows_all, tokens, logits, losses, z) depends on that bag and the window's starting state alone, not on its neighbours.
  * Enqueue-only and capturable: no allocation, no synchronisation, no host-to-device copy (the bag table travels by value).  No
  * floating-point atomics, no workgroup that waits for another: every sum has a fixed order, two runs give the same bits.
- * Launches: 12 window-wide + 13 per bag of up to 16 384 rows (csrc/ragged_window.hip lists them) - both projections, the teacher's scorer
- * and the projection's weight gradient run once over the call's row space; the per-bag middle is a loop over the entry points above.
+ * Launches: 13 window-wide + 12 per bag, + 5 window-wide for every bag above 16 384 rows (csrc/ragged_window.hip lists them) - both
+ * projections, the teacher's scorer, every bag's row list (the many-select behind mhimx_select_rows_many) and the projection's weight
+ * gradient run once over the call's row space; the rest of the per-bag middle is a loop over the entry points above.
  * cfg: mhimx_step_run's (E = 512, A = 128, C <= 4, 8 k <= 48, D % 256 == 0), with q_out, side_stream and time_project NULL / 0.
  * 1 <= n_bags <= MHIMX_RAGGED_WINDOW_MAX; per bag the checks mhimx_step_run makes (64 <= N <= MHIMX_STEP_MAX_ROWS, the cnt conditions,
  * ldx >= D, ldx % 4 == 0, N * ldx * 4 < 2^32, 16-byte aligned rows).  Bag b owns a slot of 32 * ceil((N_b + k) / 32) rows of the call's row

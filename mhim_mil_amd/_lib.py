@@ -258,6 +258,11 @@ class TopkSeg(C.Structure):
     _fields_ = [("row0", C.c_int64), ("N", C.c_int64)]
 
 
+class SelectBag(C.Structure):
+    """mhimx_select_bag: bag b of a mhimx_select_rows_many call ranks score[row0 .. row0 + N) and writes rows_out[out0 .. out0 + N - n_sel)."""
+    _fields_ = [(n, C.c_int64) for n in ("row0", "N", "k", "n_sel", "merge_R", "out0")] + [("seed", C.c_uint64)]
+
+
 PURE_WINDOW_MAX = 32         # MHIMX_PURE_WINDOW_MAX
 PURE_WINDOW_MAX_ROWS = 524288   # MHIMX_PURE_WINDOW_MAX_ROWS (rows of the call's row space: every bag rounded up to a multiple of 32)
 
@@ -316,6 +321,8 @@ SYMBOLS = {
     "mhimx_vote_scores": (C.c_int, [_P, _P, _I64, _I64, _I64, _I32, _P, _P, _I64]),
     "mhimx_compose_ids": (C.c_int, [_P, _P, _P, _P, _I64]),
     "mhimx_random_perm": (C.c_int, [_P, _I64, _U64, _P, _P, _P]),
+    "mhimx_select_rows_many_ws_bytes": (_I64, [_I32, _P]),
+    "mhimx_select_rows_many": (C.c_int, [_P, _P, _I32, _P, _P, _P, _P, _I64, _I32]),
     "mhimx_merge_ws_bytes": (_I64, [_I64, _I64, _I64, _I64, _I64]),
     "mhimx_merge_fwd": (C.c_int, [_P, C.POINTER(Merge), _P, _I64, _P, _P, _I32, _P, _I64]),
     "mhimx_merge_part_floats": (_I64, []),

@@ -207,6 +207,18 @@ int pw_reduce(hipStream_t st, int n, const float* const* parts, const int32_t* G
 // step.hip: the checks mhimx_step_run makes on (cfg, N, counts)
 int step_check_cfg(const mhimx_step_cfg* c, int64_t N, const mhimx_step_counts* n);
 
+// select_many.hip: the select of a bag above 16 384 rows as ONE helper with explicit pointers (mhimx_random_perm, mhimx_select_mask,
+// mhimx_random_perm, the [merge | stay] swap) - w.perm [k], w.ids [N], w.rows [N - n_sel] (merge_first only), w.lk [1], w.sel_ws
+// (mhimx_select_ws_bytes(N)); the bag table's checks under the caller's name `who`; and the many-select of a table that passed them (the
+// small bags in one launch, then every large bag through the helper out of the one scratch set w).  mhimx_select_rows_many is check,
+// pointer and workspace checks, launch; mhimx_ragged_window_run checks and launches with its own workspace regions.
+struct SelLargeWs { int64_t *perm, *ids, *rows, *lk; void* sel_ws; int64_t sel_ws_bytes; };
+int select_large_rows(hipStream_t st, const float* score, int64_t N, int64_t k, int64_t n_sel, uint64_t seed, const uint64_t* tick, int64_t merge_R,
+                      int64_t* rows_out, int merge_first, const SelLargeWs& w);
+int select_bags_check(const char* who, int32_t n_bags, const mhimx_select_bag* bags);
+int select_rows_many_launch(hipStream_t st, const float* score, int32_t n_bags, const mhimx_select_bag* bags, const uint64_t* tick, int64_t* rows_out,
+                            const SelLargeWs& w, int merge_first);
+
 // the ragged one-model projection launch (bag_project.hip): Hout[row0[b] + m, :] = act(X_b[m, :] W1^T + b1) for every bag b of the table
 int infer_project(hipStream_t st, const InferTab& tab, int D, const float* w1p, const float* b1, int act, float* Hout);
 

@@ -9,7 +9,7 @@
 // The call's row space: bag b owns a slot of 32 * ceil((N_b + k) / 32) rows (its N feature rows, the k Merge tokens where the per-bag entry
 // points expect them - H_student + N * E - then zero rows), so that a 32-row tile / k-step lies inside one bag.  Three parts:
 //
-//   A. the teacher half, window-wide (6 launches whatever n_bags is)
+//   A. the teacher half and every bag's row list, window-wide (7 launches whatever n_bags is; + 5 per bag above 16 384 rows)
 //      1  mhimx_prep_batch            counters, both W1 paired-plane images, both Wa fragment images, the student's transposed images, the
 //                                     query snapshot
 //      2  pure_window_project_kernel  (bag_project.hip, as it is) the teacher's feature rows: drop_p_teacher, per-bag seed
@@ -21,19 +21,21 @@
 //                                     the instantiation that also takes the class projections h . Wp_c while the rows are LDS-resident
 //      6  rw_finalize_kernel          plane = bag: the partials merged in index order -> {max, sum}, z_teacher; every row's instance score
 //                                     (attention, or the pseudo score of scoring.py:37-58 with its bp[0] quirk)
-//   B. the middle, bag after bag: mhimx_step_run's entry points in its order with pointers into the bag's slot (13 launches per bag of up
-//      to 16 384 rows, 17 above - the select_large sequence)
+//      7  select_many_kernel<KPT>     (select_many.hip) plane = bag: HAM mask + Merge split of every bag of up to 16 384 rows, the ragged form
+//                                     of mhimx_select_rows' production kernel; a bag above 16 384 rows: select_large_rows behind it
+//                                     (random_perm, select_mask, random_perm, two copies) out of the call's select scratch.  The select
+//                                     reads the bag's scores, its seed and *tick (which moves once, in A.1): the same bits as inside the loop
+//   B. the middle, bag after bag: mhimx_step_run's entry points in its order with pointers into the bag's slot (12 launches per bag)
 //      1     mhimx_prep_batch        the row list's constant tail, the parameter-only part of this bag's Merge (its workspace is shared)
-//      2     mhimx_select_rows       HAM mask + Merge split (above 16 384 rows: random_perm, select_mask, random_perm, two copies)
-//      3     mhimx_abmil_pool_fwd    phase 1: student scorer over the rows that stay, Merge's rows pass riding
-//      4-6   mhimx_merge_fwd         partial merge | O | to_out (the queries' EMA goes to scratch: the window's first queries stay)
-//      7     mhimx_abmil_pool_fwd    phase 2: the finalize that scores the tokens
-//      8     mhimx_head_fwd_bwd      loss scale 1 / n_bags
-//      9     mhimx_abmil_pool_bwd    fp32 dH rows (pg.img = NULL): the stay rows' gradient exists as rows of the bag's slot
-//      10    mhimx_merge_bwd         rows backward + the parked scorer-weight-gradient product
-//      11-13 mhimx_reduce_flush      the Merge tail's stages + the bag's queued reductions
+//      2     mhimx_abmil_pool_fwd    phase 1: student scorer over the rows that stay, Merge's rows pass riding
+//      3-5   mhimx_merge_fwd         partial merge | O | to_out (the queries' EMA goes to scratch: the window's first queries stay)
+//      6     mhimx_abmil_pool_fwd    phase 2: the finalize that scores the tokens
+//      7     mhimx_head_fwd_bwd      loss scale 1 / n_bags
+//      8     mhimx_abmil_pool_bwd    fp32 dH rows (pg.img = NULL): the stay rows' gradient exists as rows of the bag's slot
+//      9     mhimx_merge_bwd         rows backward + the parked scorer-weight-gradient product
+//      10-12 mhimx_reduce_flush      the Merge tail's stages + the bag's queued reductions
 //      The small gradients accumulate in bag order on the one stream: bag 0 overwrites cfg->grad, every later bag adds (accumulate = 1).
-//      A bag runs forward and backward before the next starts: the select, Merge and pool workspaces exist once, sized for the largest bag.
+//      A bag runs forward and backward before the next starts: the Merge and pool workspaces exist once, sized for the largest bag.
 //   C. the backward tail, window-wide (6 launches; 5 with update = 0)
 //      1  rw_keep_kernel             the kept-row map: keep[row0_b + rows_all_b[j]] = 1, j < len_keep_b
 //      2  rw_dpre_kernel             one workgroup per 32-row tile of the row space: dPRE = dH * d out / d pre on kept rows, zero rows
@@ -43,7 +45,7 @@
 //      4  pw_reduce_kernel           (pure_window.hip) d W1's slabs and d b1's per-tile partials in index order
 //      5  rw_q_chain_kernel          q <- mm^n q + (1 - mm) sum_b mm^(n-1-b) z_b on the bags' tokens
 //      6  mhimx_optim_step           Adam + EMA teacher (update = 1)
-// Launch count: 12 (window-wide: 6 + 6) + 13 x n_bags (17 for a bag above 16 384 rows).  No floating-point atomics, no workgroup waits for another, every sum has a fixed order.
+// Launch count: 13 (window-wide: 7 + 6) + 12 x n_bags (+ 5 window-wide for a bag above 16 384 rows).  No floating-point atomics, no workgroup waits for another, every sum has a fixed order.
 #include <math.h>
 #include <string.h>
 
@@ -409,6 +411,21 @@ extern "C" int mhimx_ragged_window_run_x(void* stream, const mhimx_step_cfg* cfg
   hipLaunchKernelGGL(rw_finalize_kernel, dim3((unsigned)n_bags, 1 + FIN_SCORE_BLOCKS), dim3(RG_FIN_T), 0, st, tab, F(w.pm), F(w.pl), F(w.pz), s_t, cproj, T.bp,
                      (int)C, (int)c.attn2score, F(w.z_t), F(w.stats_t), score_all);
   MHIMX_LAUNCH_CHECK();
+  // ---- HAM mask + Merge split of every bag: rows_all = [rows to merge (R) | rows that stay (Lk) | N .. N + k - 1].  The select reads the
+  // bag's scores, its seed and *tick only (the tick moves once, in A.1): every bag's row list exists before the first bag's middle starts
+  {
+    mhimx_select_bag sb[RW_MAX];
+    for (int b = 0; b < n_bags; ++b) {
+      const mhimx_step_counts& cnt = bags[b].cnt;
+      sb[b] = mhimx_select_bag{tab.row0[b], bags[b].N, cnt.k_top, cnt.n_sel, cnt.R, tab.row0[b], bags[b].seeds.select};
+    }
+    SelLargeWs lw;
+    lw.perm = reinterpret_cast<int64_t*>(base + w.sel_perm); lw.ids = reinterpret_cast<int64_t*>(base + w.sel_ids);
+    lw.rows = reinterpret_cast<int64_t*>(base + w.sel_rows); lw.lk = reinterpret_cast<int64_t*>(base + w.sel_lk);
+    lw.sel_ws = base + w.sel_ws; lw.sel_ws_bytes = w.sel_ws_bytes;
+    if (int r = select_bags_check("ragged_window", n_bags, sb)) return r;
+    if (int r = select_rows_many_launch(st, score_all, n_bags, sb, tick, rows_space, lw, 1)) return r;
+  }
 
   // ================================================================================================ B. the middle, bag after bag
   const float inv_n = 1.f / (float)n_bags;
@@ -419,30 +436,12 @@ extern "C" int mhimx_ragged_window_run_x(void* stream, const mhimx_step_cfg* cfg
     float* Hbuf = H_s + row0 * E;
     float* dH = dHall + row0 * E;
     int64_t* rows_all = rows_space + row0;
-    const float* score = score_all + row0;
     const int acc = b > 0 ? 1 : 0;
     {
       mhimx_prep_job jobs[2];
       jobs[0] = mhimx_prep_job{10, nullptr, reinterpret_cast<float*>(rows_all + len_keep), N, k};
       jobs[1] = mhimx_prep_job{6, reinterpret_cast<const float*>(&mw_prep), static_cast<float*>(merge_ws), R, w.merge_ws_bytes};
       if (int r = mhimx_prep_batch(stream, jobs, 2)) return r;
-    }
-    // ---- HAM mask + Merge split: rows_all = [rows to merge (R) | rows that stay (Lk) | N .. N + k - 1]
-    if (N <= 16384) {
-      if (int r = mhimx_select_rows(stream, score, N, cnt->k_top, cnt->n_sel, 1, g.seeds.select, tick, R, rows_all, nullptr, base + w.sel_ws, w.sel_ws_bytes, 1))
-        return r;
-    } else {
-      // select_large (step.hip: the same four launches + the [merge | stay] swap, the same seeds)
-      int64_t* perm = reinterpret_cast<int64_t*>(base + w.sel_perm);
-      int64_t* ids = reinterpret_cast<int64_t*>(base + w.sel_ids);
-      int64_t* rows = reinterpret_cast<int64_t*>(base + w.sel_rows);
-      if (int r = mhimx_random_perm(stream, cnt->k_top, g.seeds.select + 0x51ED270Bull, tick, nullptr, perm)) return r;
-      if (int r = mhimx_select_mask(stream, score, N, cnt->k_top, cnt->n_sel, 1, cnt->n_sel < cnt->k_top ? perm : nullptr, nullptr, 0, ids,
-                                    reinterpret_cast<int64_t*>(base + w.sel_lk), nullptr, base + w.sel_ws, w.sel_ws_bytes))
-        return r;
-      if (int r = mhimx_random_perm(stream, len_keep, g.seeds.select ^ 0x3C6EF372FE94F82Bull, tick, ids, rows)) return r;
-      MHIMX_HIP(hipMemcpyAsync(rows_all, rows + Lk, (size_t)R * 8, hipMemcpyDeviceToDevice, st));
-      MHIMX_HIP(hipMemcpyAsync(rows_all + R, rows, (size_t)Lk * 8, hipMemcpyDeviceToDevice, st));
     }
     // ---- the student's forward: scorer over the rows that stay (Merge's row tiles ride), the Merge tail, the finalize that scores the tokens
     mhimx_merge mw = mw_prep;

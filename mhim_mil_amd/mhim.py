@@ -855,6 +855,44 @@ class MHIM(nn.Module):
             rows = rows_out[:len_keep]
         return rows, len_keep, Lk, R
 
+    def student_rows_many(self, attns, i=None, mrh=None, merge_first=False, offsets=None):
+        """``student_rows`` of many bags: ``attns`` is a list of per-bag score vectors, or ONE packed vector with ``offsets`` (n + 1 row
+        offsets, bag b = [offsets[b], offsets[b + 1]): what ``ops.infer_many`` returns as ``attn``, ``offsets``).  Returns a list of
+        (rows, len_keep, L_keep, R), bit for bit what a loop over ``student_rows(N_b, i, attn_b, mrh=mrh, merge_first=merge_first)`` returns:
+        one ``_next_seed()`` per bag in bag order either way.  On the production condition of ``student_rows`` (v2 recipe, ABMIL / DSMIL,
+        no injected draws) with a table ``ops.select_bags_ok`` takes, all bags go through ONE ``ops.select_rows_many`` (bags of up to
+        16 384 rows share one launch); anything else - a ratio schedule without an iteration ``i`` included, which ``student_rows``
+        refuses - is that loop."""
+        if offsets is not None:
+            if not (torch.is_tensor(attns) and attns.dim() == 1):
+                raise L.MhimxError("student_rows_many: with offsets, attns must be ONE packed 1-D score vector")
+            offsets = [int(o) for o in offsets]
+            if len(offsets) < 2 or offsets[0] < 0 or any(b <= a for a, b in zip(offsets[:-1], offsets[1:])) or offsets[-1] > attns.numel():
+                raise L.MhimxError("student_rows_many: offsets must be n + 1 increasing row offsets inside the packed score vector")
+            views = [attns[a:b] for a, b in zip(offsets[:-1], offsets[1:])]
+        else:
+            if torch.is_tensor(attns) or len(attns) == 0 or not all(torch.is_tensor(a) and a.numel() > 0 for a in attns):
+                raise L.MhimxError("student_rows_many: attns must be a non-empty list of non-empty score vectors (or a packed vector with offsets)")
+            views = [a.reshape(-1) for a in attns]
+            offsets = [0]
+            for a in views:
+                offsets.append(offsets[-1] + a.numel())
+        # (student_rows reads mrh_sche[i] whatever i is; v2_counts skips the schedule when i is None: that case is the loop's, error included)
+        sched_ok = self.mrh_sche is None or i is not None
+        counts = [self.v2_counts(v.numel(), i, mrh) if sched_ok else None for v in views]
+        table, out0 = [], 0
+        if self.baseline in ("attn", "dsmil") and all(c is not None for c in counts):
+            for v, off, (k, n_sel, len_keep, Lk, R) in zip(views, offsets, counts):
+                table.append([off, v.numel(), k, n_sel, R, out0, 0])
+                out0 += len_keep
+        if not table or not ops.select_bags_ok(table) or any(c[4] == 0 for c in counts):
+            return [self.student_rows(v.numel(), i, v, mrh=mrh, merge_first=merge_first) for v in views]
+        for row in table:
+            row[6] = self._next_seed()
+        score = attns if torch.is_tensor(attns) else torch.cat(views)
+        rows = ops.select_rows_many(score.contiguous().float(), table, tick=self._tick, merge_first=merge_first)
+        return [(r, c[2], c[3], c[4]) for r, c in zip(rows, counts)]
+
     # ------------------------------------------------------------------ reference entry points
     @torch.no_grad()
     def forward_teacher(self, x, drop_mask=None, xp=None, w1p=None, wa_frag=None, H=None, tok_full=None):

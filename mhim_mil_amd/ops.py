@@ -1184,6 +1184,67 @@ def topk_many(score, offsets, k, largest=True, want_values=True, ws=None):
     return idx, val
 
 
+# ------------------------------------------------------------------------------------------- the production select of many bags
+_SELECT_WS = {}             # device index -> the cached workspace
+
+
+def select_bags(bags):
+    """The L.SelectBag table of a mhimx_select_rows_many call; ``bags``: one (row0, N, k, n_sel, merge_R, out0, seed) per bag."""
+    return (L.SelectBag * max(len(bags), 1))(*[L.SelectBag(row0=int(r), N=int(n), k=int(k), n_sel=int(s), merge_R=int(m), out0=int(o),
+                                                           seed=int(sd) & 0xFFFFFFFFFFFFFFFF) for r, n, k, s, m, o, sd in bags])
+
+
+def select_bags_ok(bags):
+    """csrc/select_many.hip sm_check, mirrored (tensor-free): 1 .. L.INFER_MAX bags; N in 1 .. L.STEP_MAX_ROWS; k in 1 .. min(N, 4096) up to
+    16 384 rows and 1 .. min(N, 16384) above; n_sel in 0 .. k; merge_R in 0 .. N - n_sel; row0, out0 >= 0; no two non-empty output
+    ranges [out0, out0 + N - n_sel) overlap.  ``bags``: (row0, N, k, n_sel, merge_R, out0, seed) per bag."""
+    if not 1 <= len(bags) <= L.INFER_MAX:
+        return False
+    for r, n, k, s, m, o, _ in bags:
+        if not (1 <= n <= L.STEP_MAX_ROWS and 1 <= k <= min(n, 4096 if n <= 16384 else 16384) and 0 <= s <= k and 0 <= m <= n - s
+                and r >= 0 and o >= 0):
+            return False
+    spans = [(o, o + n - s) for _, n, _, s, _, o, _ in bags]
+    return not any(a0 < a1 and b0 < b1 and a0 < b1 and b0 < a1 for i, (b0, b1) in enumerate(spans) for a0, a1 in spans[:i])
+
+
+def select_rows_many_ws_bytes(bags):
+    """mhimx_select_rows_many_ws_bytes for (row0, N, k, n_sel, merge_R, out0, seed) tuples: host arithmetic only (< 0: a refused table)."""
+    return L.lib().mhimx_select_rows_many_ws_bytes(len(bags), select_bags(bags))
+
+
+def select_rows_many(score, bags, tick=None, merge_first=False, out=None, ws=None):
+    """select_rows of up to L.INFER_MAX bags in ONE C call (mhimx_select_rows_many): bag b = (row0, N, k, n_sel, merge_R, out0, seed) ranks
+    ``score[row0 : row0 + N]`` and writes ``out[out0 : out0 + N - n_sel]`` - the bits ``select_rows`` writes for it (above 16 384 rows:
+    the random_perm / select_mask / random_perm sequence), wherever it stands.  Bags of up to 16 384 rows share one launch.  ``out``: an
+    int64 device vector that holds every output range (default: one just long enough); ``ws``: a uint8 workspace of the caller's (tests
+    poison it; default: one cached per device - inside a stream capture a fresh one, owned by the graph's pool).  Returns the list of
+    per-bag views of ``out``."""
+    _chk(score, name="score"); _chk(out, torch.int64, "rows out")
+    if score is None or score.dim() != 1:
+        raise L.MhimxError("select_rows_many: score must be a 1-D fp32 GPU vector")
+    bags = [tuple(int(v) for v in b) for b in bags]
+    if len(bags) > L.INFER_MAX:
+        raise L.MhimxError(f"select_rows_many: {len(bags)} bags in one call (at most {L.INFER_MAX}): chunk the table")
+    tab = select_bags(bags)
+    need = L.lib().mhimx_select_rows_many_ws_bytes(len(bags), tab)
+    if need < 0:
+        L.check(int(need), "mhimx_select_rows_many_ws_bytes")
+    if any(r + n > score.numel() for r, n, *_ in bags):
+        raise L.MhimxError(f"select_rows_many: a bag ends behind the score vector ({score.numel()} entries)")
+    end = max(o + n - s for _, n, _, s, _, o, _ in bags)
+    dev = score.device
+    if out is None:
+        out = torch.empty(end, dtype=torch.int64, device=dev)
+    elif out.dim() != 1 or out.numel() < end:
+        raise L.MhimxError(f"select_rows_many: rows out holds {out.numel()} entries, the bags' output ranges end at {end}")
+    if ws is None:
+        ws = workspace(_SELECT_WS, dev.index, need, dev, slack=1.0)
+    L.check(L.lib().mhimx_select_rows_many(_stream(), _p(score), len(bags), tab, _p(tick), _p(out), _p(ws), ws.numel(), int(bool(merge_first))),
+            "mhimx_select_rows_many")
+    return [out[o:o + n - s] for _, n, _, s, _, o, _ in bags]
+
+
 # ------------------------------------------------------------------------------------------- single-bag steps, the same-shape window
 def step_layout(cfg, N, cnt=None):
     """mhimx_step_layout_of for a bag of N rows with the counts ``cnt`` (None: mhimx_pure_step_layout_of - every row takes part): host
