@@ -96,6 +96,15 @@ inline mhimx_optim_args optim_args_of(const mhimx_step_cfg& c, int64_t host_step
   return o;
 }
 
+// the device counters at the head of every train call's preparation launch: the dropout / draw tick and, when the call has one, the
+// optimiser step.  Returns the number of jobs written (1 or 2)
+inline int prep_counters(const mhimx_step_cfg& c, mhimx_prep_job* j) {
+  int n = 0;
+  j[n++] = mhimx_prep_job{3, nullptr, reinterpret_cast<float*>(c.tick), 1, 1};
+  if (c.opt_step) j[n++] = mhimx_prep_job{3, nullptr, reinterpret_cast<float*>(c.opt_step), 1, 1};
+  return n;
+}
+
 // bump allocator over a caller-provided workspace (256-byte granules)
 struct Arena {
   char* base;

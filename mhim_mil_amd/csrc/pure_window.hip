@@ -584,9 +584,7 @@ extern "C" int mhimx_pure_window_run_x(void* stream, const mhimx_step_cfg* cfg, 
   // ---- 1. counters and weight images
   {
     mhimx_prep_job jobs[4];
-    int n = 0;
-    jobs[n++] = mhimx_prep_job{3, nullptr, reinterpret_cast<float*>(c.tick), 1, 1};
-    if (c.opt_step) jobs[n++] = mhimx_prep_job{3, nullptr, reinterpret_cast<float*>(c.opt_step), 1, 1};
+    int n = prep_counters(c, jobs);
     jobs[n++] = mhimx_prep_job{1, S.w1, w1p, c.E, c.D};
     jobs[n++] = mhimx_prep_job{4, S.wa, wa_frag, c.A, c.E};
     if (int r = mhimx_prep_batch(stream, jobs, n)) return r;

@@ -25,7 +25,8 @@
 //                                     of mhimx_select_rows' production kernel; a bag above 16 384 rows: select_large_rows behind it
 //                                     (random_perm, select_mask, random_perm, two copies) out of the call's select scratch.  The select
 //                                     reads the bag's scores, its seed and *tick (which moves once, in A.1): the same bits as inside the loop
-//   B. the middle, bag after bag: mhimx_step_run's entry points in its order with pointers into the bag's slot (12 launches per bag)
+//   B. the middle, bag after bag: mhimx_step_run's entry points in its order with pointers into the bag's slot (12 launches per bag;
+//      launches 2-9 through step_mid.hpp's one copy: mid_student_fwd, mid_head, mid_bwd_rows)
 //      1     mhimx_prep_batch        the row list's constant tail, the parameter-only part of this bag's Merge (its workspace is shared)
 //      2     mhimx_abmil_pool_fwd    phase 1: student scorer over the rows that stay, Merge's rows pass riding
 //      3-5   mhimx_merge_fwd         partial merge | O | to_out (the queries' EMA goes to scratch: the window's first queries stay)
@@ -50,6 +51,7 @@
 #include <string.h>
 
 #include "infer_tab.hpp"
+#include "step_mid.hpp"
 
 namespace mhimx {
 
@@ -356,12 +358,11 @@ extern "C" int mhimx_ragged_window_run_x(void* stream, const mhimx_step_cfg* cfg
   if (int r = rg_check_ws("ragged_window", ws, ws_bytes, w.total)) return r;
   const mhimx_step_cfg& c = *cfg;
   const mhimx_step_params &S = c.student, &T = c.teacher;
-  const int64_t D = c.D, E = c.E, A = c.A, C = c.C, k = c.k, I = 512;
+  const int64_t D = c.D, E = c.E, C = c.C, k = c.k;
   hipStream_t st = (hipStream_t)stream;
   char* base = static_cast<char*>(ws);
   auto F = [&](int64_t off) { return reinterpret_cast<float*>(base + off); };
-  float *w1p_t = F(w.w1p_t), *wa_frag_t = F(w.wa_frag_t), *w1p_s = F(w.w1p_s), *wa_frag_s = F(w.wa_frag_s), *wa_t = F(w.wa_t), *wa_t_frag = F(w.wa_t_frag);
-  float *wo_t = F(w.wo_t), *q_old = F(w.q_old), *q_scr = F(w.q_scr);
+  const MidImages im = {F(w.w1p_t), F(w.wa_frag_t), F(w.w1p_s), F(w.wa_frag_s), F(w.wa_t), F(w.wa_t_frag), F(w.wo_t), F(w.q_old)};
   float *H_t = F(w.H_t), *H_s = F(w.H_s), *dHall = F(w.dH), *s_t = F(w.s_t), *score_all = F(w.score), *cproj = F(w.cproj);
   _Float16* dact = reinterpret_cast<_Float16*>(base + w.dact);
   int64_t* rows_space = reinterpret_cast<int64_t*>(base + w.rows_all);
@@ -370,23 +371,11 @@ extern "C" int mhimx_ragged_window_run_x(void* stream, const mhimx_step_cfg* cfg
   const uint64_t* tick = c.tick;
 
   // ================================================================================================ A. the teacher half, window-wide
-  mhimx_merge mw_prep = {};            // the parameter-only part of the student's Merge (read while enqueueing: prep job kind 6, per bag)
-  mw_prep.E = E; mw_prep.k = k; mw_prep.heads = 8; mw_prep.dim_head = 64;
-  mw_prep.q_param = S.q; mw_prep.ln_w = S.ln_w; mw_prep.ln_b = S.ln_b; mw_prep.wkv = S.wkv; mw_prep.wq = S.wq; mw_prep.wo = S.wo; mw_prep.bo = S.bo;
-  mw_prep.mm = c.merge_mm; mw_prep.prec = MHIMX_PREC_BF16X3; mw_prep.drop_tick = tick; mw_prep.rep = 1.f;
+  const mhimx_merge mw_prep = mid_merge_params(c);            // (read while enqueueing, by every bag's kind-6 job: alive until the last bag's)
   {
     mhimx_prep_job jobs[10];
-    int n = 0;
-    jobs[n++] = mhimx_prep_job{3, nullptr, reinterpret_cast<float*>(c.tick), 1, 1};
-    if (c.opt_step) jobs[n++] = mhimx_prep_job{3, nullptr, reinterpret_cast<float*>(c.opt_step), 1, 1};
-    jobs[n++] = mhimx_prep_job{1, T.w1, w1p_t, E, D};
-    jobs[n++] = mhimx_prep_job{4, T.wa, wa_frag_t, A, E};
-    jobs[n++] = mhimx_prep_job{1, S.w1, w1p_s, E, D};
-    jobs[n++] = mhimx_prep_job{4, S.wa, wa_frag_s, A, E};
-    jobs[n++] = mhimx_prep_job{0, S.wa, wa_t, A, E};
-    jobs[n++] = mhimx_prep_job{5, S.wa, wa_t_frag, A, E};
-    jobs[n++] = mhimx_prep_job{0, S.wo, wo_t, E, I};
-    jobs[n++] = mhimx_prep_job{2, S.q, q_old, 1, k * E};
+    int n = mid_prep_head(c, im, jobs);
+    n += mid_prep_student(c, im, jobs + n);
     if (int r = mhimx_prep_batch(stream, jobs, n)) return r;
   }
   // both models' feature rows into the row space (mhim.py:186 and :335-336): the teacher first - its d out / d pre rows are overwritten by
@@ -396,17 +385,17 @@ extern "C" int mhimx_ragged_window_run_x(void* stream, const mhimx_step_cfg* cfg
     dr.tick = tick; dr.dact = dact;
     for (int b = 0; b < n_bags; ++b) dr.seed[b] = bags[b].seeds.drop_teacher;
     dr.drop_p = c.drop_p_teacher;
-    if (int r = pure_window_project(st, tab, dr, (int)D, w1p_t, T.b1, c.act, H_t)) return r;
+    if (int r = pure_window_project(st, tab, dr, (int)D, im.w1p_t, T.b1, c.act, H_t)) return r;
     for (int b = 0; b < n_bags; ++b) dr.seed[b] = bags[b].seeds.drop_student;
     dr.drop_p = c.drop_p_student;
-    if (int r = pure_window_project(st, tab, dr, (int)D, w1p_s, S.b1, c.act, H_s)) return r;
+    if (int r = pure_window_project(st, tab, dr, (int)D, im.w1p_s, S.b1, c.act, H_s)) return r;
   }
   hipLaunchKernelGGL(rw_pad_kernel, dim3((unsigned)n_bags, 4), dim3(RW_T), 0, st, tab, cn, H_t, H_s, dact, keep);
   MHIMX_LAUNCH_CHECK();
   // the teacher's scores, pool partials and (attn2score) class projections; then plane = bag: stats, z_teacher, every row's instance score
   if (c.attn2score) {
-    if (int r = infer_score_cproj(st, tab, H_t, wa_frag_t, T.wc, c.da_act, s_t, F(w.pm), F(w.pl), F(w.pz), T.wp, (int)C, cproj)) return r;
-  } else if (int r = infer_score(st, tab, H_t, wa_frag_t, T.wc, c.da_act, s_t, F(w.pm), F(w.pl), F(w.pz)))
+    if (int r = infer_score_cproj(st, tab, H_t, im.wa_frag_t, T.wc, c.da_act, s_t, F(w.pm), F(w.pl), F(w.pz), T.wp, (int)C, cproj)) return r;
+  } else if (int r = infer_score(st, tab, H_t, im.wa_frag_t, T.wc, c.da_act, s_t, F(w.pm), F(w.pl), F(w.pz)))
     return r;
   hipLaunchKernelGGL(rw_finalize_kernel, dim3((unsigned)n_bags, 1 + FIN_SCORE_BLOCKS), dim3(RG_FIN_T), 0, st, tab, F(w.pm), F(w.pl), F(w.pz), s_t, cproj, T.bp,
                      (int)C, (int)c.attn2score, F(w.z_t), F(w.stats_t), score_all);
@@ -431,64 +420,25 @@ extern "C" int mhimx_ragged_window_run_x(void* stream, const mhimx_step_cfg* cfg
   const float inv_n = 1.f / (float)n_bags;
   for (int b = 0; b < n_bags; ++b) {
     const mhimx_ragged_window_bag& g = bags[b];
-    const mhimx_step_counts* cnt = &g.cnt;
-    const int64_t N = g.N, R = cnt->R, Lk = cnt->Lk, len_keep = cnt->len_keep, row0 = tab.row0[b];
-    float* Hbuf = H_s + row0 * E;
-    float* dH = dHall + row0 * E;
+    const int64_t N = g.N, R = g.cnt.R, row0 = tab.row0[b];
     int64_t* rows_all = rows_space + row0;
     const int acc = b > 0 ? 1 : 0;
     {
       mhimx_prep_job jobs[2];
-      jobs[0] = mhimx_prep_job{10, nullptr, reinterpret_cast<float*>(rows_all + len_keep), N, k};
+      jobs[0] = mhimx_prep_job{10, nullptr, reinterpret_cast<float*>(rows_all + g.cnt.len_keep), N, k};
       jobs[1] = mhimx_prep_job{6, reinterpret_cast<const float*>(&mw_prep), static_cast<float*>(merge_ws), R, w.merge_ws_bytes};
       if (int r = mhimx_prep_batch(stream, jobs, 2)) return r;
     }
-    // ---- the student's forward: scorer over the rows that stay (Merge's row tiles ride), the Merge tail, the finalize that scores the tokens
-    mhimx_merge mw = mw_prep;
-    mw.drop_p = c.merge_drop_p; mw.drop_seed = g.seeds.mca; mw.x_rows = rows_all; mw.prepared = 1;
-    mhimx_scorer sc_s = {};
-    sc_s.E = E; sc_s.A = A; sc_s.act = c.da_act; sc_s.prec = MHIMX_PREC_BF16X3; sc_s.wa = S.wa; sc_s.wc = S.wc; sc_s.wa_frag = wa_frag_s;
-    mhimx_pool_io io_s = {};
-    io_s.T1 = Hbuf; io_s.M1 = Lk + k; io_s.s = F(w.s_s); io_s.stats = F(w.stats_s); io_s.z = F(w.z_s) + (int64_t)b * E;
-    io_s.ws = base + w.pool_ws_s; io_s.ws_bytes = w.pool_ws_s_bytes; io_s.rows1 = rows_all + R;
-    io_s.tail_row0 = -1;
-    if (k <= 6) {
-      io_s.phase = 1; io_s.tail_tokens = (int32_t)k;
-      io_s.ride_merge = &mw; io_s.ride_X = Hbuf; io_s.ride_R = R; io_s.ride_ws = merge_ws; io_s.ride_ws_bytes = w.merge_ws_bytes;
-      if (int r = mhimx_abmil_pool_fwd(stream, &sc_s, &io_s)) return r;
-      mw.rows_done = io_s.rode_merge;
-      if (int r = mhimx_merge_fwd(stream, &mw, Hbuf, R, Hbuf + N * E, q_scr, 1, merge_ws, w.merge_ws_bytes)) return r;
-      mw.rows_done = 0;
-      io_s.phase = 2; io_s.tail_wa_t = wa_t; io_s.tail_row0 = N;
-      if (int r = mhimx_abmil_pool_fwd(stream, &sc_s, &io_s)) return r;
-      io_s.phase = 0; io_s.ride_merge = nullptr;
-    } else {
-      if (int r = mhimx_merge_fwd(stream, &mw, Hbuf, R, Hbuf + N * E, q_scr, 1, merge_ws, w.merge_ws_bytes)) return r;
-      if (int r = mhimx_abmil_pool_fwd(stream, &sc_s, &io_s)) return r;
-    }
-    // ---- head: this bag's loss / n_bags (base_engine.py:102)
-    float* g_z = F(w.g_z);
-    if (int r = mhimx_head_fwd_bwd(stream, io_s.z, c.aux_alpha != 0.f ? F(w.z_t) + (int64_t)b * E : nullptr, S.wp, S.bp, g.label_dev, E, C, c.temp_t, c.main_alpha,
-                                   c.aux_alpha, inv_n, F(w.logits) + 16 * b, F(w.losses) + 4 * b, g_z, c.grad.wp, c.grad.bp, acc, nullptr, nullptr))
-      return r;
-    // ---- backward down to the gradient rows of the bag's slot
+    // ---- the student's forward (the queries' EMA goes to scratch), the head with this bag's loss / n_bags (base_engine.py:102), the
+    // backward down to the gradient rows of the bag's slot (no fused dPRE image: part C makes it for the whole row space)
+    const MidBag mb = {H_s + row0 * E, dHall + row0 * E, rows_all, N, R, g.cnt.Lk, g.seeds.mca, F(w.q_scr), F(w.s_s), F(w.stats_s), F(w.z_s) + (int64_t)b * E,
+                       F(w.g_z), base + w.pool_ws_s, w.pool_ws_s_bytes, merge_ws, w.merge_ws_bytes};
+    MidFwd fwd;
+    if (int r = mid_student_fwd(stream, c, im, mw_prep, mb, nullptr, &fwd)) return r;
+    if (int r = mid_head(stream, c, mb, F(w.z_t) + (int64_t)b * E, g.label_dev, inv_n, F(w.logits) + 16 * b, F(w.losses) + 4 * b, c.grad, acc)) return r;
     mhimx_reduce_list lst;
     memset(&lst, 0, sizeof(lst));
-    mhimx_merge mwb = mw;
-    mwb.q_param = q_old; mwb.wo_t = wo_t; mwb.prepared = 0;
-    mhimx_merge_grad mg = {};
-    mg.d_ln_w = c.grad.ln_w; mg.d_ln_b = c.grad.ln_b; mg.d_wkv = c.grad.wkv; mg.d_wq = c.grad.wq; mg.d_wo = c.grad.wo; mg.d_bo = c.grad.bo;
-    mg.accumulate = acc; mg.splits = 8; mg.defer = &lst;
-    if (int r = mhimx_merge_bwd_park(&mwb, Hbuf, R, dH + N * E, dH, &mg, merge_ws, w.merge_ws_bytes)) return r;
-    {
-      mhimx_scorer sc_b = sc_s;
-      sc_b.wa_frag = nullptr;
-      mhimx_pool_grad pg = {};
-      pg.g_z = g_z; pg.dT1 = dH; pg.d_wa = c.grad.wa; pg.d_wc = c.grad.wc; pg.wa_t = wa_t; pg.accumulate = acc; pg.splits = 8; pg.defer = &lst;
-      pg.wa_t_frag = wa_t_frag;
-      if (int r = mhimx_abmil_pool_bwd(stream, &sc_b, &io_s, &pg)) return r;
-    }
-    if (int r = mhimx_merge_bwd(stream, &mwb, Hbuf, R, dH + N * E, dH, &mg, merge_ws, w.merge_ws_bytes)) return r;
+    if (int r = mid_bwd_rows(stream, im, fwd, mb, c.grad, acc, nullptr, nullptr, &lst)) return r;
     if (int r = mhimx_reduce_flush(stream, &lst)) return r;      // (the per-bag workspaces are the next bag's: nothing stays queued)
   }
 
@@ -507,13 +457,9 @@ extern "C" int mhimx_ragged_window_run_x(void* stream, const mhimx_step_cfg* cfg
   }
   {
     RwChain ch = {};
-    const double mm = (double)c.merge_mm;
     ch.n = n_bags;
-    ch.wq = (float)pow(mm, (double)n_bags);
-    for (int b = 0; b < n_bags; ++b) {
-      ch.w[b] = (float)((1.0 - mm) * pow(mm, (double)(n_bags - 1 - b)));
-      ch.tok[b] = tab.row0[b] + bags[b].N;
-    }
+    q_chain_weights((double)c.merge_mm, n_bags, &ch.wq, ch.w);
+    for (int b = 0; b < n_bags; ++b) ch.tok[b] = tab.row0[b] + bags[b].N;
     hipLaunchKernelGGL(rw_q_chain_kernel, dim3((unsigned)cdiv(k * E, RW_T)), dim3(RW_T), 0, st, S.q, H_s, ch, (int)(k * E));
     MHIMX_LAUNCH_CHECK();
   }

@@ -1,22 +1,29 @@
 // step.hip — mhimx_step_run: the whole MHIM(ABMIL) train step of one bag behind ONE C call (include/mhimx.h).
 //
 // replaces: engines/common_mil.py:14-48 + engines/base_engine.py:76-167 for one bag - and, on this side of the boundary, the Python
-// orchestration of mhim_mil_amd/engine.py (FusedTrainer._nat_prep / _nat_bag / _apply): the SAME entry points in the SAME order with the SAME
-// arguments, so a step through this executor has the bits of a step through the Python path given the same seeds.  Host code only: every
-// launch goes through the library's own extern "C" entry points.  No allocation, no synchronisation: the caller owns the workspace.
+// orchestration of mhim_mil_amd/engine.py (FusedTrainer._nat_prep / _nat_bag / _apply): the SAME entry points in the SAME order on the SAME
+// seeds.  Bit-equal to a step through the Python path: logits, losses, the row list, the teacher's score, the merged tokens and every
+// gradient but the projection's pair (feature.0.weight / .bias).  That pair is bit-equal above 16 384 rows only: up to 16 384 rows the
+// scorer backward writes the stay rows' share of the dPRE image itself and the image is ordered [stay | merge] - the same sum in another
+// order, so the pair, and behind it the parameters and moments, agree to rounding (tests/test_round5_gpu.py::_same_state).  Host code
+// only: every launch goes through the library's own extern "C" entry points.  No allocation, no synchronisation: the caller owns the
+// workspace.  The student's middle (Merge description, preparation jobs, scorer descriptors, forward, head, backward down to the gradient
+// rows) is step_mid.hpp's: ONE copy for this call, mhimx_window_run below and mhimx_ragged_window_run (ragged_window.hip).
 //
 //   launch  1  mhimx_prep_batch         counters, both projection weight images, the teacher's scorer image (+ the row list's constant tail)
 //           2  mhimx_bag_project        teacher + student feature rows in ONE pass over the raw bag
 //         3,4  mhimx_abmil_pool_fwd     teacher scorer + pool partials (the student-side preparation jobs ride here) | finalize + pseudo score
-//           5  mhimx_select_rows        HAM mask + Merge split, both random subsets drawn on the device
-//        6..9  mhimx_merge_fwd          rows pass | partial merge | O | to_out + EMA of the global queries
-//       10,11  mhimx_abmil_pool_fwd     student scorer over [stay | tokens] | finalize
-//          12  mhimx_head_fwd_bwd       predictor, CE, distillation, their gradients
-//          13  mhimx_abmil_pool_bwd     one-pass rows backward: [token block | row tiles | the Merge backward's first stage, riding]; the
+//           5  mhimx_select_rows_img    HAM mask + Merge split, both random subsets drawn on the device, the dPRE image's row order
+//                                       (above 16 384 rows: select_large_rows, select_many.hip - random_perm, select_mask, random_perm, two copies)
+//           6  mhimx_abmil_pool_fwd     phase 1: student scorer over the rows that stay, Merge's rows pass riding
+//        7..9  mhimx_merge_fwd          partial merge | O | to_out + EMA of the global queries
+//          10  mhimx_abmil_pool_fwd     phase 2: the finalize that scores the tokens
+//          11  mhimx_head_fwd_bwd       predictor, CE, distillation, their gradients
+//          12  mhimx_abmil_pool_bwd     one-pass rows backward: [token block | row tiles | the Merge backward's first stage, riding]; the
 //                                       token block (block 0) makes the k tokens' gradient rows alone and opens the riders' gate
-//          14  mhimx_merge_bwd          rows backward + the parked scorer-weight-gradient product in one launch
-//       15,16  rows_dpre_image | bag_wgrad   the projection's gradient pair (the Merge tail and the last reductions ride)
-//          17  mhimx_optim_step         Adam + EMA teacher (folds the split-K slab sum)
+//          13  mhimx_merge_bwd          rows backward + the parked scorer-weight-gradient product in one launch
+//       14,15  rows_dpre_image | bag_wgrad   the projection's gradient pair (the Merge tail and the last reductions ride)
+//          16  mhimx_optim_step         Adam + EMA teacher (folds the split-K slab sum)
 //
 // Round 6 - the step as a DAG (mhimx_step_cfg.side_stream).  The chain above serialises launches that share no data;
 // with a second stream the executor forks and joins through events (capturable: the trainer's hipGraph of the step gets parallel branches):
@@ -35,7 +42,8 @@
 #include <math.h>
 #include <string.h>
 
-#include "common.hpp"
+#include "infer_tab.hpp"
+#include "step_mid.hpp"
 
 namespace mhimx {
 
@@ -110,13 +118,12 @@ struct StepBufs {
   int64_t logits, losses, g_z;
   int64_t dH, img, ws_b, ws_b_bytes, wg_ws, wg_ws_floats;
   int64_t q_scr, gslab;              // (a window's bag: where its forward's query EMA goes, its gradient slab)
-  int64_t rows_img, P0, L_img;       // (round 6, fuse_img) the kept rows in the dPRE image's order [stay | 0.. | merge from P0 | 0..], the image's rows
-  bool fuse_img;
+  int64_t rows_img, P0, L_img;       // (round 6, up to 16 384 rows) the kept rows in the dPRE image's order [stay | 0.. | merge from P0 | 0..], the image's rows
   int64_t bag0, bag_stride;          // the per-bag part of the workspace: bag b's copy of everything from merge_ws on starts bag0 + b * bag_stride
   int64_t total;
 };
 
-// fuse_img: the scorer backward wrote the stay rows' share of the dPRE image (image rows 0 .. P0-1, one partial row of column sums per tile);
+// up to 16 384 rows: the scorer backward wrote the stay rows' share of the dPRE image (image rows 0 .. P0-1, one partial row of column sums per tile);
 // this is the rest - the rows to merge from image row P0 on (mhimx_rows_dpre_image on that part of the image; the Merge backward's tail
 // stage still rides there) - and the two sets of column-sum partials become ONE queued reduction.
 int dpre_merge_rows(void* stream, const float* dH, const void* dact, const int64_t* rows_merge, int64_t R, int64_t E, char* img, int64_t P0, float* d_b1,
@@ -174,9 +181,9 @@ void layout(const mhimx_step_cfg* c, int64_t N, const mhimx_step_counts* n, Step
   b->merge_ws = cv.take_off(b->merge_ws_bytes);
   // (round 6) up to 16 384 rows the stay rows' share of the projection's dPRE image is written by the scorer backward itself
   // (mhimx_pool_grad.img): the image is ordered [rows that stay, tile for tile of that launch | rows to merge from P0 on]
-  b->fuse_img = N <= 16384;
-  b->P0 = b->fuse_img ? (n->Lk + k + 31) / 32 * 32 : 0;
-  b->L_img = b->fuse_img ? b->P0 + n->R : n->len_keep;
+  const bool fuse_img = N <= 16384;
+  b->P0 = fuse_img ? (n->Lk + k + 31) / 32 * 32 : 0;
+  b->L_img = fuse_img ? b->P0 + n->R : n->len_keep;
   b->H_t = cv.take_off(N * E * F);
   b->Hbuf = cv.take_off((N + k) * E * F);
   b->dact = cv.take_off(N * E * 2);
@@ -191,7 +198,7 @@ void layout(const mhimx_step_cfg* c, int64_t N, const mhimx_step_counts* n, Step
   b->rows_all = cv.take_off((n->len_keep + k) * 8);
   b->sel_ws_bytes = mhimx_select_ws_bytes(N);
   b->sel_ws = cv.take_off(b->sel_ws_bytes);
-  b->rows_img = b->fuse_img ? cv.take_off((b->L_img + 31) / 32 * 32 * 8) : 0;
+  b->rows_img = fuse_img ? cv.take_off((b->L_img + 31) / 32 * 32 * 8) : 0;
   b->sel_perm = b->sel_ids = b->sel_rows = b->sel_lk = 0;
   if (N > 16384) {
     b->sel_perm = cv.take_off(n->k_top * 8);
@@ -210,7 +217,7 @@ void layout(const mhimx_step_cfg* c, int64_t N, const mhimx_step_counts* n, Step
   b->g_z = cv.take_off(E * F);
   b->dH = cv.take_off((N + k) * E * F);
   b->img = cv.take_off(mhimx_wgrad_image_bytes(b->L_img, E));
-  b->ws_b_bytes = (b->fuse_img ? b->P0 / 32 + (n->R + 31) / 32 : (n->len_keep + 31) / 32) * E * F;
+  b->ws_b_bytes = (fuse_img ? b->P0 / 32 + (n->R + 31) / 32 : (n->len_keep + 31) / 32) * E * F;
   b->ws_b = cv.take_off(b->ws_b_bytes);
   b->q_scr = b->gslab = 0;
   if (n_bags > 1) {
@@ -227,6 +234,121 @@ void layout(const mhimx_step_cfg* c, int64_t N, const mhimx_step_counts* n, Step
 }  // namespace
 
 int step_check_cfg(const mhimx_step_cfg* c, int64_t N, const mhimx_step_counts* n) { return check_cfg(c, N, n); }      // (ragged_window.hip)
+
+// ---------------------------------------------------------------------------------------------- the student's middle (step_mid.hpp)
+mhimx_merge mid_merge_params(const mhimx_step_cfg& c) {
+  const mhimx_step_params& S = c.student;
+  mhimx_merge m = {};
+  m.E = c.E; m.k = c.k; m.heads = 8; m.dim_head = 64;
+  m.q_param = S.q; m.ln_w = S.ln_w; m.ln_b = S.ln_b; m.wkv = S.wkv; m.wq = S.wq; m.wo = S.wo; m.bo = S.bo;
+  m.mm = c.merge_mm; m.prec = MHIMX_PREC_BF16X3; m.drop_tick = c.tick; m.rep = 1.f;
+  return m;
+}
+
+int mid_prep_head(const mhimx_step_cfg& c, const MidImages& im, mhimx_prep_job* j) {
+  int n = prep_counters(c, j);
+  j[n++] = mhimx_prep_job{1, c.teacher.w1, im.w1p_t, c.E, c.D};
+  j[n++] = mhimx_prep_job{4, c.teacher.wa, im.wa_frag_t, c.A, c.E};
+  j[n++] = mhimx_prep_job{1, c.student.w1, im.w1p_s, c.E, c.D};
+  return n;
+}
+
+int mid_prep_student(const mhimx_step_cfg& c, const MidImages& im, mhimx_prep_job* j) {
+  const mhimx_step_params& S = c.student;
+  j[0] = mhimx_prep_job{4, S.wa, im.wa_frag_s, c.A, c.E};
+  j[1] = mhimx_prep_job{0, S.wa, im.wa_t, c.A, c.E};
+  j[2] = mhimx_prep_job{5, S.wa, im.wa_t_frag, c.A, c.E};
+  j[3] = mhimx_prep_job{0, S.wo, im.wo_t, c.E, 512};
+  j[4] = mhimx_prep_job{2, S.q, im.q_old, 1, c.k * c.E};
+  return 5;
+}
+
+mhimx_scorer mid_scorer(const mhimx_step_cfg& c, const mhimx_step_params& p, const float* wa_frag) {
+  mhimx_scorer sc = {};
+  sc.E = c.E; sc.A = c.A; sc.act = c.da_act; sc.prec = MHIMX_PREC_BF16X3; sc.wa = p.wa; sc.wc = p.wc; sc.wa_frag = wa_frag;
+  return sc;
+}
+
+// The student's scorer over the rows that stay and Merge's rows pass are independent: ONE launch runs both (the Merge row tiles ride at its
+// front), the Merge tail then makes the tokens, and the pool's finalize launch scores those k rows itself (mhimx_pool_io.phase; k <= 6:
+// check_cfg).  Merge (merge.py:127-203): the k tokens land behind the bag's rows.
+int mid_student_fwd(void* stream, const mhimx_step_cfg& c, const MidImages& im, const mhimx_merge& mw_prep, const MidBag& g, const MidDag* dag, MidFwd* f) {
+  const int64_t E = c.E, k = c.k;
+  mhimx_merge& mw = f->mw;
+  mw = mw_prep;
+  mw.drop_p = c.merge_drop_p; mw.drop_seed = g.mca_seed; mw.x_rows = g.rows_all; mw.prepared = 1;
+  f->sc_s = mid_scorer(c, c.student, im.wa_frag_s);
+  mhimx_pool_io& io = f->io_s;
+  io = mhimx_pool_io{};
+  io.T1 = g.Hbuf; io.M1 = g.Lk + k; io.s = g.s_s; io.stats = g.stats_s; io.z = g.z_s;
+  io.ws = g.pool_ws; io.ws_bytes = g.pool_ws_bytes; io.rows1 = g.rows_all + g.R;
+  io.tail_row0 = -1;
+  io.phase = 1; io.tail_tokens = (int32_t)k;
+  if (dag) {
+    // two branches: the scorer over the rows that stay (side) || Merge's whole chain (main); they meet at the finalize that scores the tokens
+    if (int r = dag_edge(dag->ev[0], dag->main_st, dag->side_st)) return r;
+  } else {
+    io.ride_merge = &mw; io.ride_X = g.Hbuf; io.ride_R = g.R; io.ride_ws = g.merge_ws; io.ride_ws_bytes = g.merge_ws_bytes;
+  }
+  if (int r = mhimx_abmil_pool_fwd(dag ? dag->side_st : stream, &f->sc_s, &io)) return r;
+  mw.rows_done = io.rode_merge;                  // (0 when nothing rode: the DAG form)
+  if (int r = mhimx_merge_fwd(stream, &mw, g.Hbuf, g.R, g.Hbuf + g.N * E, g.q_out, 1, g.merge_ws, g.merge_ws_bytes)) return r;
+  mw.rows_done = 0;
+  if (dag)
+    if (int r = dag_edge(dag->ev[1], dag->side_st, dag->main_st)) return r;
+  io.phase = 2; io.tail_wa_t = im.wa_t; io.tail_row0 = g.N;
+  if (int r = mhimx_abmil_pool_fwd(stream, &f->sc_s, &io)) return r;
+  io.phase = 0; io.ride_merge = nullptr;
+  return 0;
+}
+
+int mid_head(void* stream, const mhimx_step_cfg& c, const MidBag& g, const float* z_t, const int64_t* label, float loss_scale, float* logits,
+             float* losses, const mhimx_step_grads& gr, int accumulate) {
+  return mhimx_head_fwd_bwd(stream, g.z_s, c.aux_alpha != 0.f ? z_t : nullptr, c.student.wp, c.student.bp, label, c.E, c.C, c.temp_t, c.main_alpha,
+                            c.aux_alpha, loss_scale, logits, losses, g.g_z, gr.wp, gr.bp, accumulate, nullptr, nullptr);
+}
+
+int mid_bwd_rows(void* stream, const MidImages& im, const MidFwd& f, const MidBag& g, const mhimx_step_grads& gr, int accumulate, const MidImg* img,
+                 const MidDag* dag, mhimx_reduce_list* lst) {
+  const int64_t E = f.mw.E;
+  float* d_tok = g.dH + g.N * E;                 // the k tokens' gradient rows
+  mhimx_merge mwb = f.mw;
+  mwb.q_param = im.q_old; mwb.wo_t = im.wo_t; mwb.prepared = 0;
+  mhimx_merge_grad mg = {};
+  mg.d_ln_w = gr.ln_w; mg.d_ln_b = gr.ln_b; mg.d_wkv = gr.wkv; mg.d_wq = gr.wq; mg.d_wo = gr.wo; mg.d_bo = gr.bo;
+  mg.accumulate = accumulate; mg.splits = 8; mg.defer = lst;
+  if (int r = mhimx_merge_bwd_park(&mwb, g.Hbuf, g.R, d_tok, g.dH, &mg, g.merge_ws, g.merge_ws_bytes)) return r;
+  {
+    mhimx_scorer sc_b = f.sc_s;
+    sc_b.wa_frag = nullptr;
+    mhimx_pool_grad pg = {};
+    pg.g_z = g.g_z; pg.dT1 = g.dH; pg.d_wa = gr.wa; pg.d_wc = gr.wc; pg.wa_t = im.wa_t; pg.accumulate = accumulate; pg.splits = 8; pg.defer = lst;
+    pg.wa_t_frag = im.wa_t_frag;
+    if (img) { pg.img = img->img; pg.img_dact = img->dact; pg.img_part = img->part; pg.img_rows = g.Lk; }
+    if (int r = mhimx_abmil_pool_bwd(stream, &sc_b, &f.io_s, &pg)) return r;
+  }
+  if (dag) {
+    // side branch, first half: the parked scorer-weight-gradient product (its inputs are the pool backward's) and the reductions queued so far
+    if (int r = dag_edge(dag->ev[2], dag->main_st, dag->side_st)) return r;
+    // (the chain runs the product beside the Merge rows backward's tiles and sizes it for the CUs they leave - when the first stage rode:
+    // the same slab count here keeps the chain's summation order)
+    if (lst->parked.pending && lst->pre.pending == 2) lst->parked.reserved = (int32_t)merge2_rows_tiles(g.R) + 1;
+    if (int r = mhimx_reduce_flush(dag->side_st, lst)) return r;
+  }
+  // main: the Merge rows backward (DAG form: a launch of its own - the product it used to share a launch with is on the side branch)
+  if (int r = mhimx_merge_bwd(stream, &mwb, g.Hbuf, g.R, d_tok, g.dH, &mg, g.merge_ws, g.merge_ws_bytes)) return r;
+  if (dag) {
+    // side branch, second half: the Merge parameter-gradient tail reads what the rows backward wrote (the pooled-row partials U)
+    if (int r = dag_edge(dag->ev[3], dag->main_st, dag->side_st)) return r;
+    if (int r = mhimx_reduce_flush(dag->side_st, lst)) return r;      // (the tail's stages as launches, the last one inside the reduction launch)
+  }
+  return 0;
+}
+
+void q_chain_weights(double mm, int n, float* wq, float* w) {
+  *wq = (float)pow(mm, (double)n);
+  for (int b = 0; b < n; ++b) w[b] = (float)((1.0 - mm) * pow(mm, (double)(n - 1 - b)));
+}
 
 }  // namespace mhimx
 
@@ -267,17 +389,13 @@ extern "C" int mhimx_step_run(void* stream, const mhimx_step_cfg* cfg, const flo
                   (long long)ws_bytes, (long long)b.total);
   const mhimx_step_cfg& c = *cfg;
   const mhimx_step_params &S = c.student, &T = c.teacher;
-  const int64_t D = c.D, E = c.E, A = c.A, C = c.C, k = c.k, I = 512;
+  const int64_t D = c.D, E = c.E, C = c.C, k = c.k;
   const int64_t R = cnt->R, Lk = cnt->Lk, len_keep = cnt->len_keep;
+  const bool fuse_img = N <= 16384;            // (layout: the scorer backward writes the stay rows' share of the dPRE image itself)
+  const hipStream_t main_st = (hipStream_t)stream;
   Carve cv(ws);
-  float* w1p_t = cv.at<float>(b.w1p_t);
-  float* wa_frag_t = cv.at<float>(b.wa_frag_t);
-  float* w1p_s = cv.at<float>(b.w1p_s);
-  float* wa_frag_s = cv.at<float>(b.wa_frag_s);
-  float* wa_t = cv.at<float>(b.wa_t);
-  float* wa_t_frag = cv.at<float>(b.wa_t_frag);
-  float* wo_t = cv.at<float>(b.wo_t);
-  float* q_old = cv.at<float>(b.q_old);
+  const MidImages im = {cv.at<float>(b.w1p_t), cv.at<float>(b.wa_frag_t), cv.at<float>(b.w1p_s), cv.at<float>(b.wa_frag_s),
+                        cv.at<float>(b.wa_t),  cv.at<float>(b.wa_t_frag), cv.at<float>(b.wo_t),  cv.at<float>(b.q_old)};
   void* merge_ws = cv.at<char>(b.merge_ws);
   float* H_t = cv.at<float>(b.H_t);
   float* Hbuf = cv.at<float>(b.Hbuf);
@@ -286,43 +404,30 @@ extern "C" int mhimx_step_run(void* stream, const mhimx_step_cfg* cfg, const flo
   float* dH = cv.at<float>(b.dH);
   const uint64_t* tick = c.tick;
   // the DAG form (header comment): a second stream and its fork / join events.  The caller decides: side_stream
-  const hipStream_t main_st = (hipStream_t)stream, side_st = (hipStream_t)c.side_stream;
-  const bool dag = c.side_stream != nullptr && c.side_stream != stream;
-  hipEvent_t* ev = nullptr;
+  MidDag dag_st = {main_st, (hipStream_t)c.side_stream, nullptr};
+  const MidDag* dag = c.side_stream != nullptr && c.side_stream != stream ? &dag_st : nullptr;
   if (dag)
-    if (int r = g_dag_events.get(&ev)) return r;
+    if (int r = g_dag_events.get(&dag_st.ev)) return r;
 
   // ---- 1. the step's first launch: counters, both projection weight images, the teacher's scorer image, the row list's constant tail.
   //         Everything else the step prepares (late[]) rides in the teacher's scorer launch, off the head of the chain.
-  mhimx_merge mw_prep = {};            // the parameter-only part of the student's Merge (read while enqueueing: prep job kind 6)
-  mw_prep.E = E; mw_prep.k = k; mw_prep.heads = 8; mw_prep.dim_head = 64;
-  mw_prep.q_param = S.q; mw_prep.ln_w = S.ln_w; mw_prep.ln_b = S.ln_b; mw_prep.wkv = S.wkv; mw_prep.wq = S.wq; mw_prep.wo = S.wo; mw_prep.bo = S.bo;
-  mw_prep.mm = c.merge_mm; mw_prep.prec = MHIMX_PREC_BF16X3; mw_prep.drop_tick = tick; mw_prep.rep = 1.f;
+  const mhimx_merge mw_prep = mid_merge_params(c);            // (read while enqueueing, by late[5]: alive until the teacher's scorer launch)
   {
     mhimx_prep_job early[8];
-    int n = 0;
-    early[n++] = mhimx_prep_job{3, nullptr, reinterpret_cast<float*>(c.tick), 1, 1};
-    if (c.opt_step) early[n++] = mhimx_prep_job{3, nullptr, reinterpret_cast<float*>(c.opt_step), 1, 1};
-    early[n++] = mhimx_prep_job{1, T.w1, w1p_t, E, D};
-    early[n++] = mhimx_prep_job{4, T.wa, wa_frag_t, A, E};
-    early[n++] = mhimx_prep_job{1, S.w1, w1p_s, E, D};
+    int n = mid_prep_head(c, im, early);
     early[n++] = mhimx_prep_job{10, nullptr, reinterpret_cast<float*>(rows_all + len_keep), N, k};
     if (int r = mhimx_prep_batch(stream, early, n)) return r;
   }
   mhimx_prep_job late[6];
-  late[0] = mhimx_prep_job{4, S.wa, wa_frag_s, A, E};
-  late[1] = mhimx_prep_job{0, S.wa, wa_t, A, E};
-  late[2] = mhimx_prep_job{5, S.wa, wa_t_frag, A, E};
-  late[3] = mhimx_prep_job{0, S.wo, wo_t, E, I};
-  late[4] = mhimx_prep_job{2, S.q, q_old, 1, k * E};
+  mid_prep_student(c, im, late);
   late[5] = mhimx_prep_job{6, reinterpret_cast<const float*>(&mw_prep), static_cast<float*>(merge_ws), R, b.merge_ws_bytes};
 
   // ---- 2. both models' feature rows in one pass over the raw bag (mhim.py:186 and :335-336)
   {
     mhimx_bag_project_args a = {};
     a.X = X; a.ldx = ldx; a.N = N; a.D = D; a.E = E; a.act = c.act; a.n_heads = 2; a.drop_tick = tick;
-    a.head[0].wp = w1p_t; a.head[0].bias = T.b1; a.head[0].H = H_t; a.head[0].ldh = E; a.head[0].drop_p = c.drop_p_teacher; a.head[0].drop_seed = seeds->drop_teacher;
-    a.head[1].wp = w1p_s; a.head[1].bias = S.b1; a.head[1].H = Hbuf; a.head[1].ldh = E; a.head[1].dact = dact; a.head[1].drop_p = c.drop_p_student;
+    a.head[0].wp = im.w1p_t; a.head[0].bias = T.b1; a.head[0].H = H_t; a.head[0].ldh = E; a.head[0].drop_p = c.drop_p_teacher; a.head[0].drop_seed = seeds->drop_teacher;
+    a.head[1].wp = im.w1p_s; a.head[1].bias = S.b1; a.head[1].H = Hbuf; a.head[1].ldh = E; a.head[1].dact = dact; a.head[1].drop_p = c.drop_p_student;
     a.head[1].drop_seed = seeds->drop_student;
     hipEvent_t* tp = nullptr;
     int tp_dev = 0;
@@ -342,8 +447,7 @@ extern "C" int mhimx_step_run(void* stream, const mhimx_step_cfg* cfg, const flo
   }
 
   // ---- 3, 4. the teacher: scorer + softmax pool (+ class projections and the pseudo score, scoring.py:37-58)
-  mhimx_scorer sc_t = {};
-  sc_t.E = E; sc_t.A = A; sc_t.act = c.da_act; sc_t.prec = MHIMX_PREC_BF16X3; sc_t.wa = T.wa; sc_t.wc = T.wc; sc_t.wa_frag = wa_frag_t;
+  const mhimx_scorer sc_t = mid_scorer(c, T, im.wa_frag_t);
   const float* score = nullptr;
   {
     mhimx_pool_io io = {};
@@ -359,130 +463,51 @@ extern "C" int mhimx_step_run(void* stream, const mhimx_step_cfg* cfg, const flo
       score = cv.at<float>(b.attn);
     }
   }
-  const float* z_t = cv.at<float>(b.z_t);
 
   // ---- 5. HAM mask + Merge split: rows_all = [rows to merge (R) | rows that stay (Lk) | N .. N + k - 1]
-  if (N <= 16384) {
-    if (b.fuse_img) {
-      if (int r = mhimx_select_rows_img(stream, score, N, cnt->k_top, cnt->n_sel, 1, seeds->select, tick, R, rows_all, cv.at<int64_t>(b.rows_img), b.P0,
-                                        cv.at<char>(b.sel_ws), b.sel_ws_bytes, 1))
-        return r;
-    } else if (int r = mhimx_select_rows(stream, score, N, cnt->k_top, cnt->n_sel, 1, seeds->select, tick, R, rows_all, nullptr, cv.at<char>(b.sel_ws),
-                                         b.sel_ws_bytes, 1))
+  if (fuse_img) {
+    if (int r = mhimx_select_rows_img(stream, score, N, cnt->k_top, cnt->n_sel, 1, seeds->select, tick, R, rows_all, cv.at<int64_t>(b.rows_img), b.P0,
+                                      cv.at<char>(b.sel_ws), b.sel_ws_bytes, 1))
       return r;
   } else {
-    // select_large: the two-stage form of masking.py:61-86 + merge.py:163-170 as MHIM.student_rows issues it for such bags (mhim.py of this
-    // package: the same four launches + the [merge | stay] swap, the same seeds - the bits of the Python path):
-    //   perm  = pi_1 of 0 .. k_top-1 (masking.py:67's torch.randperm, keyed by (seed + 0x51ED270B, tick))
-    //   ids   = select_mask(score, k_top, n_sel, perm)          [kept ascending | masked]   (multi-workgroup select)
-    //   rows  = ids[pi_2(j)], j < len_keep                       (merge.py:165's shuffle of the kept rows, keyed by (seed ^ 0x3C6E.., tick))
-    //   rows_all = [rows[Lk:] (to merge) | rows[:Lk] (stay)]
-    int64_t* perm = cv.at<int64_t>(b.sel_perm);
-    int64_t* ids = cv.at<int64_t>(b.sel_ids);
-    int64_t* rows = cv.at<int64_t>(b.sel_rows);
-    if (int r = mhimx_random_perm(stream, cnt->k_top, seeds->select + 0x51ED270Bull, tick, nullptr, perm)) return r;
-    if (int r = mhimx_select_mask(stream, score, N, cnt->k_top, cnt->n_sel, 1, cnt->n_sel < cnt->k_top ? perm : nullptr, nullptr, 0, ids, cv.at<int64_t>(b.sel_lk),
-                                  nullptr, cv.at<char>(b.sel_ws), b.sel_ws_bytes))
-      return r;
-    if (int r = mhimx_random_perm(stream, len_keep, seeds->select ^ 0x3C6EF372FE94F82Bull, tick, ids, rows)) return r;
-    MHIMX_HIP(hipMemcpyAsync(rows_all, rows + Lk, (size_t)R * 8, hipMemcpyDeviceToDevice, (hipStream_t)stream));
-    MHIMX_HIP(hipMemcpyAsync(rows_all + R, rows, (size_t)Lk * 8, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    // above 16 384 rows: the two-stage form of masking.py:61-86 + merge.py:163-170 as MHIM.student_rows issues it for such bags (mhim.py of
+    // this package: the same four launches + the [merge | stay] swap, the same seeds - the bits of the Python path)
+    const SelLargeWs lw = {cv.at<int64_t>(b.sel_perm), cv.at<int64_t>(b.sel_ids), cv.at<int64_t>(b.sel_rows), cv.at<int64_t>(b.sel_lk), cv.at<char>(b.sel_ws),
+                           b.sel_ws_bytes};
+    if (int r = select_large_rows(main_st, score, N, cnt->k_top, cnt->n_sel, seeds->select, tick, R, rows_all, 1, lw)) return r;
   }
 
-  // ---- 6..9. Merge (merge.py:127-203): the k tokens land behind the bag's rows, the queries' EMA in place
-  mhimx_merge mw = mw_prep;
-  mw.drop_p = c.merge_drop_p; mw.drop_seed = seeds->mca; mw.x_rows = rows_all; mw.prepared = 1;
-  // ---- 6..11. the student's forward.  Its scorer over the rows that stay and Merge's rows pass are independent: ONE launch runs both (the Merge
-  //      row tiles ride at its front), the Merge tail then makes the tokens, and the pool's finalize launch scores those k rows itself
-  //      (mhimx_pool_io.phase; more than 6 tokens: Merge, then the scorer over [stay | tokens], as rounds 2-4 had it)
-  mhimx_scorer sc_s = sc_t;
-  sc_s.wa = S.wa; sc_s.wc = S.wc; sc_s.wa_frag = wa_frag_s;
-  mhimx_pool_io io_s = {};
-  io_s.T1 = Hbuf; io_s.M1 = Lk + k; io_s.s = cv.at<float>(b.s_s); io_s.stats = cv.at<float>(b.stats_s); io_s.z = cv.at<float>(b.z_s);
-  io_s.ws = cv.at<char>(b.pool_ws_s); io_s.ws_bytes = b.pool_ws_s_bytes; io_s.rows1 = rows_all + R;
-  io_s.tail_row0 = -1;
-  if (dag && k <= 6) {
-    // two branches: the scorer over the rows that stay (side) || Merge's whole chain (main); they meet at the finalize that scores the tokens
-    if (int r = dag_edge(ev[0], main_st, side_st)) return r;
-    io_s.phase = 1; io_s.tail_tokens = (int32_t)k;
-    if (int r = mhimx_abmil_pool_fwd(side_st, &sc_s, &io_s)) return r;
-    if (int r = mhimx_merge_fwd(stream, &mw, Hbuf, R, Hbuf + N * E, c.q_out ? c.q_out : S.q, 1, merge_ws, b.merge_ws_bytes)) return r;
-    if (int r = dag_edge(ev[1], side_st, main_st)) return r;
-    io_s.phase = 2; io_s.tail_wa_t = wa_t; io_s.tail_row0 = N;
-    if (int r = mhimx_abmil_pool_fwd(stream, &sc_s, &io_s)) return r;
-    io_s.phase = 0;
-  } else if (k <= 6) {
-    io_s.phase = 1; io_s.tail_tokens = (int32_t)k;
-    io_s.ride_merge = &mw; io_s.ride_X = Hbuf; io_s.ride_R = R; io_s.ride_ws = merge_ws; io_s.ride_ws_bytes = b.merge_ws_bytes;
-    if (int r = mhimx_abmil_pool_fwd(stream, &sc_s, &io_s)) return r;
-    mw.rows_done = io_s.rode_merge;
-    if (int r = mhimx_merge_fwd(stream, &mw, Hbuf, R, Hbuf + N * E, c.q_out ? c.q_out : S.q, 1, merge_ws, b.merge_ws_bytes)) return r;
-    mw.rows_done = 0;
-    io_s.phase = 2; io_s.tail_wa_t = wa_t; io_s.tail_row0 = N;
-    if (int r = mhimx_abmil_pool_fwd(stream, &sc_s, &io_s)) return r;
-    io_s.phase = 0; io_s.ride_merge = nullptr;
-  } else {
-    if (int r = mhimx_merge_fwd(stream, &mw, Hbuf, R, Hbuf + N * E, c.q_out ? c.q_out : S.q, 1, merge_ws, b.merge_ws_bytes)) return r;
-    if (int r = mhimx_abmil_pool_fwd(stream, &sc_s, &io_s)) return r;
-  }
+  // ---- 6..10. the student's forward (the queries' EMA in place, or where a data-parallel rank wants it), 11. the head
+  const MidBag bag = {Hbuf, dH, rows_all, N, R, Lk, seeds->mca, c.q_out ? c.q_out : S.q, cv.at<float>(b.s_s), cv.at<float>(b.stats_s), cv.at<float>(b.z_s),
+                      cv.at<float>(b.g_z), cv.at<char>(b.pool_ws_s), b.pool_ws_s_bytes, merge_ws, b.merge_ws_bytes};
+  MidFwd fwd;
+  if (int r = mid_student_fwd(stream, c, im, mw_prep, bag, dag, &fwd)) return r;
+  if (int r = mid_head(stream, c, bag, cv.at<float>(b.z_t), label_dev, 1.f, cv.at<float>(b.logits), cv.at<float>(b.losses), c.grad, 0)) return r;
 
-  // ---- 12. head: predictor, CE, distillation against the teacher's bag feature, and their gradients
-  float* g_z = cv.at<float>(b.g_z);
-  if (int r = mhimx_head_fwd_bwd(stream, io_s.z, c.aux_alpha != 0.f ? z_t : nullptr, S.wp, S.bp, label_dev, E, C, c.temp_t, c.main_alpha, c.aux_alpha, 1.f,
-                                 cv.at<float>(b.logits), cv.at<float>(b.losses), g_z, c.grad.wp, c.grad.bp, 0, nullptr, nullptr))
-    return r;
-
-  // ---- 13..16. backward
+  // ---- 12..15. backward
   mhimx_reduce_list lst;
   memset(&lst, 0, sizeof(lst));
-  mhimx_merge mwb = mw;
-  mwb.q_param = q_old; mwb.wo_t = wo_t; mwb.prepared = 0;
-  mhimx_merge_grad mg = {};
-  mg.d_ln_w = c.grad.ln_w; mg.d_ln_b = c.grad.ln_b; mg.d_wkv = c.grad.wkv; mg.d_wq = c.grad.wq; mg.d_wo = c.grad.wo; mg.d_bo = c.grad.bo;
-  mg.accumulate = 0; mg.splits = 8; mg.defer = &lst;
-  if (int r = mhimx_merge_bwd_park(&mwb, Hbuf, R, dH + N * E, dH, &mg, merge_ws, b.merge_ws_bytes)) return r;
-  {
-    mhimx_scorer sc_b = sc_s;
-    sc_b.wa_frag = nullptr;
-    mhimx_pool_grad pg = {};
-    pg.g_z = g_z; pg.dT1 = dH; pg.d_wa = c.grad.wa; pg.d_wc = c.grad.wc; pg.wa_t = wa_t; pg.accumulate = 0; pg.splits = 8; pg.defer = &lst; pg.wa_t_frag = wa_t_frag;
-    if (b.fuse_img) { pg.img = cv.at<char>(b.img); pg.img_dact = dact; pg.img_part = cv.at<float>(b.ws_b); pg.img_rows = Lk; }
-    if (int r = mhimx_abmil_pool_bwd(stream, &sc_b, &io_s, &pg)) return r;
-  }
+  const MidImg pimg = {cv.at<char>(b.img), dact, cv.at<float>(b.ws_b)};
+  if (int r = mid_bwd_rows(stream, im, fwd, bag, c.grad, 0, fuse_img ? &pimg : nullptr, dag, &lst)) return r;
   mhimx_reduce_list lst_main;                    // (DAG form: what the main branch queues - the bias partials, the weight gradient's slab sum)
   memset(&lst_main, 0, sizeof(lst_main));
   mhimx_reduce_list* lm = dag ? &lst_main : &lst;
-  if (dag) {
-    // side branch, first half: the parked scorer-weight-gradient product (its inputs are the pool backward's) and the reductions queued so far
-    if (int r = dag_edge(ev[2], main_st, side_st)) return r;
-    // (the chain runs the product beside the Merge rows backward's tiles and sizes it for the CUs they leave - when the first stage rode:
-    // the same slab count here keeps the chain's summation order)
-    if (lst.parked.pending && lst.pre.pending == 2) lst.parked.reserved = (int32_t)merge2_rows_tiles(R) + 1;
-    if (int r = mhimx_reduce_flush(side_st, &lst)) return r;
-  }
-  // main: the Merge rows backward (DAG form: a launch of its own - the product it used to share a launch with is on the side branch)
-  if (int r = mhimx_merge_bwd(stream, &mwb, Hbuf, R, dH + N * E, dH, &mg, merge_ws, b.merge_ws_bytes)) return r;
-  if (dag) {
-    // side branch, second half: the Merge parameter-gradient tail reads what the rows backward wrote (the pooled-row partials U)
-    if (int r = dag_edge(ev[3], main_st, side_st)) return r;
-    if (int r = mhimx_reduce_flush(side_st, &lst)) return r;      // (the tail's stages as launches, the last one inside the reduction launch)
-  }
-  if (b.fuse_img) {
+  if (fuse_img) {
     if (int r = dpre_merge_rows(stream, dH, dact, rows_all, R, E, cv.at<char>(b.img), b.P0, c.grad.b1, cv.at<float>(b.ws_b), b.ws_b_bytes, lm)) return r;
   } else if (int r = mhimx_rows_dpre_image(stream, dH, dact, rows_all, len_keep, E, cv.at<char>(b.img), c.grad.b1, 0, cv.at<char>(b.ws_b), b.ws_b_bytes, lm))
     return r;
   {
     mhimx_bag_wgrad_args g = {};
-    g.img = cv.at<char>(b.img); g.X = X; g.ldx = ldx; g.n_bag_rows = N; g.rows = b.fuse_img ? cv.at<int64_t>(b.rows_img) : rows_all; g.L = b.L_img; g.E = E; g.D = D;
+    g.img = cv.at<char>(b.img); g.X = X; g.ldx = ldx; g.n_bag_rows = N; g.rows = fuse_img ? cv.at<int64_t>(b.rows_img) : rows_all; g.L = b.L_img; g.E = E; g.D = D;
     g.C = c.grad.w1; g.ldc = D;
     g.accumulate = 0; g.ws = cv.at<float>(b.wg_ws); g.ws_floats = b.wg_ws_floats; g.defer = lm; g.ride_tail = update ? 1 : 0;
     if (int r = mhimx_bag_wgrad(stream, &g)) return r;
   }
   if (dag)
-    if (int r = dag_edge(ev[4], side_st, main_st)) return r;
+    if (int r = dag_edge(dag->ev[4], dag->side_st, dag->main_st)) return r;
   if (!update) return mhimx_reduce_flush(stream, lm);
 
-  // ---- 17. Adam + EMA teacher; the weight gradient's split-K slab sum is folded into the update
+  // ---- 16. Adam + EMA teacher; the weight gradient's split-K slab sum is folded into the update
   mhimx_optim_args o = optim_args_of(c, host_step, true);
   o.fold = lm;
   return mhimx_optim_step(stream, &o);
@@ -490,7 +515,7 @@ extern "C" int mhimx_step_run(void* stream, const mhimx_step_cfg* cfg, const flo
 
 // ------------------------------------------------------------------------------------------------------------------------------------
 // Round 6 - an accumulation window with every launch over ALL its bags (base_engine.py:29,47-49,100-119).
-//   prep (once)  ->  both projections of the n bags in ONE launch  ->  the step's middle (teacher scorer ... dPRE image: launches 3-15 of
+//   prep (once)  ->  both projections of the n bags in ONE launch  ->  the step's middle (teacher scorer ... dPRE image: launches 3-14 of
 //   the list at the top of this file) issued ONCE with gridDim.z = n (common.hpp: BagBatch - every kernel moves the pointers it was given to
 //   its own bag's copy of the workspace)  ->  ONE weight-gradient launch over the n images  ->  the queries' EMA chain  ->  Adam + EMA.
 // ~22 launches per window instead of ~127: the latency-bound links of the chain (select, Merge tail, finalizes, head: one to a few dozen
@@ -577,18 +602,12 @@ extern "C" int mhimx_window_run(void* stream, const mhimx_step_cfg* cfg, int32_t
   Carve cv(ws);
   const int64_t BS = b.bag_stride;                                     // bytes from a bag's copy of a buffer to the next bag's
   auto bag = [&](int64_t off, int i) { return cv.at<char>(off) + (int64_t)i * BS; };
-  float* w1p_t = cv.at<float>(b.w1p_t);
-  float* wa_frag_t = cv.at<float>(b.wa_frag_t);
-  float* w1p_s = cv.at<float>(b.w1p_s);
-  float* wa_frag_s = cv.at<float>(b.wa_frag_s);
-  float* wa_t = cv.at<float>(b.wa_t);
-  float* wa_t_frag = cv.at<float>(b.wa_t_frag);
-  float* wo_t = cv.at<float>(b.wo_t);
-  float* q_old = cv.at<float>(b.q_old);
+  const MidImages im = {cv.at<float>(b.w1p_t), cv.at<float>(b.wa_frag_t), cv.at<float>(b.w1p_s), cv.at<float>(b.wa_frag_s),
+                        cv.at<float>(b.wa_t),  cv.at<float>(b.wa_t_frag), cv.at<float>(b.wo_t),  cv.at<float>(b.q_old)};
   // bag 0's copies: what the middle is enqueued with
-  void* merge_ws = cv.at<char>(b.merge_ws);
   float* H_t = cv.at<float>(b.H_t);
   float* Hbuf = cv.at<float>(b.Hbuf);
+  void* dact = cv.at<char>(b.dact);
   int64_t* rows_all = cv.at<int64_t>(b.rows_all);
   float* dH = cv.at<float>(b.dH);
   float* slab0 = cv.at<float>(b.gslab);
@@ -601,23 +620,11 @@ extern "C" int mhimx_window_run(void* stream, const mhimx_step_cfg* cfg, int32_t
   const int64_t g_lo = E * D;
 
   // ---- 1. preparation, once for the window (nothing rides: the middle's launches are bag-batched)
-  mhimx_merge mw_prep = {};
-  mw_prep.E = E; mw_prep.k = k; mw_prep.heads = 8; mw_prep.dim_head = 64;
-  mw_prep.q_param = S.q; mw_prep.ln_w = S.ln_w; mw_prep.ln_b = S.ln_b; mw_prep.wkv = S.wkv; mw_prep.wq = S.wq; mw_prep.wo = S.wo; mw_prep.bo = S.bo;
-  mw_prep.mm = c.merge_mm; mw_prep.prec = MHIMX_PREC_BF16X3; mw_prep.drop_tick = tick; mw_prep.rep = 1.f;
+  const mhimx_merge mw_prep = mid_merge_params(c);            // (read while enqueueing, by the kind-6 jobs of this launch)
   {
     mhimx_prep_job jobs[MHIMX_PREP_MAX];
-    int n = 0;
-    jobs[n++] = mhimx_prep_job{3, nullptr, reinterpret_cast<float*>(c.tick), 1, 1};
-    if (c.opt_step) jobs[n++] = mhimx_prep_job{3, nullptr, reinterpret_cast<float*>(c.opt_step), 1, 1};
-    jobs[n++] = mhimx_prep_job{1, T.w1, w1p_t, E, D};
-    jobs[n++] = mhimx_prep_job{4, T.wa, wa_frag_t, A, E};
-    jobs[n++] = mhimx_prep_job{1, S.w1, w1p_s, E, D};
-    jobs[n++] = mhimx_prep_job{4, S.wa, wa_frag_s, A, E};
-    jobs[n++] = mhimx_prep_job{0, S.wa, wa_t, A, E};
-    jobs[n++] = mhimx_prep_job{5, S.wa, wa_t_frag, A, E};
-    jobs[n++] = mhimx_prep_job{0, S.wo, wo_t, E, I};
-    jobs[n++] = mhimx_prep_job{2, S.q, q_old, 1, k * E};
+    int n = mid_prep_head(c, im, jobs);
+    n += mid_prep_student(c, im, jobs + n);
     for (int i = 0; i < n_bags; ++i) {
       jobs[n++] = mhimx_prep_job{10, nullptr, reinterpret_cast<float*>(reinterpret_cast<int64_t*>(bag(b.rows_all, i)) + len_keep), N, k};
       jobs[n++] = mhimx_prep_job{6, reinterpret_cast<const float*>(&mw_prep), reinterpret_cast<float*>(bag(b.merge_ws, i)), R, b.merge_ws_bytes};
@@ -635,16 +642,16 @@ extern "C" int mhimx_window_run(void* stream, const mhimx_step_cfg* cfg, int32_t
     for (int i = 0; i < n_bags; ++i) {
       mhimx_bag_project_args a = {};
       a.X = X[i]; a.ldx = ldx; a.N = N; a.D = D; a.E = E; a.act = c.act; a.n_heads = 2; a.drop_tick = tick;
-      a.head[0].wp = w1p_t; a.head[0].bias = T.b1; a.head[0].H = reinterpret_cast<float*>(bag(b.H_t, i)); a.head[0].ldh = E; a.head[0].drop_p = c.drop_p_teacher;
+      a.head[0].wp = im.w1p_t; a.head[0].bias = T.b1; a.head[0].H = reinterpret_cast<float*>(bag(b.H_t, i)); a.head[0].ldh = E; a.head[0].drop_p = c.drop_p_teacher;
       a.head[0].drop_seed = seeds[i].drop_teacher;
-      a.head[1].wp = w1p_s; a.head[1].bias = S.b1; a.head[1].H = reinterpret_cast<float*>(bag(b.Hbuf, i)); a.head[1].ldh = E; a.head[1].dact = bag(b.dact, i);
+      a.head[1].wp = im.w1p_s; a.head[1].bias = S.b1; a.head[1].H = reinterpret_cast<float*>(bag(b.Hbuf, i)); a.head[1].ldh = E; a.head[1].dact = bag(b.dact, i);
       a.head[1].drop_p = c.drop_p_student; a.head[1].drop_seed = seeds[i].drop_student;
       pa[n_bags - 1 - i] = a;
     }
     if (int r = mhimx_bag_project_multi(stream, pa, n_bags)) return r;
   }
 
-  // ---- 3..15. the middle, enqueued once with bag 0's pointers, gridDim.z = n_bags
+  // ---- 3..14. the middle, enqueued once with bag 0's pointers, gridDim.z = n_bags
   BagBatch bb = {};
   bb.n = n_bags;
   bb.lo[0] = reinterpret_cast<uint64_t>(cv.at<char>(b.bag0)); bb.span[0] = (uint64_t)BS; bb.stride[0] = BS;
@@ -661,15 +668,14 @@ extern "C" int mhimx_window_run(void* stream, const mhimx_step_cfg* cfg, int32_t
   {
     BatchScope scope(&bb);
     // teacher: scorer + softmax pool (+ class projections and the pseudo score, scoring.py:37-58)
-    mhimx_scorer sc_t = {};
-    sc_t.E = E; sc_t.A = A; sc_t.act = c.da_act; sc_t.prec = MHIMX_PREC_BF16X3; sc_t.wa = T.wa; sc_t.wc = T.wc; sc_t.wa_frag = wa_frag_t;
+    const mhimx_scorer sc_t = mid_scorer(c, T, im.wa_frag_t);
     const float* score = nullptr;
     {
       mhimx_pool_io io = {};
       io.T1 = H_t; io.M1 = N; io.s = cv.at<float>(b.s_t); io.stats = cv.at<float>(b.stats_t); io.z = cv.at<float>(b.z_t);
       io.ws = cv.at<char>(b.pool_ws_t); io.ws_bytes = b.pool_ws_t_bytes;
       if (c.attn2score) { io.wp = T.wp; io.C = C; io.cproj = cv.at<float>(b.cproj_t); io.bp = T.bp; io.pscore = cv.at<float>(b.pscore); }
-    io.no_backward = 1;
+      io.no_backward = 1;
       if (int r = mhimx_abmil_pool_fwd(stream, &sc_t, &io)) return r;
       if (c.attn2score) score = io.pscore;
       else {
@@ -677,76 +683,39 @@ extern "C" int mhimx_window_run(void* stream, const mhimx_step_cfg* cfg, int32_t
         score = cv.at<float>(b.attn);
       }
     }
-    const float* z_t = cv.at<float>(b.z_t);
-    // HAM mask + Merge split
-    if (b.fuse_img) {
-      if (int r = mhimx_select_rows_img(stream, score, N, cnt->k_top, cnt->n_sel, 1, seeds[0].select, tick, R, rows_all, cv.at<int64_t>(b.rows_img), b.P0,
-                                        cv.at<char>(b.sel_ws), b.sel_ws_bytes, 1))
-        return r;
-    } else if (int r = mhimx_select_rows(stream, score, N, cnt->k_top, cnt->n_sel, 1, seeds[0].select, tick, R, rows_all, nullptr, cv.at<char>(b.sel_ws),
-                                         b.sel_ws_bytes, 1))
+    // HAM mask + Merge split (check_window: up to 16 384 rows - the select that also writes the dPRE image's row order)
+    if (int r = mhimx_select_rows_img(stream, score, N, cnt->k_top, cnt->n_sel, 1, seeds[0].select, tick, R, rows_all, cv.at<int64_t>(b.rows_img), b.P0,
+                                      cv.at<char>(b.sel_ws), b.sel_ws_bytes, 1))
       return r;
-    // the student's forward: scorer over the rows that stay (Merge's row tiles ride at its front), Merge tail, the finalize that scores the tokens
-    mhimx_merge mw = mw_prep;
-    mw.drop_p = c.merge_drop_p; mw.drop_seed = seeds[0].mca; mw.x_rows = rows_all; mw.prepared = 1;
-    mhimx_scorer sc_s = sc_t;
-    sc_s.wa = S.wa; sc_s.wc = S.wc; sc_s.wa_frag = wa_frag_s;
-    mhimx_pool_io io_s = {};
-    io_s.T1 = Hbuf; io_s.M1 = Lk + k; io_s.s = cv.at<float>(b.s_s); io_s.stats = cv.at<float>(b.stats_s); io_s.z = cv.at<float>(b.z_s);
-    io_s.ws = cv.at<char>(b.pool_ws_s); io_s.ws_bytes = b.pool_ws_s_bytes; io_s.rows1 = rows_all + R;
-    io_s.tail_row0 = -1;
-    io_s.phase = 1; io_s.tail_tokens = (int32_t)k;
-    io_s.ride_merge = &mw; io_s.ride_X = Hbuf; io_s.ride_R = R; io_s.ride_ws = merge_ws; io_s.ride_ws_bytes = b.merge_ws_bytes;
-    if (int r = mhimx_abmil_pool_fwd(stream, &sc_s, &io_s)) return r;
-    mw.rows_done = io_s.rode_merge;
-    if (int r = mhimx_merge_fwd(stream, &mw, Hbuf, R, Hbuf + N * E, cv.at<float>(b.q_scr), 1, merge_ws, b.merge_ws_bytes)) return r;
-    mw.rows_done = 0;
-    io_s.phase = 2; io_s.tail_wa_t = wa_t; io_s.tail_row0 = N;
-    if (int r = mhimx_abmil_pool_fwd(stream, &sc_s, &io_s)) return r;
-    io_s.phase = 0; io_s.ride_merge = nullptr;
+    // the student's forward (the queries' EMA goes to the bag's scratch: the window's first queries stay); head: every bag's loss / n_bags
+    // (base_engine.py:102)
+    const MidBag g = {Hbuf, dH, rows_all, N, R, Lk, seeds[0].mca, cv.at<float>(b.q_scr), cv.at<float>(b.s_s), cv.at<float>(b.stats_s), cv.at<float>(b.z_s),
+                      cv.at<float>(b.g_z), cv.at<char>(b.pool_ws_s), b.pool_ws_s_bytes, cv.at<char>(b.merge_ws), b.merge_ws_bytes};
+    MidFwd fwd;
+    if (int r = mid_student_fwd(stream, c, im, mw_prep, g, nullptr, &fwd)) return r;
+    // every parameter gradient but the projection weight's lands in the bag's slab
+    mhimx_step_grads gr = c.grad;
+    gr.b1 = gs(gr.b1); gr.wa = gs(gr.wa); gr.wc = gs(gr.wc); gr.wp = gs(gr.wp); gr.bp = gs(gr.bp); gr.ln_w = gs(gr.ln_w); gr.ln_b = gs(gr.ln_b);
+    gr.wkv = gs(gr.wkv); gr.wq = gs(gr.wq); gr.wo = gs(gr.wo); gr.bo = gs(gr.bo);
+    if (int r = mid_head(stream, c, g, cv.at<float>(b.z_t), labels_dev[0], 1.f / (float)n_bags, cv.at<float>(b.logits), cv.at<float>(b.losses), gr, 0)) return r;
 
-    // head: every bag's loss / n_bags (base_engine.py:102)
-    float* g_z = cv.at<float>(b.g_z);
-    if (int r = mhimx_head_fwd_bwd(stream, io_s.z, c.aux_alpha != 0.f ? z_t : nullptr, S.wp, S.bp, labels_dev[0], E, C, c.temp_t, c.main_alpha, c.aux_alpha,
-                                   1.f / (float)n_bags, cv.at<float>(b.logits), cv.at<float>(b.losses), g_z, gs(c.grad.wp), gs(c.grad.bp), 0, nullptr, nullptr))
-      return r;
-
-    // backward up to the dPRE image; every parameter gradient but the projection weight's lands in the bag's slab
+    // backward up to the dPRE image
     mhimx_reduce_list lst;
     memset(&lst, 0, sizeof(lst));
-    mhimx_merge mwb = mw;
-    mwb.q_param = q_old; mwb.wo_t = wo_t; mwb.prepared = 0;
-    mhimx_merge_grad mg = {};
-    mg.d_ln_w = gs(c.grad.ln_w); mg.d_ln_b = gs(c.grad.ln_b); mg.d_wkv = gs(c.grad.wkv); mg.d_wq = gs(c.grad.wq); mg.d_wo = gs(c.grad.wo); mg.d_bo = gs(c.grad.bo);
-    mg.accumulate = 0; mg.splits = 8; mg.defer = &lst;
-    if (int r = mhimx_merge_bwd_park(&mwb, Hbuf, R, dH + N * E, dH, &mg, merge_ws, b.merge_ws_bytes)) return r;
-    {
-      mhimx_scorer sc_b = sc_s;
-      sc_b.wa_frag = nullptr;
-      mhimx_pool_grad pg = {};
-      pg.g_z = g_z; pg.dT1 = dH; pg.d_wa = gs(c.grad.wa); pg.d_wc = gs(c.grad.wc); pg.wa_t = wa_t; pg.accumulate = 0; pg.splits = 8; pg.defer = &lst;
-      pg.wa_t_frag = wa_t_frag;
-      if (b.fuse_img) { pg.img = cv.at<char>(b.img); pg.img_dact = cv.at<char>(b.dact); pg.img_part = cv.at<float>(b.ws_b); pg.img_rows = Lk; }
-      if (int r = mhimx_abmil_pool_bwd(stream, &sc_b, &io_s, &pg)) return r;
-    }
-    if (int r = mhimx_merge_bwd(stream, &mwb, Hbuf, R, dH + N * E, dH, &mg, merge_ws, b.merge_ws_bytes)) return r;
-    if (b.fuse_img) {
-      if (int r = dpre_merge_rows(stream, dH, cv.at<char>(b.dact), rows_all, R, E, cv.at<char>(b.img), b.P0, gs(c.grad.b1), cv.at<float>(b.ws_b), b.ws_b_bytes, &lst))
-        return r;
-    } else if (int r = mhimx_rows_dpre_image(stream, dH, cv.at<char>(b.dact), rows_all, len_keep, E, cv.at<char>(b.img), gs(c.grad.b1), 0, cv.at<char>(b.ws_b),
-                                             b.ws_b_bytes, &lst))
-      return r;
+    const MidImg pimg = {cv.at<char>(b.img), dact, cv.at<float>(b.ws_b)};
+    if (int r = mid_bwd_rows(stream, im, fwd, g, gr, 0, &pimg, nullptr, &lst)) return r;
+    if (int r = dpre_merge_rows(stream, dH, dact, rows_all, R, E, cv.at<char>(b.img), b.P0, gr.b1, cv.at<float>(b.ws_b), b.ws_b_bytes, &lst)) return r;
     if (int r = mhimx_reduce_flush(stream, &lst)) return r;          // (the Merge tail's remaining stages + every queued reduction, bag-batched)
   }
 
-  // ---- 16. dW1 = sum_bags dPRE_b^T X_b: ONE launch, straight into the flat gradient
+  // ---- 15. dW1 = sum_bags dPRE_b^T X_b: ONE launch, straight into the flat gradient
   mhimx_reduce_list lst_w;
   memset(&lst_w, 0, sizeof(lst_w));
   {
     mhimx_bag_wgrad_args ga[MHIMX_WINDOW_MAX];
     for (int i = 0; i < n_bags; ++i) {
       mhimx_bag_wgrad_args g = {};
-      g.img = bag(b.img, i); g.X = X[i]; g.ldx = ldx; g.n_bag_rows = N; g.rows = reinterpret_cast<const int64_t*>(bag(b.fuse_img ? b.rows_img : b.rows_all, i));
+      g.img = bag(b.img, i); g.X = X[i]; g.ldx = ldx; g.n_bag_rows = N; g.rows = reinterpret_cast<const int64_t*>(bag(b.rows_img, i));
       g.L = b.L_img; g.E = E; g.D = D;
       g.C = c.grad.w1; g.ldc = D; g.accumulate = 0; g.ws = cv.at<float>(b.wg_ws); g.ws_floats = b.wg_ws_floats; g.defer = &lst_w;
       ga[i] = g;
@@ -755,10 +724,8 @@ extern "C" int mhimx_window_run(void* stream, const mhimx_step_cfg* cfg, int32_t
   }
   // ---- the queries' EMA chain over the window's tokens: q <- mm^n q + (1 - mm) sum_b mm^(n-1-b) z_b
   {
-    QChainW cw;
-    const double mm = (double)c.merge_mm;
-    cw.wq = (float)pow(mm, (double)n_bags);
-    for (int i = 0; i < MHIMX_WINDOW_MAX; ++i) cw.w[i] = i < n_bags ? (float)((1.0 - mm) * pow(mm, (double)(n_bags - 1 - i))) : 0.f;
+    QChainW cw = {};
+    q_chain_weights((double)c.merge_mm, n_bags, &cw.wq, cw.w);
     // the slab elements from E D on that none of the eleven gradient views covers
     SlabGaps gaps = {};
     {
@@ -786,7 +753,7 @@ extern "C" int mhimx_window_run(void* stream, const mhimx_step_cfg* cfg, int32_t
     MHIMX_LAUNCH_CHECK();
     return 0;
   }
-  // ---- 17. Adam + EMA teacher on g + the bags' slabs; the weight gradient's split-K slab sum is folded into the update
+  // ---- 16. Adam + EMA teacher on g + the bags' slabs; the weight gradient's split-K slab sum is folded into the update
   mhimx_optim_args o = optim_args_of(c, host_step, true);
   o.fold = &lst_w;
   o.g_extra = slab0; o.n_extra = n_bags; o.extra_pitch = BS / 4; o.extra_lo = g_lo; o.extra_only = 1;
@@ -822,8 +789,9 @@ extern "C" int mhimx_step_run_many(void* stream, const mhimx_step_cfg* cfg, int3
 // bag behind ONE C call.
 // replaces: engines/common_mil.py:32-37 (forward_func, model 'pure': model.pure(bag)) + modules/mhim.py `pure` + engines/base_engine.py:76-120
 //           (criterion, loss.backward(), optimizer.step()) for one bag - and, on this side of the boundary, the Python orchestration of
-//           FusedTrainer(model="mhim_pure") (_nat_prep / _nat_bag / _apply): the SAME entry points in the SAME order on the SAME arguments,
-//           so a step through this executor has the bits of a step through the Python path given the same seed and tick.
+//           FusedTrainer(model="mhim_pure") (_nat_prep / _nat_bag / _apply): the SAME entry points in the SAME order on the SAME arguments
+//           (no fused dPRE image here: rows_dpre_image over all N rows in bag order, as the Python path issues it), so a step through this
+//           executor has the bits of a step through the Python path given the same seed and tick (tests/test_pure_step_gpu.py).
 //
 //   launch  1  mhimx_prep_batch         counters, the W1 paired-plane image, the scorer's fragment / transposed / transposed-fragment images
 //                                       (no teacher scorer launch exists for them to ride in)
@@ -928,9 +896,7 @@ extern "C" int mhimx_pure_step_run(void* stream, const mhimx_step_cfg* cfg, cons
   // ---- 1. counters and every weight image of the step
   {
     mhimx_prep_job jobs[6];
-    int n = 0;
-    jobs[n++] = mhimx_prep_job{3, nullptr, reinterpret_cast<float*>(c.tick), 1, 1};
-    if (c.opt_step) jobs[n++] = mhimx_prep_job{3, nullptr, reinterpret_cast<float*>(c.opt_step), 1, 1};
+    int n = prep_counters(c, jobs);
     jobs[n++] = mhimx_prep_job{1, S.w1, w1p, E, D};
     jobs[n++] = mhimx_prep_job{4, S.wa, wa_frag, A, E};
     jobs[n++] = mhimx_prep_job{0, S.wa, wa_t, A, E};
