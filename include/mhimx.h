@@ -1147,6 +1147,70 @@ int mhimx_infer_dsmil_run(void* stream, const mhimx_infer_dsmil_cfg* cfg, int32_
                           const int64_t* labels_dev, const mhimx_infer_dsmil_out* out, void* ws, int64_t ws_bytes, int32_t x_dtype);
 
 /* ------------------------------------------------------------------------------------------
+ * Ragged accumulation window of the teacher-free DSMIL model ('mhim_pure' with baseline 'dsmil': the recipe's first training for the
+ * second MHIM baseline): ONE optimiser update over n_bags bags of DIFFERENT row counts in one call; n_bags = 1 is the single-bag step.
+ * replaces: engines/base_engine.py:29-51,76-120 (the accumulation window: every bag's loss divided by the window's length, the gradients
+ *           added up, one optimizer.step()) around engines/common_mil.py:32-37 (the 0.5 / 0.5 mix of the two logit vectors, :26-28),
+ *           modules/mhim.py:274-298 `pure` and mhim_modules/baseline.py:112-194 (BClassifier / DSMIL) with their autograd.
+ * Per bag the forward is mhimx_infer_dsmil_run's on h = dropout_b(act(X W1^T + b1)); loss_b = main_alpha CE(0.5 logits_bag + 0.5
+ * logits_ins, label_b) / n.  Backward: the head (fcc, i_classifier on the C critical rows), the softmax pool (d A from V . d B, the row
+ * dot as d B . B per class), the v network, the query side in two row passes (d q_max is a sum over the whole bag and returns to the
+ * critical rows of Q), the q network, the feature layer.  g = sum_b d loss_b / d theta over the twelve parameter tensors;
+ * update = 1: ONE Adam step on g (the flat gradient is cleared);  update = 0: g is left in cfg->grad (overwritten, not added to).
+ * Eighteen launches whatever n_bags and the sizes are (csrc/dsmil_window.hip lists them).  The properties are those of
+ * mhimx_pure_window_run: enqueue-only and capturable; no allocation, synchronisation or host-to-device copy (the bag table travels by
+ * value); no floating-point atomics, no workgroup waits for another, every sum has a fixed order; what is written per bag (logits, loss,
+ * crit, B, feature rows, d out / d pre) depends on that bag's N, seed and the tick alone.  crit: the lowest row on equal values.
+ * Bag b's keep-mask is the function of (drop_seed_b, tick, row inside the bag, column) the gemm epilogues use (one hash per element:
+ * mhimx_gemm_nt's dropout, which the per-op autograd route projects through) - element for element that route's mask for the same seed
+ * at the same tick value; NOT mhimx_bag_project's law, which mhimx_pure_window_run draws.
+ * The wide products (X -> h, h -> V, the q network both ways, d PreV Wv, d Pre1 Wq0, the four A^T B weight gradients) run in the 3-term
+ * bf16 form on the matrix cores; classes, scores, softmax, B, fcc, the loss and the head gradients in fp32.
+ * Shapes: E = 512, q width 128, 1 <= C <= 16, D % 256 == 0, D <= 2^20; 1 <= n_bags <= MHIMX_DSMIL_WINDOW_MAX; the bag-table and x_dtype
+ * rules of mhimx_pure_window_run_x (N >= 1, fp32 or fp16 / bf16 bags of one dtype read where they lie).  Every bag starts at a multiple of 32
+ * in the call's row space (layout.row0); the row space holds at most MHIMX_DSMIL_WINDOW_MAX_ROWS rows: the workspace takes
+ * 9 761 + 8 C bytes per row of it (feature rows 2 048, fp16 d out / d pre 1 024, V / d PreV 2 048, d PreV Wv / dPRE 2 048, Q, U1, d PreQ,
+ * d Pre1 512 each, classes 64, d a 64, per-tile partials 416, per-chunk partials 1 + 8 C), 2.6 GB at the cap with C = 16 - no more than
+ * mhimx_pure_window_run's 3.0 GB at its cap -, besides the weight images, the split-K slabs and the per-bag head partials
+ * (2 E D + 16 E D floats at most, 32 C C E floats of d fcc partials).
+ * Anything else returns < 0 before any device call, mhimx_last_error names the call and the bag.
+ * MHIMX_VERSION stays 620: additions only.
+ * ---------------------------------------------------------------------------------------- */
+#define MHIMX_DSMIL_WINDOW_MAX 32                 /* = MHIMX_INFER_MAX: the by-value bag table is the inference call's                    */
+#define MHIMX_DSMIL_WINDOW_MAX_ROWS 262144        /* rows of one call's row space                                                         */
+typedef struct {                                  /* the twelve DSMIL tensors, in mhimx_infer_dsmil_cfg's order                           */
+  const float *w1, *b1, *wi, *bi, *wq0, *bq0, *wq2, *bq2, *wv, *bv, *wfcc, *bfcc;
+} mhimx_dsmil_params;
+typedef struct {                                  /* where their gradients go (views of the flat gradient buffer), overwritten           */
+  float *w1, *b1, *wi, *bi, *wq0, *bq0, *wq2, *bq2, *wv, *bv, *wfcc, *bfcc;
+} mhimx_dsmil_grads;
+typedef struct {
+  int64_t D, E, C;                                /* input_dim, mlp_dim (512), classes                                                    */
+  int32_t act, pad;                               /* MHIMX_ACT_* of the feature layer                                                     */
+  float drop_p, main_alpha;                       /* feature dropout; weight of the cross entropy                                         */
+  mhimx_dsmil_params param;
+  mhimx_dsmil_grads grad;
+  float* p; float* g; float* m; float* v;         /* the flat buffers of mhimx_optim_step, as mhimx_step_cfg carries them                 */
+  int64_t n_train, n_all;
+  float lr, beta1, beta2, eps, weight_decay, pad2;
+  const float* lr_table; int64_t lr_len;
+  uint64_t* tick; uint64_t* opt_step;             /* device counters: dropout stream position, Adam step (advanced ONCE per call)         */
+} mhimx_dsmil_train_cfg;
+typedef struct {                                  /* byte offsets inside the workspace, valid until the next call on it                   */
+  int64_t total, rows;                            /* bytes; rows of the call's row space                                                  */
+  int64_t logits, losses;                         /* float [n, C] (mixed), float [n, 3] = {main_alpha ce, ce, 0} per bag, NOT scaled by 1 / n */
+  int64_t logits_bag, logits_ins, B, crit;        /* float [n, C], float [n, C], float [n, C, E], int64 [n, C] (row inside the bag)       */
+  int64_t H, dact;                                /* [rows, E] f32, [rows, E] f16                                                         */
+  int64_t row0[MHIMX_DSMIL_WINDOW_MAX];           /* first row of bag b in H / dact (a multiple of 32)                                    */
+} mhimx_dsmil_window_layout;
+/* pure host arithmetic: works without a device.  The bag list is mhimx_pure_window_run's (rows, pitch, N, label, dropout seed) */
+int mhimx_dsmil_window_layout_of(const mhimx_dsmil_train_cfg* cfg, int32_t n_bags, const mhimx_pure_window_bag* bags,
+                                 mhimx_dsmil_window_layout* out);
+/* host_step: the Adam step after this update when cfg->opt_step is NULL; x_dtype: MHIMX_X_* */
+int mhimx_dsmil_window_run(void* stream, const mhimx_dsmil_train_cfg* cfg, int32_t n_bags, const mhimx_pure_window_bag* bags,
+                           int64_t host_step, void* ws, int64_t ws_bytes, int32_t update, int32_t x_dtype);
+
+/* ------------------------------------------------------------------------------------------
  * Top-k instances of many score vectors: the k most (largest) or least attended instances of every bag of a ragged inference call,
  * from the call's own attention / score buffer, in one launch chain whatever n_segs is.
  * replaces: CLAM/create_heatmaps.py:53 (torch.topk of a slide's attention scores for review and heat maps) and the per-bag ranking of

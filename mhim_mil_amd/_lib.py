@@ -278,6 +278,36 @@ class PureWindowLayout(C.Structure):
         ("row0", C.c_int64 * PURE_WINDOW_MAX)]
 
 
+DSMIL_WINDOW_MAX = 32        # MHIMX_DSMIL_WINDOW_MAX
+DSMIL_WINDOW_MAX_ROWS = 262144   # MHIMX_DSMIL_WINDOW_MAX_ROWS (rows of the call's row space: every bag rounded up to a multiple of 32)
+_DSMIL_NAMES = ("w1", "b1", "wi", "bi", "wq0", "bq0", "wq2", "bq2", "wv", "bv", "wfcc", "bfcc")
+
+
+class DsmilParams(C.Structure):
+    """mhimx_dsmil_params: the twelve DSMIL tensors in mhimx_infer_dsmil_cfg's order."""
+    _fields_ = [(n, c_f32p) for n in _DSMIL_NAMES]
+
+
+class DsmilGrads(C.Structure):
+    """mhimx_dsmil_grads: their gradient views."""
+    _fields_ = [(n, c_f32p) for n in _DSMIL_NAMES]
+
+
+class DsmilTrainCfg(C.Structure):
+    """mhimx_dsmil_train_cfg: the teacher-free DSMIL model of mhimx_dsmil_window_run with the flat optimiser buffers."""
+    _fields_ = [("D", C.c_int64), ("E", C.c_int64), ("C", C.c_int64), ("act", C.c_int32), ("pad", C.c_int32), ("drop_p", C.c_float),
+                ("main_alpha", C.c_float), ("param", DsmilParams), ("grad", DsmilGrads), ("p", c_f32p), ("g", c_f32p), ("m", c_f32p),
+                ("v", c_f32p), ("n_train", C.c_int64), ("n_all", C.c_int64), ("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float),
+                ("eps", C.c_float), ("weight_decay", C.c_float), ("pad2", C.c_float), ("lr_table", c_f32p), ("lr_len", C.c_int64),
+                ("tick", C.c_void_p), ("opt_step", C.c_void_p)]
+
+
+class DsmilWindowLayout(C.Structure):
+    """mhimx_dsmil_window_layout: byte offsets inside the workspace; bag b's rows of H / dact start at row0[b]."""
+    _fields_ = [(n, C.c_int64) for n in ("total", "rows", "logits", "losses", "logits_bag", "logits_ins", "B", "crit", "H", "dact")] + [
+        ("row0", C.c_int64 * DSMIL_WINDOW_MAX)]
+
+
 RAGGED_WINDOW_MAX = 32          # MHIMX_RAGGED_WINDOW_MAX
 RAGGED_WINDOW_MAX_ROWS = 524288    # MHIMX_RAGGED_WINDOW_MAX_ROWS (rows of the call's row space: every bag's N + merge_k rounded up to a multiple of 32)
 
@@ -421,6 +451,8 @@ SYMBOLS = {
     "mhimx_pure_window_layout_of": (C.c_int, [C.POINTER(StepCfg), _I32, _P, C.POINTER(PureWindowLayout)]),
     "mhimx_pure_window_run": (C.c_int, [_P, C.POINTER(StepCfg), _I32, _P, _I64, _P, _I64, _I32]),
     "mhimx_pure_window_run_x": (C.c_int, [_P, C.POINTER(StepCfg), _I32, _P, _I64, _P, _I64, _I32, _I32]),
+    "mhimx_dsmil_window_layout_of": (C.c_int, [C.POINTER(DsmilTrainCfg), _I32, _P, C.POINTER(DsmilWindowLayout)]),
+    "mhimx_dsmil_window_run": (C.c_int, [_P, C.POINTER(DsmilTrainCfg), _I32, _P, _I64, _P, _I64, _I32, _I32]),
     "mhimx_ragged_window_layout_of": (C.c_int, [C.POINTER(StepCfg), _I32, _P, C.POINTER(RaggedWindowLayout)]),
     "mhimx_ragged_window_run": (C.c_int, [_P, C.POINTER(StepCfg), _I32, _P, _I64, _P, _I64, _I32]),
     "mhimx_ragged_window_run_x": (C.c_int, [_P, C.POINTER(StepCfg), _I32, _P, _I64, _P, _I64, _I32, _I32]),

@@ -67,7 +67,9 @@ typedef float in_f2 __attribute__((ext_vector_type(2)));
 // waits and the DMA ring are the fp32 form's), widened to fp32 in registers - exact for every fp16 and bf16 value, subnormals included - and
 // handed to the same split (XRow / x_widen: infer_tab.hpp): the LDS image, and with it every bit behind it, is that of the fp32 kernel on
 // the widened rows.
-template <bool TRAIN, int XT>
+// ELEM (TRAIN only; mhimx_dsmil_window_run): the keep-mask is the per-element law of the gemm epilogues (drop_keep_k: one 24-bit hash per
+// element, keep scale 1 / (1 - p)) - the mask ops.gemm_nt draws for the same seed, tick, row and column - instead of mhimx_bag_project's.
+template <bool TRAIN, int XT, bool ELEM = false>
 MHIMX_DEV void infer_project_body(const InferTab& tab, int D, const float* __restrict__ w1p, const float* __restrict__ b1, int act,
                                   float* __restrict__ Hout, const PureWinDrop& dr) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -251,8 +253,9 @@ MHIMX_DEV void infer_project_body(const InferTab& tab, int D, const float* __res
     uint32_t* rkeys = reinterpret_cast<uint32_t*>(smem + 80 * ITP * 4);
     const bool hashed = dr.drop_p > 0.f;
     const uint64_t dseed = hashed ? eff_seed(seed, dr.tick) : 0;
-    const uint32_t thr16 = (uint32_t)(dr.drop_p * 65536.f + 0.5f);
-    const float inv_keep = 65536.f / (float)(65536u - thr16);
+    [[maybe_unused]] const uint32_t thr16 = (uint32_t)(dr.drop_p * 65536.f + 0.5f);                       // mhimx_bag_project's pair law
+    [[maybe_unused]] const float inv_keep = 65536.f / (float)(65536u - thr16);
+    [[maybe_unused]] const float inv_keep_elem = 1.f / (1.f - dr.drop_p);                                 // ELEM: the gemm epilogues' law
     _Float16* db = dr.dact + (orow0 + m0) * IE + n;
     const int64_t rows_pad = ((N + 31) & ~(int64_t)31) - m0;   // the bag's rows up to the next multiple of 32: zero rows
 #pragma unroll 1
@@ -277,7 +280,13 @@ MHIMX_DEV void infer_project_body(const InferTab& tab, int D, const float* __res
         if (m < rows_left) {
           const f32x4 a = *reinterpret_cast<const f32x4*>(tile + r * ITP + c4);
           float ks[4] = {1.f, 1.f, 1.f, 1.f};
-          if (hashed) {
+          if constexpr (ELEM) {
+            if (hashed) {
+              const uint32_t rk = rkeys[r];
+#pragma unroll
+              for (int q = 0; q < 4; ++q) ks[q] = drop_keep_k(rk, (uint32_t)(n + q), dr.drop_p) ? inv_keep_elem : 0.f;
+            }
+          } else if (hashed) {
             const uint32_t rk = rkeys[r];
             const uint32_t h0 = pj_pair_hash(rk, (uint32_t)(n >> 1)), h1 = pj_pair_hash(rk, (uint32_t)(n >> 1) + 1u);
             ks[0] = (h0 & 0xffffu) >= thr16 ? inv_keep : 0.f;
@@ -342,6 +351,26 @@ template <int XT>
 __global__ __launch_bounds__(ITHREADS, 2) void pure_window_project_x_kernel(InferTab tab, PureWinDrop dr, int D, const float* __restrict__ w1p,
                                                                             const float* __restrict__ b1, int act, float* __restrict__ Hout) {
   infer_project_body<true, XT>(tab, D, w1p, b1, act, Hout, dr);
+}
+// the train projection with the gemm epilogues' per-element dropout law, all three element types (mhimx_dsmil_window_run)
+template <int XT>
+__global__ __launch_bounds__(ITHREADS, 2) void pure_window_project_elem_kernel(InferTab tab, PureWinDrop dr, int D, const float* __restrict__ w1p,
+                                                                               const float* __restrict__ b1, int act, float* __restrict__ Hout) {
+  infer_project_body<true, XT, true>(tab, D, w1p, b1, act, Hout, dr);
+}
+template <int XT>
+static int pure_window_project_elem_x(hipStream_t st, const InferTab& tab, const PureWinDrop& dr, int D, const float* w1p, const float* b1, int act,
+                                      float* Hout) {
+  MHIMX_ONCE_PER_DEVICE(MHIMX_HIP(hipFuncSetAttribute((const void*)pure_window_project_elem_kernel<XT>, hipFuncAttributeMaxDynamicSharedMemorySize, INST * ISTAGE)));
+  hipLaunchKernelGGL(pure_window_project_elem_kernel<XT>, dim3((unsigned)(8 * (IE / IBN) * cdiv(tab.tiles, 8))), dim3(ITHREADS), INST * ISTAGE, st, tab,
+                     dr, D, w1p, b1, act, Hout);
+  MHIMX_LAUNCH_CHECK();
+  return 0;
+}
+int pure_window_project_elem(hipStream_t st, const InferTab& tab, const PureWinDrop& dr, int D, const float* w1p, const float* b1, int act, float* Hout) {
+  if (tab.pad == MHIMX_X_F16) return pure_window_project_elem_x<1>(st, tab, dr, D, w1p, b1, act, Hout);
+  if (tab.pad == MHIMX_X_BF16) return pure_window_project_elem_x<2>(st, tab, dr, D, w1p, b1, act, Hout);
+  return pure_window_project_elem_x<0>(st, tab, dr, D, w1p, b1, act, Hout);
 }
 template <int XT>
 static int pure_window_project_x(hipStream_t st, const InferTab& tab, const PureWinDrop& dr, int D, const float* w1p, const float* b1, int act,

@@ -428,6 +428,26 @@ int dsmil_tail(hipStream_t st, const InferTab& tab, const mhimx_infer_dsmil_cfg*
 
 }  // namespace
 
+// launches 4, 5, 6 of the header for mhimx_dsmil_window_run (dsmil_window.hip): the same kernels over the caller's table and buffers
+int dsmil_rows_crit_pool(hipStream_t st, const InferTab& tab, const float* H, const float* V, const float* q0f, const float* bq0, const float* q2f,
+                         const float* bq2, const float* wi, const float* bi, int C, float* Q, float* cls, float* pmax, int32_t* parg, float* qmax,
+                         float* logits_ins, int64_t* crit, float* pm, float* pl, float* pB) {
+  MHIMX_CHECK_ARG(C >= 1 && C <= DS_MAXC, "dsmil_rows_crit_pool: 1 <= C <= %d", DS_MAXC);
+  MHIMX_ONCE_PER_DEVICE(MHIMX_HIP(hipFuncSetAttribute((const void*)dsmil_rows_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)DR_SMEM)));
+  hipLaunchKernelGGL(dsmil_rows_kernel, dim3((unsigned)tab.parts), dim3(RG_T), DR_SMEM, st, tab, H, q0f, bq0, q2f, bq2, wi, bi, C, Q, cls, nullptr, pmax,
+                     parg);
+  MHIMX_LAUNCH_CHECK();
+  hipLaunchKernelGGL(dsmil_crit_kernel, dim3((unsigned)tab.n), dim3(256), 0, st, tab, pmax, parg, Q, C, qmax, logits_ins, crit);
+  MHIMX_LAUNCH_CHECK();
+  const dim3 grid((unsigned)tab.parts), block(DP_THREADS);
+  if (C <= 2) hipLaunchKernelGGL(dsmil_pool_kernel<2>, grid, block, 0, st, tab, Q, V, qmax, C, pm, pl, pB);
+  else if (C <= 4) hipLaunchKernelGGL(dsmil_pool_kernel<4>, grid, block, 0, st, tab, Q, V, qmax, C, pm, pl, pB);
+  else if (C <= 8) hipLaunchKernelGGL(dsmil_pool_kernel<8>, grid, block, 0, st, tab, Q, V, qmax, C, pm, pl, pB);
+  else hipLaunchKernelGGL(dsmil_pool_kernel<16>, grid, block, 0, st, tab, Q, V, qmax, C, pm, pl, pB);
+  MHIMX_LAUNCH_CHECK();
+  return 0;
+}
+
 }  // namespace mhimx
 
 extern "C" int64_t mhimx_infer_dsmil_ws_bytes(const mhimx_infer_dsmil_cfg* cfg, int32_t n_bags, const mhimx_infer_bag* bags) {

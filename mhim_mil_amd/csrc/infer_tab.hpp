@@ -192,6 +192,8 @@ struct PureWinDrop {
   float drop_p, pad;
 };
 int pure_window_project(hipStream_t st, const InferTab& tab, const PureWinDrop& dr, int D, const float* w1p, const float* b1, int act, float* Hout);
+// the same launch with the gemm epilogues' per-element dropout law (the mask ops.gemm_nt draws for the same seed, tick, row, column)
+int pure_window_project_elem(hipStream_t st, const InferTab& tab, const PureWinDrop& dr, int D, const float* w1p, const float* b1, int act, float* Hout);
 // the ragged scorer + pool-partial launch of infer.hip (one workgroup per 256-row chunk of one bag; InferTab.part0 / .parts / .row0)
 int infer_score(hipStream_t st, const InferTab& tab, const float* H, const float* wa_frag, const float* wc, int act, float* s, float* pm, float* pl,
                 float* pz);
@@ -204,6 +206,15 @@ int infer_score_cproj(hipStream_t st, const InferTab& tab, const float* H, const
 int pw_split_k(int steps, int want_max, int div, int32_t* S, int32_t* per);
 int pw_wgrad_bagx(hipStream_t st, const InferTab& tab, const float* dpre, int D, int steps, int S, int per, float* slabs);
 int pw_reduce(hipStream_t st, int n, const float* const* parts, const int32_t* G, const int64_t* W, float* const* out);
+// the same product with both operands as fp32 rows of the row space (pw_tn_kernel<false, 0>): slabs[z][M][Nc] = sum over the k-steps of slab z
+// of A[rows, M]^T B[rows, Nc]; M and Nc multiples of 128, padding rows of both operands finite and zero in A
+int pw_wgrad_rows(hipStream_t st, const InferTab& tab, const float* A, int lda, int M, const float* B, int ldb, int Nc, int steps, int S, int per,
+                  float* slabs);
+// infer_dsmil.hip's launches 4, 5, 6 over a table (row space, chunks) as a host call: per-row Q / classes and the arg-max partials, the
+// critical rows (crit, logits_ins, q_max), the softmax-pool partials {pm, pl, pB}; C <= 16
+int dsmil_rows_crit_pool(hipStream_t st, const InferTab& tab, const float* H, const float* V, const float* q0f, const float* bq0, const float* q2f,
+                         const float* bq2, const float* wi, const float* bi, int C, float* Q, float* cls, float* pmax, int32_t* parg, float* qmax,
+                         float* logits_ins, int64_t* crit, float* pm, float* pl, float* pB);
 // step.hip: the checks mhimx_step_run makes on (cfg, N, counts)
 int step_check_cfg(const mhimx_step_cfg* c, int64_t N, const mhimx_step_counts* n);
 

@@ -527,6 +527,16 @@ int pw_wgrad_bagx(hipStream_t st, const InferTab& tab, const float* dpre, int D,
   MHIMX_LAUNCH_CHECK();
   return 0;
 }
+// slabs[z][M][Nc] = sum over the k-steps of slab z of A[rows, M]^T B[rows, Nc], both operands fp32 rows of the row space: launch 6 of the header
+int pw_wgrad_rows(hipStream_t st, const InferTab& tab, const float* A, int lda, int M, const float* B, int ldb, int Nc, int steps, int S, int per,
+                  float* slabs) {
+  MHIMX_CHECK_ARG(M >= TN_BM && M % TN_BM == 0 && Nc >= TN_BN && Nc % TN_BN == 0 && lda >= M && ldb >= Nc && lda % 4 == 0 && ldb % 4 == 0,
+                  "pw_wgrad_rows: M and Nc must be multiples of 128 inside their pitches");
+  hipLaunchKernelGGL((pw_tn_kernel<false, 0>), dim3((unsigned)(Nc / TN_BN), (unsigned)(M / TN_BM), (unsigned)S), dim3(TN_T), 0, st, tab, A, lda, B, ldb, steps,
+                     per, slabs, M, Nc);
+  MHIMX_LAUNCH_CHECK();
+  return 0;
+}
 // out_j[i] = sum_{g < G_j} parts_j[g W_j + i], j < n <= 6, in index order: launch 8 of the header
 int pw_reduce(hipStream_t st, int n, const float* const* parts, const int32_t* G, const int64_t* W, float* const* out) {
   MHIMX_CHECK_ARG(n >= 1 && n <= RED_JOBS, "pw_reduce: 1..%d jobs", RED_JOBS);

@@ -365,15 +365,25 @@ class FusedTrainer:
         # bag's N + merge_k rounded up to a multiple of 32) a window may have - its workspace takes 7.3 KB per row (1.9 GB at this cap);
         # include/mhimx.h allows twice as many
         self.ragged_window_row_cap = 262144
+        # 'mhim_pure' DSMIL steps and accumulation windows as ONE call (mhimx_dsmil_window_run): rows of the call's row space a call may
+        # have - its workspace takes 9.9 KB per row (1.3 GB at this cap); include/mhimx.h allows twice as many
+        self.dsmil_window_row_cap = 131072
+        self._dsmil_exec = None
 
     def _dist(self):
         return torch.distributed.is_available() and torch.distributed.is_initialized()
 
     # -------------------------------------------------------------------------------------------------
     def forward_backward(self, bag, label, perm=None, ids_shuffle=None, i=None):
-        """Teacher fwd + select + student fwd + head + backward into the flat gradient buffer (accumulating)."""
+        """Teacher fwd + select + student fwd + head + backward into the flat gradient buffer (accumulating).
+        The native one-call routes (mhimx_step_run, mhimx_pure_step_run, mhimx_dsmil_window_run) take ``label`` as an int64 tensor of one
+        element on the bag's device; an int or a CPU label takes the Python orchestration (``self.last["exec"]`` says which ran)."""
         s, t, fl = self.s, self.t, self.flat
         x = s._check_x(bag)
+        # the teacher-free DSMIL step (accumulation_steps == 1) as ONE call: mhimx_dsmil_window_run with one bag
+        if self.accum == 1 and perm is None and ids_shuffle is None and self._dsmil_window_ok([x], [label]):
+            logits, losses = self._exec_dsmil_window([x], [label], bool(self._fold_now), single=True)
+            return logits[0], losses[0]
         # parameter-only preparation of the step: weight transposes, paired-plane weights, query snapshot
         # (kept on the launch stream: a parallel branch in the captured hipGraph costs ~60 us of cross-queue signalling on
         # ROCm 7.2 — measured, profiles/ r01 notes — against ~40 us of kernels it would hide)
@@ -618,6 +628,114 @@ class FusedTrainer:
         self._window_done(n, inside, update)
         return logits, losses
 
+    # ------------------------------------------------------------------------------------------------- the teacher-free DSMIL call
+    _DSMIL_PARAMS = ("feature.0.weight", "feature.0.bias", "online_encoder.i_classifier.0.weight", "online_encoder.i_classifier.0.bias",
+                     "online_encoder.b_classifier.q.0.weight", "online_encoder.b_classifier.q.0.bias", "online_encoder.b_classifier.q.2.weight",
+                     "online_encoder.b_classifier.q.2.bias", "online_encoder.b_classifier.v.1.weight", "online_encoder.b_classifier.v.1.bias",
+                     "online_encoder.b_classifier.fcc.weight", "online_encoder.b_classifier.fcc.bias")
+
+    @staticmethod
+    def dsmil_window_shapes_ok(bags, D, E=512, Q=128, C=2, max_rows=262144, row_cap=262144, max_bags=32, elem=4):
+        """csrc/dsmil_window.hip check_dw and mhimx_dsmil_window_run's own argument checks, mirrored and tensor-free: a step or window the
+        call would refuse takes the bag-after-bag route instead of raising.  ``bags``: one (N, D, pitch, inner, ptr) per bag - shape,
+        strides in elements, address; ``D``: the model's input width; ``Q``: the q network's width; ``elem``: bytes of an element of the
+        bags' rows (4: fp32; 2: fp16 / bf16, whose pitch is a multiple of 8 elements and at most 2^20)."""
+        if not (E == 512 and Q == 128 and 1 <= C <= 16 and D > 0 and D % 256 == 0 and D <= (1 << 20) and 1 <= len(bags) <= max_bags):
+            return False
+        rows = 0
+        for N, Db, pitch, inner, ptr in bags:
+            if not (Db == D and ops.bag_rows_ok(N, D, pitch, inner, ptr, elem, max_rows, True)):
+                return False
+            rows += (N + 31) // 32 * 32
+        return rows <= row_cap
+
+    def _dsmil_window_ok(self, xs, labels):
+        """True when mhimx_dsmil_window_run takes these bags (fp32 bags, or fp16 / bf16 bags of ONE dtype) as one update of the teacher-free
+        DSMIL model.  Decided before any seed is drawn or counter touched."""
+        s = self.s
+        if ops.KERNEL_EVENT_HOOK is not None or not xs:
+            return False
+        if not (self.use_executor and self.model_kind == "mhim_pure" and s.baseline == "dsmil" and self.world == 1 and self._micro == 0
+                and s.training and s._op_prec != "f32" and len(labels) == len(xs)):
+            return False
+        dev = xs[0].device
+        if not all(torch.is_tensor(x) and x.is_cuda and x.dtype == xs[0].dtype and x.dim() == 2 and x.device == dev
+                   and s._feature_prec(x.shape[0]) == "bf16x3" for x in xs) or xs[0].dtype not in ops._X_DTYPES:
+            return False
+        if not ops.window_labels_ok(labels, dev):
+            return False
+        # (every DSMIL tensor has a gradient view; what else the model carries - the unused predictor - has no gradient on any route)
+        if not set(self._DSMIL_PARAMS) <= set(self.flat.train_names):
+            return False
+        ps = s._infer_dsmil_params()
+        Cc = s.n_classes
+        if (tuple(ps[4].shape) != (128, 512) or tuple(ps[6].shape) != (128, 128) or tuple(ps[8].shape) != (512, 512)
+                or tuple(ps[2].shape) != (Cc, 512) or ps[10].numel() != Cc * Cc * 512):
+            return False
+        if (any(not t.is_contiguous() or t.dtype != torch.float32 or t.device != dev for t in ps)
+                or any(ps[j].data_ptr() % 16 for j in (0, 1, 2, 4, 6, 8, 9))):
+            return False
+        return self.dsmil_window_shapes_ok([(x.shape[0], x.shape[1], x.stride(0), x.stride(1), x.data_ptr()) for x in xs], s.input_dim,
+                                           E=s.mlp_dim, Q=ps[4].shape[0], C=Cc, max_rows=self.exec_max_rows,
+                                           row_cap=min(self.dsmil_window_row_cap, mh.L.DSMIL_WINDOW_MAX_ROWS),
+                                           max_bags=min(self.accum, mh.L.DSMIL_WINDOW_MAX) if self.accum > 1 else 1, elem=xs[0].element_size())
+
+    def _dsmil_cfg(self):
+        """The mhimx_dsmil_train_cfg of this trainer: parameter / gradient pointers into the flat buffers (stable for the trainer's
+        lifetime); the optimiser's scalars are refreshed on every call."""
+        s, fl, L = self.s, self.flat, mh.L
+        ex = self._dsmil_exec
+        key = (s.feature[0].weight.data_ptr(), fl.grad.data_ptr())
+        if ex is None or ex["key"] != key:
+            ps, gv = s._infer_dsmil_params(), fl.grad_views
+            par = L.DsmilParams(**{n: t.data_ptr() for n, t in zip(L._DSMIL_NAMES, ps)})
+            grd = L.DsmilGrads(**{n: gv[name].data_ptr() for n, name in zip(L._DSMIL_NAMES, self._DSMIL_PARAMS)})
+            cfg = L.DsmilTrainCfg(D=s.input_dim, E=s.mlp_dim, C=s.n_classes, act=L.act_code(s.act, mh._FEATURE_ACTS), param=par, grad=grd,
+                                  p=fl.student.data_ptr(), g=fl.grad.data_ptr(), m=fl.m.data_ptr(), v=fl.v.data_ptr(), n_train=fl.n_train,
+                                  n_all=fl.n_all, tick=self.tick.data_ptr(), opt_step=self.opt_step.data_ptr())
+            ex = self._dsmil_exec = {"key": key, "cfg": cfg}
+        cfg = ex["cfg"]
+        cfg.lr, cfg.beta1, cfg.beta2, cfg.eps, cfg.weight_decay = self.lr, self.betas[0], self.betas[1], self.eps, self.wd
+        cfg.lr_table, cfg.lr_len = (None, 0) if self.lr_table is None else (self.lr_table.data_ptr(), self.lr_table.numel())
+        cfg.drop_p, cfg.main_alpha = float(s.dropout_p), float(self.main_alpha)
+        return ex
+
+    def _exec_dsmil_window(self, xs, labels, update, single=False):
+        """One update of the teacher-free DSMIL model over 1 .. accumulation_steps bags of any row counts, every loss scaled by
+        1 / len(bags), as ONE call of mhimx_dsmil_window_run.  ``single``: the one bag of forward_backward / train_step
+        (accumulation_steps == 1) with the single-bag bookkeeping.  Returns ([logits per bag], [losses per bag]); self.last keeps the
+        layout, the workspace and every bag's views."""
+        s, fl = self.s, self.flat
+        n = len(xs)
+        ex = self._dsmil_cfg()
+        table = ops.dsmil_window_bags(xs, labels, [0] * n)
+        lay = ops.dsmil_window_layout(ex["cfg"], table, n)
+        ws = ops.workspace(ex, "ws", lay.total, xs[0].device)
+        for j in range(n):                                          # ONE seed per bag, in bag order: the feature dropout's
+            table[j].drop_seed = s._next_seed()
+        inside = bool(update and not self.clip_grad)                # (clipping needs the norm of the final gradient: the update stays outside)
+        ops.dsmil_window_run(ex["cfg"], table, n, fl.step + int(inside), ws, inside, x_dtype=ops.x_dtype_of(xs))
+        E, Cc, view = s.mlp_dim, s.n_classes, ops.ws_view
+        lg, ls = view(ws, lay.logits, n * Cc).view(n, Cc), view(ws, lay.losses, n * 3).view(n, 3)
+        lb, li = view(ws, lay.logits_bag, n * Cc).view(n, Cc), view(ws, lay.logits_ins, n * Cc).view(n, Cc)
+        B, crit = view(ws, lay.B, n * Cc * E).view(n, Cc, E), view(ws, lay.crit, n * Cc, torch.int64).view(n, Cc)
+        H = view(ws, lay.H, lay.rows * E).view(lay.rows, E)
+        dact = view(ws, lay.dact, lay.rows * E, torch.float16).view(lay.rows, E)
+        per = []
+        for j, x in enumerate(xs):
+            r0, N = int(lay.row0[j]), x.shape[0]
+            per.append({"logits": lg[j], "losses": ls[j], "logits_bag": lb[j], "logits_ins": li[j], "B": B[j], "crit": crit[j], "patch_num": N,
+                        "keep_num": N, "row0": r0, "H_student": H[r0:r0 + N], "dact": dact[r0:r0 + N]})
+        logits, losses = [p["logits"] for p in per], [p["losses"] for p in per]
+        self.last = dict(self._last_pure(logits, losses, per[-1]["H_student"]), bags=per, layout=lay, ws=ws, exec="mhimx_dsmil_window_run",
+                         x_dtype=xs[0].dtype)
+        if single:
+            self.last.update(logits=logits[0], losses=losses[0])
+            self._steps_done(inside)
+        else:
+            self._window_done(n, inside, update)
+        return logits, losses
+
     @staticmethod
     def _last_pure(logits, losses, H):
         """self.last of a teacher-free bag with the feature rows H [N, E]: no row list, no score, no tokens, no teacher."""
@@ -675,13 +793,15 @@ class FusedTrainer:
         route, which scales by 1 / accumulation_steps and so needs exactly that many bags."""
         k = len(bags)
         assert 1 <= k <= self.accum and len(labels) == k, "window_step takes at most accumulation_steps bags"
+        # (the DSMIL student has its own call: mhimx_dsmil_window_run)
+        ok, run = (self._dsmil_window_ok, self._exec_dsmil_window) if self.s.baseline == "dsmil" else (self._pure_window_ok, self._exec_pure_window)
         # (a window of fp16 / bf16 bags goes into the native call as it is; every other route reads fp32 rows: widened as always)
         xs = self._half_bags(bags) if perms is None and shuffles is None else None
-        if xs is not None and self._pure_window_ok(xs, labels):
-            return self._exec_pure_window(xs, labels, update)
+        if xs is not None and ok(xs, labels):
+            return run(xs, labels, update)
         xs = [self.s._check_x(b) for b in bags]
-        if perms is None and shuffles is None and self._pure_window_ok(xs, labels):
-            return self._exec_pure_window(xs, labels, update)
+        if perms is None and shuffles is None and ok(xs, labels):
+            return run(xs, labels, update)
         assert k == self.accum, "window_step takes exactly accumulation_steps bags"
         outs = [self.train_step(b, l, i=i, **({} if perms is None else {"perm": perms[j], "ids_shuffle": shuffles[j]}))
                 for j, (b, l) in enumerate(zip(bags, labels))]
@@ -1244,8 +1364,9 @@ class FusedTrainer:
         if self.world > 1:
             raise mh.L.MhimxError("capture_window: one process (data-parallel ranks exchange gradients between windows: use capture())")
         if self.model_kind == "mhim_pure" and self.accum > 1:
-            if not self._pure_window_ok([self.s._check_x(b) for b in bags], labels):
-                raise mh.L.MhimxError("capture_window: mhimx_pure_window_run does not take these bags / this model")
+            xs_ = [self.s._check_x(b) for b in bags]
+            if not (self._dsmil_window_ok(xs_, labels) if self.s.baseline == "dsmil" else self._pure_window_ok(xs_, labels)):
+                raise mh.L.MhimxError("capture_window: mhimx_pure_window_run / mhimx_dsmil_window_run does not take these bags / this model")
         elif self._ragged_window_ok([self.s._check_x(b) for b in bags], labels, kw.get("i")):
             pass                                    # (window_step decides between mhimx_window_run and mhimx_ragged_window_run)
         elif not self.window_ok([self.s._check_x(b) for b in bags], kw.get("i")):

@@ -1325,6 +1325,27 @@ def pure_window_run(cfg, bags, n, host_step, ws, update, x_dtype=L.X_F32):
                                             int(x_dtype)), _x_name("mhimx_pure_window_run", x_dtype))
 
 
+# ------------------------------------------------------------------------------------------- ragged DSMIL accumulation window
+def dsmil_window_bags(xs, labels, seeds):
+    """The by-value bag table of mhimx_dsmil_window_run: mhimx_pure_window_run's (``pure_window_bags``)."""
+    x_dtype_of(xs, "dsmil_window_bags")
+    return pure_window_bags(xs, labels, seeds)
+
+
+def dsmil_window_layout(cfg, bags, n):
+    """mhimx_dsmil_window_layout_of: host arithmetic only (no device needed)."""
+    lay = L.DsmilWindowLayout()
+    L.check(L.lib().mhimx_dsmil_window_layout_of(C.byref(cfg), n, bags, C.byref(lay)), "mhimx_dsmil_window_layout_of")
+    return lay
+
+
+def dsmil_window_run(cfg, bags, n, host_step, ws, update, x_dtype=L.X_F32):
+    """ONE optimiser update (update = False: the summed gradient only) of the teacher-free DSMIL model over the n bags of the table as one
+    C call.  ``x_dtype``: what the table's rows are (``x_dtype_of`` of the tensors it was made from)."""
+    L.check(L.lib().mhimx_dsmil_window_run(_stream(), C.byref(cfg), n, bags, int(host_step), ws.data_ptr(), ws.numel(), int(bool(update)),
+                                           int(x_dtype)), "mhimx_dsmil_window_run")
+
+
 # ------------------------------------------------------------------------------------------- ragged MHIM accumulation window
 def ragged_window(cfg, bags, n, host_step=0, ws=None, update=False, layout_only=False, x_dtype=L.X_F32):
     """mhimx_ragged_window_layout_of (host arithmetic only) and, unless ``layout_only``, mhimx_ragged_window_run: ONE optimiser update
