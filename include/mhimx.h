@@ -1211,6 +1211,84 @@ int mhimx_dsmil_window_run(void* stream, const mhimx_dsmil_train_cfg* cfg, int32
                            int64_t host_step, void* ws, int64_t ws_bytes, int32_t update, int32_t x_dtype);
 
 /* ------------------------------------------------------------------------------------------
+ * Ragged accumulation window of the FULL MHIM(DSMIL) model (the recipe's second training for the second MHIM baseline: EMA teacher,
+ * hard-instance select, Merge, DSMIL student, per-class distillation): ONE optimiser update over n_bags bags of DIFFERENT row counts in
+ * one call; n_bags = 1 is the single-bag step.
+ * replaces: engines/base_engine.py:29-51,76-167 (the accumulation window, its one optimizer.step() and the per-parameter EMA) around
+ *           engines/common_mil.py:14-48 (forward_func: model_ema.forward_teacher -> model(bag, score, teacher_feat), the 0.5 / 0.5 mix of
+ *           the two logit vectors), modules/mhim.py:181-227 (forward_teacher), :109-179 (get_mask), :318-378 (forward, baseline 'dsmil':
+ *           :355-364), mhim_modules/merge.py:127-203 and mhim_modules/baseline.py:112-194 (BClassifier / DSMIL) with their autograd.
+ * Per bag b:
+ *   teacher   h_t = dropout_b(act(X Wt1^T + bt1)) (drop_p_teacher), the DSMIL forward of mhimx_infer_dsmil_run on it -> B_teacher [C, E]
+ *             and every row's instance score (cls_attn: max_c classes, else max_c A);
+ *   select    mhimx_select_rows_many's row list [rows that stay (Lk) | rows to merge (R)] from that score, bag b's select seed and the tick;
+ *   student   h = dropout_b(act(X W1^T + b1)) over all N rows; tokens = [h[stay rows] ; Merge(h[rows to merge])] (Lk + k rows; every bag
+ *             attends with the call's first global queries); the DSMIL forward on the tokens -> logits_bag, logits_ins, B;
+ *   loss_b    = (main_alpha CE(0.5 logits_bag + 0.5 logits_ins, label_b) + aux_alpha cl) / n,  cl = mean_c SoftTargetCE(B[c], B_teacher[c],
+ *             temp_t) (mhimx_dsmil_head's arithmetic; aux_alpha == 0: no distillation term).
+ * g = sum_b d loss_b / d theta over the twelve DSMIL tensors and the six trained Merge tensors; the global queries take the window's EMA
+ * chain q <- mm^n q + (1 - mm) sum_b mm^(n-1-b) z_b on the bags' Merge tokens z_b (into q_out when given, else in place).
+ * update = 1: ONE Adam step on g and the EMA teacher (p_teacher), the flat gradient cleared;  update = 0: g is left in cfg->base.grad /
+ * cfg->merge_grad (overwritten, not added to).
+ * Two row spaces: the bag space (every bag's N rows from a multiple of 32 on: layout.row0) and the compact token space (bag b's Lk + k
+ * token rows from a multiple of 32 on: layout.tok0).  Launches: 28 window-wide + 9 per bag, more for every bag above 16 384 rows
+ * (mhimx_select_rows_many's sequence for such a bag; csrc/dsmil_mhim.hip lists them).  Enqueue-only and capturable; no allocation, synchronisation or host-to-device copy (the bag
+ * table travels by value); no floating-point atomics, no workgroup waits for another, every sum has a fixed order; what is written per
+ * bag depends on that bag's rows, counts, seeds and the tick alone.  The dropout masks are mhimx_bag_project's law (the one
+ * mhimx_ragged_window_run draws).  Wide products in the 3-term bf16 form on the matrix cores; scores, softmax, B, fcc, both losses and
+ * the head gradients in fp32.
+ * Shapes: E = 512, q width 128, 1 <= C <= 16, D % 256 == 0, D <= 2^20, 1 <= k and 8 k <= 48; the Merge weights 16-byte aligned (the
+ * projection-free form of mhimx_merge_fwd); 1 <= n_bags <= MHIMX_DSMIL_MHIM_WINDOW_MAX; per bag the count rule of mhimx_step_run
+ * (64 <= N <= MHIMX_STEP_MAX_ROWS, 1 <= k_top <= 4096 up to 16 384 rows / 16 384 above, 1 <= n_sel <= k_top, len_keep = N - n_sel,
+ * Lk >= 1, 1 <= R <= 32768, Lk + R = len_keep) and the bag-table and x_dtype rules of mhimx_ragged_window_run_x.  The bag space holds at
+ * most MHIMX_DSMIL_MHIM_WINDOW_MAX_ROWS rows.  Workspace bytes: 7 905 + 8 C per row of the bag space (teacher and student feature rows
+ * 2 x 2 048, fp16 d out / d pre 1 024, teacher V / dPRE 2 048, teacher Q 512, classes 64, score 4, row list 8, list position 4,
+ * per-tile and per-chunk partials 145 + 8 C), 8 673 + 8 C per row of the token space (tokens, V / d PreV, d PreV Wv / d tokens 3 x 2 048,
+ * Q, U1, d PreQ, d Pre1 4 x 512, classes 64, d a 64, partials 353 + 8 C) and at most 16 900 per row to merge (the rows and their gradient
+ * 2 x 2 048, the bag's own Merge workspace): 17 KB per bag row at the default ratios, 25 KB at most - 3.3 GB at the cap, no more than
+ * mhimx_ragged_window_run's 3.8 GB at its cap -, besides the weight images, the split-K slabs and the per-bag head partials.
+ * Anything else returns < 0 before any device call, mhimx_last_error names the call and the bag.
+ * MHIMX_VERSION stays 620: additions only.
+ * ---------------------------------------------------------------------------------------- */
+#define MHIMX_DSMIL_MHIM_WINDOW_MAX 32            /* = MHIMX_INFER_MAX: the by-value bag table is the inference call's                    */
+#define MHIMX_DSMIL_MHIM_WINDOW_MAX_ROWS 131072   /* rows of one call's bag space                                                         */
+typedef struct { const float *ln_w, *ln_b, *wkv, *wq, *wo, *bo; } mhimx_dsmil_merge_params;   /* merge.norm, merge.attn.to_kv / to_q / to_out.0 */
+typedef struct { float *ln_w, *ln_b, *wkv, *wq, *wo, *bo; } mhimx_dsmil_merge_grads;
+typedef struct {
+  mhimx_dsmil_train_cfg base;                     /* the student: shapes, parameters, gradient views, optimiser buffers, counters;
+                                                     base.drop_p is the student's feature dropout                                        */
+  mhimx_dsmil_params teacher;                     /* the EMA teacher's twelve tensors (never written here: mhimx_optim_step moves them)    */
+  mhimx_dsmil_merge_params merge;                 /* the student's Merge                                                                  */
+  mhimx_dsmil_merge_grads merge_grad;
+  float* q;                                       /* merge.global_q_mm [k, E]                                                             */
+  float* q_out;                                   /* optional [k, E]: where the chained queries go (q then stays what it was)             */
+  int64_t k;                                      /* merge_k                                                                              */
+  int32_t cls_attn, pad;                          /* the teacher's instance score: 1 = max_c classes, 0 = max_c A                         */
+  float drop_p_teacher, merge_drop_p, merge_mm;   /* the teacher's feature dropout (0 unless it runs in train mode); MCA dropout; g_q_mm  */
+  float temp_t, aux_alpha, ema_mm;
+  float* p_teacher;                               /* the teacher's flat buffer (NULL: no EMA)                                             */
+  const float* mm_table; int64_t mm_len;          /* optional EMA-momentum schedule, indexed by the device step counter                   */
+} mhimx_dsmil_mhim_cfg;
+typedef struct {                                  /* byte offsets inside the workspace, valid until the next call on it                   */
+  int64_t total, rows, tok_rows;                  /* bytes; rows of the bag space; rows of the token space                                */
+  int64_t logits, losses;                         /* float [n, C] (mixed), float [n, 3] = {main_alpha ce + aux_alpha cl, ce, cl}, NOT scaled by 1 / n */
+  int64_t logits_bag, logits_ins, B, crit;        /* float [n, C], float [n, C], float [n, C, E], int64 [n, C] (token row inside the bag) */
+  int64_t B_teacher;                              /* float [n, C, E]                                                                      */
+  int64_t H_teacher, H_student, dact;             /* bag space: [rows, E] f32, [rows, E] f32, [rows, E] f16                               */
+  int64_t score, rows_all;                        /* bag space: float [rows], int64 [rows] (bag b's list of len_keep ids at row0[b])      */
+  int64_t tokens;                                 /* token space: float [tok_rows, E] (bag b: Lk stay rows, then the k Merge tokens)      */
+  int64_t row0[MHIMX_DSMIL_MHIM_WINDOW_MAX];      /* first row of bag b in the bag space (a multiple of 32)                               */
+  int64_t tok0[MHIMX_DSMIL_MHIM_WINDOW_MAX];      /* first row of bag b in the token space (a multiple of 32)                             */
+} mhimx_dsmil_mhim_window_layout;
+/* pure host arithmetic: work without a device.  The bag list is mhimx_ragged_window_run's (rows, pitch, N, label, counts, four seeds) */
+int mhimx_dsmil_mhim_window_layout_of(const mhimx_dsmil_mhim_cfg* cfg, int32_t n_bags, const mhimx_ragged_window_bag* bags,
+                                      mhimx_dsmil_mhim_window_layout* out);
+int64_t mhimx_dsmil_mhim_window_ws_bytes(const mhimx_dsmil_mhim_cfg* cfg, int32_t n_bags, const mhimx_ragged_window_bag* bags);
+/* host_step: the Adam step after this update when cfg->base.opt_step is NULL; x_dtype: MHIMX_X_* */
+int mhimx_dsmil_mhim_window_run(void* stream, const mhimx_dsmil_mhim_cfg* cfg, int32_t n_bags, const mhimx_ragged_window_bag* bags,
+                                int64_t host_step, void* ws, int64_t ws_bytes, int32_t update, int32_t x_dtype);
+
+/* ------------------------------------------------------------------------------------------
  * Top-k instances of many score vectors: the k most (largest) or least attended instances of every bag of a ragged inference call,
  * from the call's own attention / score buffer, in one launch chain whatever n_segs is.
  * replaces: CLAM/create_heatmaps.py:53 (torch.topk of a slide's attention scores for review and heat maps) and the per-bag ranking of

@@ -308,6 +308,38 @@ class DsmilWindowLayout(C.Structure):
         ("row0", C.c_int64 * DSMIL_WINDOW_MAX)]
 
 
+DSMIL_MHIM_WINDOW_MAX = 32            # MHIMX_DSMIL_MHIM_WINDOW_MAX
+DSMIL_MHIM_WINDOW_MAX_ROWS = 131072   # MHIMX_DSMIL_MHIM_WINDOW_MAX_ROWS (rows of the call's bag space: every bag rounded up to a multiple of 32)
+_DSMIL_MERGE_NAMES = ("ln_w", "ln_b", "wkv", "wq", "wo", "bo")
+
+
+class DsmilMergeParams(C.Structure):
+    """mhimx_dsmil_merge_params: merge.norm.{weight, bias}, merge.attn.to_kv / to_q / to_out.0.weight, to_out.0.bias."""
+    _fields_ = [(n, c_f32p) for n in _DSMIL_MERGE_NAMES]
+
+
+class DsmilMergeGrads(C.Structure):
+    """mhimx_dsmil_merge_grads: their gradient views."""
+    _fields_ = [(n, c_f32p) for n in _DSMIL_MERGE_NAMES]
+
+
+class DsmilMhimCfg(C.Structure):
+    """mhimx_dsmil_mhim_cfg: the full MHIM(DSMIL) model of mhimx_dsmil_mhim_window_run - the student's mhimx_dsmil_train_cfg, the teacher's
+    twelve tensors, the Merge, the global queries, the select / Merge / distillation scalars and the EMA fields."""
+    _fields_ = [("base", DsmilTrainCfg), ("teacher", DsmilParams), ("merge", DsmilMergeParams), ("merge_grad", DsmilMergeGrads),
+                ("q", c_f32p), ("q_out", c_f32p), ("k", C.c_int64), ("cls_attn", C.c_int32), ("pad", C.c_int32),
+                ("drop_p_teacher", C.c_float), ("merge_drop_p", C.c_float), ("merge_mm", C.c_float), ("temp_t", C.c_float),
+                ("aux_alpha", C.c_float), ("ema_mm", C.c_float), ("p_teacher", c_f32p), ("mm_table", c_f32p), ("mm_len", C.c_int64)]
+
+
+class DsmilMhimWindowLayout(C.Structure):
+    """mhimx_dsmil_mhim_window_layout: byte offsets inside the workspace; bag b's rows of the bag space (H_teacher, H_student, dact, score,
+    rows_all) start at row0[b], its token rows at tok0[b]."""
+    _fields_ = [(n, C.c_int64) for n in ("total", "rows", "tok_rows", "logits", "losses", "logits_bag", "logits_ins", "B", "crit", "B_teacher",
+                                        "H_teacher", "H_student", "dact", "score", "rows_all", "tokens")] + [
+        ("row0", C.c_int64 * DSMIL_MHIM_WINDOW_MAX), ("tok0", C.c_int64 * DSMIL_MHIM_WINDOW_MAX)]
+
+
 RAGGED_WINDOW_MAX = 32          # MHIMX_RAGGED_WINDOW_MAX
 RAGGED_WINDOW_MAX_ROWS = 524288    # MHIMX_RAGGED_WINDOW_MAX_ROWS (rows of the call's row space: every bag's N + merge_k rounded up to a multiple of 32)
 
@@ -453,6 +485,9 @@ SYMBOLS = {
     "mhimx_pure_window_run_x": (C.c_int, [_P, C.POINTER(StepCfg), _I32, _P, _I64, _P, _I64, _I32, _I32]),
     "mhimx_dsmil_window_layout_of": (C.c_int, [C.POINTER(DsmilTrainCfg), _I32, _P, C.POINTER(DsmilWindowLayout)]),
     "mhimx_dsmil_window_run": (C.c_int, [_P, C.POINTER(DsmilTrainCfg), _I32, _P, _I64, _P, _I64, _I32, _I32]),
+    "mhimx_dsmil_mhim_window_layout_of": (C.c_int, [C.POINTER(DsmilMhimCfg), _I32, _P, C.POINTER(DsmilMhimWindowLayout)]),
+    "mhimx_dsmil_mhim_window_ws_bytes": (_I64, [C.POINTER(DsmilMhimCfg), _I32, _P]),
+    "mhimx_dsmil_mhim_window_run": (C.c_int, [_P, C.POINTER(DsmilMhimCfg), _I32, _P, _I64, _P, _I64, _I32, _I32]),
     "mhimx_ragged_window_layout_of": (C.c_int, [C.POINTER(StepCfg), _I32, _P, C.POINTER(RaggedWindowLayout)]),
     "mhimx_ragged_window_run": (C.c_int, [_P, C.POINTER(StepCfg), _I32, _P, _I64, _P, _I64, _I32]),
     "mhimx_ragged_window_run_x": (C.c_int, [_P, C.POINTER(StepCfg), _I32, _P, _I64, _P, _I64, _I32, _I32]),

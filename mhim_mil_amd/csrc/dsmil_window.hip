@@ -317,6 +317,9 @@ __global__ __launch_bounds__(RG_FIN_T) void dw_dqmax_kernel(InferTab tab, const 
 
 // ------------------------------------------------------------------------------------------------ 11. rows pass 2
 // blockIdx.x = 32-row tile.  Wave w owns columns [32 w, 32 w + 32) of the three [32][128] tiles and column tiles 4 w .. 4 w + 3 of d h.
+// PLAIN (mhimx_dsmil_mhim_window_run's token rows, which have no d out / d pre of their own): d h is written as it is, zero rows past
+// the bag's N; dact and db1_part are not read or written.
+template <bool PLAIN>
 __global__ __launch_bounds__(DW_T) void dw_rows2_kernel(InferTab tab, const float* __restrict__ Hin, const _Float16* __restrict__ dact,
                                                       const float* __restrict__ Q, const float* __restrict__ da, const float* __restrict__ qmax,
                                                       const float* __restrict__ dqmax, const int64_t* __restrict__ crit,
@@ -433,7 +436,7 @@ __global__ __launch_bounds__(DW_T) void dw_rows2_kernel(InferTab tab, const floa
     dbq0_part[(int64_t)tile * DW_Q + tid] = t;
   }
   // ---- d h = d Pre1 Wq0 (K = 128) + the d PreV Wv rows + g_li Wi on the critical rows; dPRE = d h * d out / d pre; column sums
-  const _Float16* db = dact + r0 * IE;
+  [[maybe_unused]] const _Float16* db = dact + r0 * IE;
   float* po = dpre + r0 * IE;
 #pragma unroll 1
   for (int q = 0; q < 4; ++q) {
@@ -448,13 +451,16 @@ __global__ __launch_bounds__(DW_T) void dw_rows2_kernel(InferTab tab, const floa
         float v = acc[i] + po[(int64_t)row * IE + col];
         for (int c = 0; c < C; ++c)
           if (crel[c] == row) v = fmaf(gls[c], wi[(int64_t)c * IE + col], v);
-        d = v * (float)db[(int64_t)row * IE + col];
+        if constexpr (PLAIN) d = v;
+        else d = v * (float)db[(int64_t)row * IE + col];
       }
       po[(int64_t)row * IE + col] = d;
       s += d;
     }
-    s += __shfl_xor(s, 32, 64);
-    if (kg == 0) db1_part[(int64_t)tile * IE + col] = s;
+    if constexpr (!PLAIN) {
+      s += __shfl_xor(s, 32, 64);
+      if (kg == 0) db1_part[(int64_t)tile * IE + col] = s;
+    }
   }
 }
 
@@ -561,6 +567,33 @@ void dw_layout(const mhimx_dsmil_train_cfg* c, int32_t n_bags, const mhimx_pure_
 
 }  // namespace
 
+// launches 8, 10 and 11 as host calls (infer_tab.hpp): mhimx_dsmil_window_run below and mhimx_dsmil_mhim_window_run (dsmil_mhim.hip)
+int dw_rows1(hipStream_t st, const InferTab& tab, int steps, float* V, const float* Q, const float* qmax, const float* stats, const float* dB,
+             const float* delta, int C, float* da, float* dbv_part, float* dqm_part) {
+  MHIMX_ONCE_PER_DEVICE(MHIMX_HIP(hipFuncSetAttribute((const void*)dw_rows1_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)DW_R1_SMEM)));
+  hipLaunchKernelGGL(dw_rows1_kernel, dim3((unsigned)steps), dim3(DW_T), DW_R1_SMEM, st, tab, V, Q, qmax, stats, dB, delta, C, da, dbv_part, dqm_part);
+  MHIMX_LAUNCH_CHECK();
+  return 0;
+}
+
+int dw_dqmax(hipStream_t st, const InferTab& tab, const float* dqm_part, float* dqmax) {
+  hipLaunchKernelGGL(dw_dqmax_kernel, dim3((unsigned)tab.n, DW_MAXC * DW_Q / RG_FIN_T), dim3(RG_FIN_T), 0, st, tab, dqm_part, dqmax);
+  MHIMX_LAUNCH_CHECK();
+  return 0;
+}
+
+int dw_rows2_plain(hipStream_t st, const InferTab& tab, int steps, const float* Hin, const float* Q, const float* da, const float* qmax,
+                   const float* dqmax, const int64_t* crit, const float* gli, const float* wi, const float* q0f, const float* bq0, const float* q2tf,
+                   const float* q0tf, int C, float* dhv, float* U1, float* dPQ, float* dP1, float* dbq0_part, float* dbq2_part) {
+  MHIMX_ONCE_PER_DEVICE(MHIMX_HIP(hipFuncSetAttribute((const void*)dw_rows2_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)DW_R2_SMEM)));
+  const _Float16* no_dact = nullptr;
+  float* no_db1 = nullptr;
+  hipLaunchKernelGGL(dw_rows2_kernel<true>, dim3((unsigned)steps), dim3(DW_T), DW_R2_SMEM, st, tab, Hin, no_dact, Q, da, qmax, dqmax, crit, gli, wi, q0f,
+                     bq0, q2tf, q0tf, C, dhv, U1, dPQ, dP1, no_db1, dbq0_part, dbq2_part);
+  MHIMX_LAUNCH_CHECK();
+  return 0;
+}
+
 }  // namespace mhimx
 
 extern "C" int mhimx_dsmil_window_layout_of(const mhimx_dsmil_train_cfg* cfg, int32_t n_bags, const mhimx_pure_window_bag* bags,
@@ -642,19 +675,15 @@ extern "C" int mhimx_dsmil_window_run(void* stream, const mhimx_dsmil_train_cfg*
     MHIMX_LAUNCH_CHECK();
   }
   // ---- 8. rows pass 1
-  MHIMX_ONCE_PER_DEVICE(MHIMX_HIP(hipFuncSetAttribute((const void*)dw_rows1_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)DW_R1_SMEM)));
-  hipLaunchKernelGGL(dw_rows1_kernel, dim3((unsigned)w.steps), dim3(DW_T), DW_R1_SMEM, st, tab, V, Q, F(w.qmax), F(w.stats), F(w.dB), F(w.delta), C,
-                     F(w.da), F(w.dbv_part), F(w.dqm_part));
-  MHIMX_LAUNCH_CHECK();
+  if (int r = dw_rows1(st, tab, w.steps, V, Q, F(w.qmax), F(w.stats), F(w.dB), F(w.delta), C, F(w.da), F(w.dbv_part), F(w.dqm_part))) return r;
   // ---- 9. d PreV Wv: the eval projection on the d PreV rows with the paired image of Wv^T (no bias, no activation)
   for (int b = 0; b < n_bags; ++b) tabv.X[b] = V + tab.row0[b] * IE;
   if (int r = infer_project(st, tabv, IE, F(w.vtp), nullptr, MHIMX_ACT_NONE, dhv)) return r;
   // ---- 10. d q_max of every bag
-  hipLaunchKernelGGL(dw_dqmax_kernel, dim3((unsigned)n_bags, DW_MAXC * DW_Q / RG_FIN_T), dim3(RG_FIN_T), 0, st, tab, F(w.dqm_part), F(w.dqmax));
-  MHIMX_LAUNCH_CHECK();
+  if (int r = dw_dqmax(st, tab, F(w.dqm_part), F(w.dqmax))) return r;
   // ---- 11. rows pass 2
-  MHIMX_ONCE_PER_DEVICE(MHIMX_HIP(hipFuncSetAttribute((const void*)dw_rows2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)DW_R2_SMEM)));
-  hipLaunchKernelGGL(dw_rows2_kernel, dim3((unsigned)w.steps), dim3(DW_T), DW_R2_SMEM, st, tab, H, dact, Q, F(w.da), F(w.qmax), F(w.dqmax), crit, F(w.gli),
+  MHIMX_ONCE_PER_DEVICE(MHIMX_HIP(hipFuncSetAttribute((const void*)dw_rows2_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)DW_R2_SMEM)));
+  hipLaunchKernelGGL(dw_rows2_kernel<false>, dim3((unsigned)w.steps), dim3(DW_T), DW_R2_SMEM, st, tab, H, dact, Q, F(w.da), F(w.qmax), F(w.dqmax), crit, F(w.gli),
                      P.wi, F(w.q0f), P.bq0, F(w.q2tf), F(w.q0tf), C, dhv, F(w.U1), F(w.dPQ), F(w.dP1), F(w.db1_part), F(w.dbq0_part), F(w.dbq2_part));
   MHIMX_LAUNCH_CHECK();
   // ---- 12. - 15. the four weight gradients

@@ -431,10 +431,10 @@ int dsmil_tail(hipStream_t st, const InferTab& tab, const mhimx_infer_dsmil_cfg*
 // launches 4, 5, 6 of the header for mhimx_dsmil_window_run (dsmil_window.hip): the same kernels over the caller's table and buffers
 int dsmil_rows_crit_pool(hipStream_t st, const InferTab& tab, const float* H, const float* V, const float* q0f, const float* bq0, const float* q2f,
                          const float* bq2, const float* wi, const float* bi, int C, float* Q, float* cls, float* pmax, int32_t* parg, float* qmax,
-                         float* logits_ins, int64_t* crit, float* pm, float* pl, float* pB) {
+                         float* logits_ins, int64_t* crit, float* pm, float* pl, float* pB, float* score) {
   MHIMX_CHECK_ARG(C >= 1 && C <= DS_MAXC, "dsmil_rows_crit_pool: 1 <= C <= %d", DS_MAXC);
   MHIMX_ONCE_PER_DEVICE(MHIMX_HIP(hipFuncSetAttribute((const void*)dsmil_rows_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)DR_SMEM)));
-  hipLaunchKernelGGL(dsmil_rows_kernel, dim3((unsigned)tab.parts), dim3(RG_T), DR_SMEM, st, tab, H, q0f, bq0, q2f, bq2, wi, bi, C, Q, cls, nullptr, pmax,
+  hipLaunchKernelGGL(dsmil_rows_kernel, dim3((unsigned)tab.parts), dim3(RG_T), DR_SMEM, st, tab, H, q0f, bq0, q2f, bq2, wi, bi, C, Q, cls, score, pmax,
                      parg);
   MHIMX_LAUNCH_CHECK();
   hipLaunchKernelGGL(dsmil_crit_kernel, dim3((unsigned)tab.n), dim3(256), 0, st, tab, pmax, parg, Q, C, qmax, logits_ins, crit);
@@ -444,6 +444,21 @@ int dsmil_rows_crit_pool(hipStream_t st, const InferTab& tab, const float* H, co
   else if (C <= 4) hipLaunchKernelGGL(dsmil_pool_kernel<4>, grid, block, 0, st, tab, Q, V, qmax, C, pm, pl, pB);
   else if (C <= 8) hipLaunchKernelGGL(dsmil_pool_kernel<8>, grid, block, 0, st, tab, Q, V, qmax, C, pm, pl, pB);
   else hipLaunchKernelGGL(dsmil_pool_kernel<16>, grid, block, 0, st, tab, Q, V, qmax, C, pm, pl, pB);
+  MHIMX_LAUNCH_CHECK();
+  return 0;
+}
+
+// launch 7 for mhimx_dsmil_mhim_window_run's teacher (dsmil_mhim.hip): no labels, no loss; attn: the max_c A blocks
+int dsmil_finalize(hipStream_t st, const InferTab& tab, const float* pm, const float* pl, const float* pB, const float* Q, const float* qmax,
+                   const float* wfcc, const float* bfcc, int C, const float* logits_ins, float* logits_bag, float* logits, float* B, float* attn) {
+  MHIMX_CHECK_ARG(C >= 1 && C <= DS_MAXC, "dsmil_finalize: 1 <= C <= %d", DS_MAXC);
+  const dim3 grid((unsigned)tab.n, attn ? 1 + DF_ATTN_BLOCKS : 1), block(RG_FIN_T);
+  const int64_t* no_labels = nullptr;
+  float* no_loss = nullptr;
+  if (C <= 2) hipLaunchKernelGGL(dsmil_finalize_kernel<2>, grid, block, 0, st, tab, pm, pl, pB, Q, qmax, wfcc, bfcc, C, 0, no_labels, logits_ins, logits_bag, logits, B, attn, no_loss);
+  else if (C <= 4) hipLaunchKernelGGL(dsmil_finalize_kernel<4>, grid, block, 0, st, tab, pm, pl, pB, Q, qmax, wfcc, bfcc, C, 0, no_labels, logits_ins, logits_bag, logits, B, attn, no_loss);
+  else if (C <= 8) hipLaunchKernelGGL(dsmil_finalize_kernel<8>, grid, block, 0, st, tab, pm, pl, pB, Q, qmax, wfcc, bfcc, C, 0, no_labels, logits_ins, logits_bag, logits, B, attn, no_loss);
+  else hipLaunchKernelGGL(dsmil_finalize_kernel<16>, grid, block, 0, st, tab, pm, pl, pB, Q, qmax, wfcc, bfcc, C, 0, no_labels, logits_ins, logits_bag, logits, B, attn, no_loss);
   MHIMX_LAUNCH_CHECK();
   return 0;
 }

@@ -212,9 +212,24 @@ int pw_wgrad_rows(hipStream_t st, const InferTab& tab, const float* A, int lda, 
                   float* slabs);
 // infer_dsmil.hip's launches 4, 5, 6 over a table (row space, chunks) as a host call: per-row Q / classes and the arg-max partials, the
 // critical rows (crit, logits_ins, q_max), the softmax-pool partials {pm, pl, pB}; C <= 16
+// score (optional, rows of the row space): max_c classes of every row - the instance score of a model with cls_attn
 int dsmil_rows_crit_pool(hipStream_t st, const InferTab& tab, const float* H, const float* V, const float* q0f, const float* bq0, const float* q2f,
                          const float* bq2, const float* wi, const float* bi, int C, float* Q, float* cls, float* pmax, int32_t* parg, float* qmax,
-                         float* logits_ins, int64_t* crit, float* pm, float* pl, float* pB);
+                         float* logits_ins, int64_t* crit, float* pm, float* pl, float* pB, float* score = nullptr);
+// infer_dsmil.hip's launch 7 over a table as a host call (mhimx_dsmil_mhim_window_run's teacher): plane = bag, the partials merged in index
+// order -> B [n, C, 512], logits_bag, logits [n, C]; attn (optional, rows of the row space): max_c A of every row
+int dsmil_finalize(hipStream_t st, const InferTab& tab, const float* pm, const float* pl, const float* pB, const float* Q, const float* qmax,
+                   const float* wfcc, const float* bfcc, int C, const float* logits_ins, float* logits_bag, float* logits, float* B, float* attn);
+// dsmil_window.hip's backward launches 8, 10 and 11 over a table as host calls.  dw_rows2_plain: launch 11 for rows that have no
+// d out / d pre of their own (a student's token rows): d h as it is over dhv in place, no feature-bias partials
+int dw_rows1(hipStream_t st, const InferTab& tab, int steps, float* V, const float* Q, const float* qmax, const float* stats, const float* dB,
+             const float* delta, int C, float* da, float* dbv_part, float* dqm_part);
+int dw_dqmax(hipStream_t st, const InferTab& tab, const float* dqm_part, float* dqmax);
+int dw_rows2_plain(hipStream_t st, const InferTab& tab, int steps, const float* Hin, const float* Q, const float* da, const float* qmax,
+                   const float* dqmax, const int64_t* crit, const float* gli, const float* wi, const float* q0f, const float* bq0, const float* q2tf,
+                   const float* q0tf, int C, float* dhv, float* U1, float* dPQ, float* dP1, float* dbq0_part, float* dbq2_part);
+// ragged_window.hip's launch C.5 as a host call: q <- mm^n q + (1 - mm) sum_b mm^(n-1-b) z_b, z_b = the k rows of Hs from row tok[b] on
+int rw_q_chain(hipStream_t st, float* q, const float* Hs, int n_bags, const int64_t* tok, double mm, int n_floats);
 // step.hip: the checks mhimx_step_run makes on (cfg, N, counts)
 int step_check_cfg(const mhimx_step_cfg* c, int64_t N, const mhimx_step_counts* n);
 

@@ -320,6 +320,17 @@ void rw_layout(const mhimx_step_cfg* c, int32_t n_bags, const mhimx_ragged_windo
 
 }  // namespace
 
+// launch C.5 for mhimx_dsmil_mhim_window_run (dsmil_mhim.hip): the same kernel on that call's token rows
+int rw_q_chain(hipStream_t st, float* q, const float* Hs, int n_bags, const int64_t* tok, double mm, int n_floats) {
+  RwChain ch = {};
+  ch.n = n_bags;
+  q_chain_weights(mm, n_bags, &ch.wq, ch.w);
+  for (int b = 0; b < n_bags; ++b) ch.tok[b] = tok[b];
+  hipLaunchKernelGGL(rw_q_chain_kernel, dim3((unsigned)cdiv(n_floats, RW_T)), dim3(RW_T), 0, st, q, Hs, ch, n_floats);
+  MHIMX_LAUNCH_CHECK();
+  return 0;
+}
+
 }  // namespace mhimx
 
 using namespace mhimx;
@@ -456,12 +467,9 @@ extern "C" int mhimx_ragged_window_run_x(void* stream, const mhimx_step_cfg* cfg
     if (int r = pw_reduce(st, 2, parts, G, W, out)) return r;
   }
   {
-    RwChain ch = {};
-    ch.n = n_bags;
-    q_chain_weights((double)c.merge_mm, n_bags, &ch.wq, ch.w);
-    for (int b = 0; b < n_bags; ++b) ch.tok[b] = tab.row0[b] + bags[b].N;
-    hipLaunchKernelGGL(rw_q_chain_kernel, dim3((unsigned)cdiv(k * E, RW_T)), dim3(RW_T), 0, st, S.q, H_s, ch, (int)(k * E));
-    MHIMX_LAUNCH_CHECK();
+    int64_t tok[RW_MAX];
+    for (int b = 0; b < n_bags; ++b) tok[b] = tab.row0[b] + bags[b].N;
+    if (int r = rw_q_chain(st, S.q, H_s, n_bags, tok, (double)c.merge_mm, (int)(k * E))) return r;
   }
   if (!update) return 0;
   const mhimx_optim_args o = optim_args_of(c, host_step, true);

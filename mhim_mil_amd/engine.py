@@ -369,6 +369,10 @@ class FusedTrainer:
         # have - its workspace takes 9.9 KB per row (1.3 GB at this cap); include/mhimx.h allows twice as many
         self.dsmil_window_row_cap = 131072
         self._dsmil_exec = None
+        # 'mhim' DSMIL steps and accumulation windows as ONE call (mhimx_dsmil_mhim_window_run): rows of the call's bag space a call may
+        # have - its workspace takes 17 KB per row at the default ratios (2.2 GB at this cap, which is include/mhimx.h's)
+        self.dsmil_mhim_window_row_cap = 131072
+        self._dsmil_mhim_exec = None
 
     def _dist(self):
         return torch.distributed.is_available() and torch.distributed.is_initialized()
@@ -376,13 +380,18 @@ class FusedTrainer:
     # -------------------------------------------------------------------------------------------------
     def forward_backward(self, bag, label, perm=None, ids_shuffle=None, i=None):
         """Teacher fwd + select + student fwd + head + backward into the flat gradient buffer (accumulating).
-        The native one-call routes (mhimx_step_run, mhimx_pure_step_run, mhimx_dsmil_window_run) take ``label`` as an int64 tensor of one
-        element on the bag's device; an int or a CPU label takes the Python orchestration (``self.last["exec"]`` says which ran)."""
+        The native one-call routes (mhimx_step_run, mhimx_pure_step_run, mhimx_dsmil_window_run, mhimx_dsmil_mhim_window_run) take ``label``
+        as an int64 tensor of one element on the bag's device; an int or a CPU label takes the Python orchestration (``self.last["exec"]``
+        says which ran)."""
         s, t, fl = self.s, self.t, self.flat
         x = s._check_x(bag)
         # the teacher-free DSMIL step (accumulation_steps == 1) as ONE call: mhimx_dsmil_window_run with one bag
         if self.accum == 1 and perm is None and ids_shuffle is None and self._dsmil_window_ok([x], [label]):
             logits, losses = self._exec_dsmil_window([x], [label], bool(self._fold_now), single=True)
+            return logits[0], losses[0]
+        # the full MHIM(DSMIL) step (accumulation_steps == 1) as ONE call: mhimx_dsmil_mhim_window_run with one bag
+        if self.accum == 1 and perm is None and ids_shuffle is None and self._dsmil_mhim_window_ok([x], [label], i):
+            logits, losses = self._exec_dsmil_mhim_window([x], [label], i, bool(self._fold_now), single=True)
             return logits[0], losses[0]
         # parameter-only preparation of the step: weight transposes, paired-plane weights, query snapshot
         # (kept on the launch stream: a parallel branch in the captured hipGraph costs ~60 us of cross-queue signalling on
@@ -728,6 +737,150 @@ class FusedTrainer:
                         "keep_num": N, "row0": r0, "H_student": H[r0:r0 + N], "dact": dact[r0:r0 + N]})
         logits, losses = [p["logits"] for p in per], [p["losses"] for p in per]
         self.last = dict(self._last_pure(logits, losses, per[-1]["H_student"]), bags=per, layout=lay, ws=ws, exec="mhimx_dsmil_window_run",
+                         x_dtype=xs[0].dtype)
+        if single:
+            self.last.update(logits=logits[0], losses=losses[0])
+            self._steps_done(inside)
+        else:
+            self._window_done(n, inside, update)
+        return logits, losses
+
+    # ------------------------------------------------------------------------------------------------- the full MHIM(DSMIL) call
+    _DSMIL_MERGE_PARAMS = ("merge.norm.weight", "merge.norm.bias", "merge.attn.to_kv.weight", "merge.attn.to_q.weight",
+                           "merge.attn.to_out.0.weight", "merge.attn.to_out.0.bias")
+
+    @staticmethod
+    def dsmil_mhim_window_shapes_ok(bags, D, k, E=512, Q=128, C=2, max_rows=262144, row_cap=131072, max_bags=32, elem=4):
+        """csrc/dsmil_mhim.hip check_dm and mhimx_dsmil_mhim_window_run's own argument checks, mirrored and tensor-free: a step or window
+        the call would refuse takes today's route instead of raising.  ``bags``: one (N, D, pitch, inner, ptr, (k_top, n_sel, len_keep, Lk,
+        R)) per bag - shape, strides in elements, address, its counts; ``D``: the model's input width; ``k``: merge_k; ``Q``: the q
+        network's width; ``elem``: bytes of an element of the bags' rows (4: fp32; 2: fp16 / bf16, whose pitch is a multiple of 8 elements
+        and at most 2^20)."""
+        if not (E == 512 and Q == 128 and 1 <= C <= 16 and D > 0 and D % 256 == 0 and D <= (1 << 20) and k >= 1 and 8 * k <= 48
+                and 1 <= len(bags) <= max_bags):
+            return False
+        rows = 0
+        for N, Db, pitch, inner, ptr, cnt in bags:
+            if not (Db == D and cnt is not None and ops.bag_rows_ok(N, D, pitch, inner, ptr, elem, max_rows, True)
+                    and FusedTrainer._step_counts_ok(N, cnt, max_rows)):
+                return False
+            rows += (N + 31) // 32 * 32
+        return rows <= row_cap
+
+    def _dsmil_mhim_window_ok(self, xs, labels, i=None):
+        """True when mhimx_dsmil_mhim_window_run takes these bags (fp32 bags, or fp16 / bf16 bags of ONE dtype) as one update of the full
+        MHIM(DSMIL) model: 1 .. accumulation_steps bags, one process, device-drawn subsets, no mid-run ratio schedule, no merge_test, no
+        kernel event hook, not prec="f32".  Decided before any seed is drawn or counter touched."""
+        s, t = self.s, self.t
+        if ops.KERNEL_EVENT_HOOK is not None or not xs or self.model_kind != "mhim" or s.baseline != "dsmil":
+            return False
+        if not (self.use_executor and t is not None and t.baseline == "dsmil" and self.world == 1 and self._chain is None and self._micro == 0
+                and 1 <= len(xs) <= self.accum and len(labels) == len(xs) and s.training and s.merge_enable and not t.merge_test
+                and s.mrh_sche is None and s._op_prec != "f32" and t._op_prec != "f32" and s.act == t.act and s.n_classes == t.n_classes):
+            return False
+        dev = xs[0].device
+        if not all(torch.is_tensor(x) and x.is_cuda and x.dtype == xs[0].dtype and x.dim() == 2 and x.device == dev
+                   and s._feature_prec(x.shape[0]) == "bf16x3" for x in xs) or xs[0].dtype not in ops._X_DTYPES:
+            return False
+        if not ops.window_labels_ok(labels, dev):
+            return False
+        fl = self.flat
+        if not set(self._DSMIL_PARAMS + self._DSMIL_MERGE_PARAMS) <= set(fl.train_names):
+            return False
+        mg, Cc = s.merge, s.n_classes
+        mps = (mg.norm.weight.data, mg.norm.bias.data, mg.attn.to_kv.weight.data, mg.attn.to_q.weight.data, mg.attn.to_out[0].weight.data,
+               mg.attn.to_out[0].bias.data, mg.global_q_mm.data)
+        if (tuple(mps[2].shape) != (1024, 512) or tuple(mps[3].shape) != (512, 512) or tuple(mps[4].shape) != (512, 512)
+                or mps[6].numel() != mg.k * 512 or any(not p.is_contiguous() or p.dtype != torch.float32 or p.device != dev for p in mps)
+                or any(mps[j].data_ptr() % 16 for j in (0, 1, 2, 3, 4, 6))):
+            return False
+        for m in (s, t):
+            ps = m._infer_dsmil_params()
+            if (tuple(ps[0].shape) != (512, s.input_dim) or tuple(ps[4].shape) != (128, 512) or tuple(ps[6].shape) != (128, 128)
+                    or tuple(ps[8].shape) != (512, 512) or tuple(ps[2].shape) != (Cc, 512) or ps[10].numel() != Cc * Cc * 512):
+                return False
+            if (any(not p.is_contiguous() or p.dtype != torch.float32 or p.device != dev for p in ps)
+                    or any(ps[j].data_ptr() % 16 for j in (0, 1, 2, 4, 6, 8, 9))):
+                return False
+        return self.dsmil_mhim_window_shapes_ok(
+            [(x.shape[0], x.shape[1], x.stride(0), x.stride(1), x.data_ptr(), s.v2_counts(x.shape[0], i)) for x in xs], s.input_dim, mg.k,
+            E=s.mlp_dim, Q=128, C=Cc, max_rows=self.exec_max_rows,
+            row_cap=min(self.dsmil_mhim_window_row_cap, mh.L.DSMIL_MHIM_WINDOW_MAX_ROWS), max_bags=mh.L.DSMIL_MHIM_WINDOW_MAX,
+            elem=xs[0].element_size())
+
+    def _dsmil_mhim_cfg(self):
+        """The mhimx_dsmil_mhim_cfg of this trainer: parameter / gradient pointers into the flat buffers (stable for the trainer's
+        lifetime); the scalars are refreshed on every call."""
+        s, t, fl, L = self.s, self.t, self.flat, mh.L
+        ex = self._dsmil_mhim_exec
+        key = (s.feature[0].weight.data_ptr(), t.feature[0].weight.data_ptr(), fl.grad.data_ptr())
+        if ex is None or ex["key"] != key:
+            gv, mg = fl.grad_views, s.merge
+            par = L.DsmilParams(**{n: p.data_ptr() for n, p in zip(L._DSMIL_NAMES, s._infer_dsmil_params())})
+            tea = L.DsmilParams(**{n: p.data_ptr() for n, p in zip(L._DSMIL_NAMES, t._infer_dsmil_params())})
+            grd = L.DsmilGrads(**{n: gv[name].data_ptr() for n, name in zip(L._DSMIL_NAMES, self._DSMIL_PARAMS)})
+            mps = (mg.norm.weight, mg.norm.bias, mg.attn.to_kv.weight, mg.attn.to_q.weight, mg.attn.to_out[0].weight, mg.attn.to_out[0].bias)
+            mpar = L.DsmilMergeParams(**{n: p.data_ptr() for n, p in zip(L._DSMIL_MERGE_NAMES, mps)})
+            mgrd = L.DsmilMergeGrads(**{n: gv[name].data_ptr() for n, name in zip(L._DSMIL_MERGE_NAMES, self._DSMIL_MERGE_PARAMS)})
+            base = L.DsmilTrainCfg(D=s.input_dim, E=s.mlp_dim, C=s.n_classes, act=L.act_code(s.act, mh._FEATURE_ACTS), param=par, grad=grd,
+                                   p=fl.student.data_ptr(), g=fl.grad.data_ptr(), m=fl.m.data_ptr(), v=fl.v.data_ptr(), n_train=fl.n_train,
+                                   n_all=fl.n_all, tick=self.tick.data_ptr(), opt_step=self.opt_step.data_ptr())
+            cfg = L.DsmilMhimCfg(base=base, teacher=tea, merge=mpar, merge_grad=mgrd, q=mg.global_q_mm.data_ptr(), q_out=None, k=mg.k)
+            ex = self._dsmil_mhim_exec = {"key": key, "cfg": cfg}
+        cfg = ex["cfg"]
+        b = cfg.base
+        b.lr, b.beta1, b.beta2, b.eps, b.weight_decay = self.lr, self.betas[0], self.betas[1], self.eps, self.wd
+        b.lr_table, b.lr_len = (None, 0) if self.lr_table is None else (self.lr_table.data_ptr(), self.lr_table.numel())
+        b.drop_p, b.main_alpha = float(s.dropout_p), float(self.main_alpha)
+        cfg.cls_attn = int(bool(t.online_encoder.cls_attn))
+        cfg.drop_p_teacher = float(t.dropout_p if t.training else 0.0)
+        cfg.merge_drop_p, cfg.merge_mm = float(s.merge.dropout), float(s.merge.g_q_mm)
+        cfg.temp_t, cfg.aux_alpha, cfg.ema_mm = float(s.temp_t), float(self.aux_alpha), float(self.mm)
+        cfg.p_teacher = None if fl.same_teacher else fl.teacher.data_ptr()
+        cfg.mm_table, cfg.mm_len = (None, 0) if self.mm_table is None else (self.mm_table.data_ptr(), self.mm_table.numel())
+        return ex
+
+    def _exec_dsmil_mhim_window(self, xs, labels, i, update, single=False):
+        """One update of the full MHIM(DSMIL) model over 1 .. accumulation_steps bags of any row counts, every loss scaled by
+        1 / len(bags), as ONE call of mhimx_dsmil_mhim_window_run.  ``single``: the one bag of forward_backward / train_step
+        (accumulation_steps == 1) with the single-bag bookkeeping (_exec_step's).  Seeds are drawn bag after bag, per bag in the order
+        today's route draws them for that bag: the teacher's feature dropout (the teacher's stream), then from the student's stream its
+        feature dropout, the select's, Merge's.  Returns ([logits per bag], [losses per bag]); self.last keeps the layout, the workspace
+        and every bag's views."""
+        L = mh.L
+        s, fl = self.s, self.flat
+        n = len(xs)
+        ex = self._dsmil_mhim_cfg()
+        table = (L.RaggedWindowBag * n)()
+        for j, (x, l) in enumerate(zip(xs, labels)):
+            k_top, n_sel, len_keep, Lk, R = s.v2_counts(x.shape[0], i)
+            table[j].X, table[j].ldx, table[j].N, table[j].label_dev = x.data_ptr(), x.stride(0), x.shape[0], l.data_ptr()
+            table[j].cnt = L.StepCounts(k_top=k_top, n_sel=n_sel, len_keep=len_keep, Lk=Lk, R=R)
+        lay = ops.dsmil_mhim_window(ex["cfg"], table, n, layout_only=True)
+        ws = ops.workspace(ex, "ws", lay.total, xs[0].device)
+        for j in range(n):
+            table[j].seeds = self._step_seeds()
+        inside = bool(update and not self.clip_grad)                # (clipping needs the norm of the final gradient: the update stays outside)
+        ops.dsmil_mhim_window(ex["cfg"], table, n, fl.step + int(inside), ws, inside, x_dtype=ops.x_dtype_of(xs))
+        E, Cc, km, view = s.mlp_dim, s.n_classes, s.merge.k, ops.ws_view
+        lg, ls = view(ws, lay.logits, n * Cc).view(n, Cc), view(ws, lay.losses, n * 3).view(n, 3)
+        lb, li = view(ws, lay.logits_bag, n * Cc).view(n, Cc), view(ws, lay.logits_ins, n * Cc).view(n, Cc)
+        B, Bt = view(ws, lay.B, n * Cc * E).view(n, Cc, E), view(ws, lay.B_teacher, n * Cc * E).view(n, Cc, E)
+        crit = view(ws, lay.crit, n * Cc, torch.int64).view(n, Cc)
+        Ht, Hs = view(ws, lay.H_teacher, lay.rows * E).view(lay.rows, E), view(ws, lay.H_student, lay.rows * E).view(lay.rows, E)
+        dact = view(ws, lay.dact, lay.rows * E, torch.float16).view(lay.rows, E)
+        score, rows_all = view(ws, lay.score, lay.rows), view(ws, lay.rows_all, lay.rows, torch.int64)
+        T = view(ws, lay.tokens, lay.tok_rows * E).view(lay.tok_rows, E)
+        per = []
+        for j, x in enumerate(xs):
+            r0, t0, N, cnt = int(lay.row0[j]), int(lay.tok0[j]), x.shape[0], table[j].cnt
+            per.append({"logits": lg[j], "losses": ls[j], "logits_bag": lb[j], "logits_ins": li[j], "B": B[j], "B_teacher": Bt[j],
+                        "score": score[r0:r0 + N], "rows": rows_all[r0:r0 + cnt.len_keep], "Lk": int(cnt.Lk), "R": int(cnt.R), "crit": crit[j],
+                        "H_student": Hs[r0:r0 + N], "H_teacher": Ht[r0:r0 + N], "dact": dact[r0:r0 + N],
+                        "tokens": T[t0 + cnt.Lk:t0 + cnt.Lk + km], "token_rows": T[t0:t0 + cnt.Lk + km], "row0": r0, "tok0": t0,
+                        "patch_num": N, "keep_num": int(cnt.Lk) + km})
+        logits, losses = [p_["logits"] for p_ in per], [p_["losses"] for p_ in per]
+        self.last = dict(per[-1], logits=logits, losses=losses, bags=per, layout=lay, table=table, ws=ws, exec="mhimx_dsmil_mhim_window_run",
                          x_dtype=xs[0].dtype)
         if single:
             self.last.update(logits=logits[0], losses=losses[0])
@@ -1265,12 +1418,22 @@ class FusedTrainer:
           differs from the reference's bag-after-bag order in second order of 1 - merge_mm).
         Each bag's loss is scaled by 1 / accumulation_steps in the head kernel (base_engine.py:102).  Capturable (``capture_window``).
         Full windows of same-shaped bags take mhimx_window_run; windows of DIFFERENT-sized bags (1 .. accumulation_steps of them: a shorter last window
-        is scaled by its own length) take mhimx_ragged_window_run; injected draws, several processes, a kernel event hook, a ratio
-        schedule, prec="f32", merge_k > 6 and MHIMX_STEP_EXEC=0 keep the stream form below.  ``self.last["exec"]`` names the route.
+        is scaled by its own length) take mhimx_ragged_window_run; a DSMIL student's windows (1 .. accumulation_steps bags of any sizes) take
+        mhimx_dsmil_mhim_window_run; injected draws, several processes, a kernel event hook, a ratio schedule, prec="f32", merge_k > 6 and
+        MHIMX_STEP_EXEC=0 keep the stream form below (DSMIL: the bag-after-bag route).  ``self.last["exec"]`` names the route.
         Returns ([logits per bag], [losses per bag])."""
         k = len(bags)
         if self.model_kind == "mhim_pure" and self.accum > 1:
             return self._pure_window_step(bags, labels, i, perms, shuffles, update)
+        # the DSMIL student has its own call: mhimx_dsmil_mhim_window_run, for 1 <= len(bags) <= accumulation_steps (fp16 / bf16 bags go in as
+        # they are); what it refuses takes today's route below
+        if self.model_kind == "mhim" and self.s.baseline == "dsmil" and perms is None and shuffles is None and 1 <= k <= self.accum:
+            xs = self._half_bags(bags)
+            if xs is not None and self._dsmil_mhim_window_ok(xs, labels, i):
+                return self._exec_dsmil_mhim_window(xs, labels, i, update)
+            xs = [self.s._check_x(b) for b in bags]
+            if self._dsmil_mhim_window_ok(xs, labels, i):
+                return self._exec_dsmil_mhim_window(xs, labels, i, update)
         # (a window of fp16 / bf16 bags goes into mhimx_ragged_window_run_x as it is; every other route reads fp32 rows: widened as always)
         xs = self._half_bags(bags) if perms is None and shuffles is None else None
         if xs is not None and not (k == self.accum and all(x.shape == xs[0].shape for x in xs)) and self._ragged_window_ok(xs, labels, i):
@@ -1369,6 +1532,8 @@ class FusedTrainer:
                 raise mh.L.MhimxError("capture_window: mhimx_pure_window_run / mhimx_dsmil_window_run does not take these bags / this model")
         elif self._ragged_window_ok([self.s._check_x(b) for b in bags], labels, kw.get("i")):
             pass                                    # (window_step decides between mhimx_window_run and mhimx_ragged_window_run)
+        elif self._dsmil_mhim_window_ok([self.s._check_x(b) for b in bags], labels, kw.get("i")):
+            pass                                    # (mhimx_dsmil_mhim_window_run)
         elif not self.window_ok([self.s._check_x(b) for b in bags], kw.get("i")):
             raise mh.L.MhimxError("capture_window: these bags / this model do not take the single-pass ABMIL step")
         self._capturing = True
@@ -1613,7 +1778,7 @@ class FusedTrainer:
         s, t = self.s, self.t
         if not (self.accum == 1 and self.world == 1 and x.is_cuda and x.dim() == 2 and not self._capturing and self._micro == 0):
             return None
-        nat = self._nat_ok(x, i)
+        nat = self._nat_ok(x, i) or self._dsmil_mhim_window_ok([x], [label], i)      # (mhimx_dsmil_mhim_window_run: no host read-back either)
         # (round 5) the TransMIL / DSMIL students: their step runs autograd over kernel-backed nodes whose gradient-accumulation nodes belong to
         # the stream they were first run on, so EVERY step of such a shape runs on the trainer's capture stream - eager on the first two
         # visits (the second is the capture's warm-up), captured on the third.  v2 recipe only (a v1 ratio reads a count back).

@@ -1346,6 +1346,20 @@ def dsmil_window_run(cfg, bags, n, host_step, ws, update, x_dtype=L.X_F32):
                                            int(x_dtype)), "mhimx_dsmil_window_run")
 
 
+# ------------------------------------------------------------------------------------------- ragged MHIM(DSMIL) accumulation window
+def dsmil_mhim_window(cfg, bags, n, host_step=0, ws=None, update=False, layout_only=False, x_dtype=L.X_F32):
+    """mhimx_dsmil_mhim_window_layout_of (host arithmetic only) and, unless ``layout_only``, mhimx_dsmil_mhim_window_run: ONE optimiser
+    update (update = False: the summed gradient only) of the full MHIM(DSMIL) model over the n bags of the by-value table ``bags``
+    (_lib.RaggedWindowBag * n: rows, pitch, N, label, this bag's counts and seeds) as one C call.  ``x_dtype``: what the table's rows are
+    (``x_dtype_of`` of the tensors it was made from).  Returns the layout."""
+    lay = L.DsmilMhimWindowLayout()
+    L.check(L.lib().mhimx_dsmil_mhim_window_layout_of(C.byref(cfg), n, bags, C.byref(lay)), "mhimx_dsmil_mhim_window_layout_of")
+    if not layout_only:
+        L.check(L.lib().mhimx_dsmil_mhim_window_run(_stream(), C.byref(cfg), n, bags, int(host_step), ws.data_ptr(), ws.numel(), int(bool(update)),
+                                                    int(x_dtype)), "mhimx_dsmil_mhim_window_run")
+    return lay
+
+
 # ------------------------------------------------------------------------------------------- ragged MHIM accumulation window
 def ragged_window(cfg, bags, n, host_step=0, ws=None, update=False, layout_only=False, x_dtype=L.X_F32):
     """mhimx_ragged_window_layout_of (host arithmetic only) and, unless ``layout_only``, mhimx_ragged_window_run: ONE optimiser update
