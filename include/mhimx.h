@@ -1334,6 +1334,45 @@ int mhimx_cls_metrics(void* stream, const float* logits, int64_t ld, const int64
                       int32_t bin_metric, const int64_t* sample_idx, int64_t B, float* out, void* ws, int64_t ws_bytes);
 
 /* ------------------------------------------------------------------------------------------
+ * Survival validation on the device (csrc/surv.hip)
+ * replaces: train_utils.py:8-37 (nll_loss / NLLSurvLoss), engines/base_engine.py:636-643 (hazards, survival curve, risk score of
+ *           surv_validate), engines/metrics.py:66-104 (ConcordanceIndexCensored = sksurv's concordance_index_censored with
+ *           tied_tol=1e-8, get_surv_metrics) and :35-64 (DeterministicBootStrapper: B resamples, mean / std taken by the caller)
+ * ---------------------------------------------------------------------------------------- */
+#define MHIMX_SURV_MAX_N 16777216     /* rows of one mhimx_surv_nll call */
+#define MHIMX_CINDEX_MAX_N 4194304    /* samples of one mhimx_cindex call */
+#define MHIMX_CINDEX_MAX_B 65535      /* resamples of one call (a grid dimension) */
+#define MHIMX_CINDEX_MAX_BN 134217728 /* B * n of one call: the workspace holds 13 bytes per gathered sample, 1.7 GB at this limit */
+
+/* Survival head of n bags.  logits [n, K] (row pitch ld, 1 <= K <= 16), Y [n] int64 (time bin), c [n] float (censorship: 1 = censored).
+ * h = sigmoid(l), S_k = prod_{m<=k} (1 - h_m), S_pad = [1, S];  risk[r] = -sum_k S_k   (base_engine.py:636-643)
+ * unc = -(1 - c) (log max(S_pad[Y], eps) + log max(h[Y], eps));  cen = -c log max(S_pad[Y + 1], eps)
+ * losses[r] = (1 - alpha)(cen + unc) + alpha unc                                           (train_utils.py:8-25, before its .mean())
+ * The logs are taken in the stable forms log(1 - h) = -softplus(l), log h = -softplus(-l); the clamp is on the quantity, as in the
+ * reference, so a clamped term is the constant log(eps) and has zero gradient.  0 < eps < 1, 0 <= alpha <= 1.
+ * The head is evaluated in fp64 and every output rounded to fp32 once (n x K values: nothing beside the forward that made the logits).
+ * g_logits [n, K] contiguous or NULL: g_scale * d losses[r] / d logits[r, :].
+ * Y outside [0, K): losses[r] = NaN, gradient row 0; risk is still written.  One launch, no workspace. */
+int mhimx_surv_nll(void* stream, const float* logits, int64_t ld, const int64_t* Y, const float* c, int64_t n, int64_t K,
+                   float alpha, float eps, float g_scale, float* risk, float* losses, float* g_logits);
+
+/* Censored concordance index of B resamples in one call  (engines/metrics.py:66-104 + :35-64).
+ * event [n] uint8 (1 = event observed = 1 - censorship), time [n] double, risk [n] float; sample_idx [B, n] int64 (NULL with B == 1).
+ * Pair (i, j) of a resample is comparable iff event_i and (time_j > time_i or (time_j == time_i and !event_j)).
+ * Tied iff |risk_j - risk_i| <= tied_tol, the difference taken in fp32.  Concordant iff not tied and risk_j < risk_i.
+ * out [B, 5] double = {cindex, concordant, discordant, tied_risk, tied_time}.
+ * cindex = (concordant + 0.5 tied_risk) / comparable in fp64; NaN when a resample has no comparable pair.
+ * tied_time = comparable pairs with time_j == time_i.
+ * All counts are 64-bit integers on the device: the result does not depend on launch order.
+ * A resample with an index outside [0, n) reads nothing out of bounds and gets NaN in all five outputs.
+ * Three launches and one memset, no host sync, no allocation (capturable).  ws: 256-byte aligned, mhimx_cindex_ws_bytes(n, B) bytes;
+ * n <= MHIMX_CINDEX_MAX_N, B <= MHIMX_CINDEX_MAX_B, B * n <= MHIMX_CINDEX_MAX_BN - larger inputs are refused before any launch (and by the
+ * workspace query, which then returns -1). */
+int64_t mhimx_cindex_ws_bytes(int64_t n, int64_t B);
+int mhimx_cindex(void* stream, const uint8_t* event, const double* time, const float* risk, int64_t n, const int64_t* sample_idx,
+                 int64_t B, float tied_tol, double* out, void* ws, int64_t ws_bytes);
+
+/* ------------------------------------------------------------------------------------------
  * Communicator handle: the data-parallel update's ONE collective behind the C boundary.
  * replaces: DistributedDataParallel's bucketed all-reduce (options.py:287, engines/base_engine.py:112-139); RCCL is loaded at run
  * time (dlopen).  unique_id: 128 bytes made on rank 0 and handed to every rank by the host (any side channel); init is collective.

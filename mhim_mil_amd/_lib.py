@@ -252,6 +252,11 @@ X_F32, X_F16, X_BF16 = 0, 1, 2   # MHIMX_X_*: the element type of the bags' rows
 
 TOPK_MAX_K = 4096            # MHIMX_TOPK_MAX_K
 
+SURV_MAX_N = 16777216        # MHIMX_SURV_MAX_N
+CINDEX_MAX_N = 4194304       # MHIMX_CINDEX_MAX_N
+CINDEX_MAX_B = 65535         # MHIMX_CINDEX_MAX_B
+CINDEX_MAX_BN = 134217728    # MHIMX_CINDEX_MAX_BN
+
 
 class TopkSeg(C.Structure):
     """mhimx_topk_seg: segment b of a mhimx_topk_many call is score[row0 .. row0 + N)."""
@@ -417,6 +422,9 @@ SYMBOLS = {
     "mhimx_reduce_flush": (C.c_int, [_P, _P]),
     "mhimx_cls_metrics_ws_bytes": (C.c_int64, [_I64, _I64, _I64]),
     "mhimx_cls_metrics": (C.c_int, [_P, _P, _I64, _P, _I64, _I64, _I32, _P, _I64, _P, _P, _I64]),
+    "mhimx_surv_nll": (C.c_int, [_P, _P, _I64, _P, _P, _I64, _I64, _F, _F, _F, _P, _P, _P]),
+    "mhimx_cindex_ws_bytes": (C.c_int64, [_I64, _I64]),
+    "mhimx_cindex": (C.c_int, [_P, _P, _P, _P, _I64, _P, _I64, _F, _P, _P, _I64]),
     "mhimx_colsum": (C.c_int, [_P, _P, _I64, _I64, _P, _I32, _P, _I64]),
     "mhimx_head_fwd_bwd": (C.c_int, [_P, _P, _P, _P, _P, _P, _I64, _I64, _F, _F, _F, _F, _P, _P, _P, _P, _P, _I32, _P, _P]),
     "mhimx_adam_ema": (C.c_int, [_P, _P, _P, _P, _P, _P, _I64, _I64, _I64, _F, _F, _F, _F, _F, _F, _F, _I32, _P, _P, _I64]),

@@ -941,6 +941,58 @@ def cls_metrics(logits, labels, n_classes, bin_metric=False, sample_idx=None):
     return out
 
 
+# ------------------------------------------------------------------------------------------------ survival validation
+CINDEX_KEYS = ("cindex", "concordant", "discordant", "tied_risk", "tied_time")
+
+
+def surv_nll(logits, Y, c, alpha=0.0, eps=1e-7, g_scale=None):
+    """Survival head of n bags (mhimx_surv_nll, one launch).  logits [n, K] fp32 (unit inner stride, any row pitch >= K), Y [n] int64
+    (time bin), c [n] fp32 (censorship) -> (risk [n], losses [n]) and, with ``g_scale``, g_logits [n, K] = g_scale * d losses / d logits.
+    A Y outside [0, K) gives a NaN loss and a zero gradient row."""
+    if not (torch.is_tensor(logits) and logits.is_cuda and logits.dtype == torch.float32 and logits.dim() == 2):
+        raise L.MhimxError("surv_nll: logits must be a GPU fp32 tensor [n, K] (the HIP path has no CPU fallback)")
+    n, K = logits.shape
+    if not (1 <= K <= 16 and 1 <= n <= L.SURV_MAX_N):
+        raise L.MhimxError(f"surv_nll: logits [{n}, {K}]: 1 <= K <= 16 time bins, 1 <= n <= {L.SURV_MAX_N} rows")
+    if not ((K == 1 or logits.stride(1) == 1) and (n == 1 or logits.stride(0) >= K)):
+        raise L.MhimxError(f"surv_nll: logits strides {tuple(logits.stride())}: rows of K contiguous values, row pitch >= K")
+    _chk(Y, torch.int64, "Y"); _chk(c, torch.float32, "c")
+    if Y.numel() != n or c.numel() != n or Y.device != logits.device or c.device != logits.device:
+        raise L.MhimxError(f"surv_nll: {Y.numel()} bins and {c.numel()} censorships for {n} rows (all on the logits' device)")
+    if not (0.0 < eps < 1.0 and 0.0 <= alpha <= 1.0):
+        raise L.MhimxError(f"surv_nll: eps={eps} must be in (0, 1), alpha={alpha} in [0, 1]")
+    risk, losses = torch.empty(n, device=logits.device), torch.empty(n, device=logits.device)
+    g = None if g_scale is None else torch.empty((n, K), device=logits.device)
+    L.check(L.lib().mhimx_surv_nll(_stream(), _p(logits), logits.stride(0) if n > 1 else K, _p(Y), _p(c), n, K, float(alpha), float(eps),
+                                   0.0 if g_scale is None else float(g_scale), _p(risk), _p(losses), _p(g)), "mhimx_surv_nll")
+    return (risk, losses) if g is None else (risk, losses, g)
+
+
+def cindex(event, time, risk, sample_idx=None, tied_tol=1e-8):
+    """Censored concordance index on the device (mhimx_cindex).  event [n] uint8 / bool (1 = event observed), time [n] fp64, risk [n] fp32
+    -> out [B, 5] fp64 in the order CINDEX_KEYS; ``sample_idx`` [B, n] int64 evaluates B bootstrap resamples in the same three launches
+    (B = 1 without).  A resample without a comparable pair has a NaN cindex."""
+    if not all(torch.is_tensor(t) for t in (event, time, risk)):
+        raise L.MhimxError("cindex: event, time and risk must be tensors")
+    if event.dtype == torch.bool:
+        event = event.view(torch.uint8)
+    _chk(event, torch.uint8, "event"); _chk(time, torch.float64, "time"); _chk(risk, torch.float32, "risk")
+    _chk(sample_idx, torch.int64, "sample_idx")
+    n = risk.numel()
+    if event.numel() != n or time.numel() != n or event.device != risk.device or time.device != risk.device:
+        raise L.MhimxError(f"cindex: {event.numel()} events and {time.numel()} times for {n} risks (all on one device)")
+    if sample_idx is not None and (sample_idx.dim() != 2 or sample_idx.shape[1] != n or sample_idx.device != risk.device):
+        raise L.MhimxError(f"cindex: sample_idx {tuple(sample_idx.shape)} must be [B, {n}] on the risks' device")
+    B = 1 if sample_idx is None else sample_idx.shape[0]
+    need = L.lib().mhimx_cindex_ws_bytes(n, B)
+    L.check(0 if need > 0 else -1, "mhimx_cindex_ws_bytes")
+    out = torch.empty((B, 5), device=risk.device, dtype=torch.float64)
+    ws = torch.empty(need, device=risk.device, dtype=torch.uint8)
+    L.check(L.lib().mhimx_cindex(_stream(), _p(event), _p(time), _p(risk), n, _p(sample_idx), B, float(tied_tol), _p(out), _p(ws), need),
+            "mhimx_cindex")
+    return out
+
+
 # ------------------------------------------------------------------------------------------- native calls: the shared host pieces
 def workspace(cache, key, total, dev, slack=1.25):
     """The uint8 workspace of a native call that needs ``total`` bytes on ``dev``.  Inside a stream capture: a fresh one (the graph's
