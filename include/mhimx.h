@@ -1373,6 +1373,64 @@ int mhimx_cindex(void* stream, const uint8_t* event, const double* time, const f
                  int64_t B, float tied_tol, double* out, void* ws, int64_t ws_bytes);
 
 /* ------------------------------------------------------------------------------------------
+ * Survival training in the native train calls: the discrete-time NLL survival head in place of the cross entropy
+ * replaces: engines/base_engine.py:395-441 (surv_train: the accumulation window of a survival dataset - every bag's loss divided by
+ *           the window's length, the gradients added up, one optimizer.step()) around engines/common_mil.py:14-48 (forward_func) with
+ *           the criterion of train_utils.py:8-37 (NLLSurvLoss(alpha)) instead of nn.CrossEntropyLoss.
+ * The model does not change: C = n_classes is the number of time bins (the reference ships 4), everything up to the bag logits is the
+ * classification call's - the same launches, the same bits.  The label is a pair: the bag table's label_dev carries the time bin Y
+ * (int64 [1]), the survival description the censorship flag c (fp32 [1], 1 = censored).  Only the head's criterion differs:
+ *   nll = (1 - alpha)(cen + unc) + alpha unc of mhimx_surv_nll's comment, evaluated by the SAME device function (csrc/surv_dev.hpp:
+ *   fp64, every output rounded to fp32 once): loss, risk and d loss / d logits out of a train call are, bit for bit, what
+ *   mhimx_surv_nll(g_scale = main_alpha * inv_accum, the product taken in fp32) gives on the logits that call wrote.
+ * A Y outside [0, C): NaN loss, zero survival gradient row (mhimx_surv_nll's rule; the cross-entropy calls give a NaN gradient).
+ * MHIMX_VERSION stays 620: additions only - no existing entry point or struct changed shape.
+ * ---------------------------------------------------------------------------------------- */
+
+/* mhimx_head_fwd_bwd with the survival criterion in place of the cross entropy; one launch.
+ * replaces: mhim.py:97,371 (predictor), train_utils.py:8-37, losses.py:26-45, base_engine.py:395-441 (the loss line of surv_train).
+ *  logits[C] = Wp z + bp;  nll = NLLSurv(logits, Y, c; surv_alpha, surv_eps);  cl = SoftTargetCE against t (t may be NULL)
+ *  loss = (main_alpha*nll + aux_alpha*cl)/accum;  out: losses[3] = {loss*accum, nll, cl}; risk[1] = -sum_k S_k (or NULL)
+ *  g_z[E], d_wp[C,E], d_bp[C] (of `loss`; accumulate = 1 adds to d_wp / d_bp).  The predictor, the distillation term and the gradient
+ *  assembly are mhimx_head_fwd_bwd's code: logits are bit-equal to that call's, and the gradients to those of its autograd form fed
+ *  with mhimx_surv_nll's g_logits.
+ * Refused before the launch: a null label_dev (the autograd form is mhimx_head_fwd_bwd's) or censor_dev, surv_alpha outside [0, 1],
+ * surv_eps outside (0, 1), C > 16, a bag-batched launch (one bag per launch). */
+int mhimx_head_surv_fwd_bwd(void* stream, const float* z, const float* t, const float* wp, const float* bp,
+                            const int64_t* label_dev, const float* censor_dev, int64_t E, int64_t C, float temp_t,
+                            float main_alpha, float aux_alpha, float inv_accum, float surv_alpha, float surv_eps,
+                            float* logits, float* losses, float* risk, float* g_z, float* d_wp, float* d_bp, int32_t accumulate);
+
+typedef struct {
+  float alpha, eps;                            /* NLLSurvLoss(alpha), train_utils.py:8 eps */
+  const float* censor_dev[MHIMX_INFER_MAX];    /* fp32 [1] per bag, on the device          */
+  float* risk;                                 /* optional float [n_bags] on the device     */
+} mhimx_surv_spec;
+
+/* mhimx_pure_window_run_x (the teacher-free ABMIL stage) with the survival head: the same nine launches, pw_head_kernel in its
+ * survival form.  replaces: engines/base_engine.py:395-441 around engines/common_mil.py:14-48 (`pure`), criterion train_utils.py:8-37.
+ * layout.losses per bag = {main_alpha * nll, nll, 0}; surv->risk[b] = the bag's risk.  Everything mhimx_pure_window_run states holds:
+ * enqueue-only and capturable; no allocation, synchronisation or copy; every sum in a fixed order, the same bits on two runs; what a
+ * bag writes depends on that bag alone.  Checks: mhimx_pure_window_run_x's, then per bag a non-null surv->censor_dev[b], alpha in
+ * [0, 1], eps in (0, 1) - all before any device call, mhimx_last_error names the bag.  surv NULL is refused (that is the _x call).
+ * One bag is a window of one (n_bags = 1): there is no survival form of mhimx_pure_step_run. */
+int mhimx_pure_window_run_surv(void* stream, const mhimx_step_cfg* cfg, int32_t n_bags, const mhimx_pure_window_bag* bags,
+                               int64_t host_step, void* ws, int64_t ws_bytes, int32_t update, int32_t x_dtype,
+                               const mhimx_surv_spec* surv);
+
+/* mhimx_ragged_window_run_x (the full MHIM(ABMIL) model) with the survival head: the same launches, every bag's head launch is
+ * mhimx_head_surv_fwd_bwd (loss scale 1 / n_bags, the distillation term against the teacher's row as before).
+ * replaces: engines/base_engine.py:395-441 around engines/common_mil.py:14-48, criterion train_utils.py:8-37.
+ * layout.losses per bag = {main_alpha * nll + aux_alpha * cl, nll, cl, -}; surv->risk[b] = the bag's risk.  Everything
+ * mhimx_ragged_window_run states holds (enqueue-only, capturable, no allocation / sync / copy, fixed summation order, the same bits on
+ * two runs).  Checks: mhimx_ragged_window_run_x's, then the survival ones of mhimx_pure_window_run_surv.
+ * One bag is a window of one, and a window of same-shaped bags is a ragged window: there is no survival form of mhimx_step_run or
+ * mhimx_window_run. */
+int mhimx_ragged_window_run_surv(void* stream, const mhimx_step_cfg* cfg, int32_t n_bags, const mhimx_ragged_window_bag* bags,
+                                 int64_t host_step, void* ws, int64_t ws_bytes, int32_t update, int32_t x_dtype,
+                                 const mhimx_surv_spec* surv);
+
+/* ------------------------------------------------------------------------------------------
  * Communicator handle: the data-parallel update's ONE collective behind the C boundary.
  * replaces: DistributedDataParallel's bucketed all-reduce (options.py:287, engines/base_engine.py:112-139); RCCL is loaded at run
  * time (dlopen).  unique_id: 128 bytes made on rank 0 and handed to every rank by the host (any side channel); init is collective.

@@ -360,6 +360,12 @@ class RaggedWindowLayout(C.Structure):
                                         "z_teacher", "z_student")] + [("row0", C.c_int64 * RAGGED_WINDOW_MAX)]
 
 
+class SurvSpec(C.Structure):
+    """mhimx_surv_spec: the survival head of mhimx_pure_window_run_surv / mhimx_ragged_window_run_surv - NLLSurvLoss(alpha), the clamp, every
+    bag's censorship flag (fp32 [1] on the device), the optional per-bag risks (float [n_bags] on the device)."""
+    _fields_ = [("alpha", C.c_float), ("eps", C.c_float), ("censor_dev", C.c_void_p * INFER_MAX), ("risk", C.c_void_p)]
+
+
 SYMBOLS = {
     "mhimx_last_error": (C.c_char_p, []),
     "mhimx_version": (C.c_int, []),
@@ -427,6 +433,7 @@ SYMBOLS = {
     "mhimx_cindex": (C.c_int, [_P, _P, _P, _P, _I64, _P, _I64, _F, _P, _P, _I64]),
     "mhimx_colsum": (C.c_int, [_P, _P, _I64, _I64, _P, _I32, _P, _I64]),
     "mhimx_head_fwd_bwd": (C.c_int, [_P, _P, _P, _P, _P, _P, _I64, _I64, _F, _F, _F, _F, _P, _P, _P, _P, _P, _I32, _P, _P]),
+    "mhimx_head_surv_fwd_bwd": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _I64, _I64, _F, _F, _F, _F, _F, _F, _P, _P, _P, _P, _P, _P, _I32]),
     "mhimx_adam_ema": (C.c_int, [_P, _P, _P, _P, _P, _P, _I64, _I64, _I64, _F, _F, _F, _F, _F, _F, _F, _I32, _P, _P, _I64]),
     "mhimx_bmm_chain": (C.c_int, [_P, C.POINTER(BmmStep), _I32, _I32, _P]),
     "mhimx_optim_step": (C.c_int, [_P, C.POINTER(OptimArgs)]),
@@ -491,6 +498,7 @@ SYMBOLS = {
     "mhimx_pure_window_layout_of": (C.c_int, [C.POINTER(StepCfg), _I32, _P, C.POINTER(PureWindowLayout)]),
     "mhimx_pure_window_run": (C.c_int, [_P, C.POINTER(StepCfg), _I32, _P, _I64, _P, _I64, _I32]),
     "mhimx_pure_window_run_x": (C.c_int, [_P, C.POINTER(StepCfg), _I32, _P, _I64, _P, _I64, _I32, _I32]),
+    "mhimx_pure_window_run_surv": (C.c_int, [_P, C.POINTER(StepCfg), _I32, _P, _I64, _P, _I64, _I32, _I32, C.POINTER(SurvSpec)]),
     "mhimx_dsmil_window_layout_of": (C.c_int, [C.POINTER(DsmilTrainCfg), _I32, _P, C.POINTER(DsmilWindowLayout)]),
     "mhimx_dsmil_window_run": (C.c_int, [_P, C.POINTER(DsmilTrainCfg), _I32, _P, _I64, _P, _I64, _I32, _I32]),
     "mhimx_dsmil_mhim_window_layout_of": (C.c_int, [C.POINTER(DsmilMhimCfg), _I32, _P, C.POINTER(DsmilMhimWindowLayout)]),
@@ -499,6 +507,7 @@ SYMBOLS = {
     "mhimx_ragged_window_layout_of": (C.c_int, [C.POINTER(StepCfg), _I32, _P, C.POINTER(RaggedWindowLayout)]),
     "mhimx_ragged_window_run": (C.c_int, [_P, C.POINTER(StepCfg), _I32, _P, _I64, _P, _I64, _I32]),
     "mhimx_ragged_window_run_x": (C.c_int, [_P, C.POINTER(StepCfg), _I32, _P, _I64, _P, _I64, _I32, _I32]),
+    "mhimx_ragged_window_run_surv": (C.c_int, [_P, C.POINTER(StepCfg), _I32, _P, _I64, _P, _I64, _I32, _I32, C.POINTER(SurvSpec)]),
 }
 
 _lib = None

@@ -3,6 +3,7 @@
 #include <math.h>
 
 #include "common.hpp"
+#include "surv_dev.hpp"
 
 namespace mhimx {
 
@@ -35,7 +36,14 @@ MHIMX_DEV float mul_rounded(float a, float b) {
   return a * b;
 }
 
+// the criterion on the logits is a compile-time parameter of the two head kernels below: the trailing pack SURV.  Empty: the cross
+// entropy - the kernels, kernel arguments and instructions of before.  One HeadSurv: the discrete-time survival NLL (surv_dev.hpp) on the
+// same logits.  The predictor, the distillation term and the gradient assembly are one text for both.
+template <class T>
+MHIMX_DEV const T& head_surv_of(const T& sv) { return sv; }
+
 // One block.  C <= 16 classes.
+template <class... SURV>
 __global__ __launch_bounds__(HEAD_THREADS) void head_kernel(const float* __restrict__ z, const float* __restrict__ t,
                                                             const float* __restrict__ wp, const float* __restrict__ bp,
                                                             const int64_t* __restrict__ label, int E, int C, float temp_t,
@@ -44,7 +52,7 @@ __global__ __launch_bounds__(HEAD_THREADS) void head_kernel(const float* __restr
                                                             float* __restrict__ g_z, float* __restrict__ d_wp,
                                                             float* __restrict__ d_bp, int accumulate,
                                                             const float* __restrict__ g_logits_in,
-                                                            const float* __restrict__ g_cl_in) {
+                                                            const float* __restrict__ g_cl_in, SURV... surv) {
   __shared__ float red[4];
   __shared__ float lg[16], gl[16];
   const int tid = threadIdx.x;
@@ -58,7 +66,20 @@ __global__ __launch_bounds__(HEAD_THREADS) void head_kernel(const float* __restr
   __syncthreads();
   // cross entropy on the logits (criterion = nn.CrossEntropyLoss, base_engine.py:99)
   float ce = 0.f;
-  if (label) {
+  if constexpr (sizeof...(SURV) == 1) {
+    // discrete-time survival NLL on the logits (criterion = NLLSurvLoss, train_utils.py:8-37): surv_dev.hpp's row, gradient scale
+    // main_alpha / accum.  Thread 0 alone: it is the one that writes the losses
+    if (tid == 0) {
+      const HeadSurv& sv = head_surv_of(surv...);
+      float l[SURV_MAXK], g[SURV_MAXK], rk;
+#pragma unroll
+      for (int c = 0; c < SURV_MAXK; ++c) l[c] = c < C ? lg[c] : 0.f;
+      surv_row<SURV_MAXK>(l, C, label[0], sv.censor[0], sv.alpha, sv.eps, main_alpha * inv_accum, true, rk, ce, g);
+#pragma unroll
+      for (int c = 0; c < SURV_MAXK; ++c) gl[c] = g[c];
+      if (sv.risk) sv.risk[0] = rk;
+    }
+  } else if (label) {
     float mx = -INFINITY;
     for (int c = 0; c < C; ++c) mx = fmaxf(mx, lg[c]);
     float den = 0.f;
@@ -115,7 +136,8 @@ __global__ __launch_bounds__(HEAD_THREADS) void head_kernel(const float* __restr
 // 2 + C + 3 block reductions of two barriers each.  Here every input is requested at entry (registers), and the block reductions are
 // batched: {C logit sums, max z, max t} -> {sum e^z, sum e^t} -> {soft-target CE}: three barrier pairs.  Same sums in the same order
 // (wave_sum, then the four wave values left to right): the bits of head_kernel.
-template <int Q>
+// (the survival form is one bag per launch: the bag batch it is handed is the empty one)
+template <int Q, class... SURV>
 __global__ __launch_bounds__(HEAD_THREADS) void head_fast_kernel(const float* __restrict__ z, const float* __restrict__ t,
                                                                  const float* __restrict__ wp, const float* __restrict__ bp,
                                                                  const int64_t* __restrict__ label, int E, int C, float temp_t,
@@ -124,7 +146,7 @@ __global__ __launch_bounds__(HEAD_THREADS) void head_fast_kernel(const float* __
                                                                  float* __restrict__ g_z, float* __restrict__ d_wp,
                                                                  float* __restrict__ d_bp, int accumulate,
                                                                  const float* __restrict__ g_logits_in,
-                                                                 const float* __restrict__ g_cl_in, BagBatch bb) {
+                                                                 const float* __restrict__ g_cl_in, BagBatch bb, SURV... surv) {
   __shared__ float red[8][4];
   if (blockIdx.z) {      // (common.hpp: one workgroup per bag of an accumulation window; the label list is one of the moving ranges)
     MHIMX_BAG(z); MHIMX_BAG(t); MHIMX_BAG(label); MHIMX_BAG(logits); MHIMX_BAG(losses); MHIMX_BAG(g_z); MHIMX_BAG(d_wp); MHIMX_BAG(d_bp);
@@ -147,6 +169,9 @@ __global__ __launch_bounds__(HEAD_THREADS) void head_fast_kernel(const float* __
     }
   }
   const int y = label ? (int)label[0] : 0;
+  [[maybe_unused]] int64_t y64 = 0;
+  [[maybe_unused]] float cens = 0.f;
+  if constexpr (sizeof...(SURV) == 1) { y64 = label[0]; cens = head_surv_of(surv...).censor[0]; }
   float bpv[4], glin[4], dbp_old[4];
 #pragma unroll
   for (int c = 0; c < 4; ++c) {
@@ -182,7 +207,13 @@ __global__ __launch_bounds__(HEAD_THREADS) void head_fast_kernel(const float* __
   const float tmx = aux ? fmaxf(fmaxf(red[5][0], red[5][1]), fmaxf(red[5][2], red[5][3])) : 0.f;
   // cross entropy on the logits (every thread: C <= 4 values)
   float ce = 0.f, gl[4] = {0.f, 0.f, 0.f, 0.f};
-  if (label) {
+  if constexpr (sizeof...(SURV) == 1) {
+    // discrete-time survival NLL on the logits (every thread: C <= 4 values; surv_dev.hpp's row, gradient scale main_alpha / accum)
+    const HeadSurv& sv = head_surv_of(surv...);
+    float rk;
+    surv_row<4>(lg, C, y64, cens, sv.alpha, sv.eps, main_alpha * inv_accum, true, rk, ce, gl);
+    if (tid == 0 && sv.risk) sv.risk[0] = rk;
+  } else if (label) {
     float mx = -INFINITY;
 #pragma unroll
     for (int c = 0; c < 4; ++c) if (c < C) mx = fmaxf(mx, lg[c]);
@@ -496,8 +527,34 @@ extern "C" int mhimx_head_fwd_bwd(void* stream, const float* z, const float* t, 
   else if (cur_batch().n > 0)
     return fail(-1, "head: a bag-batched launch takes the short-chain head (C <= 4, E <= 1024)");
   else
-  hipLaunchKernelGGL(head_kernel, dim3(1), dim3(HEAD_THREADS), 0, (hipStream_t)stream, z, t, wp, bp, label_dev, (int)E, (int)C,
+  hipLaunchKernelGGL(head_kernel<>, dim3(1), dim3(HEAD_THREADS), 0, (hipStream_t)stream, z, t, wp, bp, label_dev, (int)E, (int)C,
                      temp_t, main_alpha, aux_alpha, inv_accum, logits, losses, g_z, d_wp, d_bp, accumulate, g_logits_in, g_cl_in);
+  MHIMX_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int mhimx_head_surv_fwd_bwd(void* stream, const float* z, const float* t, const float* wp, const float* bp,
+                                       const int64_t* label_dev, const float* censor_dev, int64_t E, int64_t C, float temp_t,
+                                       float main_alpha, float aux_alpha, float inv_accum, float surv_alpha, float surv_eps,
+                                       float* logits, float* losses, float* risk, float* g_z, float* d_wp, float* d_bp,
+                                       int32_t accumulate) {
+  MHIMX_CHECK_ARG(z && wp && logits && losses && g_z, "head_surv: null args");
+  MHIMX_CHECK_ARG(label_dev, "head_surv: null label (the autograd form of the head is mhimx_head_fwd_bwd's: the criterion does not enter it)");
+  MHIMX_CHECK_ARG(censor_dev, "head_surv: a label needs its censorship flag (null censor_dev)");
+  MHIMX_CHECK_ARG(C > 0 && C <= SURV_MAXK && E > 0, "head_surv: bad dims (1 <= C <= %d time bins)", SURV_MAXK);
+  MHIMX_CHECK_ARG(surv_alpha >= 0.f && surv_alpha <= 1.f, "head_surv: alpha=%g must be in [0, 1]", (double)surv_alpha);
+  MHIMX_CHECK_ARG(surv_eps > 0.f && surv_eps < 1.f, "head_surv: eps=%g must be in (0, 1)", (double)surv_eps);
+  if (cur_batch().n > 0) return fail(-1, "head_surv: no bag-batched form (one bag per launch)");
+  const HeadSurv sv = {censor_dev, surv_alpha, surv_eps, risk};
+  if (C <= 4 && E <= 2 * HEAD_THREADS)
+    hipLaunchKernelGGL((head_fast_kernel<2, HeadSurv>), dim3(1), dim3(HEAD_THREADS), 0, (hipStream_t)stream, z, t, wp, bp, label_dev, (int)E, (int)C,
+                       temp_t, main_alpha, aux_alpha, inv_accum, logits, losses, g_z, d_wp, d_bp, accumulate, nullptr, nullptr, BagBatch{}, sv);
+  else if (C <= 4 && E <= 4 * HEAD_THREADS)
+    hipLaunchKernelGGL((head_fast_kernel<4, HeadSurv>), dim3(1), dim3(HEAD_THREADS), 0, (hipStream_t)stream, z, t, wp, bp, label_dev, (int)E, (int)C,
+                       temp_t, main_alpha, aux_alpha, inv_accum, logits, losses, g_z, d_wp, d_bp, accumulate, nullptr, nullptr, BagBatch{}, sv);
+  else
+    hipLaunchKernelGGL(head_kernel<HeadSurv>, dim3(1), dim3(HEAD_THREADS), 0, (hipStream_t)stream, z, t, wp, bp, label_dev, (int)E, (int)C, temp_t,
+                       main_alpha, aux_alpha, inv_accum, logits, losses, g_z, d_wp, d_bp, accumulate, nullptr, nullptr, sv);
   MHIMX_LAUNCH_CHECK();
   return 0;
 }

@@ -29,6 +29,7 @@
 #include <string.h>
 
 #include "infer_tab.hpp"
+#include "surv_dev.hpp"
 
 namespace mhimx {
 
@@ -42,16 +43,23 @@ constexpr int RED_JOBS = 6, RED_T = 256, RED_BLOCKS = 256, RED_WIDE_G = 64;
 typedef __bf16 pw_b4 __attribute__((ext_vector_type(4)));
 
 struct PwLabels { const int64_t* p[MHIMX_INFER_MAX]; };
+// the survival head of mhimx_pure_window_run_surv: every bag's censorship flag, NLLSurvLoss(alpha), the clamp, risk [n_bags] or NULL
+struct PwSurv { const float* censor[MHIMX_INFER_MAX]; float alpha, eps; float* risk; };
+template <class T>
+MHIMX_DEV const T& pw_surv_of(const T& sv) { return sv; }
 
 // ------------------------------------------------------------------------------------------------ 4. merge + head + CE + their gradients
 // blockIdx.x = bag.  infer_finalize_kernel's merge (partials in index order) and predictor, then the backward of the head:
 // g_logits = main_alpha (softmax - onehot) / n, g_z = Wp^T g_logits, zg = z . g_z, the bag's d Wp / d bp partial.
+// The criterion on the logits is the trailing pack SURV.  Empty: the cross entropy - the kernel, kernel arguments and instructions of
+// before.  One PwSurv: the discrete-time survival NLL of surv_dev.hpp (mhimx_pure_window_run_surv); everything around it is one text.
+template <class... SURV>
 __global__ __launch_bounds__(RG_FIN_T) void pw_head_kernel(InferTab tab, PwLabels lab, const float* __restrict__ pm, const float* __restrict__ pl,
                                                          const float* __restrict__ pz, const float* __restrict__ wp, const float* __restrict__ bp,
                                                          int C, float main_alpha, float inv_n, float* __restrict__ logits,
                                                          float* __restrict__ losses, float* __restrict__ z_out, float* __restrict__ stats,
                                                          float* __restrict__ g_z, float* __restrict__ zg, float* __restrict__ dwp_part,
-                                                         float* __restrict__ dbp_part) {
+                                                         float* __restrict__ dbp_part, SURV... surv) {
   __shared__ float red[8];
   __shared__ float wgt[RG_FIN_T];
   __shared__ float zs[IE];
@@ -92,7 +100,27 @@ __global__ __launch_bounds__(RG_FIN_T) void pw_head_kernel(InferTab tab, PwLabel
     }
   }
   __syncthreads();
-  if (tid == 0) {
+  if constexpr (sizeof...(SURV) == 1) {
+    if (tid == 0) {
+      // NLLSurvLoss on one row (train_utils.py:8-37; a bin outside [0, C): NaN loss, zero gradient row), gradient scale main_alpha / n
+      const PwSurv& sv = pw_surv_of(surv...);
+      const float* cens = sv.censor[0];
+      RG_PICK(cens, sv.censor, bag)
+      float l[PW_MAXC], g[PW_MAXC], rk, nll;
+#pragma unroll
+      for (int c = 0; c < PW_MAXC; ++c) l[c] = c < C ? lg[c] : 0.f;
+      surv_row<PW_MAXC>(l, C, label[0], cens[0], sv.alpha, sv.eps, main_alpha * inv_n, true, rk, nll, g);
+      losses[3 * bag] = main_alpha * nll;
+      losses[3 * bag + 1] = nll;
+      losses[3 * bag + 2] = 0.f;
+      if (sv.risk) sv.risk[bag] = rk;
+#pragma unroll
+      for (int c = 0; c < PW_MAXC; ++c) {
+        gl[c] = g[c];
+        if (c < C) dbp_part[C * bag + c] = g[c];
+      }
+    }
+  } else if (tid == 0) {
     // torch.nn.CrossEntropyLoss on one row (a label outside [0, C): NaN, where torch raises)
     float cm = lg[0];
     for (int c = 1; c < C; ++c) cm = fmaxf(cm, lg[c]);
@@ -569,8 +597,22 @@ extern "C" int mhimx_pure_window_run(void* stream, const mhimx_step_cfg* cfg, in
 
 extern "C" int mhimx_pure_window_run_x(void* stream, const mhimx_step_cfg* cfg, int32_t n_bags, const mhimx_pure_window_bag* bags,
                                        int64_t host_step, void* ws, int64_t ws_bytes, int32_t update, int32_t x_dtype) {
-  using namespace mhimx;
+  return mhimx::pure_window_run(stream, cfg, n_bags, bags, host_step, ws, ws_bytes, update, x_dtype, nullptr);
+}
+
+extern "C" int mhimx_pure_window_run_surv(void* stream, const mhimx_step_cfg* cfg, int32_t n_bags, const mhimx_pure_window_bag* bags,
+                                          int64_t host_step, void* ws, int64_t ws_bytes, int32_t update, int32_t x_dtype,
+                                          const mhimx_surv_spec* surv) {
+  MHIMX_CHECK_ARG(surv, "pure_window: null survival description (mhimx_pure_window_run_x is the classification call)");
+  return mhimx::pure_window_run(stream, cfg, n_bags, bags, host_step, ws, ws_bytes, update, x_dtype, surv);
+}
+
+// the one body of mhimx_pure_window_run(_x) (surv NULL: cross entropy) and mhimx_pure_window_run_surv
+int mhimx::pure_window_run(void* stream, const mhimx_step_cfg* cfg, int32_t n_bags, const mhimx_pure_window_bag* bags, int64_t host_step, void* ws,
+                           int64_t ws_bytes, int32_t update, int32_t x_dtype, const mhimx_surv_spec* surv) {
   if (int r = check_pw(cfg, n_bags, bags, x_dtype)) return r;
+  if (surv)
+    if (int r = surv_spec_check("pure_window", n_bags, surv)) return r;
   for (int b = 0; b < n_bags; ++b) {
     MHIMX_CHECK_ARG(bags[b].X && aligned16(bags[b].X), "pure_window: bag %d: null or unaligned rows", b);
     MHIMX_CHECK_ARG(bags[b].label_dev, "pure_window: bag %d: null label", b);
@@ -612,8 +654,16 @@ extern "C" int mhimx_pure_window_run_x(void* stream, const mhimx_step_cfg* cfg, 
   {
     PwLabels lab = {};
     for (int b = 0; b < n_bags; ++b) lab.p[b] = bags[b].label_dev;
-    hipLaunchKernelGGL(pw_head_kernel, dim3((unsigned)n_bags), dim3(RG_FIN_T), 0, st, tab, lab, pm, pl, pz, S.wp, S.bp, C, c.main_alpha,
-                       1.f / (float)n_bags, F(w.logits), F(w.losses), F(w.z), F(w.stats), F(w.g_z), F(w.zg), F(w.dwp_part), F(w.dbp_part));
+    if (surv) {
+      PwSurv sv = {};
+      for (int b = 0; b < n_bags; ++b) sv.censor[b] = surv->censor_dev[b];
+      sv.alpha = surv->alpha; sv.eps = surv->eps; sv.risk = surv->risk;
+      hipLaunchKernelGGL(pw_head_kernel<PwSurv>, dim3((unsigned)n_bags), dim3(RG_FIN_T), 0, st, tab, lab, pm, pl, pz, S.wp, S.bp, C, c.main_alpha,
+                         1.f / (float)n_bags, F(w.logits), F(w.losses), F(w.z), F(w.stats), F(w.g_z), F(w.zg), F(w.dwp_part), F(w.dbp_part), sv);
+    } else {
+      hipLaunchKernelGGL(pw_head_kernel<>, dim3((unsigned)n_bags), dim3(RG_FIN_T), 0, st, tab, lab, pm, pl, pz, S.wp, S.bp, C, c.main_alpha,
+                         1.f / (float)n_bags, F(w.logits), F(w.losses), F(w.z), F(w.stats), F(w.g_z), F(w.zg), F(w.dwp_part), F(w.dbp_part));
+    }
     MHIMX_LAUNCH_CHECK();
   }
   // ---- 5. pool backward over the row space

@@ -52,6 +52,7 @@
 
 #include "infer_tab.hpp"
 #include "step_mid.hpp"
+#include "surv_dev.hpp"
 
 namespace mhimx {
 
@@ -354,7 +355,22 @@ extern "C" int mhimx_ragged_window_run(void* stream, const mhimx_step_cfg* cfg, 
 
 extern "C" int mhimx_ragged_window_run_x(void* stream, const mhimx_step_cfg* cfg, int32_t n_bags, const mhimx_ragged_window_bag* bags,
                                          int64_t host_step, void* ws, int64_t ws_bytes, int32_t update, int32_t x_dtype) {
+  return mhimx::ragged_window_run(stream, cfg, n_bags, bags, host_step, ws, ws_bytes, update, x_dtype, nullptr);
+}
+
+extern "C" int mhimx_ragged_window_run_surv(void* stream, const mhimx_step_cfg* cfg, int32_t n_bags, const mhimx_ragged_window_bag* bags,
+                                            int64_t host_step, void* ws, int64_t ws_bytes, int32_t update, int32_t x_dtype,
+                                            const mhimx_surv_spec* surv) {
+  MHIMX_CHECK_ARG(surv, "ragged_window: null survival description (mhimx_ragged_window_run_x is the classification call)");
+  return mhimx::ragged_window_run(stream, cfg, n_bags, bags, host_step, ws, ws_bytes, update, x_dtype, surv);
+}
+
+// the one body of mhimx_ragged_window_run(_x) (surv NULL: cross entropy) and mhimx_ragged_window_run_surv
+int mhimx::ragged_window_run(void* stream, const mhimx_step_cfg* cfg, int32_t n_bags, const mhimx_ragged_window_bag* bags, int64_t host_step,
+                             void* ws, int64_t ws_bytes, int32_t update, int32_t x_dtype, const mhimx_surv_spec* surv) {
   if (int r = check_rw(cfg, n_bags, bags, x_dtype)) return r;
+  if (surv)
+    if (int r = surv_spec_check("ragged_window", n_bags, surv)) return r;
   for (int b = 0; b < n_bags; ++b) {
     MHIMX_CHECK_ARG(bags[b].X && aligned16(bags[b].X), "ragged_window: bag %d: null or unaligned rows", b);
     MHIMX_CHECK_ARG(bags[b].label_dev, "ragged_window: bag %d: null label", b);
@@ -446,7 +462,10 @@ extern "C" int mhimx_ragged_window_run_x(void* stream, const mhimx_step_cfg* cfg
                        F(w.g_z), base + w.pool_ws_s, w.pool_ws_s_bytes, merge_ws, w.merge_ws_bytes};
     MidFwd fwd;
     if (int r = mid_student_fwd(stream, c, im, mw_prep, mb, nullptr, &fwd)) return r;
-    if (int r = mid_head(stream, c, mb, F(w.z_t) + (int64_t)b * E, g.label_dev, inv_n, F(w.logits) + 16 * b, F(w.losses) + 4 * b, c.grad, acc)) return r;
+    const MidSurv sv = {surv ? surv->censor_dev[b] : nullptr, surv ? surv->alpha : 0.f, surv ? surv->eps : 0.f, surv && surv->risk ? surv->risk + b : nullptr};
+    if (int r = mid_head(stream, c, mb, F(w.z_t) + (int64_t)b * E, g.label_dev, inv_n, F(w.logits) + 16 * b, F(w.losses) + 4 * b, c.grad, acc,
+                         surv ? &sv : nullptr))
+      return r;
     mhimx_reduce_list lst;
     memset(&lst, 0, sizeof(lst));
     if (int r = mid_bwd_rows(stream, im, fwd, mb, c.grad, acc, nullptr, nullptr, &lst)) return r;

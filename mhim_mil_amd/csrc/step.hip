@@ -303,7 +303,10 @@ int mid_student_fwd(void* stream, const mhimx_step_cfg& c, const MidImages& im, 
 }
 
 int mid_head(void* stream, const mhimx_step_cfg& c, const MidBag& g, const float* z_t, const int64_t* label, float loss_scale, float* logits,
-             float* losses, const mhimx_step_grads& gr, int accumulate) {
+             float* losses, const mhimx_step_grads& gr, int accumulate, const MidSurv* sv) {
+  if (sv)
+    return mhimx_head_surv_fwd_bwd(stream, g.z_s, c.aux_alpha != 0.f ? z_t : nullptr, c.student.wp, c.student.bp, label, sv->censor, c.E, c.C, c.temp_t,
+                                   c.main_alpha, c.aux_alpha, loss_scale, sv->alpha, sv->eps, logits, losses, sv->risk, g.g_z, gr.wp, gr.bp, accumulate);
   return mhimx_head_fwd_bwd(stream, g.z_s, c.aux_alpha != 0.f ? z_t : nullptr, c.student.wp, c.student.bp, label, c.E, c.C, c.temp_t, c.main_alpha,
                             c.aux_alpha, loss_scale, logits, losses, g.g_z, gr.wp, gr.bp, accumulate, nullptr, nullptr);
 }

@@ -44,9 +44,12 @@ mhimx_scorer mid_scorer(const mhimx_step_cfg& c, const mhimx_step_params& p, con
 // phase-1 scorer over the rows that stay with Merge's row tiles riding -> mhimx_merge_fwd's tail -> the phase-2 finalize that scores the
 // tokens.  dag: the scorer on the side stream beside Merge's whole chain on the main one (nothing rides), joined before the finalize
 int mid_student_fwd(void* stream, const mhimx_step_cfg& c, const MidImages& im, const mhimx_merge& mw_prep, const MidBag& g, const MidDag* dag, MidFwd* f);
-// predictor, CE, distillation against z_t (not read when aux_alpha == 0) and their gradients: g.g_z, gr.wp / gr.bp
+// a bag's survival head (mhimx_ragged_window_run_surv): its censorship flag, NLLSurvLoss(alpha), the clamp, where its risk goes (or NULL)
+struct MidSurv { const float* censor; float alpha, eps; float* risk; };
+// predictor, CE, distillation against z_t (not read when aux_alpha == 0) and their gradients: g.g_z, gr.wp / gr.bp.  sv: the survival
+// criterion in place of the cross entropy (mhimx_head_surv_fwd_bwd); NULL: mhimx_head_fwd_bwd
 int mid_head(void* stream, const mhimx_step_cfg& c, const MidBag& g, const float* z_t, const int64_t* label, float loss_scale, float* logits,
-             float* losses, const mhimx_step_grads& gr, int accumulate);
+             float* losses, const mhimx_step_grads& gr, int accumulate, const MidSurv* sv = nullptr);
 // mhimx_merge_bwd_park, mhimx_abmil_pool_bwd, mhimx_merge_bwd with their reductions queued on the caller's list.  dag: the side branch's
 // two halves (the parked scorer-weight-gradient product, then the Merge parameter-gradient tail) are flushed from here
 int mid_bwd_rows(void* stream, const MidImages& im, const MidFwd& f, const MidBag& g, const mhimx_step_grads& gr, int accumulate, const MidImg* img,

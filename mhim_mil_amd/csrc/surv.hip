@@ -11,68 +11,29 @@
 #include <math.h>
 
 #include "common.hpp"
+#include "surv_dev.hpp"
 
 namespace mhimx {
 
-constexpr int SURV_MAXK = 16;
 constexpr int CI_TILE = 1024;
 
-MHIMX_DEV double surv_softplus(double x) { return fmax(x, 0.0) + log1p(exp(-fabs(x))); }
-
-// one thread per row: K <= 16 logits in registers, one pass for hazards / survival / risk / loss, one for the gradient row.  The head is
-// n x K values - nothing beside the forward that made the logits - so it is evaluated in fp64 and rounded to fp32 once per output: the
-// deviation from an fp64 evaluation of the reference's formulas is the rounding of the result, whatever the device's fp32 log / exp do.
+// one thread per row: K <= 16 logits in registers, the row math of surv_dev.hpp (fp64, every output rounded to fp32 once)
 __global__ __launch_bounds__(256) void surv_nll_kernel(const float* __restrict__ logits, int64_t ld, const int64_t* __restrict__ Y,
                                                        const float* __restrict__ c, int64_t n, int K, float alpha, float eps, float g_scale,
                                                        float* __restrict__ risk, float* __restrict__ losses, float* __restrict__ g_logits) {
   const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (r >= n) return;
-  const int64_t y64 = Y[r];
-  const bool y_ok = y64 >= 0 && y64 < K;
-  const int y = y_ok ? (int)y64 : -1;
-  const double cr = (double)c[r], al = (double)alpha, ep = (double)eps;
-  double h[SURV_MAXK];
-  // S_pad[y] = S_{y-1} (1 at y = 0), S_pad[y + 1] = S_y: the two survival values the loss gathers, each with its log in the stable
-  // form log S_k = -sum_{m <= k} softplus(l_m); log h_y = -softplus(-l_y)
-  double S = 1.0, logS = 0.0, rsum = 0.0;
-  double S_prev = 1.0, logS_prev = 0.0, S_at = 1.0, logS_at = 0.0, h_at = 1.0, logh_at = 0.0;
+  float l[SURV_MAXK], g[SURV_MAXK];
 #pragma unroll
-  for (int k = 0; k < SURV_MAXK; ++k) {
-    if (k < K) {
-      const double l = (double)logits[r * ld + k];
-      h[k] = 1.0 / (1.0 + exp(-l));
-      if (k == y) { S_prev = S; logS_prev = logS; h_at = h[k]; logh_at = -surv_softplus(-l); }
-      S *= 1.0 / (1.0 + exp(l));                                // 1 - h without the cancellation
-      logS -= surv_softplus(l);
-      rsum += S;
-      if (k == y) { S_at = S; logS_at = logS; }
-    } else {
-      h[k] = 0.0;
-    }
-  }
-  risk[r] = (float)-rsum;
-  // the reference clamps the QUANTITY (torch.clamp(min=eps) before the log): a clamped term is the constant log(eps), gradient 0
-  const bool a_live = S_prev >= ep, b_live = h_at >= ep, c_live = S_at >= ep;
-  const double log_eps = log(ep);
-  const double unc = -(1.0 - cr) * ((a_live ? logS_prev : log_eps) + (b_live ? logh_at : log_eps));
-  const double cen = -cr * (c_live ? logS_at : log_eps);
-  losses[r] = y_ok ? (float)((1.0 - al) * (cen + unc) + al * unc) : NAN;
+  for (int k = 0; k < SURV_MAXK; ++k) l[k] = k < K ? logits[r * ld + k] : 0.f;
+  float rk, ls;
+  surv_row<SURV_MAXK>(l, K, Y[r], c[r], alpha, eps, g_scale, g_logits != nullptr, rk, ls, g);
+  risk[r] = rk;
+  losses[r] = ls;
   if (g_logits) {
-    // d log S_k / d l_m = -h_m (m <= k);  d log h_y / d l_y = 1 - h_y;  unc enters both terms of the loss: weight (1 - alpha) + alpha = 1
 #pragma unroll
-    for (int k = 0; k < SURV_MAXK; ++k) {
-      if (k < K) {
-        double g = 0.0;
-        if (y_ok) {
-          double du = 0.0, dc = 0.0;                            // d (log terms) / d l_k
-          if (a_live && k < y) du -= h[k];
-          if (b_live && k == y) du += 1.0 - h[k];
-          if (c_live && k <= y) dc -= h[k];
-          g = (double)g_scale * (-(1.0 - cr) * du + (1.0 - al) * (-cr * dc));
-        }
-        g_logits[r * K + k] = (float)g;
-      }
-    }
+    for (int k = 0; k < SURV_MAXK; ++k)
+      if (k < K) g_logits[r * K + k] = g[k];
   }
 }
 
@@ -176,6 +137,15 @@ static int ci_check(const char* who, int64_t n, int64_t B) {
   MHIMX_CHECK_ARG(B >= 1 && B <= MHIMX_CINDEX_MAX_B, "%s: B=%lld must be in 1..%d", who, (long long)B, MHIMX_CINDEX_MAX_B);
   MHIMX_CHECK_ARG(B * n <= MHIMX_CINDEX_MAX_BN, "%s: B * n = %lld exceeds %d (evaluate the resamples in slices)", who, (long long)(B * n),
                   MHIMX_CINDEX_MAX_BN);
+  return 0;
+}
+
+// alpha in [0, 1], eps in (0, 1), a censorship flag for every bag: mhimx_surv_nll's rules, per bag of a train call
+int surv_spec_check(const char* who, int32_t n_bags, const mhimx_surv_spec* surv) {
+  MHIMX_CHECK_ARG(surv->alpha >= 0.f && surv->alpha <= 1.f, "%s: survival alpha=%g must be in [0, 1]", who, (double)surv->alpha);
+  MHIMX_CHECK_ARG(surv->eps > 0.f && surv->eps < 1.f, "%s: survival eps=%g must be in (0, 1)", who, (double)surv->eps);
+  for (int b = 0; b < n_bags && b < MHIMX_INFER_MAX; ++b)
+    MHIMX_CHECK_ARG(surv->censor_dev[b], "%s: bag %d: null censorship flag (surv->censor_dev)", who, b);
   return 0;
 }
 

@@ -74,6 +74,23 @@ class CommonMIL:
             lg = logits.detach().view(batch_size, -1).clone().requires_grad_(True)     # (clone: a replay rewrites the graph's buffers)
             aux = losses[2].detach().clone().requires_grad_(True)
             return lg, label, aux, patch_num, keep_num, 0., 0.
+        if (fz is not None and model is fz.model and model_ema is fz.model_ema and model.training and not dsmil
+                and args.model == fz.trainer.model_kind and fz.trainer.loss == "nll_surv" and batch_size == 1
+                and isinstance(label, (list, tuple)) and len(label) == 2):
+            from .survival import NLLSurvLoss
+            if type(criterion) is NLLSurvLoss:
+                # the survival loop's loss is main_alpha * NLLSurvLoss(alpha)(logits, Y, c) + aux_alpha * aux (engines/base_engine.py:395-441):
+                # the native step computes exactly that and its gradient; the loop gets LEAVES, as in the cross-entropy branch above
+                tr = fz.trainer
+                tr.main_alpha, tr.aux_alpha, tr.surv_alpha = float(getattr(args, "main_alpha", 1.0)), float(args.aux_alpha), float(criterion.alpha)
+                dev = tr.flat.student.device
+                Y = label[0].reshape(-1)[:1].to(device=dev, dtype=torch.int64).contiguous()
+                c = label[1].reshape(-1)[:1].to(device=dev, dtype=torch.float32).contiguous()
+                extra = {k: kwargs[k] for k in ("perm", "ids_shuffle") if k in kwargs}
+                logits, losses = tr.forward_backward(bag, (Y, c), i=n_iter, **extra)
+                lg = logits.detach().view(batch_size, -1).clone().requires_grad_(True)
+                aux = losses[2].detach().clone().requires_grad_(True)
+                return lg, label, aux, tr.last["patch_num"], tr.last["keep_num"], 0., 0.
         if args.model == "mhim":
             teacher_feat, score = (None, None)
             if model_ema is not None:
@@ -283,9 +300,26 @@ class FusedTrainer:
 
     def __init__(self, student: MHIM, teacher: Optional[MHIM], lr=2e-4, weight_decay=1e-5, betas=(0.9, 0.999), eps=1e-8,
                  mm=0.9997, main_alpha=1.0, aux_alpha=0.5, accumulation_steps=1, process_group=None, model="mhim", mm_sche=None,
-                 clip_grad=None, lr_sche=None):
+                 clip_grad=None, lr_sche=None, loss="ce", surv_alpha=0.0, surv_eps=1e-7):
         if model not in ("mhim", "mhim_pure"):
             raise mh.L.MhimxError(f"FusedTrainer: model={model!r} (the path knows 'mhim' and 'mhim_pure')")
+        if loss not in ("ce", "nll_surv"):
+            raise mh.L.MhimxError(f"FusedTrainer: loss={loss!r} (the path knows 'ce' and 'nll_surv')")
+        if loss == "nll_surv":
+            # survival training (engines/base_engine.py:395-441, criterion train_utils.py:8-37): the ABMIL student with the plain scorer, one
+            # process - the models mhimx_pure_window_run_surv / mhimx_ragged_window_run_surv serve.  Everything else keeps training through
+            # CommonMIL.forward_func's autograd form
+            if student.baseline != "attn" or getattr(student.online_encoder, "gated", False):
+                raise mh.L.MhimxError(f"FusedTrainer(loss='nll_surv'): the ABMIL student with the plain scorer only (baseline="
+                                      f"{student.baseline!r}, gated={getattr(student.online_encoder, 'gated', False)}); other models train "
+                                      f"through CommonMIL.forward_func's autograd form")
+            if process_group is not None or (torch.distributed.is_available() and torch.distributed.is_initialized()
+                                             and torch.distributed.get_world_size() > 1):
+                raise mh.L.MhimxError("FusedTrainer(loss='nll_surv'): one process (world > 1 trains through CommonMIL.forward_func's autograd form)")
+            if not (0.0 <= float(surv_alpha) <= 1.0 and 0.0 < float(surv_eps) < 1.0):
+                raise mh.L.MhimxError(f"FusedTrainer(loss='nll_surv'): surv_alpha={surv_alpha} must be in [0, 1], surv_eps={surv_eps} in (0, 1)")
+        # loss="nll_surv": a label is a pair (Y, c) - the time bin (int64 [1]) and the censorship flag (fp32 [1]) as device tensors
+        self.loss, self.surv_alpha, self.surv_eps = loss, float(surv_alpha), float(surv_eps)
         if model == "mhim" and teacher is None:
             raise mh.L.MhimxError("FusedTrainer(model='mhim') needs the EMA teacher (modules/__init__.py:176-214 builds it)")
         if model == "mhim" and not student.merge_enable:
@@ -385,6 +419,17 @@ class FusedTrainer:
         says which ran)."""
         s, t, fl = self.s, self.t, self.flat
         x = s._check_x(bag)
+        if self.loss == "nll_surv":
+            # one survival bag is a window of one: mhimx_pure_window_run_surv / mhimx_ragged_window_run_surv (accumulation_steps == 1: a bag
+            # of a longer window is scaled by 1 / accumulation_steps, which only the bag-after-bag route below does)
+            label = self._surv_label(label, x.device)
+            if self.accum == 1 and perm is None and ids_shuffle is None:
+                if self.model_kind == "mhim_pure" and self._pure_window_ok([x], [label[0]]):
+                    logits, losses = self._exec_pure_window([x], [label[0]], bool(self._fold_now), surv=[label[1]], single=True)
+                    return logits[0], losses[0]
+                if self.model_kind == "mhim" and self._ragged_window_ok([x], [label[0]], i):
+                    logits, losses = self._exec_ragged_window([x], [label[0]], i, bool(self._fold_now), surv=[label[1]], single=True)
+                    return logits[0], losses[0]
         # the teacher-free DSMIL step (accumulation_steps == 1) as ONE call: mhimx_dsmil_window_run with one bag
         if self.accum == 1 and perm is None and ids_shuffle is None and self._dsmil_window_ok([x], [label]):
             logits, losses = self._exec_dsmil_window([x], [label], bool(self._fold_now), single=True)
@@ -490,7 +535,7 @@ class FusedTrainer:
                 tok = saved.get("z_tok")
                 self._chain.tokens = self._chain_tokens = tok if tok is not None else s.merge.global_q_mm.data.view(s.merge.k, -1).clone()
             t_in = teacher_feat.view(-1) if (teacher_feat is not None and self.aux_alpha != 0.) else None
-            logits, losses, g_z, _, _ = ops.head_fwd_bwd(
+            logits, losses, g_z, _, _ = (self._surv_head if self.loss == "nll_surv" else ops.head_fwd_bwd)(
                 z, t_in, s.predictor.weight.data, s.predictor.bias.data, label, temp_t=float(s.temp_t),
                 main_alpha=self.main_alpha, aux_alpha=self.aux_alpha, inv_accum=1.0 / self.accum,
                 d_wp=gv["predictor.weight"], d_bp=gv["predictor.bias"], accumulate=not first)
@@ -508,6 +553,67 @@ class FusedTrainer:
             s.merge_enable = merge_on
         self._micro += 1
         self.last = {"logits": logits, "losses": losses, "patch_num": ps, "keep_num": keep_num, "exec": False}
+        if self.loss == "nll_surv":
+            self.last["risk"] = self._risk_now
+        return logits, losses
+
+    # ------------------------------------------------------------------------------------------------- survival training (loss="nll_surv")
+    @staticmethod
+    def _surv_label(label, dev):
+        """A survival label: the pair (Y, c) - time bin int64 [1], censorship flag fp32 [1] - as contiguous tensors on the bag's device."""
+        ok = isinstance(label, (tuple, list)) and len(label) == 2 and all(torch.is_tensor(v) and v.is_cuda and v.device == dev
+                                                                          and v.numel() == 1 and v.is_contiguous() for v in label)
+        if not (ok and label[0].dtype == torch.int64 and label[1].dtype == torch.float32):
+            raise mh.L.MhimxError(f"loss='nll_surv': a label is a pair (Y, c) - an int64 [1] time bin and an fp32 [1] censorship flag on "
+                                  f"the bag's device ({dev})")
+        return label[0].view(1), label[1].view(1)
+
+    def _surv_head(self, z, t, wp, bp, label, temp_t=1.0, main_alpha=1.0, aux_alpha=0.0, inv_accum=1.0, d_wp=None, d_bp=None,
+                   accumulate=False):
+        """ops.head_fwd_bwd's place on the bag-after-bag route: the predictor (its label-free form: logits and the distillation loss),
+        ops.surv_nll on those logits with g_scale = main_alpha * inv_accum (the fp32 product the native head takes), then
+        mhimx_head_fwd_bwd's autograd form on that gradient row - the two-launch composition the native head is tested against."""
+        Y, c = label
+        logits, _, _, _, _ = ops.head_fwd_bwd(z, t, wp, bp, None, temp_t=temp_t, main_alpha=main_alpha, aux_alpha=aux_alpha, inv_accum=inv_accum)
+        g_scale = float(torch.tensor(main_alpha, dtype=torch.float32) * torch.tensor(inv_accum, dtype=torch.float32))
+        risk, nll, g = ops.surv_nll(logits.view(1, -1), Y, c, alpha=self.surv_alpha, eps=self.surv_eps, g_scale=g_scale)
+        logits, ls, g_z, d_wp, d_bp = ops.head_fwd_bwd(z, t, wp, bp, None, temp_t=temp_t, main_alpha=main_alpha, aux_alpha=aux_alpha,
+                                                       inv_accum=inv_accum, d_wp=d_wp, d_bp=d_bp, accumulate=accumulate, g_logits_in=g.view(-1))
+        losses = torch.stack([main_alpha * nll[0] + ls[0], nll[0], ls[2]])
+        self._risk_now = risk
+        return logits, losses, g_z, d_wp, d_bp
+
+    def _surv_window_step(self, bags, labels, i, perms, shuffles, update):
+        """window_step of a loss="nll_surv" trainer: 1 .. accumulation_steps bags as ONE call of mhimx_pure_window_run_surv ('mhim_pure') or
+        mhimx_ragged_window_run_surv ('mhim'; same-shaped windows too: mhimx_window_run has no survival form) when the call takes them.
+        Else 'mhim_pure': bag after bag (exactly accumulation_steps bags: that route scales by 1 / accumulation_steps); 'mhim': None -
+        window_step goes on to its stream form.  ``labels``: (Y, c) pairs as _surv_label returns them."""
+        k = len(bags)
+        assert 1 <= k <= self.accum and len(labels) == k, "window_step takes at most accumulation_steps bags"
+        pure = self.model_kind == "mhim_pure"
+        if perms is None and shuffles is None:
+            # (a window of fp16 / bf16 bags goes into the native call as it is; every other route reads fp32 rows: widened as always)
+            half = self._half_bags(bags)
+            for xs in ([] if half is None else [half]) + [[self.s._check_x(b) for b in bags]]:
+                Ys, cs = [p[0] for p in labels], [p[1] for p in labels]
+                if pure and self._pure_window_ok(xs, Ys):
+                    return self._exec_pure_window(xs, Ys, update, surv=cs)
+                if not pure and self._ragged_window_ok(xs, Ys, i):
+                    return self._exec_ragged_window(xs, Ys, i, update, surv=cs)
+        if not pure:
+            return None
+        assert k == self.accum, "window_step takes exactly accumulation_steps bags"
+        outs, risks, per = [], [], []
+        for j, (b, l) in enumerate(zip(bags, labels)):
+            kw = {} if perms is None else {"perm": perms[j], "ids_shuffle": shuffles[j]}
+            if update:
+                outs.append(self.train_step(b, l, i=i, **kw))
+            else:
+                outs.append(self.forward_backward(b, l, i=i, **kw))
+            risks.append(self.last["risk"])
+            per.append(self.last)
+        logits, losses = [o[0] for o in outs], [o[1] for o in outs]
+        self.last = dict(self.last, logits=logits, losses=losses, bags=per, risk=torch.cat([r.view(1) for r in risks]))
         return logits, losses
 
     def _nat_ok(self, x, i=None):
@@ -522,6 +628,8 @@ class FusedTrainer:
         update, no injected draws (csrc/step.hip: check_cfg).  ``window``: as a bag of mhimx_window_run (several bags per update)."""
         s, t = self.s, self.t
         if ops.KERNEL_EVENT_HOOK is not None:          # (a caller brackets single launches with events: only the Python orchestration can)
+            return False
+        if self.loss != "ce" and not window:           # (the single-bag executors have no survival form: a bag is a window of one)
             return False
         # (round 6) a data-parallel rank takes it too - forward + backward with update = 0, the EMA of the global queries sent to the
         # QueryChain's scratch (mhimx_step_cfg.q_out), then the all-reduce and mhimx_optim_step as always - unless the eager step overlaps
@@ -609,10 +717,11 @@ class FusedTrainer:
                                           max_rows=self.exec_max_rows, row_cap=min(self.pure_window_row_cap, mh.L.PURE_WINDOW_MAX_ROWS),
                                           max_bags=mh.L.PURE_WINDOW_MAX, elem=xs[0].element_size())
 
-    def _exec_pure_window(self, xs, labels, update):
+    def _exec_pure_window(self, xs, labels, update, surv=None, single=False):
         """One accumulation window of the teacher-free model - 1 .. accumulation_steps bags of any row counts, every loss scaled by
         1 / len(bags) - as ONE call of mhimx_pure_window_run.  Returns ([logits per bag], [losses per bag]); self.last keeps the layout,
-        the workspace and every bag's views."""
+        the workspace and every bag's views.  ``surv``: the bags' censorship flags - mhimx_pure_window_run_surv, ``labels`` are the time
+        bins; ``single``: the one bag of forward_backward / train_step with the single-bag bookkeeping."""
         s, fl = self.s, self.flat
         n = len(xs)
         ex = self._exec_cfg()
@@ -622,7 +731,9 @@ class FusedTrainer:
         for j in range(n):                                          # ONE seed per bag, in bag order: the feature dropout's
             table[j].drop_seed = s._next_seed()
         inside = bool(update and not self.clip_grad)                # (clipping needs the norm of the final gradient: the update stays outside)
-        ops.pure_window_run(ex["cfg"], table, n, fl.step + int(inside), ws, inside, x_dtype=ops.x_dtype_of(xs))
+        risk = None if surv is None else torch.empty(n, device=xs[0].device)
+        spec = None if surv is None else ops.surv_spec(surv, self.surv_alpha, self.surv_eps, risk)
+        ops.pure_window_run(ex["cfg"], table, n, fl.step + int(inside), ws, inside, x_dtype=ops.x_dtype_of(xs), surv=spec)
         E, Cc, view = s.mlp_dim, s.n_classes, ops.ws_view
         lg, ls = view(ws, lay.logits, n * Cc).view(n, Cc), view(ws, lay.losses, n * 3).view(n, 3)
         H = view(ws, lay.H, lay.rows * E).view(lay.rows, E)
@@ -634,7 +745,13 @@ class FusedTrainer:
                         "dact": dact[r0:r0 + N]})
         logits, losses = [p["logits"] for p in per], [p["losses"] for p in per]
         self.last = dict(self._last_pure(logits, losses, per[-1]["H_student"]), bags=per, layout=lay, ws=ws, exec=True, x_dtype=xs[0].dtype)
-        self._window_done(n, inside, update)
+        if surv is not None:
+            self.last.update(exec="mhimx_pure_window_run_surv", risk=risk)
+        if single:
+            self.last.update(logits=logits[0], losses=losses[0])
+            self._steps_done(inside)
+        else:
+            self._window_done(n, inside, update)
         return logits, losses
 
     # ------------------------------------------------------------------------------------------------- the teacher-free DSMIL call
@@ -1095,7 +1212,8 @@ class FusedTrainer:
         s = self.s
         if ops.KERNEL_EVENT_HOOK is not None or not xs or self.model_kind != "mhim":
             return False
-        if not (self.use_executor and self.accum > 1 and 1 <= len(xs) <= self.accum and len(labels) == len(xs) and self.world == 1
+        # (loss="nll_surv": a single bag of accumulation_steps == 1 is a window of one - there is no survival form of mhimx_step_run)
+        if not (self.use_executor and (self.accum > 1 or self.loss == "nll_surv") and 1 <= len(xs) <= self.accum and len(labels) == len(xs) and self.world == 1
                 and self._chain is None and not self.step_dag and not getattr(self, "time_project", False) and self._micro == 0
                 and s.baseline == "attn" and s.mrh_sche is None and s._op_prec != "f32" and s.merge_enable and s.merge.k <= 6):
             return False
@@ -1112,9 +1230,11 @@ class FusedTrainer:
             E=s.mlp_dim, A=s.online_encoder.attention.attention[0].weight.shape[0], C=s.n_classes, max_rows=self.exec_max_rows,
             row_cap=min(self.ragged_window_row_cap, mh.L.RAGGED_WINDOW_MAX_ROWS), max_bags=mh.L.RAGGED_WINDOW_MAX, elem=xs[0].element_size())
 
-    def _exec_ragged_window(self, xs, labels, i, update):
+    def _exec_ragged_window(self, xs, labels, i, update, surv=None, single=False):
         """One accumulation window of different-sized bags - 1 .. accumulation_steps of them, every loss scaled by 1 / len(bags) - as ONE
-        call of mhimx_ragged_window_run.  Returns ([logits per bag], [losses per bag]); self.last["bags"] holds each bag's views."""
+        call of mhimx_ragged_window_run.  Returns ([logits per bag], [losses per bag]); self.last["bags"] holds each bag's views.
+        ``surv``: the bags' censorship flags - mhimx_ragged_window_run_surv, ``labels`` are the time bins; ``single``: the one bag of
+        forward_backward / train_step with the single-bag bookkeeping."""
         L = mh.L
         s, fl = self.s, self.flat
         n = len(xs)
@@ -1131,7 +1251,9 @@ class FusedTrainer:
         for j in range(n):
             table[j].seeds = self._step_seeds()
         inside = bool(update and not self.clip_grad)              # (clipping needs the norm of the final gradient: the update stays outside)
-        ops.ragged_window(ex["cfg"], table, n, fl.step + int(inside), ws, inside, x_dtype=ops.x_dtype_of(xs))
+        risk = None if surv is None else torch.empty(n, device=xs[0].device)
+        spec = None if surv is None else ops.surv_spec(surv, self.surv_alpha, self.surv_eps, risk)
+        ops.ragged_window(ex["cfg"], table, n, fl.step + int(inside), ws, inside, x_dtype=ops.x_dtype_of(xs), surv=spec)
         E, Cc, view = s.mlp_dim, s.n_classes, ops.ws_view
         lg, ls = view(ws, lay.logits, n * 16).view(n, 16), view(ws, lay.losses, n * 4).view(n, 4)
         dact = view(ws, lay.dact, lay.rows * E, torch.float16).view(lay.rows, E)
@@ -1144,7 +1266,13 @@ class FusedTrainer:
         logits, losses = [p_["logits"] for p_ in per], [p_["losses"] for p_ in per]
         self.last = dict(per[-1], logits=logits, losses=losses, bags=per, layout=lay, table=table, ws=ws, exec="mhimx_ragged_window_run",
                          x_dtype=xs[0].dtype)
-        self._window_done(n, inside, update)
+        if surv is not None:
+            self.last.update(exec="mhimx_ragged_window_run_surv", risk=risk)
+        if single:
+            self.last.update(logits=logits[0], losses=losses[0])
+            self._steps_done(inside)
+        else:
+            self._window_done(n, inside, update)
         return logits, losses
 
     def _exec_plan(self, ex, N, i):
@@ -1352,7 +1480,7 @@ class FusedTrainer:
                 keep_num = ps
             z, saved = s._bag_forward_nat(x, plan, Hbuf, DACT, rows_all, prep_s)
             t_in = teacher_feat.view(-1) if (teacher_feat is not None and self.aux_alpha != 0.) else None
-            logits, losses, g_z, _, _ = ops.head_fwd_bwd(
+            logits, losses, g_z, _, _ = (self._surv_head if self.loss == "nll_surv" else ops.head_fwd_bwd)(
                 z, t_in, s.predictor.weight.data, s.predictor.bias.data, label, temp_t=float(s.temp_t),
                 main_alpha=self.main_alpha, aux_alpha=self.aux_alpha, inv_accum=1.0 / self.accum,
                 d_wp=gv["predictor.weight"], d_bp=gv["predictor.bias"], accumulate=accumulate)
@@ -1373,6 +1501,8 @@ class FusedTrainer:
         self.last = {"logits": logits, "losses": losses, "patch_num": ps, "keep_num": keep_num, "rows": plan.rows,
                      "score": score, "R": plan.R, "tokens": Hbuf[ps:] if mhim else None,
                      "H_student": Hbuf[:ps], "H_teacher": heads[0].out if mhim else None, "exec": False}
+        if self.loss == "nll_surv":
+            self.last["risk"] = self._risk_now
         return logits, losses
 
     # ------------------------------------------------------------------------------------------------- accumulation windows
@@ -1423,6 +1553,13 @@ class FusedTrainer:
         MHIMX_STEP_EXEC=0 keep the stream form below (DSMIL: the bag-after-bag route).  ``self.last["exec"]`` names the route.
         Returns ([logits per bag], [losses per bag])."""
         k = len(bags)
+        if self.loss == "nll_surv":
+            # the two survival calls; a window they refuse takes today's routes below (the stream form / bag after bag), whose head is
+            # _surv_head: the native calls below are the cross entropy's and see no survival label (a pair is no label tensor)
+            labels = [self._surv_label(l, bags[0].device) for l in labels]
+            out = self._surv_window_step(bags, labels, i, perms, shuffles, update)
+            if out is not None:
+                return out
         if self.model_kind == "mhim_pure" and self.accum > 1:
             return self._pure_window_step(bags, labels, i, perms, shuffles, update)
         # the DSMIL student has its own call: mhimx_dsmil_mhim_window_run, for 1 <= len(bags) <= accumulation_steps (fp16 / bf16 bags go in as
@@ -1519,6 +1656,8 @@ class FusedTrainer:
         if update:
             self.update()
         self.last = dict(self.last, logits=logits, losses=losses, bags=per_bag)
+        if self.loss == "nll_surv":
+            self.last["risk"] = torch.cat([b["risk"].view(1) for b in per_bag])
         return logits, losses
 
     def capture_window(self, bags, labels, warmup=1, n_streams=None, **kw):
@@ -1526,7 +1665,12 @@ class FusedTrainer:
         window's streams; ``graph.replay()`` runs prep, the k bags, the slab sum, Adam + EMA."""
         if self.world > 1:
             raise mh.L.MhimxError("capture_window: one process (data-parallel ranks exchange gradients between windows: use capture())")
-        if self.model_kind == "mhim_pure" and self.accum > 1:
+        if self.loss == "nll_surv":
+            xs_ = [self.s._check_x(b) for b in bags]
+            Ys_ = [self._surv_label(l, xs_[0].device)[0] for l in labels]
+            if not (self._pure_window_ok(xs_, Ys_) if self.model_kind == "mhim_pure" else self._ragged_window_ok(xs_, Ys_, kw.get("i"))):
+                raise mh.L.MhimxError("capture_window: mhimx_pure_window_run_surv / mhimx_ragged_window_run_surv does not take these bags / this model")
+        elif self.model_kind == "mhim_pure" and self.accum > 1:
             xs_ = [self.s._check_x(b) for b in bags]
             if not (self._dsmil_window_ok(xs_, labels) if self.s.baseline == "dsmil" else self._pure_window_ok(xs_, labels)):
                 raise mh.L.MhimxError("capture_window: mhimx_pure_window_run / mhimx_dsmil_window_run does not take these bags / this model")

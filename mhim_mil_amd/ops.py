@@ -878,6 +878,26 @@ def head_fwd_bwd(z, t, wp, bp, label, temp_t=1.0, main_alpha=1.0, aux_alpha=0.0,
     return logits, losses, g_z, d_wp, d_bp
 
 
+def head_surv_fwd_bwd(z, t, wp, bp, label, censor, surv_alpha=0.0, surv_eps=1e-7, temp_t=1.0, main_alpha=1.0, aux_alpha=0.0, inv_accum=1.0,
+                      d_wp=None, d_bp=None, accumulate=False, g_z=None):
+    """head_fwd_bwd with the survival criterion (mhimx_head_surv_fwd_bwd, one launch): ``label`` the time bin (int64 [1]), ``censor`` the
+    censorship flag (fp32 [1]).  logits, losses[3] = {main*nll + aux*cl, nll, cl}, risk[1], g_z, d_wp, d_bp."""
+    dev = z.device
+    Cc, E = wp.shape
+    _chk(label, torch.int64, "label"); _chk(censor, torch.float32, "censor")
+    logits = torch.empty(Cc, device=dev)
+    losses = torch.empty(3, device=dev)
+    risk = torch.empty(1, device=dev)
+    g_z = g_z if g_z is not None else torch.empty(E, device=dev)
+    d_wp = d_wp if d_wp is not None else torch.empty_like(wp)
+    d_bp = d_bp if d_bp is not None else torch.empty(Cc, device=dev)
+    L.check(L.lib().mhimx_head_surv_fwd_bwd(_stream(), _p(z), _p(t), _p(wp), _p(bp), _p(label), _p(censor), E, Cc, float(temp_t),
+                                            float(main_alpha), float(aux_alpha), float(inv_accum), float(surv_alpha), float(surv_eps),
+                                            _p(logits), _p(losses), _p(risk), _p(g_z), _p(d_wp), _p(d_bp), int(bool(accumulate))),
+            "mhimx_head_surv_fwd_bwd")
+    return logits, losses, risk, g_z, d_wp, d_bp
+
+
 def adam_ema(p, g, m, v, teacher, n_train, step, lr=2e-4, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=1e-5,
              grad_scale=1.0, ema_mm=0.9997, zero_grad=True, step_dev=None, mm_table=None):
     n_all = p.numel()
@@ -1370,9 +1390,37 @@ def pure_window_layout(cfg, bags, n):
     return lay
 
 
-def pure_window_run(cfg, bags, n, host_step, ws, update, x_dtype=L.X_F32):
+def surv_spec_ok(alpha, eps, censor_ptrs, n):
+    """csrc/surv.hip surv_spec_check, mirrored without tensors: alpha in [0, 1], eps in (0, 1), a non-null censorship address for each of
+    the n bags (``censor_ptrs``: their addresses)."""
+    return bool(0.0 <= alpha <= 1.0 and 0.0 < eps < 1.0 and len(censor_ptrs) >= n and all(int(p or 0) != 0 for p in censor_ptrs[:n]))
+
+
+def surv_spec(censors, alpha=0.0, eps=1e-7, risk=None):
+    """The mhimx_surv_spec of a window: ``censors`` one fp32 [1] device tensor per bag, ``risk`` an fp32 [n] device tensor or None."""
+    if len(censors) > L.INFER_MAX:
+        raise L.MhimxError(f"surv_spec: {len(censors)} bags, at most {L.INFER_MAX}")
+    for c in censors:
+        _chk(c, torch.float32, "censor")
+        if c.numel() != 1:
+            raise L.MhimxError("surv_spec: a censorship flag is one fp32 element per bag")
+    _chk(risk, torch.float32, "risk")
+    if risk is not None and risk.numel() < len(censors):
+        raise L.MhimxError(f"surv_spec: risk holds {risk.numel()} elements for {len(censors)} bags")
+    sp = L.SurvSpec(alpha=float(alpha), eps=float(eps), risk=_p(risk))
+    for b, c in enumerate(censors):
+        sp.censor_dev[b] = c.data_ptr()
+    return sp
+
+
+def pure_window_run(cfg, bags, n, host_step, ws, update, x_dtype=L.X_F32, surv=None):
     """ONE optimiser update (update = False: the summed gradient only) over the n bags of the table as one C call.  ``x_dtype``: what the
-    table's rows are (``x_dtype_of`` of the tensors it was made from)."""
+    table's rows are (``x_dtype_of`` of the tensors it was made from).  ``surv`` (a ``surv_spec``): the survival head in place of the
+    cross entropy - mhimx_pure_window_run_surv, the table's labels are the time bins."""
+    if surv is not None:
+        L.check(L.lib().mhimx_pure_window_run_surv(_stream(), C.byref(cfg), n, bags, int(host_step), ws.data_ptr(), ws.numel(), int(bool(update)),
+                                                   int(x_dtype), C.byref(surv)), "mhimx_pure_window_run_surv")
+        return
     L.check(L.lib().mhimx_pure_window_run_x(_stream(), C.byref(cfg), n, bags, int(host_step), ws.data_ptr(), ws.numel(), int(bool(update)),
                                             int(x_dtype)), _x_name("mhimx_pure_window_run", x_dtype))
 
@@ -1413,13 +1461,17 @@ def dsmil_mhim_window(cfg, bags, n, host_step=0, ws=None, update=False, layout_o
 
 
 # ------------------------------------------------------------------------------------------- ragged MHIM accumulation window
-def ragged_window(cfg, bags, n, host_step=0, ws=None, update=False, layout_only=False, x_dtype=L.X_F32):
+def ragged_window(cfg, bags, n, host_step=0, ws=None, update=False, layout_only=False, x_dtype=L.X_F32, surv=None):
     """mhimx_ragged_window_layout_of (host arithmetic only) and, unless ``layout_only``, mhimx_ragged_window_run: ONE optimiser update
     (update = False: the summed gradient only) of the full MHIM(ABMIL) model over the n bags of the by-value table ``bags``
-    (_lib.RaggedWindowBag * n: rows, pitch, N, label, this bag's counts and seeds) as one C call.  ``x_dtype``: what the table's rows are (``x_dtype_of`` of the tensors it was made from).  Returns the layout."""
+    (_lib.RaggedWindowBag * n: rows, pitch, N, label, this bag's counts and seeds) as one C call.  ``x_dtype``: what the table's rows are (``x_dtype_of`` of the tensors it was made from).  ``surv`` (a ``surv_spec``): the survival head in place of the cross entropy -
+    mhimx_ragged_window_run_surv, the table's labels are the time bins.  Returns the layout."""
     lay = L.RaggedWindowLayout()
     L.check(L.lib().mhimx_ragged_window_layout_of(C.byref(cfg), n, bags, C.byref(lay)), "mhimx_ragged_window_layout_of")
-    if not layout_only:
+    if not layout_only and surv is not None:
+        L.check(L.lib().mhimx_ragged_window_run_surv(_stream(), C.byref(cfg), n, bags, int(host_step), ws.data_ptr(), ws.numel(), int(bool(update)),
+                                                     int(x_dtype), C.byref(surv)), "mhimx_ragged_window_run_surv")
+    elif not layout_only:
         L.check(L.lib().mhimx_ragged_window_run_x(_stream(), C.byref(cfg), n, bags, int(host_step), ws.data_ptr(), ws.numel(), int(bool(update)),
                                                   int(x_dtype)), _x_name("mhimx_ragged_window_run", x_dtype))
     return lay

@@ -54,7 +54,7 @@ def schedule_at_updates(sche, accumulation_steps=1, len_loader=None):
 
 class FusedAdamEMA(torch.optim.Optimizer):
     def __init__(self, model, model_ema=None, lr=2e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-5, mm=0.9997, mm_sche=None,
-                 main_alpha=1.0, aux_alpha=0.5, accumulation_steps=1, model_kind=None, len_loader=None):
+                 main_alpha=1.0, aux_alpha=0.5, accumulation_steps=1, model_kind=None, len_loader=None, loss="ce", surv_alpha=0.0):
         if not any(p.is_cuda for p in model.parameters()):
             raise ValueError("FusedAdamEMA: move the model to the GPU first (the flat buffers live where the parameters are)")
         kind = model_kind or ("mhim" if model_ema is not None else "mhim_pure")
@@ -66,7 +66,8 @@ class FusedAdamEMA(torch.optim.Optimizer):
         # and the update kernel then clamped to mm ~ 1 early).  Without ``len_loader`` the slice stays (exact when acc divides len).
         mm_sche = schedule_at_updates(mm_sche, accumulation_steps, len_loader)
         self.trainer = FusedTrainer(model, model_ema, lr=lr, weight_decay=weight_decay, betas=betas, eps=eps, mm=mm, main_alpha=main_alpha,
-                                    aux_alpha=aux_alpha, accumulation_steps=accumulation_steps, model=kind, mm_sche=mm_sche)
+                                    aux_alpha=aux_alpha, accumulation_steps=accumulation_steps, model=kind, mm_sche=mm_sche, loss=loss,
+                                    surv_alpha=surv_alpha)
         self.flat = self.trainer.flat
         named = dict(model.named_parameters())
         params = [named[n] for n in self.flat.train_names]
