@@ -14,6 +14,7 @@ from __future__ import annotations
 
 from typing import Optional
 
+import dataclasses
 import os
 
 import torch
@@ -295,6 +296,156 @@ class _SplitStep:
         ops.step_images(None)                                  # (nothing on the host installed any; a replay must not leave any either)
 
 
+# ------------------------------------------------------------------------------------------------- the four ragged native train calls
+@dataclasses.dataclass(frozen=True)
+class _WindowFamily:
+    """What differs between the four native calls that make one update over 1 .. 32 bags of different row counts; FusedTrainer._run_family,
+    _family_ok, _window_rows_ok and _try_native hold what they share.  The trainer's methods and attributes are named, not bound:
+    tests replace ``ok`` and ``run`` on an instance."""
+    model_kind: str                 # the trainer's model and
+    baseline: str                   # the student's baseline the call serves
+    ok: str                         # the trainer's check,
+    run: str                        # its call,
+    shapes: str                     # its static mirror of the C checks,
+    row_cap: str                    # its cap on the rows of a call's row space,
+    cfg: str                        # its cfg builder, whose {"key", "cfg", ...} also caches the workspace at
+    ws_key: str
+    layout_of: object               # ops: (cfg, table, n) -> the layout; host arithmetic only
+    call: object                    # ops: (cfg, table, n, host_step, ws, update, x_dtype=[, surv=])
+    exec: object                    # last["exec"]
+    exec_surv: object               # last["exec"] of the call's survival form (None: it has none)
+    full: bool                      # the full model: RaggedWindowBag rows (counts, _step_seeds), ok / run take ``i``, last is the last bag's
+    #                                 views + "table"; else PureWindowBag rows (one dropout seed) made by
+    table: object                   # ops: (xs, labels, seeds) -> the rows, and last is _last_pure of the last bag
+    views: object                   # (trainer, ws, layout, xs, table) -> the bags' dictionaries of workspace views
+    max_bags: int                   # include/mhimx.h's bounds of the call
+    max_rows: int
+    accum_caps_bags: bool           # see _DSMIL
+    feature_bf16x3: bool            # every bag's feature precision must be "bf16x3"
+    trainer_ok: object              # (trainer, n bags) -> the family's own trainer and model conditions
+    bags_ok: object                 # (trainer, xs, i, device) -> its parameter / per-bag conditions, behind the labels' (None: none)
+
+
+def _plain_views(tr, ws, lay, xs, table, dsmil=False):
+    """The bags of a teacher-free call: logits, losses, feature rows and their dropout / activation image; DSMIL: its two heads, B, crit."""
+    s, view, n = tr.s, ops.ws_view, len(xs)
+    E, Cc = s.mlp_dim, s.n_classes
+    lg, ls = view(ws, lay.logits, n * Cc).view(n, Cc), view(ws, lay.losses, n * 3).view(n, 3)
+    if dsmil:
+        lb, li = view(ws, lay.logits_bag, n * Cc).view(n, Cc), view(ws, lay.logits_ins, n * Cc).view(n, Cc)
+        B, crit = view(ws, lay.B, n * Cc * E).view(n, Cc, E), view(ws, lay.crit, n * Cc, torch.int64).view(n, Cc)
+    H = view(ws, lay.H, lay.rows * E).view(lay.rows, E)
+    dact = view(ws, lay.dact, lay.rows * E, torch.float16).view(lay.rows, E)
+    per = []
+    for j, x in enumerate(xs):
+        r0, N = int(lay.row0[j]), x.shape[0]
+        heads = {"logits_bag": lb[j], "logits_ins": li[j], "B": B[j], "crit": crit[j]} if dsmil else {}
+        per.append({"logits": lg[j], "losses": ls[j], **heads, "patch_num": N, "keep_num": N, "row0": r0, "H_student": H[r0:r0 + N],
+                    "dact": dact[r0:r0 + N]})
+    return per
+
+
+def _dsmil_mhim_views(tr, ws, lay, xs, table):
+    s, view, n = tr.s, ops.ws_view, len(xs)
+    E, Cc, km = s.mlp_dim, s.n_classes, s.merge.k
+    lg, ls = view(ws, lay.logits, n * Cc).view(n, Cc), view(ws, lay.losses, n * 3).view(n, 3)
+    lb, li = view(ws, lay.logits_bag, n * Cc).view(n, Cc), view(ws, lay.logits_ins, n * Cc).view(n, Cc)
+    B, Bt = view(ws, lay.B, n * Cc * E).view(n, Cc, E), view(ws, lay.B_teacher, n * Cc * E).view(n, Cc, E)
+    crit = view(ws, lay.crit, n * Cc, torch.int64).view(n, Cc)
+    Ht, Hs = view(ws, lay.H_teacher, lay.rows * E).view(lay.rows, E), view(ws, lay.H_student, lay.rows * E).view(lay.rows, E)
+    dact = view(ws, lay.dact, lay.rows * E, torch.float16).view(lay.rows, E)
+    score, rows_all = view(ws, lay.score, lay.rows), view(ws, lay.rows_all, lay.rows, torch.int64)
+    T = view(ws, lay.tokens, lay.tok_rows * E).view(lay.tok_rows, E)
+    per = []
+    for j, x in enumerate(xs):
+        r0, t0, N, cnt = int(lay.row0[j]), int(lay.tok0[j]), x.shape[0], table[j].cnt
+        per.append({"logits": lg[j], "losses": ls[j], "logits_bag": lb[j], "logits_ins": li[j], "B": B[j], "B_teacher": Bt[j],
+                    "score": score[r0:r0 + N], "rows": rows_all[r0:r0 + cnt.len_keep], "Lk": int(cnt.Lk), "R": int(cnt.R), "crit": crit[j],
+                    "H_student": Hs[r0:r0 + N], "H_teacher": Ht[r0:r0 + N], "dact": dact[r0:r0 + N],
+                    "tokens": T[t0 + cnt.Lk:t0 + cnt.Lk + km], "token_rows": T[t0:t0 + cnt.Lk + km], "row0": r0, "tok0": t0,
+                    "patch_num": N, "keep_num": int(cnt.Lk) + km})
+    return per
+
+
+def _ragged_views(tr, ws, lay, xs, table):
+    s, view, n = tr.s, ops.ws_view, len(xs)
+    E, Cc = s.mlp_dim, s.n_classes
+    lg, ls = view(ws, lay.logits, n * 16).view(n, 16), view(ws, lay.losses, n * 4).view(n, 4)
+    dact = view(ws, lay.dact, lay.rows * E, torch.float16).view(lay.rows, E)
+    zt, zs = view(ws, lay.z_teacher, n * E).view(n, E), view(ws, lay.z_student, n * E).view(n, E)
+    per = []
+    for j, x in enumerate(xs):
+        r0, N = int(lay.row0[j]), x.shape[0]
+        per.append(dict(tr._last_full(ws, lay, N, table[j].cnt, lg[j, :Cc], ls[j, :3], r0=r0), dact=dact[r0:r0 + N], z_teacher=zt[j],
+                        z_student=zs[j], row0=r0))
+    return per
+
+
+def _dsmil_mhim_trainer_ok(tr, n):
+    s, t = tr.s, tr.t
+    return (t is not None and t.baseline == "dsmil" and tr._chain is None                  # check_dm refuses a q_out
+            and 1 <= n <= tr.accum and s.training and s.merge_enable and not t.merge_test and s.mrh_sche is None and t._op_prec != "f32"
+            and s.act == t.act and s.n_classes == t.n_classes)
+
+
+def _ragged_trainer_ok(tr, n):
+    s = tr.s
+    # (a cross-entropy bag of accumulation_steps == 1 keeps mhimx_step_run; loss="nll_surv": there is no survival form of that call, a
+    # single bag is a window of one)
+    return ((tr.accum > 1 or tr.loss == "nll_surv") and 1 <= n <= tr.accum
+            and tr._chain is None and not tr.step_dag and not getattr(tr, "time_project", False)   # check_rw: q_out, side_stream, time_project
+            and s.mrh_sche is None and s.merge_enable and s.merge.k <= 6)
+
+
+def _dsmil_mhim_bags_ok(tr, xs, i, dev):
+    s, mg = tr.s, tr.s.merge
+    if not set(tr._DSMIL_PARAMS + tr._DSMIL_MERGE_PARAMS) <= set(tr.flat.train_names):
+        return False
+    mps = (mg.norm.weight.data, mg.norm.bias.data, mg.attn.to_kv.weight.data, mg.attn.to_q.weight.data, mg.attn.to_out[0].weight.data,
+           mg.attn.to_out[0].bias.data, mg.global_q_mm.data)
+    if (tuple(mps[2].shape) != (1024, 512) or tuple(mps[3].shape) != (512, 512) or tuple(mps[4].shape) != (512, 512)
+            or mps[6].numel() != mg.k * 512 or any(not p.is_contiguous() or p.dtype != torch.float32 or p.device != dev for p in mps)
+            or any(mps[j].data_ptr() % 16 for j in (0, 1, 2, 3, 4, 6))):
+        return False
+    # (w1_shape: the teacher is a model of its own - only the student's D and E reach dsmil_mhim_window_shapes_ok)
+    return all(tr._dsmil_params_ok(m, dev, w1_shape=True) for m in (s, tr.t))
+
+
+_L = mh.L
+_PURE = _WindowFamily(
+    "mhim_pure", "attn", ok="_pure_window_ok", run="_exec_pure_window", shapes="pure_window_shapes_ok", row_cap="pure_window_row_cap",
+    cfg="_exec_cfg", ws_key="ws_pw", layout_of=ops.pure_window_layout, call=ops.pure_window_run, exec=True, exec_surv="mhimx_pure_window_run_surv",
+    full=False, table=ops.pure_window_bags, views=_plain_views,
+    max_bags=_L.PURE_WINDOW_MAX, max_rows=_L.PURE_WINDOW_MAX_ROWS, accum_caps_bags=False,       # check_pw (window_step bounds len(bags))
+    feature_bf16x3=True,                                                                        # the call projects in the 3-term bf16 form only
+    trainer_ok=lambda tr, n: tr.s.training and not tr.s.online_encoder.gated, bags_ok=None)
+_DSMIL = _WindowFamily(
+    "mhim_pure", "dsmil", ok="_dsmil_window_ok", run="_exec_dsmil_window", shapes="dsmil_window_shapes_ok", row_cap="dsmil_window_row_cap",
+    cfg="_dsmil_cfg", ws_key="ws", layout_of=ops.dsmil_window_layout, call=ops.dsmil_window_run, exec="mhimx_dsmil_window_run", exec_surv=None,
+    full=False, table=ops.dsmil_window_bags, views=lambda *a: _plain_views(*a, dsmil=True),
+    max_bags=_L.DSMIL_WINDOW_MAX, max_rows=_L.DSMIL_WINDOW_MAX_ROWS,                            # check_dw
+    accum_caps_bags=True,               # max_bags is min(accumulation_steps, max_bags), ONE bag at accumulation_steps == 1 (the others
+    #                                     bound len(bags) by accumulation_steps in trainer_ok, or leave that to window_step)
+    feature_bf16x3=True, trainer_ok=lambda tr, n: tr.s.training,
+    # (every DSMIL tensor has a gradient view; what else the model carries - the unused predictor - has no gradient on any route)
+    bags_ok=lambda tr, xs, i, dev: set(tr._DSMIL_PARAMS) <= set(tr.flat.train_names) and tr._dsmil_params_ok(tr.s, dev))
+_DSMIL_MHIM = _WindowFamily(
+    "mhim", "dsmil", ok="_dsmil_mhim_window_ok", run="_exec_dsmil_mhim_window", shapes="dsmil_mhim_window_shapes_ok",
+    row_cap="dsmil_mhim_window_row_cap", cfg="_dsmil_mhim_cfg", ws_key="ws",
+    layout_of=lambda cfg, table, n: ops.dsmil_mhim_window(cfg, table, n, layout_only=True), call=ops.dsmil_mhim_window,
+    exec="mhimx_dsmil_mhim_window_run", exec_surv=None, full=True, table=None, views=_dsmil_mhim_views,
+    max_bags=_L.DSMIL_MHIM_WINDOW_MAX, max_rows=_L.DSMIL_MHIM_WINDOW_MAX_ROWS, accum_caps_bags=False,     # check_dm
+    feature_bf16x3=True, trainer_ok=_dsmil_mhim_trainer_ok, bags_ok=_dsmil_mhim_bags_ok)
+_RAGGED = _WindowFamily(
+    "mhim", "attn", ok="_ragged_window_ok", run="_exec_ragged_window", shapes="ragged_window_shapes_ok", row_cap="ragged_window_row_cap",
+    cfg="_exec_cfg", ws_key="ws_rw", layout_of=lambda cfg, table, n: ops.ragged_window(cfg, table, n, layout_only=True), call=ops.ragged_window,
+    exec="mhimx_ragged_window_run", exec_surv="mhimx_ragged_window_run_surv", full=True, table=None, views=_ragged_views,
+    max_bags=_L.RAGGED_WINDOW_MAX, max_rows=_L.RAGGED_WINDOW_MAX_ROWS, accum_caps_bags=False,   # check_rw
+    feature_bf16x3=False,                                                                       # check_cfg has no such rule: _exec_ok decides
+    trainer_ok=_ragged_trainer_ok,
+    bags_ok=lambda tr, xs, i, dev: all(tr._nat_ok(x, i) and tr._exec_ok(x, i, window=True) for x in xs))   # check_rw: check_cfg per bag
+
+
 class FusedTrainer:
     """One-call MHIM(ABMIL) train step on flat buffers (the benchmarked path)."""
 
@@ -419,25 +570,19 @@ class FusedTrainer:
         says which ran)."""
         s, t, fl = self.s, self.t, self.flat
         x = s._check_x(bag)
-        if self.loss == "nll_surv":
-            # one survival bag is a window of one: mhimx_pure_window_run_surv / mhimx_ragged_window_run_surv (accumulation_steps == 1: a bag
-            # of a longer window is scaled by 1 / accumulation_steps, which only the bag-after-bag route below does)
+        surv = self.loss == "nll_surv"
+        if surv:
             label = self._surv_label(label, x.device)
-            if self.accum == 1 and perm is None and ids_shuffle is None:
-                if self.model_kind == "mhim_pure" and self._pure_window_ok([x], [label[0]]):
-                    logits, losses = self._exec_pure_window([x], [label[0]], bool(self._fold_now), surv=[label[1]], single=True)
-                    return logits[0], losses[0]
-                if self.model_kind == "mhim" and self._ragged_window_ok([x], [label[0]], i):
-                    logits, losses = self._exec_ragged_window([x], [label[0]], i, bool(self._fold_now), surv=[label[1]], single=True)
-                    return logits[0], losses[0]
-        # the teacher-free DSMIL step (accumulation_steps == 1) as ONE call: mhimx_dsmil_window_run with one bag
-        if self.accum == 1 and perm is None and ids_shuffle is None and self._dsmil_window_ok([x], [label]):
-            logits, losses = self._exec_dsmil_window([x], [label], bool(self._fold_now), single=True)
-            return logits[0], losses[0]
-        # the full MHIM(DSMIL) step (accumulation_steps == 1) as ONE call: mhimx_dsmil_mhim_window_run with one bag
-        if self.accum == 1 and perm is None and ids_shuffle is None and self._dsmil_mhim_window_ok([x], [label], i):
-            logits, losses = self._exec_dsmil_mhim_window([x], [label], i, bool(self._fold_now), single=True)
-            return logits[0], losses[0]
+        if self.accum == 1 and perm is None and ids_shuffle is None:
+            # one bag as a window of one (``x`` is widened already: a half bag is not offered as it is).  A survival bag: mhimx_pure_window_run_surv
+            # / mhimx_ragged_window_run_surv (accumulation_steps == 1: a bag of a longer window is scaled by 1 / accumulation_steps, which only
+            # the bag-after-bag route below does); the DSMIL steps: mhimx_dsmil_window_run, mhimx_dsmil_mhim_window_run
+            for fam in ((_PURE, _RAGGED) if surv else ()) + (_DSMIL, _DSMIL_MHIM):
+                sv = surv and fam.exec_surv is not None
+                out = self._try_native(fam, [x], [label[0]] if sv else [label], i, bool(self._fold_now), surv=[label[1]] if sv else None,
+                                       single=True)
+                if out is not None:
+                    return out[0][0], out[1][0]
         # parameter-only preparation of the step: weight transposes, paired-plane weights, query snapshot
         # (kept on the launch stream: a parallel branch in the captured hipGraph costs ~60 us of cross-queue signalling on
         # ROCm 7.2 — measured, profiles/ r01 notes — against ~40 us of kernels it would hide)
@@ -592,14 +737,9 @@ class FusedTrainer:
         assert 1 <= k <= self.accum and len(labels) == k, "window_step takes at most accumulation_steps bags"
         pure = self.model_kind == "mhim_pure"
         if perms is None and shuffles is None:
-            # (a window of fp16 / bf16 bags goes into the native call as it is; every other route reads fp32 rows: widened as always)
-            half = self._half_bags(bags)
-            for xs in ([] if half is None else [half]) + [[self.s._check_x(b) for b in bags]]:
-                Ys, cs = [p[0] for p in labels], [p[1] for p in labels]
-                if pure and self._pure_window_ok(xs, Ys):
-                    return self._exec_pure_window(xs, Ys, update, surv=cs)
-                if not pure and self._ragged_window_ok(xs, Ys, i):
-                    return self._exec_ragged_window(xs, Ys, i, update, surv=cs)
+            out = self._try_native(_PURE if pure else _RAGGED, bags, [p[0] for p in labels], i, update, surv=[p[1] for p in labels])
+            if out is not None:
+                return out
         if not pure:
             return None
         assert k == self.accum, "window_step takes exactly accumulation_steps bags"
@@ -688,71 +828,123 @@ class FusedTrainer:
         refuse takes the bag-after-bag route instead of raising.  ``bags``: one (N, D, pitch, inner, ptr) per bag - shape, strides in
         elements, address; ``D``: the model's input width; ``elem``: bytes of an element of the bags' rows (4: fp32; 2: fp16 / bf16, whose
         pitch is a multiple of 8 elements and at most 2^20)."""
-        if not (ops.model_dims_ok(E, A, C, D) and D <= (1 << 20) and 1 <= len(bags) <= max_bags):
+        return FusedTrainer._window_rows_ok(bags, D, ops.model_dims_ok(E, A, C, D), max_rows, row_cap, max_bags, elem)
+
+    @staticmethod
+    def _window_rows_ok(bags, D, model_ok, max_rows, row_cap, max_bags, elem, k=None, n_in_counts=False):
+        """The row loop of the four *_window_shapes_ok.  ``model_ok``: the call's model rule; ``k``: merge_k of a full-model call, whose
+        bags carry their counts behind the address (None: the teacher-free calls); ``n_in_counts``: mhimx_ragged_window_run_x - the count
+        rule alone bounds a bag's rows (check_cfg) and a bag's slot holds its k tokens too."""
+        if not (model_ok and D <= (1 << 20) and (k is None or (k >= 1 and 8 * k <= 48)) and 1 <= len(bags) <= max_bags):
             return False
         rows = 0
-        for N, Db, pitch, inner, ptr in bags:
-            if not (Db == D and ops.bag_rows_ok(N, D, pitch, inner, ptr, elem, max_rows, True)):
+        for N, Db, pitch, inner, ptr, *cnt in bags:
+            if not (Db == D and ops.bag_rows_ok(N, D, pitch, inner, ptr, elem, 0 if n_in_counts else max_rows, True)):
                 return False
-            rows += (N + 31) // 32 * 32
+            if k is not None and not (cnt[0] is not None and FusedTrainer._step_counts_ok(N, cnt[0], max_rows)):
+                return False
+            rows += (N + (k if n_in_counts else 0) + 31) // 32 * 32
         return rows <= row_cap
 
-    def _pure_window_ok(self, xs, labels):
-        """True when mhimx_pure_window_run_x takes this window (fp32 bags, or fp16 / bf16 bags of ONE dtype).  Decided before any seed is drawn
-        or counter touched."""
+    def _family_ok(self, fam, xs, labels, i=None):
+        """The four _*_window_ok: True when ``fam``'s call takes these bags (fp32 bags, or fp16 / bf16 bags of ONE dtype) as one update.
+        Decided before any seed is drawn or counter touched."""
         s = self.s
-        if ops.KERNEL_EVENT_HOOK is not None or not xs:
+        if ops.KERNEL_EVENT_HOOK is not None or not xs:       # (a caller brackets single launches with events: only the Python orchestration can)
             return False
-        if not (self.use_executor and self.model_kind == "mhim_pure" and self.world == 1 and self._micro == 0 and s.training
-                and s.baseline == "attn" and not s.online_encoder.gated and s._op_prec != "f32" and len(labels) == len(xs)):
+        if not (self.model_kind == fam.model_kind and s.baseline == fam.baseline and self.use_executor and self.world == 1
+                and self._micro == 0 and s._op_prec != "f32" and len(labels) == len(xs) and fam.trainer_ok(self, len(xs))):
             return False
-        dev = xs[0].device
+        dev, any_prec = xs[0].device, not fam.feature_bf16x3
         if not all(torch.is_tensor(x) and x.is_cuda and x.dtype == xs[0].dtype and x.dim() == 2 and x.device == dev
-                   and s._feature_prec(x.shape[0]) == "bf16x3" for x in xs) or xs[0].dtype not in ops._X_DTYPES:
+                   and (any_prec or s._feature_prec(x.shape[0]) == "bf16x3") for x in xs) or xs[0].dtype not in ops._X_DTYPES:
             return False
         if not ops.window_labels_ok(labels, dev):
             return False
-        return self.pure_window_shapes_ok([(x.shape[0], x.shape[1], x.stride(0), x.stride(1), x.data_ptr()) for x in xs], s.input_dim,
-                                          E=s.mlp_dim, A=s.online_encoder.attention.attention[0].weight.shape[0], C=s.n_classes,
-                                          max_rows=self.exec_max_rows, row_cap=min(self.pure_window_row_cap, mh.L.PURE_WINDOW_MAX_ROWS),
-                                          max_bags=mh.L.PURE_WINDOW_MAX, elem=xs[0].element_size())
+        if fam.bags_ok is not None and not fam.bags_ok(self, xs, i, dev):
+            return False
+        bags = [(x.shape[0], x.shape[1], x.stride(0), x.stride(1), x.data_ptr()) + ((s.v2_counts(x.shape[0], i),) if fam.full else ())
+                for x in xs]
+        # (the scorer's width of an ABMIL student; a DSMIL student's q network: _dsmil_params_ok has held it to 128)
+        kw = {"A": s.online_encoder.attention.attention[0].weight.shape[0]} if fam.baseline == "attn" else {"Q": 128}
+        if fam.full:
+            kw["k"] = s.merge.k
+        max_bags = fam.max_bags if not fam.accum_caps_bags else min(self.accum, fam.max_bags) if self.accum > 1 else 1
+        return getattr(self, fam.shapes)(
+            bags, s.input_dim, E=s.mlp_dim, C=s.n_classes, max_rows=self.exec_max_rows, max_bags=max_bags, elem=xs[0].element_size(),
+            row_cap=min(getattr(self, fam.row_cap), fam.max_rows), **kw)
 
-    def _exec_pure_window(self, xs, labels, update, surv=None, single=False):
-        """One accumulation window of the teacher-free model - 1 .. accumulation_steps bags of any row counts, every loss scaled by
-        1 / len(bags) - as ONE call of mhimx_pure_window_run.  Returns ([logits per bag], [losses per bag]); self.last keeps the layout,
-        the workspace and every bag's views.  ``surv``: the bags' censorship flags - mhimx_pure_window_run_surv, ``labels`` are the time
-        bins; ``single``: the one bag of forward_backward / train_step with the single-bag bookkeeping."""
+    def _run_family(self, fam, xs, labels, i, update, surv=None, single=False):
+        """The four _exec_*_window: one update over 1 .. accumulation_steps bags of any row counts, every loss scaled by 1 / len(bags), as
+        ONE call of ``fam``'s entry point.  Returns ([logits per bag], [losses per bag]); self.last keeps the layout, the workspace and
+        every bag's views.  ``surv``: the bags' censorship flags - the call's _surv form, ``labels`` are the time bins; ``single``: the one
+        bag of forward_backward / train_step with the single-bag bookkeeping.  The layout call comes first: a window it refuses leaves
+        every seed stream and counter alone.  Seeds are drawn bag after bag - a teacher-free bag: the feature dropout's; a full-model bag:
+        _step_seeds, the order the bag-after-bag and stream routes draw them in for such a window."""
         s, fl = self.s, self.flat
-        n = len(xs)
-        ex = self._exec_cfg()
-        table = ops.pure_window_bags(xs, labels, [0] * n)
-        lay = ops.pure_window_layout(ex["cfg"], table, n)
-        ws = ops.workspace(ex, "ws_pw", lay.total, xs[0].device)
-        for j in range(n):                                          # ONE seed per bag, in bag order: the feature dropout's
-            table[j].drop_seed = s._next_seed()
+        n, dev = len(xs), xs[0].device
+        ex = getattr(self, fam.cfg)()
+        if fam.full:
+            table = (mh.L.RaggedWindowBag * n)()
+            for j, (x, l) in enumerate(zip(xs, labels)):
+                k_top, n_sel, len_keep, Lk, R = s.v2_counts(x.shape[0], i)
+                table[j].X, table[j].ldx, table[j].N, table[j].label_dev = x.data_ptr(), x.stride(0), x.shape[0], l.data_ptr()
+                table[j].cnt = mh.L.StepCounts(k_top=k_top, n_sel=n_sel, len_keep=len_keep, Lk=Lk, R=R)
+        else:
+            table = fam.table(xs, labels, [0] * n)
+        lay = fam.layout_of(ex["cfg"], table, n)
+        ws = ops.workspace(ex, fam.ws_key, lay.total, dev)
+        for j in range(n):
+            if fam.full:
+                table[j].seeds = self._step_seeds()
+            else:
+                table[j].drop_seed = s._next_seed()
         inside = bool(update and not self.clip_grad)                # (clipping needs the norm of the final gradient: the update stays outside)
-        risk = None if surv is None else torch.empty(n, device=xs[0].device)
+        risk = None if surv is None else torch.empty(n, device=dev)
         spec = None if surv is None else ops.surv_spec(surv, self.surv_alpha, self.surv_eps, risk)
-        ops.pure_window_run(ex["cfg"], table, n, fl.step + int(inside), ws, inside, x_dtype=ops.x_dtype_of(xs), surv=spec)
-        E, Cc, view = s.mlp_dim, s.n_classes, ops.ws_view
-        lg, ls = view(ws, lay.logits, n * Cc).view(n, Cc), view(ws, lay.losses, n * 3).view(n, 3)
-        H = view(ws, lay.H, lay.rows * E).view(lay.rows, E)
-        dact = view(ws, lay.dact, lay.rows * E, torch.float16).view(lay.rows, E)
-        per = []
-        for j, x in enumerate(xs):
-            r0, N = int(lay.row0[j]), x.shape[0]
-            per.append({"logits": lg[j], "losses": ls[j], "patch_num": N, "keep_num": N, "row0": r0, "H_student": H[r0:r0 + N],
-                        "dact": dact[r0:r0 + N]})
+        fam.call(ex["cfg"], table, n, fl.step + int(inside), ws, inside, x_dtype=ops.x_dtype_of(xs), **({} if surv is None else {"surv": spec}))
+        per = fam.views(self, ws, lay, xs, table)
         logits, losses = [p["logits"] for p in per], [p["losses"] for p in per]
-        self.last = dict(self._last_pure(logits, losses, per[-1]["H_student"]), bags=per, layout=lay, ws=ws, exec=True, x_dtype=xs[0].dtype)
+        if fam.full:
+            self.last = dict(per[-1], logits=logits, losses=losses, bags=per, layout=lay, table=table, ws=ws, exec=fam.exec, x_dtype=xs[0].dtype)
+        else:
+            self.last = dict(self._last_pure(logits, losses, per[-1]["H_student"]), bags=per, layout=lay, ws=ws, exec=fam.exec, x_dtype=xs[0].dtype)
         if surv is not None:
-            self.last.update(exec="mhimx_pure_window_run_surv", risk=risk)
+            self.last.update(exec=fam.exec_surv, risk=risk)
         if single:
             self.last.update(logits=logits[0], losses=losses[0])
             self._steps_done(inside)
         else:
             self._window_done(n, inside, update)
         return logits, losses
+
+    def _try_native(self, fam, bags, labels, i, update, surv=None, single=False, offer=None, wide=None):
+        """``fam``'s native call for these bags when its check takes them: first as they are when all are fp16, or all bf16 (_half_bags:
+        the call reads them where they lie), then widened to fp32 as every other route reads them; None when neither is taken.  ``offer``
+        (bags, widened) -> False: this form of the window is not offered to the call.  ``wide``: the caller's list of the widened bags -
+        filled here when it is empty and they are needed, so that a window is widened once however many calls and routes see it.  The
+        check and the call are looked up on the instance here."""
+        if self.model_kind != fam.model_kind or self.s.baseline != fam.baseline:
+            return None
+        ok, run = getattr(self, fam.ok), getattr(self, fam.run)
+        ia = (i,) if fam.full else ()
+        kw = {n: v for n, v in (("surv", surv), ("single", single)) if v}          # (only what is set: a plain window is (xs, labels[, i], update))
+        wide = [] if wide is None else wide
+        for widened in (False, True):
+            if widened and not wide:
+                wide.extend(self.s._check_x(b) for b in bags)
+            xs = wide if widened else self._half_bags(bags)
+            if xs is not None and (offer is None or offer(xs, widened)) and ok(xs, labels, *ia):
+                return run(xs, labels, *ia, update, **kw)
+        return None
+
+    def _pure_window_ok(self, xs, labels):
+        """True when mhimx_pure_window_run_x takes this window (_family_ok)."""
+        return self._family_ok(_PURE, xs, labels)
+
+    def _exec_pure_window(self, xs, labels, update, surv=None, single=False):
+        """One accumulation window of the teacher-free model as ONE call of mhimx_pure_window_run_x / _surv (_run_family)."""
+        return self._run_family(_PURE, xs, labels, None, update, surv, single)
 
     # ------------------------------------------------------------------------------------------------- the teacher-free DSMIL call
     _DSMIL_PARAMS = ("feature.0.weight", "feature.0.bias", "online_encoder.i_classifier.0.weight", "online_encoder.i_classifier.0.bias",
@@ -766,101 +958,51 @@ class FusedTrainer:
         call would refuse takes the bag-after-bag route instead of raising.  ``bags``: one (N, D, pitch, inner, ptr) per bag - shape,
         strides in elements, address; ``D``: the model's input width; ``Q``: the q network's width; ``elem``: bytes of an element of the
         bags' rows (4: fp32; 2: fp16 / bf16, whose pitch is a multiple of 8 elements and at most 2^20)."""
-        if not (E == 512 and Q == 128 and 1 <= C <= 16 and D > 0 and D % 256 == 0 and D <= (1 << 20) and 1 <= len(bags) <= max_bags):
-            return False
-        rows = 0
-        for N, Db, pitch, inner, ptr in bags:
-            if not (Db == D and ops.bag_rows_ok(N, D, pitch, inner, ptr, elem, max_rows, True)):
-                return False
-            rows += (N + 31) // 32 * 32
-        return rows <= row_cap
+        return FusedTrainer._window_rows_ok(bags, D, E == 512 and Q == 128 and 1 <= C <= 16 and D > 0 and D % 256 == 0, max_rows, row_cap,
+                                            max_bags, elem)
 
     def _dsmil_window_ok(self, xs, labels):
-        """True when mhimx_dsmil_window_run takes these bags (fp32 bags, or fp16 / bf16 bags of ONE dtype) as one update of the teacher-free
-        DSMIL model.  Decided before any seed is drawn or counter touched."""
-        s = self.s
-        if ops.KERNEL_EVENT_HOOK is not None or not xs:
-            return False
-        if not (self.use_executor and self.model_kind == "mhim_pure" and s.baseline == "dsmil" and self.world == 1 and self._micro == 0
-                and s.training and s._op_prec != "f32" and len(labels) == len(xs)):
-            return False
-        dev = xs[0].device
-        if not all(torch.is_tensor(x) and x.is_cuda and x.dtype == xs[0].dtype and x.dim() == 2 and x.device == dev
-                   and s._feature_prec(x.shape[0]) == "bf16x3" for x in xs) or xs[0].dtype not in ops._X_DTYPES:
-            return False
-        if not ops.window_labels_ok(labels, dev):
-            return False
-        # (every DSMIL tensor has a gradient view; what else the model carries - the unused predictor - has no gradient on any route)
-        if not set(self._DSMIL_PARAMS) <= set(self.flat.train_names):
-            return False
-        ps = s._infer_dsmil_params()
-        Cc = s.n_classes
-        if (tuple(ps[4].shape) != (128, 512) or tuple(ps[6].shape) != (128, 128) or tuple(ps[8].shape) != (512, 512)
-                or tuple(ps[2].shape) != (Cc, 512) or ps[10].numel() != Cc * Cc * 512):
-            return False
-        if (any(not t.is_contiguous() or t.dtype != torch.float32 or t.device != dev for t in ps)
-                or any(ps[j].data_ptr() % 16 for j in (0, 1, 2, 4, 6, 8, 9))):
-            return False
-        return self.dsmil_window_shapes_ok([(x.shape[0], x.shape[1], x.stride(0), x.stride(1), x.data_ptr()) for x in xs], s.input_dim,
-                                           E=s.mlp_dim, Q=ps[4].shape[0], C=Cc, max_rows=self.exec_max_rows,
-                                           row_cap=min(self.dsmil_window_row_cap, mh.L.DSMIL_WINDOW_MAX_ROWS),
-                                           max_bags=min(self.accum, mh.L.DSMIL_WINDOW_MAX) if self.accum > 1 else 1, elem=xs[0].element_size())
+        """True when mhimx_dsmil_window_run takes these bags as one update of the teacher-free DSMIL model (_family_ok)."""
+        return self._family_ok(_DSMIL, xs, labels)
+
+    def _dsmil_params_ok(self, model, dev, w1_shape=False):
+        """The twelve DSMIL tensors of ``model`` as check_dw / check_dm and the kernels' 16-byte loads want them: the shapes for
+        ``self.s.n_classes`` classes (``w1_shape``: feature.0.weight's too), contiguous fp32 on ``dev``, the matrices 16-byte aligned."""
+        ps, Cc = model._infer_dsmil_params(), self.s.n_classes
+        return bool((not w1_shape or tuple(ps[0].shape) == (512, self.s.input_dim))
+                    and tuple(ps[4].shape) == (128, 512) and tuple(ps[6].shape) == (128, 128) and tuple(ps[8].shape) == (512, 512)
+                    and tuple(ps[2].shape) == (Cc, 512) and ps[10].numel() == Cc * Cc * 512
+                    and all(p.is_contiguous() and p.dtype == torch.float32 and p.device == dev for p in ps)
+                    and not any(ps[j].data_ptr() % 16 for j in (0, 1, 2, 4, 6, 8, 9)))
+
+    def _dsmil_base(self, b=None):
+        """The mhimx_dsmil_train_cfg of this trainer - made (``b`` None: parameter / gradient pointers into the flat buffers, stable for
+        the trainer's lifetime) and refreshed: the optimiser's scalars, on every call."""
+        s, fl, L = self.s, self.flat, mh.L
+        if b is None:
+            gv = fl.grad_views
+            par = L.DsmilParams(**{n: p.data_ptr() for n, p in zip(L._DSMIL_NAMES, s._infer_dsmil_params())})
+            grd = L.DsmilGrads(**{n: gv[name].data_ptr() for n, name in zip(L._DSMIL_NAMES, self._DSMIL_PARAMS)})
+            b = L.DsmilTrainCfg(D=s.input_dim, E=s.mlp_dim, C=s.n_classes, act=L.act_code(s.act, mh._FEATURE_ACTS), param=par, grad=grd,
+                                p=fl.student.data_ptr(), g=fl.grad.data_ptr(), m=fl.m.data_ptr(), v=fl.v.data_ptr(), n_train=fl.n_train,
+                                n_all=fl.n_all, tick=self.tick.data_ptr(), opt_step=self.opt_step.data_ptr())
+        b.lr, b.beta1, b.beta2, b.eps, b.weight_decay = self.lr, self.betas[0], self.betas[1], self.eps, self.wd
+        b.lr_table, b.lr_len = (None, 0) if self.lr_table is None else (self.lr_table.data_ptr(), self.lr_table.numel())
+        b.drop_p, b.main_alpha = float(s.dropout_p), float(self.main_alpha)
+        return b
 
     def _dsmil_cfg(self):
-        """The mhimx_dsmil_train_cfg of this trainer: parameter / gradient pointers into the flat buffers (stable for the trainer's
-        lifetime); the optimiser's scalars are refreshed on every call."""
-        s, fl, L = self.s, self.flat, mh.L
+        """{"key", "cfg"}: the mhimx_dsmil_train_cfg of this trainer (_dsmil_base)."""
         ex = self._dsmil_exec
-        key = (s.feature[0].weight.data_ptr(), fl.grad.data_ptr())
+        key = (self.s.feature[0].weight.data_ptr(), self.flat.grad.data_ptr())
         if ex is None or ex["key"] != key:
-            ps, gv = s._infer_dsmil_params(), fl.grad_views
-            par = L.DsmilParams(**{n: t.data_ptr() for n, t in zip(L._DSMIL_NAMES, ps)})
-            grd = L.DsmilGrads(**{n: gv[name].data_ptr() for n, name in zip(L._DSMIL_NAMES, self._DSMIL_PARAMS)})
-            cfg = L.DsmilTrainCfg(D=s.input_dim, E=s.mlp_dim, C=s.n_classes, act=L.act_code(s.act, mh._FEATURE_ACTS), param=par, grad=grd,
-                                  p=fl.student.data_ptr(), g=fl.grad.data_ptr(), m=fl.m.data_ptr(), v=fl.v.data_ptr(), n_train=fl.n_train,
-                                  n_all=fl.n_all, tick=self.tick.data_ptr(), opt_step=self.opt_step.data_ptr())
-            ex = self._dsmil_exec = {"key": key, "cfg": cfg}
-        cfg = ex["cfg"]
-        cfg.lr, cfg.beta1, cfg.beta2, cfg.eps, cfg.weight_decay = self.lr, self.betas[0], self.betas[1], self.eps, self.wd
-        cfg.lr_table, cfg.lr_len = (None, 0) if self.lr_table is None else (self.lr_table.data_ptr(), self.lr_table.numel())
-        cfg.drop_p, cfg.main_alpha = float(s.dropout_p), float(self.main_alpha)
+            ex = self._dsmil_exec = {"key": key, "cfg": None}
+        ex["cfg"] = self._dsmil_base(ex["cfg"])
         return ex
 
     def _exec_dsmil_window(self, xs, labels, update, single=False):
-        """One update of the teacher-free DSMIL model over 1 .. accumulation_steps bags of any row counts, every loss scaled by
-        1 / len(bags), as ONE call of mhimx_dsmil_window_run.  ``single``: the one bag of forward_backward / train_step
-        (accumulation_steps == 1) with the single-bag bookkeeping.  Returns ([logits per bag], [losses per bag]); self.last keeps the
-        layout, the workspace and every bag's views."""
-        s, fl = self.s, self.flat
-        n = len(xs)
-        ex = self._dsmil_cfg()
-        table = ops.dsmil_window_bags(xs, labels, [0] * n)
-        lay = ops.dsmil_window_layout(ex["cfg"], table, n)
-        ws = ops.workspace(ex, "ws", lay.total, xs[0].device)
-        for j in range(n):                                          # ONE seed per bag, in bag order: the feature dropout's
-            table[j].drop_seed = s._next_seed()
-        inside = bool(update and not self.clip_grad)                # (clipping needs the norm of the final gradient: the update stays outside)
-        ops.dsmil_window_run(ex["cfg"], table, n, fl.step + int(inside), ws, inside, x_dtype=ops.x_dtype_of(xs))
-        E, Cc, view = s.mlp_dim, s.n_classes, ops.ws_view
-        lg, ls = view(ws, lay.logits, n * Cc).view(n, Cc), view(ws, lay.losses, n * 3).view(n, 3)
-        lb, li = view(ws, lay.logits_bag, n * Cc).view(n, Cc), view(ws, lay.logits_ins, n * Cc).view(n, Cc)
-        B, crit = view(ws, lay.B, n * Cc * E).view(n, Cc, E), view(ws, lay.crit, n * Cc, torch.int64).view(n, Cc)
-        H = view(ws, lay.H, lay.rows * E).view(lay.rows, E)
-        dact = view(ws, lay.dact, lay.rows * E, torch.float16).view(lay.rows, E)
-        per = []
-        for j, x in enumerate(xs):
-            r0, N = int(lay.row0[j]), x.shape[0]
-            per.append({"logits": lg[j], "losses": ls[j], "logits_bag": lb[j], "logits_ins": li[j], "B": B[j], "crit": crit[j], "patch_num": N,
-                        "keep_num": N, "row0": r0, "H_student": H[r0:r0 + N], "dact": dact[r0:r0 + N]})
-        logits, losses = [p["logits"] for p in per], [p["losses"] for p in per]
-        self.last = dict(self._last_pure(logits, losses, per[-1]["H_student"]), bags=per, layout=lay, ws=ws, exec="mhimx_dsmil_window_run",
-                         x_dtype=xs[0].dtype)
-        if single:
-            self.last.update(logits=logits[0], losses=losses[0])
-            self._steps_done(inside)
-        else:
-            self._window_done(n, inside, update)
-        return logits, losses
+        """One update of the teacher-free DSMIL model as ONE call of mhimx_dsmil_window_run (_run_family)."""
+        return self._run_family(_DSMIL, xs, labels, None, update, None, single)
 
     # ------------------------------------------------------------------------------------------------- the full MHIM(DSMIL) call
     _DSMIL_MERGE_PARAMS = ("merge.norm.weight", "merge.norm.bias", "merge.attn.to_kv.weight", "merge.attn.to_q.weight",
@@ -873,57 +1015,13 @@ class FusedTrainer:
         R)) per bag - shape, strides in elements, address, its counts; ``D``: the model's input width; ``k``: merge_k; ``Q``: the q
         network's width; ``elem``: bytes of an element of the bags' rows (4: fp32; 2: fp16 / bf16, whose pitch is a multiple of 8 elements
         and at most 2^20)."""
-        if not (E == 512 and Q == 128 and 1 <= C <= 16 and D > 0 and D % 256 == 0 and D <= (1 << 20) and k >= 1 and 8 * k <= 48
-                and 1 <= len(bags) <= max_bags):
-            return False
-        rows = 0
-        for N, Db, pitch, inner, ptr, cnt in bags:
-            if not (Db == D and cnt is not None and ops.bag_rows_ok(N, D, pitch, inner, ptr, elem, max_rows, True)
-                    and FusedTrainer._step_counts_ok(N, cnt, max_rows)):
-                return False
-            rows += (N + 31) // 32 * 32
-        return rows <= row_cap
+        return FusedTrainer._window_rows_ok(bags, D, E == 512 and Q == 128 and 1 <= C <= 16 and D > 0 and D % 256 == 0, max_rows, row_cap,
+                                            max_bags, elem, k=k)
 
     def _dsmil_mhim_window_ok(self, xs, labels, i=None):
-        """True when mhimx_dsmil_mhim_window_run takes these bags (fp32 bags, or fp16 / bf16 bags of ONE dtype) as one update of the full
-        MHIM(DSMIL) model: 1 .. accumulation_steps bags, one process, device-drawn subsets, no mid-run ratio schedule, no merge_test, no
-        kernel event hook, not prec="f32".  Decided before any seed is drawn or counter touched."""
-        s, t = self.s, self.t
-        if ops.KERNEL_EVENT_HOOK is not None or not xs or self.model_kind != "mhim" or s.baseline != "dsmil":
-            return False
-        if not (self.use_executor and t is not None and t.baseline == "dsmil" and self.world == 1 and self._chain is None and self._micro == 0
-                and 1 <= len(xs) <= self.accum and len(labels) == len(xs) and s.training and s.merge_enable and not t.merge_test
-                and s.mrh_sche is None and s._op_prec != "f32" and t._op_prec != "f32" and s.act == t.act and s.n_classes == t.n_classes):
-            return False
-        dev = xs[0].device
-        if not all(torch.is_tensor(x) and x.is_cuda and x.dtype == xs[0].dtype and x.dim() == 2 and x.device == dev
-                   and s._feature_prec(x.shape[0]) == "bf16x3" for x in xs) or xs[0].dtype not in ops._X_DTYPES:
-            return False
-        if not ops.window_labels_ok(labels, dev):
-            return False
-        fl = self.flat
-        if not set(self._DSMIL_PARAMS + self._DSMIL_MERGE_PARAMS) <= set(fl.train_names):
-            return False
-        mg, Cc = s.merge, s.n_classes
-        mps = (mg.norm.weight.data, mg.norm.bias.data, mg.attn.to_kv.weight.data, mg.attn.to_q.weight.data, mg.attn.to_out[0].weight.data,
-               mg.attn.to_out[0].bias.data, mg.global_q_mm.data)
-        if (tuple(mps[2].shape) != (1024, 512) or tuple(mps[3].shape) != (512, 512) or tuple(mps[4].shape) != (512, 512)
-                or mps[6].numel() != mg.k * 512 or any(not p.is_contiguous() or p.dtype != torch.float32 or p.device != dev for p in mps)
-                or any(mps[j].data_ptr() % 16 for j in (0, 1, 2, 3, 4, 6))):
-            return False
-        for m in (s, t):
-            ps = m._infer_dsmil_params()
-            if (tuple(ps[0].shape) != (512, s.input_dim) or tuple(ps[4].shape) != (128, 512) or tuple(ps[6].shape) != (128, 128)
-                    or tuple(ps[8].shape) != (512, 512) or tuple(ps[2].shape) != (Cc, 512) or ps[10].numel() != Cc * Cc * 512):
-                return False
-            if (any(not p.is_contiguous() or p.dtype != torch.float32 or p.device != dev for p in ps)
-                    or any(ps[j].data_ptr() % 16 for j in (0, 1, 2, 4, 6, 8, 9))):
-                return False
-        return self.dsmil_mhim_window_shapes_ok(
-            [(x.shape[0], x.shape[1], x.stride(0), x.stride(1), x.data_ptr(), s.v2_counts(x.shape[0], i)) for x in xs], s.input_dim, mg.k,
-            E=s.mlp_dim, Q=128, C=Cc, max_rows=self.exec_max_rows,
-            row_cap=min(self.dsmil_mhim_window_row_cap, mh.L.DSMIL_MHIM_WINDOW_MAX_ROWS), max_bags=mh.L.DSMIL_MHIM_WINDOW_MAX,
-            elem=xs[0].element_size())
+        """True when mhimx_dsmil_mhim_window_run takes these bags as one update of the full MHIM(DSMIL) model: 1 .. accumulation_steps bags,
+        one process, device-drawn subsets, no mid-run ratio schedule, no merge_test, no kernel event hook, not prec="f32" (_family_ok)."""
+        return self._family_ok(_DSMIL_MHIM, xs, labels, i)
 
     def _dsmil_mhim_cfg(self):
         """The mhimx_dsmil_mhim_cfg of this trainer: parameter / gradient pointers into the flat buffers (stable for the trainer's
@@ -933,22 +1031,14 @@ class FusedTrainer:
         key = (s.feature[0].weight.data_ptr(), t.feature[0].weight.data_ptr(), fl.grad.data_ptr())
         if ex is None or ex["key"] != key:
             gv, mg = fl.grad_views, s.merge
-            par = L.DsmilParams(**{n: p.data_ptr() for n, p in zip(L._DSMIL_NAMES, s._infer_dsmil_params())})
             tea = L.DsmilParams(**{n: p.data_ptr() for n, p in zip(L._DSMIL_NAMES, t._infer_dsmil_params())})
-            grd = L.DsmilGrads(**{n: gv[name].data_ptr() for n, name in zip(L._DSMIL_NAMES, self._DSMIL_PARAMS)})
             mps = (mg.norm.weight, mg.norm.bias, mg.attn.to_kv.weight, mg.attn.to_q.weight, mg.attn.to_out[0].weight, mg.attn.to_out[0].bias)
             mpar = L.DsmilMergeParams(**{n: p.data_ptr() for n, p in zip(L._DSMIL_MERGE_NAMES, mps)})
             mgrd = L.DsmilMergeGrads(**{n: gv[name].data_ptr() for n, name in zip(L._DSMIL_MERGE_NAMES, self._DSMIL_MERGE_PARAMS)})
-            base = L.DsmilTrainCfg(D=s.input_dim, E=s.mlp_dim, C=s.n_classes, act=L.act_code(s.act, mh._FEATURE_ACTS), param=par, grad=grd,
-                                   p=fl.student.data_ptr(), g=fl.grad.data_ptr(), m=fl.m.data_ptr(), v=fl.v.data_ptr(), n_train=fl.n_train,
-                                   n_all=fl.n_all, tick=self.tick.data_ptr(), opt_step=self.opt_step.data_ptr())
-            cfg = L.DsmilMhimCfg(base=base, teacher=tea, merge=mpar, merge_grad=mgrd, q=mg.global_q_mm.data_ptr(), q_out=None, k=mg.k)
+            cfg = L.DsmilMhimCfg(base=self._dsmil_base(), teacher=tea, merge=mpar, merge_grad=mgrd, q=mg.global_q_mm.data_ptr(), q_out=None, k=mg.k)
             ex = self._dsmil_mhim_exec = {"key": key, "cfg": cfg}
         cfg = ex["cfg"]
-        b = cfg.base
-        b.lr, b.beta1, b.beta2, b.eps, b.weight_decay = self.lr, self.betas[0], self.betas[1], self.eps, self.wd
-        b.lr_table, b.lr_len = (None, 0) if self.lr_table is None else (self.lr_table.data_ptr(), self.lr_table.numel())
-        b.drop_p, b.main_alpha = float(s.dropout_p), float(self.main_alpha)
+        self._dsmil_base(cfg.base)
         cfg.cls_attn = int(bool(t.online_encoder.cls_attn))
         cfg.drop_p_teacher = float(t.dropout_p if t.training else 0.0)
         cfg.merge_drop_p, cfg.merge_mm = float(s.merge.dropout), float(s.merge.g_q_mm)
@@ -958,53 +1048,8 @@ class FusedTrainer:
         return ex
 
     def _exec_dsmil_mhim_window(self, xs, labels, i, update, single=False):
-        """One update of the full MHIM(DSMIL) model over 1 .. accumulation_steps bags of any row counts, every loss scaled by
-        1 / len(bags), as ONE call of mhimx_dsmil_mhim_window_run.  ``single``: the one bag of forward_backward / train_step
-        (accumulation_steps == 1) with the single-bag bookkeeping (_exec_step's).  Seeds are drawn bag after bag, per bag in the order
-        today's route draws them for that bag: the teacher's feature dropout (the teacher's stream), then from the student's stream its
-        feature dropout, the select's, Merge's.  Returns ([logits per bag], [losses per bag]); self.last keeps the layout, the workspace
-        and every bag's views."""
-        L = mh.L
-        s, fl = self.s, self.flat
-        n = len(xs)
-        ex = self._dsmil_mhim_cfg()
-        table = (L.RaggedWindowBag * n)()
-        for j, (x, l) in enumerate(zip(xs, labels)):
-            k_top, n_sel, len_keep, Lk, R = s.v2_counts(x.shape[0], i)
-            table[j].X, table[j].ldx, table[j].N, table[j].label_dev = x.data_ptr(), x.stride(0), x.shape[0], l.data_ptr()
-            table[j].cnt = L.StepCounts(k_top=k_top, n_sel=n_sel, len_keep=len_keep, Lk=Lk, R=R)
-        lay = ops.dsmil_mhim_window(ex["cfg"], table, n, layout_only=True)
-        ws = ops.workspace(ex, "ws", lay.total, xs[0].device)
-        for j in range(n):
-            table[j].seeds = self._step_seeds()
-        inside = bool(update and not self.clip_grad)                # (clipping needs the norm of the final gradient: the update stays outside)
-        ops.dsmil_mhim_window(ex["cfg"], table, n, fl.step + int(inside), ws, inside, x_dtype=ops.x_dtype_of(xs))
-        E, Cc, km, view = s.mlp_dim, s.n_classes, s.merge.k, ops.ws_view
-        lg, ls = view(ws, lay.logits, n * Cc).view(n, Cc), view(ws, lay.losses, n * 3).view(n, 3)
-        lb, li = view(ws, lay.logits_bag, n * Cc).view(n, Cc), view(ws, lay.logits_ins, n * Cc).view(n, Cc)
-        B, Bt = view(ws, lay.B, n * Cc * E).view(n, Cc, E), view(ws, lay.B_teacher, n * Cc * E).view(n, Cc, E)
-        crit = view(ws, lay.crit, n * Cc, torch.int64).view(n, Cc)
-        Ht, Hs = view(ws, lay.H_teacher, lay.rows * E).view(lay.rows, E), view(ws, lay.H_student, lay.rows * E).view(lay.rows, E)
-        dact = view(ws, lay.dact, lay.rows * E, torch.float16).view(lay.rows, E)
-        score, rows_all = view(ws, lay.score, lay.rows), view(ws, lay.rows_all, lay.rows, torch.int64)
-        T = view(ws, lay.tokens, lay.tok_rows * E).view(lay.tok_rows, E)
-        per = []
-        for j, x in enumerate(xs):
-            r0, t0, N, cnt = int(lay.row0[j]), int(lay.tok0[j]), x.shape[0], table[j].cnt
-            per.append({"logits": lg[j], "losses": ls[j], "logits_bag": lb[j], "logits_ins": li[j], "B": B[j], "B_teacher": Bt[j],
-                        "score": score[r0:r0 + N], "rows": rows_all[r0:r0 + cnt.len_keep], "Lk": int(cnt.Lk), "R": int(cnt.R), "crit": crit[j],
-                        "H_student": Hs[r0:r0 + N], "H_teacher": Ht[r0:r0 + N], "dact": dact[r0:r0 + N],
-                        "tokens": T[t0 + cnt.Lk:t0 + cnt.Lk + km], "token_rows": T[t0:t0 + cnt.Lk + km], "row0": r0, "tok0": t0,
-                        "patch_num": N, "keep_num": int(cnt.Lk) + km})
-        logits, losses = [p_["logits"] for p_ in per], [p_["losses"] for p_ in per]
-        self.last = dict(per[-1], logits=logits, losses=losses, bags=per, layout=lay, table=table, ws=ws, exec="mhimx_dsmil_mhim_window_run",
-                         x_dtype=xs[0].dtype)
-        if single:
-            self.last.update(logits=logits[0], losses=losses[0])
-            self._steps_done(inside)
-        else:
-            self._window_done(n, inside, update)
-        return logits, losses
+        """One update of the full MHIM(DSMIL) model as ONE call of mhimx_dsmil_mhim_window_run (_run_family)."""
+        return self._run_family(_DSMIL_MHIM, xs, labels, i, update, None, single)
 
     @staticmethod
     def _last_pure(logits, losses, H):
@@ -1063,15 +1108,11 @@ class FusedTrainer:
         route, which scales by 1 / accumulation_steps and so needs exactly that many bags."""
         k = len(bags)
         assert 1 <= k <= self.accum and len(labels) == k, "window_step takes at most accumulation_steps bags"
-        # (the DSMIL student has its own call: mhimx_dsmil_window_run)
-        ok, run = (self._dsmil_window_ok, self._exec_dsmil_window) if self.s.baseline == "dsmil" else (self._pure_window_ok, self._exec_pure_window)
-        # (a window of fp16 / bf16 bags goes into the native call as it is; every other route reads fp32 rows: widened as always)
-        xs = self._half_bags(bags) if perms is None and shuffles is None else None
-        if xs is not None and ok(xs, labels):
-            return run(xs, labels, update)
-        xs = [self.s._check_x(b) for b in bags]
-        if perms is None and shuffles is None and ok(xs, labels):
-            return run(xs, labels, update)
+        if perms is None and shuffles is None:
+            # (the DSMIL student has its own call: mhimx_dsmil_window_run)
+            out = self._try_native(_DSMIL if self.s.baseline == "dsmil" else _PURE, bags, labels, i, update)
+            if out is not None:
+                return out
         assert k == self.accum, "window_step takes exactly accumulation_steps bags"
         outs = [self.train_step(b, l, i=i, **({} if perms is None else {"perm": perms[j], "ids_shuffle": shuffles[j]}))
                 for j, (b, l) in enumerate(zip(bags, labels))]
@@ -1197,83 +1238,16 @@ class FusedTrainer:
         (k_top, n_sel, len_keep, Lk, R)) per bag - shape, strides in elements, address, its counts; ``D``: the model's input width; ``k``:
         merge_k; ``elem``: bytes of an element of the bags' rows (4: fp32; 2: fp16 / bf16, whose pitch is a multiple of 8 elements and at
         most 2^20)."""
-        if not (ops.model_dims_ok(E, A, C, D) and k >= 1 and 8 * k <= 48 and D <= (1 << 20) and 1 <= len(bags) <= max_bags):
-            return False
-        rows = 0
-        for N, Db, pitch, inner, ptr, cnt in bags:
-            if not (Db == D and FusedTrainer._step_counts_ok(N, cnt, max_rows) and ops.bag_rows_ok(N, D, pitch, inner, ptr, elem, 0, True)):
-                return False
-            rows += (N + k + 31) // 32 * 32
-        return rows <= row_cap
+        return FusedTrainer._window_rows_ok(bags, D, ops.model_dims_ok(E, A, C, D), max_rows, row_cap, max_bags, elem, k=k, n_in_counts=True)
 
     def _ragged_window_ok(self, xs, labels, i=None):
         """True when mhimx_ragged_window_run takes this window: 1 .. accumulation_steps bags that each take the step executor, one process,
-        device-drawn subsets, no mid-run ratio schedule, merge_k <= 6.  Decided before any seed is drawn or counter touched."""
-        s = self.s
-        if ops.KERNEL_EVENT_HOOK is not None or not xs or self.model_kind != "mhim":
-            return False
-        # (loss="nll_surv": a single bag of accumulation_steps == 1 is a window of one - there is no survival form of mhimx_step_run)
-        if not (self.use_executor and (self.accum > 1 or self.loss == "nll_surv") and 1 <= len(xs) <= self.accum and len(labels) == len(xs) and self.world == 1
-                and self._chain is None and not self.step_dag and not getattr(self, "time_project", False) and self._micro == 0
-                and s.baseline == "attn" and s.mrh_sche is None and s._op_prec != "f32" and s.merge_enable and s.merge.k <= 6):
-            return False
-        dev = xs[0].device
-        if not all(torch.is_tensor(x) and x.is_cuda and x.dtype == xs[0].dtype and x.dim() == 2 and x.device == dev for x in xs) \
-                or xs[0].dtype not in ops._X_DTYPES:
-            return False
-        if not ops.window_labels_ok(labels, dev):
-            return False
-        if not all(self._nat_ok(x, i) and self._exec_ok(x, i, window=True) for x in xs):
-            return False
-        return self.ragged_window_shapes_ok(
-            [(x.shape[0], x.shape[1], x.stride(0), x.stride(1), x.data_ptr(), s.v2_counts(x.shape[0], i)) for x in xs], s.input_dim, s.merge.k,
-            E=s.mlp_dim, A=s.online_encoder.attention.attention[0].weight.shape[0], C=s.n_classes, max_rows=self.exec_max_rows,
-            row_cap=min(self.ragged_window_row_cap, mh.L.RAGGED_WINDOW_MAX_ROWS), max_bags=mh.L.RAGGED_WINDOW_MAX, elem=xs[0].element_size())
+        device-drawn subsets, no mid-run ratio schedule, merge_k <= 6 (_family_ok)."""
+        return self._family_ok(_RAGGED, xs, labels, i)
 
     def _exec_ragged_window(self, xs, labels, i, update, surv=None, single=False):
-        """One accumulation window of different-sized bags - 1 .. accumulation_steps of them, every loss scaled by 1 / len(bags) - as ONE
-        call of mhimx_ragged_window_run.  Returns ([logits per bag], [losses per bag]); self.last["bags"] holds each bag's views.
-        ``surv``: the bags' censorship flags - mhimx_ragged_window_run_surv, ``labels`` are the time bins; ``single``: the one bag of
-        forward_backward / train_step with the single-bag bookkeeping."""
-        L = mh.L
-        s, fl = self.s, self.flat
-        n = len(xs)
-        ex = self._exec_cfg()
-        table = (L.RaggedWindowBag * n)()
-        for j, (x, l) in enumerate(zip(xs, labels)):
-            k_top, n_sel, len_keep, Lk, R = s.v2_counts(x.shape[0], i)
-            table[j].X, table[j].ldx, table[j].N, table[j].label_dev = x.data_ptr(), x.stride(0), x.shape[0], l.data_ptr()
-            table[j].cnt = L.StepCounts(k_top=k_top, n_sel=n_sel, len_keep=len_keep, Lk=Lk, R=R)
-        lay = ops.ragged_window(ex["cfg"], table, n, layout_only=True)
-        ws = ops.workspace(ex, "ws_rw", lay.total, xs[0].device)
-        # (bag after bag - both dropout streams, the select's, Merge's - the order the stream form draws them in for such a window: the
-        # two routes make the same draws)
-        for j in range(n):
-            table[j].seeds = self._step_seeds()
-        inside = bool(update and not self.clip_grad)              # (clipping needs the norm of the final gradient: the update stays outside)
-        risk = None if surv is None else torch.empty(n, device=xs[0].device)
-        spec = None if surv is None else ops.surv_spec(surv, self.surv_alpha, self.surv_eps, risk)
-        ops.ragged_window(ex["cfg"], table, n, fl.step + int(inside), ws, inside, x_dtype=ops.x_dtype_of(xs), surv=spec)
-        E, Cc, view = s.mlp_dim, s.n_classes, ops.ws_view
-        lg, ls = view(ws, lay.logits, n * 16).view(n, 16), view(ws, lay.losses, n * 4).view(n, 4)
-        dact = view(ws, lay.dact, lay.rows * E, torch.float16).view(lay.rows, E)
-        zt, zs = view(ws, lay.z_teacher, n * E).view(n, E), view(ws, lay.z_student, n * E).view(n, E)
-        per = []
-        for j, x in enumerate(xs):
-            r0, N = int(lay.row0[j]), x.shape[0]
-            per.append(dict(self._last_full(ws, lay, N, table[j].cnt, lg[j, :Cc], ls[j, :3], r0=r0), dact=dact[r0:r0 + N], z_teacher=zt[j],
-                            z_student=zs[j], row0=r0))
-        logits, losses = [p_["logits"] for p_ in per], [p_["losses"] for p_ in per]
-        self.last = dict(per[-1], logits=logits, losses=losses, bags=per, layout=lay, table=table, ws=ws, exec="mhimx_ragged_window_run",
-                         x_dtype=xs[0].dtype)
-        if surv is not None:
-            self.last.update(exec="mhimx_ragged_window_run_surv", risk=risk)
-        if single:
-            self.last.update(logits=logits[0], losses=losses[0])
-            self._steps_done(inside)
-        else:
-            self._window_done(n, inside, update)
-        return logits, losses
+        """One accumulation window of different-sized bags as ONE call of mhimx_ragged_window_run_x / _surv (_run_family)."""
+        return self._run_family(_RAGGED, xs, labels, i, update, surv, single)
 
     def _exec_plan(self, ex, N, i):
         """(counts, layout) of a bag of N rows at iteration i - cached: they follow from N and the HAM ratio alone."""
@@ -1564,24 +1538,18 @@ class FusedTrainer:
             return self._pure_window_step(bags, labels, i, perms, shuffles, update)
         # the DSMIL student has its own call: mhimx_dsmil_mhim_window_run, for 1 <= len(bags) <= accumulation_steps (fp16 / bf16 bags go in as
         # they are); what it refuses takes today's route below
-        if self.model_kind == "mhim" and self.s.baseline == "dsmil" and perms is None and shuffles is None and 1 <= k <= self.accum:
-            xs = self._half_bags(bags)
-            if xs is not None and self._dsmil_mhim_window_ok(xs, labels, i):
-                return self._exec_dsmil_mhim_window(xs, labels, i, update)
-            xs = [self.s._check_x(b) for b in bags]
-            if self._dsmil_mhim_window_ok(xs, labels, i):
-                return self._exec_dsmil_mhim_window(xs, labels, i, update)
-        # (a window of fp16 / bf16 bags goes into mhimx_ragged_window_run_x as it is; every other route reads fp32 rows: widened as always)
-        xs = self._half_bags(bags) if perms is None and shuffles is None else None
-        if xs is not None and not (k == self.accum and all(x.shape == xs[0].shape for x in xs)) and self._ragged_window_ok(xs, labels, i):
-            return self._exec_ragged_window(xs, labels, i, update)
-        xs = [self.s._check_x(b) for b in bags]
-        # bags of different sizes (or a same-shaped window mhimx_window_run does not take), a shorter last window too: ONE call of
-        # mhimx_ragged_window_run, every loss scaled by 1 / len(bags) (base_engine.py:30,50-51,102)
-        # (a full window of same-shaped bags keeps its routes: mhimx_window_run, or the stream form where that call does not take it)
-        one_shape = k == self.accum and all(x.shape == xs[0].shape and x.stride() == xs[0].stride() for x in xs)
-        if not one_shape and perms is None and shuffles is None and self._ragged_window_ok(xs, labels, i):
-            return self._exec_ragged_window(xs, labels, i, update)
+        wide = []                                                     # (the widened bags, made once: by the first route that needs them)
+        if perms is None and shuffles is None:
+            out = self._try_native(_DSMIL_MHIM, bags, labels, i, update, wide=wide) if 1 <= k <= self.accum else None
+            # bags of different sizes, a shorter last window too: ONE call of mhimx_ragged_window_run, every loss scaled by 1 / len(bags)
+            # (base_engine.py:30,50-51,102).  A full window of same-shaped bags is not offered: it keeps its routes - mhimx_window_run, or the
+            # stream form where that call does not take it (fp16 / bf16 bags as they are: one shape; widened: one shape and one pitch)
+            if out is None:
+                out = self._try_native(_RAGGED, bags, labels, i, update, wide=wide, offer=lambda xs, widened: not (k == self.accum and all(
+                    x.shape == xs[0].shape and (not widened or x.stride() == xs[0].stride()) for x in xs)))
+            if out is not None:
+                return out
+        xs = wide or [self.s._check_x(b) for b in bags]
         assert k == self.accum and len(labels) == k, "window_step takes exactly accumulation_steps bags"
         if not self.window_ok(xs, i) or perms is not None or self.world > 1:
             outs = [self.train_step(b, l, i=i, **({} if perms is None else {"perm": perms[j], "ids_shuffle": shuffles[j]}))

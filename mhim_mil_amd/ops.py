@@ -6,6 +6,7 @@ contiguous and on the GPU; nothing falls back to torch math.
 """
 from __future__ import annotations
 
+import collections
 import ctypes as C
 from typing import Optional
 
@@ -1383,11 +1384,34 @@ def pure_window_bags(xs, labels, seeds):
                                            for x, l, sd in zip(xs, labels, seeds)])
 
 
+# the symbols of the four ragged train calls.  ``run``: the run symbol without its suffix - ``x_form``: it is called as run + "_x" (else by
+# the plain name); the survival form of a call that has one is run + "_surv"
+_WindowSyms = collections.namedtuple("_WindowSyms", "layout_of run x_form layout_type")
+_PURE_WINDOW = _WindowSyms("mhimx_pure_window_layout_of", "mhimx_pure_window_run", True, L.PureWindowLayout)
+_DSMIL_WINDOW = _WindowSyms("mhimx_dsmil_window_layout_of", "mhimx_dsmil_window_run", False, L.DsmilWindowLayout)
+_DSMIL_MHIM_WINDOW = _WindowSyms("mhimx_dsmil_mhim_window_layout_of", "mhimx_dsmil_mhim_window_run", False, L.DsmilMhimWindowLayout)
+_RAGGED_WINDOW = _WindowSyms("mhimx_ragged_window_layout_of", "mhimx_ragged_window_run", True, L.RaggedWindowLayout)
+
+
+def _window_call(syms, cfg, bags, n, layout_only=True, host_step=0, ws=None, update=False, x_dtype=L.X_F32, surv=None):
+    """One of the four ragged train calls over the n bags of the by-value table ``bags``: its layout_of call (host arithmetic only;
+    ``layout_only`` None: skipped) and, unless ``layout_only``, its run call - with ``surv`` (a ``surv_spec``) its _surv form.  Returns the
+    layout (None when skipped)."""
+    lay = None
+    if layout_only is not None:
+        lay = syms.layout_type()
+        L.check(getattr(L.lib(), syms.layout_of)(C.byref(cfg), n, bags, C.byref(lay)), syms.layout_of)
+    if not layout_only:
+        sym = syms.run + ("_surv" if surv is not None else "_x" if syms.x_form else "")
+        who = _x_name(syms.run, x_dtype) if syms.x_form and surv is None else sym
+        L.check(getattr(L.lib(), sym)(_stream(), C.byref(cfg), n, bags, int(host_step), ws.data_ptr(), ws.numel(), int(bool(update)), int(x_dtype),
+                                      *(() if surv is None else (C.byref(surv),))), who)
+    return lay
+
+
 def pure_window_layout(cfg, bags, n):
     """mhimx_pure_window_layout_of: host arithmetic only (no device needed)."""
-    lay = L.PureWindowLayout()
-    L.check(L.lib().mhimx_pure_window_layout_of(C.byref(cfg), n, bags, C.byref(lay)), "mhimx_pure_window_layout_of")
-    return lay
+    return _window_call(_PURE_WINDOW, cfg, bags, n)
 
 
 def surv_spec_ok(alpha, eps, censor_ptrs, n):
@@ -1417,12 +1441,7 @@ def pure_window_run(cfg, bags, n, host_step, ws, update, x_dtype=L.X_F32, surv=N
     """ONE optimiser update (update = False: the summed gradient only) over the n bags of the table as one C call.  ``x_dtype``: what the
     table's rows are (``x_dtype_of`` of the tensors it was made from).  ``surv`` (a ``surv_spec``): the survival head in place of the
     cross entropy - mhimx_pure_window_run_surv, the table's labels are the time bins."""
-    if surv is not None:
-        L.check(L.lib().mhimx_pure_window_run_surv(_stream(), C.byref(cfg), n, bags, int(host_step), ws.data_ptr(), ws.numel(), int(bool(update)),
-                                                   int(x_dtype), C.byref(surv)), "mhimx_pure_window_run_surv")
-        return
-    L.check(L.lib().mhimx_pure_window_run_x(_stream(), C.byref(cfg), n, bags, int(host_step), ws.data_ptr(), ws.numel(), int(bool(update)),
-                                            int(x_dtype)), _x_name("mhimx_pure_window_run", x_dtype))
+    _window_call(_PURE_WINDOW, cfg, bags, n, None, host_step, ws, update, x_dtype, surv)
 
 
 # ------------------------------------------------------------------------------------------- ragged DSMIL accumulation window
@@ -1434,16 +1453,13 @@ def dsmil_window_bags(xs, labels, seeds):
 
 def dsmil_window_layout(cfg, bags, n):
     """mhimx_dsmil_window_layout_of: host arithmetic only (no device needed)."""
-    lay = L.DsmilWindowLayout()
-    L.check(L.lib().mhimx_dsmil_window_layout_of(C.byref(cfg), n, bags, C.byref(lay)), "mhimx_dsmil_window_layout_of")
-    return lay
+    return _window_call(_DSMIL_WINDOW, cfg, bags, n)
 
 
 def dsmil_window_run(cfg, bags, n, host_step, ws, update, x_dtype=L.X_F32):
     """ONE optimiser update (update = False: the summed gradient only) of the teacher-free DSMIL model over the n bags of the table as one
     C call.  ``x_dtype``: what the table's rows are (``x_dtype_of`` of the tensors it was made from)."""
-    L.check(L.lib().mhimx_dsmil_window_run(_stream(), C.byref(cfg), n, bags, int(host_step), ws.data_ptr(), ws.numel(), int(bool(update)),
-                                           int(x_dtype)), "mhimx_dsmil_window_run")
+    _window_call(_DSMIL_WINDOW, cfg, bags, n, None, host_step, ws, update, x_dtype)
 
 
 # ------------------------------------------------------------------------------------------- ragged MHIM(DSMIL) accumulation window
@@ -1452,29 +1468,17 @@ def dsmil_mhim_window(cfg, bags, n, host_step=0, ws=None, update=False, layout_o
     update (update = False: the summed gradient only) of the full MHIM(DSMIL) model over the n bags of the by-value table ``bags``
     (_lib.RaggedWindowBag * n: rows, pitch, N, label, this bag's counts and seeds) as one C call.  ``x_dtype``: what the table's rows are
     (``x_dtype_of`` of the tensors it was made from).  Returns the layout."""
-    lay = L.DsmilMhimWindowLayout()
-    L.check(L.lib().mhimx_dsmil_mhim_window_layout_of(C.byref(cfg), n, bags, C.byref(lay)), "mhimx_dsmil_mhim_window_layout_of")
-    if not layout_only:
-        L.check(L.lib().mhimx_dsmil_mhim_window_run(_stream(), C.byref(cfg), n, bags, int(host_step), ws.data_ptr(), ws.numel(), int(bool(update)),
-                                                    int(x_dtype)), "mhimx_dsmil_mhim_window_run")
-    return lay
+    return _window_call(_DSMIL_MHIM_WINDOW, cfg, bags, n, bool(layout_only), host_step, ws, update, x_dtype)
 
 
 # ------------------------------------------------------------------------------------------- ragged MHIM accumulation window
 def ragged_window(cfg, bags, n, host_step=0, ws=None, update=False, layout_only=False, x_dtype=L.X_F32, surv=None):
     """mhimx_ragged_window_layout_of (host arithmetic only) and, unless ``layout_only``, mhimx_ragged_window_run: ONE optimiser update
     (update = False: the summed gradient only) of the full MHIM(ABMIL) model over the n bags of the by-value table ``bags``
-    (_lib.RaggedWindowBag * n: rows, pitch, N, label, this bag's counts and seeds) as one C call.  ``x_dtype``: what the table's rows are (``x_dtype_of`` of the tensors it was made from).  ``surv`` (a ``surv_spec``): the survival head in place of the cross entropy -
+    (_lib.RaggedWindowBag * n: rows, pitch, N, label, this bag's counts and seeds) as one C call.  ``x_dtype``: what the table's rows are
+    (``x_dtype_of`` of the tensors it was made from).  ``surv`` (a ``surv_spec``): the survival head in place of the cross entropy -
     mhimx_ragged_window_run_surv, the table's labels are the time bins.  Returns the layout."""
-    lay = L.RaggedWindowLayout()
-    L.check(L.lib().mhimx_ragged_window_layout_of(C.byref(cfg), n, bags, C.byref(lay)), "mhimx_ragged_window_layout_of")
-    if not layout_only and surv is not None:
-        L.check(L.lib().mhimx_ragged_window_run_surv(_stream(), C.byref(cfg), n, bags, int(host_step), ws.data_ptr(), ws.numel(), int(bool(update)),
-                                                     int(x_dtype), C.byref(surv)), "mhimx_ragged_window_run_surv")
-    elif not layout_only:
-        L.check(L.lib().mhimx_ragged_window_run_x(_stream(), C.byref(cfg), n, bags, int(host_step), ws.data_ptr(), ws.numel(), int(bool(update)),
-                                                  int(x_dtype)), _x_name("mhimx_ragged_window_run", x_dtype))
-    return lay
+    return _window_call(_RAGGED_WINDOW, cfg, bags, n, bool(layout_only), host_step, ws, update, x_dtype, surv)
 
 
 # ------------------------------------------------------------------------------------------- streamed Nystrom attention
