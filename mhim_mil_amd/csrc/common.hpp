@@ -86,12 +86,18 @@ int reduce_slabs_now(hipStream_t st, const float* ws, float* C, int64_t K1, int6
                      int batch = 1, int64_t sC = 0);
 
 // the optimiser launch's arguments from a step configuration: Adam on the flat buffers, the gradient cleared behind it; with_teacher: the
-// EMA teacher rides along (p_teacher, ema_mm or its table).  Callers add what is theirs (fold, the extra gradient slabs).
-inline mhimx_optim_args optim_args_of(const mhimx_step_cfg& c, int64_t host_step, bool with_teacher) {
+// EMA teacher rides along (p_teacher, ema_mm or its table).  Callers add what is theirs (fold, the extra gradient slabs).  The Adam half
+// alone takes either configuration (mhimx_step_cfg, mhimx_dsmil_train_cfg: the field names agree).
+template <class CFG>
+inline mhimx_optim_args optim_args_of(const CFG& c, int64_t host_step) {
   mhimx_optim_args o = {};
   o.p = c.p; o.g = c.g; o.m = c.m; o.v = c.v; o.n_train = c.n_train; o.n_all = c.n_all; o.step = host_step; o.step_dev = c.opt_step;
   o.lr = c.lr; o.lr_table = c.lr_table; o.lr_len = c.lr_len; o.beta1 = c.beta1; o.beta2 = c.beta2; o.eps = c.eps; o.weight_decay = c.weight_decay;
   o.grad_scale = 1.f; o.zero_grad = 1;
+  return o;
+}
+inline mhimx_optim_args optim_args_of(const mhimx_step_cfg& c, int64_t host_step, bool with_teacher) {
+  mhimx_optim_args o = optim_args_of(c, host_step);
   if (with_teacher) { o.teacher = c.p_teacher; o.ema_mm = c.ema_mm; o.mm_table = c.mm_table; o.mm_len = c.mm_len; }
   return o;
 }

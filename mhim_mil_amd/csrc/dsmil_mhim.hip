@@ -26,10 +26,10 @@
 //                                      the token slots' zero rows, every kept row's position in its list
 //   B. Merge forward, bag after bag (4 launches per bag: rows pass, partial merge, O, to_out; + 1 mhimx_prep_batch per 8 bags past the
 //      first 8): the k tokens land in the bag's token slot.  Every bag attends with the call's first queries.
-//   C. the student, token-space-wide (12 launches)
+//   C. the student, token-space-wide (12 launches, through dsmil_student.hpp's ds_forward, ds_head and ds_backward)
 //      1  infer_project_kernel         tokens -> V
 //      2-4  dsmil_rows / crit / pool   Q, classes, critical rows, pool partials
-//      5  dm_head_kernel               NEW: dw_head_kernel + the distillation: B, fcc, the mix, CE, cl = mean_c SoftTargetCE(B[c],
+//      5  ds_head_kernel<DsDist>       (dsmil_student.hpp) the teacher-free head + the distillation: B, fcc, the mix, CE, cl = mean_c SoftTargetCE(B[c],
 //                                      B_teacher[c], temp_t); d B = Wfcc^T g_lb + aux_alpha / (n C) (softmax(B[c]) - softmax(B_t[c] / temp_t))
 //      6  dw_rows1_kernel              (dsmil_window.hip) d a, d PreV over V in place, the tiles' d bv and d q_max partials
 //      7  infer_project_kernel         d PreV Wv
@@ -54,7 +54,7 @@
 #include <math.h>
 #include <string.h>
 
-#include "infer_tab.hpp"
+#include "dsmil_student.hpp"
 
 namespace mhimx {
 
@@ -63,7 +63,7 @@ int64_t merge2_ws_bytes(int64_t R, int64_t k);
 
 namespace {
 
-constexpr int DM_Q = 128, DM_MAXC = 16, DM_ROWS = RG_ROWS, DM_T = 256;
+constexpr int DM_Q = DS_Q, DM_MAXC = DS_MAXC, DM_ROWS = RG_ROWS, DM_T = 256;
 constexpr int DM_MAX = MHIMX_DSMIL_MHIM_WINDOW_MAX;
 constexpr int DM_GATHER_Y = 64;                                  // gather workgroups per bag
 static_assert(DM_MAX == MHIMX_INFER_MAX, "the by-value bag table is the inference call's");
@@ -75,7 +75,6 @@ struct DmCnt {
   int64_t tok0[DM_MAX], mrg0[DM_MAX];                            // first row of the bag in the token space / in the merge buffer
   int32_t len_keep[DM_MAX], Lk[DM_MAX], tslot[DM_MAX];           // tslot: rows of the bag's token slot
 };
-struct DmLabels { const int64_t* p[DM_MAX]; };
 
 // ------------------------------------------------------------------------------------------------ A10. gather
 // blockIdx.x = bag, blockIdx.y = a share of the bag's list.  One wave per list entry j: row rows[j] of the student's feature rows goes to
@@ -107,166 +106,6 @@ __global__ __launch_bounds__(DM_T) void dm_gather_kernel(InferTab tab, DmCnt cn,
     const int first = Lk + k;
     f32x4* dst = reinterpret_cast<f32x4*>(T + (tok0 + first) * IE);
     for (int f = tid; f < (tslot - first) * (IE / 4); f += DM_T) dst[f] = z4;
-  }
-}
-
-// {max, sum} style block reductions of dm_head_kernel: wave results combined in index order (red: 8 floats of LDS)
-MHIMX_DEV float dm_blk_max(float v, float* red) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  v = wave_max(v);
-  if (lane == 0) red[wave] = v;
-  __syncthreads();
-  float r = red[0];
-#pragma unroll
-  for (int w = 1; w < 8; ++w) r = fmaxf(r, red[w]);
-  __syncthreads();
-  return r;
-}
-MHIMX_DEV float dm_blk_sum(float v, float* red) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  v = wave_sum(v);
-  if (lane == 0) red[wave] = v;
-  __syncthreads();
-  float r = 0.f;
-#pragma unroll
-  for (int w = 0; w < 8; ++w) r += red[w];
-  __syncthreads();
-  return r;
-}
-
-// ------------------------------------------------------------------------------------------------ C5. merge + fcc + mix + CE + distillation
-// blockIdx.x = bag; thread e = column e.  dw_head_kernel (dsmil_window.hip) with the per-class distillation of mhimx_dsmil_head
-// (optim.hip: dsmil_head_kernel) between the forward and the head gradients: cl = mean_c [ - sum_e softmax(Bt[c] / temp_t)_e
-// log_softmax(B[c])_e ], d B[c] += aux_alpha inv_n / C (softmax(B[c]) - softmax(Bt[c] / temp_t)).  Bt NULL: no distillation term.
-__global__ __launch_bounds__(RG_FIN_T) void dm_head_kernel(InferTab tab, DmLabels lab, const float* __restrict__ pm, const float* __restrict__ pl,
-                                                         const float* __restrict__ pB, const float* __restrict__ H,
-                                                         const float* __restrict__ wfcc, const float* __restrict__ bfcc,
-                                                         const float* __restrict__ logits_ins, const int64_t* __restrict__ crit,
-                                                         const float* __restrict__ Bt, int C, float temp_t, float main_alpha, float aux_alpha,
-                                                         float inv_n, float* __restrict__ logits_bag, float* __restrict__ logits,
-                                                         float* __restrict__ losses, float* __restrict__ B_out, float* __restrict__ stats,
-                                                         float* __restrict__ gli, float* __restrict__ dB, float* __restrict__ delta,
-                                                         float* __restrict__ dwfcc_part, float* __restrict__ dbfcc_part,
-                                                         float* __restrict__ dwi_part, float* __restrict__ dbi_part) {
-  __shared__ float red[8];
-  __shared__ float wgt[RG_FIN_T];
-  __shared__ float smx[DM_MAXC], sinv[DM_MAXC], lg[DM_MAXC], gl[DM_MAXC];
-  __shared__ float dl[DM_MAXC][8];
-  __shared__ __attribute__((aligned(16))) float big[DM_MAXC * IE];   // B [C][512]
-  const int bag = blockIdx.x;
-  RG_BAG(bag)
-  const int64_t* label = lab.p[0];
-  RG_PICK(label, lab.p, bag)
-  const int G = rg_parts(N);
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  pm += (int64_t)p0 * DM_MAXC; pl += (int64_t)p0 * DM_MAXC; pB += (int64_t)p0 * C * IE;
-  for (int c = 0; c < C; ++c) {
-    float mx, Ls;
-    rg_merge_stats(pm + c, pl + c, G, DM_MAXC, red, mx, Ls);
-    if (tid == 0) {
-      smx[c] = mx; sinv[c] = 1.f / Ls;
-      stats[((int64_t)bag * DM_MAXC + c) * 2] = mx;
-      stats[((int64_t)bag * DM_MAXC + c) * 2 + 1] = 1.f / Ls;
-    }
-    __syncthreads();
-  }
-  for (int c = 0; c < C; ++c) {
-    const float mx = smx[c];
-    float acc = 0.f;                                            // column tid of B[c]
-    for (int base = 0; base < G; base += RG_FIN_T) {
-      __syncthreads();
-      wgt[tid] = base + tid < G ? __expf(pm[(int64_t)(base + tid) * DM_MAXC + c] - mx) : 0.f;
-      __syncthreads();
-      const int cnt = G - base < RG_FIN_T ? G - base : RG_FIN_T;
-#pragma unroll 8
-      for (int j = 0; j < cnt; ++j) acc += pB[((int64_t)(base + j) * C + c) * IE + tid] * wgt[j];
-    }
-    const float bv = acc * sinv[c];
-    big[c * IE + tid] = bv;
-    B_out[((int64_t)bag * C + c) * IE + tid] = bv;
-  }
-  __syncthreads();
-  for (int o = wave; o < C; o += RG_FIN_T / 64) {
-    float d = 0.f;
-    for (int c = 0; c < C; ++c) {
-      const float* w = wfcc + ((int64_t)o * C + c) * IE;
-#pragma unroll
-      for (int q = 0; q < IE / 64; ++q) d += big[c * IE + lane + 64 * q] * w[lane + 64 * q];
-    }
-    d = wave_sum(d);
-    if (lane == 0) {
-      const float lb = d + bfcc[o];
-      const float mix = 0.5f * lb + 0.5f * logits_ins[(int64_t)bag * C + o];
-      logits_bag[(int64_t)bag * C + o] = lb;
-      logits[(int64_t)bag * C + o] = mix;
-      lg[o] = mix;
-    }
-  }
-  __syncthreads();
-  // ---- distillation: this thread's column of d cl / d B[c] (scaled) stays in dist[c]; every thread ends with the same cl
-  float cl = 0.f;
-  float dist[DM_MAXC];
-#pragma unroll
-  for (int c = 0; c < DM_MAXC; ++c) dist[c] = 0.f;
-  if (Bt) {
-    const float gs = aux_alpha * inv_n / (float)C;
-#pragma unroll
-    for (int c = 0; c < DM_MAXC; ++c)
-      if (c < C) {
-        const float s = big[c * IE + tid], t = Bt[((int64_t)bag * C + c) * IE + tid] / temp_t;
-        const float s_mx = dm_blk_max(s, red), t_mx = dm_blk_max(t, red);
-        const float es = expf(s - s_mx), et = expf(t - t_mx);
-        const float s_den = dm_blk_sum(es, red), t_den = dm_blk_sum(et, red);
-        const float pt = et / t_den;
-        cl -= dm_blk_sum(pt * (s - s_mx - logf(s_den)), red) / (float)C;
-        dist[c] = gs * (es / s_den - pt);
-      }
-  }
-  if (tid == 0) {
-    // torch.nn.CrossEntropyLoss on one row (a label outside [0, C): NaN, where torch raises); g_lb = g_li = 0.5 g_logits
-    float cm = lg[0];
-    for (int c = 1; c < C; ++c) cm = fmaxf(cm, lg[c]);
-    float den = 0.f;
-    for (int c = 0; c < C; ++c) den += expf(lg[c] - cm);
-    const int64_t y = label[0];
-    const bool ok = y >= 0 && y < C;
-    const float ce = ok ? (cm + logf(den)) - lg[ok ? y : 0] : NAN;
-    losses[3 * bag] = main_alpha * ce + aux_alpha * cl;
-    losses[3 * bag + 1] = ce;
-    losses[3 * bag + 2] = cl;
-    for (int c = 0; c < DM_MAXC; ++c) {
-      const float g = c < C ? (ok ? 0.5f * (main_alpha * (expf(lg[c] - cm) / den - (c == y ? 1.f : 0.f)) * inv_n) : NAN) : 0.f;
-      gl[c] = g;
-      gli[(int64_t)bag * DM_MAXC + c] = g;
-      if (c < C) { dbfcc_part[(int64_t)bag * C + c] = g; dbi_part[(int64_t)bag * C + c] = g; }
-    }
-  }
-  __syncthreads();
-#pragma unroll
-  for (int c = 0; c < DM_MAXC; ++c)
-    if (c < C) {
-      const float b = big[c * IE + tid];
-      float db = 0.f;
-      for (int o = 0; o < C; ++o) {
-        db = fmaf(wfcc[((int64_t)o * C + c) * IE + tid], gl[o], db);
-        dwfcc_part[(((int64_t)bag * C + o) * C + c) * IE + tid] = gl[o] * b;
-      }
-      db += dist[c];
-      dB[((int64_t)bag * DM_MAXC + c) * IE + tid] = db;
-      int64_t cr = crit[(int64_t)bag * C + c];
-      if (cr < 0 || cr >= N) cr = 0;                            // (a class whose logits are all NaN has no critical row)
-      dwi_part[((int64_t)bag * C + c) * IE + tid] = gl[c] * H[(orow0 + cr) * IE + tid];
-      const float d = wave_sum(db * b);
-      if (lane == 0) dl[c][wave] = d;
-    }
-  __syncthreads();
-  if (tid < DM_MAXC) {
-    float t = 0.f;
-    if (tid < C) {
-#pragma unroll
-      for (int w = 0; w < 8; ++w) t += dl[tid][w];
-    }
-    delta[(int64_t)bag * DM_MAXC + tid] = t;
   }
 }
 
@@ -328,19 +167,19 @@ __global__ __launch_bounds__(DM_T) void dm_scatter_kernel(InferTab tab, DmCnt cn
 
 // ------------------------------------------------------------------------------------------------ host
 struct DmLay {
+  DsLay s;                                    // the student's share, over the token space (dsmil_student.hpp)
   // weight images
-  int64_t w1p_t, w1p_s, vp_t, q0f_t, q2f_t, vp, vtp, q0f, q2f, q2tf, q0tf, wo_t;
-  // per-bag heads
-  int64_t logits, losses, logits_bag, logits_ins, B, crit, B_t, lb_t, lg_t, li_t, crit_t, qmax_t, qmax, stats, gli, dB, delta, dqmax, dwfcc_part,
-      dbfcc_part, dwi_part, dbi_part;
+  int64_t w1p_t, w1p_s, vp_t, q0f_t, q2f_t, wo_t;
+  // the teacher's per-bag heads
+  int64_t B_t, lb_t, lg_t, li_t, crit_t, qmax_t;
   // bag space
   int64_t H_t, H_s, dact, V_t, Q_t, cls_t, score, rows_all, pos, db1_part, pmax_t, parg_t, pm_t, pl_t, pB_t, slab_1;
-  // token space
-  int64_t T, V, dhv, Q, cls, da, U1, dPQ, dP1, pmax, parg, pm, pl, pB, dbv_part, dbq0_part, dbq2_part, dqm_part, slab_v, slab_q0, slab_q2;
+  // the tokens
+  int64_t T;
   // the rows to merge and the per-bag Merge workspaces; the select's scratch
   int64_t Xm, dXm, merge_ws[DM_MAX], merge_ws_bytes[DM_MAX], sel_ws, sel_ws_bytes, sel_perm, sel_ids, sel_rows, sel_lk;
   int64_t total, rows, trows, mrows;
-  int32_t steps, tsteps, s1, s1_per, sv, sv_per, sq0, sq0_per, sq2, sq2_per;
+  int32_t steps, s1, s1_per;
 };
 
 mhimx_merge dm_merge_params(const mhimx_dsmil_mhim_cfg& c) {
@@ -351,34 +190,17 @@ mhimx_merge dm_merge_params(const mhimx_dsmil_mhim_cfg& c) {
   return m;
 }
 
-bool dm_params_ok(const mhimx_dsmil_params& p) {
-  return p.w1 && p.b1 && p.wi && p.bi && p.wq0 && p.bq0 && p.wq2 && p.bq2 && p.wv && p.bv && p.wfcc && p.bfcc;
-}
-bool dm_params_aligned(const mhimx_dsmil_params& p) {
-  return aligned16(p.w1) && aligned16(p.b1) && aligned16(p.wi) && aligned16(p.wq0) && aligned16(p.wq2) && aligned16(p.wv) && aligned16(p.bv);
-}
-
 int check_dm(const mhimx_dsmil_mhim_cfg* cfg, int32_t n_bags, const mhimx_ragged_window_bag* bags, int32_t xdt = MHIMX_X_F32) {
   const char* who = "dsmil_mhim_window";
-  if (int r = rg_check_xdt(who, xdt)) return r;
-  MHIMX_CHECK_ARG(cfg && bags, "dsmil_mhim_window: null configuration / bag list");
-  MHIMX_CHECK_ARG(n_bags >= 1 && n_bags <= DM_MAX, "dsmil_mhim_window: 1..%d bags per window (got %d)", DM_MAX, n_bags);
-  const mhimx_dsmil_train_cfg* c = &cfg->base;
-  MHIMX_CHECK_ARG(c->E == IE && c->C >= 1 && c->C <= DM_MAXC && c->D > 0 && c->D % 256 == 0 && c->D <= (1 << 20),
-                  "dsmil_mhim_window: shapes outside the ragged MHIM(DSMIL) window (E = 512, q width 128, 1 <= C <= %d, D %% 256 == 0, D <= 2^20)", DM_MAXC);
+  const mhimx_dsmil_train_cfg* c = cfg ? &cfg->base : nullptr;
+  if (int r = ds_check_base(who, c, xdt, n_bags, DM_MAX, bags, "student ")) return r;
   MHIMX_CHECK_ARG(cfg->k >= 1 && 8 * cfg->k <= 48, "dsmil_mhim_window: merge_k outside 1..6 (8 k <= 48)");
-  MHIMX_CHECK_ARG(c->act >= MHIMX_ACT_NONE && c->act <= MHIMX_ACT_TANH, "dsmil_mhim_window: unknown activation");
-  MHIMX_CHECK_ARG(c->drop_p >= 0.f && c->drop_p < 1.f && cfg->drop_p_teacher >= 0.f && cfg->drop_p_teacher < 1.f && cfg->merge_drop_p >= 0.f &&
-                      cfg->merge_drop_p < 1.f,
+  MHIMX_CHECK_ARG(cfg->drop_p_teacher >= 0.f && cfg->drop_p_teacher < 1.f && cfg->merge_drop_p >= 0.f && cfg->merge_drop_p < 1.f,
                   "dsmil_mhim_window: dropout probability outside [0,1)");
   MHIMX_CHECK_ARG(cfg->temp_t > 0.f, "dsmil_mhim_window: the distillation temperature must be positive");
-  MHIMX_CHECK_ARG(dm_params_ok(c->param), "dsmil_mhim_window: null student parameter");
-  MHIMX_CHECK_ARG(dm_params_ok(cfg->teacher), "dsmil_mhim_window: null teacher parameter");
-  MHIMX_CHECK_ARG(dm_params_aligned(c->param) && dm_params_aligned(cfg->teacher),
-                  "dsmil_mhim_window: the feature, i_classifier, q and v weights of both models must be 16-byte aligned");
-  const mhimx_dsmil_grads& g = c->grad;
-  MHIMX_CHECK_ARG(g.w1 && g.b1 && g.wi && g.bi && g.wq0 && g.bq0 && g.wq2 && g.bq2 && g.wv && g.bv && g.wfcc && g.bfcc,
-                  "dsmil_mhim_window: null gradient view");
+  MHIMX_CHECK_ARG(ds_params_ok(cfg->teacher), "dsmil_mhim_window: null teacher parameter");
+  MHIMX_CHECK_ARG(ds_params_aligned(cfg->teacher),
+                  "dsmil_mhim_window: the feature, i_classifier, q and v weights of the teacher model must be 16-byte aligned");
   const mhimx_dsmil_merge_params& m = cfg->merge;
   MHIMX_CHECK_ARG(m.ln_w && m.ln_b && m.wkv && m.wq && m.wo && m.bo && cfg->q, "dsmil_mhim_window: null Merge parameter / global queries");
   MHIMX_CHECK_ARG(aligned16(m.ln_w) && aligned16(m.ln_b) && aligned16(m.wkv) && aligned16(m.wq) && aligned16(m.wo) && aligned16(cfg->q) &&
@@ -386,7 +208,6 @@ int check_dm(const mhimx_dsmil_mhim_cfg* cfg, int32_t n_bags, const mhimx_ragged
                   "dsmil_mhim_window: the Merge weights and the global queries must be 16-byte aligned");
   const mhimx_dsmil_merge_grads& mg = cfg->merge_grad;
   MHIMX_CHECK_ARG(mg.ln_w && mg.ln_b && mg.wkv && mg.wq && mg.wo && mg.bo, "dsmil_mhim_window: null Merge gradient view");
-  MHIMX_CHECK_ARG(c->tick, "dsmil_mhim_window: the device dropout / draw counter (tick) is required");
   const mhimx_merge mw = dm_merge_params(*cfg);
   int64_t rows = 0;
   for (int b = 0; b < n_bags; ++b) {
@@ -434,47 +255,21 @@ void dm_layout(const mhimx_dsmil_mhim_cfg* cfg, int32_t n_bags, const mhimx_ragg
   const int64_t rows = cnt.rows, parts = cnt.parts, trows = cnt2.rows, tparts = cnt2.parts;
   w->rows = rows; w->trows = trows; w->mrows = mrows;
   w->steps = (int32_t)(rows / DM_ROWS);
-  w->tsteps = (int32_t)(trows / DM_ROWS);
-  // split-K slabs (dsmil_window.hip's rule): d W1 over the bag space, the three others over the token space
+  // d W1's split-K slabs over the bag space (dsmil_window.hip's rule); the student's three over the token space
   const int s1_room = pw_split_k(w->steps, 8, 8, &w->s1, &w->s1_per);
-  const int sv_room = pw_split_k(w->tsteps, 16, 4, &w->sv, &w->sv_per);
-  const int sq0_room = pw_split_k(w->tsteps, 64, 4, &w->sq0, &w->sq0_per);
-  const int sq2_room = pw_split_k(w->tsteps, 64, 2, &w->sq2, &w->sq2_per);
   Arena ar(nullptr, 0);
   w->w1p_t = ar.off; ar.take<float>(E * D);
   w->w1p_s = ar.off; ar.take<float>(E * D);
   w->vp_t = ar.off; ar.take<float>(E * E);
   w->q0f_t = ar.off; ar.take<float>(DM_Q * E);
   w->q2f_t = ar.off; ar.take<float>(DM_Q * DM_Q);
-  w->vp = ar.off; ar.take<float>(E * E);
-  w->vtp = ar.off; ar.take<float>(E * E);
-  w->q0f = ar.off; ar.take<float>(DM_Q * E);
-  w->q2f = ar.off; ar.take<float>(DM_Q * DM_Q);
-  w->q2tf = ar.off; ar.take<float>(DM_Q * DM_Q);
-  w->q0tf = ar.off; ar.take<float>(DM_Q * E);
   w->wo_t = ar.off; ar.take<float>(512 * E);
-  w->logits = ar.off; ar.take<float>(n * C);
-  w->losses = ar.off; ar.take<float>(n * 3);
-  w->logits_bag = ar.off; ar.take<float>(n * C);
-  w->logits_ins = ar.off; ar.take<float>(n * C);
-  w->B = ar.off; ar.take<float>(n * C * E);
-  w->crit = ar.off; ar.take<int64_t>(n * C);
   w->B_t = ar.off; ar.take<float>(n * C * E);
   w->lb_t = ar.off; ar.take<float>(n * C);
   w->lg_t = ar.off; ar.take<float>(n * C);
   w->li_t = ar.off; ar.take<float>(n * C);
   w->crit_t = ar.off; ar.take<int64_t>(n * C);
   w->qmax_t = ar.off; ar.take<float>(n * DM_MAXC * DM_Q);
-  w->qmax = ar.off; ar.take<float>(n * DM_MAXC * DM_Q);
-  w->stats = ar.off; ar.take<float>(n * DM_MAXC * 2);
-  w->gli = ar.off; ar.take<float>(n * DM_MAXC);
-  w->dB = ar.off; ar.take<float>(n * DM_MAXC * E);
-  w->delta = ar.off; ar.take<float>(n * DM_MAXC);
-  w->dqmax = ar.off; ar.take<float>(n * DM_MAXC * DM_Q);
-  w->dwfcc_part = ar.off; ar.take<float>(n * C * C * E);
-  w->dbfcc_part = ar.off; ar.take<float>(n * C);
-  w->dwi_part = ar.off; ar.take<float>(n * C * E);
-  w->dbi_part = ar.off; ar.take<float>(n * C);
   // ---- the bag space (V_t: the teacher's V rows, and - the teacher is done by then - the dPRE rows of the tail)
   w->H_t = ar.off; ar.take<float>(rows * E);
   w->H_s = ar.off; ar.take<float>(rows * E);
@@ -492,28 +287,9 @@ void dm_layout(const mhimx_dsmil_mhim_cfg* cfg, int32_t n_bags, const mhimx_ragg
   w->pl_t = ar.off; ar.take<float>(parts * DM_MAXC);
   w->pB_t = ar.off; ar.take<float>(parts * C * E);
   w->slab_1 = ar.off; ar.take<float>((int64_t)s1_room * E * D);
-  // ---- the token space
+  // ---- the token space: the tokens and the student's share
   w->T = ar.off; ar.take<float>(trows * E);
-  w->V = ar.off; ar.take<float>(trows * E);
-  w->dhv = ar.off; ar.take<float>(trows * E);
-  w->Q = ar.off; ar.take<float>(trows * DM_Q);
-  w->cls = ar.off; ar.take<float>(trows * DM_MAXC);
-  w->da = ar.off; ar.take<float>(trows * DM_MAXC);
-  w->U1 = ar.off; ar.take<float>(trows * DM_Q);
-  w->dPQ = ar.off; ar.take<float>(trows * DM_Q);
-  w->dP1 = ar.off; ar.take<float>(trows * DM_Q);
-  w->pmax = ar.off; ar.take<float>(tparts * DM_MAXC);
-  w->parg = ar.off; ar.take<int32_t>(tparts * DM_MAXC);
-  w->pm = ar.off; ar.take<float>(tparts * DM_MAXC);
-  w->pl = ar.off; ar.take<float>(tparts * DM_MAXC);
-  w->pB = ar.off; ar.take<float>(tparts * C * E);
-  w->dbv_part = ar.off; ar.take<float>((int64_t)w->tsteps * E);
-  w->dbq0_part = ar.off; ar.take<float>((int64_t)w->tsteps * DM_Q);
-  w->dbq2_part = ar.off; ar.take<float>((int64_t)w->tsteps * DM_Q);
-  w->dqm_part = ar.off; ar.take<float>((int64_t)w->tsteps * DM_MAXC * DM_Q);
-  w->slab_v = ar.off; ar.take<float>((int64_t)sv_room * E * E);
-  w->slab_q0 = ar.off; ar.take<float>((int64_t)sq0_room * DM_Q * E);
-  w->slab_q2 = ar.off; ar.take<float>((int64_t)sq2_room * DM_Q * DM_Q);
+  ds_take(ar, &w->s, n, C, trows, tparts, (int32_t)(trows / DM_ROWS));
   // ---- the rows to merge, their gradient rows, every bag's own Merge workspace (the forward leaves there what the backward reads)
   w->Xm = ar.off; ar.take<float>(mrows * E);
   w->dXm = ar.off; ar.take<float>(mrows * E);
@@ -543,8 +319,8 @@ extern "C" int mhimx_dsmil_mhim_window_layout_of(const mhimx_dsmil_mhim_cfg* cfg
   DmLay w;
   memset(out, 0, sizeof(*out));
   dm_layout(cfg, n_bags, bags, &w, nullptr, nullptr, nullptr, out->row0, out->tok0);
-  out->total = w.total; out->rows = w.rows; out->tok_rows = w.trows; out->logits = w.logits; out->losses = w.losses; out->logits_bag = w.logits_bag;
-  out->logits_ins = w.logits_ins; out->B = w.B; out->crit = w.crit; out->B_teacher = w.B_t; out->H_teacher = w.H_t; out->H_student = w.H_s;
+  out->total = w.total; out->rows = w.rows; out->tok_rows = w.trows; out->logits = w.s.logits; out->losses = w.s.losses; out->logits_bag = w.s.logits_bag;
+  out->logits_ins = w.s.logits_ins; out->B = w.s.B; out->crit = w.s.crit; out->B_teacher = w.B_t; out->H_teacher = w.H_t; out->H_student = w.H_s;
   out->dact = w.dact; out->score = w.score; out->rows_all = w.rows_all; out->tokens = w.T;
   return 0;
 }
@@ -579,12 +355,11 @@ extern "C" int mhimx_dsmil_mhim_window_run(void* stream, const mhimx_dsmil_mhim_
   const int D = (int)c.D, C = (int)c.C;
   const int64_t k = cfg->k;
   float *H_t = F(w.H_t), *H_s = F(w.H_s), *V_t = F(w.V_t), *Q_t = F(w.Q_t), *score = F(w.score);
-  float *T = F(w.T), *V = F(w.V), *dhv = F(w.dhv), *Q = F(w.Q), *Xm = F(w.Xm), *dXm = F(w.dXm);
+  float *T = F(w.T), *dhv = F(w.s.dhv), *Xm = F(w.Xm), *dXm = F(w.dXm);
   float* dpre = V_t;                           // (the teacher's V rows are dead behind A.8)
   _Float16* dact = reinterpret_cast<_Float16*>(base + w.dact);
   int64_t* rows_space = reinterpret_cast<int64_t*>(base + w.rows_all);
   int32_t* pos = reinterpret_cast<int32_t*>(base + w.pos);
-  int64_t* crit = reinterpret_cast<int64_t*>(base + w.crit);
   const uint64_t* tick = c.tick;
   float* q_dst = cfg->q_out ? cfg->q_out : cfg->q;
 
@@ -601,12 +376,7 @@ extern "C" int mhimx_dsmil_mhim_window_run(void* stream, const mhimx_dsmil_mhim_
     jobs[n++] = mhimx_prep_job{1, Tp.wv, F(w.vp_t), c.E, c.E};
     jobs[n++] = mhimx_prep_job{4, Tp.wq0, F(w.q0f_t), DM_Q, c.E};
     jobs[n++] = mhimx_prep_job{4, Tp.wq2, F(w.q2f_t), DM_Q, DM_Q};
-    jobs[n++] = mhimx_prep_job{1, P.wv, F(w.vp), c.E, c.E};
-    jobs[n++] = mhimx_prep_job{7, P.wv, F(w.vtp), c.E, c.E};
-    jobs[n++] = mhimx_prep_job{4, P.wq0, F(w.q0f), DM_Q, c.E};
-    jobs[n++] = mhimx_prep_job{4, P.wq2, F(w.q2f), DM_Q, DM_Q};
-    jobs[n++] = mhimx_prep_job{5, P.wq2, F(w.q2tf), DM_Q, DM_Q};
-    jobs[n++] = mhimx_prep_job{5, P.wq0, F(w.q0tf), DM_Q, c.E};
+    n += ds_prep_jobs(P, base, w.s, jobs + n);
     jobs[n++] = mhimx_prep_job{0, cfg->merge.wo, F(w.wo_t), c.E, 512};
     if (cfg->q_out) jobs[n++] = mhimx_prep_job{2, cfg->q, cfg->q_out, 1, k * c.E};
     for (int b = 0; b < n_bags && b < 8; ++b)
@@ -672,31 +442,16 @@ extern "C" int mhimx_dsmil_mhim_window_run(void* stream, const mhimx_dsmil_mhim_
   }
 
   // ================================================================================================ C. the student, token-space-wide
-  InferTab tabt = tab2;
-  for (int b = 0; b < n_bags; ++b) tabt.X[b] = T + tab2.row0[b] * IE;
-  if (int r = infer_project(st, tabt, IE, F(w.vp), P.bv, MHIMX_ACT_RELU, V)) return r;
-  if (int r = dsmil_rows_crit_pool(st, tab2, T, V, F(w.q0f), P.bq0, F(w.q2f), P.bq2, P.wi, P.bi, C, Q, F(w.cls), F(w.pmax),
-                                   reinterpret_cast<int32_t*>(base + w.parg), F(w.qmax), F(w.logits_ins), crit, F(w.pm), F(w.pl), F(w.pB)))
-    return r;
+  // the tokens have no d out / d pre of their own (it lives in the bag space; the k Merge tokens have none): plain d tokens, no d b1 partials.
+  // The head is always the distillation instantiation; Bt NULL when aux_alpha == 0
+  if (int r = ds_forward(st, tab2, base, w.s, P, C, T)) return r;
   {
-    DmLabels lab = {};
+    DsLabels lab = {};
     for (int b = 0; b < n_bags; ++b) lab.p[b] = bags[b].label_dev;
-    const float* Bt = cfg->aux_alpha != 0.f ? F(w.B_t) : nullptr;
-    hipLaunchKernelGGL(dm_head_kernel, dim3((unsigned)n_bags), dim3(RG_FIN_T), 0, st, tab2, lab, F(w.pm), F(w.pl), F(w.pB), T, P.wfcc, P.bfcc, F(w.logits_ins),
-                       crit, Bt, C, cfg->temp_t, c.main_alpha, cfg->aux_alpha, 1.f / (float)n_bags, F(w.logits_bag), F(w.logits), F(w.losses), F(w.B),
-                       F(w.stats), F(w.gli), F(w.dB), F(w.delta), F(w.dwfcc_part), F(w.dbfcc_part), F(w.dwi_part), F(w.dbi_part));
-    MHIMX_LAUNCH_CHECK();
+    const DsDist dist = {cfg->aux_alpha != 0.f ? F(w.B_t) : nullptr, cfg->temp_t, cfg->aux_alpha};
+    if (int r = ds_head(st, tab2, base, w.s, P, C, T, lab, c.main_alpha, dist)) return r;
   }
-  if (int r = dw_rows1(st, tab2, w.tsteps, V, Q, F(w.qmax), F(w.stats), F(w.dB), F(w.delta), C, F(w.da), F(w.dbv_part), F(w.dqm_part))) return r;
-  for (int b = 0; b < n_bags; ++b) tabt.X[b] = V + tab2.row0[b] * IE;
-  if (int r = infer_project(st, tabt, IE, F(w.vtp), nullptr, MHIMX_ACT_NONE, dhv)) return r;
-  if (int r = dw_dqmax(st, tab2, F(w.dqm_part), F(w.dqmax))) return r;
-  if (int r = dw_rows2_plain(st, tab2, w.tsteps, T, Q, F(w.da), F(w.qmax), F(w.dqmax), crit, F(w.gli), P.wi, F(w.q0f), P.bq0, F(w.q2tf), F(w.q0tf), C, dhv,
-                             F(w.U1), F(w.dPQ), F(w.dP1), F(w.dbq0_part), F(w.dbq2_part)))
-    return r;
-  if (int r = pw_wgrad_rows(st, tab2, V, IE, IE, T, IE, IE, w.tsteps, w.sv, w.sv_per, F(w.slab_v))) return r;
-  if (int r = pw_wgrad_rows(st, tab2, F(w.dPQ), DM_Q, DM_Q, F(w.U1), DM_Q, DM_Q, w.tsteps, w.sq2, w.sq2_per, F(w.slab_q2))) return r;
-  if (int r = pw_wgrad_rows(st, tab2, F(w.dP1), DM_Q, DM_Q, T, IE, IE, w.tsteps, w.sq0, w.sq0_per, F(w.slab_q0))) return r;
+  if (int r = ds_backward(st, tab2, base, w.s, P, C, T, nullptr, nullptr)) return r;
 
   // ================================================================================================ D. Merge backward, bag after bag
   // d X of the bag's R merged rows from its k tokens' gradient rows; the six Merge gradients accumulate in bag order on the one stream:
@@ -720,29 +475,14 @@ extern "C" int mhimx_dsmil_mhim_window_run(void* stream, const mhimx_dsmil_mhim_
   hipLaunchKernelGGL(dm_scatter_kernel, dim3((unsigned)w.steps), dim3(DM_T), 0, st, tab, cn, rows_space, pos, dhv, dXm, dact, dpre, F(w.db1_part));
   MHIMX_LAUNCH_CHECK();
   if (int r = pw_wgrad_bagx(st, tab, dpre, D, w.steps, w.s1, w.s1_per, F(w.slab_1))) return r;
-  {
-    const mhimx_dsmil_grads& G_ = c.grad;
-    const float* parts[6] = {F(w.slab_1), F(w.slab_v), F(w.slab_q0), F(w.slab_q2), F(w.dwfcc_part), F(w.dwi_part)};
-    const int32_t G[6] = {w.s1, w.sv, w.sq0, w.sq2, n_bags, n_bags};
-    const int64_t W[6] = {(int64_t)c.E * c.D, (int64_t)c.E * c.E, (int64_t)DM_Q * c.E, (int64_t)DM_Q * DM_Q, (int64_t)C * C * c.E, (int64_t)C * c.E};
-    float* out[6] = {G_.w1, G_.wv, G_.wq0, G_.wq2, G_.wfcc, G_.wi};
-    if (int r = pw_reduce(st, 6, parts, G, W, out)) return r;
-    const float* parts2[6] = {F(w.db1_part), F(w.dbv_part), F(w.dbq0_part), F(w.dbq2_part), F(w.dbfcc_part), F(w.dbi_part)};
-    const int32_t G2[6] = {w.steps, w.tsteps, w.tsteps, w.tsteps, n_bags, n_bags};
-    const int64_t W2[6] = {c.E, c.E, DM_Q, DM_Q, C, C};
-    float* out2[6] = {G_.b1, G_.bv, G_.bq0, G_.bq2, G_.bfcc, G_.bi};
-    if (int r = pw_reduce(st, 6, parts2, G2, W2, out2)) return r;
-  }
+  if (int r = ds_reduce(st, base, w.s, c.grad, D, C, n_bags, F(w.slab_1), w.s1, F(w.db1_part), w.steps)) return r;
   {
     int64_t tok[DM_MAX];
     for (int b = 0; b < n_bags; ++b) tok[b] = cn.tok0[b] + cn.Lk[b];
     if (int r = rw_q_chain(st, q_dst, T, n_bags, tok, (double)cfg->merge_mm, (int)(k * c.E))) return r;
   }
   if (!update) return 0;
-  mhimx_optim_args o = {};
-  o.p = c.p; o.g = c.g; o.m = c.m; o.v = c.v; o.n_train = c.n_train; o.n_all = c.n_all; o.step = host_step; o.step_dev = c.opt_step;
-  o.lr = c.lr; o.lr_table = c.lr_table; o.lr_len = c.lr_len; o.beta1 = c.beta1; o.beta2 = c.beta2; o.eps = c.eps; o.weight_decay = c.weight_decay;
-  o.grad_scale = 1.f; o.zero_grad = 1;
+  mhimx_optim_args o = optim_args_of(c, host_step);
   o.teacher = cfg->p_teacher; o.ema_mm = cfg->ema_mm; o.mm_table = cfg->mm_table; o.mm_len = cfg->mm_len;
   return mhimx_optim_step(stream, &o);
 }

@@ -17,7 +17,7 @@
 //   4  dsmil_rows_kernel           (infer_dsmil.hip, as it is) Q, classes, per-chunk arg-max partials
 //   5  dsmil_crit_kernel           crit, logits_ins, q_max
 //   6  dsmil_pool_kernel           per-chunk softmax-pool partials
-//   7  dw_head_kernel              plane = bag: merge of the partials in index order -> B, fcc, the mix, CE; g_lb = g_li = 0.5 g_logits,
+//   7  ds_head_kernel<>            (dsmil_student.hpp) plane = bag: merge of the partials in index order -> B, fcc, the mix, CE; g_lb = g_li = 0.5 g_logits,
 //                                  d B = Wfcc^T g_lb, delta_c = d B[c] . B[c], the bag's d fcc / d i_classifier partials
 //   8  dw_rows1_kernel             one workgroup per 32-row tile: A again from Q and q_max, d A = V d B^T, d a = A (d A - delta),
 //                                  d PreV = (A d B) [V > 0] over V in place, the tile's d bv and d q_max partials
@@ -31,135 +31,23 @@
 //  18  mhimx_optim_step            Adam (update = 1)
 // No floating-point atomics, no workgroup waits for another, every sum has a fixed order.  What is written per bag depends on that bag's
 // N, seed and the tick alone.
+// The student from launch 3 on (but d W1, launch 15) is enqueued through dsmil_student.hpp's helpers, which are defined here and which
+// mhimx_dsmil_mhim_window_run (dsmil_mhim.hip) enqueues over its token space.
 #include <math.h>
 #include <string.h>
 
-#include "infer_tab.hpp"
+#include "dsmil_student.hpp"
 
 namespace mhimx {
 
 namespace {
 
-constexpr int DW_Q = 128, DW_MAXC = 16, DW_ROWS = RG_ROWS, DW_T = RG_T;
+constexpr int DW_Q = DS_Q, DW_MAXC = DS_MAXC, DW_ROWS = RG_ROWS, DW_T = RG_T;
 constexpr int DW_ULD = DW_Q + 4;                                 // pitch of a [32][128] tile in LDS
 constexpr float DW_SCALE = 0.08838834764831845f;                 // 1 / sqrt(128)
 constexpr size_t DW_R1_SMEM = (size_t)(DW_ROWS * RG_LD + DW_MAXC * DW_Q + DW_ROWS * DW_ULD + 2 * DW_ROWS * DW_MAXC) * sizeof(float);
 constexpr size_t DW_R2_SMEM = (size_t)(DW_ROWS * RG_LD) * sizeof(float);
 static_assert(3 * DW_ROWS * DW_ULD <= DW_ROWS * RG_LD, "U1, d PreQ and d Pre1 tiles reuse the feature tile's LDS");
-
-struct DwLabels { const int64_t* p[MHIMX_INFER_MAX]; };
-
-// ------------------------------------------------------------------------------------------------ 7. merge + fcc + mix + CE + head gradients
-// blockIdx.x = bag; thread e = column e.  The forward half is dsmil_finalize_kernel's y = 0 plane (same order of every sum).
-__global__ __launch_bounds__(RG_FIN_T) void dw_head_kernel(InferTab tab, DwLabels lab, const float* __restrict__ pm, const float* __restrict__ pl,
-                                                         const float* __restrict__ pB, const float* __restrict__ H,
-                                                         const float* __restrict__ wfcc, const float* __restrict__ bfcc,
-                                                         const float* __restrict__ logits_ins, const int64_t* __restrict__ crit, int C,
-                                                         float main_alpha, float inv_n, float* __restrict__ logits_bag,
-                                                         float* __restrict__ logits, float* __restrict__ losses, float* __restrict__ B_out,
-                                                         float* __restrict__ stats, float* __restrict__ gli, float* __restrict__ dB,
-                                                         float* __restrict__ delta, float* __restrict__ dwfcc_part,
-                                                         float* __restrict__ dbfcc_part, float* __restrict__ dwi_part,
-                                                         float* __restrict__ dbi_part) {
-  __shared__ float red[8];
-  __shared__ float wgt[RG_FIN_T];
-  __shared__ float smx[DW_MAXC], sinv[DW_MAXC], lg[DW_MAXC], gl[DW_MAXC];
-  __shared__ float dl[DW_MAXC][8];
-  __shared__ __attribute__((aligned(16))) float big[DW_MAXC * IE];   // B [C][512]
-  const int bag = blockIdx.x;
-  RG_BAG(bag)
-  const int64_t* label = lab.p[0];
-  RG_PICK(label, lab.p, bag)
-  const int G = rg_parts(N);
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  pm += (int64_t)p0 * DW_MAXC; pl += (int64_t)p0 * DW_MAXC; pB += (int64_t)p0 * C * IE;
-  for (int c = 0; c < C; ++c) {
-    float mx, Ls;
-    rg_merge_stats(pm + c, pl + c, G, DW_MAXC, red, mx, Ls);
-    if (tid == 0) {
-      smx[c] = mx; sinv[c] = 1.f / Ls;
-      stats[((int64_t)bag * DW_MAXC + c) * 2] = mx;
-      stats[((int64_t)bag * DW_MAXC + c) * 2 + 1] = 1.f / Ls;
-    }
-    __syncthreads();
-  }
-  for (int c = 0; c < C; ++c) {
-    const float mx = smx[c];
-    float acc = 0.f;                                            // column tid of B[c]
-    for (int base = 0; base < G; base += RG_FIN_T) {
-      __syncthreads();
-      wgt[tid] = base + tid < G ? __expf(pm[(int64_t)(base + tid) * DW_MAXC + c] - mx) : 0.f;
-      __syncthreads();
-      const int cnt = G - base < RG_FIN_T ? G - base : RG_FIN_T;
-#pragma unroll 8
-      for (int j = 0; j < cnt; ++j) acc += pB[((int64_t)(base + j) * C + c) * IE + tid] * wgt[j];
-    }
-    const float bv = acc * sinv[c];
-    big[c * IE + tid] = bv;
-    B_out[((int64_t)bag * C + c) * IE + tid] = bv;
-  }
-  __syncthreads();
-  for (int o = wave; o < C; o += RG_FIN_T / 64) {
-    float d = 0.f;
-    for (int c = 0; c < C; ++c) {
-      const float* w = wfcc + ((int64_t)o * C + c) * IE;
-#pragma unroll
-      for (int q = 0; q < IE / 64; ++q) d += big[c * IE + lane + 64 * q] * w[lane + 64 * q];
-    }
-    d = wave_sum(d);
-    if (lane == 0) {
-      const float lb = d + bfcc[o];
-      const float mix = 0.5f * lb + 0.5f * logits_ins[(int64_t)bag * C + o];
-      logits_bag[(int64_t)bag * C + o] = lb;
-      logits[(int64_t)bag * C + o] = mix;
-      lg[o] = mix;
-    }
-  }
-  __syncthreads();
-  if (tid == 0) {
-    // torch.nn.CrossEntropyLoss on one row (a label outside [0, C): NaN, where torch raises); g_lb = g_li = 0.5 g_logits
-    float cm = lg[0];
-    for (int c = 1; c < C; ++c) cm = fmaxf(cm, lg[c]);
-    float den = 0.f;
-    for (int c = 0; c < C; ++c) den += expf(lg[c] - cm);
-    const int64_t y = label[0];
-    const bool ok = y >= 0 && y < C;
-    const float ce = ok ? (cm + logf(den)) - lg[ok ? y : 0] : NAN;
-    losses[3 * bag] = main_alpha * ce;
-    losses[3 * bag + 1] = ce;
-    losses[3 * bag + 2] = 0.f;
-    for (int c = 0; c < DW_MAXC; ++c) {
-      const float g = c < C ? (ok ? 0.5f * (main_alpha * (expf(lg[c] - cm) / den - (c == y ? 1.f : 0.f)) * inv_n) : NAN) : 0.f;
-      gl[c] = g;
-      gli[(int64_t)bag * DW_MAXC + c] = g;
-      if (c < C) { dbfcc_part[(int64_t)bag * C + c] = g; dbi_part[(int64_t)bag * C + c] = g; }
-    }
-  }
-  __syncthreads();
-  for (int c = 0; c < C; ++c) {
-    const float b = big[c * IE + tid];
-    float db = 0.f;
-    for (int o = 0; o < C; ++o) {
-      db = fmaf(wfcc[((int64_t)o * C + c) * IE + tid], gl[o], db);
-      dwfcc_part[(((int64_t)bag * C + o) * C + c) * IE + tid] = gl[o] * b;
-    }
-    dB[((int64_t)bag * DW_MAXC + c) * IE + tid] = db;
-    int64_t cr = crit[(int64_t)bag * C + c];
-    if (cr < 0 || cr >= N) cr = 0;                              // (a class whose logits are all NaN has no critical row)
-    dwi_part[((int64_t)bag * C + c) * IE + tid] = gl[c] * H[(orow0 + cr) * IE + tid];
-    const float d = wave_sum(db * b);
-    if (lane == 0) dl[c][wave] = d;
-  }
-  __syncthreads();
-  if (tid < DW_MAXC) {
-    float t = 0.f;
-    if (tid < C) {
-#pragma unroll
-      for (int w = 0; w < 8; ++w) t += dl[tid][w];
-    }
-    delta[(int64_t)bag * DW_MAXC + tid] = t;
-  }
-}
 
 // ------------------------------------------------------------------------------------------------ 8. rows pass 1
 // blockIdx.x = 32-row tile of the row space (inside ONE bag).  Threads (row = tid >> 3, seg = tid & 7): 8 lanes per row for the two row dots
@@ -466,28 +354,13 @@ __global__ __launch_bounds__(DW_T) void dw_rows2_kernel(InferTab tab, const floa
 
 // ------------------------------------------------------------------------------------------------ host
 struct DwLay {
-  int64_t w1p, vp, vtp, q0f, q2f, q2tf, q0tf, logits, losses, logits_bag, logits_ins, B, crit, qmax, stats, gli, dB, delta, dqmax, dwfcc_part,
-      dbfcc_part, dwi_part, dbi_part, H, dact, V, Q, cls, da, dhv, U1, dPQ, dP1, pmax, parg, pm, pl, pB, db1_part, dbv_part, dbq0_part, dbq2_part,
-      dqm_part, slab_1, slab_v, slab_q0, slab_q2, total;
-  int64_t rows;
-  int32_t steps, s1, s1_per, sv, sv_per, sq0, sq0_per, sq2, sq2_per;
+  DsLay s;
+  int64_t w1p, H, dact, db1_part, slab_1, total, rows;
+  int32_t steps, s1, s1_per;
 };
 
 int check_dw(const mhimx_dsmil_train_cfg* c, int32_t n_bags, const mhimx_pure_window_bag* bags, int32_t xdt = MHIMX_X_F32) {
-  if (int r = rg_check_xdt("dsmil_window", xdt)) return r;
-  MHIMX_CHECK_ARG(c && bags, "dsmil_window: null configuration / bag list");
-  MHIMX_CHECK_ARG(n_bags >= 1 && n_bags <= MHIMX_DSMIL_WINDOW_MAX, "dsmil_window: 1..%d bags per window (got %d)", MHIMX_DSMIL_WINDOW_MAX, n_bags);
-  MHIMX_CHECK_ARG(c->E == IE && c->C >= 1 && c->C <= DW_MAXC && c->D > 0 && c->D % 256 == 0 && c->D <= (1 << 20),
-                  "dsmil_window: shapes outside the ragged DSMIL window (E = 512, q width 128, 1 <= C <= %d, D %% 256 == 0)", DW_MAXC);
-  MHIMX_CHECK_ARG(c->act >= MHIMX_ACT_NONE && c->act <= MHIMX_ACT_TANH, "dsmil_window: unknown activation");
-  MHIMX_CHECK_ARG(c->drop_p >= 0.f && c->drop_p < 1.f, "dsmil_window: dropout probability outside [0,1)");
-  const mhimx_dsmil_params& p = c->param;
-  MHIMX_CHECK_ARG(p.w1 && p.b1 && p.wi && p.bi && p.wq0 && p.bq0 && p.wq2 && p.bq2 && p.wv && p.bv && p.wfcc && p.bfcc, "dsmil_window: null parameter");
-  MHIMX_CHECK_ARG(aligned16(p.w1) && aligned16(p.b1) && aligned16(p.wi) && aligned16(p.wq0) && aligned16(p.wq2) && aligned16(p.wv) && aligned16(p.bv),
-                  "dsmil_window: the feature, i_classifier, q and v weights must be 16-byte aligned");
-  const mhimx_dsmil_grads& g = c->grad;
-  MHIMX_CHECK_ARG(g.w1 && g.b1 && g.wi && g.bi && g.wq0 && g.bq0 && g.wq2 && g.bq2 && g.wv && g.bv && g.wfcc && g.bfcc, "dsmil_window: null gradient view");
-  MHIMX_CHECK_ARG(c->tick, "dsmil_window: the device dropout counter (tick) is required");
+  if (int r = ds_check_base("dsmil_window", c, xdt, n_bags, MHIMX_DSMIL_WINDOW_MAX, bags, "")) return r;
   int64_t rows = 0;
   for (int b = 0; b < n_bags; ++b) {
     if (int r = rg_check_bag("dsmil_window", b, bags[b].N, bags[b].ldx, c->D, xdt, RgRules{MHIMX_STEP_MAX_ROWS, true})) return r;
@@ -505,92 +378,170 @@ void dw_layout(const mhimx_dsmil_train_cfg* c, int32_t n_bags, const mhimx_pure_
     rg_tab_add(tab, cnt, b, bags[b].X, bags[b].ldx, bags[b].N, align_up(bags[b].N, DW_ROWS));
   }
   rg_tab_close(tab, cnt, n_bags);
-  const int64_t rows = cnt.rows, parts = cnt.parts;
-  const int64_t E = c->E, D = c->D, C = c->C, n = n_bags;
+  const int64_t rows = cnt.rows, E = c->E, D = c->D;
   w->rows = rows;
   w->steps = (int32_t)(rows / DW_ROWS);
-  // split-K slabs: enough workgroups to fill the part (4 D / 128 output tiles for d W1, 16 for d Wv, 4 for d Wq0, 1 for d Wq2), never an empty slab
+  // d W1's split-K slabs: enough workgroups to fill the part (4 D / 128 output tiles), never an empty slab
   const int s1_room = pw_split_k(w->steps, 8, 8, &w->s1, &w->s1_per);
-  const int sv_room = pw_split_k(w->steps, 16, 4, &w->sv, &w->sv_per);
-  const int sq0_room = pw_split_k(w->steps, 64, 4, &w->sq0, &w->sq0_per);
-  const int sq2_room = pw_split_k(w->steps, 64, 2, &w->sq2, &w->sq2_per);
   Arena ar(nullptr, 0);
   w->w1p = ar.off; ar.take<float>(E * D);
-  w->vp = ar.off; ar.take<float>(E * E);
-  w->vtp = ar.off; ar.take<float>(E * E);
-  w->q0f = ar.off; ar.take<float>(DW_Q * E);
-  w->q2f = ar.off; ar.take<float>(DW_Q * DW_Q);
-  w->q2tf = ar.off; ar.take<float>(DW_Q * DW_Q);
-  w->q0tf = ar.off; ar.take<float>(DW_Q * E);
-  w->logits = ar.off; ar.take<float>(n * C);
-  w->losses = ar.off; ar.take<float>(n * 3);
-  w->logits_bag = ar.off; ar.take<float>(n * C);
-  w->logits_ins = ar.off; ar.take<float>(n * C);
-  w->B = ar.off; ar.take<float>(n * C * E);
-  w->crit = ar.off; ar.take<int64_t>(n * C);
-  w->qmax = ar.off; ar.take<float>(n * DW_MAXC * DW_Q);
-  w->stats = ar.off; ar.take<float>(n * DW_MAXC * 2);
-  w->gli = ar.off; ar.take<float>(n * DW_MAXC);
-  w->dB = ar.off; ar.take<float>(n * DW_MAXC * E);
-  w->delta = ar.off; ar.take<float>(n * DW_MAXC);
-  w->dqmax = ar.off; ar.take<float>(n * DW_MAXC * DW_Q);
-  w->dwfcc_part = ar.off; ar.take<float>(n * C * C * E);
-  w->dbfcc_part = ar.off; ar.take<float>(n * C);
-  w->dwi_part = ar.off; ar.take<float>(n * C * E);
-  w->dbi_part = ar.off; ar.take<float>(n * C);
+  ds_take(ar, &w->s, n_bags, c->C, rows, cnt.parts, w->steps);
   w->H = ar.off; ar.take<float>(rows * E);
   w->dact = ar.off; ar.take<_Float16>(rows * E);
-  w->V = ar.off; ar.take<float>(rows * E);
-  w->Q = ar.off; ar.take<float>(rows * DW_Q);
-  w->cls = ar.off; ar.take<float>(rows * DW_MAXC);
-  w->da = ar.off; ar.take<float>(rows * DW_MAXC);
-  w->dhv = ar.off; ar.take<float>(rows * E);
-  w->U1 = ar.off; ar.take<float>(rows * DW_Q);
-  w->dPQ = ar.off; ar.take<float>(rows * DW_Q);
-  w->dP1 = ar.off; ar.take<float>(rows * DW_Q);
-  w->pmax = ar.off; ar.take<float>(parts * DW_MAXC);
-  w->parg = ar.off; ar.take<int32_t>(parts * DW_MAXC);
-  w->pm = ar.off; ar.take<float>(parts * DW_MAXC);
-  w->pl = ar.off; ar.take<float>(parts * DW_MAXC);
-  w->pB = ar.off; ar.take<float>(parts * C * E);
   w->db1_part = ar.off; ar.take<float>((int64_t)w->steps * E);
-  w->dbv_part = ar.off; ar.take<float>((int64_t)w->steps * E);
-  w->dbq0_part = ar.off; ar.take<float>((int64_t)w->steps * DW_Q);
-  w->dbq2_part = ar.off; ar.take<float>((int64_t)w->steps * DW_Q);
-  w->dqm_part = ar.off; ar.take<float>((int64_t)w->steps * DW_MAXC * DW_Q);
   w->slab_1 = ar.off; ar.take<float>((int64_t)s1_room * E * D);
-  w->slab_v = ar.off; ar.take<float>((int64_t)sv_room * E * E);
-  w->slab_q0 = ar.off; ar.take<float>((int64_t)sq0_room * DW_Q * E);
-  w->slab_q2 = ar.off; ar.take<float>((int64_t)sq2_room * DW_Q * DW_Q);
   w->total = ar.off;
+}
+
+// the table of a launch that reads fp32 rows of pitch 512 of the row space as its "bags"
+InferTab ds_rows_tab(const InferTab& tab, const float* rows) {
+  InferTab t = tab;
+  for (int b = 0; b < tab.n; ++b) { t.X[b] = rows + tab.row0[b] * IE; t.ldx[b] = IE; }
+  t.pad = MHIMX_X_F32;
+  return t;
+}
+
+// rows pass 2.  PLAIN: rows that have no d out / d pre of their own (a student's token rows): d h as it is over dhv in place, no feature-bias
+// partials
+template <bool PLAIN>
+int dw_rows2(hipStream_t st, const InferTab& tab, char* base, const DsLay& s, const mhimx_dsmil_params& P, int C, const float* H, const _Float16* dact,
+             float* db1_part) {
+  auto F = [&](int64_t off) { return reinterpret_cast<float*>(base + off); };
+  MHIMX_ONCE_PER_DEVICE(MHIMX_HIP(hipFuncSetAttribute((const void*)dw_rows2_kernel<PLAIN>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)DW_R2_SMEM)));
+  hipLaunchKernelGGL(dw_rows2_kernel<PLAIN>, dim3((unsigned)s.steps), dim3(DW_T), DW_R2_SMEM, st, tab, H, dact, F(s.Q), F(s.da), F(s.qmax), F(s.dqmax),
+                     reinterpret_cast<const int64_t*>(base + s.crit), F(s.gli), P.wi, F(s.q0f), P.bq0, F(s.q2tf), F(s.q0tf), C, F(s.dhv), F(s.U1), F(s.dPQ),
+                     F(s.dP1), db1_part, F(s.dbq0_part), F(s.dbq2_part));
+  MHIMX_LAUNCH_CHECK();
+  return 0;
 }
 
 }  // namespace
 
-// launches 8, 10 and 11 as host calls (infer_tab.hpp): mhimx_dsmil_window_run below and mhimx_dsmil_mhim_window_run (dsmil_mhim.hip)
-int dw_rows1(hipStream_t st, const InferTab& tab, int steps, float* V, const float* Q, const float* qmax, const float* stats, const float* dB,
-             const float* delta, int C, float* da, float* dbv_part, float* dqm_part) {
+// ------------------------------------------------------------------------------------------------ host: dsmil_student.hpp's helpers
+void ds_take(Arena& ar, DsLay* s, int64_t n, int64_t C, int64_t rows, int64_t parts, int32_t steps) {
+  const int64_t E = IE;
+  s->steps = steps;
+  // split-K slabs: enough workgroups to fill the part (16 output tiles for d Wv, 4 for d Wq0, 1 for d Wq2), never an empty slab
+  const int sv_room = pw_split_k(steps, 16, 4, &s->sv, &s->sv_per);
+  const int sq0_room = pw_split_k(steps, 64, 4, &s->sq0, &s->sq0_per);
+  const int sq2_room = pw_split_k(steps, 64, 2, &s->sq2, &s->sq2_per);
+  s->vp = ar.off; ar.take<float>(E * E);
+  s->vtp = ar.off; ar.take<float>(E * E);
+  s->q0f = ar.off; ar.take<float>(DS_Q * E);
+  s->q2f = ar.off; ar.take<float>(DS_Q * DS_Q);
+  s->q2tf = ar.off; ar.take<float>(DS_Q * DS_Q);
+  s->q0tf = ar.off; ar.take<float>(DS_Q * E);
+  s->logits = ar.off; ar.take<float>(n * C);
+  s->losses = ar.off; ar.take<float>(n * 3);
+  s->logits_bag = ar.off; ar.take<float>(n * C);
+  s->logits_ins = ar.off; ar.take<float>(n * C);
+  s->B = ar.off; ar.take<float>(n * C * E);
+  s->crit = ar.off; ar.take<int64_t>(n * C);
+  s->qmax = ar.off; ar.take<float>(n * DS_MAXC * DS_Q);
+  s->stats = ar.off; ar.take<float>(n * DS_MAXC * 2);
+  s->gli = ar.off; ar.take<float>(n * DS_MAXC);
+  s->dB = ar.off; ar.take<float>(n * DS_MAXC * E);
+  s->delta = ar.off; ar.take<float>(n * DS_MAXC);
+  s->dqmax = ar.off; ar.take<float>(n * DS_MAXC * DS_Q);
+  s->dwfcc_part = ar.off; ar.take<float>(n * C * C * E);
+  s->dbfcc_part = ar.off; ar.take<float>(n * C);
+  s->dwi_part = ar.off; ar.take<float>(n * C * E);
+  s->dbi_part = ar.off; ar.take<float>(n * C);
+  s->V = ar.off; ar.take<float>(rows * E);
+  s->Q = ar.off; ar.take<float>(rows * DS_Q);
+  s->cls = ar.off; ar.take<float>(rows * DS_MAXC);
+  s->da = ar.off; ar.take<float>(rows * DS_MAXC);
+  s->dhv = ar.off; ar.take<float>(rows * E);
+  s->U1 = ar.off; ar.take<float>(rows * DS_Q);
+  s->dPQ = ar.off; ar.take<float>(rows * DS_Q);
+  s->dP1 = ar.off; ar.take<float>(rows * DS_Q);
+  s->pmax = ar.off; ar.take<float>(parts * DS_MAXC);
+  s->parg = ar.off; ar.take<int32_t>(parts * DS_MAXC);
+  s->pm = ar.off; ar.take<float>(parts * DS_MAXC);
+  s->pl = ar.off; ar.take<float>(parts * DS_MAXC);
+  s->pB = ar.off; ar.take<float>(parts * C * E);
+  s->dbv_part = ar.off; ar.take<float>((int64_t)steps * E);
+  s->dbq0_part = ar.off; ar.take<float>((int64_t)steps * DS_Q);
+  s->dbq2_part = ar.off; ar.take<float>((int64_t)steps * DS_Q);
+  s->dqm_part = ar.off; ar.take<float>((int64_t)steps * DS_MAXC * DS_Q);
+  s->slab_v = ar.off; ar.take<float>((int64_t)sv_room * E * E);
+  s->slab_q0 = ar.off; ar.take<float>((int64_t)sq0_room * DS_Q * E);
+  s->slab_q2 = ar.off; ar.take<float>((int64_t)sq2_room * DS_Q * DS_Q);
+}
+
+int ds_prep_jobs(const mhimx_dsmil_params& P, char* base, const DsLay& s, mhimx_prep_job* j) {
+  auto F = [&](int64_t off) { return reinterpret_cast<float*>(base + off); };
+  int n = 0;
+  j[n++] = mhimx_prep_job{1, P.wv, F(s.vp), IE, IE};
+  j[n++] = mhimx_prep_job{7, P.wv, F(s.vtp), IE, IE};
+  j[n++] = mhimx_prep_job{4, P.wq0, F(s.q0f), DS_Q, IE};
+  j[n++] = mhimx_prep_job{4, P.wq2, F(s.q2f), DS_Q, DS_Q};
+  j[n++] = mhimx_prep_job{5, P.wq2, F(s.q2tf), DS_Q, DS_Q};
+  j[n++] = mhimx_prep_job{5, P.wq0, F(s.q0tf), DS_Q, IE};
+  return n;
+}
+
+int ds_forward(hipStream_t st, const InferTab& tab, char* base, const DsLay& s, const mhimx_dsmil_params& P, int C, const float* H) {
+  auto F = [&](int64_t off) { return reinterpret_cast<float*>(base + off); };
+  // V = relu(h Wv^T + bv): the eval projection over the feature rows as fp32 "bags" of pitch 512
+  if (int r = infer_project(st, ds_rows_tab(tab, H), IE, F(s.vp), P.bv, MHIMX_ACT_RELU, F(s.V))) return r;
+  // Q, classes, critical rows, pool partials (infer_dsmil.hip)
+  return dsmil_rows_crit_pool(st, tab, H, F(s.V), F(s.q0f), P.bq0, F(s.q2f), P.bq2, P.wi, P.bi, C, F(s.Q), F(s.cls), F(s.pmax),
+                              reinterpret_cast<int32_t*>(base + s.parg), F(s.qmax), F(s.logits_ins), reinterpret_cast<int64_t*>(base + s.crit), F(s.pm),
+                              F(s.pl), F(s.pB));
+}
+
+int ds_backward(hipStream_t st, const InferTab& tab, char* base, const DsLay& s, const mhimx_dsmil_params& P, int C, const float* H,
+                const _Float16* dact, float* db1_part) {
+  auto F = [&](int64_t off) { return reinterpret_cast<float*>(base + off); };
+  float *V = F(s.V), *dhv = F(s.dhv);
+  // rows pass 1
   MHIMX_ONCE_PER_DEVICE(MHIMX_HIP(hipFuncSetAttribute((const void*)dw_rows1_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)DW_R1_SMEM)));
-  hipLaunchKernelGGL(dw_rows1_kernel, dim3((unsigned)steps), dim3(DW_T), DW_R1_SMEM, st, tab, V, Q, qmax, stats, dB, delta, C, da, dbv_part, dqm_part);
+  hipLaunchKernelGGL(dw_rows1_kernel, dim3((unsigned)s.steps), dim3(DW_T), DW_R1_SMEM, st, tab, V, F(s.Q), F(s.qmax), F(s.stats), F(s.dB), F(s.delta), C,
+                     F(s.da), F(s.dbv_part), F(s.dqm_part));
   MHIMX_LAUNCH_CHECK();
-  return 0;
+  // d PreV Wv: the eval projection on the d PreV rows with the paired image of Wv^T (no bias, no activation)
+  if (int r = infer_project(st, ds_rows_tab(tab, V), IE, F(s.vtp), nullptr, MHIMX_ACT_NONE, dhv)) return r;
+  // d q_max of every bag
+  hipLaunchKernelGGL(dw_dqmax_kernel, dim3((unsigned)tab.n, DW_MAXC * DW_Q / RG_FIN_T), dim3(RG_FIN_T), 0, st, tab, F(s.dqm_part), F(s.dqmax));
+  MHIMX_LAUNCH_CHECK();
+  // rows pass 2
+  if (int r = dact ? dw_rows2<false>(st, tab, base, s, P, C, H, dact, db1_part) : dw_rows2<true>(st, tab, base, s, P, C, H, dact, db1_part)) return r;
+  // d Wv = dPreV^T h, d Wq2 = dPreQ^T U1, d Wq0 = dPre1^T h
+  if (int r = pw_wgrad_rows(st, tab, V, IE, IE, H, IE, IE, s.steps, s.sv, s.sv_per, F(s.slab_v))) return r;
+  if (int r = pw_wgrad_rows(st, tab, F(s.dPQ), DS_Q, DS_Q, F(s.U1), DS_Q, DS_Q, s.steps, s.sq2, s.sq2_per, F(s.slab_q2))) return r;
+  return pw_wgrad_rows(st, tab, F(s.dP1), DS_Q, DS_Q, H, IE, IE, s.steps, s.sq0, s.sq0_per, F(s.slab_q0));
 }
 
-int dw_dqmax(hipStream_t st, const InferTab& tab, const float* dqm_part, float* dqmax) {
-  hipLaunchKernelGGL(dw_dqmax_kernel, dim3((unsigned)tab.n, DW_MAXC * DW_Q / RG_FIN_T), dim3(RG_FIN_T), 0, st, tab, dqm_part, dqmax);
-  MHIMX_LAUNCH_CHECK();
-  return 0;
+int ds_reduce(hipStream_t st, char* base, const DsLay& s, const mhimx_dsmil_grads& g, int64_t D, int C, int n_bags, const float* slab_1,
+              int32_t s1, const float* db1_part, int32_t steps1) {
+  auto F = [&](int64_t off) { return reinterpret_cast<float*>(base + off); };
+  const float* parts[6] = {slab_1, F(s.slab_v), F(s.slab_q0), F(s.slab_q2), F(s.dwfcc_part), F(s.dwi_part)};
+  const int32_t G[6] = {s1, s.sv, s.sq0, s.sq2, n_bags, n_bags};
+  const int64_t W[6] = {(int64_t)IE * D, (int64_t)IE * IE, (int64_t)DS_Q * IE, (int64_t)DS_Q * DS_Q, (int64_t)C * C * IE, (int64_t)C * IE};
+  float* out[6] = {g.w1, g.wv, g.wq0, g.wq2, g.wfcc, g.wi};
+  if (int r = pw_reduce(st, 6, parts, G, W, out)) return r;
+  const float* parts2[6] = {db1_part, F(s.dbv_part), F(s.dbq0_part), F(s.dbq2_part), F(s.dbfcc_part), F(s.dbi_part)};
+  const int32_t G2[6] = {steps1, s.steps, s.steps, s.steps, n_bags, n_bags};
+  const int64_t W2[6] = {IE, IE, DS_Q, DS_Q, C, C};
+  float* out2[6] = {g.b1, g.bv, g.bq0, g.bq2, g.bfcc, g.bi};
+  return pw_reduce(st, 6, parts2, G2, W2, out2);
 }
 
-int dw_rows2_plain(hipStream_t st, const InferTab& tab, int steps, const float* Hin, const float* Q, const float* da, const float* qmax,
-                   const float* dqmax, const int64_t* crit, const float* gli, const float* wi, const float* q0f, const float* bq0, const float* q2tf,
-                   const float* q0tf, int C, float* dhv, float* U1, float* dPQ, float* dP1, float* dbq0_part, float* dbq2_part) {
-  MHIMX_ONCE_PER_DEVICE(MHIMX_HIP(hipFuncSetAttribute((const void*)dw_rows2_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)DW_R2_SMEM)));
-  const _Float16* no_dact = nullptr;
-  float* no_db1 = nullptr;
-  hipLaunchKernelGGL(dw_rows2_kernel<true>, dim3((unsigned)steps), dim3(DW_T), DW_R2_SMEM, st, tab, Hin, no_dact, Q, da, qmax, dqmax, crit, gli, wi, q0f,
-                     bq0, q2tf, q0tf, C, dhv, U1, dPQ, dP1, no_db1, dbq0_part, dbq2_part);
-  MHIMX_LAUNCH_CHECK();
+int ds_check_base(const char* who, const mhimx_dsmil_train_cfg* c, int32_t xdt, int32_t n_bags, int32_t max_bags, const void* bags,
+                  const char* student) {
+  if (int r = rg_check_xdt(who, xdt)) return r;
+  MHIMX_CHECK_ARG(c && bags, "%s: null configuration / bag list", who);
+  MHIMX_CHECK_ARG(n_bags >= 1 && n_bags <= max_bags, "%s: 1..%d bags per window (got %d)", who, max_bags, n_bags);
+  MHIMX_CHECK_ARG(c->E == IE && c->C >= 1 && c->C <= DS_MAXC && c->D > 0 && c->D % 256 == 0 && c->D <= (1 << 20),
+                  "%s: shapes outside the ragged DSMIL train calls (E = 512, q width 128, 1 <= C <= %d, D %% 256 == 0, D <= 2^20)", who, DS_MAXC);
+  MHIMX_CHECK_ARG(c->act >= MHIMX_ACT_NONE && c->act <= MHIMX_ACT_TANH, "%s: unknown activation", who);
+  MHIMX_CHECK_ARG(c->drop_p >= 0.f && c->drop_p < 1.f, "%s: dropout probability outside [0,1)", who);
+  MHIMX_CHECK_ARG(ds_params_ok(c->param), "%s: null %sparameter", who, student);
+  MHIMX_CHECK_ARG(ds_params_aligned(c->param), "%s: the feature, i_classifier, q and v weights of the %smodel must be 16-byte aligned", who, student);
+  const mhimx_dsmil_grads& g = c->grad;
+  MHIMX_CHECK_ARG(g.w1 && g.b1 && g.wi && g.bi && g.wq0 && g.bq0 && g.wq2 && g.bq2 && g.wv && g.bv && g.wfcc && g.bfcc, "%s: null gradient view", who);
+  MHIMX_CHECK_ARG(c->tick, "%s: the device dropout / draw counter (tick) is required", who);
   return 0;
 }
 
@@ -604,8 +555,8 @@ extern "C" int mhimx_dsmil_window_layout_of(const mhimx_dsmil_train_cfg* cfg, in
   DwLay w;
   memset(out, 0, sizeof(*out));
   dw_layout(cfg, n_bags, bags, &w, nullptr, out->row0);
-  out->total = w.total; out->rows = w.rows; out->logits = w.logits; out->losses = w.losses; out->logits_bag = w.logits_bag;
-  out->logits_ins = w.logits_ins; out->B = w.B; out->crit = w.crit; out->H = w.H; out->dact = w.dact;
+  out->total = w.total; out->rows = w.rows; out->logits = w.s.logits; out->losses = w.s.losses; out->logits_bag = w.s.logits_bag;
+  out->logits_ins = w.s.logits_ins; out->B = w.s.B; out->crit = w.s.crit; out->H = w.H; out->dact = w.dact;
   return 0;
 }
 
@@ -630,9 +581,8 @@ extern "C" int mhimx_dsmil_window_run(void* stream, const mhimx_dsmil_train_cfg*
   char* base = static_cast<char*>(ws);
   auto F = [&](int64_t off) { return reinterpret_cast<float*>(base + off); };
   const int D = (int)c.D, C = (int)c.C;
-  float *H = F(w.H), *V = F(w.V), *Q = F(w.Q), *dhv = F(w.dhv);
+  float* H = F(w.H);
   _Float16* dact = reinterpret_cast<_Float16*>(base + w.dact);
-  int64_t* crit = reinterpret_cast<int64_t*>(base + w.crit);
 
   // ---- 1. counters and weight images
   {
@@ -641,12 +591,7 @@ extern "C" int mhimx_dsmil_window_run(void* stream, const mhimx_dsmil_train_cfg*
     jobs[n++] = mhimx_prep_job{3, nullptr, reinterpret_cast<float*>(c.tick), 1, 1};
     if (c.opt_step) jobs[n++] = mhimx_prep_job{3, nullptr, reinterpret_cast<float*>(c.opt_step), 1, 1};
     jobs[n++] = mhimx_prep_job{1, P.w1, F(w.w1p), c.E, c.D};
-    jobs[n++] = mhimx_prep_job{1, P.wv, F(w.vp), c.E, c.E};
-    jobs[n++] = mhimx_prep_job{7, P.wv, F(w.vtp), c.E, c.E};
-    jobs[n++] = mhimx_prep_job{4, P.wq0, F(w.q0f), DW_Q, c.E};
-    jobs[n++] = mhimx_prep_job{4, P.wq2, F(w.q2f), DW_Q, DW_Q};
-    jobs[n++] = mhimx_prep_job{5, P.wq2, F(w.q2tf), DW_Q, DW_Q};
-    jobs[n++] = mhimx_prep_job{5, P.wq0, F(w.q0tf), DW_Q, c.E};
+    n += ds_prep_jobs(P, base, w.s, jobs + n);
     if (int r = mhimx_prep_batch(stream, jobs, n)) return r;
   }
   // ---- 2. feature rows, dropout, d out / d pre of every bag
@@ -656,60 +601,19 @@ extern "C" int mhimx_dsmil_window_run(void* stream, const mhimx_dsmil_train_cfg*
     dr.tick = c.tick; dr.dact = dact; dr.drop_p = c.drop_p;
     if (int r = pure_window_project_elem(st, tab, dr, D, F(w.w1p), P.b1, c.act, H)) return r;
   }
-  // ---- 3. V = relu(h Wv^T + bv): the eval projection over the feature rows as fp32 "bags" of pitch 512
-  InferTab tabv = tab;
-  for (int b = 0; b < n_bags; ++b) { tabv.X[b] = H + tab.row0[b] * IE; tabv.ldx[b] = IE; }
-  tabv.pad = MHIMX_X_F32;
-  if (int r = infer_project(st, tabv, IE, F(w.vp), P.bv, MHIMX_ACT_RELU, V)) return r;
-  // ---- 4. - 6. Q, classes, critical rows, pool partials (infer_dsmil.hip)
-  if (int r = dsmil_rows_crit_pool(st, tab, H, V, F(w.q0f), P.bq0, F(w.q2f), P.bq2, P.wi, P.bi, C, Q, F(w.cls), F(w.pmax),
-                                   reinterpret_cast<int32_t*>(base + w.parg), F(w.qmax), F(w.logits_ins), crit, F(w.pm), F(w.pl), F(w.pB)))
-    return r;
+  // ---- 3. - 6. V, Q, classes, critical rows, pool partials
+  if (int r = ds_forward(st, tab, base, w.s, P, C, H)) return r;
   // ---- 7. merge, fcc, mix, CE and the head gradients
-  {
-    DwLabels lab = {};
-    for (int b = 0; b < n_bags; ++b) lab.p[b] = bags[b].label_dev;
-    hipLaunchKernelGGL(dw_head_kernel, dim3((unsigned)n_bags), dim3(RG_FIN_T), 0, st, tab, lab, F(w.pm), F(w.pl), F(w.pB), H, P.wfcc, P.bfcc,
-                       F(w.logits_ins), crit, C, c.main_alpha, 1.f / (float)n_bags, F(w.logits_bag), F(w.logits), F(w.losses), F(w.B), F(w.stats),
-                       F(w.gli), F(w.dB), F(w.delta), F(w.dwfcc_part), F(w.dbfcc_part), F(w.dwi_part), F(w.dbi_part));
-    MHIMX_LAUNCH_CHECK();
-  }
-  // ---- 8. rows pass 1
-  if (int r = dw_rows1(st, tab, w.steps, V, Q, F(w.qmax), F(w.stats), F(w.dB), F(w.delta), C, F(w.da), F(w.dbv_part), F(w.dqm_part))) return r;
-  // ---- 9. d PreV Wv: the eval projection on the d PreV rows with the paired image of Wv^T (no bias, no activation)
-  for (int b = 0; b < n_bags; ++b) tabv.X[b] = V + tab.row0[b] * IE;
-  if (int r = infer_project(st, tabv, IE, F(w.vtp), nullptr, MHIMX_ACT_NONE, dhv)) return r;
-  // ---- 10. d q_max of every bag
-  if (int r = dw_dqmax(st, tab, F(w.dqm_part), F(w.dqmax))) return r;
-  // ---- 11. rows pass 2
-  MHIMX_ONCE_PER_DEVICE(MHIMX_HIP(hipFuncSetAttribute((const void*)dw_rows2_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)DW_R2_SMEM)));
-  hipLaunchKernelGGL(dw_rows2_kernel<false>, dim3((unsigned)w.steps), dim3(DW_T), DW_R2_SMEM, st, tab, H, dact, Q, F(w.da), F(w.qmax), F(w.dqmax), crit, F(w.gli),
-                     P.wi, F(w.q0f), P.bq0, F(w.q2tf), F(w.q0tf), C, dhv, F(w.U1), F(w.dPQ), F(w.dP1), F(w.db1_part), F(w.dbq0_part), F(w.dbq2_part));
-  MHIMX_LAUNCH_CHECK();
-  // ---- 12. - 15. the four weight gradients
-  if (int r = pw_wgrad_rows(st, tab, V, IE, IE, H, IE, IE, w.steps, w.sv, w.sv_per, F(w.slab_v))) return r;
-  if (int r = pw_wgrad_rows(st, tab, F(w.dPQ), DW_Q, DW_Q, F(w.U1), DW_Q, DW_Q, w.steps, w.sq2, w.sq2_per, F(w.slab_q2))) return r;
-  if (int r = pw_wgrad_rows(st, tab, F(w.dP1), DW_Q, DW_Q, H, IE, IE, w.steps, w.sq0, w.sq0_per, F(w.slab_q0))) return r;
-  if (int r = pw_wgrad_bagx(st, tab, dhv, D, w.steps, w.s1, w.s1_per, F(w.slab_1))) return r;
+  DsLabels lab = {};
+  for (int b = 0; b < n_bags; ++b) lab.p[b] = bags[b].label_dev;
+  if (int r = ds_head(st, tab, base, w.s, P, C, H, lab, c.main_alpha)) return r;
+  // ---- 8. - 14. the two rows passes and the student's three weight gradients; 15. d W1
+  if (int r = ds_backward(st, tab, base, w.s, P, C, H, dact, F(w.db1_part))) return r;
+  if (int r = pw_wgrad_bagx(st, tab, F(w.s.dhv), D, w.steps, w.s1, w.s1_per, F(w.slab_1))) return r;
   // ---- 16., 17. the partial buffers, in index order, into the gradient views
-  {
-    const mhimx_dsmil_grads& G_ = c.grad;
-    const float* parts[6] = {F(w.slab_1), F(w.slab_v), F(w.slab_q0), F(w.slab_q2), F(w.dwfcc_part), F(w.dwi_part)};
-    const int32_t G[6] = {w.s1, w.sv, w.sq0, w.sq2, n_bags, n_bags};
-    const int64_t W[6] = {(int64_t)c.E * c.D, (int64_t)c.E * c.E, (int64_t)DW_Q * c.E, (int64_t)DW_Q * DW_Q, (int64_t)C * C * c.E, (int64_t)C * c.E};
-    float* out[6] = {G_.w1, G_.wv, G_.wq0, G_.wq2, G_.wfcc, G_.wi};
-    if (int r = pw_reduce(st, 6, parts, G, W, out)) return r;
-    const float* parts2[6] = {F(w.db1_part), F(w.dbv_part), F(w.dbq0_part), F(w.dbq2_part), F(w.dbfcc_part), F(w.dbi_part)};
-    const int32_t G2[6] = {w.steps, w.steps, w.steps, w.steps, n_bags, n_bags};
-    const int64_t W2[6] = {c.E, c.E, DW_Q, DW_Q, C, C};
-    float* out2[6] = {G_.b1, G_.bv, G_.bq0, G_.bq2, G_.bfcc, G_.bi};
-    if (int r = pw_reduce(st, 6, parts2, G2, W2, out2)) return r;
-  }
+  if (int r = ds_reduce(st, base, w.s, c.grad, D, C, n_bags, F(w.slab_1), w.s1, F(w.db1_part), w.steps)) return r;
   if (!update) return 0;
   // ---- 18. Adam
-  mhimx_optim_args o = {};
-  o.p = c.p; o.g = c.g; o.m = c.m; o.v = c.v; o.n_train = c.n_train; o.n_all = c.n_all; o.step = host_step; o.step_dev = c.opt_step;
-  o.lr = c.lr; o.lr_table = c.lr_table; o.lr_len = c.lr_len; o.beta1 = c.beta1; o.beta2 = c.beta2; o.eps = c.eps; o.weight_decay = c.weight_decay;
-  o.grad_scale = 1.f; o.zero_grad = 1;
+  const mhimx_optim_args o = optim_args_of(c, host_step);
   return mhimx_optim_step(stream, &o);
 }

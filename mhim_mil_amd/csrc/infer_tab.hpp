@@ -220,14 +220,7 @@ int dsmil_rows_crit_pool(hipStream_t st, const InferTab& tab, const float* H, co
 // order -> B [n, C, 512], logits_bag, logits [n, C]; attn (optional, rows of the row space): max_c A of every row
 int dsmil_finalize(hipStream_t st, const InferTab& tab, const float* pm, const float* pl, const float* pB, const float* Q, const float* qmax,
                    const float* wfcc, const float* bfcc, int C, const float* logits_ins, float* logits_bag, float* logits, float* B, float* attn);
-// dsmil_window.hip's backward launches 8, 10 and 11 over a table as host calls.  dw_rows2_plain: launch 11 for rows that have no
-// d out / d pre of their own (a student's token rows): d h as it is over dhv in place, no feature-bias partials
-int dw_rows1(hipStream_t st, const InferTab& tab, int steps, float* V, const float* Q, const float* qmax, const float* stats, const float* dB,
-             const float* delta, int C, float* da, float* dbv_part, float* dqm_part);
-int dw_dqmax(hipStream_t st, const InferTab& tab, const float* dqm_part, float* dqmax);
-int dw_rows2_plain(hipStream_t st, const InferTab& tab, int steps, const float* Hin, const float* Q, const float* da, const float* qmax,
-                   const float* dqmax, const int64_t* crit, const float* gli, const float* wi, const float* q0f, const float* bq0, const float* q2tf,
-                   const float* q0tf, int C, float* dhv, float* U1, float* dPQ, float* dP1, float* dbq0_part, float* dbq2_part);
+// (the DSMIL student of the two DSMIL train calls - head kernel, layout share, forward, backward, reductions, checks: dsmil_student.hpp)
 // ragged_window.hip's launch C.5 as a host call: q <- mm^n q + (1 - mm) sum_b mm^(n-1-b) z_b, z_b = the k rows of Hs from row tok[b] on
 int rw_q_chain(hipStream_t st, float* q, const float* Hs, int n_bags, const int64_t* tok, double mm, int n_floats);
 // step.hip: the checks mhimx_step_run makes on (cfg, N, counts)

@@ -53,13 +53,13 @@ def _mk(sd, Cc=2, **cfg):
     return m
 
 
-def _pair(dropout=0.0, accum=4, Cc=2, executor=True, model_kw=None, **kw):
+def _pair(dropout=0.0, accum=4, Cc=2, executor=True, model_kw=None, aux_alpha=0.5, **kw):
     from mhim_mil_amd.engine import FusedTrainer
     torch.manual_seed(SEED)
     base, tsd = _states(Cc)
     cfg = dict(V2, dropout=dropout, **(model_kw or {}))
     s, t = _mk(base, Cc, **cfg), _mk(tsd, Cc, **cfg)
-    tr = FusedTrainer(s, t, lr=LR, aux_alpha=0.5, mm=0.9997, accumulation_steps=accum, **kw)
+    tr = FusedTrainer(s, t, lr=LR, aux_alpha=aux_alpha, mm=0.9997, accumulation_steps=accum, **kw)
     if not executor:
         tr.use_executor = False
     return tr, s, t, base, tsd
@@ -127,6 +127,7 @@ def _oracle_window(bags, labels, stu, tea, opt, ocfg, step, perms, shufs, scores
             t_feat = tfeats[j]
         lg, cl, _, _, ex = O.forward_student(x, stu_g, ocfg, scores[j], t_feat if aux_alpha != 0.0 else None, perms[j], shufs[j],
                                              drop_mask=None if masks is None else masks[j])
+        cl = torch.as_tensor(cl)                           # (0.0 without a teacher feature)
         logits = 0.5 * lg[0] + 0.5 * lg[1]
         ce = O.cross_entropy(logits, int(labels[j]))
         ((ce + aux_alpha * cl) / n).backward()
@@ -204,6 +205,39 @@ def test_two_windows_vs_oracle(Cc):
         for name, (m_ref, v_ref) in opt.items():
             o = tr.flat.offsets[name]
             tr.flat.m[o:o + m_ref.numel()].copy_(m_ref.reshape(-1)); tr.flat.v[o:o + v_ref.numel()].copy_(v_ref.reshape(-1))
+
+
+def test_aux_alpha_zero_window_vs_oracle():
+    """aux_alpha = 0 on the full model: the call launches the head's distillation instantiation without the teacher's B (no other test
+    reaches that).  Bags of 64 rows (the call's minimum) and 97 (a ragged last tile), C = 2, against the oracle's window at the bounds
+    above; the distillation loss is exactly 0 and the loss exactly main_alpha * CE."""
+    sizes = (64, 97)
+    tr, s, t, base, tsd = _pair(accum=2, aux_alpha=0.0)
+    ocfg = O.Cfg(**{**V2, "baseline": "dsmil"})
+    bags = [_bag(550 + j, n) for j, n in enumerate(sizes)]
+    labels = [1, 0]
+    xs, ls = _dev(bags, labels)
+    tr.window_step(xs, ls, update=False)
+    torch.cuda.synchronize()
+    assert tr.last["exec"] == ROUTE and float(tr._dsmil_mhim_cfg()["cfg"].aux_alpha) == 0.0
+    per = tr.last["bags"]
+    perms, shufs, scores = _read_draws(per, sizes)
+    stu, tea, opt, info = _oracle_window(bags, labels, O.as_torch(base), O.as_torch(tsd), {}, ocfg, 1, perms, shufs, scores, tr.mm, aux_alpha=0.0)
+    for j in range(len(sizes)):
+        losses = per[j]["losses"].float().cpu()
+        print(f"  bag {j}: losses {losses.tolist()}, oracle CE {info['ce'][j]:.6f}")
+        np.testing.assert_allclose(per[j]["logits"].cpu().numpy().ravel(), info["logits"][j].numpy().ravel(), atol=1e-4, rtol=0)
+        np.testing.assert_allclose(per[j]["logits_bag"].cpu().numpy().ravel(), info["lb"][j].numpy().ravel(), atol=1e-4, rtol=0)
+        np.testing.assert_allclose(per[j]["logits_ins"].cpu().numpy().ravel(), info["li"][j].numpy().ravel(), atol=1e-4, rtol=0)
+        assert abs(float(losses[0]) - info["loss"][j]) < 3e-4 and abs(float(losses[1]) - info["ce"][j]) < 3e-4
+        assert float(losses[2]) == 0.0
+        assert float(losses[0]) == float(torch.tensor(tr.main_alpha, dtype=torch.float32) * losses[1])
+    assert _grads_close(tr.flat.grad_views, info["grads"]) == EIGHTEEN == len(tr.flat.grad_views)
+    tr.update()
+    torch.cuda.synchronize()
+    _check_student(s, stu, opt, "student")
+    _check_teacher(t, tea, "teacher")
+    np.testing.assert_allclose(s.merge.global_q_mm.detach().cpu().numpy(), stu["merge.global_q_mm"].numpy(), atol=2e-6, rtol=0)
 
 
 # ------------------------------------------------------------------------------------------------------------------ 2
