@@ -14,6 +14,8 @@ from __future__ import annotations
 
 from typing import Optional
 
+import collections
+import contextlib
 import dataclasses
 import os
 
@@ -411,6 +413,12 @@ def _dsmil_mhim_bags_ok(tr, xs, i, dev):
     return all(tr._dsmil_params_ok(m, dev, w1_shape=True) for m in (s, tr.t))
 
 
+# FusedTrainer._window_route's answer: the route's name, the family of a native call (else None), the bags as the route reads them, the
+# labels and the censorship flags (a survival call's) it takes
+_Route = collections.namedtuple("_Route", "name fam xs labels surv")
+# FusedTrainer.shape_cached's cache entry: the graph, its static bag / label / output buffers, self.last and the optimiser's scalars it baked in
+_ShapeGraph = collections.namedtuple("_ShapeGraph", "graph x label logits losses patch_num keep_num last scal")
+
 _L = mh.L
 _PURE = _WindowFamily(
     "mhim_pure", "attn", ok="_pure_window_ok", run="_exec_pure_window", shapes="pure_window_shapes_ok", row_cap="pure_window_row_cap",
@@ -562,14 +570,41 @@ class FusedTrainer:
     def _dist(self):
         return torch.distributed.is_available() and torch.distributed.is_initialized()
 
+    @contextlib.contextmanager
+    def _merge_off_if_pure(self):
+        """'mhim_pure': the student runs with its Merge switched off inside the block, and gets its switch back behind it."""
+        s, merge_on = self.s, self.s.merge_enable
+        if self.model_kind != "mhim":
+            s.merge_enable = False
+        try:
+            yield
+        finally:
+            s.merge_enable = merge_on
+
+    def _head(self, z, teacher_feat, label, gv, accumulate):
+        """The head of a bag on the Python routes: predictor, loss (cross entropy, or _surv_head), distillation and their gradients into
+        ``gv``'s predictor views.  Returns (logits, losses, g_z)."""
+        s = self.s
+        t_in = teacher_feat.view(-1) if (teacher_feat is not None and self.aux_alpha != 0.) else None
+        logits, losses, g_z, _, _ = (self._surv_head if self.loss == "nll_surv" else ops.head_fwd_bwd)(
+            z, t_in, s.predictor.weight.data, s.predictor.bias.data, label, temp_t=float(s.temp_t),
+            main_alpha=self.main_alpha, aux_alpha=self.aux_alpha, inv_accum=1.0 / self.accum,
+            d_wp=gv["predictor.weight"], d_bp=gv["predictor.bias"], accumulate=accumulate)
+        return logits, losses, g_z
+
+    def _overlap_hook(self, first):
+        """_mid_hook when this bag's backward overlaps the all-reduce of its gradient's second piece (data parallel, eager, one bag per
+        update, ``first``: the update's first bag), else None."""
+        return self._mid_hook if (first and self.overlap_comm and self.comm is None and self.world > 1 and self.accum == 1
+                                  and not self._capturing and self._split > 0) else None
+
     # -------------------------------------------------------------------------------------------------
     def forward_backward(self, bag, label, perm=None, ids_shuffle=None, i=None):
         """Teacher fwd + select + student fwd + head + backward into the flat gradient buffer (accumulating).
         The native one-call routes (mhimx_step_run, mhimx_pure_step_run, mhimx_dsmil_window_run, mhimx_dsmil_mhim_window_run) take ``label``
         as an int64 tensor of one element on the bag's device; an int or a CPU label takes the Python orchestration (``self.last["exec"]``
         says which ran)."""
-        s, t, fl = self.s, self.t, self.flat
-        x = s._check_x(bag)
+        x = self.s._check_x(bag)
         surv = self.loss == "nll_surv"
         if surv:
             label = self._surv_label(label, x.device)
@@ -583,14 +618,19 @@ class FusedTrainer:
                                        single=True)
                 if out is not None:
                     return out[0][0], out[1][0]
-        # parameter-only preparation of the step: weight transposes, paired-plane weights, query snapshot
-        # (kept on the launch stream: a parallel branch in the captured hipGraph costs ~60 us of cross-queue signalling on
-        # ROCm 7.2 — measured, profiles/ r01 notes — against ~40 us of kernels it would hide)
-        # together with the two device counters (dropout stream position, Adam step) it is ONE launch
         if self._nat_ok(x, i):
             if self._exec_ok(x, i, perm, ids_shuffle):
                 return self._exec_step(x, label, i)
             return self._forward_backward_nat(x, label, perm, ids_shuffle, i)
+        return self._forward_backward_py(x, label, perm, ids_shuffle, i)
+
+    def _forward_backward_py(self, x, label, perm, ids_shuffle, i):
+        """The Python orchestration of a step: every model and every case the native calls and the single-pass step refuse."""
+        s, t, fl = self.s, self.t, self.flat
+        # parameter-only preparation of the step: weight transposes, paired-plane weights, query snapshot
+        # (kept on the launch stream: a parallel branch in the captured hipGraph costs ~60 us of cross-queue signalling on
+        # ROCm 7.2 — measured, profiles/ r01 notes — against ~40 us of kernels it would hide)
+        # together with the two device counters (dropout stream position, Adam step) it is ONE launch
         prep_s = prep_t = None
         jobs = [(ops.PREP_TICK, None, self.tick)]
         if self._micro == 0:
@@ -669,33 +709,22 @@ class FusedTrainer:
             return self._selfattn_forward_backward(x, label, plan, teacher_feat, keep_num, first)
         if s.baseline == "dsmil":
             return self._dsmil_forward_backward(x, label, plan, teacher_feat, keep_num)
-        merge_on = s.merge_enable
-        if self.model_kind != "mhim":
-            s.merge_enable = False
-        try:
+        with self._merge_off_if_pure():
             z, saved = s._bag_forward(x, plan, xp=xp, prep=prep_s)
             if self._chain is not None and self.model_kind == "mhim":
                 # this rank's term of the chain: the tokens its Merge produced; a bag with no rows to merge leaves the queries alone in the
                 # reference (its EMA step is skipped) - handing the chain the current queries does the same up to second order in 1 - mm
                 tok = saved.get("z_tok")
                 self._chain.tokens = self._chain_tokens = tok if tok is not None else s.merge.global_q_mm.data.view(s.merge.k, -1).clone()
-            t_in = teacher_feat.view(-1) if (teacher_feat is not None and self.aux_alpha != 0.) else None
-            logits, losses, g_z, _, _ = (self._surv_head if self.loss == "nll_surv" else ops.head_fwd_bwd)(
-                z, t_in, s.predictor.weight.data, s.predictor.bias.data, label, temp_t=float(s.temp_t),
-                main_alpha=self.main_alpha, aux_alpha=self.aux_alpha, inv_accum=1.0 / self.accum,
-                d_wp=gv["predictor.weight"], d_bp=gv["predictor.bias"], accumulate=not first)
+            logits, losses, g_z = self._head(z, teacher_feat, label, gv, accumulate=not first)
             if first:
                 # the six final gradient reductions of the backward (slab sums, column partials) run as ONE launch
-                hook = self._mid_hook if (self.overlap_comm and self.comm is None and self.world > 1 and self.accum == 1 and not self._capturing
-                                          and self._split > 0) else None
-                s._bag_backward(x, plan, saved, g_z, out=gv, defer=self._defer, mid_hook=hook)
+                s._bag_backward(x, plan, saved, g_z, out=gv, defer=self._defer, mid_hook=self._overlap_hook(True))
                 ops.reduce_flush(self._defer)
             else:                                   # gradient accumulation: fresh buffers, then add (rare path)
                 g = s._bag_backward(x, plan, saved, g_z)
                 for n, v in g.items():
                     gv[n].add_(v)
-        finally:
-            s.merge_enable = merge_on
         self._micro += 1
         self.last = {"logits": logits, "losses": losses, "patch_num": ps, "keep_num": keep_num, "exec": False}
         if self.loss == "nll_surv":
@@ -728,34 +757,6 @@ class FusedTrainer:
         self._risk_now = risk
         return logits, losses, g_z, d_wp, d_bp
 
-    def _surv_window_step(self, bags, labels, i, perms, shuffles, update):
-        """window_step of a loss="nll_surv" trainer: 1 .. accumulation_steps bags as ONE call of mhimx_pure_window_run_surv ('mhim_pure') or
-        mhimx_ragged_window_run_surv ('mhim'; same-shaped windows too: mhimx_window_run has no survival form) when the call takes them.
-        Else 'mhim_pure': bag after bag (exactly accumulation_steps bags: that route scales by 1 / accumulation_steps); 'mhim': None -
-        window_step goes on to its stream form.  ``labels``: (Y, c) pairs as _surv_label returns them."""
-        k = len(bags)
-        assert 1 <= k <= self.accum and len(labels) == k, "window_step takes at most accumulation_steps bags"
-        pure = self.model_kind == "mhim_pure"
-        if perms is None and shuffles is None:
-            out = self._try_native(_PURE if pure else _RAGGED, bags, [p[0] for p in labels], i, update, surv=[p[1] for p in labels])
-            if out is not None:
-                return out
-        if not pure:
-            return None
-        assert k == self.accum, "window_step takes exactly accumulation_steps bags"
-        outs, risks, per = [], [], []
-        for j, (b, l) in enumerate(zip(bags, labels)):
-            kw = {} if perms is None else {"perm": perms[j], "ids_shuffle": shuffles[j]}
-            if update:
-                outs.append(self.train_step(b, l, i=i, **kw))
-            else:
-                outs.append(self.forward_backward(b, l, i=i, **kw))
-            risks.append(self.last["risk"])
-            per.append(self.last)
-        logits, losses = [o[0] for o in outs], [o[1] for o in outs]
-        self.last = dict(self.last, logits=logits, losses=losses, bags=per, risk=torch.cat([r.view(1) for r in risks]))
-        return logits, losses
-
     def _nat_ok(self, x, i=None):
         """True when the bag takes the single-pass ABMIL step (_forward_backward_nat): no host read-back anywhere, fixed launch shapes."""
         s, t = self.s, self.t
@@ -774,7 +775,7 @@ class FusedTrainer:
         # (round 6) a data-parallel rank takes it too - forward + backward with update = 0, the EMA of the global queries sent to the
         # QueryChain's scratch (mhimx_step_cfg.q_out), then the all-reduce and mhimx_optim_step as always - unless the eager step overlaps
         # its all-reduce with the backward (the mid-backward hook lives in the Python orchestration)
-        hooked = (self.overlap_comm and self.comm is None and self.world > 1 and self.accum == 1 and not self._capturing and self._split > 0)
+        hooked = self._overlap_hook(True) is not None
         if self.model_kind == "mhim_pure":
             # mhimx_pure_step_run.  Decided on the model's kind, baseline and scorer form BEFORE anything of s.merge or
             # attention.attention[...] is touched: a pure model is built with merge_enable=False (s.merge is an Identity) and may be gated,
@@ -923,20 +924,31 @@ class FusedTrainer:
         the call reads them where they lie), then widened to fp32 as every other route reads them; None when neither is taken.  ``offer``
         (bags, widened) -> False: this form of the window is not offered to the call.  ``wide``: the caller's list of the widened bags -
         filled here when it is empty and they are needed, so that a window is widened once however many calls and routes see it.  The
-        check and the call are looked up on the instance here."""
+        check (_native_form) and the call (_run_native) are looked up on the instance."""
+        xs = self._native_form(fam, bags, labels, i, offer, wide)
+        return None if xs is None else self._run_native(fam, xs, labels, i, update, surv, single)
+
+    def _native_form(self, fam, bags, labels, i, offer=None, wide=None):
+        """_try_native's decision: the bags in the form ``fam``'s check takes them in - as they are, else widened - or None.  It draws no
+        seed and touches no counter or workspace (_family_ok)."""
         if self.model_kind != fam.model_kind or self.s.baseline != fam.baseline:
             return None
-        ok, run = getattr(self, fam.ok), getattr(self, fam.run)
+        ok = getattr(self, fam.ok)
         ia = (i,) if fam.full else ()
-        kw = {n: v for n, v in (("surv", surv), ("single", single)) if v}          # (only what is set: a plain window is (xs, labels[, i], update))
         wide = [] if wide is None else wide
         for widened in (False, True):
             if widened and not wide:
                 wide.extend(self.s._check_x(b) for b in bags)
             xs = wide if widened else self._half_bags(bags)
             if xs is not None and (offer is None or offer(xs, widened)) and ok(xs, labels, *ia):
-                return run(xs, labels, *ia, update, **kw)
+                return xs
         return None
+
+    def _run_native(self, fam, xs, labels, i, update, surv=None, single=False):
+        """_try_native's run: ``fam``'s call on the bags its check took."""
+        ia = (i,) if fam.full else ()
+        kw = {n: v for n, v in (("surv", surv), ("single", single)) if v}          # (only what is set: a plain window is (xs, labels[, i], update))
+        return getattr(self, fam.run)(xs, labels, *ia, update, **kw)
 
     def _pure_window_ok(self, xs, labels):
         """True when mhimx_pure_window_run_x takes this window (_family_ok)."""
@@ -1101,22 +1113,6 @@ class FusedTrainer:
             return None
         xs = [b[0] if b.dim() == 3 and b.shape[0] == 1 else b for b in bags]
         return [x.contiguous() for x in xs] if all(x.dim() == 2 for x in xs) else None
-
-    def _pure_window_step(self, bags, labels, i, perms, shuffles, update):
-        """window_step of a 'mhim_pure' trainer with accumulation_steps > 1: the native ragged window when it takes the bags (a SHORTER last
-        window too: 1 <= len(bags) <= accumulation_steps, scaled by 1 / len(bags) - base_engine.py:30,50-51,102), else today's bag-after-bag
-        route, which scales by 1 / accumulation_steps and so needs exactly that many bags."""
-        k = len(bags)
-        assert 1 <= k <= self.accum and len(labels) == k, "window_step takes at most accumulation_steps bags"
-        if perms is None and shuffles is None:
-            # (the DSMIL student has its own call: mhimx_dsmil_window_run)
-            out = self._try_native(_DSMIL if self.s.baseline == "dsmil" else _PURE, bags, labels, i, update)
-            if out is not None:
-                return out
-        assert k == self.accum, "window_step takes exactly accumulation_steps bags"
-        outs = [self.train_step(b, l, i=i, **({} if perms is None else {"perm": perms[j], "ids_shuffle": shuffles[j]}))
-                for j, (b, l) in enumerate(zip(bags, labels))]
-        return [o[0] for o in outs], [o[1] for o in outs]
 
     def _exec_cfg(self):
         """The mhimx_step_cfg of this trainer: parameter / gradient pointers into the flat buffers (stable for the trainer's lifetime), the
@@ -1337,10 +1333,8 @@ class FusedTrainer:
             res = self._nat_prep([x], i, with_opt_tick=first, split=True)       # (the student-side preparation jobs ride in the teacher's scorer launch)
             prep_t, preps = res[0], res[1]
             preps[0]["_ride_jobs"] = res[2] if len(res) > 2 else None
-            hook = self._mid_hook if (first and self.overlap_comm and self.comm is None and self.world > 1 and self.accum == 1
-                                      and not self._capturing and self._split > 0) else None
             out = self._nat_bag(x, label, prep_t, preps[0], self.flat.grad_views, accumulate=not first, perm=perm, ids_shuffle=ids_shuffle,
-                                i=i, mid_hook=hook)
+                                i=i, mid_hook=self._overlap_hook(first))
         self._micro += 1
         return out
 
@@ -1362,10 +1356,7 @@ class FusedTrainer:
         if mhim:
             jt, prep_t = t.prep_jobs(backward=False)
             jobs += jt
-        merge_on = s.merge_enable
-        if not mhim:
-            s.merge_enable = False
-        try:
+        with self._merge_off_if_pure():
             Rs = [s.v2_counts(x.shape[0], i)[4] if mhim else 0 for x in xs]
             lean = mhim and s.merge.k * 8 <= 48 and all(1 <= R <= 32768 for R in Rs) and s._op_prec != "f32"
             js, prep_s = s.prep_jobs(backward=True, lean_merge=lean)
@@ -1387,8 +1378,6 @@ class FusedTrainer:
                 late = [j for j in js if not any(j is e for e in early)]
                 js = early
             ops.prep_batch(jobs + js)
-        finally:
-            s.merge_enable = merge_on
         return (prep_t, preps, late) if split else (prep_t, preps)
 
     def _nat_heads(self, x, prep_t, prep_s):
@@ -1413,10 +1402,7 @@ class FusedTrainer:
         mhim = self.model_kind == "mhim"
         ps, E = x.shape[0], s.mlp_dim
         dev = x.device
-        merge_on = s.merge_enable
-        if not mhim:
-            s.merge_enable = False
-        try:
+        with self._merge_off_if_pure():
             k = s.merge.k if mhim else 0
             act = mh.L.act_code(s.act, mh._FEATURE_ACTS)
             if projected is None:
@@ -1453,11 +1439,7 @@ class FusedTrainer:
                 plan = BagPlan(rows=None, L=ps, Lk=ps, R=0, training=True)
                 keep_num = ps
             z, saved = s._bag_forward_nat(x, plan, Hbuf, DACT, rows_all, prep_s)
-            t_in = teacher_feat.view(-1) if (teacher_feat is not None and self.aux_alpha != 0.) else None
-            logits, losses, g_z, _, _ = (self._surv_head if self.loss == "nll_surv" else ops.head_fwd_bwd)(
-                z, t_in, s.predictor.weight.data, s.predictor.bias.data, label, temp_t=float(s.temp_t),
-                main_alpha=self.main_alpha, aux_alpha=self.aux_alpha, inv_accum=1.0 / self.accum,
-                d_wp=gv["predictor.weight"], d_bp=gv["predictor.bias"], accumulate=accumulate)
+            logits, losses, g_z = self._head(z, teacher_feat, label, gv, accumulate)
             # the six final gradient reductions of the backward (slab sums, column partials) run as ONE launch
             # train_step (one bag per update, one process, no clipping): nothing reads the gradient between this backward and the update,
             # so no reduction launch stands between them - the reductions that are final before the weight-gradient product starts ride in
@@ -1469,8 +1451,6 @@ class FusedTrainer:
                 self._fold_list = self._defer
             else:
                 ops.reduce_flush(self._defer)
-        finally:
-            s.merge_enable = merge_on
         # (kept for inspection / parity tests: under graph replay these are the static buffers the replay rewrites)
         self.last = {"logits": logits, "losses": losses, "patch_num": ps, "keep_num": keep_num, "rows": plan.rows,
                      "score": score, "R": plan.R, "tokens": Hbuf[ps:] if mhim else None,
@@ -1521,43 +1501,79 @@ class FusedTrainer:
           window ends with the same chain of EMA steps on the tokens those forwards produced (oracle ``train_window(q_ema="window")``;
           differs from the reference's bag-after-bag order in second order of 1 - merge_mm).
         Each bag's loss is scaled by 1 / accumulation_steps in the head kernel (base_engine.py:102).  Capturable (``capture_window``).
-        Full windows of same-shaped bags take mhimx_window_run; windows of DIFFERENT-sized bags (1 .. accumulation_steps of them: a shorter last window
-        is scaled by its own length) take mhimx_ragged_window_run; a DSMIL student's windows (1 .. accumulation_steps bags of any sizes) take
-        mhimx_dsmil_mhim_window_run; injected draws, several processes, a kernel event hook, a ratio schedule, prec="f32", merge_k > 6 and
-        MHIMX_STEP_EXEC=0 keep the stream form below (DSMIL: the bag-after-bag route).  ``self.last["exec"]`` names the route.
-        Returns ([logits per bag], [losses per bag])."""
-        k = len(bags)
-        if self.loss == "nll_surv":
-            # the two survival calls; a window they refuse takes today's routes below (the stream form / bag after bag), whose head is
-            # _surv_head: the native calls below are the cross entropy's and see no survival label (a pair is no label tensor)
+        That is the stream form (_stream_window); which windows take a native call instead, which go bag after bag, and in which order
+        they are offered: _window_route, and the route table in DESIGN.md ("Native calls: the shared host pieces").
+        ``self.last["exec"]`` names the route.  Returns ([logits per bag], [losses per bag])."""
+        k, surv = len(bags), self.loss == "nll_surv"
+        if surv:
             labels = [self._surv_label(l, bags[0].device) for l in labels]
-            out = self._surv_window_step(bags, labels, i, perms, shuffles, update)
-            if out is not None:
-                return out
-        if self.model_kind == "mhim_pure" and self.accum > 1:
-            return self._pure_window_step(bags, labels, i, perms, shuffles, update)
-        # the DSMIL student has its own call: mhimx_dsmil_mhim_window_run, for 1 <= len(bags) <= accumulation_steps (fp16 / bf16 bags go in as
-        # they are); what it refuses takes today's route below
-        wide = []                                                     # (the widened bags, made once: by the first route that needs them)
-        if perms is None and shuffles is None:
-            out = self._try_native(_DSMIL_MHIM, bags, labels, i, update, wide=wide) if 1 <= k <= self.accum else None
-            # bags of different sizes, a shorter last window too: ONE call of mhimx_ragged_window_run, every loss scaled by 1 / len(bags)
-            # (base_engine.py:30,50-51,102).  A full window of same-shaped bags is not offered: it keeps its routes - mhimx_window_run, or the
-            # stream form where that call does not take it (fp16 / bf16 bags as they are: one shape; widened: one shape and one pitch)
-            if out is None:
-                out = self._try_native(_RAGGED, bags, labels, i, update, wide=wide, offer=lambda xs, widened: not (k == self.accum and all(
-                    x.shape == xs[0].shape and (not widened or x.stride() == xs[0].stride()) for x in xs)))
-            if out is not None:
-                return out
-        xs = wide or [self.s._check_x(b) for b in bags]
+        if surv or (self.model_kind == "mhim_pure" and self.accum > 1):
+            assert 1 <= k <= self.accum and len(labels) == k, "window_step takes at most accumulation_steps bags"
+        r = self._window_route(bags, labels, i, perms, shuffles)
+        if r.fam is not None:
+            return self._run_native(r.fam, r.xs, r.labels, i, update, surv=r.surv)
+        if r.name == "bag_surv":
+            return self._bag_after_bag(bags, labels, i, perms, shuffles, update=update, aggregate=True)
+        if r.name == "bag":                                            # (train_step, whatever ``update`` says)
+            return self._bag_after_bag(bags, labels, i, perms, shuffles, update=True, aggregate=False)
         assert k == self.accum and len(labels) == k, "window_step takes exactly accumulation_steps bags"
-        if not self.window_ok(xs, i) or perms is not None or self.world > 1:
-            outs = [self.train_step(b, l, i=i, **({} if perms is None else {"perm": perms[j], "ids_shuffle": shuffles[j]}))
-                    for j, (b, l) in enumerate(zip(bags, labels))]
-            return [o[0] for o in outs], [o[1] for o in outs]
         assert self._micro == 0, "window_step starts a fresh accumulation window"
-        if self._exec_window_ok(xs, labels, i):
-            return self._exec_window(xs, labels, i, update)
+        if r.name == "window_run":
+            return self._exec_window(r.xs, labels, i, update)
+        return self._stream_window(r.xs, labels, i, n_streams, update)
+
+    def _window_route(self, bags, labels, i, perms, shuffles):
+        """The _Route that takes this window (``labels`` of a survival trainer: _surv_label's pairs): window_step's and capture_window's
+        one decision, made before any seed is drawn, counter touched or workspace made.  DESIGN.md has the table in words."""
+        k, pure, surv = len(bags), self.model_kind == "mhim_pure", self.loss == "nll_surv"
+        Ys, censored = ([p[0] for p in labels], [p[1] for p in labels]) if surv else (labels, None)
+        # the route table - offers: (family, labels, censorship flags, which forms of the window it is offered) in order, made only without
+        # injected draws; rest: who takes what they refuse (None: window_ok, the draws and world decide between "bag", "window_run", "stream").
+        # capture_window asks for the widened bags without draws, and accepts what _RAGGED's check takes even where ragged_too keeps the
+        # window from it: with window_ok False such a window is captured bag after bag
+        if surv and pure:
+            offers, rest = [(_PURE, Ys, censored, None)], "bag_surv"
+        elif pure and self.accum > 1:
+            offers, rest = [(_DSMIL if self.s.baseline == "dsmil" else _PURE, labels, None, None)], "bag"
+        else:
+            # (a full window of same-shaped bags keeps mhimx_window_run, or the stream form where that call does not take it; the survival
+            # trainer's second offer has the pairs as labels, which no check takes)
+            ragged_too = lambda xs, widened: not (k == self.accum and all(
+                x.shape == xs[0].shape and (not widened or x.stride() == xs[0].stride()) for x in xs))
+            offers, rest = [(_RAGGED, Ys, censored, None)] if surv else [], None
+            if 1 <= k <= self.accum:
+                offers.append((_DSMIL_MHIM, labels, None, None))
+            offers.append((_RAGGED, labels, None, ragged_too))
+        wide = []                                                     # (the widened bags, made once: by the first offer or route that needs them)
+        if perms is None and shuffles is None:
+            for fam, lab, flags, offer in offers:
+                xs = self._native_form(fam, bags, lab, i, offer, wide)
+                if xs is not None:
+                    return _Route(fam.run, fam, xs, lab, flags)
+        if rest is not None:
+            return _Route(rest, None, bags, labels, None)
+        xs = wide or [self.s._check_x(b) for b in bags]
+        if not self.window_ok(xs, i) or perms is not None or self.world > 1:
+            return _Route("bag", None, bags, labels, None)
+        return _Route("window_run" if self._exec_window_ok(xs, labels, i) else "stream", None, xs, labels, None)
+
+    def _bag_after_bag(self, bags, labels, i, perms, shuffles, update, aggregate):
+        """A window no call and neither window form takes: train_step (``update`` False: forward_backward) bag after bag, which scales
+        by 1 / accumulation_steps and so needs exactly that many bags.  ``aggregate``: self.last gathers the bags' - "bags", "risk"."""
+        assert len(bags) == self.accum and len(labels) == len(bags), "window_step takes exactly accumulation_steps bags"
+        step = self.train_step if update else self.forward_backward
+        outs, per = [], []
+        for j, (b, l) in enumerate(zip(bags, labels)):
+            outs.append(step(b, l, i=i, **({} if perms is None else {"perm": perms[j], "ids_shuffle": shuffles[j]})))
+            per.append(self.last)
+        logits, losses = [o[0] for o in outs], [o[1] for o in outs]
+        if aggregate:
+            self.last = dict(self.last, logits=logits, losses=losses, bags=per, risk=torch.cat([b["risk"].view(1) for b in per]))
+        return logits, losses
+
+    def _stream_window(self, xs, labels, i, n_streams, update):
+        """window_step's stream form (its docstring): the window's bags round-robin on HIP streams, one preparation, one update."""
+        k = len(xs)
         S = max(1, min(int(n_streams or self.window_streams), k))
         dev = xs[0].device
         s, fl = self.s, self.flat
@@ -1633,40 +1649,52 @@ class FusedTrainer:
         window's streams; ``graph.replay()`` runs prep, the k bags, the slab sum, Adam + EMA."""
         if self.world > 1:
             raise mh.L.MhimxError("capture_window: one process (data-parallel ranks exchange gradients between windows: use capture())")
-        if self.loss == "nll_surv":
-            xs_ = [self.s._check_x(b) for b in bags]
-            Ys_ = [self._surv_label(l, xs_[0].device)[0] for l in labels]
-            if not (self._pure_window_ok(xs_, Ys_) if self.model_kind == "mhim_pure" else self._ragged_window_ok(xs_, Ys_, kw.get("i"))):
-                raise mh.L.MhimxError("capture_window: mhimx_pure_window_run_surv / mhimx_ragged_window_run_surv does not take these bags / this model")
-        elif self.model_kind == "mhim_pure" and self.accum > 1:
-            xs_ = [self.s._check_x(b) for b in bags]
-            if not (self._dsmil_window_ok(xs_, labels) if self.s.baseline == "dsmil" else self._pure_window_ok(xs_, labels)):
-                raise mh.L.MhimxError("capture_window: mhimx_pure_window_run / mhimx_dsmil_window_run does not take these bags / this model")
-        elif self._ragged_window_ok([self.s._check_x(b) for b in bags], labels, kw.get("i")):
-            pass                                    # (window_step decides between mhimx_window_run and mhimx_ragged_window_run)
-        elif self._dsmil_mhim_window_ok([self.s._check_x(b) for b in bags], labels, kw.get("i")):
-            pass                                    # (mhimx_dsmil_mhim_window_run)
-        elif not self.window_ok([self.s._check_x(b) for b in bags], kw.get("i")):
+        # the route of the widened bags without injected draws (_window_route says where that differs from window_step's own question)
+        i, surv = kw.get("i"), self.loss == "nll_surv"
+        xs = [self.s._check_x(b) for b in bags]
+        r = self._window_route(xs, [self._surv_label(l, xs[0].device) for l in labels] if surv else labels, i, None, None)
+        if surv or (self.model_kind == "mhim_pure" and self.accum > 1):
+            if r.fam is None:
+                calls = "mhimx_pure_window_run_surv / mhimx_ragged_window_run_surv" if surv else "mhimx_pure_window_run / mhimx_dsmil_window_run"
+                raise mh.L.MhimxError(f"capture_window: {calls} does not take these bags / this model")
+        elif r.name == "bag" and not self._ragged_window_ok(xs, labels, i):
             raise mh.L.MhimxError("capture_window: these bags / this model do not take the single-pass ABMIL step")
+        step = lambda: self.window_step(bags, labels, n_streams=n_streams, **kw)
         self._capturing = True
         try:
-            if self._cap_stream is None:
-                self._cap_stream = torch.cuda.Stream()
-            cs = self._cap_stream
-            cs.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(cs):
-                for _ in range(warmup):
-                    self.window_step(bags, labels, n_streams=n_streams, **kw)
-            torch.cuda.current_stream().wait_stream(cs)
+            cs = self._capture_stream()
+            self._warm_up(cs, step, warmup)
             torch.cuda.synchronize()
-            if self._graph_pool is None:
-                self._graph_pool = torch.cuda.graph_pool_handle()
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, pool=self._graph_pool, stream=cs):
-                self.window_step(bags, labels, n_streams=n_streams, **kw)
-            return g
+            return self._record(cs, step)[0]
         finally:
             self._capturing = False
+
+    # ------------------------------------------------------------------------------------------------- graph capture: the shared steps
+    def _capture_stream(self):
+        """The trainer's capture stream - made on first use - behind the work the current stream holds."""
+        if self._cap_stream is None:
+            self._cap_stream = torch.cuda.Stream()
+        self._cap_stream.wait_stream(torch.cuda.current_stream())
+        return self._cap_stream
+
+    def _warm_up(self, cs, fn, n=1):
+        """``fn`` n times on the capture stream, the current stream behind it.  Returns what the last call returned."""
+        out = None
+        with torch.cuda.stream(cs):
+            for _ in range(n):
+                out = fn()
+        torch.cuda.current_stream().wait_stream(cs)
+        return out
+
+    def _record(self, cs, fn, **kw):
+        """``fn`` recorded into a new hipGraph on the capture stream and the trainer's graph pool (made on first use); ``kw``:
+        torch.cuda.graph's (capture_error_mode).  Returns (graph, what fn returned)."""
+        if self._graph_pool is None:
+            self._graph_pool = torch.cuda.graph_pool_handle()
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g, pool=self._graph_pool, stream=cs, **kw):
+            out = fn()
+        return g, out
 
     def _bind_grads(self):
         """Every trainable parameter's .grad IS its view of the flat gradient buffer: autograd accumulates straight into the
@@ -1808,17 +1836,10 @@ class FusedTrainer:
     def _capture(self, bag, label, warmup, **kw):
         # warm up ON the capture stream: autograd's gradient-accumulation nodes (TransMIL student) remember the stream they
         # were created on, and a node living on another stream would need a cross-stream event inside the capture
-        if self._cap_stream is None:
-            self._cap_stream = torch.cuda.Stream()
-        cs = self._cap_stream
-        cs.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(cs):
-            for _ in range(warmup):
-                self.train_step(bag, label, **kw)
-        torch.cuda.current_stream().wait_stream(cs)
+        step = lambda: self.train_step(bag, label, **kw)
+        cs = self._capture_stream()
+        self._warm_up(cs, step, warmup)
         torch.cuda.synchronize()
-        if self._graph_pool is None:
-            self._graph_pool = torch.cuda.graph_pool_handle()
         if self.world > 1:
             # data parallel: the gradient all-reduce stays OUTSIDE the graphs (compute | RCCL all-reduce | optimiser): a
             # collective inside a captured graph depends on the RCCL build, and a rank that replays while another launches
@@ -1828,22 +1849,20 @@ class FusedTrainer:
             # is graph | one collective | graph, nothing else on the host.  capture_error_mode "thread_local": the process group's
             # watchdog thread polls its events while we capture (a "global" capture would be invalidated by it).
             fl = self.flat
-            g_fb, g_up = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g_fb, pool=self._graph_pool, stream=cs, capture_error_mode="thread_local"):
+            def fb():
                 self.forward_backward(bag, label, **kw)        # (leaves the QueryChain's tokens: static buffer of this capture)
                 fill_tail(fl.grad, fl.student, fl.n_train, self._chain)
+            g_fb, _ = self._record(cs, fb, capture_error_mode="thread_local")
             ops.step_images(None)                              # (graph-static images of the capture-time weights: never hand them out)
             self._all_reduce(fl.grad)
             scale = 1.0 / self.world
-            with torch.cuda.graph(g_up, pool=self._graph_pool, stream=cs, capture_error_mode="thread_local"):
+            def up():
                 finish_tail(fl.grad, fl.student, fl.n_train, scale, self._chain)
                 self._apply(scale)
+            g_up, _ = self._record(cs, up, capture_error_mode="thread_local")
             fl.grad.zero_()                                # (the capture-time all-reduce summed stale values)
             return _SplitStep(self, g_fb, g_up)
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g, pool=self._graph_pool, stream=cs):
-            self.train_step(bag, label, **kw)
-        return g
+        return self._record(cs, step)[0]
 
     def capture_steps(self, bags, labels, warmup=1, **kw):
         """ONE hipGraph of len(bags) consecutive COMPLETE train steps (each with its own update), bag after bag: a trainer that walks a
@@ -1853,25 +1872,15 @@ class FusedTrainer:
         assert self.accum == 1 and self.world == 1, "capture_steps: one process, one bag per update"
         if self.s.mrh_sche is not None:
             raise mh.L.MhimxError("capture_steps(): the HAM-ratio schedule changes the launch shapes per iteration")
+        def steps():
+            for b, l in zip(bags, labels):
+                self.train_step(b, l, **kw)
         self._capturing = True
         try:
-            if self._cap_stream is None:
-                self._cap_stream = torch.cuda.Stream()
-            cs = self._cap_stream
-            cs.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(cs):
-                for _ in range(warmup):
-                    for b, l in zip(bags, labels):
-                        self.train_step(b, l, **kw)
-            torch.cuda.current_stream().wait_stream(cs)
+            cs = self._capture_stream()
+            self._warm_up(cs, steps, warmup)
             torch.cuda.synchronize()
-            if self._graph_pool is None:
-                self._graph_pool = torch.cuda.graph_pool_handle()
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, pool=self._graph_pool, stream=cs):
-                for b, l in zip(bags, labels):
-                    self.train_step(b, l, **kw)
-            return g
+            return self._record(cs, steps)[0]
         finally:
             self._capturing = False
 
@@ -1915,7 +1924,7 @@ class FusedTrainer:
         if key in st["bad"]:
             return None
         ent = st["graphs"].get(key)
-        if ent is not None and ent[8] != scal:
+        if ent is not None and ent.scal != scal:
             st["graphs"].pop(key)
             ent = None
             n_re = st.setdefault("rescaled", {})
@@ -1928,19 +1937,11 @@ class FusedTrainer:
         if len(st["seen"]) > 4096:                               # (visit counts of shapes that never came back)
             st["seen"] = {k_: v_ for k_, v_ in st["seen"].items() if k_ in st["graphs"]}
         fn = self.train_step if what == "train_step" else self.forward_backward
-        if auto and self._cap_stream is None:
-            self._cap_stream = torch.cuda.Stream()
         if ent is None:
             st["seen"][key] = st["seen"].get(key, 0) + 1
             if st["seen"][key] < (3 if auto else 2):
-                if auto:
-                    cur = torch.cuda.current_stream()
-                    self._cap_stream.wait_stream(cur)
-                    with torch.cuda.stream(self._cap_stream):
-                        logits, losses = fn(bag, label, i=i)
-                    cur.wait_stream(self._cap_stream)
-                else:
-                    logits, losses = fn(bag, label, i=i)
+                step = lambda: fn(bag, label, i=i)
+                logits, losses = self._warm_up(self._capture_stream(), step) if auto else step()
                 return logits, losses, self.last["patch_num"], self.last["keep_num"]
             while len(st["graphs"]) >= max(1, int(cache)):        # the least recently used shape makes room
                 st["graphs"].pop(next(iter(st["graphs"])))
@@ -1949,56 +1950,46 @@ class FusedTrainer:
             if ar is None or ar.numel() < need or ar.dtype != x.dtype or ar.device != x.device:
                 ar = st["arena"] = torch.empty(need, dtype=x.dtype, device=x.device)
             xs, ls = ar[:need].view(x.shape), torch.empty_like(label)
-            if self._cap_stream is None:
-                self._cap_stream = torch.cuda.Stream()
-            if self._graph_pool is None:
-                self._graph_pool = torch.cuda.graph_pool_handle()
-            cs = self._cap_stream
-            cs.wait_stream(torch.cuda.current_stream())
+            cs = self._capture_stream()                           # (no warm-up here: the shape's earlier visits were it)
             torch.cuda.synchronize()
-            g = torch.cuda.CUDAGraph()
             micro, host_step = self._micro, self.flat.step
+
+            def restore(failed):
+                """The host's state as before the recording (a recording runs nothing); ``failed``: and nothing left pending."""
+                self._micro, self.flat.step = micro, host_step
+                if failed:
+                    self._fold_list, self._defer = None, ops.ReduceList()
+                ops.step_images(None)
             self._capturing = True
             try:
-                with torch.cuda.graph(g, pool=self._graph_pool, stream=cs):      # (recorded, not run: the replay below is this bag's step)
-                    logits, losses = fn(xs, ls, i=i)
+                g, (logits, losses) = self._record(cs, lambda: fn(xs, ls, i=i))      # (recorded, not run: the replay below is this bag's step)
             except Exception as exc:
                 # a step that turned out not to be capturable (a host read-back somewhere): this shape runs eagerly from now on.  Argument
                 # errors of the library (a label on the wrong device, a refused shape) are the caller's bug, not a capture problem: they
                 # propagate (ADVICE r5); the first capture failure of every other kind is kept for inspection
+                restore(True)
                 if isinstance(exc, mh.L.MhimxError):
-                    self._capturing = False
-                    self._micro, self.flat.step = micro, host_step
-                    self._fold_list = None
-                    self._defer = ops.ReduceList()
-                    ops.step_images(None)
                     raise
                 st["bad"].add(key)
                 st.setdefault("errors", []).append(repr(exc))
-                self._micro, self.flat.step = micro, host_step
-                self._fold_list = None
-                self._defer = ops.ReduceList()
-                ops.step_images(None)
                 torch.cuda.synchronize()
                 return None
             finally:
                 self._capturing = False
-            ops.step_images(None)
-            self._micro, self.flat.step = micro, host_step
-            ent = st["graphs"][key] = (g, xs, ls, logits, losses, self.last["patch_num"], self.last["keep_num"], dict(self.last), scal)
+            restore(False)
+            ent = st["graphs"][key] = _ShapeGraph(g, xs, ls, logits, losses, self.last["patch_num"], self.last["keep_num"], dict(self.last), scal)
         else:
             st["graphs"][key] = st["graphs"].pop(key)             # most recently used: to the end of the (insertion-ordered) dict
-        g, xs, ls, logits, losses, pn, kn, last, _ = ent
-        xs.copy_(x)
-        ls.copy_(label)
-        g.replay()
+        ent.x.copy_(x)
+        ent.label.copy_(label)
+        ent.graph.replay()
         if what == "train_step":
             self.flat.step += 1                                # (the host's count of updates: the device counter advanced in the graph)
             ops.step_images(None)
         else:
             self._micro += 1
-        self.last = last
-        return logits, losses, pn, kn
+        self.last = ent.last
+        return ent.logits, ent.losses, ent.patch_num, ent.keep_num
 
     def train_step(self, bag, label, **kw):
         # (a step that is followed by its update right here may leave its last reductions to the update kernel: _nat_bag)
