@@ -1147,6 +1147,85 @@ int mhimx_infer_dsmil_run(void* stream, const mhimx_infer_dsmil_cfg* cfg, int32_
                           const int64_t* labels_dev, const mhimx_infer_dsmil_out* out, void* ws, int64_t ws_bytes, int32_t x_dtype);
 
 /* ------------------------------------------------------------------------------------------
+ * Ragged multi-bag inference for MHIM(TransMIL): the eval-mode forward of the reference's DEFAULT baseline ('selfattn', the Nystrom
+ * encoder) for n_bags bags of DIFFERENT row counts in one call - a TransMIL validation or test pass as one C call per chunk of bags
+ * instead of about 35 launches per bag (two of them the persistent pseudo-inverse chain of 26 grid-wide stages) from the host loop.
+ * replaces: modules/mhim.py:229-272 (forward_test, baseline == 'selfattn', merge_test off) over mhim_modules/baseline.py:196-288
+ *           (SAttention, TransLayer), modules/nystrom_attention.py:12-27,65-152 (the pseudo-inverse iteration, NystromAttention.forward),
+ *           modules/emb_position.py:85-120 (PPEG) under engines/common_mil.py:56-68 (validate_func) and the per-bag loop + criterion call
+ *           of engines/base_engine.py:234-329.
+ * Per bag of N rows (eval mode: every dropout is the identity):
+ *           h = act(X W1^T + b1),  tok = [cls_token; h]: n = N + 1 tokens.  Every layer pads zero rows IN FRONT to T = 256 ceil(n / 256)
+ *           tokens, l = T / 256 (the pad tokens stay unmasked keys, as in the reference).
+ *           layer:  y = x + to_out(Nystrom(to_qkv(LN(x)))) on the n token rows.  Nystrom, per head (8 x 64): q~, k~ = means of l
+ *           consecutive q / k rows (256 landmarks),  a2 = softmax(s q~ k~^T), s = 1/8,  z0 = a2^T / (max column sum x max row sum, both over
+ *           the bag's 8 heads),  six times z <- 1/4 z (13 I - az (15 I - az (7 I - az))), az = a2 z,  a3v = softmax_n(s q~ k^T) v,
+ *           w2 = z a3v,  out = res_conv(v) + softmax_m(s q k~^T) w2  (33-tap depth-wise convolution along the T rows).
+ *           x2 = [y1[0]; PPEG(y1[1:])] (side ceil(sqrt(N)), wrap, 7 x 7 minimum),  y2 = layer2(x2),  z = LN(y2[0]) (the cls row only),
+ *           logits = z Wp^T + bp,  loss = cross entropy of the row (a label outside [0, C) gives NaN).
+ *           The wide products (feature, to_qkv, to_out, the landmark products, the streamed attention) run in the 3-term bf16 form
+ *           (~2^-16); LayerNorm, the softmaxes, the stencils, the predictor and the loss in fp32.
+ * Workspace = ONE concatenated padded token space: bag b owns T[b] consecutive rows from tok0[b] on, its pad[b] = T[b] - n pad rows first.
+ * mhimx_infer_transmil_layout gives the byte offsets of every intermediate (tests read them).
+ * 96 launches whatever n_bags is:  3 in front (W1 image; the ragged projection of bag_project.hip, all three element types, written at row
+ * tok0[b] + pad[b] + 1; the cls rows),  45 per layer (LayerNorm over the token space with exact zeros on the pad rows - to_qkv has no bias,
+ * so the pad rows of qkv are exact zeros;  to_qkv as one GEMM over all sum T rows;  bag-batched landmark means;  q~ k~^T as 8 launches,
+ * one per head over all bags;  mhimx_softmax_rows with R = n 8 256;  3 for the per-bag pseudo-inverse start;  24 mhimx_bmm_affine2 /
+ * mhimx_bmm_affine launches with batch = 8 n - never mhimx_bmm_chain;  bag-batched a3v partials + merge;  w2 with batch = 8 n;  bag-batched
+ * residual convolution;  bag-batched out launch;  to_out + bias + residual as one GEMM),  2 between the layers (PPEG stencil image, the
+ * bag-batched PPEG launch),  1 tail (grid = bags: final norm of the cls row, predictor, loss).
+ * Row-wise stages are chunk-wide, the landmark stage runs over all 8 n matrices at once, the token-streaming stages are bag-batched
+ * (grid z = bag; a by-value table relocates the single-bag kernel's arguments; per bag min(T / 64, 32) chunks, the single-bag kernel's
+ * tile walk and merge order); no stage loops over bags.
+ * Properties, those of mhimx_infer_run: enqueue-only and capturable; no allocation, synchronisation or host-to-device copy; no
+ * floating-point atomics; no workgroup waits for another; the same bytes on two runs; a bag's outputs have the same bits wherever it
+ * stands in a call and whatever its neighbours are.
+ * Shapes: E = 512, 8 x 64 heads, 256 landmarks, 1 <= C <= 16, D % 256 == 0, every N >= 1, at most MHIMX_INFER_MAX bags; the checks on
+ * the bag table and x_dtype are those of mhimx_infer_run_x.  Anything else returns < 0 before any device call; mhimx_last_error names
+ * the bag.
+ * Workspace: mhimx_infer_transmil_ws_bytes (pure host arithmetic; < 0 on a refused shape), 256-byte aligned: 26 KiB per padded token
+ * (x 2 x 2, qkv 2 x 6, block output 2 x 2, y 2 x 2, LN rows 2) and about 56 MiB per bag (landmark matrices, the a3v partials).
+ * MHIMX_VERSION stays 620: additions only.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct {
+  const float *ln_w, *ln_b;                       /* layerK.norm.{weight, bias} [512]                                                     */
+  const float* w_qkv;                             /* layerK.attn.to_qkv.weight [1536, 512] (no bias)                                      */
+  const float *w_out, *b_out;                     /* layerK.attn.to_out.0.{weight [512, 512], bias [512]}                                 */
+  const float* conv_w;                            /* layerK.attn.res_conv.weight [8, 1, 33, 1]                                            */
+} mhimx_transmil_layer;
+typedef struct {
+  int64_t D, C;                                   /* input_dim, classes                                                                   */
+  int32_t act;                                    /* MHIMX_ACT_* of the feature layer                                                     */
+  int32_t pad;
+  const float *w1, *b1;                           /* feature.0.{weight [512, D], bias [512]}                                              */
+  const float* cls_token;                         /* online_encoder.cls_token [1, 1, 512]                                                 */
+  mhimx_transmil_layer layer[2];                  /* online_encoder.layer1 / layer2                                                       */
+  const float *w7, *w5, *w3, *b7, *b5, *b3;       /* pos_embedding.proj / proj1 / proj2 .{weight [512, 1, k, k], bias [512]}              */
+  const float *norm_w, *norm_b;                   /* online_encoder.norm.{weight, bias} [512]                                             */
+  const float *wp, *bp;                           /* predictor.{weight [C, 512], bias [C]}                                                */
+} mhimx_infer_transmil_cfg;
+typedef struct {                                  /* byte offsets inside the workspace; [l]: layer l                                      */
+  int64_t n_bags, tokens;                         /* tokens = sum T                                                                       */
+  int64_t tok0[MHIMX_INFER_MAX], T[MHIMX_INFER_MAX], pad[MHIMX_INFER_MAX];   /* rows: bag b's first row, padded tokens, pad rows          */
+  int64_t x[2];                                   /* [tokens, 512] the token rows going into the layer (pad rows: not written, not read)  */
+  int64_t qkv[2];                                 /* [tokens, 1536] q | k | v; pad rows exact zeros                                       */
+  int64_t lm[2];                                  /* [n, 256, 1024] landmark means q~ | k~                                                */
+  int64_t a2[2], z[2];                            /* [n, 8, 256, 256] softmax(s q~ k~^T), its pseudo-inverse after six iterations         */
+  int64_t a3v[2], lse3[2], w2[2];                 /* [n, 8, 256, 64], [n, 8, 256] (base-2 log-sum-exp), [n, 8, 256, 64]                   */
+  int64_t out[2];                                 /* [tokens, 512] the block output res_conv(v) + a1 w2                                   */
+  int64_t y[2];                                   /* [tokens, 512] x + to_out(out) (pad rows: to_out of the pad tokens)                   */
+  int64_t cls;                                    /* [n, 512] the cls rows after the final norm                                           */
+  int64_t total;                                  /* = mhimx_infer_transmil_ws_bytes                                                      */
+} mhimx_infer_transmil_layout;
+int64_t mhimx_infer_transmil_ws_bytes(const mhimx_infer_transmil_cfg* cfg, int32_t n_bags, const mhimx_infer_bag* bags);
+int mhimx_infer_transmil_layout_of(const mhimx_infer_transmil_cfg* cfg, int32_t n_bags, const mhimx_infer_bag* bags,
+                                   mhimx_infer_transmil_layout* out);
+/* labels_dev: int64 [n_bags] on the device, or NULL; logits [n_bags, C]; loss [n_bags] or NULL (needs labels); z [n_bags, 512] or NULL
+ * (the cls rows after the final norm); x_dtype: MHIMX_X_* */
+int mhimx_infer_transmil_run(void* stream, const mhimx_infer_transmil_cfg* cfg, int32_t n_bags, const mhimx_infer_bag* bags,
+                             const int64_t* labels_dev, float* logits, float* loss, float* z, void* ws, int64_t ws_bytes, int32_t x_dtype);
+
+/* ------------------------------------------------------------------------------------------
  * Ragged accumulation window of the teacher-free DSMIL model ('mhim_pure' with baseline 'dsmil': the recipe's first training for the
  * second MHIM baseline): ONE optimiser update over n_bags bags of DIFFERENT row counts in one call; n_bags = 1 is the single-bag step.
  * replaces: engines/base_engine.py:29-51,76-120 (the accumulation window: every bag's loss divided by the window's length, the gradients

@@ -247,6 +247,25 @@ class InferDsmilOut(C.Structure):
 
 
 INFER_MAX = 32               # MHIMX_INFER_MAX
+
+
+class TransmilLayer(C.Structure):
+    """mhimx_transmil_layer: one TransLayer (norm, attn.to_qkv, attn.to_out.0, attn.res_conv)."""
+    _fields_ = [(n, c_f32p) for n in ("ln_w", "ln_b", "w_qkv", "w_out", "b_out", "conv_w")]
+
+
+class InferTransmilCfg(C.Structure):
+    """mhimx_infer_transmil_cfg: the eval-mode forward of ONE MHIM(TransMIL) model over bags of different row counts."""
+    _fields_ = ([("D", C.c_int64), ("C", C.c_int64), ("act", C.c_int32), ("pad", C.c_int32)]
+                + [(n, c_f32p) for n in ("w1", "b1", "cls_token")] + [("layer", TransmilLayer * 2)]
+                + [(n, c_f32p) for n in ("w7", "w5", "w3", "b7", "b5", "b3", "norm_w", "norm_b", "wp", "bp")])
+
+
+class InferTransmilLayout(C.Structure):
+    """mhimx_infer_transmil_layout: byte offsets of every intermediate inside the workspace ([l]: layer l)."""
+    _fields_ = ([("n_bags", C.c_int64), ("tokens", C.c_int64)] + [(n, C.c_int64 * INFER_MAX) for n in ("tok0", "T", "pad")]
+                + [(n, C.c_int64 * 2) for n in ("x", "qkv", "lm", "a2", "z", "a3v", "lse3", "w2", "out", "y")]
+                + [("cls", C.c_int64), ("total", C.c_int64)])
 INFER_MAX_ROWS = 4194304     # MHIMX_INFER_MAX_ROWS
 X_F32, X_F16, X_BF16 = 0, 1, 2   # MHIMX_X_*: the element type of the bags' rows in the three *_run_x calls
 
@@ -489,6 +508,9 @@ SYMBOLS = {
     "mhimx_infer_run_x": (C.c_int, [_P, C.POINTER(InferCfg), _I32, _P, _P, C.POINTER(InferOut), _P, _I64, _I32]),
     "mhimx_infer_dsmil_ws_bytes": (_I64, [C.POINTER(InferDsmilCfg), _I32, _P]),
     "mhimx_infer_dsmil_run": (C.c_int, [_P, C.POINTER(InferDsmilCfg), _I32, _P, _P, C.POINTER(InferDsmilOut), _P, _I64, _I32]),
+    "mhimx_infer_transmil_ws_bytes": (_I64, [C.POINTER(InferTransmilCfg), _I32, _P]),
+    "mhimx_infer_transmil_layout_of": (C.c_int, [C.POINTER(InferTransmilCfg), _I32, _P, C.POINTER(InferTransmilLayout)]),
+    "mhimx_infer_transmil_run": (C.c_int, [_P, C.POINTER(InferTransmilCfg), _I32, _P, _P, _P, _P, _P, _P, _I64, _I32]),
     "mhimx_topk_many_ws_bytes": (_I64, [_I32, _P, _I64]),
     "mhimx_topk_many": (C.c_int, [_P, _P, _I32, _P, _I64, _I32, _P, _P, _P, _I64]),
     "mhimx_step_run_many": (C.c_int, [_P, C.POINTER(StepCfg), _I32, _P, _P, _P, _P, C.POINTER(StepCounts), C.POINTER(StepSeeds), _I64, _P, _I64]),

@@ -5,6 +5,7 @@
 #include <math.h>
 
 #include "common.hpp"
+#include "nys_args.hpp"
 
 namespace mhimx {
 int transpose(hipStream_t st, const float* in, float* out, int64_t R, int64_t C);   // gemm.hip
@@ -137,7 +138,7 @@ __global__ void landmark_fwd_kernel(const float* __restrict__ x, int64_t ldx, in
 }
 // the same sums for 16-byte aligned rows with C % 256 == 0: block = (landmark, 256 columns); its four waves take the rows t = w mod 4
 // with four independent 16-byte loads in flight each (the scalar form above is one l-long dependent chain per thread: latency bound)
-__global__ __launch_bounds__(256) void landmark_fwd_vec_kernel(const float* __restrict__ x, int64_t ldx, int l, int C, float* __restrict__ out) {
+MHIMX_DEV void landmark_fwd_vec_body(const float* __restrict__ x, int64_t ldx, int l, int C, float* __restrict__ out) {
   typedef float f4 __attribute__((ext_vector_type(4)));
   __shared__ f4 part[3][64];
   const int j = blockIdx.x, lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -160,6 +161,17 @@ __global__ __launch_bounds__(256) void landmark_fwd_vec_kernel(const float* __re
     const float inv = 1.f / (float)l;
     reinterpret_cast<f4*>(out + (int64_t)j * C + blockIdx.y * 256)[lane] = acc * inv;
   }
+}
+__global__ __launch_bounds__(256) void landmark_fwd_vec_kernel(const float* __restrict__ x, int64_t ldx, int l, int C, float* __restrict__ out) {
+  landmark_fwd_vec_body(x, ldx, l, C, out);
+}
+// bag-batched entry (NyBags, nys_args.hpp): blockIdx.z = bag; every bag has 256 landmarks of l = T / 256 rows
+__global__ __launch_bounds__(256) void landmark_fwd_vec_many_kernel(NyBags tb, const float* __restrict__ x, int64_t ldx, int C,
+                                                                    float* __restrict__ out) {
+  int64_t tok0 = tb.tok0[0];
+  int T = tb.T[0];
+  NY_PICK(tok0, tb.tok0, blockIdx.z) NY_PICK(T, tb.T, blockIdx.z)
+  landmark_fwd_vec_body(x + tok0 * ldx, ldx, T / 256, C, out + (int64_t)blockIdx.z * 256 * C);
 }
 __global__ void landmark_bwd_kernel(const float* __restrict__ dout, int l, int C, float* __restrict__ dx, int64_t ldx, int64_t T,
                                     int accumulate) {
@@ -268,8 +280,7 @@ __global__ __launch_bounds__(AT) void pinv_sums_kernel(const float* __restrict__
   s = blk_sum4(s, red);
   if (threadIdx.x == 0) (is_col ? colsum : rowsum)[q] = s;
 }
-__global__ __launch_bounds__(AT) void pinv_argmax_kernel(const float* __restrict__ rowsum, const float* __restrict__ colsum, int total,
-                                                         float* __restrict__ stats) {
+MHIMX_DEV void pinv_argmax_body(const float* __restrict__ rowsum, const float* __restrict__ colsum, int total, float* __restrict__ stats) {
   __shared__ float bv[AT];
   __shared__ int bi[AT];
   for (int which = 0; which < 2; ++which) {
@@ -292,8 +303,17 @@ __global__ __launch_bounds__(AT) void pinv_argmax_kernel(const float* __restrict
     __syncthreads();
   }
 }
+__global__ __launch_bounds__(AT) void pinv_argmax_kernel(const float* __restrict__ rowsum, const float* __restrict__ colsum, int total,
+                                                         float* __restrict__ stats) {
+  pinv_argmax_body(rowsum, colsum, total, stats);
+}
+// per-bag form: blockIdx.x = bag, the maxima over that bag's `per` row / column sums (per = 8 n: its 8 matrices)
+__global__ __launch_bounds__(AT) void pinv_argmax_many_kernel(const float* __restrict__ rowsum, const float* __restrict__ colsum, int per,
+                                                              float* __restrict__ stats) {
+  pinv_argmax_body(rowsum + (int64_t)blockIdx.x * per, colsum + (int64_t)blockIdx.x * per, per, stats + 4 * blockIdx.x);
+}
 // z0[b,j,i] = a[b,i,j] / (c*r)
-__global__ void pinv_init_kernel(const float* __restrict__ a, const float* __restrict__ stats, int B, int n, float* __restrict__ z) {
+MHIMX_DEV void pinv_init_body(const float* __restrict__ a, const float* __restrict__ stats, int n, float* __restrict__ z) {
   __shared__ float tile[32][33];
   const float s = 1.f / (stats[0] * stats[1]);
   const int b = blockIdx.z;
@@ -301,6 +321,13 @@ __global__ void pinv_init_kernel(const float* __restrict__ a, const float* __res
   for (int i = threadIdx.y; i < 32; i += blockDim.y) tile[i][threadIdx.x] = a[((int64_t)b * n + r0 + i) * n + c0 + threadIdx.x];
   __syncthreads();
   for (int i = threadIdx.y; i < 32; i += blockDim.y) z[((int64_t)b * n + c0 + i) * n + r0 + threadIdx.x] = tile[threadIdx.x][i] * s;
+}
+__global__ void pinv_init_kernel(const float* __restrict__ a, const float* __restrict__ stats, int B, int n, float* __restrict__ z) {
+  pinv_init_body(a, stats, n, z);
+}
+// per-bag form: matrix blockIdx.z belongs to bag blockIdx.z / 8 and is scaled by that bag's maxima
+__global__ void pinv_init_many_kernel(const float* __restrict__ a, const float* __restrict__ stats, int n, float* __restrict__ z) {
+  pinv_init_body(a, stats + 4 * (blockIdx.z >> 3), n, z);
 }
 // backward: da = dz^T * s  - g * s * (1/c on the argmax row, 1/r on the argmax column),  g = sum(dz * z0)/s ... see host
 __global__ __launch_bounds__(AT) void dot_total_kernel(const float* __restrict__ x, const float* __restrict__ y, int64_t n,
@@ -529,9 +556,8 @@ __global__ __launch_bounds__(AT) void resconv_strip_kernel(const float* __restri
 // times through L2 (48 rows per 16 outputs).
 constexpr int RT_ROWS = 128, RT_CH = 64;
 template <int KS>
-__global__ __launch_bounds__(256) void resconv_tile_kernel(const float* __restrict__ v, int64_t ldv, const float* __restrict__ w, int dh,
-                                                           int64_t T, int C, float* __restrict__ out, int64_t ldo, int accumulate,
-                                                           int flip) {
+MHIMX_DEV void resconv_tile_body(const float* __restrict__ v, int64_t ldv, const float* __restrict__ w, int dh, int64_t T, int C,
+                                 float* __restrict__ out, int64_t ldo, int accumulate, int flip) {
   typedef float f4 __attribute__((ext_vector_type(4)));
   constexpr int P = KS / 2, IN = RT_ROWS + 2 * P;
   __shared__ __attribute__((aligned(16))) float tile[IN * RT_CH];
@@ -570,6 +596,22 @@ __global__ __launch_bounds__(256) void resconv_tile_kernel(const float* __restri
         *p = accumulate ? *p + acc[j] : acc[j];
       }
   }
+}
+template <int KS>
+__global__ __launch_bounds__(256) void resconv_tile_kernel(const float* __restrict__ v, int64_t ldv, const float* __restrict__ w, int dh,
+                                                           int64_t T, int C, float* __restrict__ out, int64_t ldo, int accumulate,
+                                                           int flip) {
+  resconv_tile_body<KS>(v, ldv, w, dh, T, C, out, ldo, accumulate, flip);
+}
+// bag-batched entry: blockIdx.z = bag; the stencil sees the bag's own T rows (zeros beyond both ends, as in the single-bag launch)
+template <int KS>
+__global__ __launch_bounds__(256) void resconv_tile_many_kernel(NyBags tb, const float* __restrict__ v, int64_t ldv, const float* __restrict__ w,
+                                                                int dh, int C, float* __restrict__ out, int64_t ldo) {
+  int64_t tok0 = tb.tok0[0];
+  int T = tb.T[0];
+  NY_PICK(tok0, tb.tok0, blockIdx.z) NY_PICK(T, tb.T, blockIdx.z)
+  if ((int64_t)blockIdx.x * RT_ROWS >= T) return;
+  resconv_tile_body<KS>(v + tok0 * ldv, ldv, w, dh, T, C, out + tok0 * ldo, ldo, 0, 0);
 }
 // dw partials: block (x = token chunk, y = 256-channel group = 4 heads of 64); part[x][h*KS + tau]
 template <int KS>
@@ -614,9 +656,8 @@ constexpr int PS = 8;                   // PPEG: outputs per thread along a grid
 // above, with 3 reads per output, does gain from its LDS window.)
 constexpr int PSY = 4;
 template <int FLIP>
-__global__ __launch_bounds__(AT) void ppeg_strip_kernel(const float* __restrict__ in, int64_t N, int C, int H, int64_t wrapN,
-                                                        const float* __restrict__ wc, const float* __restrict__ bc,
-                                                        float* __restrict__ out, int nsx) {
+MHIMX_DEV void ppeg_strip_body(const float* __restrict__ in, int64_t N, int C, int H, int64_t wrapN, const float* __restrict__ wc,
+                               const float* __restrict__ bc, float* __restrict__ out, int nsx) {
   const int c = blockIdx.y * AT + threadIdx.x;
   if (c >= C) return;
   const int gy0 = (blockIdx.x / nsx) * PSY, gx0 = (blockIdx.x % nsx) * PS;
@@ -665,6 +706,27 @@ __global__ __launch_bounds__(AT) void ppeg_strip_kernel(const float* __restrict_
       const int64_t cell = (int64_t)(gy0 + jy) * H + gx0 + j;
       if (gy0 + jy < H && gx0 + j < H && cell < N) out[cell * C + c] = acc[jy][j];
     }
+}
+template <int FLIP>
+__global__ __launch_bounds__(AT) void ppeg_strip_kernel(const float* __restrict__ in, int64_t N, int C, int H, int64_t wrapN,
+                                                        const float* __restrict__ wc, const float* __restrict__ bc,
+                                                        float* __restrict__ out, int nsx) {
+  ppeg_strip_body<FLIP>(in, N, C, H, wrapN, wc, bc, out, nsx);
+}
+// bag-batched forward entry: blockIdx.z = bag; the stencil runs on the n - 1 rows behind the bag's cls row (baseline.py:265-266), which
+// the bag's first block copies through
+__global__ __launch_bounds__(AT) void ppeg_strip_many_kernel(NyBags tb, const float* __restrict__ in, int C, const float* __restrict__ wc,
+                                                             const float* __restrict__ bc, float* __restrict__ out) {
+  int64_t tok0 = tb.tok0[0];
+  int T = tb.T[0], n = tb.n[0], H = tb.H[0], wrapN = tb.wrapN[0];
+  NY_PICK(tok0, tb.tok0, blockIdx.z) NY_PICK(T, tb.T, blockIdx.z) NY_PICK(n, tb.n, blockIdx.z) NY_PICK(H, tb.H, blockIdx.z)
+  NY_PICK(wrapN, tb.wrapN, blockIdx.z)
+  const int nsx = (H + PS - 1) / PS;
+  if ((int)blockIdx.x >= nsx * ((H + PSY - 1) / PSY)) return;
+  const int64_t cls = (tok0 + (T - n)) * C;
+  const int c = blockIdx.y * AT + threadIdx.x;
+  if (blockIdx.x == 0 && c < C) out[cls + c] = in[cls + c];
+  ppeg_strip_body<0>(in + cls + C, n - 1, C, H, wrapN, wc, bc, out + cls + C, nsx);
 }
 // dwc / dbc partials, coalesced layout: part[blk][tap*C + c], part_b[blk][c]
 __global__ __launch_bounds__(AT) void ppeg_dw_strip_kernel(const float* __restrict__ dy, const float* __restrict__ x, int64_t N, int C,
@@ -803,6 +865,49 @@ __global__ void bn_coef_kernel(int bwd, const float* __restrict__ w, const float
   A[c] = wr;
   B[c] = -wr * rstd[c] * dw * inv;
   D[c] = wr * (mean[c] * rstd[c] * dw - db) * inv;
+}
+
+// ------------------------------------------------------------------------------------------------
+// bag-batched launches of the forward stencils and reductions (nys_args.hpp: NyBags; mhimx_infer_transmil_run).  One launch each,
+// whatever the number of bags; grid z (pinv: x / z) is the bag.
+// ------------------------------------------------------------------------------------------------
+int landmark_mean_many(hipStream_t st, const NyBags& tb, const float* x, int64_t ldx, int C, float* lm) {
+  MHIMX_CHECK_ARG(x && lm && C % 256 == 0 && ldx % 4 == 0 && aligned16(x) && aligned16(lm), "landmark_mean_many: C %% 256, 16-byte aligned rows");
+  hipLaunchKernelGGL(landmark_fwd_vec_many_kernel, dim3(256, (unsigned)(C / 256), (unsigned)tb.nbags), dim3(256), 0, st, tb, x, ldx, C, lm);
+  MHIMX_LAUNCH_CHECK();
+  return 0;
+}
+int pinv_init_many(hipStream_t st, int nbags, const float* a, float* z, float* stats, float* ws) {
+  constexpr int n = 256, heads = 8;
+  MHIMX_CHECK_ARG(a && z && stats && ws && nbags >= 1, "pinv_init_many: null args");
+  const int B = heads * nbags;
+  float* rowsum = ws;
+  float* colsum = ws + (int64_t)B * n;
+  hipLaunchKernelGGL(pinv_sums_kernel, dim3((unsigned)(2 * B * n)), dim3(AT), 0, st, a, B, n, rowsum, colsum);
+  MHIMX_LAUNCH_CHECK();
+  hipLaunchKernelGGL(pinv_argmax_many_kernel, dim3((unsigned)nbags), dim3(AT), 0, st, rowsum, colsum, heads * n, stats);
+  MHIMX_LAUNCH_CHECK();
+  hipLaunchKernelGGL(pinv_init_many_kernel, dim3(n / 32, n / 32, (unsigned)B), dim3(32, 8), 0, st, a, stats, n, z);
+  MHIMX_LAUNCH_CHECK();
+  return 0;
+}
+int resconv_many(hipStream_t st, const NyBags& tb, const float* v, int64_t ldv, const float* w, float* out, int64_t ldo) {
+  constexpr int C = 512, dh = 64;
+  MHIMX_CHECK_ARG(v && w && out && ldv % 4 == 0 && aligned16(v), "resconv_many: 16-byte aligned rows");
+  hipLaunchKernelGGL(resconv_tile_many_kernel<33>, dim3((unsigned)cdiv(tb.maxT, RT_ROWS), C / RT_CH, (unsigned)tb.nbags), dim3(256), 0, st, tb, v, ldv,
+                     w, dh, C, out, ldo);
+  MHIMX_LAUNCH_CHECK();
+  return 0;
+}
+int ppeg_fwd_many(hipStream_t st, const NyBags& tb, const float* y, const float* wc, const float* bc, float* x2) {
+  constexpr int C = 512;
+  MHIMX_CHECK_ARG(y && wc && bc && x2, "ppeg_fwd_many: null args");
+  int maxH = 7;
+  for (int b = 0; b < tb.nbags; ++b) maxH = tb.H[b] > maxH ? tb.H[b] : maxH;
+  hipLaunchKernelGGL(ppeg_strip_many_kernel, dim3((unsigned)(cdiv(maxH, PS) * cdiv(maxH, PSY)), (unsigned)cdiv(C, AT), (unsigned)tb.nbags), dim3(AT), 0,
+                     st, tb, y, C, wc, bc, x2);
+  MHIMX_LAUNCH_CHECK();
+  return 0;
 }
 
 }  // namespace mhimx

@@ -33,6 +33,7 @@
 namespace mhimx {
 
 constexpr int NY_THREADS = 512, NY_NW = 8, NY_LB = 2;
+constexpr int64_t NY_WS_FLOATS = (int64_t)NY_H * NY_MAXCH * (2 * NY_PART + 2 * NY_M) + NY_H * NY_M;   // mhimx_nys_ws_floats
 
 MHIMX_DEV float ny_kgsum(float v) { v += __shfl_xor(v, 16); v += __shfl_xor(v, 32); return v; }
 MHIMX_DEV float ny_kgmax(float v) { v = fmaxf(v, __shfl_xor(v, 16)); v = fmaxf(v, __shfl_xor(v, 32)); return v; }
@@ -162,7 +163,7 @@ MHIMX_DEV void ny_chunk(const NyArgs& g, int ch, int& t_begin, int& t_end) {
 // forward 1: a3v partials.  landmark-column: S[tb][lb] = RM(k) x LM(q~); online softmax per landmark (= per lane column);
 // o^T[db][lb] += TR(v) x P.      part[h][ch] = { o [256][64] | m [256] | l [256] }
 // ===========================================================================================================================
-__global__ __launch_bounds__(NY_THREADS) void ny_a3v_fwd_kernel(NyArgs g) {
+MHIMX_DEV void ny_a3v_fwd_body(const NyArgs g) {
   __shared__ __attribute__((aligned(16))) char sm[2 * NY_IMG];
   NY_IDS;
   NyLM qf;
@@ -244,11 +245,28 @@ __global__ __launch_bounds__(NY_THREADS) void ny_a3v_fwd_kernel(NyArgs g) {
     }
   }
 }
+__global__ __launch_bounds__(NY_THREADS) void ny_a3v_fwd_kernel(NyArgs g) { ny_a3v_fwd_body(g); }
+// bag-batched entry (NyBags, nys_args.hpp): blockIdx.z = bag.  The bag's chunk count is the single-bag launch's, min(T / 64, NY_MAXCH);
+// blocks beyond it return.  Its partials live in its own mhimx_nys_ws_floats slab.
+__global__ __launch_bounds__(NY_THREADS) void ny_a3v_fwd_many_kernel(NyArgs g, NyBags tb) {
+  int64_t tok0 = tb.tok0[0];
+  int T = tb.T[0];
+  NY_PICK(tok0, tb.tok0, blockIdx.z) NY_PICK(T, tb.T, blockIdx.z)
+  const int nch = T / NY_TT < NY_MAXCH ? T / NY_TT : NY_MAXCH;
+  if ((int)blockIdx.x >= nch) return;
+  g.T = T;
+  g.nch = nch;
+  g.k += tok0 * g.ld;
+  g.v += tok0 * g.ld;
+  g.ql += (int64_t)blockIdx.z * NY_M * g.ldl;
+  g.part += (int64_t)blockIdx.z * NY_WS_FLOATS;
+  ny_a3v_fwd_body(g);
+}
 
 // a3v[h][lm][d] = sum_ch o e^{(m_ch - M) scale} / L,  lse3[h][lm] = M sl2e + log2 L  (base-2 log-sum-exp of the scaled scores).
 // 64 outputs x 4 chunk quarters per workgroup: the maximum over ALL chunks first (LDS), then every quarter's weighted sums against
 // it, added in a fixed order.
-__global__ __launch_bounds__(256) void ny_a3v_merge_kernel(const float* part, int nch, float sl2e, float* a3v, float* lse3) {
+MHIMX_DEV void ny_a3v_merge_body(const float* part, int nch, float sl2e, float* a3v, float* lse3) {
   __shared__ f32x4 sacc[3][64];
   __shared__ float smax[4][64], sl[3][64];
   const int q = threadIdx.x >> 6, t = threadIdx.x & 63, idx = blockIdx.x * 64 + t;            // (h, lm, d4)
@@ -277,6 +295,17 @@ __global__ __launch_bounds__(256) void ny_a3v_merge_kernel(const float* part, in
     *reinterpret_cast<f32x4*>(a3v + ((int64_t)h * NY_M + lm) * NY_D + 4 * d4) = acc * inv;
     if (d4 == 0) lse3[h * NY_M + lm] = M * sl2e + log2f(L);
   }
+}
+__global__ __launch_bounds__(256) void ny_a3v_merge_kernel(const float* part, int nch, float sl2e, float* a3v, float* lse3) {
+  ny_a3v_merge_body(part, nch, sl2e, a3v, lse3);
+}
+// bag-batched entry: blockIdx.y = bag; the bag's own chunk count, partial slab and outputs
+__global__ __launch_bounds__(256) void ny_a3v_merge_many_kernel(NyBags tb, const float* part, float sl2e, float* a3v, float* lse3) {
+  int T = tb.T[0];
+  NY_PICK(T, tb.T, blockIdx.y)
+  const int nch = T / NY_TT < NY_MAXCH ? T / NY_TT : NY_MAXCH;
+  ny_a3v_merge_body(part + (int64_t)blockIdx.y * NY_WS_FLOATS, nch, sl2e, a3v + (int64_t)blockIdx.y * NY_H * NY_PART,
+                    lse3 + (int64_t)blockIdx.y * NY_H * NY_M);
 }
 
 // ===========================================================================================================================
@@ -484,8 +513,25 @@ __global__ __launch_bounds__(NY_THREADS) void ny_a3v_bwd_l_kernel(NyArgs g) {
 // memory (a lane's 8 consecutive head dims of its token: two 16-byte loads per k-step).  8 independent waves per workgroup.
 // ===========================================================================================================================
 constexpr int NY_SM_OUT8 = 2 * 65536;
-__global__ __launch_bounds__(NY_THREADS) void ny_out_fwd_tok8_kernel(NyArgs g) {
+// MANY: the bag-batched entry (NyBags, nys_args.hpp) - blockIdx.z = bag, min(T / 64, NY_TOKCH) chunks of its own tokens, blocks beyond return;
+// the argument block is relocated to the bag and the single-bag code runs as it is.  (One kernel template and not a __device__ body under
+// two entries: behind a function boundary the single-bag kernel came out with another schedule and register count.)
+template <bool MANY>
+__global__ __launch_bounds__(NY_THREADS) void ny_out_fwd_tok8_kernel(NyArgs g, NyBags tb) {
   extern __shared__ __attribute__((aligned(16))) char sm[];
+  if constexpr (MANY) {
+    int64_t tok0 = tb.tok0[0];
+    int T = tb.T[0];
+    NY_PICK(tok0, tb.tok0, blockIdx.z) NY_PICK(T, tb.T, blockIdx.z)
+    const int nch = T / NY_TT < NY_TOKCH ? T / NY_TT : NY_TOKCH;
+    if ((int)blockIdx.x >= nch) return;
+    g.T = T;
+    g.nch = nch;
+    g.q += tok0 * g.ld;
+    g.out += tok0 * g.ldo;
+    g.kl += (int64_t)blockIdx.z * NY_M * g.ldl;
+    g.w2 += (int64_t)blockIdx.z * NY_H * NY_PART;
+  }
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, c = lane & 15, kg = lane >> 4;
   const int h = blockIdx.y, ch = blockIdx.x;
   int t_begin, t_end;
@@ -659,13 +705,37 @@ static int ny_base(const mhimx_nys* a, NyArgs& g, const char* who) {
   return 0;
 }
 
+// ---- the bag-batched forward launches (mhimx_infer_transmil_run): one launch each whatever the number of bags
+int nys_a3v_fwd_many(hipStream_t st, const NyBags& tb, const NyArgs& base, float* a3v, float* lse3, float* ws) {
+  MHIMX_CHECK_ARG(base.k && base.v && base.ql && a3v && lse3 && ws && aligned16(base.k) && aligned16(base.v) && aligned16(base.ql) &&
+                      base.ld % 4 == 0 && base.ldl % 4 == 0,
+                  "nys_a3v_fwd_many: null / unaligned operands");
+  NyArgs g = base;
+  g.part = ws;
+  hipLaunchKernelGGL(ny_a3v_fwd_many_kernel, dim3(NY_MAXCH, NY_H, (unsigned)tb.nbags), dim3(NY_THREADS), 0, st, g, tb);
+  hipLaunchKernelGGL(ny_a3v_merge_many_kernel, dim3(NY_H * NY_M * 16 / 64, (unsigned)tb.nbags), dim3(256), 0, st, tb, ws, g.sl2e, a3v, lse3);
+  MHIMX_LAUNCH_CHECK();
+  return 0;
+}
+int nys_out_fwd_many(hipStream_t st, const NyBags& tb, const NyArgs& base, const float* w2, float* out, int64_t ldo, int accumulate) {
+  MHIMX_CHECK_ARG(base.q && base.kl && w2 && out && aligned16(base.q) && aligned16(base.kl) && aligned16(out) && ldo % 4 == 0 && base.ld % 4 == 0 &&
+                      base.ldl % 4 == 0,
+                  "nys_out_fwd_many: null / unaligned operands");
+  NyArgs g = base;
+  g.w2 = w2; g.out = out; g.ldo = ldo; g.lse1_o = nullptr; g.accumulate = accumulate;
+  MHIMX_ONCE_PER_DEVICE(MHIMX_HIP(hipFuncSetAttribute((const void*)ny_out_fwd_tok8_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, NY_SM_OUT8)));
+  hipLaunchKernelGGL(ny_out_fwd_tok8_kernel<true>, dim3(NY_TOKCH, NY_H, (unsigned)tb.nbags), dim3(NY_THREADS), NY_SM_OUT8, st, g, tb);
+  MHIMX_LAUNCH_CHECK();
+  return 0;
+}
+
 }  // namespace mhimx
 
 using namespace mhimx;
 
 extern "C" int64_t mhimx_nys_ws_floats(int64_t T) {
   (void)T;
-  return (int64_t)NY_H * NY_MAXCH * (2 * NY_PART + 2 * NY_M) + NY_H * NY_M;
+  return NY_WS_FLOATS;
 }
 
 extern "C" int mhimx_nys_a3v_fwd(void* stream, const mhimx_nys* a, float* a3v, float* lse3) {
@@ -684,10 +754,10 @@ extern "C" int mhimx_nys_out_fwd(void* stream, const mhimx_nys* a, const float* 
   if (int e = ny_base(a, g, "nys_out_fwd")) return e;
   MHIMX_CHECK_ARG(a->q && a->kl && w2 && out && aligned16(a->q) && aligned16(a->kl) && aligned16(out) && ldo % 4 == 0, "nys_out_fwd: null / unaligned operands");
   g.w2 = w2; g.out = out; g.ldo = ldo; g.lse1_o = lse1; g.accumulate = accumulate;
-  MHIMX_ONCE_PER_DEVICE(MHIMX_HIP(hipFuncSetAttribute((const void*)ny_out_fwd_tok8_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, NY_SM_OUT8)));
+  MHIMX_ONCE_PER_DEVICE(MHIMX_HIP(hipFuncSetAttribute((const void*)ny_out_fwd_tok8_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, NY_SM_OUT8)));
   const int64_t tiles = g.T / NY_TT;
   g.nch = (int)(tiles < NY_TOKCH ? tiles : NY_TOKCH);                    // 128 KB of LDS: one workgroup per CU
-  hipLaunchKernelGGL(ny_out_fwd_tok8_kernel, dim3(g.nch, NY_H), dim3(NY_THREADS), NY_SM_OUT8, (hipStream_t)stream, g);
+  hipLaunchKernelGGL(ny_out_fwd_tok8_kernel<false>, dim3(g.nch, NY_H), dim3(NY_THREADS), NY_SM_OUT8, (hipStream_t)stream, g, NyBags{});
   MHIMX_LAUNCH_CHECK();
   return 0;
 }

@@ -1005,6 +1005,15 @@ class MHIM(nn.Module):
             if (any(not t.is_contiguous() or t.dtype != torch.float32 or t.device != dev for t in ps)
                     or any(ps[j].data_ptr() % 16 for j in (0, 1, 2, 4, 6, 8, 9))):
                 return False
+        elif self.baseline == "selfattn":                       # mhimx_infer_transmil_run (csrc/infer_transmil.hip: check_transmil), mirrored
+            if not (self.mlp_dim == 512 and 1 <= self.n_classes <= 16 and self.input_dim % 256 == 0 and self.input_dim <= (1 << 20)):
+                return False
+            ps, layers = self._infer_transmil_params()
+            flat = list(ps) + [t for ly in layers for t in ly]
+            if any(not t.is_contiguous() or t.dtype != torch.float32 or t.device != dev for t in flat):
+                return False
+            if any(t.data_ptr() % 16 for t in (ps[0], ps[1], ps[2], ps[9], ps[10], ps[11])) or any(t.data_ptr() % 16 for ly in layers for t in ly[:5]):
+                return False
         else:
             if self.baseline != "attn" or self.online_encoder.gated:
                 return False
@@ -1039,10 +1048,29 @@ class MHIM(nn.Module):
         return ops.infer_dsmil_cfg(self.input_dim, self.mlp_dim, self.n_classes, L.act_code(self.act, _FEATURE_ACTS),
                                    self.online_encoder.cls_attn, no_norm, self._infer_dsmil_params())
 
+    def _infer_transmil_params(self):
+        """The tensors of mhimx_infer_transmil_cfg: (the thirteen outside the layers, in its order; the two layers' six)."""
+        f, enc, pr = self.feature[0], self.online_encoder, self.predictor
+        pe = enc.pos_embedding
+        ly = lambda t: (t.norm.weight.data, t.norm.bias.data, t.attn.to_qkv.weight.data, t.attn.to_out[0].weight.data, t.attn.to_out[0].bias.data,
+                        t.attn.res_conv.weight.data)
+        return ((f.weight.data, f.bias.data, enc.cls_token.data, pe.proj.weight.data, pe.proj1.weight.data, pe.proj2.weight.data,
+                 pe.proj.bias.data, pe.proj1.bias.data, pe.proj2.bias.data, enc.norm.weight.data, enc.norm.bias.data, pr.weight.data,
+                 pr.bias.data), (ly(enc.layer1), ly(enc.layer2)))
+
+    def _infer_transmil_cfg(self):
+        ps, layers = self._infer_transmil_params()
+        return ops.infer_transmil_cfg(self.input_dim, self.n_classes, L.act_code(self.act, _FEATURE_ACTS), ps, layers)
+
     def infer_rows_per_call(self):
         """Row cap of one native call.  ABMIL: ``infer_row_cap`` (its workspace: 2060 bytes per row).  DSMIL keeps h, V, Q and the classes
         of every row (4673 + 8 C bytes per row with the per-chunk partials) and two more weight images: its cap is the row count whose
         workspace is no larger than the ABMIL call's at ``infer_row_cap`` - a little under half of it."""
+        if getattr(self, "baseline", "attn") == "selfattn":
+            # TransMIL keeps 26 KiB per PADDED token (x, qkv, block output and y of both layers, the LayerNorm rows): the token count
+            # whose share of the workspace is no larger than the ABMIL call's at ``infer_row_cap``.  (The per-bag share - landmark
+            # matrices and a3v partials, about 56 MiB per bag - comes on top whatever the rows are.)
+            return max(1, self.infer_row_cap * 2060 // (26 * 1024))
         if getattr(self, "baseline", "attn") != "dsmil":
             return self.infer_row_cap
         return max(1, (self.infer_row_cap * 2060 - (4 << 20)) // (4673 + 8 * self.n_classes))   # (4 MiB: images, 32 bags' last chunks)
@@ -1070,7 +1098,9 @@ class MHIM(nn.Module):
         An eval-mode plain-ABMIL model without merge_test takes mhimx_infer_run_x - one C call (four launches) per chunk of bags, see
         ``infer_chunks``; an eval-mode DSMIL model without merge_test takes mhimx_infer_dsmil_run (seven launches per chunk) and returns
         the MIXED logits 0.5 * bag + 0.5 * max-instance of validate_func, with ``self.last["infer_parts"] = (logits_bag, logits_ins, B)``
-        and the DSMIL instance score as the attention; anything else loops over forward_test (DSMIL: the same mix).
+        and the DSMIL instance score as the attention; an eval-mode TransMIL model without merge_test takes mhimx_infer_transmil_run
+        (96 launches per chunk) unless ``return_attn`` asks for the attention maps; anything else loops over forward_test (DSMIL: the
+        same mix).
         ``self.last["infer_native"]`` says which route ran.
         A list of fp16 bags, or of bf16 bags, that the native route takes goes in as it is (no widened copy; same bits as on the widened
         bags); a list of mixed dtypes, and every model outside the native route, gets ``x.float()`` first."""
@@ -1132,7 +1162,15 @@ class MHIM(nn.Module):
                 logits = 0.5 * lb + 0.5 * li
                 loss = None if labels is None else torch.nn.functional.cross_entropy(logits, labels, reduction="none")
                 self.last = {"infer_native": False, "infer_calls": 0, "infer_parts": (lb, li, torch.cat(Bs) if Bs else None)}
-        elif native:
+        elif native and self.baseline == "selfattn" and not return_attn:
+            cfg = self._infer_transmil_cfg()
+            chunks = self.infer_chunks(xs)
+            rs = [ops.infer_transmil_many(cfg, xs[lo:hi], labels=None if labels is None else labels[lo:hi].contiguous()) for lo, hi in chunks]
+            self._step += 3 * n                   # (what the forward_test loop consumes per bag: the feature seed, two to_out seeds of _encode)
+            logits = rs[0].logits if len(rs) == 1 else torch.cat([r.logits for r in rs])
+            loss = None if labels is None else (rs[0].loss if len(rs) == 1 else torch.cat([r.loss for r in rs]))
+            self.last = {"infer_native": True, "infer_calls": len(chunks)}
+        elif native and self.baseline != "selfattn":
             cfg = self._infer_cfg()
             chunks = self.infer_chunks(xs)
             lg, ls = [], []

@@ -8,6 +8,7 @@ from __future__ import annotations
 
 import collections
 import ctypes as C
+import math
 from typing import Optional
 
 import torch
@@ -1199,6 +1200,59 @@ def infer_dsmil_many(cfg, xs, labels=None, want_attn=False, want_B=False, want_c
                           attn=_p(r.attn), loss=_p(r.loss))
     L.check(L.lib().mhimx_infer_dsmil_run(_stream(), C.byref(cfg), n, bags, _p(labels), C.byref(out), _p(ws), ws.numel(), xdt),
             "mhimx_infer_dsmil_run")
+    return r
+
+
+class InferTransmilResult:
+    """Outputs of one mhimx_infer_transmil_run: logits [n, C], loss [n] or None, z [n, 512] (the cls rows after the final norm) or None;
+    ``ws`` (the uint8 workspace) and ``layout`` (L.InferTransmilLayout: byte offsets of every intermediate inside it)."""
+    __slots__ = ("logits", "loss", "z", "ws", "layout")
+
+    def view(self, name, shape, layer=None):
+        """The intermediate ``name`` of the layout (of ``layer`` 0 / 1 where it is per layer) as an fp32 view of the workspace of the
+        given shape (mhimx.h: mhimx_infer_transmil_layout)."""
+        off = getattr(self.layout, name)
+        off = int(off if layer is None else off[layer])
+        return ws_view(self.ws, off, math.prod(shape)).view(*shape)
+
+
+_TRANSMIL_PARAMS = ("w1", "b1", "cls_token", "w7", "w5", "w3", "b7", "b5", "b3", "norm_w", "norm_b", "wp", "bp")
+_TRANSMIL_LAYER = ("ln_w", "ln_b", "w_qkv", "w_out", "b_out", "conv_w")
+
+
+def infer_transmil_cfg(D, Cc, act, params, layers):
+    """mhimx_infer_transmil_cfg; ``params``: the thirteen tensors feature.0.{weight, bias}, cls_token, pos_embedding.proj / proj1 /
+    proj2 weights then biases, norm.{weight, bias}, predictor.{weight, bias}; ``layers``: two tuples (norm.weight, norm.bias,
+    attn.to_qkv.weight, attn.to_out.0.weight, attn.to_out.0.bias, attn.res_conv.weight) - all kept alive by the caller."""
+    if len(params) != len(_TRANSMIL_PARAMS) or len(layers) != 2 or any(len(t) != len(_TRANSMIL_LAYER) for t in layers):
+        raise L.MhimxError("infer_transmil_cfg: 13 parameter tensors and two layers of 6")
+    for n, t in list(zip(_TRANSMIL_PARAMS, params)) + [(n, t) for ly in layers for n, t in zip(_TRANSMIL_LAYER, ly)]:
+        _chk(t, name=n)
+    cfg = L.InferTransmilCfg(D=int(D), C=int(Cc), act=int(act), **{n: t.data_ptr() for n, t in zip(_TRANSMIL_PARAMS, params)})
+    for j, ly in enumerate(layers):
+        cfg.layer[j] = L.TransmilLayer(**{n: t.data_ptr() for n, t in zip(_TRANSMIL_LAYER, ly)})
+    return cfg
+
+
+def infer_transmil_ws_bytes(cfg, xs):
+    """mhimx_infer_transmil_ws_bytes for the bags ``xs`` ([N, D] each): host arithmetic only."""
+    bags = (L.InferBag * max(len(xs), 1))(*[L.InferBag(X=x.data_ptr(), ldx=x.stride(0), N=x.shape[0]) for x in xs])
+    return L.lib().mhimx_infer_transmil_ws_bytes(C.byref(cfg), len(xs), bags)
+
+
+def infer_transmil_many(cfg, xs, labels=None, want_z=False, ws=None):
+    """The eval-mode MHIM(TransMIL) forward of up to L.INFER_MAX bags of different row counts in ONE C call (mhimx_infer_transmil_run).
+    cfg: L.InferTransmilCfg (its parameter tensors are kept alive by the caller); xs, labels, ws: as ``infer_many`` takes them (half bags
+    are read where they lie; the workspace cache is shared with it)."""
+    n, xdt, bags, ws, dev, _ = _infer_front("infer_transmil_many", "mhimx_infer_transmil_ws_bytes", cfg, xs, labels, ws)
+    r = InferTransmilResult()
+    r.logits = torch.empty((n, int(cfg.C)), device=dev)
+    r.loss = torch.empty(n, device=dev) if labels is not None else None
+    r.z = torch.empty((n, 512), device=dev) if want_z else None
+    r.ws, r.layout = ws, L.InferTransmilLayout()
+    L.check(L.lib().mhimx_infer_transmil_layout_of(C.byref(cfg), n, bags, C.byref(r.layout)), "mhimx_infer_transmil_layout_of")
+    L.check(L.lib().mhimx_infer_transmil_run(_stream(), C.byref(cfg), n, bags, _p(labels), _p(r.logits), _p(r.loss), _p(r.z), _p(ws), ws.numel(),
+                                             xdt), "mhimx_infer_transmil_run")
     return r
 
 
