@@ -254,26 +254,16 @@ struct InferWs { int64_t w1p, wa_frag, H, s, pm, pl, pz, total; };
 
 // xdt: the element type of the bags' rows (MHIMX_X_*); the 2-byte types have their own pitch rule (16-byte rows: 8 elements)
 int check_infer(const mhimx_infer_cfg* c, int32_t n_bags, const mhimx_infer_bag* bags, int32_t xdt = MHIMX_X_F32) {
-  if (int r = rg_check_xdt("infer", xdt)) return r;
-  MHIMX_CHECK_ARG(c && bags, "infer: null configuration / bag list");
-  MHIMX_CHECK_ARG(n_bags >= 1 && n_bags <= MHIMX_INFER_MAX, "infer: 1..%d bags per call", MHIMX_INFER_MAX);
+  if (int r = rg_check_infer_front("infer", xdt, c, n_bags, bags, false)) return r;
   MHIMX_CHECK_ARG(c->E == IE && c->A == IA && c->C >= 1 && c->C <= FIN_MAXC && c->D > 0 && c->D % 256 == 0 && c->D <= (1 << 20),
                   "infer: shapes outside the ragged ABMIL forward (E = 512, A = 128, 1 <= C <= %d, D %% 256 == 0)", FIN_MAXC);
   MHIMX_CHECK_ARG(c->act >= MHIMX_ACT_NONE && c->act <= MHIMX_ACT_TANH && c->da_act >= MHIMX_ACT_NONE && c->da_act <= MHIMX_ACT_TANH,
                   "infer: unknown activation");
-  int64_t rows = 0;
-  for (int b = 0; b < n_bags; ++b) {
-    if (int r = rg_check_bag("infer", b, bags[b].N, bags[b].ldx, c->D, xdt, RgRules{MHIMX_INFER_MAX_ROWS, false})) return r;
-    rows += bags[b].N;
-  }
-  MHIMX_CHECK_ARG(rows <= MHIMX_INFER_MAX_ROWS, "infer: more than %d rows in one call", MHIMX_INFER_MAX_ROWS);
-  return 0;
+  return rg_check_infer_bags("infer", c->D, n_bags, bags, xdt);
 }
 
 void infer_layout(const mhimx_infer_cfg* c, int32_t n_bags, const mhimx_infer_bag* bags, InferWs* w, InferTab* tab) {
-  RgCount n;
-  for (int b = 0; b < n_bags; ++b) rg_tab_add(tab, n, b, bags[b].X, bags[b].ldx, bags[b].N, bags[b].N);
-  rg_tab_close(tab, n, n_bags);
+  const RgCount n = rg_tab_fill(tab, n_bags, bags);
   const int64_t rows = n.rows, parts = n.parts;
   Arena ar(nullptr, 0);
   w->w1p = ar.off; ar.take<float>(c->E * c->D);
@@ -330,9 +320,9 @@ extern "C" int mhimx_infer_run_x(void* stream, const mhimx_infer_cfg* cfg, int32
   const mhimx_step_params& P = cfg->p;
   MHIMX_CHECK_ARG(P.w1 && P.b1 && P.wa && P.wc && P.wp && P.bp, "infer: null parameter");
   MHIMX_CHECK_ARG(aligned16(P.w1) && aligned16(P.b1) && aligned16(P.wa), "infer: feature / scorer weights must be 16-byte aligned");
-  for (int b = 0; b < n_bags; ++b) MHIMX_CHECK_ARG(bags[b].X && aligned16(bags[b].X), "infer: bag %d: null or unaligned rows", b);
-  MHIMX_CHECK_ARG(out && out->logits && out->stats, "infer: logits and stats outputs are required");
-  MHIMX_CHECK_ARG(!out->loss || labels_dev, "infer: the loss output needs labels");
+  if (int r = rg_check_infer_io("infer", n_bags, bags, out && out->logits && out->stats, "logits and stats outputs are required",
+                                out ? out->loss : nullptr, labels_dev))
+    return r;
   InferWs w;
   InferTab tab = {};
   infer_layout(cfg, n_bags, bags, &w, &tab);

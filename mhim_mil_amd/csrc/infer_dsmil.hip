@@ -26,6 +26,8 @@
 #include <limits.h>
 #include <math.h>
 
+#include <type_traits>
+
 #include "infer_tab.hpp"
 
 namespace mhimx {
@@ -375,25 +377,15 @@ struct DsmilWs { int64_t w1p, vp, q0f, q2f, H, V, Q, cls, pmax, parg, qmax, pm, 
 
 // the checks of mhimx_infer_run_x on the bag table and the element type (infer.hip: check_infer), and this call's own shape rules
 int check_dsmil(const mhimx_infer_dsmil_cfg* c, int32_t n_bags, const mhimx_infer_bag* bags, int32_t xdt) {
-  if (int r = rg_check_xdt("infer_dsmil", xdt)) return r;
-  MHIMX_CHECK_ARG(c && bags, "infer_dsmil: null configuration / bag list");
-  MHIMX_CHECK_ARG(n_bags >= 1 && n_bags <= MHIMX_INFER_MAX, "infer_dsmil: 1..%d bags per call (got %d)", MHIMX_INFER_MAX, n_bags);
+  if (int r = rg_check_infer_front("infer_dsmil", xdt, c, n_bags, bags, true)) return r;
   MHIMX_CHECK_ARG(c->E == IE && c->C >= 1 && c->C <= DS_MAXC && c->D > 0 && c->D % 256 == 0 && c->D <= (1 << 20),
                   "infer_dsmil: shapes outside the ragged DSMIL forward (E = 512, q width 128, 1 <= C <= %d, D %% 256 == 0)", DS_MAXC);
   MHIMX_CHECK_ARG(c->act >= MHIMX_ACT_NONE && c->act <= MHIMX_ACT_TANH, "infer_dsmil: unknown activation");
-  int64_t rows = 0;
-  for (int b = 0; b < n_bags; ++b) {
-    if (int r = rg_check_bag("infer_dsmil", b, bags[b].N, bags[b].ldx, c->D, xdt, RgRules{MHIMX_INFER_MAX_ROWS, false})) return r;
-    rows += bags[b].N;
-  }
-  MHIMX_CHECK_ARG(rows <= MHIMX_INFER_MAX_ROWS, "infer_dsmil: more than %d rows in one call", MHIMX_INFER_MAX_ROWS);
-  return 0;
+  return rg_check_infer_bags("infer_dsmil", c->D, n_bags, bags, xdt);
 }
 
 void dsmil_layout(const mhimx_infer_dsmil_cfg* c, int32_t n_bags, const mhimx_infer_bag* bags, DsmilWs* w, InferTab* tab) {
-  RgCount n;
-  for (int b = 0; b < n_bags; ++b) rg_tab_add(tab, n, b, bags[b].X, bags[b].ldx, bags[b].N, bags[b].N);
-  rg_tab_close(tab, n, n_bags);
+  const RgCount n = rg_tab_fill(tab, n_bags, bags);
   const int64_t rows = n.rows, parts = n.parts;
   Arena ar(nullptr, 0);
   w->w1p = ar.off; ar.take<float>(c->E * c->D);
@@ -413,17 +405,13 @@ void dsmil_layout(const mhimx_infer_dsmil_cfg* c, int32_t n_bags, const mhimx_in
   w->total = ar.off;
 }
 
-template <int CT>
-int dsmil_tail(hipStream_t st, const InferTab& tab, const mhimx_infer_dsmil_cfg* cfg, const float* Q, const float* V, const float* qmax, float* pm,
-               float* pl, float* pB, const int64_t* labels, const float* logits_ins, const mhimx_infer_dsmil_out* out, bool attn_blocks) {
-  const int C = (int)cfg->C;
-  hipLaunchKernelGGL(dsmil_pool_kernel<CT>, dim3((unsigned)tab.parts), dim3(DP_THREADS), 0, st, tab, Q, V, qmax, C, pm, pl, pB);
-  MHIMX_LAUNCH_CHECK();
-  hipLaunchKernelGGL(dsmil_finalize_kernel<CT>, dim3((unsigned)tab.n, attn_blocks ? 1 + DF_ATTN_BLOCKS : 1), dim3(RG_FIN_T), 0, st, tab, pm, pl, pB, Q,
-                     qmax, cfg->wfcc, cfg->bfcc, C, (int)(cfg->no_norm != 0), labels, logits_ins, out->logits_bag, out->logits, out->B,
-                     attn_blocks ? out->attn : nullptr, out->loss);
-  MHIMX_LAUNCH_CHECK();
-  return 0;
+// f(std::integral_constant<int, CT>) for the instance CT of the pool and finalize kernels that holds C classes
+template <class F>
+void ds_for_ct(int C, F&& f) {
+  if (C <= 2) f(std::integral_constant<int, 2>{});
+  else if (C <= 4) f(std::integral_constant<int, 4>{});
+  else if (C <= 8) f(std::integral_constant<int, 8>{});
+  else f(std::integral_constant<int, 16>{});
 }
 
 }  // namespace
@@ -439,26 +427,22 @@ int dsmil_rows_crit_pool(hipStream_t st, const InferTab& tab, const float* H, co
   MHIMX_LAUNCH_CHECK();
   hipLaunchKernelGGL(dsmil_crit_kernel, dim3((unsigned)tab.n), dim3(256), 0, st, tab, pmax, parg, Q, C, qmax, logits_ins, crit);
   MHIMX_LAUNCH_CHECK();
-  const dim3 grid((unsigned)tab.parts), block(DP_THREADS);
-  if (C <= 2) hipLaunchKernelGGL(dsmil_pool_kernel<2>, grid, block, 0, st, tab, Q, V, qmax, C, pm, pl, pB);
-  else if (C <= 4) hipLaunchKernelGGL(dsmil_pool_kernel<4>, grid, block, 0, st, tab, Q, V, qmax, C, pm, pl, pB);
-  else if (C <= 8) hipLaunchKernelGGL(dsmil_pool_kernel<8>, grid, block, 0, st, tab, Q, V, qmax, C, pm, pl, pB);
-  else hipLaunchKernelGGL(dsmil_pool_kernel<16>, grid, block, 0, st, tab, Q, V, qmax, C, pm, pl, pB);
+  ds_for_ct(C, [&](auto ct) {
+    hipLaunchKernelGGL(dsmil_pool_kernel<decltype(ct)::value>, dim3((unsigned)tab.parts), dim3(DP_THREADS), 0, st, tab, Q, V, qmax, C, pm, pl, pB);
+  });
   MHIMX_LAUNCH_CHECK();
   return 0;
 }
 
-// launch 7 for mhimx_dsmil_mhim_window_run's teacher (dsmil_mhim.hip): no labels, no loss; attn: the max_c A blocks
+// launch 7; attn: the max_c A (no_norm: max_c a) blocks.  mhimx_dsmil_mhim_window_run's teacher (dsmil_mhim.hip): no labels, no loss
 int dsmil_finalize(hipStream_t st, const InferTab& tab, const float* pm, const float* pl, const float* pB, const float* Q, const float* qmax,
-                   const float* wfcc, const float* bfcc, int C, const float* logits_ins, float* logits_bag, float* logits, float* B, float* attn) {
+                   const float* wfcc, const float* bfcc, int C, const float* logits_ins, float* logits_bag, float* logits, float* B, float* attn,
+                   int no_norm, const int64_t* labels, float* loss) {
   MHIMX_CHECK_ARG(C >= 1 && C <= DS_MAXC, "dsmil_finalize: 1 <= C <= %d", DS_MAXC);
-  const dim3 grid((unsigned)tab.n, attn ? 1 + DF_ATTN_BLOCKS : 1), block(RG_FIN_T);
-  const int64_t* no_labels = nullptr;
-  float* no_loss = nullptr;
-  if (C <= 2) hipLaunchKernelGGL(dsmil_finalize_kernel<2>, grid, block, 0, st, tab, pm, pl, pB, Q, qmax, wfcc, bfcc, C, 0, no_labels, logits_ins, logits_bag, logits, B, attn, no_loss);
-  else if (C <= 4) hipLaunchKernelGGL(dsmil_finalize_kernel<4>, grid, block, 0, st, tab, pm, pl, pB, Q, qmax, wfcc, bfcc, C, 0, no_labels, logits_ins, logits_bag, logits, B, attn, no_loss);
-  else if (C <= 8) hipLaunchKernelGGL(dsmil_finalize_kernel<8>, grid, block, 0, st, tab, pm, pl, pB, Q, qmax, wfcc, bfcc, C, 0, no_labels, logits_ins, logits_bag, logits, B, attn, no_loss);
-  else hipLaunchKernelGGL(dsmil_finalize_kernel<16>, grid, block, 0, st, tab, pm, pl, pB, Q, qmax, wfcc, bfcc, C, 0, no_labels, logits_ins, logits_bag, logits, B, attn, no_loss);
+  ds_for_ct(C, [&](auto ct) {
+    hipLaunchKernelGGL(dsmil_finalize_kernel<decltype(ct)::value>, dim3((unsigned)tab.n, attn ? 1 + DF_ATTN_BLOCKS : 1), dim3(RG_FIN_T), 0, st, tab,
+                       pm, pl, pB, Q, qmax, wfcc, bfcc, C, no_norm, labels, logits_ins, logits_bag, logits, B, attn, loss);
+  });
   MHIMX_LAUNCH_CHECK();
   return 0;
 }
@@ -484,9 +468,9 @@ extern "C" int mhimx_infer_dsmil_run(void* stream, const mhimx_infer_dsmil_cfg* 
   MHIMX_CHECK_ARG(aligned16(cfg->w1) && aligned16(cfg->b1) && aligned16(cfg->wi) && aligned16(cfg->wq0) && aligned16(cfg->wq2) &&
                       aligned16(cfg->wv) && aligned16(cfg->bv),
                   "infer_dsmil: the feature, i_classifier, q and v weights must be 16-byte aligned");
-  for (int b = 0; b < n_bags; ++b) MHIMX_CHECK_ARG(bags[b].X && aligned16(bags[b].X), "infer_dsmil: bag %d: null or unaligned rows", b);
-  MHIMX_CHECK_ARG(out && out->logits_bag && out->logits_ins && out->logits, "infer_dsmil: the three logits outputs are required");
-  MHIMX_CHECK_ARG(!out->loss || labels_dev, "infer_dsmil: the loss output needs labels");
+  if (int r = rg_check_infer_io("infer_dsmil", n_bags, bags, out && out->logits_bag && out->logits_ins && out->logits,
+                                "the three logits outputs are required", out ? out->loss : nullptr, labels_dev))
+    return r;
   DsmilWs w;
   InferTab tab = {};
   dsmil_layout(cfg, n_bags, bags, &w, &tab);
@@ -511,18 +495,12 @@ extern "C" int mhimx_infer_dsmil_run(void* stream, const mhimx_infer_dsmil_cfg* 
   for (int b = 0; b < n_bags; ++b) { tabv.X[b] = H + tab.row0[b] * IE; tabv.ldx[b] = IE; }
   tabv.pad = MHIMX_X_F32;
   if (int r = infer_project(st, tabv, IE, vp, cfg->bv, MHIMX_ACT_RELU, V)) return r;
-  // 4. Q, classes, arg-max partials (the instance score too when it is max_c classes)
-  MHIMX_ONCE_PER_DEVICE(MHIMX_HIP(hipFuncSetAttribute((const void*)dsmil_rows_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)DR_SMEM)));
-  hipLaunchKernelGGL(dsmil_rows_kernel, dim3((unsigned)tab.parts), dim3(RG_T), DR_SMEM, st, tab, H, q0f, cfg->bq0, q2f, cfg->bq2, cfg->wi,
-                     cfg->bi, C, Q, cls, cfg->cls_attn ? out->attn : nullptr, pmax, parg);
-  MHIMX_LAUNCH_CHECK();
-  // 5. critical rows, max-instance logits, q_max
-  hipLaunchKernelGGL(dsmil_crit_kernel, dim3((unsigned)n_bags), dim3(256), 0, st, tab, pmax, parg, Q, C, qmax, out->logits_ins, out->crit);
-  MHIMX_LAUNCH_CHECK();
-  // 6. + 7. pool partials; merge, fcc, mix, loss, attention
-  const bool attn_blocks = out->attn && !cfg->cls_attn;
-  if (C <= 2) return dsmil_tail<2>(st, tab, cfg, Q, V, qmax, pm, pl, pB, labels_dev, out->logits_ins, out, attn_blocks);
-  if (C <= 4) return dsmil_tail<4>(st, tab, cfg, Q, V, qmax, pm, pl, pB, labels_dev, out->logits_ins, out, attn_blocks);
-  if (C <= 8) return dsmil_tail<8>(st, tab, cfg, Q, V, qmax, pm, pl, pB, labels_dev, out->logits_ins, out, attn_blocks);
-  return dsmil_tail<16>(st, tab, cfg, Q, V, qmax, pm, pl, pB, labels_dev, out->logits_ins, out, attn_blocks);
+  // 4. Q, classes, arg-max partials (the instance score too when it is max_c classes); 5. critical rows, max-instance logits, q_max;
+  // 6. pool partials
+  if (int r = dsmil_rows_crit_pool(st, tab, H, V, q0f, cfg->bq0, q2f, cfg->bq2, cfg->wi, cfg->bi, C, Q, cls, pmax, parg, qmax, out->logits_ins,
+                                   out->crit, pm, pl, pB, cfg->cls_attn ? out->attn : nullptr))
+    return r;
+  // 7. merge, fcc, mix, loss, attention (its blocks run only where the attention is not the instance score of launch 4)
+  return dsmil_finalize(st, tab, pm, pl, pB, Q, qmax, cfg->wfcc, cfg->bfcc, C, out->logits_ins, out->logits_bag, out->logits, out->B,
+                        cfg->cls_attn ? nullptr : out->attn, (int)(cfg->no_norm != 0), labels_dev, out->loss);
 }

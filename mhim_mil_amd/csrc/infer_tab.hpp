@@ -2,7 +2,9 @@
 // mhimx_pure_window_run: pure_window.hip, mhimx_ragged_window_run: ragged_window.hip, their projection kernels: bag_project.hip): the
 // per-bag table, ONE copy of the device pieces their kernels have in common (the bag lookup RG_PICK / RG_BAG / RG_FIND_BAG, the bf16 split
 // rg_split, the 3-term bf16 k-loop rg_mma3, the {max, sum} merge of a bag's pool partials in index order rg_merge_stats) and ONE copy of
-// the host checks and table fill (rg_check_*, rg_tab_*).  A piece is shared only where every kernel that uses it keeps its code,
+// the host checks and table fill (rg_check_*, rg_tab_*; for the three inference calls - mhimx_infer_transmil_run: infer_transmil.hip is the
+// third - their whole common front rg_check_infer_front / rg_check_infer_bags / rg_check_infer_io and their table rg_tab_fill; the DSMIL
+// launches 4 - 7 as host calls dsmil_rows_crit_pool / dsmil_finalize).  A piece is shared only where every kernel that uses it keeps its code,
 // instruction for instruction (tools/kernel_meta.py --diff against the build before; profiles/ragged_shared.md names what stayed a copy).
 #pragma once
 #include <math.h>
@@ -182,6 +184,40 @@ inline void rg_tab_add(InferTab* tab, RgCount& n, int b, const float* X, int64_t
 inline void rg_tab_close(InferTab* tab, const RgCount& n, int n_bags) {
   if (tab) { tab->n = n_bags; tab->tiles = (int32_t)n.tiles; tab->parts = (int32_t)n.parts; }
 }
+// the table of an inference call: every bag takes its own N rows of the row space
+inline RgCount rg_tab_fill(InferTab* tab, int32_t n_bags, const mhimx_infer_bag* bags) {
+  RgCount n;
+  for (int b = 0; b < n_bags; ++b) rg_tab_add(tab, n, b, bags[b].X, bags[b].ldx, bags[b].N, bags[b].N);
+  rg_tab_close(tab, n, n_bags);
+  return n;
+}
+// The checks the three inference calls (`who`: infer, infer_dsmil, infer_transmil) make alike, in the order they refuse: the element type,
+// null arguments, the bag count (`got`: the message names n_bags) - rg_check_infer_front; the call's own shape and activation lines; every
+// bag's N and pitch, the rows of the call - rg_check_infer_bags.  And what only the *_run entry points ask, behind their parameter
+// checks: every bag's address, the outputs the call cannot do without (`outputs`, else "<who>: <outputs_text>"), labels for the loss.
+inline int rg_check_infer_front(const char* who, int32_t xdt, const void* cfg, int32_t n_bags, const mhimx_infer_bag* bags, bool got) {
+  if (int r = rg_check_xdt(who, xdt)) return r;
+  MHIMX_CHECK_ARG(cfg && bags, "%s: null configuration / bag list", who);
+  if (got) MHIMX_CHECK_ARG(n_bags >= 1 && n_bags <= MHIMX_INFER_MAX, "%s: 1..%d bags per call (got %d)", who, MHIMX_INFER_MAX, n_bags);
+  MHIMX_CHECK_ARG(n_bags >= 1 && n_bags <= MHIMX_INFER_MAX, "%s: 1..%d bags per call", who, MHIMX_INFER_MAX);
+  return 0;
+}
+inline int rg_check_infer_bags(const char* who, int64_t D, int32_t n_bags, const mhimx_infer_bag* bags, int32_t xdt) {
+  int64_t rows = 0;
+  for (int b = 0; b < n_bags; ++b) {
+    if (int r = rg_check_bag(who, b, bags[b].N, bags[b].ldx, D, xdt, RgRules{MHIMX_INFER_MAX_ROWS, false})) return r;
+    rows += bags[b].N;
+  }
+  MHIMX_CHECK_ARG(rows <= MHIMX_INFER_MAX_ROWS, "%s: more than %d rows in one call", who, MHIMX_INFER_MAX_ROWS);
+  return 0;
+}
+inline int rg_check_infer_io(const char* who, int32_t n_bags, const mhimx_infer_bag* bags, bool outputs, const char* outputs_text, const void* loss,
+                             const void* labels) {
+  for (int b = 0; b < n_bags; ++b) MHIMX_CHECK_ARG(bags[b].X && aligned16(bags[b].X), "%s: bag %d: null or unaligned rows", who, b);
+  MHIMX_CHECK_ARG(outputs, "%s: %s", who, outputs_text);
+  MHIMX_CHECK_ARG(!loss || labels, "%s: the loss output needs labels", who);
+  return 0;
+}
 
 // what the TRAIN-mode ragged projection (mhimx_pure_window_run) needs beyond the table: every bag's dropout seed, the device tick the
 // seeds are mixed with, the dropout probability and the fp16 d out / d pre rows (row space of the call, like the feature rows)
@@ -216,10 +252,11 @@ int pw_wgrad_rows(hipStream_t st, const InferTab& tab, const float* A, int lda, 
 int dsmil_rows_crit_pool(hipStream_t st, const InferTab& tab, const float* H, const float* V, const float* q0f, const float* bq0, const float* q2f,
                          const float* bq2, const float* wi, const float* bi, int C, float* Q, float* cls, float* pmax, int32_t* parg, float* qmax,
                          float* logits_ins, int64_t* crit, float* pm, float* pl, float* pB, float* score = nullptr);
-// infer_dsmil.hip's launch 7 over a table as a host call (mhimx_dsmil_mhim_window_run's teacher): plane = bag, the partials merged in index
-// order -> B [n, C, 512], logits_bag, logits [n, C]; attn (optional, rows of the row space): max_c A of every row
+// infer_dsmil.hip's launch 7 over a table as a host call: plane = bag, the partials merged in index order -> B [n, C, 512], logits_bag,
+// logits [n, C]; attn (optional, rows of the row space): max_c A of every row (no_norm: max_c a); loss (optional, needs labels) [n]
 int dsmil_finalize(hipStream_t st, const InferTab& tab, const float* pm, const float* pl, const float* pB, const float* Q, const float* qmax,
-                   const float* wfcc, const float* bfcc, int C, const float* logits_ins, float* logits_bag, float* logits, float* B, float* attn);
+                   const float* wfcc, const float* bfcc, int C, const float* logits_ins, float* logits_bag, float* logits, float* B, float* attn,
+                   int no_norm = 0, const int64_t* labels = nullptr, float* loss = nullptr);
 // (the DSMIL student of the two DSMIL train calls - head kernel, layout share, forward, backward, reductions, checks: dsmil_student.hpp)
 // ragged_window.hip's launch C.5 as a host call: q <- mm^n q + (1 - mm) sum_b mm^(n-1-b) z_b, z_b = the k rows of Hs from row tok[b] on
 int rw_q_chain(hipStream_t st, float* q, const float* Hs, int n_bags, const int64_t* tok, double mm, int n_floats);

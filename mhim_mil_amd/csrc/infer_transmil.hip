@@ -166,20 +166,12 @@ __global__ __launch_bounds__(64) void tm_tail_kernel(NyBags tb, const float* __r
 // ------------------------------------------------------------------------------------------------ host
 // the checks of mhimx_infer_run_x on the bag table and the element type, and this call's own shape rules
 int check_transmil(const mhimx_infer_transmil_cfg* c, int32_t n_bags, const mhimx_infer_bag* bags, int32_t xdt) {
-  if (int r = rg_check_xdt("infer_transmil", xdt)) return r;
-  MHIMX_CHECK_ARG(c && bags, "infer_transmil: null configuration / bag list");
-  MHIMX_CHECK_ARG(n_bags >= 1 && n_bags <= MHIMX_INFER_MAX, "infer_transmil: 1..%d bags per call (got %d)", MHIMX_INFER_MAX, n_bags);
+  if (int r = rg_check_infer_front("infer_transmil", xdt, c, n_bags, bags, true)) return r;
   MHIMX_CHECK_ARG(c->C >= 1 && c->C <= TM_MAXC && c->D > 0 && c->D % 256 == 0 && c->D <= (1 << 20),
                   "infer_transmil: shapes outside the ragged TransMIL forward (E = 512, 8 x 64 heads, 256 landmarks, 1 <= C <= %d, D %% 256 == 0)",
                   TM_MAXC);
   MHIMX_CHECK_ARG(c->act >= MHIMX_ACT_NONE && c->act <= MHIMX_ACT_TANH, "infer_transmil: unknown activation");
-  int64_t rows = 0;
-  for (int b = 0; b < n_bags; ++b) {
-    if (int r = rg_check_bag("infer_transmil", b, bags[b].N, bags[b].ldx, c->D, xdt, RgRules{MHIMX_INFER_MAX_ROWS, false})) return r;
-    rows += bags[b].N;
-  }
-  MHIMX_CHECK_ARG(rows <= MHIMX_INFER_MAX_ROWS, "infer_transmil: more than %d rows in one call", MHIMX_INFER_MAX_ROWS);
-  return 0;
+  return rg_check_infer_bags("infer_transmil", c->D, n_bags, bags, xdt);
 }
 
 // offsets that are not part of the public layout: weight image, LN rows, pseudo-inverse temporaries, PPEG stencil, partials
@@ -273,9 +265,7 @@ extern "C" int mhimx_infer_transmil_run(void* stream, const mhimx_infer_transmil
   }
   MHIMX_CHECK_ARG(params, "infer_transmil: null parameter");
   MHIMX_CHECK_ARG(algn, "infer_transmil: the feature, cls token, norm, to_qkv, to_out and predictor parameters must be 16-byte aligned");
-  for (int b = 0; b < n_bags; ++b) MHIMX_CHECK_ARG(bags[b].X && aligned16(bags[b].X), "infer_transmil: bag %d: null or unaligned rows", b);
-  MHIMX_CHECK_ARG(logits, "infer_transmil: the logits output is required");
-  MHIMX_CHECK_ARG(!loss || labels_dev, "infer_transmil: the loss output needs labels");
+  if (int r = rg_check_infer_io("infer_transmil", n_bags, bags, logits, "the logits output is required", loss, labels_dev)) return r;
   mhimx_infer_transmil_layout lo;
   TmScratch sc;
   NyBags tb = {};
@@ -292,12 +282,8 @@ extern "C" int mhimx_infer_transmil_run(void* stream, const mhimx_infer_transmil
   mhimx_prep_job job = {1, cfg->w1, F(sc.w1p), TM_E, cfg->D};
   if (int r = mhimx_prep_batch(stream, &job, 1)) return r;
   InferTab tab = {};
-  RgCount cnt;
-  for (int b = 0; b < n_bags; ++b) {
-    rg_tab_add(&tab, cnt, b, bags[b].X, bags[b].ldx, bags[b].N, bags[b].N);
-    tab.row0[b] = lo.tok0[b] + lo.pad[b] + 1;
-  }
-  rg_tab_close(&tab, cnt, n_bags);
+  rg_tab_fill(&tab, n_bags, bags);
+  for (int b = 0; b < n_bags; ++b) tab.row0[b] = lo.tok0[b] + lo.pad[b] + 1;
   tab.pad = x_dtype;
   if (int r = infer_project(st, tab, D, F(sc.w1p), cfg->b1, cfg->act, F(lo.x[0]))) return r;
   hipLaunchKernelGGL(tm_cls_kernel, dim3((unsigned)n_bags), dim3(128), 0, st, tb, cfg->cls_token, F(lo.x[0]));

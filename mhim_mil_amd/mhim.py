@@ -24,7 +24,7 @@ from __future__ import annotations
 import itertools
 import math
 import os
-from typing import Optional
+from typing import Callable, NamedTuple, Optional
 
 import numpy as np
 
@@ -277,6 +277,21 @@ class BagPlan:
         self.rows, self.L, self.Lk, self.R = rows, L, Lk, R
         self.merge_first = merge_first            # rows = [rows to merge (R) | rows that stay (Lk)] instead of [stay | merge]
         self.drop_seed, self.drop_mask, self.mca_seed, self.training = drop_seed, drop_mask, mca_seed, training
+
+
+class _InferFamily(NamedTuple):
+    """What differs between the native multi-bag inference calls (MHIM._INFER_FAMILIES: one record per baseline)."""
+    params: Callable            # model -> the parameter tensors the call reads, flat; None: not the call's model (a gated scorer)
+    shape_ok: Callable          # those tensors -> bool: the call's shape pins beyond the common dimension rule
+    aligned: tuple              # which of them (indices) must be 16-byte aligned
+    c_max: int                  # the most classes
+    cfg: Callable               # (model, no_norm) -> the call's configuration struct
+    run: Callable               # (cfg, the chunk's bags, its labels | None, return_attn, no_norm) -> the chunk's result
+    vector: Optional[Callable]  # (result, no_norm) -> the buffer of the per-bag vectors (rows at result.offsets); None: no return_attn
+    last: Callable              # (cat, the chunks' results) -> the family's own ``self.last`` entries
+    seeds: int                  # seeds the forward_test loop draws per bag: ``_step`` moves as far
+    row_bytes: Callable         # model -> workspace bytes per row of a call ...
+    fixed: int                  # ... and the share that does not grow with the rows (infer_rows_per_call)
 
 
 # ----------------------------------------------------------------------------------------------- model
@@ -987,55 +1002,17 @@ class MHIM(nn.Module):
             out.append(x)
         return out
 
-    def _infer_ok(self, xs):
-        """True when mhimx_infer_run_x (ABMIL) / mhimx_infer_dsmil_run (DSMIL) takes these bags (csrc/infer.hip: check_infer,
-        csrc/infer_dsmil.hip: check_dsmil, and the calls' own argument checks, mirrored: what they would refuse takes the forward_test loop
-        instead of raising).  One dtype per call - fp32, fp16 or bf16; the row pitch of a 2-byte bag is a multiple of 8 elements (16-byte
-        rows)."""
-        if self.training or self.merge_test or self._op_prec == "f32" or ops.KERNEL_EVENT_HOOK is not None:
-            return False
-        dev = self.feature[0].weight.device
-        if self.baseline == "dsmil":                            # mhimx_infer_dsmil_run (csrc/infer_dsmil.hip: check_dsmil), mirrored
-            if not (self.mlp_dim == 512 and DS.QDIM == 128 and 1 <= self.n_classes <= 16 and self.input_dim % 256 == 0
-                    and self.input_dim <= (1 << 20)):
-                return False
-            ps = self._infer_dsmil_params()
-            if tuple(ps[4].shape) != (128, 512) or tuple(ps[6].shape) != (128, 128) or tuple(ps[8].shape) != (512, 512):
-                return False
-            if (any(not t.is_contiguous() or t.dtype != torch.float32 or t.device != dev for t in ps)
-                    or any(ps[j].data_ptr() % 16 for j in (0, 1, 2, 4, 6, 8, 9))):
-                return False
-        elif self.baseline == "selfattn":                       # mhimx_infer_transmil_run (csrc/infer_transmil.hip: check_transmil), mirrored
-            if not (self.mlp_dim == 512 and 1 <= self.n_classes <= 16 and self.input_dim % 256 == 0 and self.input_dim <= (1 << 20)):
-                return False
-            ps, layers = self._infer_transmil_params()
-            flat = list(ps) + [t for ly in layers for t in ly]
-            if any(not t.is_contiguous() or t.dtype != torch.float32 or t.device != dev for t in flat):
-                return False
-            if any(t.data_ptr() % 16 for t in (ps[0], ps[1], ps[2], ps[9], ps[10], ps[11])) or any(t.data_ptr() % 16 for ly in layers for t in ly[:5]):
-                return False
-        else:
-            if self.baseline != "attn" or self.online_encoder.gated:
-                return False
-            att = self.online_encoder.attention.attention
-            if not (self.mlp_dim == 512 and att[0].weight.shape[0] == 128 and 1 <= self.n_classes <= 16 and self.input_dim % 256 == 0
-                    and self.input_dim <= (1 << 20)):
-                return False
-            ps = (self.feature[0].weight, self.feature[0].bias, att[0].weight, att[2].weight, self.predictor.weight, self.predictor.bias)
-            if any(not t.is_contiguous() or t.dtype != torch.float32 or t.device != dev for t in ps) or any(t.data_ptr() % 16 for t in ps[:3]):
-                return False
-        kinds = {x.dtype for x in xs}
-        if len(kinds) != 1 or not kinds <= {torch.float32, torch.float16, torch.bfloat16}:
-            return False
-        return all(x.dim() == 2 and x.device == dev for x in xs) and ops.infer_bags_ok(
-            [(x.shape[0], x.shape[1], x.stride(0), x.stride(1), x.data_ptr()) for x in xs], self.input_dim, xs[0].element_size())
+    def _infer_abmil_params(self):
+        """The six tensors of mhimx_infer_cfg.p, in its order; None for a gated scorer (not the call's model)."""
+        if self.online_encoder.gated:
+            return None
+        f, att, pr = self.feature[0], self.online_encoder.attention.attention, self.predictor
+        return (f.weight, f.bias, att[0].weight, att[2].weight, pr.weight, pr.bias)
 
     def _infer_cfg(self):
-        att = self.online_encoder.attention.attention
-        f, pr = self.feature[0], self.predictor
-        return L.InferCfg(D=self.input_dim, E=self.mlp_dim, A=att[0].weight.shape[0], C=self.n_classes,
-                          act=L.act_code(self.act, _FEATURE_ACTS), da_act=L.act_code(self.da_act, _SCORER_ACTS),
-                          p=ops.infer_params(f.weight.data, f.bias.data, att[0].weight.data, att[2].weight.data, pr.weight.data, pr.bias.data))
+        ps = self._infer_abmil_params()
+        return L.InferCfg(D=self.input_dim, E=self.mlp_dim, A=ps[2].shape[0], C=self.n_classes, act=L.act_code(self.act, _FEATURE_ACTS),
+                          da_act=L.act_code(self.da_act, _SCORER_ACTS), p=ops.infer_params(*(t.data for t in ps)))
 
     def _infer_dsmil_params(self):
         """The twelve tensors of mhimx_infer_dsmil_cfg, in its order."""
@@ -1062,18 +1039,59 @@ class MHIM(nn.Module):
         ps, layers = self._infer_transmil_params()
         return ops.infer_transmil_cfg(self.input_dim, self.n_classes, L.act_code(self.act, _FEATURE_ACTS), ps, layers)
 
+    # One record per native family: everything _infer_ok, _infer_run and infer_rows_per_call need to know about the call behind a baseline.
+    # (row_bytes / fixed: the call's workspace share per row and whatever the rows are - TransMIL's row is a PADDED token, and its per-bag
+    # share, landmark matrices and a3v partials, about 56 MiB per bag, comes on top; DSMIL keeps h, V, Q and the classes of every row with
+    # the per-chunk partials, and 4 MiB of weight images and 32 bags' last chunks.)
+    _INFER_FAMILIES = {
+        "attn": _InferFamily(                                   # mhimx_infer_run_x (csrc/infer.hip: check_infer), mirrored
+            params=lambda m: m._infer_abmil_params(), shape_ok=lambda ps: ps[2].shape[0] == 128, aligned=(0, 1, 2), c_max=16, cfg=lambda m, no_norm: m._infer_cfg(),
+            run=lambda cfg, xs, labels, attn, no_norm: ops.infer_many(cfg, xs, labels=labels, want_attn=attn and not no_norm,
+                                                                      want_score=attn and no_norm),
+            vector=lambda r, no_norm: r.score if no_norm else r.attn, last=lambda cat, rs: {}, seeds=1, row_bytes=lambda m: 2060, fixed=0),
+        "dsmil": _InferFamily(                                  # mhimx_infer_dsmil_run (csrc/infer_dsmil.hip: check_dsmil), mirrored
+            params=lambda m: m._infer_dsmil_params(),
+            shape_ok=lambda ps: DS.QDIM == 128 and [tuple(ps[j].shape) for j in (4, 6, 8)] == [(128, 512), (128, 128), (512, 512)],   # (q.0, q.2, v.1)
+            aligned=(0, 1, 2, 4, 6, 8, 9), c_max=16, cfg=lambda m, no_norm: m._infer_dsmil_cfg(no_norm),
+            run=lambda cfg, xs, labels, attn, no_norm: ops.infer_dsmil_many(cfg, xs, labels=labels, want_attn=attn, want_B=True),
+            vector=lambda r, no_norm: r.attn,                   # (the instance score)
+            last=lambda cat, rs: {"infer_parts": (cat([r.logits_bag for r in rs]), cat([r.logits_ins for r in rs]), cat([r.B for r in rs]))},
+            seeds=1, row_bytes=lambda m: 4673 + 8 * m.n_classes, fixed=4 << 20),
+        "selfattn": _InferFamily(                               # mhimx_infer_transmil_run (csrc/infer_transmil.hip: check_transmil), mirrored
+            params=lambda m: (lambda ps, layers: ps + layers[0] + layers[1])(*m._infer_transmil_params()), shape_ok=lambda ps: True,
+            aligned=(0, 1, 2, 9, 10, 11) + tuple(13 + 6 * l + j for l in range(2) for j in range(5)), c_max=16,
+            cfg=lambda m, no_norm: m._infer_transmil_cfg(),
+            run=lambda cfg, xs, labels, attn, no_norm: ops.infer_transmil_many(cfg, xs, labels=labels),
+            vector=None,                                        # (one attention map per layer: return_attn takes the forward_test loop)
+            last=lambda cat, rs: {}, seeds=3,                   # (the feature seed, two to_out seeds of _encode)
+            row_bytes=lambda m: 26 * 1024, fixed=0),
+    }
+
+    def _infer_ok(self, xs):
+        """True when the baseline's native call (_INFER_FAMILIES) takes these bags: the calls' common front, their parameter and shape rules
+        and their per-bag checks, mirrored - what they would refuse takes the forward_test loop instead of raising.  One dtype per call -
+        fp32, fp16 or bf16; the row pitch of a 2-byte bag is a multiple of 8 elements (16-byte rows)."""
+        fam = self._INFER_FAMILIES[self.baseline]
+        if self.training or self.merge_test or self._op_prec == "f32" or ops.KERNEL_EVENT_HOOK is not None:
+            return False
+        if not (self.mlp_dim == 512 and 1 <= self.n_classes <= fam.c_max and self.input_dim % 256 == 0 and self.input_dim <= (1 << 20)):
+            return False
+        dev = self.feature[0].weight.device
+        ps = fam.params(self)
+        if (ps is None or not fam.shape_ok(ps) or any(not t.is_contiguous() or t.dtype != torch.float32 or t.device != dev for t in ps)
+                or any(ps[j].data_ptr() % 16 for j in fam.aligned)):
+            return False
+        kinds = {x.dtype for x in xs}
+        if len(kinds) != 1 or not kinds <= {torch.float32, torch.float16, torch.bfloat16}:
+            return False
+        return all(x.dim() == 2 and x.device == dev for x in xs) and ops.infer_bags_ok(
+            [(x.shape[0], x.shape[1], x.stride(0), x.stride(1), x.data_ptr()) for x in xs], self.input_dim, xs[0].element_size())
+
     def infer_rows_per_call(self):
-        """Row cap of one native call.  ABMIL: ``infer_row_cap`` (its workspace: 2060 bytes per row).  DSMIL keeps h, V, Q and the classes
-        of every row (4673 + 8 C bytes per row with the per-chunk partials) and two more weight images: its cap is the row count whose
-        workspace is no larger than the ABMIL call's at ``infer_row_cap`` - a little under half of it."""
-        if getattr(self, "baseline", "attn") == "selfattn":
-            # TransMIL keeps 26 KiB per PADDED token (x, qkv, block output and y of both layers, the LayerNorm rows): the token count
-            # whose share of the workspace is no larger than the ABMIL call's at ``infer_row_cap``.  (The per-bag share - landmark
-            # matrices and a3v partials, about 56 MiB per bag - comes on top whatever the rows are.)
-            return max(1, self.infer_row_cap * 2060 // (26 * 1024))
-        if getattr(self, "baseline", "attn") != "dsmil":
-            return self.infer_row_cap
-        return max(1, (self.infer_row_cap * 2060 - (4 << 20)) // (4673 + 8 * self.n_classes))   # (4 MiB: images, 32 bags' last chunks)
+        """Row cap of one native call: the row count whose workspace share is no larger than the ABMIL call's at ``infer_row_cap`` (2060
+        bytes per row).  ABMIL: ``infer_row_cap`` itself; DSMIL: a little under half of it; TransMIL: about a thirteenth, in padded tokens."""
+        fam = self._INFER_FAMILIES[getattr(self, "baseline", "attn")]
+        return max(1, (self.infer_row_cap * 2060 - fam.fixed) // fam.row_bytes(self))
 
     def infer_chunks(self, xs):
         """Index ranges of the calls ``infer_many`` makes: at most L.INFER_MAX bags and ``infer_rows_per_call()`` rows each (one bag at
@@ -1110,99 +1128,65 @@ class MHIM(nn.Module):
 
     def _infer_run(self, xs, labels, return_attn, no_norm, topk=None):
         """``infer_many``'s routes -> (logits, per-bag attention list, loss | None, top-k | None).  ``topk`` = (k, largest): the per-bag
-        vectors are not handed out but ranked - on the native routes one ops.topk_many per chunk, on the chunk's own attention / score
+        vectors are not handed out but ranked - on the native route one ops.topk_many per chunk, on the chunk's own attention / score
         buffer with the chunk's offsets; on the forward_test loop the bags' vectors packed into one vector per L.INFER_MAX bags - and the
         fourth result is (idx [n, k], val [n, k])."""
         return_attn = return_attn or topk is not None
-        tk = []                                   # (idx, val) of every ops.topk_many call, in bag order
+        fam = self._INFER_FAMILIES[self.baseline]
         xs = self._infer_bags(xs, keep_half=True)
-        if any(x.dtype != torch.float32 for x in xs) and not self._infer_ok(xs):
-            xs = [x.float() for x in xs]
         n = len(xs)
+        native = n > 0 and self._infer_ok(xs)
+        if not native and any(x.dtype != torch.float32 for x in xs):        # (a half list the call refuses: widened, and asked again)
+            xs = [x.float() for x in xs]
+            native = self._infer_ok(xs)
+        native = native and (fam.vector is not None or not return_attn)
         if labels is not None:
             labels = labels.reshape(-1).to(device=xs[0].device, dtype=torch.int64) if n else labels
             if labels.numel() != n:
                 raise L.MhimxError(f"MHIM.infer_many: {labels.numel()} labels for {n} bags")
-        native = n > 0 and self._infer_ok(xs)
-        attns = []
-        if self.baseline == "dsmil":
-            # the MIXED logits 0.5 * bag + 0.5 * max-instance (what validate_func makes of forward_test's pair, common_mil.py:66-67);
-            # the pair itself and B: self.last["infer_parts"]
-            if native:
-                cfg = self._infer_dsmil_cfg(no_norm)
-                chunks = self.infer_chunks(xs)
-                rs = []
-                for lo, hi in chunks:
-                    r = ops.infer_dsmil_many(cfg, xs[lo:hi], labels=None if labels is None else labels[lo:hi].contiguous(),
-                                             want_attn=return_attn, want_B=True)
-                    rs.append(r)
-                    if topk is not None:
-                        tk.append(ops.topk_many(r.attn, r.offsets, *topk))
-                    elif return_attn:
-                        attns += [r.attn[r.offsets[j]:r.offsets[j + 1]] for j in range(hi - lo)]
-                self._step += n                   # (the stream position the forward_test loop leaves behind: one seed per bag)
-                cat = lambda ts: ts[0] if len(ts) == 1 else torch.cat(ts)
-                logits = cat([r.logits for r in rs])
-                loss = None if labels is None else cat([r.loss for r in rs])
-                self.last = {"infer_native": True, "infer_calls": len(chunks),
-                             "infer_parts": (cat([r.logits_bag for r in rs]), cat([r.logits_ins for r in rs]), cat([r.B for r in rs]))}
-            else:
-                lb, li, Bs = [], [], []
-                for x in xs:
-                    o = self.forward_test(x, return_attn=return_attn, no_norm=no_norm)
-                    lb.append(o[0][0].reshape(1, -1))
-                    li.append(o[0][1].reshape(1, -1))
-                    if return_attn:
-                        attns.append(o[1].reshape(-1))
-                    else:
-                        Bs.append(o[1])
-                dev = self.feature[0].weight.device
-                lb = torch.cat(lb) if lb else torch.empty((0, self.n_classes), device=dev)
-                li = torch.cat(li) if li else torch.empty((0, self.n_classes), device=dev)
-                logits = 0.5 * lb + 0.5 * li
-                loss = None if labels is None else torch.nn.functional.cross_entropy(logits, labels, reduction="none")
-                self.last = {"infer_native": False, "infer_calls": 0, "infer_parts": (lb, li, torch.cat(Bs) if Bs else None)}
-        elif native and self.baseline == "selfattn" and not return_attn:
-            cfg = self._infer_transmil_cfg()
-            chunks = self.infer_chunks(xs)
-            rs = [ops.infer_transmil_many(cfg, xs[lo:hi], labels=None if labels is None else labels[lo:hi].contiguous()) for lo, hi in chunks]
-            self._step += 3 * n                   # (what the forward_test loop consumes per bag: the feature seed, two to_out seeds of _encode)
-            logits = rs[0].logits if len(rs) == 1 else torch.cat([r.logits for r in rs])
-            loss = None if labels is None else (rs[0].loss if len(rs) == 1 else torch.cat([r.loss for r in rs]))
-            self.last = {"infer_native": True, "infer_calls": len(chunks)}
-        elif native and self.baseline != "selfattn":
-            cfg = self._infer_cfg()
-            chunks = self.infer_chunks(xs)
-            lg, ls = [], []
+        tk, attns = [], []                        # (idx, val) of every ops.topk_many call, in bag order; the per-bag vectors
+        if native:
+            cfg, chunks, rs = fam.cfg(self, no_norm), self.infer_chunks(xs), []
             for lo, hi in chunks:
-                r = ops.infer_many(cfg, xs[lo:hi], labels=None if labels is None else labels[lo:hi].contiguous(),
-                                   want_attn=return_attn and not no_norm, want_score=return_attn and no_norm)
-                lg.append(r.logits)
-                ls.append(r.loss)
+                r = fam.run(cfg, xs[lo:hi], None if labels is None else labels[lo:hi].contiguous(), return_attn, no_norm)
+                rs.append(r)
+                vec = fam.vector(r, no_norm) if return_attn else None
                 if topk is not None:
-                    tk.append(ops.topk_many(r.score if no_norm else r.attn, r.offsets, *topk))
+                    tk.append(ops.topk_many(vec, r.offsets, *topk))
                 elif return_attn:
-                    a = r.score if no_norm else r.attn
-                    attns += [a[r.offsets[j]:r.offsets[j + 1]] for j in range(hi - lo)]
-            self._step += n                       # (the stream position the forward_test loop leaves behind: one seed per bag)
-            logits = lg[0] if len(lg) == 1 else torch.cat(lg)
-            loss = None if labels is None else (ls[0] if len(ls) == 1 else torch.cat(ls))
-            self.last = {"infer_native": True, "infer_calls": len(chunks)}
+                    attns += [vec[r.offsets[j]:r.offsets[j + 1]] for j in range(hi - lo)]
+            self._step += fam.seeds * n           # (the stream position the forward_test loop leaves behind)
+            cat = lambda ts: ts[0] if len(ts) == 1 else torch.cat(ts)
+            logits = cat([r.logits for r in rs])
+            loss = None if labels is None else cat([r.loss for r in rs])
+            self.last = {"infer_native": True, "infer_calls": len(chunks), **fam.last(cat, rs)}
         else:
-            lg = []
+            # DSMIL: forward_test's pair ([bag, max-instance], B | attn) becomes the MIXED logits 0.5 * bag + 0.5 * max-instance (what
+            # validate_func makes of it, common_mil.py:66-67); the pair itself and B: self.last["infer_parts"]
+            dsmil, dev = self.baseline == "dsmil", self.feature[0].weight.device
+            lg, li, Bs = [], [], []
             for x in xs:
                 o = self.forward_test(x, return_attn=return_attn, no_norm=no_norm)
+                head, tail = o if dsmil or return_attn else (o, None)
+                if dsmil:
+                    head, ins = head
+                    li.append(ins.reshape(1, -1))
+                lg.append(head.reshape(1, -1))
                 if return_attn:
-                    lg.append(o[0].reshape(1, -1))
-                    attns.append(o[1].reshape(-1) if torch.is_tensor(o[1]) else o[1])
-                else:
-                    lg.append(o.reshape(1, -1))
-            logits = torch.cat(lg) if lg else torch.empty((0, self.n_classes), device=self.feature[0].weight.device)
+                    attns.append(tail.reshape(-1) if torch.is_tensor(tail) else tail)
+                elif dsmil:
+                    Bs.append(tail)
+            logits = torch.cat(lg) if lg else torch.empty((0, self.n_classes), device=dev)
+            parts = {}
+            if dsmil:
+                lb, li = logits, torch.cat(li) if li else torch.empty((0, self.n_classes), device=dev)
+                logits = 0.5 * lb + 0.5 * li
+                parts = {"infer_parts": (lb, li, torch.cat(Bs) if Bs else None)}
             loss = None if labels is None else torch.nn.functional.cross_entropy(logits, labels, reduction="none")
-            self.last = {"infer_native": False, "infer_calls": 0}
+            self.last = {"infer_native": False, "infer_calls": 0, **parts}
         if topk is None:
             return logits, attns, loss, None
-        for lo in range(0, len(attns), L.INFER_MAX):            # (the forward_test loop's vectors; the native routes left none)
+        for lo in range(0, len(attns), L.INFER_MAX):            # (the forward_test loop's vectors; the native route left none)
             part = [a.reshape(-1).float() for a in attns[lo:lo + L.INFER_MAX]]
             tk.append(ops.topk_many(torch.cat(part).contiguous(), [0] + list(itertools.accumulate(a.numel() for a in part)), *topk))
         dev = self.feature[0].weight.device

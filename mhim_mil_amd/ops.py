@@ -8,6 +8,8 @@ from __future__ import annotations
 
 import collections
 import ctypes as C
+import functools
+import itertools
 import math
 from typing import Optional
 
@@ -1078,16 +1080,25 @@ class InferResult:
 _INFER_WS = {}              # device index -> the cached workspace (grown on demand, like the step executor's)
 
 
+def _infer_table(xs):
+    """The mhimx_infer_bag array of the bags ``xs`` (one entry at least: the calls refuse an empty list before they read it)."""
+    return (L.InferBag * max(len(xs), 1))(*[L.InferBag(X=x.data_ptr(), ldx=x.stride(0), N=x.shape[0]) for x in xs])
+
+
 def infer_params(w1, b1, wa, wc, wp, bp):
     for n, t in (("w1", w1), ("b1", b1), ("wa", wa), ("wc", wc), ("wp", wp), ("bp", bp)):
         _chk(t, name=n)
     return L.StepParams(w1=w1.data_ptr(), b1=b1.data_ptr(), wa=wa.data_ptr(), wc=wc.data_ptr(), wp=wp.data_ptr(), bp=bp.data_ptr())
 
 
-def infer_ws_bytes(cfg, xs):
-    """mhimx_infer_ws_bytes for the bags ``xs`` ([N, D] each): host arithmetic only."""
-    bags = (L.InferBag * len(xs))(*[L.InferBag(X=x.data_ptr(), ldx=x.stride(0), N=x.shape[0]) for x in xs])
-    return L.lib().mhimx_infer_ws_bytes(C.byref(cfg), len(xs), bags)
+def infer_ws_bytes(cfg, xs, call="mhimx_infer_ws_bytes"):
+    """mhimx_infer_ws_bytes (or, with their own configurations, the DSMIL and TransMIL calls' query) for the bags ``xs`` ([N, D] each):
+    host arithmetic only."""
+    return getattr(L.lib(), call)(C.byref(cfg), len(xs), _infer_table(xs))
+
+
+infer_dsmil_ws_bytes = functools.partial(infer_ws_bytes, call="mhimx_infer_dsmil_ws_bytes")
+infer_transmil_ws_bytes = functools.partial(infer_ws_bytes, call="mhimx_infer_transmil_ws_bytes")
 
 
 _X_DTYPES = {torch.float32: L.X_F32, torch.float16: L.X_F16, torch.bfloat16: L.X_BF16}
@@ -1121,17 +1132,14 @@ def _infer_front(who, ws_bytes_fn, cfg, xs, labels, ws):
     _chk(labels, torch.int64, "labels")
     if labels is not None and labels.numel() != n:
         raise L.MhimxError(f"{who}: {labels.numel()} labels for {n} bags")
-    bags = (L.InferBag * max(n, 1))(*[L.InferBag(X=x.data_ptr(), ldx=x.stride(0), N=x.shape[0]) for x in xs])
+    bags = _infer_table(xs)
     need = getattr(L.lib(), ws_bytes_fn)(C.byref(cfg), n, bags)
     if need < 0:
         L.check(int(need), ws_bytes_fn)
     dev = xs[0].device
     if ws is None:
         ws = workspace(_INFER_WS, dev.index, need, dev, slack=1.0)
-    offsets = [0]
-    for x in xs:
-        offsets.append(offsets[-1] + int(x.shape[0]))
-    return n, xdt, bags, ws, dev, offsets
+    return n, xdt, bags, ws, dev, [0] + list(itertools.accumulate(int(x.shape[0]) for x in xs))
 
 
 def infer_many(cfg, xs, labels=None, want_attn=False, want_score=False, want_z=False, ws=None):
@@ -1173,12 +1181,6 @@ def infer_dsmil_cfg(D, E, Cc, act, cls_attn, no_norm, params):
         _chk(t, name=n)
     return L.InferDsmilCfg(D=int(D), E=int(E), C=int(Cc), act=int(act), cls_attn=int(bool(cls_attn)), no_norm=int(bool(no_norm)),
                            **{n: t.data_ptr() for n, t in zip(_DSMIL_PARAMS, params)})
-
-
-def infer_dsmil_ws_bytes(cfg, xs):
-    """mhimx_infer_dsmil_ws_bytes for the bags ``xs`` ([N, D] each): host arithmetic only."""
-    bags = (L.InferBag * max(len(xs), 1))(*[L.InferBag(X=x.data_ptr(), ldx=x.stride(0), N=x.shape[0]) for x in xs])
-    return L.lib().mhimx_infer_dsmil_ws_bytes(C.byref(cfg), len(xs), bags)
 
 
 def infer_dsmil_many(cfg, xs, labels=None, want_attn=False, want_B=False, want_crit=False, ws=None):
@@ -1232,12 +1234,6 @@ def infer_transmil_cfg(D, Cc, act, params, layers):
     for j, ly in enumerate(layers):
         cfg.layer[j] = L.TransmilLayer(**{n: t.data_ptr() for n, t in zip(_TRANSMIL_LAYER, ly)})
     return cfg
-
-
-def infer_transmil_ws_bytes(cfg, xs):
-    """mhimx_infer_transmil_ws_bytes for the bags ``xs`` ([N, D] each): host arithmetic only."""
-    bags = (L.InferBag * max(len(xs), 1))(*[L.InferBag(X=x.data_ptr(), ldx=x.stride(0), N=x.shape[0]) for x in xs])
-    return L.lib().mhimx_infer_transmil_ws_bytes(C.byref(cfg), len(xs), bags)
 
 
 def infer_transmil_many(cfg, xs, labels=None, want_z=False, ws=None):
