@@ -302,7 +302,7 @@ class _SplitStep:
 @dataclasses.dataclass(frozen=True)
 class _WindowFamily:
     """What differs between the four native calls that make one update over 1 .. 32 bags of different row counts; FusedTrainer._run_family,
-    _family_ok, _window_rows_ok and _try_native hold what they share.  The trainer's methods and attributes are named, not bound:
+    _family_ok, _window_rows_ok and _native_form hold what they share.  The trainer's methods and attributes are named, not bound:
     tests replace ``ok`` and ``run`` on an instance."""
     model_kind: str                 # the trainer's model and
     baseline: str                   # the student's baseline the call serves
@@ -395,7 +395,7 @@ def _ragged_trainer_ok(tr, n):
     # (a cross-entropy bag of accumulation_steps == 1 keeps mhimx_step_run; loss="nll_surv": there is no survival form of that call, a
     # single bag is a window of one)
     return ((tr.accum > 1 or tr.loss == "nll_surv") and 1 <= n <= tr.accum
-            and tr._chain is None and not tr.step_dag and not getattr(tr, "time_project", False)   # check_rw: q_out, side_stream, time_project
+            and tr._chain is None and not tr.step_dag and not tr.time_project                     # check_rw: q_out, side_stream, time_project
             and s.mrh_sche is None and s.merge_enable and s.merge.k <= 6)
 
 
@@ -416,6 +416,8 @@ def _dsmil_mhim_bags_ok(tr, xs, i, dev):
 # FusedTrainer._window_route's answer: the route's name, the family of a native call (else None), the bags as the route reads them, the
 # labels and the censorship flags (a survival call's) it takes
 _Route = collections.namedtuple("_Route", "name fam xs labels surv")
+# FusedTrainer._step_route's answer, its single-bag twin: "exec", "nat", "py", or a family's run with the family, its labels and flags
+_StepRoute = collections.namedtuple("_StepRoute", "name fam labels surv")
 # FusedTrainer.shape_cached's cache entry: the graph, its static bag / label / output buffers, self.last and the optimiser's scalars it baked in
 _ShapeGraph = collections.namedtuple("_ShapeGraph", "graph x label logits losses patch_num keep_num last scal")
 
@@ -451,7 +453,7 @@ _RAGGED = _WindowFamily(
     max_bags=_L.RAGGED_WINDOW_MAX, max_rows=_L.RAGGED_WINDOW_MAX_ROWS, accum_caps_bags=False,   # check_rw
     feature_bf16x3=False,                                                                       # check_cfg has no such rule: _exec_ok decides
     trainer_ok=_ragged_trainer_ok,
-    bags_ok=lambda tr, xs, i, dev: all(tr._nat_ok(x, i) and tr._exec_ok(x, i, window=True) for x in xs))   # check_rw: check_cfg per bag
+    bags_ok=lambda tr, xs, i, dev: all(tr._exec_ok(x, i, window=True) for x in xs))             # check_rw: check_cfg per bag
 
 
 class FusedTrainer:
@@ -543,13 +545,15 @@ class FusedTrainer:
         # library itself - a bag costs one ctypes call instead of ~1700 interpreter calls (the eager step was host-bound).  MHIMX_STEP_EXEC=0:
         # the Python orchestration (kept: it is the executor's specification and takes every case the executor refuses)
         self.use_executor = os.environ.get("MHIMX_STEP_EXEC", "1") != "0"
-        self._exec = None
+        self._exec, self.time_project = None, False      # (mhimx_step_cfg.time_project: eager steps time their projection launch - bench.py)
         self.exec_max_rows = 262144        # include/mhimx.h MHIMX_STEP_MAX_ROWS
         self.single_pass = True            # ABMIL: one projection launch for teacher + student, bag-ordered buffers (when shapes allow)
         self.window_streams = 4            # accumulation windows (window_step): HIP streams the window's bags are issued on
         # (round 6) a window of same-shaped bags as ONE C call with every launch over all its bags (mhimx_window_run, csrc/step.hip);
         # MHIMX_WINDOW_BATCHED=0: the bags on HIP streams, as rounds 3-5 had it
         self.window_batched = _WINDOW_BATCHED
+        # made on first use: the stream form's side streams and slabs, its EMA weights per window length, shape_cached's graphs and counts
+        self._win, self._win_w, self._shape_graphs = None, {}, None
         self._rows_cache = {}
         # 'mhim_pure' accumulation windows as ONE call (mhimx_pure_window_run): rows of the call's row space (every bag rounded up to a
         # multiple of 32) a window may have - its workspace takes 5.7 KB per row (1.5 GB at this cap); include/mhimx.h allows twice as many
@@ -605,24 +609,32 @@ class FusedTrainer:
         as an int64 tensor of one element on the bag's device; an int or a CPU label takes the Python orchestration (``self.last["exec"]``
         says which ran)."""
         x = self.s._check_x(bag)
-        surv = self.loss == "nll_surv"
-        if surv:
+        if self.loss == "nll_surv":
             label = self._surv_label(label, x.device)
+        r = self._step_route(x, label, i, perm, ids_shuffle)
+        if r.fam is not None:
+            out = self._run_native(r.fam, [x], r.labels, i, bool(self._fold_now), surv=r.surv, single=True)
+            return out[0][0], out[1][0]
+        if r.name == "exec":
+            return self._exec_step(x, label, i)
+        return (self._forward_backward_nat if r.name == "nat" else self._forward_backward_py)(x, label, perm, ids_shuffle, i)
+
+    def _step_route(self, x, label, i, perm, ids_shuffle, executor=True):
+        """The _StepRoute that takes the widened bag ``x`` (``label`` of a survival trainer: _surv_label's pair): the one decision of
+        forward_backward, run_steps and shape_cached, made - like _window_route's - before any seed is drawn, counter touched, workspace
+        made or self.last written.  ``executor`` False: "exec" is not told from "nat" (_exec_ok is not asked).  DESIGN.md has the routes."""
+        surv = self.loss == "nll_surv"
         if self.accum == 1 and perm is None and ids_shuffle is None:
-            # one bag as a window of one (``x`` is widened already: a half bag is not offered as it is).  A survival bag: mhimx_pure_window_run_surv
-            # / mhimx_ragged_window_run_surv (accumulation_steps == 1: a bag of a longer window is scaled by 1 / accumulation_steps, which only
-            # the bag-after-bag route below does); the DSMIL steps: mhimx_dsmil_window_run, mhimx_dsmil_mhim_window_run
-            for fam in ((_PURE, _RAGGED) if surv else ()) + (_DSMIL, _DSMIL_MHIM):
-                sv = surv and fam.exec_surv is not None
-                out = self._try_native(fam, [x], [label[0]] if sv else [label], i, bool(self._fold_now), surv=[label[1]] if sv else None,
-                                       single=True)
-                if out is not None:
-                    return out[0][0], out[1][0]
-        if self._nat_ok(x, i):
-            if self._exec_ok(x, i, perm, ids_shuffle):
-                return self._exec_step(x, label, i)
-            return self._forward_backward_nat(x, label, perm, ids_shuffle, i)
-        return self._forward_backward_py(x, label, perm, ids_shuffle, i)
+            # one bag as a window of one (``x`` is the widened form already: a half bag is not offered as it is).  A survival bag (the plain
+            # ABMIL student's, by the constructor): mhimx_pure_window_run_surv / mhimx_ragged_window_run_surv (accumulation_steps == 1: only the
+            # orchestrations scale a bag by 1 / accumulation_steps); else the DSMIL steps: mhimx_dsmil_window_run, mhimx_dsmil_mhim_window_run
+            labels, flags = ([label[0]], [label[1]]) if surv else ([label], None)
+            for fam in (_PURE, _RAGGED) if surv else (_DSMIL, _DSMIL_MHIM):
+                if self._native_form(fam, [x], labels, i, wide=[x]) is not None:
+                    return _StepRoute(fam.run, fam, labels, flags)
+        nat = self._nat_ok(x, i)
+        name = "py" if not nat else "exec" if executor and self._exec_ok(x, i, perm, ids_shuffle, nat=nat) else "nat"
+        return _StepRoute(name, None, label, None)
 
     def _forward_backward_py(self, x, label, perm, ids_shuffle, i):
         """The Python orchestration of a step: every model and every case the native calls and the single-pass step refuse."""
@@ -764,11 +776,12 @@ class FusedTrainer:
             t is not None and t.bag_ordered_ok(x) and not t.merge_test and s.merge_enable and s.v2_counts(x.shape[0], i) is not None)))
 
     # ------------------------------------------------------------------------------------------------- the step behind the C-ABI
-    def _exec_ok(self, x, i=None, perm=None, ids_shuffle=None, window=False):
+    def _exec_ok(self, x, i=None, perm=None, ids_shuffle=None, window=False, nat=None):
         """True when mhimx_step_run takes this bag's step: the single-pass ABMIL step with device-drawn subsets, one process, one bag per
-        update, no injected draws (csrc/step.hip: check_cfg).  ``window``: as a bag of mhimx_window_run (several bags per update)."""
-        s, t = self.s, self.t
-        if ops.KERNEL_EVENT_HOOK is not None:          # (a caller brackets single launches with events: only the Python orchestration can)
+        update, no injected draws (csrc/step.hip: check_cfg).  ``window``: as a bag of mhimx_window_run (several bags per update).  The
+        executor enqueues _forward_backward_nat's launches, so it asks _nat_ok itself (``nat``: its answer, if the caller has it): never an error."""
+        s = self.s
+        if ops.KERNEL_EVENT_HOOK is not None or not (self._nat_ok(x, i) if nat is None else nat):      # (the hook: events around single launches)
             return False
         if self.loss != "ce" and not window:           # (the single-bag executors have no survival form: a bag is a window of one)
             return False
@@ -786,18 +799,13 @@ class FusedTrainer:
                 return False
             return self.pure_exec_shapes_ok(x.shape[0], x.shape[1], x.stride(0), x.stride(1), x.data_ptr(), E=s.mlp_dim,
                                             A=s.online_encoder.attention.attention[0].weight.shape[0], C=s.n_classes, max_rows=self.exec_max_rows)
-        mg = s.merge
-        if not (self.use_executor and self.model_kind == "mhim" and (self.accum == 1 or window) and not hooked and perm is None
-                and ids_shuffle is None and s.training and s._op_prec != "f32"
-                and mg.attn.to_q.weight.shape[0] == 512 and mg.attn.to_kv.weight.shape[0] == 1024):
+        mg = s.merge                                   # (_nat_ok: the plain ABMIL student with Merge on and the v2 recipe's counts)
+        if not (self.use_executor and (self.accum == 1 or window) and not hooked and perm is None and ids_shuffle is None and s.training
+                and s._op_prec != "f32" and mg.attn.to_q.weight.shape[0] == 512 and mg.attn.to_kv.weight.shape[0] == 1024):
             return False
+        # up to 16 384 rows: both random subsets drawn inside the one-workgroup select (MHIM.device_draw_ok: _step_counts_ok's 4096); above
+        # (round 6): the multi-workgroup select with the draws as keyed permutations - the launches MHIM.student_rows issues for such bags
         c = s.v2_counts(x.shape[0], i)
-        if c is None:
-            return False
-        # up to 16 384 rows: both random subsets drawn inside the one-workgroup select; above (round 6): the multi-workgroup select with the
-        # draws as keyed permutations - the launches MHIM.student_rows issues for such bags
-        if not (s.device_draw_ok(x.shape[0], i) if x.shape[0] <= 16384 else s.baseline == "attn"):
-            return False
         return self.step_exec_shapes_ok(x.shape[0], x.shape[1], x.stride(0), x.stride(1), x.data_ptr(), c, mg.k, E=s.mlp_dim,
                                         A=s.online_encoder.attention.attention[0].weight.shape[0], C=s.n_classes, max_rows=self.exec_max_rows)
 
@@ -919,18 +927,12 @@ class FusedTrainer:
             self._window_done(n, inside, update)
         return logits, losses
 
-    def _try_native(self, fam, bags, labels, i, update, surv=None, single=False, offer=None, wide=None):
-        """``fam``'s native call for these bags when its check takes them: first as they are when all are fp16, or all bf16 (_half_bags:
-        the call reads them where they lie), then widened to fp32 as every other route reads them; None when neither is taken.  ``offer``
-        (bags, widened) -> False: this form of the window is not offered to the call.  ``wide``: the caller's list of the widened bags -
-        filled here when it is empty and they are needed, so that a window is widened once however many calls and routes see it.  The
-        check (_native_form) and the call (_run_native) are looked up on the instance."""
-        xs = self._native_form(fam, bags, labels, i, offer, wide)
-        return None if xs is None else self._run_native(fam, xs, labels, i, update, surv, single)
-
     def _native_form(self, fam, bags, labels, i, offer=None, wide=None):
-        """_try_native's decision: the bags in the form ``fam``'s check takes them in - as they are, else widened - or None.  It draws no
-        seed and touches no counter or workspace (_family_ok)."""
+        """The bags in the form ``fam``'s check takes them in, or None: first as they are when all are fp16, or all bf16 (_half_bags: the
+        call reads them where they lie), then widened to fp32 as every other route reads them.  ``offer`` (bags, widened) -> False: this
+        form of the window is not offered to the call.  ``wide``: the caller's list of the widened bags - filled here when it is empty and
+        they are needed, so that a window is widened once however many calls and routes see it.  It draws no seed and touches no counter
+        or workspace (_family_ok); the check, like the call (_run_native), is looked up on the instance."""
         if self.model_kind != fam.model_kind or self.s.baseline != fam.baseline:
             return None
         ok = getattr(self, fam.ok)
@@ -945,7 +947,7 @@ class FusedTrainer:
         return None
 
     def _run_native(self, fam, xs, labels, i, update, surv=None, single=False):
-        """_try_native's run: ``fam``'s call on the bags its check took."""
+        """``fam``'s call on the bags its check took."""
         ia = (i,) if fam.full else ()
         kw = {n: v for n, v in (("surv", surv), ("single", single)) if v}          # (only what is set: a plain window is (xs, labels[, i], update))
         return getattr(self, fam.run)(xs, labels, *ia, update, **kw)
@@ -1167,7 +1169,7 @@ class FusedTrainer:
             cfg.q_out = self._q_scratch.data_ptr()
         else:
             cfg.q_out = None
-        cfg.time_project = int(bool(getattr(self, "time_project", False)))
+        cfg.time_project = int(bool(self.time_project))
         cfg.attn2score = int(bool(t.attn2score))
         cfg.drop_p_teacher = float(t.dropout_p if t.training else 0.0)
         cfg.merge_drop_p, cfg.merge_mm = float(s.merge.dropout), float(s.merge.g_q_mm)
@@ -1179,9 +1181,8 @@ class FusedTrainer:
     def _exec_window_ok(self, xs, labels, i=None):
         """True when mhimx_window_run takes this window: 2..8 bags of ONE shape that each pass _exec_ok, up to 16 384 rows (the one-workgroup
         select), merge_k <= 6, one process, no mid-run ratio schedule (csrc/step.hip: check_window)."""
-        from . import _lib as LB
         n = len(xs)
-        if not (self.window_batched and 2 <= n <= LB.WINDOW_MAX and self.world == 1 and self._chain is None and not self.step_dag
+        if not (self.window_batched and 2 <= n <= _L.WINDOW_MAX and self.world == 1 and self._chain is None and not self.step_dag
                 and self.flat.n_all % 4 == 0 and self.s.merge.k <= 6 and self.s.mrh_sche is None and self.flat.names[0] == "feature.0.weight"):
             return False
         x0 = xs[0]
@@ -1288,8 +1289,8 @@ class FusedTrainer:
         """len(bags) consecutive complete train steps (one update each) as ONE call of mhimx_step_run_many (SURVEY 7 H4 "run_steps"): the
         bags of a resident dataset, bag after bag, on one workspace.  ``i``: the iteration of the FIRST bag (bag j runs at i + j, as the
         reference's loop counts them - base_engine.py:78) or a sequence with one entry per bag.  Returns the last bag's (logits, losses).
-        What the executor's in-launch update does not do - gradient clipping (base_engine.py:115-119), unfolded reductions, accumulation -
-        goes bag by bag through train_step, which does."""
+        What the executor's in-launch update does not do - clipping (base_engine.py:115-119), unfolded reductions, accumulation, the survival
+        loss - and every chunk with a bag whose route (_step_route) is not "exec" goes bag by bag through train_step, which does."""
         L = mh.L
         n = len(bags)
         if n == 0 or len(labels) != n:
@@ -1300,7 +1301,8 @@ class FusedTrainer:
         xs = [self.s._check_x(b) for b in bags]
         if self._micro != 0:
             raise L.MhimxError("run_steps: called inside an accumulation window (a fresh update is required)")
-        if self.clip_grad or self.accum != 1 or self.world != 1 or not all(self._exec_ok(x, it) and self._nat_ok(x, it) for x, it in zip(xs, its)):
+        if self.clip_grad or self.accum != 1 or self.world != 1 or self.loss != "ce" or not all(
+                self._step_route(x, l, it, None, None).name == "exec" for x, l, it in zip(xs, labels, its)):
             out = None
             for b, l, it in zip(bags, labels, its):
                 out = self.train_step(b, l, i=it)
@@ -1461,23 +1463,19 @@ class FusedTrainer:
 
     # ------------------------------------------------------------------------------------------------- accumulation windows
     def window_ok(self, bags, i=None):
-        """The batched window takes the single-pass ABMIL step for every bag (the shapes _forward_backward_nat takes), one process."""
-        s, t = self.s, self.t
-        if self.model_kind != "mhim" or s.baseline != "attn" or not self.single_pass or s.mrh_sche is not None:
+        """The batched window takes the single-pass ABMIL step for every bag (_nat_ok: the shapes _forward_backward_nat takes) of the full
+        model, with device-drawn subsets and the dedicated weight-gradient pair, no mid-run ratio schedule, one process."""
+        s, xs = self.s, [b[0] if b.dim() == 3 else b for b in bags]
+        if self.model_kind != "mhim" or not self.single_pass or s.mrh_sche is not None:
             return False
-        for b in bags:
-            x = b[0] if b.dim() == 3 else b
-            if not (x.is_cuda and s.bag_ordered_ok(x) and t.bag_ordered_ok(x) and not t.merge_test and s.merge_enable
-                    and s.v2_counts(x.shape[0], i) is not None and s.device_draw_ok(x.shape[0], i)
-                    and ops.bag_wgrad_ok(x, s.mlp_dim, s.v2_counts(x.shape[0], i)[2])):
-                return False
-        if (_WINDOW_WGRAD or _WINDOW_PROJECT) and len({tuple((b[0] if b.dim() == 3 else b).shape) for b in bags}) > 1:
-            return False                                   # the opt-in multi-bag launches size their workspace from bag 0
-        return True
+        if not all(x.is_cuda and self._nat_ok(x, i) and s.device_draw_ok(x.shape[0], i)
+                   and ops.bag_wgrad_ok(x, s.mlp_dim, s.v2_counts(x.shape[0], i)[2]) for x in xs):
+            return False
+        return not ((_WINDOW_WGRAD or _WINDOW_PROJECT) and len({tuple(x.shape) for x in xs}) > 1)       # (they size their workspace from bag 0)
 
     def _window_state(self, n_streams, dev):
         """Side streams and their gradient slabs (stream 0 = the caller's stream accumulates straight into the flat gradient)."""
-        st = getattr(self, "_win", None)
+        st = self._win
         if st is None or len(st["streams"]) < n_streams - 1:
             fl = self.flat
             slabs = torch.zeros((max(n_streams - 1, 1), fl.n_all), device=dev)
@@ -1628,10 +1626,8 @@ class FusedTrainer:
                 ops.reduce_flush(lst)
         # the window's EMA chain on the k token sets: q <- mm^k q + (1 - mm) sum_j mm^(k-1-j) z_j
         mm = float(s.merge.g_q_mm)
-        w = self._win_w.get(k) if hasattr(self, "_win_w") else None
+        w = self._win_w.get(k)
         if w is None:                                                 # (device arithmetic only: capture-safe)
-            if not hasattr(self, "_win_w"):
-                self._win_w = {}
             w = self._win_w[k] = ((1.0 - mm) * mm ** torch.arange(k - 1, -1, -1, device=dev, dtype=torch.float64)).float()
         Z = torch.stack(tokens)                                       # [k, km, E]
         q = s.merge.global_q_mm.data.view(km, E)
@@ -1890,16 +1886,19 @@ class FusedTrainer:
         into ONE buffer all the graphs share (they never run concurrently; so do they their memory pool), one launch - and replayed, every later
         one replays.  A dataset of bags of many sizes replays from its second epoch on.  The draw / dropout streams advance through the device
         step counter: replays draw fresh masks.  Only the single-pass ABMIL step is cached (``_nat_ok``: no host read-back, fixed launch
-        shapes - a v1 mask ratio or a shape the one-pass kernels do not take runs eagerly), one process, accumulation_steps == 1.  The key
+        shapes - a v1 mask ratio or a shape the one-pass kernels do not take runs eagerly), one process, cross entropy, accumulation_steps == 1.  The key
         holds everything a capture bakes in on the host: shape, the HAM-ratio schedule's row counts, the models' train / eval state, the
         Merge switch, the loss weights and - for 'train_step' - the optimiser's scalars.  ``cache``: the K most recently USED shapes stay.
         Returns (logits, losses, patch_num, keep_num) - the graph's static output buffers: read them before the next call - or None when
         the step cannot be cached (run it eagerly)."""
         x = bag[0] if bag.dim() == 3 else bag
         s, t = self.s, self.t
-        if not (self.accum == 1 and self.world == 1 and x.is_cuda and x.dim() == 2 and not self._capturing and self._micro == 0):
+        if not (self.accum == 1 and self.world == 1 and self.loss == "ce" and x.is_cuda and x.dim() == 2 and not self._capturing and self._micro == 0):
             return None
-        nat = self._nat_ok(x, i) or self._dsmil_mhim_window_ok([x], [label], i)      # (mhimx_dsmil_mhim_window_run: no host read-back either)
+        # the eager step's own route, asked of the bag as handed over ("exec" and "nat" are one answer here: a replay does not pay for telling
+        # them apart).  mhimx_dsmil_mhim_window_run has no host read-back either; the teacher-free DSMIL call's shapes keep the form below
+        r = self._step_route(x, label, i, None, None, executor=False)
+        nat = r.name == "nat" or r.fam not in (None, _DSMIL)
         # (round 5) the TransMIL / DSMIL students: their step runs autograd over kernel-backed nodes whose gradient-accumulation nodes belong to
         # the stream they were first run on, so EVERY step of such a shape runs on the trainer's capture stream - eager on the first two
         # visits (the second is the capture's warm-up), captured on the third.  v2 recipe only (a v1 ratio reads a count back).
@@ -1908,7 +1907,7 @@ class FusedTrainer:
             return None
         # (a HAM-ratio schedule, --mrh_sche, changes the row counts - the launch shapes - every few hundred iterations: they are part of the key)
         counts = s.v2_counts(x.shape[0], i) if self.model_kind == "mhim" else None
-        st = getattr(self, "_shape_graphs", None)
+        st = self._shape_graphs
         if st is None:
             st = self._shape_graphs = {"graphs": {}, "seen": {}, "arena": None, "bad": set()}
         key = (what, tuple(x.shape), x.dtype, x.device.index, counts, s.training, None if t is None else t.training, s.merge_enable,
