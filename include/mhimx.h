@@ -1226,6 +1226,40 @@ int mhimx_infer_transmil_run(void* stream, const mhimx_infer_transmil_cfg* cfg, 
                              const int64_t* labels_dev, float* logits, float* loss, float* z, void* ws, int64_t ws_bytes, int32_t x_dtype);
 
 /* ------------------------------------------------------------------------------------------
+ * TransMIL attention maps and instance scores from the ragged call: the per-instance view of the same forward - the cls token's attention
+ * row of both layers for every bag of the call, and the pseudo-score the MHIM teacher ranks TransMIL instances by.
+ * replaces: modules/nystrom_attention.py:143-150 (return_attn: attn1[cls] @ pinv(attn2) @ attn3, the columns behind the padding and the cls
+ *           token) under mhim_modules/baseline.py:244-288 (SAttention.forward with return_attn: one map per layer),
+ *           modules/scoring.py:9-34 (get_pseudo_score_trans) under modules/mhim.py:207-227,250-260 (forward_teacher's attn2score branch,
+ *           forward_test with return_attn) - bag after bag from the host loop, about 35 launches per bag plus five for each map and four
+ *           for the score.
+ * mhimx_infer_transmil_run_attn runs the 96 launches of mhimx_infer_transmil_run through that call's ONE body (logits, loss and z are
+ * bit-equal to that call's) and then, out of the operands the layers left in the workspace (qkv, lm, z, lse3 of the layout), per layer
+ *           a1c = softmax_m(s q_cls . k~_m),  u = a1c z  (fp32, fixed order; grid (head, bag)),
+ *           attn[l][h][row0[b] + i] = sum_m u[m] softmax_n(s q~ k^T)[m, pad + 1 + i],  i < N_b  (the bag-batched form of
+ *           mhimx_nys_cls_attn: per bag that call's min(T / 64, 64) chunks and bits; the pad columns and the cls column are not written),
+ * attn [2, 8, R]: layer, head, then the bags' rows packed in bag order, R = sum N_b, row0[b] = N_0 + .. + N_{b-1} (head pitch R).
+ * With pscore [R] (optional, NULL): f = v * attn[0] per head over the R rows (v where layer 1 left it), to_out of layer 1 + bias, cam =
+ * f Wp^T (both in the 3-term bf16 form, over max(R, 32) rows: a row's bits do not depend on the size of the call),
+ * pscore[r] = max_c softmax_c(cam[r, c] + bp[0]) (mhimx_pseudo_score's row-wise form).
+ * Eval mode and the normalised form only (no_norm needs the pseudo-inverse of the raw landmark scores: the host loop keeps it).
+ * Launches: 96 + 4 (+ 4 with pscore), whatever n_bags is.  Properties and shape rules are mhimx_infer_transmil_run's (enqueue-only and
+ * capturable; no allocation, synchronisation or host-to-device copy; no floating-point atomics; no workgroup waits for another; the same
+ * bytes on two runs; a bag's outputs have the same bits wherever it stands in a call).  Checks, before any device call, mhimx_last_error
+ * names the call ("infer_transmil_attn") and the bag: everything mhimx_infer_transmil_run checks; a null attn; attn or pscore not 16-byte
+ * aligned; a workspace below mhimx_infer_transmil_attn_ws_bytes.
+ * Workspace: mhimx_infer_transmil_layout is its PREFIX (mhimx_infer_transmil_layout_of stays valid for it; mhimx_infer_transmil_ws_bytes
+ * does not change); behind it, in this order and 256-byte aligned each: u [n, 8, 256] of layer 0, u of layer 1 and, with want_pscore,
+ * f and to_out(f) [max(R, 32), 512] and cam [max(R, 32), C].
+ * MHIMX_VERSION stays 620: additions only.
+ * ---------------------------------------------------------------------------------------- */
+int64_t mhimx_infer_transmil_attn_ws_bytes(const mhimx_infer_transmil_cfg* cfg, int32_t n_bags, const mhimx_infer_bag* bags,
+                                           int32_t want_pscore);
+int mhimx_infer_transmil_run_attn(void* stream, const mhimx_infer_transmil_cfg* cfg, int32_t n_bags, const mhimx_infer_bag* bags,
+                                  const int64_t* labels_dev, float* logits, float* loss, float* z, float* attn, float* pscore, void* ws,
+                                  int64_t ws_bytes, int32_t x_dtype);
+
+/* ------------------------------------------------------------------------------------------
  * Ragged accumulation window of the teacher-free DSMIL model ('mhim_pure' with baseline 'dsmil': the recipe's first training for the
  * second MHIM baseline): ONE optimiser update over n_bags bags of DIFFERENT row counts in one call; n_bags = 1 is the single-bag step.
  * replaces: engines/base_engine.py:29-51,76-120 (the accumulation window: every bag's loss divided by the window's length, the gradients

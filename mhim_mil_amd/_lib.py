@@ -511,6 +511,8 @@ SYMBOLS = {
     "mhimx_infer_transmil_ws_bytes": (_I64, [C.POINTER(InferTransmilCfg), _I32, _P]),
     "mhimx_infer_transmil_layout_of": (C.c_int, [C.POINTER(InferTransmilCfg), _I32, _P, C.POINTER(InferTransmilLayout)]),
     "mhimx_infer_transmil_run": (C.c_int, [_P, C.POINTER(InferTransmilCfg), _I32, _P, _P, _P, _P, _P, _P, _I64, _I32]),
+    "mhimx_infer_transmil_attn_ws_bytes": (_I64, [C.POINTER(InferTransmilCfg), _I32, _P, _I32]),
+    "mhimx_infer_transmil_run_attn": (C.c_int, [_P, C.POINTER(InferTransmilCfg), _I32, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _I32]),
     "mhimx_topk_many_ws_bytes": (_I64, [_I32, _P, _I64]),
     "mhimx_topk_many": (C.c_int, [_P, _P, _I32, _P, _I64, _I32, _P, _P, _P, _I64]),
     "mhimx_step_run_many": (C.c_int, [_P, C.POINTER(StepCfg), _I32, _P, _P, _P, _P, C.POINTER(StepCounts), C.POINTER(StepSeeds), _I64, _P, _I64]),

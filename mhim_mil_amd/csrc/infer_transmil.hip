@@ -32,6 +32,19 @@
 //   and    1 tm_tail_kernel             grid = bags: LN of the cls row, predictor, cross entropy
 // No workgroup waits for another and there are no floating-point atomics.  A bag's chunks, tile walk and merge order depend on its own N
 // alone and every chunk-wide kernel computes a row from that row alone, so a bag's results have the same bits wherever it stands in a call.
+//
+// mhimx_infer_transmil_run_attn runs the same body (ONE body: the entry above passes no attention output) and then the attention tail
+// (nystrom_attention.py:143-150 under baseline.py:244-288; normalised form, eval mode), out of the operands the layers left in the workspace:
+//   per layer (2 launches, twice):
+//    1      tm_cls_u_kernel             grid (head, bag): a1c = softmax_m(scale q_cls k~_m), u = a1c z (the cls row of attn1 times the pseudo-inverse)
+//    1      ny_cls_row8_kernel<true>    bag-batched r = u softmax_n(q~ k^T), columns pad + 1 .. of every bag packed: attn [2, 8, R], R = sum N_b
+//   with pscore (get_pseudo_score_trans, scoring.py:9-34 under mhim.py:207-227,250-260; 4 launches):
+//    1      tm_pscore_f_kernel          f[r] = v_r * attn_l1[head, r] over the R instance rows, v read in the token space
+//    1      gemm_nt                     to_out of layer 1 + bias over the R rows
+//    1      gemm_nt                     cam = f Wp^T
+//    1      mhimx_pseudo_score          + bp[0], softmax over the classes, max
+// 96 + 4 (+ 4) launches.  Both products run over max(R, 32) rows (the rows behind R are zeros): a call of fewer than 17 rows stays on the tiled
+// kernel, so a row's bits do not depend on how many rows the call has.
 #include <math.h>
 #include <string.h>
 
@@ -163,15 +176,94 @@ __global__ __launch_bounds__(64) void tm_tail_kernel(NyBags tb, const float* __r
   loss[bag] = (lab >= 0 && lab < C) ? (cm + logf(den)) - picked : NAN;
 }
 
+// ------------------------------------------------------------------------------------------------ attention tail: u = attn1[cls] pinv
+// grid (head, bag), 256 threads, fp32, every sum in a fixed order.  s[m] = scale q_cls . k~_m (thread m; q_cls = row tok0 + pad of qkv, k~ the
+// second half of the bag's landmark means), a1c = softmax_m(s) (wave reductions, the four wave results in index order), then
+// u[m'] = sum_m a1c[m] z[m, m']: thread (g, c) adds rows 64 g .. 64 g + 63 of columns 4 c .. 4 c + 3 in index order (one 16-byte load per
+// row: the head's z is read once, 1 KiB rows across the workgroup), the four row groups are added in index order.
+__global__ __launch_bounds__(256) void tm_cls_u_kernel(NyBags tb, const float* __restrict__ qkv, const float* __restrict__ lm, const float* __restrict__ z,
+                                                       float* __restrict__ u) {
+  __shared__ float qs[TM_DH];
+  __shared__ float a1c[TM_M];
+  __shared__ float red[4];
+  __shared__ f32x4 part[4][64];
+  const int h = blockIdx.x, bag = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  int64_t tok0 = tb.tok0[0];
+  int T = tb.T[0], n = tb.n[0];
+  NY_PICK(tok0, tb.tok0, bag) NY_PICK(T, tb.T, bag) NY_PICK(n, tb.n, bag)
+  if (tid < TM_DH) qs[tid] = qkv[(tok0 + (T - n)) * TM_QKV + h * TM_DH + tid];
+  __syncthreads();
+  const f32x4* kr = reinterpret_cast<const f32x4*>(lm + ((int64_t)bag * TM_M + tid) * (2 * TM_E) + TM_E + h * TM_DH);
+  float s = 0.f;
+#pragma unroll
+  for (int d = 0; d < TM_DH / 4; ++d) {
+    const f32x4 kv = kr[d];
+    s = fmaf(qs[4 * d + 3], kv[3], fmaf(qs[4 * d + 2], kv[2], fmaf(qs[4 * d + 1], kv[1], fmaf(qs[4 * d], kv[0], s))));
+  }
+  s *= TM_SCALE;
+  const float wm = wave_max(s);
+  if (lane == 0) red[wave] = wm;
+  __syncthreads();
+  const float mx = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+  __syncthreads();
+  const float e = expf(s - mx);
+  const float wsum = wave_sum(e);
+  if (lane == 0) red[wave] = wsum;
+  __syncthreads();
+  a1c[tid] = e / (((red[0] + red[1]) + red[2]) + red[3]);
+  __syncthreads();
+  const f32x4* zp = reinterpret_cast<const f32x4*>(z + ((int64_t)bag * TM_H + h) * TM_MM) + lane;
+  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll 8
+  for (int i = 0; i < 64; ++i) {
+    const int m = 64 * wave + i;
+    const f32x4 zv = zp[m * (TM_M / 4)];
+    const float am = a1c[m];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[j] = fmaf(am, zv[j], acc[j]);
+  }
+  part[wave][lane] = acc;
+  __syncthreads();
+  if (tid < 64) reinterpret_cast<f32x4*>(u + ((int64_t)bag * TM_H + h) * TM_M)[tid] = ((part[0][tid] + part[1][tid]) + part[2][tid]) + part[3][tid];
+}
+
+// ------------------------------------------------------------------------------------------------ attention tail: f = v * attn per head
+// The bag-aware form of scale_heads_kernel (scoring.py:25): one wave per packed instance row r, f[r, c] = v[token(r), c] attn[c / 64, r]
+// with v read where the layer left it (columns 1024.. of the token space; token(r) = the bag's row tok0 + pad + 1 + (r - the bag's first
+// packed row)).  Rows R .. rows - 1 get exact zeros.
+__global__ __launch_bounds__(256) void tm_pscore_f_kernel(NyBags tb, const float* __restrict__ v, const float* __restrict__ attn, int64_t R, int64_t rows,
+                                                          float* __restrict__ f) {
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int64_t r = (int64_t)blockIdx.x * 4 + wave;
+  if (r >= rows) return;
+  f32x4* fo = reinterpret_cast<f32x4*>(f + r * TM_E);
+  if (r >= R) {
+    const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+    fo[lane] = zero; fo[64 + lane] = zero;
+    return;
+  }
+  int64_t tok0 = tb.tok0[0], row0 = 0, o = 0;
+  int T = tb.T[0], n = tb.n[0];
+#pragma unroll
+  for (int q = 0; q < MHIMX_INFER_MAX; ++q)
+    if (q < tb.nbags) {
+      if (r >= o) { tok0 = tb.tok0[q]; T = tb.T[q]; n = tb.n[q]; row0 = o; }
+      o += tb.n[q] - 1;
+    }
+  const f32x4* vi = reinterpret_cast<const f32x4*>(v + (tok0 + (T - n) + 1 + (r - row0)) * TM_QKV);
+#pragma unroll
+  for (int q = 0; q < 2; ++q) fo[64 * q + lane] = vi[64 * q + lane] * attn[(int64_t)(4 * q + (lane >> 4)) * R + r];
+}
+
 // ------------------------------------------------------------------------------------------------ host
 // the checks of mhimx_infer_run_x on the bag table and the element type, and this call's own shape rules
-int check_transmil(const mhimx_infer_transmil_cfg* c, int32_t n_bags, const mhimx_infer_bag* bags, int32_t xdt) {
-  if (int r = rg_check_infer_front("infer_transmil", xdt, c, n_bags, bags, true)) return r;
+int check_transmil(const char* who, const mhimx_infer_transmil_cfg* c, int32_t n_bags, const mhimx_infer_bag* bags, int32_t xdt) {
+  if (int r = rg_check_infer_front(who, xdt, c, n_bags, bags, true)) return r;
   MHIMX_CHECK_ARG(c->C >= 1 && c->C <= TM_MAXC && c->D > 0 && c->D % 256 == 0 && c->D <= (1 << 20),
-                  "infer_transmil: shapes outside the ragged TransMIL forward (E = 512, 8 x 64 heads, 256 landmarks, 1 <= C <= %d, D %% 256 == 0)",
-                  TM_MAXC);
-  MHIMX_CHECK_ARG(c->act >= MHIMX_ACT_NONE && c->act <= MHIMX_ACT_TANH, "infer_transmil: unknown activation");
-  return rg_check_infer_bags("infer_transmil", c->D, n_bags, bags, xdt);
+                  "%s: shapes outside the ragged TransMIL forward (E = 512, 8 x 64 heads, 256 landmarks, 1 <= C <= %d, D %% 256 == 0)", who, TM_MAXC);
+  MHIMX_CHECK_ARG(c->act >= MHIMX_ACT_NONE && c->act <= MHIMX_ACT_TANH, "%s: unknown activation", who);
+  return rg_check_infer_bags(who, c->D, n_bags, bags, xdt);
 }
 
 // offsets that are not part of the public layout: weight image, LN rows, pseudo-inverse temporaries, PPEG stencil, partials
@@ -229,31 +321,62 @@ void transmil_layout(const mhimx_infer_transmil_cfg* c, int32_t n_bags, const mh
   if (sc) *sc = s;
 }
 
+// what mhimx_infer_transmil_run_attn keeps BEHIND that layout (its prefix): u of both layers, and for the pseudo-score f, to_out(f), cam
+struct TmAttnWs { int64_t R, rows, u[2], f, g, cam, total; };
+
+void transmil_attn_layout(const mhimx_infer_transmil_cfg* c, int32_t n_bags, const mhimx_infer_bag* bags, const mhimx_infer_transmil_layout& lo,
+                          bool want_pscore, TmAttnWs* a) {
+  a->R = 0;
+  for (int b = 0; b < n_bags; ++b) a->R += bags[b].N;
+  a->rows = a->R < 32 ? 32 : a->R;
+  Arena ar(nullptr, 0);
+  ar.off = lo.total;
+  auto F = [&](int64_t floats) { const int64_t o = ar.off; ar.take<float>(floats); return o; };
+  for (int l = 0; l < 2; ++l) a->u[l] = F((int64_t)n_bags * TM_H * TM_M);
+  a->f = a->g = a->cam = 0;
+  if (want_pscore) { a->f = F(a->rows * TM_E); a->g = F(a->rows * TM_E); a->cam = F(a->rows * c->C); }
+  a->total = ar.off;
+}
+
+struct TmAttnOut { float* attn; float* pscore; };             // the outputs of the tail (transmil_run)
+
 }  // namespace
 }  // namespace mhimx
 
 extern "C" int64_t mhimx_infer_transmil_ws_bytes(const mhimx_infer_transmil_cfg* cfg, int32_t n_bags, const mhimx_infer_bag* bags) {
   using namespace mhimx;
-  if (int r = check_transmil(cfg, n_bags, bags, MHIMX_X_F32)) return r;
+  if (int r = check_transmil("infer_transmil", cfg, n_bags, bags, MHIMX_X_F32)) return r;
   mhimx_infer_transmil_layout lo;
   transmil_layout(cfg, n_bags, bags, &lo, nullptr, nullptr);
   return lo.total;
 }
 
+extern "C" int64_t mhimx_infer_transmil_attn_ws_bytes(const mhimx_infer_transmil_cfg* cfg, int32_t n_bags, const mhimx_infer_bag* bags,
+                                                      int32_t want_pscore) {
+  using namespace mhimx;
+  if (int r = check_transmil("infer_transmil_attn", cfg, n_bags, bags, MHIMX_X_F32)) return r;
+  mhimx_infer_transmil_layout lo;
+  TmAttnWs aw;
+  transmil_layout(cfg, n_bags, bags, &lo, nullptr, nullptr);
+  transmil_attn_layout(cfg, n_bags, bags, lo, want_pscore != 0, &aw);
+  return aw.total;
+}
+
 extern "C" int mhimx_infer_transmil_layout_of(const mhimx_infer_transmil_cfg* cfg, int32_t n_bags, const mhimx_infer_bag* bags,
                                               mhimx_infer_transmil_layout* out) {
   using namespace mhimx;
-  if (int r = check_transmil(cfg, n_bags, bags, MHIMX_X_F32)) return r;
+  if (int r = check_transmil("infer_transmil", cfg, n_bags, bags, MHIMX_X_F32)) return r;
   MHIMX_CHECK_ARG(out, "infer_transmil_layout_of: null output");
   transmil_layout(cfg, n_bags, bags, out, nullptr, nullptr);
   return 0;
 }
 
-extern "C" int mhimx_infer_transmil_run(void* stream, const mhimx_infer_transmil_cfg* cfg, int32_t n_bags, const mhimx_infer_bag* bags,
-                                        const int64_t* labels_dev, float* logits, float* loss, float* z, void* ws, int64_t ws_bytes,
-                                        int32_t x_dtype) {
-  using namespace mhimx;
-  if (int r = check_transmil(cfg, n_bags, bags, x_dtype)) return r;
+namespace mhimx {
+namespace {
+// the ONE body of mhimx_infer_transmil_run (ao null: no tail) and mhimx_infer_transmil_run_attn; `who` names the entry point in the messages
+int transmil_run(const char* who, void* stream, const mhimx_infer_transmil_cfg* cfg, int32_t n_bags, const mhimx_infer_bag* bags,
+                 const int64_t* labels_dev, float* logits, float* loss, float* z, const TmAttnOut* ao, void* ws, int64_t ws_bytes, int32_t x_dtype) {
+  if (int r = check_transmil(who, cfg, n_bags, bags, x_dtype)) return r;
   bool params = cfg->w1 && cfg->b1 && cfg->cls_token && cfg->w7 && cfg->w5 && cfg->w3 && cfg->b7 && cfg->b5 && cfg->b3 && cfg->norm_w && cfg->norm_b &&
                 cfg->wp && cfg->bp;
   bool algn = aligned16(cfg->w1) && aligned16(cfg->b1) && aligned16(cfg->cls_token) && aligned16(cfg->norm_w) && aligned16(cfg->norm_b) &&
@@ -263,14 +386,20 @@ extern "C" int mhimx_infer_transmil_run(void* stream, const mhimx_infer_transmil
     params = params && t.ln_w && t.ln_b && t.w_qkv && t.w_out && t.b_out && t.conv_w;
     algn = algn && aligned16(t.ln_w) && aligned16(t.ln_b) && aligned16(t.w_qkv) && aligned16(t.w_out) && aligned16(t.b_out);
   }
-  MHIMX_CHECK_ARG(params, "infer_transmil: null parameter");
-  MHIMX_CHECK_ARG(algn, "infer_transmil: the feature, cls token, norm, to_qkv, to_out and predictor parameters must be 16-byte aligned");
-  if (int r = rg_check_infer_io("infer_transmil", n_bags, bags, logits, "the logits output is required", loss, labels_dev)) return r;
+  MHIMX_CHECK_ARG(params, "%s: null parameter", who);
+  MHIMX_CHECK_ARG(algn, "%s: the feature, cls token, norm, to_qkv, to_out and predictor parameters must be 16-byte aligned", who);
+  if (int r = rg_check_infer_io(who, n_bags, bags, logits, "the logits output is required", loss, labels_dev)) return r;
+  if (ao) {
+    MHIMX_CHECK_ARG(ao->attn, "%s: the attention output is required", who);
+    MHIMX_CHECK_ARG(aligned16(ao->attn) && aligned16(ao->pscore), "%s: the attention and pseudo-score outputs must be 16-byte aligned", who);
+  }
   mhimx_infer_transmil_layout lo;
   TmScratch sc;
+  TmAttnWs aw = {};
   NyBags tb = {};
   transmil_layout(cfg, n_bags, bags, &lo, &sc, &tb);
-  if (int r = rg_check_ws("infer_transmil", ws, ws_bytes, lo.total)) return r;
+  if (ao) transmil_attn_layout(cfg, n_bags, bags, lo, ao->pscore != nullptr, &aw);
+  if (int r = rg_check_ws(who, ws, ws_bytes, ao ? aw.total : lo.total)) return r;
   hipStream_t st = (hipStream_t)stream;
   char* base = static_cast<char*>(ws);
   auto F = [&](int64_t off) { return reinterpret_cast<float*>(base + off); };
@@ -355,5 +484,46 @@ extern "C" int mhimx_infer_transmil_run(void* stream, const mhimx_infer_transmil
   hipLaunchKernelGGL(tm_tail_kernel, dim3((unsigned)n_bags), dim3(64), 0, st, tb, F(lo.y[1]), cfg->norm_w, cfg->norm_b, cfg->wp, cfg->bp, C, labels_dev,
                      F(lo.cls), z, logits, loss);
   MHIMX_LAUNCH_CHECK();
-  return 0;
+  if (!ao) return 0;
+
+  // the attention tail: per layer u = attn1[cls] pinv, then the cls row of the streamed attention into the packed instance rows
+  const int64_t R = aw.R;
+  for (int l = 0; l < 2; ++l) {
+    float *qkv = F(lo.qkv[l]), *lm = F(lo.lm[l]), *u = F(aw.u[l]);
+    hipLaunchKernelGGL(tm_cls_u_kernel, dim3(TM_H, (unsigned)n_bags), dim3(256), 0, st, tb, qkv, lm, F(lo.z[l]), u);
+    MHIMX_LAUNCH_CHECK();
+    NyArgs ny;
+    memset(&ny, 0, sizeof(ny));
+    ny.k = qkv + TM_E; ny.ld = TM_QKV; ny.ql = lm; ny.ldl = 2 * TM_E; ny.scale = TM_SCALE; ny.sl2e = TM_SCALE * 1.4426950408889634f;
+    if (int r = nys_cls_attn_many(st, tb, ny, F(lo.lse3[l]), u, ao->attn + (int64_t)l * TM_H * R, R)) return r;
+  }
+  if (!ao->pscore) return 0;
+  // get_pseudo_score_trans on layer 1: f = v * attn per head, to_out + bias, cam = f Wp^T, max_c softmax_c(cam + bp[0])
+  float *f = F(aw.f), *fo = F(aw.g), *cam = F(aw.cam);
+  hipLaunchKernelGGL(tm_pscore_f_kernel, dim3((unsigned)cdiv(aw.rows, 4)), dim3(256), 0, st, tb, F(lo.qkv[0]) + 2 * TM_E, ao->attn, R, aw.rows, f);
+  MHIMX_LAUNCH_CHECK();
+  const mhimx_transmil_layer& t0 = cfg->layer[0];
+  mhimx_gemm_nt_args o = {};
+  o.A = f; o.lda = TM_E; o.B = t0.w_out; o.ldb = TM_E; o.C = fo; o.ldc = TM_E; o.M = aw.rows; o.N = TM_E; o.K = TM_E; o.bias = t0.b_out;
+  o.prec = MHIMX_PREC_BF16X3;
+  if (int r = gemm_nt(st, o)) return r;
+  mhimx_gemm_nt_args p = {};
+  p.A = fo; p.lda = TM_E; p.B = cfg->wp; p.ldb = TM_E; p.C = cam; p.ldc = C; p.M = aw.rows; p.N = C; p.K = TM_E; p.prec = MHIMX_PREC_BF16X3;
+  if (int r = gemm_nt(st, p)) return r;
+  return mhimx_pseudo_score(stream, nullptr, nullptr, cam, cfg->bp, ao->pscore, nullptr, R, C);
+}
+}  // namespace
+}  // namespace mhimx
+
+extern "C" int mhimx_infer_transmil_run(void* stream, const mhimx_infer_transmil_cfg* cfg, int32_t n_bags, const mhimx_infer_bag* bags,
+                                        const int64_t* labels_dev, float* logits, float* loss, float* z, void* ws, int64_t ws_bytes,
+                                        int32_t x_dtype) {
+  return mhimx::transmil_run("infer_transmil", stream, cfg, n_bags, bags, labels_dev, logits, loss, z, nullptr, ws, ws_bytes, x_dtype);
+}
+
+extern "C" int mhimx_infer_transmil_run_attn(void* stream, const mhimx_infer_transmil_cfg* cfg, int32_t n_bags, const mhimx_infer_bag* bags,
+                                             const int64_t* labels_dev, float* logits, float* loss, float* z, float* attn, float* pscore, void* ws,
+                                             int64_t ws_bytes, int32_t x_dtype) {
+  const mhimx::TmAttnOut ao = {attn, pscore};
+  return mhimx::transmil_run("infer_transmil_attn", stream, cfg, n_bags, bags, labels_dev, logits, loss, z, &ao, ws, ws_bytes, x_dtype);
 }

@@ -63,5 +63,10 @@ int ppeg_fwd_many(hipStream_t st, const NyBags& tb, const float* y, const float*
 int nys_a3v_fwd_many(hipStream_t st, const NyBags& tb, const NyArgs& base, float* a3v, float* lse3, float* ws);
 // out (+)= softmax_m(q k~^T) w2, w2 [nbags, 8, 256, 64], out rows of the token space (pitch ldo)
 int nys_out_fwd_many(hipStream_t st, const NyBags& tb, const NyArgs& base, const float* w2, float* out, int64_t ldo, int accumulate);
+// nys_flash_tok.hip.  The cls row of every bag's streamed attention, r[token] = sum_lm u[lm] softmax_n(q~ k^T)[lm, token] (mhimx_nys_cls_attn
+// per bag: min(T / 64, 64) chunks), written WITHOUT the pad columns and the cls column (r[:, pad + 1:]) into the bag's segment of the packed
+// rows: attn [8, R], head pitch R = sum N_b, bag b's rows from N_0 + .. + N_{b-1} on.  base: k / ld of the whole token space, ql / ldl of
+// bag 0's landmark means, scale; lse3, u [nbags, 8, 256]
+int nys_cls_attn_many(hipStream_t st, const NyBags& tb, const NyArgs& base, const float* lse3, const float* u, float* attn, int64_t R);
 
 }  // namespace mhimx

@@ -341,9 +341,36 @@ __global__ __launch_bounds__(NY8_THREADS) void ny_out_bwd_q8_kernel(NyArgs g) {
 // ===========================================================================================================================
 // The cls row r[token] = sum_lm u[lm] softmax_n(q~ k^T)[lm, token] (nystrom:143-150) in the token-owning form: q~ as row-major planes,
 // a wave owns 16 tokens and all 256 landmarks (S^T[16 lb] in registers), no barrier in the loop.
+// MANY: the bag-batched entry (NyBags, nys_args.hpp; one kernel template for the reason given at ny_out_fwd_tok8_kernel) - blockIdx.z = bag,
+// min(T / 64, NY_CLSCH) chunks of its own tokens, blocks beyond return; the argument block is relocated to the bag and the single-bag code
+// runs as it is up to the store: the bag's row lands in its segment of the packed instance rows (head pitch g.ldo), token pad + 1 + i at
+// entry i - the pad columns and the cls column are not written.
 // ===========================================================================================================================
-__global__ __launch_bounds__(NY8_THREADS) void ny_cls_row8_kernel(NyArgs g) {
+constexpr int NY_CLSCH = 64;                                   // 66 KB of LDS, 84 VGPRs: two workgroups per CU
+constexpr int NY_SM_CLS = 2 * NY_PLANE + 2 * NY_M * 4;
+template <bool MANY>
+__global__ __launch_bounds__(NY8_THREADS) void ny_cls_row8_kernel(NyArgs g, NyBags tb) {
   extern __shared__ __attribute__((aligned(16))) char sm[];
+  [[maybe_unused]] int first = 0;                              // MANY: the bag's first instance token (pad + 1)
+  if constexpr (MANY) {
+    int64_t tok0 = tb.tok0[0];
+    int T = tb.T[0], n = tb.n[0];
+    NY_PICK(tok0, tb.tok0, blockIdx.z) NY_PICK(T, tb.T, blockIdx.z) NY_PICK(n, tb.n, blockIdx.z)
+    const int nch = T / NY_TT < NY_CLSCH ? T / NY_TT : NY_CLSCH;
+    if ((int)blockIdx.x >= nch) return;
+    int64_t row0 = 0;                                          // instance rows of the bags in front
+#pragma unroll
+    for (int q = 0; q < MHIMX_INFER_MAX; ++q)
+      if (q < (int)blockIdx.z) row0 += tb.n[q] - 1;
+    g.T = T;
+    g.nch = nch;
+    g.k += tok0 * g.ld;
+    g.ql += (int64_t)blockIdx.z * NY_M * g.ldl;
+    g.lse3 += (int64_t)blockIdx.z * NY_H * NY_M;
+    g.u += (int64_t)blockIdx.z * NY_H * NY_M;
+    g.out += row0;
+    first = T - n + 1;
+  }
   char* q_hi = sm;
   char* q_lo = sm + NY_PLANE;
   float* lmst = reinterpret_cast<float*>(sm + 2 * NY_PLANE);   // lse3[256] | u[256]
@@ -404,7 +431,11 @@ __global__ __launch_bounds__(NY8_THREADS) void ny_cls_row8_kernel(NyArgs g) {
       __builtin_amdgcn_sched_barrier(0);
     }
     r = ny_kgsum(r);
-    if (kg == 0) g.out[(int64_t)h * g.T + tok] = r;
+    if constexpr (MANY) {
+      if (kg == 0 && tok >= first) g.out[(int64_t)h * g.ldo + (tok - first)] = r;
+    } else {
+      if (kg == 0) g.out[(int64_t)h * g.T + tok] = r;
+    }
   }
 }
 
@@ -435,12 +466,22 @@ int nytok_a3v_bwd_t(hipStream_t st, const NyArgs& g0, int mode) {
     MHIMX_LAUNCH_CHECK();
     return 0;
   }
-  constexpr int sm_cls = 2 * NY_PLANE + 2 * NY_M * 4, cls_ch = 64;
-  NyArgs gc = g0;                                            // 66 KB of LDS, 84 VGPRs: two workgroups per CU
+  NyArgs gc = g0;
   const int64_t tiles = gc.T / NY_TT;
-  gc.nch = (int)(tiles < cls_ch ? tiles : cls_ch);
-  MHIMX_ONCE_PER_DEVICE(MHIMX_HIP(hipFuncSetAttribute((const void*)ny_cls_row8_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, sm_cls)));
-  hipLaunchKernelGGL(ny_cls_row8_kernel, dim3(gc.nch, NY_H), dim3(NY8_THREADS), sm_cls, st, gc);
+  gc.nch = (int)(tiles < NY_CLSCH ? tiles : NY_CLSCH);
+  MHIMX_ONCE_PER_DEVICE(MHIMX_HIP(hipFuncSetAttribute((const void*)ny_cls_row8_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, NY_SM_CLS)));
+  hipLaunchKernelGGL(ny_cls_row8_kernel<false>, dim3(gc.nch, NY_H), dim3(NY8_THREADS), NY_SM_CLS, st, gc, NyBags{});
+  MHIMX_LAUNCH_CHECK();
+  return 0;
+}
+int nys_cls_attn_many(hipStream_t st, const NyBags& tb, const NyArgs& base, const float* lse3, const float* u, float* attn, int64_t R) {
+  using namespace nytok;
+  MHIMX_CHECK_ARG(base.k && base.ql && lse3 && u && attn && aligned16(base.k) && aligned16(base.ql) && base.ld % 4 == 0 && base.ldl % 4 == 0 && R >= 1,
+                  "nys_cls_attn_many: null / unaligned operands");
+  NyArgs g = base;
+  g.lse3 = lse3; g.u = u; g.out = attn; g.ldo = R;
+  MHIMX_ONCE_PER_DEVICE(MHIMX_HIP(hipFuncSetAttribute((const void*)ny_cls_row8_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, NY_SM_CLS)));
+  hipLaunchKernelGGL(ny_cls_row8_kernel<true>, dim3(NY_CLSCH, NY_H, (unsigned)tb.nbags), dim3(NY8_THREADS), NY_SM_CLS, st, g, tb);
   MHIMX_LAUNCH_CHECK();
   return 0;
 }

@@ -1062,7 +1062,8 @@ class MHIM(nn.Module):
             aligned=(0, 1, 2, 9, 10, 11) + tuple(13 + 6 * l + j for l in range(2) for j in range(5)), c_max=16,
             cfg=lambda m, no_norm: m._infer_transmil_cfg(),
             run=lambda cfg, xs, labels, attn, no_norm: ops.infer_transmil_many(cfg, xs, labels=labels),
-            vector=None,                                        # (one attention map per layer: return_attn takes the forward_test loop)
+            vector=None,                                        # (one attention map per layer: return_attn takes the forward_test loop;
+                                                                #  the maps of many bags: infer_cls_attn)
             last=lambda cat, rs: {}, seeds=3,                   # (the feature seed, two to_out seeds of _encode)
             row_bytes=lambda m: 26 * 1024, fixed=0),
     }
@@ -1126,6 +1127,23 @@ class MHIM(nn.Module):
         out = (logits,) + ((attns,) if return_attn else ()) + ((loss,) if labels is not None else ())
         return out[0] if len(out) == 1 else out
 
+    def _infer_admit(self, xs, labels, who, mixed_native=True):
+        """The front of the multi-bag routes -> (the bags as ``_infer_bags`` leaves them, their count, whether the baseline's native call takes
+        them, the labels as int64 [n] on the bags' device).  A half list the call refuses is widened and asked again; a list of mixed dtypes
+        too, unless ``mixed_native`` is off: then it is widened for the forward_test loop."""
+        xs = self._infer_bags(xs, keep_half=True)
+        n = len(xs)
+        native = n > 0 and self._infer_ok(xs)
+        if not native and any(x.dtype != torch.float32 for x in xs):
+            mixed = len({x.dtype for x in xs}) > 1
+            xs = [x.float() for x in xs]
+            native = (mixed_native or not mixed) and self._infer_ok(xs)
+        if labels is not None:
+            labels = labels.reshape(-1).to(device=xs[0].device, dtype=torch.int64) if n else labels
+            if labels.numel() != n:
+                raise L.MhimxError(f"{who}: {labels.numel()} labels for {n} bags")
+        return xs, n, native, labels
+
     def _infer_run(self, xs, labels, return_attn, no_norm, topk=None):
         """``infer_many``'s routes -> (logits, per-bag attention list, loss | None, top-k | None).  ``topk`` = (k, largest): the per-bag
         vectors are not handed out but ranked - on the native route one ops.topk_many per chunk, on the chunk's own attention / score
@@ -1133,17 +1151,8 @@ class MHIM(nn.Module):
         fourth result is (idx [n, k], val [n, k])."""
         return_attn = return_attn or topk is not None
         fam = self._INFER_FAMILIES[self.baseline]
-        xs = self._infer_bags(xs, keep_half=True)
-        n = len(xs)
-        native = n > 0 and self._infer_ok(xs)
-        if not native and any(x.dtype != torch.float32 for x in xs):        # (a half list the call refuses: widened, and asked again)
-            xs = [x.float() for x in xs]
-            native = self._infer_ok(xs)
+        xs, n, native, labels = self._infer_admit(xs, labels, "MHIM.infer_many")
         native = native and (fam.vector is not None or not return_attn)
-        if labels is not None:
-            labels = labels.reshape(-1).to(device=xs[0].device, dtype=torch.int64) if n else labels
-            if labels.numel() != n:
-                raise L.MhimxError(f"MHIM.infer_many: {labels.numel()} labels for {n} bags")
         tk, attns = [], []                        # (idx, val) of every ops.topk_many call, in bag order; the per-bag vectors
         if native:
             cfg, chunks, rs = fam.cfg(self, no_norm), self.infer_chunks(xs), []
@@ -1211,6 +1220,107 @@ class MHIM(nn.Module):
         if self.baseline == "selfattn":
             raise L.MhimxError("MHIM.infer_topk: TransMIL returns one attention map per layer, not one vector of N entries per bag")
         logits, _, loss, (idx, val) = self._infer_run(xs, labels, True, no_norm, topk=(k, bool(largest)))
+        self.last["infer_topk"] = (idx, val)
+        return (logits, idx, val) + ((loss,) if labels is not None else ())
+
+    # ------------------------------------------------------------------ TransMIL: attention maps and instance scores of many bags
+    def _infer_cls_run(self, xs, labels, pseudo):
+        """``infer_cls_attn``'s routes -> (logits, loss | None, packs): one pack (attn [2, 8, R], pscore [R] | None, offsets) per native
+        call, or per L.INFER_MAX bags of the forward_test loop.  Routes, chunks, ``_step`` and ``self.last`` as in ``_infer_run``."""
+        if self.baseline != "selfattn":
+            raise L.MhimxError("MHIM.infer_cls_attn: the cls token's attention maps of a TransMIL (baseline='selfattn') model; "
+                               "ABMIL and DSMIL models have infer_many(return_attn=True)")
+        fam = self._INFER_FAMILIES["selfattn"]
+        xs, n, native, labels = self._infer_admit(xs, labels, "MHIM.infer_cls_attn", mixed_native=False)
+        dev = self.feature[0].weight.device
+        packs = []
+        if native:
+            cfg, chunks, rs = fam.cfg(self, False), self.infer_chunks(xs), []
+            for lo, hi in chunks:
+                r = ops.infer_transmil_many(cfg, xs[lo:hi], labels=None if labels is None else labels[lo:hi].contiguous(), want_attn=True,
+                                            want_pscore=bool(pseudo))
+                rs.append(r)
+                packs.append((r.attn, r.pscore, list(r.offsets)))
+            self._step += fam.seeds * n           # (the stream position the forward_test loop leaves behind)
+            cat = lambda ts: ts[0] if len(ts) == 1 else torch.cat(ts)
+            logits = cat([r.logits for r in rs])
+            loss = None if labels is None else cat([r.loss for r in rs])
+            self.last = {"infer_native": True, "infer_calls": len(chunks)}
+        else:
+            lg = []
+            for lo in range(0, n, L.INFER_MAX):
+                maps, scores = [], []
+                for x in xs[lo:lo + L.INFER_MAX]:
+                    N = int(x.shape[0])
+                    head, tail = self.forward_test(x, return_attn=True, return_act=bool(pseudo))
+                    lg.append(head.reshape(1, -1))
+                    attn, v = tail if pseudo else (tail, None)
+                    maps.append(torch.stack([a[0][:, :N] for a in attn]))                          # [2, 8, N] (merge_test: the bag's own rows)
+                    if pseudo:
+                        step = self._step         # (_trans_score draws a fourth seed; both routes leave three per bag behind)
+                        scores.append(self._trans_score(v[0].permute(1, 0, 2).reshape(v.shape[2], NY.INNER)[:N], attn[0][0][:, :N]).reshape(-1))
+                        self._step = step
+                offs = [0] + list(itertools.accumulate(int(m.shape[2]) for m in maps))
+                packs.append((torch.cat(maps, 2).contiguous(), torch.cat(scores).contiguous() if pseudo else None, offs))
+            logits = torch.cat(lg) if lg else torch.empty((0, self.n_classes), device=dev)
+            loss = None if labels is None else torch.nn.functional.cross_entropy(logits, labels, reduction="none")
+            self.last = {"infer_native": False, "infer_calls": 0}
+        return logits, loss, packs
+
+    @torch.no_grad()
+    def infer_cls_attn(self, xs, labels=None, pseudo=False):
+        """The per-instance view of a TransMIL model over a LIST of bags of different row counts: ``(logits [n, C], attn, pscore | None)``
+        plus ``loss [n]`` with ``labels``.  ``attn``: per bag the cls token's attention row of both layers, a view [2, 8, N_b] (layer, head,
+        instance) - what ``forward_test(x, return_attn=True)`` returns as two [1, 8, N_b] maps; ``pscore`` (with ``pseudo``): per bag [N_b],
+        the pseudo-score the MHIM teacher ranks TransMIL instances by (``_trans_score`` of layer 1's map, attn2score).
+        An eval-mode model without merge_test takes mhimx_infer_transmil_run_attn - one C call (96 + 4 launches, + 4 with ``pseudo``) per
+        chunk of bags (``infer_chunks``); whatever that call refuses (train mode, merge_test, prec='f32', a kernel event hook, mixed dtypes, a
+        bad pitch) loops over forward_test and returns the same shapes.  ``_step`` moves three seeds per bag on both routes;
+        ``self.last["infer_native"]`` / ``["infer_calls"]`` as after ``infer_many``; ``self.last["infer_attn"] = (attn [2, 8, R], pscore [R]
+        | None, offsets)``, the bags' rows packed in bag order - what ``student_rows_many(offsets=)`` and ``ops.topk_many`` take.  Half bags
+        pass through as in ``infer_many``.  A model that is not TransMIL: MhimxError."""
+        logits, loss, packs = self._infer_cls_run(xs, labels, pseudo)
+        attns, scores, offsets = [], [], [0]
+        for a, p, offs in packs:
+            attns += [a[:, :, offs[j]:offs[j + 1]] for j in range(len(offs) - 1)]
+            if p is not None:
+                scores += [p[offs[j]:offs[j + 1]] for j in range(len(offs) - 1)]
+            offsets += [offsets[-1] + o for o in offs[1:]]
+        if len(packs) == 1:
+            packed = (packs[0][0], packs[0][1], offsets)
+        elif packs:
+            packed = (torch.cat([a for a, _, _ in packs], 2), torch.cat([p for _, p, _ in packs]) if pseudo else None, offsets)
+        else:
+            dev = self.feature[0].weight.device
+            packed = (torch.empty((2, NY.HEADS, 0), device=dev), torch.empty(0, device=dev) if pseudo else None, offsets)
+        self.last["infer_attn"] = packed
+        return (logits, attns, scores if pseudo else None) + ((loss,) if labels is not None else ())
+
+    @torch.no_grad()
+    def infer_cls_topk(self, xs, k, largest=True, by="pseudo", layer=0, labels=None):
+        """The k most (least, if not ``largest``) relevant instances of every bag of a LIST of bags for a TransMIL model: ``(logits [n, C],
+        idx, val)`` plus ``loss [n]`` with ``labels``.  ``by="pseudo"``: idx, val [n, k] rank the pseudo-score (``infer_cls_attn(pseudo=
+        True)``), one ops.topk_many per chunk; ``by="heads"``: idx, val [n, 8, k] rank every head's row of ``attn[layer]``, one
+        ops.topk_many per head and chunk - each on the chunk's own buffer with the chunk's offsets.  Tie contract and padding are
+        ``infer_topk``'s: value, then lowest index; idx = -1, val = 0 behind min(k, N_b).  Routes and bookkeeping are ``infer_cls_attn``'s;
+        ``self.last["infer_topk"] = (idx, val)``.  (``infer_topk`` itself keeps refusing TransMIL: it ranks ONE vector per bag.)"""
+        k = int(k)
+        if not 1 <= k <= L.TOPK_MAX_K:
+            raise L.MhimxError(f"MHIM.infer_cls_topk: k={k} must be in 1..{L.TOPK_MAX_K}")
+        if by not in ("pseudo", "heads") or layer not in (0, 1):
+            raise L.MhimxError(f"MHIM.infer_cls_topk: by={by!r} must be 'pseudo' or 'heads', layer={layer!r} 0 or 1")
+        logits, loss, packs = self._infer_cls_run(xs, labels, by == "pseudo")
+        tk = []
+        for a, p, offs in packs:
+            if by == "pseudo":
+                tk.append(ops.topk_many(p, offs, k, bool(largest)))
+            else:
+                heads = [ops.topk_many(a[layer, h], offs, k, bool(largest)) for h in range(NY.HEADS)]
+                tk.append((torch.stack([t[0] for t in heads], 1), torch.stack([t[1] for t in heads], 1)))
+        dev = self.feature[0].weight.device
+        shape = (0, k) if by == "pseudo" else (0, NY.HEADS, k)
+        idx = torch.cat([t[0] for t in tk]) if tk else torch.empty(shape, dtype=torch.int64, device=dev)
+        val = torch.cat([t[1] for t in tk]) if tk else torch.empty(shape, device=dev)
         self.last["infer_topk"] = (idx, val)
         return (logits, idx, val) + ((loss,) if labels is not None else ())
 

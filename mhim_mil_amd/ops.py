@@ -1120,10 +1120,10 @@ def _x_name(name, x_dtype):
     return name if x_dtype == L.X_F32 else name + "_x"
 
 
-def _infer_front(who, ws_bytes_fn, cfg, xs, labels, ws):
+def _infer_front(who, ws_bytes_fn, cfg, xs, labels, ws, ws_args=()):
     """What ops.infer_many and ops.infer_dsmil_many do before their outputs: dtype, bag and label checks, the bag table, the workspace
     (the caller's, or the one cached per device) and the bags' row offsets.  ``who`` names the wrapper in the messages; ``ws_bytes_fn``:
-    the call's workspace query.  Returns (n, x_dtype, table, ws, device, offsets)."""
+    the call's workspace query (``ws_args``: what it takes behind the bag table).  Returns (n, x_dtype, table, ws, device, offsets)."""
     n = len(xs)
     xdt = x_dtype_of(xs, who)
     for x in xs:
@@ -1133,7 +1133,7 @@ def _infer_front(who, ws_bytes_fn, cfg, xs, labels, ws):
     if labels is not None and labels.numel() != n:
         raise L.MhimxError(f"{who}: {labels.numel()} labels for {n} bags")
     bags = _infer_table(xs)
-    need = getattr(L.lib(), ws_bytes_fn)(C.byref(cfg), n, bags)
+    need = getattr(L.lib(), ws_bytes_fn)(C.byref(cfg), n, bags, *ws_args)
     if need < 0:
         L.check(int(need), ws_bytes_fn)
     dev = xs[0].device
@@ -1207,8 +1207,10 @@ def infer_dsmil_many(cfg, xs, labels=None, want_attn=False, want_B=False, want_c
 
 class InferTransmilResult:
     """Outputs of one mhimx_infer_transmil_run: logits [n, C], loss [n] or None, z [n, 512] (the cls rows after the final norm) or None;
-    ``ws`` (the uint8 workspace) and ``layout`` (L.InferTransmilLayout: byte offsets of every intermediate inside it)."""
-    __slots__ = ("logits", "loss", "z", "ws", "layout")
+    ``ws`` (the uint8 workspace) and ``layout`` (L.InferTransmilLayout: byte offsets of every intermediate inside it).  From
+    mhimx_infer_transmil_run_attn also ``attn`` [2, 8, R] (layer, head, the bags' instance rows packed in bag order: bag b's at
+    offsets[b] .. offsets[b + 1], R = offsets[-1]) and ``pscore`` [R] or None; ``offsets`` either way."""
+    __slots__ = ("logits", "loss", "z", "ws", "layout", "attn", "pscore", "offsets")
 
     def view(self, name, shape, layer=None):
         """The intermediate ``name`` of the layout (of ``layer`` 0 / 1 where it is per layer) as an fp32 view of the workspace of the
@@ -1236,19 +1238,55 @@ def infer_transmil_cfg(D, Cc, act, params, layers):
     return cfg
 
 
-def infer_transmil_many(cfg, xs, labels=None, want_z=False, ws=None):
+def infer_transmil_attn_args_ok(attn_ptr, pscore_ptr, ws_bytes, need):
+    """What mhimx_infer_transmil_run_attn asks beyond mhimx_infer_transmil_run, tensor-free: an attention output, 16-byte aligned outputs
+    (``pscore_ptr`` 0: no pseudo-score), a workspace of ``need`` = mhimx_infer_transmil_attn_ws_bytes bytes."""
+    return bool(attn_ptr != 0 and attn_ptr % 16 == 0 and pscore_ptr % 16 == 0 and ws_bytes >= need)
+
+
+def infer_transmil_attn_ws_bytes(cfg, xs, want_pscore=False):
+    """mhimx_infer_transmil_attn_ws_bytes for the bags ``xs``: host arithmetic only."""
+    return L.lib().mhimx_infer_transmil_attn_ws_bytes(C.byref(cfg), len(xs), _infer_table(xs), int(bool(want_pscore)))
+
+
+def infer_transmil_many(cfg, xs, labels=None, want_z=False, ws=None, want_attn=False, want_pscore=False, attn=None, pscore=None):
     """The eval-mode MHIM(TransMIL) forward of up to L.INFER_MAX bags of different row counts in ONE C call (mhimx_infer_transmil_run).
     cfg: L.InferTransmilCfg (its parameter tensors are kept alive by the caller); xs, labels, ws: as ``infer_many`` takes them (half bags
-    are read where they lie; the workspace cache is shared with it)."""
-    n, xdt, bags, ws, dev, _ = _infer_front("infer_transmil_many", "mhimx_infer_transmil_ws_bytes", cfg, xs, labels, ws)
+    are read where they lie; the workspace cache is shared with it).
+    ``want_attn`` / ``want_pscore`` (the pseudo-score implies the maps): mhimx_infer_transmil_run_attn instead - the same forward plus the cls
+    token's attention row of both layers, ``attn`` [2, 8, R], and the teacher's pseudo-score ``pscore`` [R] of every instance row
+    (InferTransmilResult).  ``attn`` / ``pscore``: output buffers of the caller's (fp32, contiguous, 16 R and R elements; tests put guards
+    behind them); default: fresh ones."""
+    tail = bool(want_attn or want_pscore)
+    who, query = "infer_transmil_many", "mhimx_infer_transmil_attn_ws_bytes" if tail else "mhimx_infer_transmil_ws_bytes"
+    n, xdt, bags, ws, dev, offsets = _infer_front(who, query, cfg, xs, labels, ws, (int(bool(want_pscore)),) if tail else ())
     r = InferTransmilResult()
     r.logits = torch.empty((n, int(cfg.C)), device=dev)
     r.loss = torch.empty(n, device=dev) if labels is not None else None
     r.z = torch.empty((n, 512), device=dev) if want_z else None
     r.ws, r.layout = ws, L.InferTransmilLayout()
+    r.attn, r.pscore, r.offsets = None, None, offsets
     L.check(L.lib().mhimx_infer_transmil_layout_of(C.byref(cfg), n, bags, C.byref(r.layout)), "mhimx_infer_transmil_layout_of")
-    L.check(L.lib().mhimx_infer_transmil_run(_stream(), C.byref(cfg), n, bags, _p(labels), _p(r.logits), _p(r.loss), _p(r.z), _p(ws), ws.numel(),
-                                             xdt), "mhimx_infer_transmil_run")
+    if not tail:
+        if attn is not None or pscore is not None:
+            raise L.MhimxError(f"{who}: output buffers for the attention maps without want_attn / want_pscore")
+        L.check(L.lib().mhimx_infer_transmil_run(_stream(), C.byref(cfg), n, bags, _p(labels), _p(r.logits), _p(r.loss), _p(r.z), _p(ws), ws.numel(),
+                                                 xdt), "mhimx_infer_transmil_run")
+        return r
+    R = offsets[-1]
+    if pscore is not None and not want_pscore:
+        raise L.MhimxError(f"{who}: a pseudo-score buffer without want_pscore")
+    for t, name, count in ((attn, "attn", 16 * R), (pscore, "pscore", R)):
+        _chk(t, name=name)
+        if t is not None and (t.numel() != count or t.device != dev):
+            raise L.MhimxError(f"{who}: {name} must hold {count} fp32 elements on the bags' device")
+    r.attn = torch.empty((2, 8, R), device=dev) if attn is None else attn.view(2, 8, R)
+    r.pscore = (torch.empty(R, device=dev) if pscore is None else pscore.view(R)) if want_pscore else None
+    need = L.lib().mhimx_infer_transmil_attn_ws_bytes(C.byref(cfg), n, bags, int(bool(want_pscore)))
+    if not infer_transmil_attn_args_ok(r.attn.data_ptr(), 0 if r.pscore is None else r.pscore.data_ptr(), ws.numel(), need):
+        raise L.MhimxError(f"{who}: attn / pscore must be 16-byte aligned and the workspace hold {need} bytes (got {ws.numel()})")
+    L.check(L.lib().mhimx_infer_transmil_run_attn(_stream(), C.byref(cfg), n, bags, _p(labels), _p(r.logits), _p(r.loss), _p(r.z), _p(r.attn),
+                                                  _p(r.pscore), _p(ws), ws.numel(), xdt), "mhimx_infer_transmil_run_attn")
     return r
 
 
