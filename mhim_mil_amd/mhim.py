@@ -10,6 +10,8 @@ Same constructor arguments, same methods and return conventions, same state_dict
     MHIM.forward_test     (mhim.py:229-272) forward_test     -> logits | (logits, attn)
     MHIM.pure             (mhim.py:274-298) pure             -> (logits, 0, ps, ps) | logits
     MHIM.infer_many       (forward_test over a LIST of bags of different sizes: mhimx_infer_run, one C call per chunk) -> logits [n,C], ..
+    MHIM.infer_topk / infer_cls_attn / infer_cls_topk     (the same lists: the top-k instances per bag; TransMIL's maps and pseudo-scores)
+                          - all four read the packs of ONE driver, MHIM._infer_run, over the records of MHIM._INFER_FAMILIES
 
 All math runs in libmhimx.so (hand-written gfx950 kernels behind the C-ABI); torch only owns
 parameters, device memory, the stream and autograd's graph bookkeeping.  There is no eager/CPU
@@ -24,6 +26,7 @@ from __future__ import annotations
 import itertools
 import math
 import os
+import types
 from typing import Callable, NamedTuple, Optional
 
 import numpy as np
@@ -280,18 +283,28 @@ class BagPlan:
 
 
 class _InferFamily(NamedTuple):
-    """What differs between the native multi-bag inference calls (MHIM._INFER_FAMILIES: one record per baseline)."""
+    """What differs between the multi-bag inference routes (MHIM._INFER_FAMILIES: one record per baseline, one more per view of one).
+    ``want``: the per-row buffers are asked for; ``opt``: the view's one option - ``no_norm`` of the bag vectors, ``pseudo`` of the cls
+    view."""
     params: Callable            # model -> the parameter tensors the call reads, flat; None: not the call's model (a gated scorer)
     shape_ok: Callable          # those tensors -> bool: the call's shape pins beyond the common dimension rule
     aligned: tuple              # which of them (indices) must be 16-byte aligned
     c_max: int                  # the most classes
-    cfg: Callable               # (model, no_norm) -> the call's configuration struct
-    run: Callable               # (cfg, the chunk's bags, its labels | None, return_attn, no_norm) -> the chunk's result
-    vector: Optional[Callable]  # (result, no_norm) -> the buffer of the per-bag vectors (rows at result.offsets); None: no return_attn
-    last: Callable              # (cat, the chunks' results) -> the family's own ``self.last`` entries
+    cfg: Callable               # (model, opt) -> the call's configuration struct
+    run: Callable               # (cfg, the chunk's bags, its labels | None, want, opt) -> the chunk's result (.logits, .loss, .offsets)
+    bufs: Optional[Callable]    # (result, opt) -> the call's per-row buffers, rows (last axis) at result.offsets; None: ``want`` takes the loop
+    loop: Callable              # (model, bag, want, opt) -> (the bag's result: .logits [1, C] and what ``last`` reads; its per-row buffers)
+    last: Callable              # (cat, the chunks' or the bags' results) -> the family's own ``self.last`` entries
     seeds: int                  # seeds the forward_test loop draws per bag: ``_step`` moves as far
     row_bytes: Callable         # model -> workspace bytes per row of a call ...
     fixed: int                  # ... and the share that does not grow with the rows (infer_rows_per_call)
+    mixed_native: bool = True   # a list of mixed dtypes is widened and offered to the call (off: it takes the loop)
+
+
+class _InferPack(NamedTuple):
+    """What one native call, or L.INFER_MAX bags of the forward_test loop, hands out: what MHIM._infer_run and the public methods trade in."""
+    bufs: tuple                 # the family's per-row buffers (None: not asked for): the call's own outputs in place; the loop's, concatenated
+    offsets: list               # bag b's rows: offsets[b] .. offsets[b + 1] of the last axis
 
 
 # ----------------------------------------------------------------------------------------------- model
@@ -1039,7 +1052,35 @@ class MHIM(nn.Module):
         ps, layers = self._infer_transmil_params()
         return ops.infer_transmil_cfg(self.input_dim, self.n_classes, L.act_code(self.act, _FEATURE_ACTS), ps, layers)
 
-    # One record per native family: everything _infer_ok, _infer_run and infer_rows_per_call need to know about the call behind a baseline.
+    # forward_test of ONE bag as the families' records hand it to the loop route (_InferFamily.loop)
+    def _infer_loop_bag(self, x, want, no_norm):
+        """ABMIL and plain TransMIL: the bag's vector, or whatever else forward_test calls its attention (TransMIL: a list of maps)."""
+        o = self.forward_test(x, return_attn=want, no_norm=no_norm)
+        head, tail = o if want else (o, None)
+        return types.SimpleNamespace(logits=head.reshape(1, -1)), (tail.reshape(-1) if torch.is_tensor(tail) else tail,)
+
+    def _infer_loop_dsmil(self, x, want, no_norm):
+        """DSMIL: forward_test's pair ([bag, max-instance], B | attn) becomes the MIXED logits 0.5 * bag + 0.5 * max-instance (what
+        validate_func makes of it, common_mil.py:66-67); the pair itself and B are kept for ``self.last["infer_parts"]``."""
+        (bag, ins), tail = self.forward_test(x, return_attn=want, no_norm=no_norm)
+        bag, ins = bag.reshape(1, -1), ins.reshape(1, -1)
+        return (types.SimpleNamespace(logits=0.5 * bag + 0.5 * ins, logits_bag=bag, logits_ins=ins, B=None if want else tail),
+                (tail.reshape(-1) if want else None,))
+
+    def _infer_loop_cls(self, x, want, pseudo):
+        """The cls view of TransMIL: both layers' maps cut to the bag's own rows, [2, 8, N] (merge_test scores N + k tokens), and with
+        ``pseudo`` the teacher's score of them."""
+        N = int(x.shape[0])
+        head, tail = self.forward_test(x, return_attn=True, return_act=pseudo)
+        attn, v = tail if pseudo else (tail, None)
+        maps, score = torch.stack([a[0][:, :N] for a in attn]), None
+        if pseudo:
+            step = self._step                     # (_trans_score draws a fourth seed; both routes leave three per bag behind)
+            score = self._trans_score(v[0].permute(1, 0, 2).reshape(v.shape[2], NY.INNER)[:N], attn[0][0][:, :N]).reshape(-1)
+            self._step = step
+        return types.SimpleNamespace(logits=head.reshape(1, -1)), (maps, score)
+
+    # One record per family: everything _infer_ok, _infer_run and infer_rows_per_call need to know about the routes behind a baseline.
     # (row_bytes / fixed: the call's workspace share per row and whatever the rows are - TransMIL's row is a PADDED token, and its per-bag
     # share, landmark matrices and a3v partials, about 56 MiB per bag, comes on top; DSMIL keeps h, V, Q and the classes of every row with
     # the per-chunk partials, and 4 MiB of weight images and 32 bags' last chunks.)
@@ -1048,25 +1089,32 @@ class MHIM(nn.Module):
             params=lambda m: m._infer_abmil_params(), shape_ok=lambda ps: ps[2].shape[0] == 128, aligned=(0, 1, 2), c_max=16, cfg=lambda m, no_norm: m._infer_cfg(),
             run=lambda cfg, xs, labels, attn, no_norm: ops.infer_many(cfg, xs, labels=labels, want_attn=attn and not no_norm,
                                                                       want_score=attn and no_norm),
-            vector=lambda r, no_norm: r.score if no_norm else r.attn, last=lambda cat, rs: {}, seeds=1, row_bytes=lambda m: 2060, fixed=0),
+            bufs=lambda r, no_norm: (r.score if no_norm else r.attn,), loop=_infer_loop_bag, last=lambda cat, rs: {}, seeds=1,
+            row_bytes=lambda m: 2060, fixed=0),
         "dsmil": _InferFamily(                                  # mhimx_infer_dsmil_run (csrc/infer_dsmil.hip: check_dsmil), mirrored
             params=lambda m: m._infer_dsmil_params(),
             shape_ok=lambda ps: DS.QDIM == 128 and [tuple(ps[j].shape) for j in (4, 6, 8)] == [(128, 512), (128, 128), (512, 512)],   # (q.0, q.2, v.1)
             aligned=(0, 1, 2, 4, 6, 8, 9), c_max=16, cfg=lambda m, no_norm: m._infer_dsmil_cfg(no_norm),
             run=lambda cfg, xs, labels, attn, no_norm: ops.infer_dsmil_many(cfg, xs, labels=labels, want_attn=attn, want_B=True),
-            vector=lambda r, no_norm: r.attn,                   # (the instance score)
-            last=lambda cat, rs: {"infer_parts": (cat([r.logits_bag for r in rs]), cat([r.logits_ins for r in rs]), cat([r.B for r in rs]))},
+            bufs=lambda r, no_norm: (r.attn,), loop=_infer_loop_dsmil,     # (the instance score)
+            last=lambda cat, rs: {"infer_parts": (cat([r.logits_bag for r in rs]), cat([r.logits_ins for r in rs]),
+                                                  cat([r.B for r in rs]) if rs and rs[0].B is not None else None)},   # (the loop with attn: no B)
             seeds=1, row_bytes=lambda m: 4673 + 8 * m.n_classes, fixed=4 << 20),
         "selfattn": _InferFamily(                               # mhimx_infer_transmil_run (csrc/infer_transmil.hip: check_transmil), mirrored
             params=lambda m: (lambda ps, layers: ps + layers[0] + layers[1])(*m._infer_transmil_params()), shape_ok=lambda ps: True,
             aligned=(0, 1, 2, 9, 10, 11) + tuple(13 + 6 * l + j for l in range(2) for j in range(5)), c_max=16,
-            cfg=lambda m, no_norm: m._infer_transmil_cfg(),
+            cfg=lambda m, opt: m._infer_transmil_cfg(),
             run=lambda cfg, xs, labels, attn, no_norm: ops.infer_transmil_many(cfg, xs, labels=labels),
-            vector=None,                                        # (one attention map per layer: return_attn takes the forward_test loop;
-                                                                #  the maps of many bags: infer_cls_attn)
+            bufs=None, loop=_infer_loop_bag,                    # (one attention map per layer: return_attn takes the forward_test loop;
+                                                                #  the maps of many bags: the cls view below)
             last=lambda cat, rs: {}, seeds=3,                   # (the feature seed, two to_out seeds of _encode)
             row_bytes=lambda m: 26 * 1024, fixed=0),
     }
+    # The per-instance view of TransMIL (infer_cls_attn / infer_cls_topk): the same model, shapes, chunks and seeds; its call is
+    # mhimx_infer_transmil_run_attn, its buffers the maps [2, 8, R] and (with ``pseudo``) the pseudo-score [R]
+    _INFER_FAMILIES["selfattn", "cls"] = _INFER_FAMILIES["selfattn"]._replace(
+        run=lambda cfg, xs, labels, want, pseudo: ops.infer_transmil_many(cfg, xs, labels=labels, want_attn=True, want_pscore=pseudo),
+        bufs=lambda r, pseudo: (r.attn, r.pscore), loop=_infer_loop_cls, mixed_native=False)
 
     def _infer_ok(self, xs):
         """True when the baseline's native call (_INFER_FAMILIES) takes these bags: the calls' common front, their parameter and shape rules
@@ -1123,7 +1171,9 @@ class MHIM(nn.Module):
         ``self.last["infer_native"]`` says which route ran.
         A list of fp16 bags, or of bf16 bags, that the native route takes goes in as it is (no widened copy; same bits as on the widened
         bags); a list of mixed dtypes, and every model outside the native route, gets ``x.float()`` first."""
-        logits, attns, loss, _ = self._infer_run(xs, labels, return_attn, no_norm)
+        logits, loss, packs, bags = self._infer_run(self._INFER_FAMILIES[self.baseline], "MHIM.infer_many", xs, labels, return_attn, no_norm,
+                                                    pack=False)
+        attns = [b[0] for b in bags] if bags else self._infer_views(packs, 0)      # (the loop: what forward_test gave, no packed copy)
         out = (logits,) + ((attns,) if return_attn else ()) + ((loss,) if labels is not None else ())
         return out[0] if len(out) == 1 else out
 
@@ -1144,64 +1194,61 @@ class MHIM(nn.Module):
                 raise L.MhimxError(f"{who}: {labels.numel()} labels for {n} bags")
         return xs, n, native, labels
 
-    def _infer_run(self, xs, labels, return_attn, no_norm, topk=None):
-        """``infer_many``'s routes -> (logits, per-bag attention list, loss | None, top-k | None).  ``topk`` = (k, largest): the per-bag
-        vectors are not handed out but ranked - on the native route one ops.topk_many per chunk, on the chunk's own attention / score
-        buffer with the chunk's offsets; on the forward_test loop the bags' vectors packed into one vector per L.INFER_MAX bags - and the
-        fourth result is (idx [n, k], val [n, k])."""
-        return_attn = return_attn or topk is not None
-        fam = self._INFER_FAMILIES[self.baseline]
-        xs, n, native, labels = self._infer_admit(xs, labels, "MHIM.infer_many")
-        native = native and (fam.vector is not None or not return_attn)
-        tk, attns = [], []                        # (idx, val) of every ops.topk_many call, in bag order; the per-bag vectors
+    def _infer_cat(self, ts, empty, dim=0, dtype=torch.float32):
+        """The chunks' tensors as one: a single one as it is (a native call's own buffer stays in place), none: ``empty`` (a shape) -
+        the one place that builds the results of an empty list."""
+        if len(ts) == 1:
+            return ts[0]
+        return torch.cat(ts, dim) if ts else torch.empty(empty, dtype=dtype, device=self.feature[0].weight.device)
+
+    def _infer_run(self, fam, who, xs, labels, want, opt, pack=True, each=lambda pack: None):
+        """The multi-bag driver of ``fam`` (an _InferFamily) -> (logits [n, C], loss [n] | None, packs, the loop's per-bag buffers).  With
+        ``want`` the per-row buffers come back as _InferPacks: one per native call, holding the call's own buffers, or - with ``pack`` - one
+        per L.INFER_MAX bags of the forward_test loop, built behind the loop.  ``each`` is called with every pack as soon as it exists
+        (infer_topk ranks a chunk before the next chunk's call).  ``_step`` moves ``fam.seeds`` per bag on both routes; ``self.last``:
+        ``infer_native``, ``infer_calls`` and the family's own entries."""
+        xs, n, native, labels = self._infer_admit(xs, labels, who, fam.mixed_native)
+        native = native and (fam.bufs is not None or not want)
+        cat = lambda ts: self._infer_cat(ts, (0, self.n_classes))
+        rs, packs, bags = [], [], []
         if native:
-            cfg, chunks, rs = fam.cfg(self, no_norm), self.infer_chunks(xs), []
-            for lo, hi in chunks:
-                r = fam.run(cfg, xs[lo:hi], None if labels is None else labels[lo:hi].contiguous(), return_attn, no_norm)
+            cfg = fam.cfg(self, opt)
+            for lo, hi in self.infer_chunks(xs):
+                r = fam.run(cfg, xs[lo:hi], None if labels is None else labels[lo:hi].contiguous(), want, opt)
                 rs.append(r)
-                vec = fam.vector(r, no_norm) if return_attn else None
-                if topk is not None:
-                    tk.append(ops.topk_many(vec, r.offsets, *topk))
-                elif return_attn:
-                    attns += [vec[r.offsets[j]:r.offsets[j + 1]] for j in range(hi - lo)]
+                if want:
+                    packs.append(_InferPack(fam.bufs(r, opt), r.offsets))
+                    each(packs[-1])
             self._step += fam.seeds * n           # (the stream position the forward_test loop leaves behind)
-            cat = lambda ts: ts[0] if len(ts) == 1 else torch.cat(ts)
-            logits = cat([r.logits for r in rs])
-            loss = None if labels is None else cat([r.loss for r in rs])
-            self.last = {"infer_native": True, "infer_calls": len(chunks), **fam.last(cat, rs)}
         else:
-            # DSMIL: forward_test's pair ([bag, max-instance], B | attn) becomes the MIXED logits 0.5 * bag + 0.5 * max-instance (what
-            # validate_func makes of it, common_mil.py:66-67); the pair itself and B: self.last["infer_parts"]
-            dsmil, dev = self.baseline == "dsmil", self.feature[0].weight.device
-            lg, li, Bs = [], [], []
             for x in xs:
-                o = self.forward_test(x, return_attn=return_attn, no_norm=no_norm)
-                head, tail = o if dsmil or return_attn else (o, None)
-                if dsmil:
-                    head, ins = head
-                    li.append(ins.reshape(1, -1))
-                lg.append(head.reshape(1, -1))
-                if return_attn:
-                    attns.append(tail.reshape(-1) if torch.is_tensor(tail) else tail)
-                elif dsmil:
-                    Bs.append(tail)
-            logits = torch.cat(lg) if lg else torch.empty((0, self.n_classes), device=dev)
-            parts = {}
-            if dsmil:
-                lb, li = logits, torch.cat(li) if li else torch.empty((0, self.n_classes), device=dev)
-                logits = 0.5 * lb + 0.5 * li
-                parts = {"infer_parts": (lb, li, torch.cat(Bs) if Bs else None)}
-            loss = None if labels is None else torch.nn.functional.cross_entropy(logits, labels, reduction="none")
-            self.last = {"infer_native": False, "infer_calls": 0, **parts}
-        if topk is None:
-            return logits, attns, loss, None
-        for lo in range(0, len(attns), L.INFER_MAX):            # (the forward_test loop's vectors; the native route left none)
-            part = [a.reshape(-1).float() for a in attns[lo:lo + L.INFER_MAX]]
-            tk.append(ops.topk_many(torch.cat(part).contiguous(), [0] + list(itertools.accumulate(a.numel() for a in part)), *topk))
-        dev = self.feature[0].weight.device
-        idx = torch.cat([t[0] for t in tk]) if tk else torch.empty((0, topk[0]), dtype=torch.int64, device=dev)
-        val = torch.cat([t[1] for t in tk]) if tk else torch.empty((0, topk[0]), device=dev)
-        return logits, [], loss, (idx, val)
+                r, b = fam.loop(self, x, want, opt)
+                rs.append(r)
+                bags.append(b)
+            for lo in range(0, n if want and pack else 0, L.INFER_MAX):
+                part = bags[lo:lo + L.INFER_MAX]
+                packs.append(_InferPack(tuple(None if part[0][i] is None else torch.cat([b[i].float() for b in part], -1).contiguous()
+                                              for i in range(len(part[0]))), [0] + list(itertools.accumulate(int(b[0].shape[-1]) for b in part))))
+                each(packs[-1])
+        logits = cat([r.logits for r in rs])
+        loss = None if labels is None else cat([r.loss for r in rs]) if native else torch.nn.functional.cross_entropy(logits, labels, reduction="none")
+        self.last = {"infer_native": native, "infer_calls": len(rs) if native else 0, **fam.last(cat, rs)}
+        return logits, loss, packs, bags
+
+    @staticmethod
+    def _infer_views(packs, i):
+        """Buffer ``i`` of every pack as per-bag views, in bag order."""
+        return [p.bufs[i][..., lo:hi] for p in packs for lo, hi in zip(p.offsets, p.offsets[1:])]
+
+    def _infer_ranker(self, pick, k, largest, vectors=1):
+        """The one place that ranks -> (rank, ranked).  ``rank(pack)`` makes the pack's ops.topk_many calls, one per vector of
+        ``pick(pack)`` (``vectors`` of them), on the pack's own buffer with the pack's offsets; ``ranked()``: per vector (idx [n, k],
+        val [n, k]) over the bags of every pack ranked so far."""
+        tk = []
+        rank = lambda pack: tk.append([ops.topk_many(v, pack.offsets, k, largest) for v in pick(pack)])
+        ranked = lambda: [(self._infer_cat([t[v][0] for t in tk], (0, k), dtype=torch.int64), self._infer_cat([t[v][1] for t in tk], (0, k)))
+                          for v in range(vectors)]
+        return rank, ranked
 
     @torch.no_grad()
     def infer_topk(self, xs, k, largest=True, no_norm=False, labels=None):
@@ -1219,53 +1266,17 @@ class MHIM(nn.Module):
             raise L.MhimxError("MHIM.infer_topk: merge_test scores N + k tokens, not the N rows of the bag")
         if self.baseline == "selfattn":
             raise L.MhimxError("MHIM.infer_topk: TransMIL returns one attention map per layer, not one vector of N entries per bag")
-        logits, _, loss, (idx, val) = self._infer_run(xs, labels, True, no_norm, topk=(k, bool(largest)))
-        self.last["infer_topk"] = (idx, val)
+        rank, ranked = self._infer_ranker(lambda p: p.bufs, k, bool(largest))
+        logits, loss, _, _ = self._infer_run(self._INFER_FAMILIES[self.baseline], "MHIM.infer_many", xs, labels, True, no_norm, each=rank)
+        self.last["infer_topk"] = idx, val = ranked()[0]
         return (logits, idx, val) + ((loss,) if labels is not None else ())
 
     # ------------------------------------------------------------------ TransMIL: attention maps and instance scores of many bags
-    def _infer_cls_run(self, xs, labels, pseudo):
-        """``infer_cls_attn``'s routes -> (logits, loss | None, packs): one pack (attn [2, 8, R], pscore [R] | None, offsets) per native
-        call, or per L.INFER_MAX bags of the forward_test loop.  Routes, chunks, ``_step`` and ``self.last`` as in ``_infer_run``."""
+    def _infer_cls_family(self):                                # (a model that is not TransMIL is refused before anything looks at the bags)
         if self.baseline != "selfattn":
             raise L.MhimxError("MHIM.infer_cls_attn: the cls token's attention maps of a TransMIL (baseline='selfattn') model; "
                                "ABMIL and DSMIL models have infer_many(return_attn=True)")
-        fam = self._INFER_FAMILIES["selfattn"]
-        xs, n, native, labels = self._infer_admit(xs, labels, "MHIM.infer_cls_attn", mixed_native=False)
-        dev = self.feature[0].weight.device
-        packs = []
-        if native:
-            cfg, chunks, rs = fam.cfg(self, False), self.infer_chunks(xs), []
-            for lo, hi in chunks:
-                r = ops.infer_transmil_many(cfg, xs[lo:hi], labels=None if labels is None else labels[lo:hi].contiguous(), want_attn=True,
-                                            want_pscore=bool(pseudo))
-                rs.append(r)
-                packs.append((r.attn, r.pscore, list(r.offsets)))
-            self._step += fam.seeds * n           # (the stream position the forward_test loop leaves behind)
-            cat = lambda ts: ts[0] if len(ts) == 1 else torch.cat(ts)
-            logits = cat([r.logits for r in rs])
-            loss = None if labels is None else cat([r.loss for r in rs])
-            self.last = {"infer_native": True, "infer_calls": len(chunks)}
-        else:
-            lg = []
-            for lo in range(0, n, L.INFER_MAX):
-                maps, scores = [], []
-                for x in xs[lo:lo + L.INFER_MAX]:
-                    N = int(x.shape[0])
-                    head, tail = self.forward_test(x, return_attn=True, return_act=bool(pseudo))
-                    lg.append(head.reshape(1, -1))
-                    attn, v = tail if pseudo else (tail, None)
-                    maps.append(torch.stack([a[0][:, :N] for a in attn]))                          # [2, 8, N] (merge_test: the bag's own rows)
-                    if pseudo:
-                        step = self._step         # (_trans_score draws a fourth seed; both routes leave three per bag behind)
-                        scores.append(self._trans_score(v[0].permute(1, 0, 2).reshape(v.shape[2], NY.INNER)[:N], attn[0][0][:, :N]).reshape(-1))
-                        self._step = step
-                offs = [0] + list(itertools.accumulate(int(m.shape[2]) for m in maps))
-                packs.append((torch.cat(maps, 2).contiguous(), torch.cat(scores).contiguous() if pseudo else None, offs))
-            logits = torch.cat(lg) if lg else torch.empty((0, self.n_classes), device=dev)
-            loss = None if labels is None else torch.nn.functional.cross_entropy(logits, labels, reduction="none")
-            self.last = {"infer_native": False, "infer_calls": 0}
-        return logits, loss, packs
+        return self._INFER_FAMILIES["selfattn", "cls"]
 
     @torch.no_grad()
     def infer_cls_attn(self, xs, labels=None, pseudo=False):
@@ -1279,22 +1290,12 @@ class MHIM(nn.Module):
         ``self.last["infer_native"]`` / ``["infer_calls"]`` as after ``infer_many``; ``self.last["infer_attn"] = (attn [2, 8, R], pscore [R]
         | None, offsets)``, the bags' rows packed in bag order - what ``student_rows_many(offsets=)`` and ``ops.topk_many`` take.  Half bags
         pass through as in ``infer_many``.  A model that is not TransMIL: MhimxError."""
-        logits, loss, packs = self._infer_cls_run(xs, labels, pseudo)
-        attns, scores, offsets = [], [], [0]
-        for a, p, offs in packs:
-            attns += [a[:, :, offs[j]:offs[j + 1]] for j in range(len(offs) - 1)]
-            if p is not None:
-                scores += [p[offs[j]:offs[j + 1]] for j in range(len(offs) - 1)]
-            offsets += [offsets[-1] + o for o in offs[1:]]
-        if len(packs) == 1:
-            packed = (packs[0][0], packs[0][1], offsets)
-        elif packs:
-            packed = (torch.cat([a for a, _, _ in packs], 2), torch.cat([p for _, p, _ in packs]) if pseudo else None, offsets)
-        else:
-            dev = self.feature[0].weight.device
-            packed = (torch.empty((2, NY.HEADS, 0), device=dev), torch.empty(0, device=dev) if pseudo else None, offsets)
-        self.last["infer_attn"] = packed
-        return (logits, attns, scores if pseudo else None) + ((loss,) if labels is not None else ())
+        pseudo = bool(pseudo)
+        logits, loss, packs, _ = self._infer_run(self._infer_cls_family(), "MHIM.infer_cls_attn", xs, labels, True, pseudo)
+        offsets = [0] + list(itertools.accumulate(hi - lo for p in packs for lo, hi in zip(p.offsets, p.offsets[1:])))
+        self.last["infer_attn"] = (self._infer_cat([p.bufs[0] for p in packs], (2, NY.HEADS, 0), 2),
+                                   self._infer_cat([p.bufs[1] for p in packs], (0,)) if pseudo else None, offsets)
+        return (logits, self._infer_views(packs, 0), self._infer_views(packs, 1) if pseudo else None) + ((loss,) if labels is not None else ())
 
     @torch.no_grad()
     def infer_cls_topk(self, xs, k, largest=True, by="pseudo", layer=0, labels=None):
@@ -1309,19 +1310,14 @@ class MHIM(nn.Module):
             raise L.MhimxError(f"MHIM.infer_cls_topk: k={k} must be in 1..{L.TOPK_MAX_K}")
         if by not in ("pseudo", "heads") or layer not in (0, 1):
             raise L.MhimxError(f"MHIM.infer_cls_topk: by={by!r} must be 'pseudo' or 'heads', layer={layer!r} 0 or 1")
-        logits, loss, packs = self._infer_cls_run(xs, labels, by == "pseudo")
-        tk = []
-        for a, p, offs in packs:
-            if by == "pseudo":
-                tk.append(ops.topk_many(p, offs, k, bool(largest)))
-            else:
-                heads = [ops.topk_many(a[layer, h], offs, k, bool(largest)) for h in range(NY.HEADS)]
-                tk.append((torch.stack([t[0] for t in heads], 1), torch.stack([t[1] for t in heads], 1)))
-        dev = self.feature[0].weight.device
-        shape = (0, k) if by == "pseudo" else (0, NY.HEADS, k)
-        idx = torch.cat([t[0] for t in tk]) if tk else torch.empty(shape, dtype=torch.int64, device=dev)
-        val = torch.cat([t[1] for t in tk]) if tk else torch.empty(shape, device=dev)
-        self.last["infer_topk"] = (idx, val)
+        heads = by == "heads"                                   # (eight vectors per pack: every head's row of attn[layer]; else the pseudo-score)
+        rank, ranked = self._infer_ranker((lambda p: [p.bufs[0][layer, h] for h in range(NY.HEADS)]) if heads else (lambda p: p.bufs[1:]),
+                                          k, bool(largest), NY.HEADS if heads else 1)
+        logits, loss, packs, _ = self._infer_run(self._infer_cls_family(), "MHIM.infer_cls_attn", xs, labels, True, not heads)
+        for p in packs:
+            rank(p)
+        tk = ranked()
+        self.last["infer_topk"] = idx, val = (torch.stack([t[0] for t in tk], 1), torch.stack([t[1] for t in tk], 1)) if heads else tk[0]
         return (logits, idx, val) + ((loss,) if labels is not None else ())
 
     # ------------------------------------------------------------------ TransMIL (selfattn) pieces

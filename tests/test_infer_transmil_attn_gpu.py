@@ -293,6 +293,50 @@ def test_what_the_call_refuses_returns_the_loop_s_values_in_the_same_shapes(kind
     assert idx.shape == (2, 3) and mm.last["infer_native"] is False
 
 
+# ------------------------------------------------------------------------------------------------ 11. more bags than one call takes
+@pytest.mark.parametrize("route", ["native", "loop"])
+def test_more_bags_than_one_call_takes_on_both_routes(route):
+    """33 bags of 1 / 255 / 256 / 300 rows - one more than L.INFER_MAX - through infer_cls_attn(pseudo=True) and infer_cls_topk(k=4,
+    by="pseudo"): two native calls (on the merge_test model: the forward_test loop, no call), ``_step`` moves by 99, the packed
+    ``infer_attn`` (infer_cls_attn's entry; infer_cls_topk leaves ``infer_topk`` [33, 4]) covers all 33 bags, and every per-bag view
+    equals bit for bit what the same method returns for that bag alone.  The loop route is also held to ``loop()`` of each bag bit for
+    bit, the bound of test_what_the_call_refuses_returns_the_loop_s_values_in_the_same_shapes (the merge_test model scores N + 5 tokens:
+    it is another function than the plain model's, so the two models' values are not compared)."""
+    native = route == "native"
+    sizes = tuple((1, 255, 256, 300)[j % 4] for j in range(33))
+    xs = _dev(bags_np(1700, sizes=sizes))
+    if native:
+        mm = model()
+    else:
+        sd = synth.mhim_state(SEEDS[CC][0], input_dim=D, n_classes=CC, baseline="selfattn", merge_k=5)
+        mm = build(sd, CC, merge_enable=True, merge_k=5, merge_test=True)
+        mm.merge.dropout = 0.0
+    s0 = mm._step = 50
+    lg, attn, ps = mm.infer_cls_attn(xs, pseudo=True)
+    assert mm.last["infer_native"] is native and mm.last["infer_calls"] == (2 if native else 0) and mm._step == s0 + 99
+    packed, pp, offs = mm.last["infer_attn"]
+    assert len(offs) == 34 and offs == [0] + list(np.cumsum(sizes)) and packed.shape == (2, 8, offs[-1]) and pp.shape == (offs[-1],)
+    assert lg.shape == (33, CC) and len(attn) == len(ps) == 33
+    mm._step = s0
+    tlg, idx, val = mm.infer_cls_topk(xs, 4, by="pseudo")
+    assert mm.last["infer_native"] is native and mm.last["infer_calls"] == (2 if native else 0) and mm._step == s0 + 99
+    assert idx.shape == (33, 4) and val.shape == (33, 4) and mm.last["infer_topk"][0] is idx and torch.equal(tlg, lg)
+    for j, (x, N) in enumerate(zip(xs, sizes)):
+        mm._step = s0 + 3 * j                                        # (the stream position the bag had in the list)
+        l1, a1, p1 = mm.infer_cls_attn([x], pseudo=True)
+        assert mm.last["infer_native"] is native and mm._step == s0 + 3 * j + 3
+        assert attn[j].shape == (2, 8, N) and ps[j].shape == (N,)
+        assert torch.equal(lg[j], l1[0]) and torch.equal(attn[j], a1[0]) and torch.equal(ps[j], p1[0]), (route, j)
+        assert torch.equal(packed[:, :, offs[j]:offs[j + 1]], a1[0]) and torch.equal(pp[offs[j]:offs[j + 1]], p1[0]), (route, j)
+        mm._step = s0 + 3 * j
+        _, i1, v1 = mm.infer_cls_topk([x], 4, by="pseudo")
+        assert torch.equal(idx[j], i1[0]) and torch.equal(val[j], v1[0]), (route, j)
+        if not native:
+            mm._step = s0 + 3 * j
+            l, a, p = loop(mm, x)
+            assert torch.equal(lg[j], l) and torch.equal(attn[j], a) and torch.equal(ps[j], p), (route, j)
+
+
 def test_a_dsmil_model_raises():
     from mhim_mil_amd import _lib as L
     from mhim_mil_amd.mhim import MHIM
