@@ -675,9 +675,17 @@ typedef struct {
                                                             (mhimx_rows_dpre_image_k: rows that did not take part are zero rows), rows = NULL,
                                                             L = n_bag_rows, and both operands reach LDS by linear DMA: no register path, no
                                                             split in the loop (the four E-side tiles of a k-step no longer split X four times) */
+  int32_t form;                                          /* which product kernel: 0 = automatic; 1 = 128 x 256 tiles, one workgroup per CU;
+                                                            2 = 128 x 128 tiles, two workgroups per CU (one bag, no ximg, D % 128 == 0 is
+                                                            enough).  The same slabs, k order and term order: every slab float has the same
+                                                            bits in either form.  Automatic: 2 where it applies and all its workgroups
+                                                            are resident at once (tiles x slabs <= 512), or D % 256 == 128             */
 } mhimx_bag_wgrad_args;
 int64_t mhimx_wgrad_ws_floats(int64_t L, int64_t E, int64_t D);
 int mhimx_bag_wgrad(void* stream, const mhimx_bag_wgrad_args* a);
+/* the product kernel a launch of n_bags bags with these arguments takes (1 or 2: mhimx_bag_wgrad_args.form), < 0 if none takes them.
+ * Host-side only: reads the shape fields, ximg and form. */
+int32_t mhimx_bag_wgrad_form(const mhimx_bag_wgrad_args* a, int32_t n_bags);
 /* The same product SUMMED over the n_bags <= 8 bags of an accumulation window (base_engine.py:100-119: the gradients of the window's bags
  * add up before the one optimiser step) in ONE launch: dW (+)= sum_b dPRE_b^T X_b.  Every bag brings its image, bag and row ids and owns
  * its slabs of k-steps; the slab sum (and everything a launch pays once: row tables, first tiles, 34 MB of slab traffic) happens once per
@@ -837,6 +845,7 @@ typedef struct {
                                                        backward  scorer-weight-gradient product, Merge parameter-gradient tail, queued reductions
                                                                  ||  Merge rows backward -> dPRE image -> projection weight gradient.
                                                      Same kernels on the same data: the results have the bits of the chain.  NULL: one stream, the chain. */
+  int32_t wgrad_form;                             /* mhimx_bag_wgrad_args.form of the single-bag steps' weight-gradient launch (0: automatic)  */
 } mhimx_step_cfg;
 /* row counts of one step (masking.py:30-35,61 and merge.py:163 in float64, as the reference computes them):
  * k_top = ceil(N r), r = mask_ratio_h / mask_ratio_hr (r > 1: r = 1, hr = mask_ratio_h); n_sel = ceil(k_top hr) if hr < 1 else k_top;

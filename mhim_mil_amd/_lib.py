@@ -58,7 +58,7 @@ class BagProject(C.Structure):
 class BagWgrad(C.Structure):
     _fields_ = [("img", C.c_void_p), ("X", c_f32p), ("ldx", C.c_int64), ("n_bag_rows", C.c_int64), ("rows", C.c_void_p),
                 ("L", C.c_int64), ("E", C.c_int64), ("D", C.c_int64), ("C", c_f32p), ("ldc", C.c_int64), ("accumulate", C.c_int32),
-                ("ws", c_f32p), ("ws_floats", C.c_int64), ("defer", C.c_void_p), ("ride_tail", C.c_int32), ("ximg", C.c_void_p)]
+                ("ws", c_f32p), ("ws_floats", C.c_int64), ("defer", C.c_void_p), ("ride_tail", C.c_int32), ("ximg", C.c_void_p), ("form", C.c_int32)]
 
 
 class PpegBand(C.Structure):
@@ -196,7 +196,7 @@ class StepCfg(C.Structure):
                 ("n_train", C.c_int64), ("n_all", C.c_int64),
                 ("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float), ("weight_decay", C.c_float), ("ema_mm", C.c_float),
                 ("mm_table", C.c_void_p), ("mm_len", C.c_int64), ("lr_table", C.c_void_p), ("lr_len", C.c_int64),
-                ("tick", C.c_void_p), ("opt_step", C.c_void_p), ("q_out", C.c_void_p), ("time_project", C.c_int32), ("side_stream", C.c_void_p)]
+                ("tick", C.c_void_p), ("opt_step", C.c_void_p), ("q_out", C.c_void_p), ("time_project", C.c_int32), ("side_stream", C.c_void_p), ("wgrad_form", C.c_int32)]
 
 
 class StepCounts(C.Structure):
@@ -442,6 +442,7 @@ SYMBOLS = {
     "mhimx_wgrad_image_bytes": (_I64, [_I64, _I64]),
     "mhimx_wgrad_ws_floats": (_I64, [_I64, _I64, _I64]),
     "mhimx_bag_wgrad": (C.c_int, [_P, _P]),
+    "mhimx_bag_wgrad_form": (_I32, [_P, _I32]),
     "mhimx_bag_wgrad_multi": (C.c_int, [_P, _P, _I32]),
     "mhimx_wgrad_multi_ws_floats": (C.c_int64, [_I64, _I64, _I64, _I32]),
     "mhimx_reduce_flush": (C.c_int, [_P, _P]),

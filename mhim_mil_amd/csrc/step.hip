@@ -503,7 +503,7 @@ extern "C" int mhimx_step_run(void* stream, const mhimx_step_cfg* cfg, const flo
     mhimx_bag_wgrad_args g = {};
     g.img = cv.at<char>(b.img); g.X = X; g.ldx = ldx; g.n_bag_rows = N; g.rows = fuse_img ? cv.at<int64_t>(b.rows_img) : rows_all; g.L = b.L_img; g.E = E; g.D = D;
     g.C = c.grad.w1; g.ldc = D;
-    g.accumulate = 0; g.ws = cv.at<float>(b.wg_ws); g.ws_floats = b.wg_ws_floats; g.defer = lm; g.ride_tail = update ? 1 : 0;
+    g.accumulate = 0; g.ws = cv.at<float>(b.wg_ws); g.ws_floats = b.wg_ws_floats; g.defer = lm; g.ride_tail = update ? 1 : 0; g.form = c.wgrad_form;
     if (int r = mhimx_bag_wgrad(stream, &g)) return r;
   }
   if (dag)
@@ -945,7 +945,7 @@ extern "C" int mhimx_pure_step_run(void* stream, const mhimx_step_cfg* cfg, cons
     mhimx_bag_wgrad_args g = {};
     g.img = cv.at<char>(b.img); g.X = X; g.ldx = ldx; g.n_bag_rows = N; g.rows = nullptr; g.L = N; g.E = E; g.D = D;
     g.C = c.grad.w1; g.ldc = D;
-    g.accumulate = 0; g.ws = cv.at<float>(b.wg_ws); g.ws_floats = b.wg_ws_floats; g.defer = &lst; g.ride_tail = update ? 1 : 0;
+    g.accumulate = 0; g.ws = cv.at<float>(b.wg_ws); g.ws_floats = b.wg_ws_floats; g.defer = &lst; g.ride_tail = update ? 1 : 0; g.form = c.wgrad_form;
     if (int r = mhimx_bag_wgrad(stream, &g)) return r;
   }
   if (!update) return mhimx_reduce_flush(stream, &lst);

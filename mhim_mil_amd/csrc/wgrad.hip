@@ -21,6 +21,8 @@
 //     (144 KB per CU: at ~2 us of loaded-memory latency less starves the ~70 KB/us a CU can ingest).
 //   * 16 reduction slabs x 16 output tiles = 256 workgroups (one per CU); the tiles of a slab run on ONE XCD (its X rows and dPRE
 //     tiles are shared through that L2); the slab sum is a job of the step's deferred reduction launch, as before.
+//   * a launch whose workgroups are all resident at once (the 10 000-row step) runs the same slabs as 128 x 128 tiles, two workgroups
+//     per CU (bag_wgrad_ws2_kernel, mhimx_bag_wgrad_args.form): the same bits, 45.7 -> 41.5 us.
 #include <string.h>
 
 #include "mma_tile.hpp"
@@ -391,6 +393,217 @@ __global__ __launch_bounds__(WTHREADS) void bag_wgrad_ws_kernel(WgradArgs g, Wgr
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
+// The same product with TWO workgroups per CU (mhimx_bag_wgrad_args.form 2).  With one 144 KB workgroup per CU every CU fills, multiplies
+// and stores in the same phase as every other: its matrix pipe has no second wave during fill and drain.  Here the workgroup tile is
+// 128 (E) x 128 (D) - the D-side stage is the X stage at half the width, byte for byte the layout of the image tile - and the ring two
+// stages of each operand (64 KiB) plus the row table, so that two workgroups share a CU and one's fill and drain run under the other's
+// loop.  4 producer waves as above (at half the width a register set holds 16 instead of 32 registers); 4 consumer waves as 2 x 2 of
+// 64 x 64: 16 accumulator tiles, 12 fragment reads and 48 MFMAs per k-step in three units (lo*hi, hi*hi, hi*lo - the order of the kernel
+// above, per k-step and per output element, so every slab float has its bits).  One s_barrier per k-step: it publishes tile t+1 and
+// retires tile t-1; a consumer cannot read ahead across it, its SIMD's wave of the other workgroup multiplies meanwhile.
+// The image tile comes by LDS-DMA, requested at the start of the phase that ends with its publication.  MEASURED (profiles/
+// wgrad_two_per_cu.md): the launch 45.7 -> 41.5 us in the step; the image tile through the producers' registers instead (requested three
+// k-steps ahead, nothing to wait for inside the phase) measured the same, so the look-ahead is not what paces the loop - a workgroup's loop
+// takes 2 x its MFMA time with its neighbour beside it, the CU's L2 -> LDS stream (64 KB per 128 x 256 x 32 products, 48 KB above) does.
+// ---------------------------------------------------------------------------------------------------------------------------
+constexpr int W2BN = 128, W2B_BYTES = W2BN * 128;                                                 // 16 KiB per k-step
+constexpr int S2NA = 2, S2NB = 2, S2RING = S2NA * WA_BYTES + S2NB * W2B_BYTES;                    // 64 KiB
+constexpr int W2_MAX_LDS = 81920;                                                                 // half of a CU's LDS
+static_assert(S2RING + W_MAX_CHUNK * 4 <= W2_MAX_LDS, "ring + the largest row table must leave room for a second workgroup");
+static_assert(M2_SIDE_LDS * 4 <= S2RING && 32 * 33 * 4 <= S2RING, "the riders' LDS must fit the smaller launch");
+
+MHIMX_DEV void ws2_unit(const f32x4 (&a)[4], const f32x4 (&b)[4], f32x4 (&acc)[4][4]) {
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[i][j] = mt_mfma(a[i], b[j], acc[i][j]);
+}
+
+__global__ __launch_bounds__(WTHREADS, 2) void bag_wgrad_ws2_kernel(WgradArgs g, int side_blocks, Merge2Side side, WgradTail tail) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  if (wg_rider_block(smem, side_blocks, side, tail)) return;
+  const unsigned bx = blockIdx.x - (unsigned)side_blocks;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+#ifdef WG_PROF
+  const uint64_t wp_t0 = __builtin_readcyclecounter();
+  const uint64_t wp_rt0 = wall_clock64();
+#endif
+  const int nJ = (int)(g.D / W2BN), nIT = (int)(g.E / WBI), nT = nIT * nJ;
+  const int xcd = bx & 7, sidx = bx >> 3;
+  const int slab = (sidx / nT) * 8 + xcd, tile = sidx % nT;     // the tiles of a slab on one XCD (c2: 64 slots = 2 slabs x 32 tiles)
+  if (slab >= g.splits) return;
+  const int itile = tile / nJ;
+  const int64_t i0 = (int64_t)itile * WBI, n0 = (int64_t)(tile % nJ) * W2BN;
+  const int ks0 = slab * g.kps;
+  const int nk = (ks0 + g.kps < g.ksteps ? ks0 + g.kps : g.ksteps) - ks0;
+  unsigned* rowtab = reinterpret_cast<unsigned*>(smem + S2RING);
+  for (int q = tid; q < nk * WBK; q += WTHREADS) {
+    int64_t l = (int64_t)ks0 * WBK + q;
+    if (l >= g.L) l = g.L - 1;
+    rowtab[q] = (unsigned)((g.rows ? g.rows[l] : l) * g.ldx * 4);
+  }
+  __syncthreads();
+  const unsigned lds0 = (unsigned)(uintptr_t)(lptr_f)smem;
+
+  if (wave < 4) {
+    // =========================================================== producers: wave = row octet of the k-step
+    const int oct = wave, half = lane >> 5, c = lane & 31;
+    const unsigned colb = (unsigned)((n0 + 4 * c) * 4);
+    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+    struct XSet { f32x4 v[4]; };                               // the lane's four rows of X
+    const float* const gX = g.X;
+    const char* const gA = g.img + ((int64_t)ks0 * nIT + itile) * WA_BYTES;      // this slab's first tile of this workgroup's tile row
+    const unsigned astep = (unsigned)(nIT * WA_BYTES), apiece = (unsigned)((wave * 64 + lane) * 16);
+    auto row_offsets = [&](int t) {
+      return *reinterpret_cast<const u32x4*>(reinterpret_cast<const char*>(rowtab) + (oct * 8 + half * 4) * 4 + (t < nk ? t : nk - 1) * 128);
+    };
+    auto load_x_async = [&](int t, XSet& r) {                  // X(t) (past the end: the last k-step's rows again)
+      const u32x4 ro = row_offsets(t);
+      asm volatile("global_load_dwordx4 %0, %4, %8\n\tglobal_load_dwordx4 %1, %5, %8\n\tglobal_load_dwordx4 %2, %6, %8\n\t"
+                   "global_load_dwordx4 %3, %7, %8"
+                   : "=&v"(r.v[0]), "=&v"(r.v[1]), "=&v"(r.v[2]), "=&v"(r.v[3])
+                   : "v"(ro[0] + colb), "v"(ro[1] + colb), "v"(ro[2] + colb), "v"(ro[3] + colb), "s"(gX)
+                   : "memory");
+    };
+    const unsigned xs0 = (unsigned)(S2NA * WA_BYTES + ((oct * 2) * 128 + (2 * half) * 32 + c) * 16);
+    auto store_x = [&](int t, XSet& r) {
+      char* sb = smem + (t % S2NB) * W2B_BYTES + xs0;
+      float a[4][4];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        a[q][0] = r.v[q][0]; a[q][1] = r.v[q][1]; a[q][2] = r.v[q][2]; a[q][3] = r.v[q][3];
+        wg_swap(a[q][0], a[q][2]);
+        wg_swap(a[q][1], a[q][3]);
+      }
+#pragma unroll
+      for (int sx = 0; sx < 2; ++sx) {
+        const float kv[8] = {a[0][sx], a[1][sx], a[2][sx], a[3][sx], a[0][sx + 2], a[1][sx + 2], a[2][sx + 2], a[3][sx + 2]};
+        f32x4 hi, lo;
+        wg_split8(kv, hi, lo);
+        *reinterpret_cast<f32x4*>(sb + sx * 512) = hi;
+        *reinterpret_cast<f32x4*>(sb + sx * 512 + 2048) = lo;
+      }
+    };
+    auto issue_a = [&](int t, bool live) {                     // 16 KiB by 256 threads: four 4 KiB pieces
+      char* sa = smem + (t % S2NA) * WA_BYTES + wave * 1024;
+      const char* src = live ? gA + (int64_t)t * astep + apiece : g.img;
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        __builtin_amdgcn_global_load_lds((gptr_f)(live ? src + j * 4096 : src), (lptr_f)(sa + j * 4096), 16, 0, 0);
+    };
+    XSet s0, s1, s2;
+    issue_a(0, true);
+    {                                                         // tile 0 with the compiler's own loads and waits
+      const char* xb = reinterpret_cast<const char*>(gX);
+      const u32x4 ro = row_offsets(0);
+      XSet r0;
+#pragma unroll
+      for (int q = 0; q < 4; ++q) r0.v[q] = *reinterpret_cast<const f32x4*>(xb + ro[q] + colb);
+      store_x(0, r0);
+    }
+    // in the loop's own order from here on: {4 image pieces, 4 X loads} per tile
+    load_x_async(1, s1);
+    issue_a(1, false);                                        // (four dummy pieces into the stage nobody reads yet: keeps the loop's VMEM count)
+    load_x_async(2, s2);
+    asm volatile("s_waitcnt vmcnt(12) lgkmcnt(0)" ::: "memory");      // image tile 0 has landed, my X(0) stores are done
+    __builtin_amdgcn_s_barrier();                             // #0: tile 0 is in LDS
+#define WS2_SET(s) "+v"(s.v[0]), "+v"(s.v[1]), "+v"(s.v[2]), "+v"(s.v[3])
+    auto body = [&](int t, XSet& r_load, XSet& r_use) {       // phase t: the consumers multiply tile t, tile t+1 goes into the stage of tile t-1
+      issue_a(t + 1, t + 1 < nk);
+      load_x_async(t + 3, r_load);
+      // X(t+1) has landed: behind it {image pieces of t, X(t+2), image pieces of t+1, X(t+3)}
+      asm volatile("s_waitcnt vmcnt(16)" : WS2_SET(r_use) : : "memory");
+      if (t + 1 < nk) store_x(t + 1, r_use);
+      asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)" ::: "memory");       // image tile t+1 landed, my X(t+1) stores are done
+      __builtin_amdgcn_s_barrier();                           // #t+1
+    };
+#ifdef WG_PROF
+    const uint64_t wp_t1 = __builtin_readcyclecounter();
+#endif
+    int t = 0;
+#pragma unroll 1
+    for (; t + 2 < nk; t += 3) {
+      body(t, s0, s1);                                        // X(t+3) -> s0, X(t+1) from s1
+      body(t + 1, s1, s2);
+      body(t + 2, s2, s0);
+    }
+    if (t < nk) body(t, s0, s1);
+    if (t + 1 < nk) body(t + 1, s1, s2);
+    // EVERY register of the three sets is named: the last (clamped, unused) prefetches are still in flight here (see the kernel above)
+    asm volatile("s_waitcnt vmcnt(0)" : WS2_SET(s0), WS2_SET(s1), WS2_SET(s2) : : "memory");
+#undef WS2_SET
+#ifdef WG_PROF
+    if (bx == 0 && lane == 0) {
+      const uint64_t wp_t2 = __builtin_readcyclecounter();
+      float* pr = reinterpret_cast<float*>(const_cast<char*>(g.img) + (int64_t)g.ksteps * nIT * WA_BYTES) + wave * 4;
+      pr[0] = (float)(wp_t1 - wp_t0); pr[1] = (float)(wp_t2 - wp_t1); pr[2] = 0.f; pr[3] = (float)nk;
+    }
+#endif
+    return;
+  }
+
+  // =============================================================== consumers: 2 x 2 waves of 64 (E) x 64 (D)
+  const int cw = wave - 4, wm = cw >> 1, wn = cw & 1;
+  const int r16 = lane & 15, kg = lane >> 4;
+  const unsigned fa_hi = lds0 + ((kg * 2) * 128 + 16 * wm + r16) * 16, fa_lo = fa_hi + 2048;
+  const unsigned fb_hi = lds0 + S2NA * WA_BYTES + ((kg * 2) * 128 + 16 * wn + r16) * 16, fb_lo = fb_hi + 2048;
+  f32x4 acc[4][4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  // three fragment slots of four blocks:  P <- A lo, Q <- B hi, R <- A hi | u1 P x Q (lo*hi) | P <- B lo | u2 R x Q (hi*hi) | u3 R x P (hi*lo)
+  f32x4 P[4], Q[4], R[4];
+  __builtin_amdgcn_s_barrier();                               // #0
+#ifdef WG_PROF
+  const uint64_t wp_t1 = __builtin_readcyclecounter();
+#endif
+#pragma unroll 1
+  for (int t = 0; t < nk; ++t) {
+    const unsigned ca = (unsigned)((t % S2NA) * WA_BYTES), cb = (unsigned)((t % S2NB) * W2B_BYTES);
+    WS_READ4A(P, fa_lo + ca);
+    WS_READ4A(Q, fb_hi + cb);
+    WS_READ4A(R, fa_hi + ca);
+    WS_WAIT8(4, P, Q);
+    __builtin_amdgcn_sched_barrier(0);
+    ws2_unit(P, Q, acc);                                      // u1  lo*hi
+    __builtin_amdgcn_sched_barrier(0);
+    WS_READ4A(P, fb_lo + cb);
+    WS_WAIT8(4, R, Q);
+    __builtin_amdgcn_sched_barrier(0);
+    ws2_unit(R, Q, acc);                                      // u2  hi*hi
+    __builtin_amdgcn_sched_barrier(0);
+    WS_WAIT8(0, R, P);
+    __builtin_amdgcn_sched_barrier(0);
+    ws2_unit(R, P, acc);                                      // u3  hi*lo
+    __builtin_amdgcn_sched_barrier(0);
+    __builtin_amdgcn_s_barrier();                             // #t+1: tile t is retired, tile t+1 published
+  }
+#ifdef WG_PROF
+  const uint64_t wp_t2 = __builtin_readcyclecounter();
+#endif
+  // epilogue: block (ja, jb) of a lane is row 4 (16 wm + 4 kg + e) + ja, column 4 (16 wn + r16) + jb
+  float* out = g.out + (int64_t)slab * g.E * g.D;
+#pragma unroll
+  for (int ja = 0; ja < 4; ++ja)
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const int64_t i = i0 + 4 * (16 * wm + 4 * kg + e) + ja;
+      const int64_t n = n0 + 4 * (16 * wn + r16);
+      *reinterpret_cast<f32x4*>(out + i * g.D + n) = f32x4{acc[ja][0][e], acc[ja][1][e], acc[ja][2][e], acc[ja][3][e]};
+    }
+#ifdef WG_PROF
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  if (bx == 0 && lane == 0) {
+    const uint64_t wp_t3 = __builtin_readcyclecounter();
+    float* pr = reinterpret_cast<float*>(const_cast<char*>(g.img) + (int64_t)g.ksteps * nIT * WA_BYTES) + wave * 4;
+    pr[0] = (float)(wp_t1 - wp_t0); pr[1] = (float)(wp_t2 - wp_t1); pr[2] = (float)(wp_t3 - wp_t2); pr[3] = (float)nk;
+    if (wave == 4) { pr[32 - 16] = (float)(wall_clock64() - wp_rt0); pr[33 - 16] = (float)(wp_t3 - wp_t0); }
+  }
+#endif
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
 // BOTH operands as images (round 4).  The kernel above reads X raw and splits it on its way into LDS: four E-side tiles do that work for
 // every X element, and it is half of the loop (stamped: the consumers alone and the producers alone take the same time).  Here the bag
 // has been laid down ONCE as the D-side operand image (prep job kind 9: per 32-row k-step and 256-column block one 32 KiB tile, byte for
@@ -543,8 +756,9 @@ __global__ __launch_bounds__(256) void rows_dpre_image_kernel(const float* __res
   }
 }
 
-static bool wgrad_shape_ok(int64_t L, int64_t E, int64_t D, int64_t ldx, int64_t n_bag_rows) {
-  return L >= 1 && E >= WBI && E % WBI == 0 && D >= WBN && D % WBN == 0 && ldx % 4 == 0 && ldx >= D &&
+// bn: the D-side width of the workgroup tile (WBN; W2BN for the two-per-CU form)
+static bool wgrad_shape_ok(int64_t L, int64_t E, int64_t D, int64_t ldx, int64_t n_bag_rows, int bn = WBN) {
+  return L >= 1 && E >= WBI && E % WBI == 0 && D >= bn && D % bn == 0 && ldx % 4 == 0 && ldx >= D &&
          n_bag_rows * ldx * 4 < ((int64_t)1 << 32);
 }
 
@@ -560,7 +774,7 @@ extern "C" int64_t mhimx_wgrad_image_bytes(int64_t L, int64_t E) { return cdiv(L
 // column tiles re-reading the image the launch moves ~1.6 GB through L2 and is bound there, not by how its workgroups fill the CUs.)
 static int wgrad_plan(int64_t L, int64_t E, int64_t D, int* kps_out) {
   const int ksteps = (int)cdiv(L, WBK);
-  const int64_t tiles = (E / WBI) * (D / WBN);
+  const int64_t tiles = (E / WBI) * cdiv(D, WBN);             // (a D the two-per-CU form alone takes - D % 256 == 128 - plans as D + 128)
   int64_t want = cdiv(256, tiles);                            // one workgroup per CU
   if (want > cdiv(ksteps, 4)) want = cdiv(ksteps, 4);         // at least 4 k-steps each
   if (want < 1) want = 1;
@@ -630,11 +844,31 @@ extern "C" int64_t mhimx_wgrad_multi_ws_floats(int64_t L, int64_t E, int64_t D, 
   return (int64_t)wgrad_plan_multi(L, E, D, n_bags, &kps) * n_bags * E * D;
 }
 
+// the two-per-CU form (bag_wgrad_ws2_kernel): one bag, X raw, whole 128 x 128 tiles (its row table always fits: W2_MAX_LDS).  The launch of
+// an accumulation window's bags, the both-images kernel and form 1 stay on the kernels above.  Automatic takes it where ALL its workgroups
+// are resident at once (tiles x slabs <= 2 x 256 CUs: the benchmarked step's 32 x 16) - that is where one workgroup's fill and drain run
+// under its neighbour's loop.  A launch of several rounds is bound by what it moves through L2 (wgrad_plan's note), and this form moves a
+// third more: MEASURED, the sharded 200 000-row step (48 tiles x 64 slabs) 1.6 % slower with it, the 10 000-row step 1.4 % faster.
+static bool wgrad_two_per_cu(const mhimx_bag_wgrad_args* a, int n_bags) {
+  if (a->form == 1 || n_bags != 1 || a->ximg || !wgrad_shape_ok(a->L, a->E, a->D, a->ldx, a->n_bag_rows, W2BN)) return false;
+  if (a->form == 2 || !wgrad_shape_ok(a->L, a->E, a->D, a->ldx, a->n_bag_rows)) return true;      // forced, or D % 256 == 128: this form alone
+  int kps;
+  return (a->E / WBI) * (a->D / W2BN) * wgrad_plan(a->L, a->E, a->D, &kps) <= 2 * 256;
+}
+extern "C" int32_t mhimx_bag_wgrad_form(const mhimx_bag_wgrad_args* a, int32_t n_bags) {
+  if (!a || n_bags < 1 || n_bags > W_MAX_BAGS || a->form < 0 || a->form > 2) return -1;
+  if (wgrad_two_per_cu(a, n_bags)) return 2;
+  return a->form != 2 && wgrad_shape_ok(a->L, a->E, a->D, a->ldx, a->n_bag_rows) ? 1 : -1;
+}
+
 static int bag_wgrad_impl(void* stream, const mhimx_bag_wgrad_args* bags, int n_bags) {
   const mhimx_bag_wgrad_args* a = bags;
   MHIMX_CHECK_ARG(a->img && a->X && a->C && a->ws && aligned16(a->img) && aligned16(a->X) && aligned16(a->C) && aligned16(a->ws) && a->ldc % 4 == 0,
                   "bag_wgrad: null / unaligned operand");
-  MHIMX_CHECK_ARG(wgrad_shape_ok(a->L, a->E, a->D, a->ldx, a->n_bag_rows),
+  MHIMX_CHECK_ARG(a->form >= 0 && a->form <= 2, "bag_wgrad: form is 0 (automatic), 1 (one workgroup per CU) or 2 (two per CU)");
+  const bool two = wgrad_two_per_cu(a, n_bags);
+  MHIMX_CHECK_ARG(a->form != 2 || two, "bag_wgrad: form 2 takes one bag without ximg, E %% 128 == 0, D %% 128 == 0, 16-byte aligned rows, a bag below 4 GiB");
+  MHIMX_CHECK_ARG(two || wgrad_shape_ok(a->L, a->E, a->D, a->ldx, a->n_bag_rows),
                   "bag_wgrad: needs E %% 128 == 0, D %% 256 == 0, 16-byte aligned rows and a bag below 4 GiB");
   WgradArgs g;
   g.img = (const char*)a->img; g.X = a->X; g.ldx = a->ldx; g.rows = a->rows; g.L = a->L; g.E = a->E; g.D = a->D;
@@ -656,7 +890,7 @@ static int bag_wgrad_impl(void* stream, const mhimx_bag_wgrad_args* bags, int n_
   }
   MHIMX_CHECK_ARG(a->ws_floats >= (int64_t)g.splits * a->E * a->D, "bag_wgrad: workspace too small (%lld floats)", (long long)((int64_t)g.splits * a->E * a->D));
   g.out = a->ws;
-  const size_t smem = SRING + (size_t)g.kps * WBK * 4;
+  const size_t smem = (two ? S2RING : SRING) + (size_t)g.kps * WBK * 4;
   Merge2Side side = {};
   int side_blocks = 0;
   mhimx_reduce_list* defer = a->defer;
@@ -666,7 +900,7 @@ static int bag_wgrad_impl(void* stream, const mhimx_bag_wgrad_args* bags, int n_
     if (side_blocks % 8 == 0) defer->side.pending = 3;
     else side_blocks = 0;
   }
-  const int64_t tiles = (a->E / WBI) * (a->D / WBN);
+  const int64_t tiles = (a->E / WBI) * (a->D / (two ? W2BN : WBN));
   dim3 grid((unsigned)(8 * tiles * cdiv(g.splits, 8) + side_blocks));
   WgradTail tail = {};
   MHIMX_CHECK_ARG(!a->ximg || (n_bags == 1 && !a->rows && aligned16(a->ximg) && a->L == a->n_bag_rows),
@@ -695,6 +929,9 @@ static int bag_wgrad_impl(void* stream, const mhimx_bag_wgrad_args* bags, int n_
   if (a->ximg) {                                               // both operands as images: nothing but linear DMA and fragments in the loop
     MHIMX_ONCE_PER_DEVICE(MHIMX_HIP(hipFuncSetAttribute((const void*)bag_wgrad_dma_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, DRING)));
     hipLaunchKernelGGL(bag_wgrad_dma_kernel, grid, dim3(WTHREADS), DRING, (hipStream_t)stream, g, (const char*)a->ximg, side_blocks, side, tail);
+  } else if (two) {
+    MHIMX_ONCE_PER_DEVICE(MHIMX_HIP(hipFuncSetAttribute((const void*)bag_wgrad_ws2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, W2_MAX_LDS)));
+    hipLaunchKernelGGL(bag_wgrad_ws2_kernel, grid, dim3(WTHREADS), smem, (hipStream_t)stream, g, side_blocks, side, tail);
   } else {
     MHIMX_ONCE_PER_DEVICE(MHIMX_HIP(hipFuncSetAttribute((const void*)bag_wgrad_ws_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, SRING + W_MAX_CHUNK * 4)));
     hipLaunchKernelGGL(bag_wgrad_ws_kernel, grid, dim3(WTHREADS), smem, (hipStream_t)stream, g, mb, side_blocks, side, tail);

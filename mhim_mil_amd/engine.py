@@ -545,6 +545,7 @@ class FusedTrainer:
         # library itself - a bag costs one ctypes call instead of ~1700 interpreter calls (the eager step was host-bound).  MHIMX_STEP_EXEC=0:
         # the Python orchestration (kept: it is the executor's specification and takes every case the executor refuses)
         self.use_executor = os.environ.get("MHIMX_STEP_EXEC", "1") != "0"
+        self.wgrad_form = 0                # mhimx_step_cfg.wgrad_form: which weight-gradient kernel the step executor launches (tests force 1 / 2)
         self._exec, self.time_project = None, False      # (mhimx_step_cfg.time_project: eager steps time their projection launch - bench.py)
         self.exec_max_rows = 262144        # include/mhimx.h MHIMX_STEP_MAX_ROWS
         self.single_pass = True            # ABMIL: one projection launch for teacher + student, bag-ordered buffers (when shapes allow)
@@ -1170,6 +1171,7 @@ class FusedTrainer:
         else:
             cfg.q_out = None
         cfg.time_project = int(bool(self.time_project))
+        cfg.wgrad_form = int(self.wgrad_form)
         cfg.attn2score = int(bool(t.attn2score))
         cfg.drop_p_teacher = float(t.dropout_p if t.training else 0.0)
         cfg.merge_drop_p, cfg.merge_mm = float(s.merge.dropout), float(s.merge.g_q_mm)

@@ -723,14 +723,15 @@ def bag_wgrad_ximg_ok(x, E):
 
 
 def bag_wgrad(dH, dact16, x, rows, n_rows, out_w=None, out_b=None, accumulate=False, defer=None, rows_dh="same", want_bias=True,
-              dh_compact=False, ride_tail=False, ximg=None, keep=None):
+              dh_compact=False, ride_tail=False, ximg=None, keep=None, form=0):
     """The projection's weight and bias gradient from the bag-ordered buffers:
     dPre[p] = dH[rows[p]] * dact16[rows[p]],  out_b (+)= sum_p dPre[p],  out_w [E,D] (+)= dPre^T x[rows]   (p < n_rows)
     — mhimx_rows_dpre_image (dPre as a bf16 hi/lo matrix-core image) + mhimx_bag_wgrad.
     dact16 None: dPre = dH (any Linear's weight gradient dy^T x); rows_dh: the row list of dH when it differs from x's (None: dH is
     compact); want_bias False: no column sums; dh_compact: dH is compact while dact16 is gathered by rows (mhimx_rows_dpre_image_c).
     ride_tail (with defer): the reductions already queued on the list and the last stage of a parked Merge tail run as trailing workgroups
-    of the product launch (mhimx_bag_wgrad_args.ride_tail) - the list then holds the product's own slab sum only."""
+    of the product launch (mhimx_bag_wgrad_args.ride_tail) - the list then holds the product's own slab sum only.
+    form: mhimx_bag_wgrad_args.form (0 automatic, 1 one workgroup per CU, 2 two per CU: D % 128 == 0 is enough)."""
     _chk(dH, name="dH"); _chk(dact16, torch.float16, "dact16"); _chk(rows, torch.int64, "rows")
     if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.stride(1) == 1):
         raise L.MhimxError("x: expected a GPU fp32 matrix with contiguous rows")
@@ -753,7 +754,7 @@ def bag_wgrad(dH, dact16, x, rows, n_rows, out_w=None, out_b=None, accumulate=Fa
         ws = torch.empty(lib.mhimx_wgrad_ws_floats(N, E, D), device=dev)
         g = L.BagWgrad(img=_p(img), X=_p(x), ldx=x.stride(0), n_bag_rows=N, rows=None, L=N, E=E, D=D, C=_p(out_w), ldc=out_w.stride(0),
                        accumulate=int(bool(accumulate)), ws=_p(ws), ws_floats=ws.numel(), defer=_dp(defer),
-                       ride_tail=int(bool(ride_tail and defer is not None)), ximg=_p(ximg))
+                       ride_tail=int(bool(ride_tail and defer is not None)), ximg=_p(ximg), form=int(form))
         L.check(lib.mhimx_bag_wgrad(_stream(), C.byref(g)), "mhimx_bag_wgrad")
         if defer is not None:
             defer.keep.extend((ws_b, ws, img))
@@ -776,7 +777,7 @@ def bag_wgrad(dH, dact16, x, rows, n_rows, out_w=None, out_b=None, accumulate=Fa
     ws = torch.empty(lib.mhimx_wgrad_ws_floats(n_rows, E, D), device=dev)
     g = L.BagWgrad(img=_p(img), X=_p(x), ldx=x.stride(0), n_bag_rows=x.shape[0], rows=_p(rows), L=n_rows, E=E, D=D, C=_p(out_w),
                    ldc=out_w.stride(0), accumulate=int(bool(accumulate)), ws=_p(ws), ws_floats=ws.numel(), defer=_dp(defer),
-                   ride_tail=int(bool(ride_tail and defer is not None)))
+                   ride_tail=int(bool(ride_tail and defer is not None)), form=int(form))
     L.check(lib.mhimx_bag_wgrad(_stream(), C.byref(g)), "mhimx_bag_wgrad")
     if defer is not None:
         defer.keep.extend((ws_b, ws, img))

@@ -1,4 +1,5 @@
-"""Timing of the projection's weight gradient at c2 size: the two kernels of the dedicated pair (wgrad.hip) and the generic pair."""
+"""Timing of the projection's weight gradient at c2 size: the two kernels of the dedicated pair (wgrad.hip) and the generic pair.
+wgrad: the automatic form; wgrad1 / wgrad2: one / two workgroups per CU (mhimx_bag_wgrad_args.form)."""
 import ctypes as C
 import os
 import sys
@@ -31,9 +32,10 @@ def image():
                                       ws_b.data_ptr(), ws_b.numel() * 4, lst.ptr()), "image")
 
 
-def wgrad():
+def wgrad(form=0):
     lst.c.n = 0
     g.defer = lst.ptr()
+    g.form = form
     L.check(lib.mhimx_bag_wgrad(None, C.byref(g)), "wgrad")
 
 
@@ -68,7 +70,7 @@ def wgrad_dma():
 
 which = sys.argv[1:] or ["image", "wgrad", "ximage", "image_k", "wgrad_dma", "image", "wgrad", "wgrad_dma"]
 for name in which:
-    fn = {"image": image, "wgrad": wgrad, "old": old, "ximage": ximage, "image_k": image_k, "wgrad_dma": wgrad_dma}[name]
+    fn = {"image": image, "wgrad": wgrad, "wgrad1": lambda: wgrad(1), "wgrad2": lambda: wgrad(2), "old": old, "ximage": ximage, "image_k": image_k, "wgrad_dma": wgrad_dma}[name]
     for _ in range(10):
         fn()
     torch.cuda.synchronize()
@@ -79,11 +81,11 @@ for name in which:
     e1.record(); torch.cuda.synchronize()
     print("%-6s %.1f us per call (back-to-back launches)" % (name, e0.elapsed_time(e1) * 1e3 / 100))
 
-if os.environ.get("WG_PROF"):
-    wgrad(); torch.cuda.synchronize()
+for form in (1, 2) if os.environ.get("WG_PROF") else ():
+    wgrad(form); torch.cuda.synchronize()
     tail_ = img[lib.mhimx_wgrad_image_bytes(L_, E) // 4:][:64].cpu()
     st = tail_[:32].view(8, 4).tolist()
     if float(tail_[32]) > 0:
-        print("workgroup 0: %.0f shader cycles in %.2f us (100 MHz clock) -> %.3f GHz" % (float(tail_[33]), float(tail_[32]) / 100, float(tail_[33]) / float(tail_[32]) / 10))
+        print("form %d, workgroup 0: %.0f shader cycles in %.2f us (100 MHz clock) -> %.3f GHz" % (form, float(tail_[33]), float(tail_[32]) / 100, float(tail_[33]) / float(tail_[32]) / 10))
     for w in (0, 4):
         print("wave %d: entry -> loop %.0f, loop %.0f (%d k-steps), epilogue %.0f shader cycles" % (w, st[w][0], st[w][1], st[w][3], st[w][2]))
