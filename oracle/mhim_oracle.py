@@ -544,11 +544,12 @@ def pure(x, params, cfg: Cfg, drop_mask=None):
 
 
 def forward_student(x, params, cfg: Cfg, attn, teacher_feat=None, perm=None, ids_shuffle=None,
-                    drop_mask=None, mrh=None, perms=None):
+                    drop_mask=None, mrh=None, perms=None, merge_kw=None):
     """MHIM.forward (mhim.py:318-378).
 
     attn: teacher score, numpy/torch [N] or [h,N].  perm: injected randperm(k) for the HAM
-    subsample; ids_shuffle: injected argsort(rand(L)) for Merge.masking.
+    subsample; ids_shuffle: injected argsort(rand(L)) for Merge.masking.  merge_kw: Merge's own dropout
+    (mhim.py:104) as mca()'s injected keep-masks, dict(attn_mask [heads, k, R], out_mask [k, E], p).
     Returns (logits [C], cls_loss scalar-or-0., ps, len_keep_after_merge, extras dict).
     """
     h = feature(x, params, cfg.act, drop_mask, cfg.dropout)
@@ -561,7 +562,7 @@ def forward_student(x, params, cfg: Cfg, attn, teacher_feat=None, perm=None, ids
     hk = h[ids_keep]                                                # masking.py:107
     g_new = None
     if cfg.merge_enable:
-        hk, g_new = merge_train(hk, ids_shuffle, params, cfg.merge_ratio, cfg.merge_mm)
+        hk, g_new = merge_train(hk, ids_shuffle, params, cfg.merge_ratio, cfg.merge_mm, **(merge_kw or {}))
     if cfg.baseline == "dsmil":                                     # mhim.py:355-364: distillation on B [C,E], mean over classes
         lb, li, _, B, _ = dsmil(hk, params, cls_attn=cfg.attn2score)
         cls_loss = soft_target_ce(B, teacher_feat.detach(), cfg.temp_t).mean() if teacher_feat is not None else 0.0
@@ -626,9 +627,10 @@ def clip_grad_norm(grads, max_norm):
 
 def train_step(x, label, stu, tea, opt_state, cfg: Cfg, step, perm=None, ids_shuffle=None,
                aux_alpha=0.5, main_alpha=1.0, mm=0.9997, lr=2e-4, wd=1e-5, model="mhim", score_override=None, clip_grad=None,
-               drop_mask_t=None, drop_mask_s=None):
+               drop_mask_t=None, drop_mask_s=None, merge_kw=None):
     """One CommonMIL.forward_func + BaseTrainer step (accumulation 1).  Dropout (cfg.dropout > 0) takes injected keep-masks [N, E]
-    for the teacher's and the student's feature dropout (mhim.py:76; the trainer keeps the teacher in train mode, base_engine.py:37-38).
+    for the teacher's and the student's feature dropout (mhim.py:76; the trainer keeps the teacher in train mode, base_engine.py:37-38);
+    merge_kw: the keep-masks of Merge's own dropout (forward_student).
 
     stu/tea: dicts of fp32 tensors (reference key names).  opt_state: {name: (m, v)}.
     Returns (new_stu, new_tea, new_opt_state, info).
@@ -640,7 +642,8 @@ def train_step(x, label, stu, tea, opt_state, cfg: Cfg, step, perm=None, ids_shu
         if score_override is not None:      # tests: select on the scores the device saw (its random subsets are read back as perm)
             score = score_override
         t_in = None if aux_alpha == 0.0 else t_feat                 # common_mil.py:24
-        logits, cls_loss, ps, keep, ex = forward_student(x, stu_g, cfg, score, t_in, perm, ids_shuffle, drop_mask=drop_mask_s)
+        logits, cls_loss, ps, keep, ex = forward_student(x, stu_g, cfg, score, t_in, perm, ids_shuffle, drop_mask=drop_mask_s,
+                                                         merge_kw=merge_kw)
     else:
         logits, cls_loss, ps, keep, ex = pure(x, stu_g, cfg), 0.0, x.shape[0], x.shape[0], {}
     if isinstance(logits, list):                                    # dsmil: common_mil.py:26-28 mixes the two logit vectors
