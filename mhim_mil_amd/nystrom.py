@@ -195,10 +195,7 @@ class LayerNorm(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w, b):
         x = x.contiguous()
-        M, E = x.shape
-        y = torch.empty_like(x)
-        mean, rstd = torch.empty(M, device=x.device), torch.empty(M, device=x.device)
-        L.check(L.lib().mhimx_layernorm_fwd(_st(), _ptr(x), M, E, _ptr(w), _ptr(b), _ptr(y), _ptr(mean), _ptr(rstd)), "layernorm_fwd")
+        y, mean, rstd = _layernorm_fwd(x, w, b)
         ctx.save_for_backward(x, w, mean, rstd)
         return y
 
@@ -231,11 +228,7 @@ class Linear(torch.autograd.Function):
         drop_p, seed, tick, has_b = ctx.cfg
         dy = dy.contiguous()
         M, N = dy.shape
-        if drop_p > 0:
-            g = torch.empty_like(dy)
-            L.check(L.lib().mhimx_dropout_apply(_st(), _ptr(dy), _ptr(g), M, N, float(drop_p), int(seed) & 0xFFFFFFFFFFFFFFFF,
-                                                None if tick is None else _ptr(tick)), "dropout_apply")
-            dy = g
+        dy = _redraw_mask(dy, drop_p, seed, tick, False)               # (ops.gemm_nt drew it: never the projection kernel's stream)
         dx = dw = db = None
         if ctx.needs_input_grad[0]:
             dx = torch.empty_like(x)
@@ -545,8 +538,7 @@ def _core_forward(qkv, conv_w, l, scale):
     no = ops.NysOperands(qkv, lm, scale)
     a2, z, z0, stats, chain = _landmark_pinv_forward(lm, scale)        # the landmark-only chain
     a3v, lse3 = ops.nys_a3v_fwd(no)                                    # softmax_n(q~ k^T) v   nystrom:116,131,133
-    w2 = torch.empty((HEADS, m, DH), device=dev)
-    _heads_mm("nn", batched(z), batched(a3v), batched(w2), HEADS)     # pinv (a3 v)
+    w2 = _heads_product("nn", z, a3v, m, DH)                            # pinv (a3 v)
     wc = conv_w.reshape(HEADS, -1).contiguous()
     out = torch.empty((T, INNER), device=dev)
     L.check(lib.mhimx_resconv(_st(), _ptr(qkv, 2 * INNER), ld, _ptr(wc), wc.shape[1], DH, T, INNER, _ptr(out), INNER, 0, 0),
@@ -574,12 +566,10 @@ def _core_backward(saved, dout):
     # out = a1 w2: dq, the S1 term of dk~, dw2 = a1^T dout
     dw2 = ops.nys_out_bwd(no, w2, dout, lse1, dqkv, dlm)
     # w2 = z a3v
-    dz = torch.empty_like(z)
-    _heads_mm("nt", batched(dw2), batched(a3v), batched(dz), HEADS)    # dz = dw2 a3v^T
+    dz = _heads_product("nt", dw2, a3v, m, m)                          # dz = dw2 a3v^T
     dlm2 = torch.empty_like(dlm)
     _landmark_pinv_backward(lm, scale, a2, z0, stats, chain, dz, dlm2, accumulate=False)
-    da3v = torch.empty_like(a3v)
-    _heads_mm("tn", batched(z), batched(dw2), batched(da3v), HEADS)    # da3v = z^T dw2
+    da3v = _heads_product("tn", z, dw2, m, DH)                         # da3v = z^T dw2
     # a3v = a3 v: dk, dv +=, the S3 term of dq~
     ops.nys_a3v_bwd(no, a3v, da3v, lse3, dqkv, dlm, accumulate_dv=True)
     L.check(lib.mhimx_axpby(_st(), _ptr(dlm2), _ptr(dlm), dlm.numel(), 1.0, 1.0), "axpby")      # + the attn2 terms
@@ -612,16 +602,89 @@ class NystromCore(torch.autograd.Function):
         return dqkv, dwc, None, None
 
 
-def _cls_attention(qkv, lm, z, lse3, pad, scale):
-    """nystrom:143-150: the cls token's attention row [8, T] = (attn1[cls] pinv) attn3, without attn1 / attn3."""
+# ------------------------------------------------------------------------------------------------ the layer shell
+# What TransLayerFn and nystrom_sharded.ShardedTransLayerFn launch alike around their cores ("the layer shell"): plain
+# functions of views, a tick or None and flags the caller computed.  ``big``: the single-pass projection kernel and ITS dropout stream.
+def _layernorm_fwd(x, w, b):
+    """LayerNorm of the rows of x [M, E] (contiguous) -> (xn, mean [M], rstd [M])."""
+    M, E = x.shape
+    xn = torch.empty_like(x)
+    mean, rstd = torch.empty(M, device=x.device), torch.empty(M, device=x.device)
+    L.check(L.lib().mhimx_layernorm_fwd(_st(), _ptr(x), M, E, _ptr(w), _ptr(b), _ptr(xn), _ptr(mean), _ptr(rstd)), "layernorm_fwd")
+    return xn, mean, rstd
+
+
+def _layernorm_bwd_res(dxn, x, ln_w, mean, rstd, dy):
+    """LayerNorm backward with the residual's gradient added inside: dx = LayerNorm'(dxn) + dy -> (dx, d weight, d bias)."""
+    M, E = x.shape
+    dx, dlw, dlb = torch.empty_like(x), torch.empty_like(ln_w), torch.empty_like(ln_w)
+    ws = torch.empty(2 * 512 * E, device=x.device)
+    L.check(L.lib().mhimx_layernorm_bwd_res(_st(), _ptr(dxn), _ptr(x), M, E, _ptr(ln_w), _ptr(mean), _ptr(rstd), _ptr(dy), _ptr(dx),
+                                            _ptr(dlw), _ptr(dlb), 0, _ptr(ws)), "layernorm_bwd_res")
+    return dx, dlw, dlb
+
+
+def _to_qkv(xn, w_qkv, qkv, big):
+    """qkv [rows of xn, 1536] = xn w_qkv^T (no bias), written into the caller's rows."""
+    if big:
+        # to_qkv on the single-pass projection kernel (one "model" of width 1536: raw fp32 rows split on their way into LDS,
+        # 160 x 256 tiles; 330 -> ~270 us at n = 50 000)
+        ops.bag_project(xn, [ops.ProjHead(ops.pair_planes(w_qkv), None, out=qkv)], act=0)
+    else:
+        ops.gemm_nt(xn, w_qkv, out=qkv, prec=_PREC)
+
+
+def _to_out_res(a, w_out, b_out, x, drop_p, seed, tick, big):
+    """y = x + dropout(a w_out^T + b_out) (nystrom_attention.py:60-63, baseline.py:213-218); tick: the device step counter or None."""
+    if big:                                   # to_out on the projection kernel too (bias + its own dropout stream in the epilogue; 154 -> ~85 us)
+        return ops.bag_project(a, [ops.ProjHead(ops.pair_planes(w_out), b_out, drop_p=drop_p, drop_seed=seed, resid=x)], act=0,
+                               drop_tick=tick if drop_p > 0 else None)[0].out                             # y = x + dropout(to_out(.)): one launch
+    y = ops.gemm_nt(a, w_out, bias=b_out, drop_p=drop_p, drop_seed=seed, drop_tick=tick, prec=_PREC)
+    L.check(L.lib().mhimx_axpby(_st(), _ptr(x), _ptr(y), y.numel(), 1.0, 1.0), "axpby")                   # y += x
+    return y
+
+
+def _redraw_mask(dy, drop_p, seed, tick, big):
+    """dy under the forward's dropout mask again, from the stream of the kernel that drew it (dy itself where nothing was dropped)."""
+    if not drop_p > 0:
+        return dy
+    M, N = dy.shape
+    g = torch.empty_like(dy)
+    fn = L.lib().mhimx_dropout_apply_proj if big else L.lib().mhimx_dropout_apply
+    L.check(fn(_st(), _ptr(dy), _ptr(g), M, N, float(drop_p), int(seed) & 0xFFFFFFFFFFFFFFFF, None if tick is None else _ptr(tick)),
+            "dropout_apply")
+    return g
+
+
+def _linear_wgrad(dy, a, pair, want_bias=True):
+    """(d weight = dy^T a, d bias = column sums of dy or None) of y = a W^T + b; pair: the matrix-core-image weight-gradient pair
+    (csrc/wgrad.hip), where the caller found it applicable (ops.bag_wgrad_ok)."""
+    n = dy.shape[0]
+    if pair:
+        return ops.bag_wgrad(dy, None, a, None, n, want_bias=want_bias)
+    return ops.gemm_tn(dy, a, splits=8 if n >= 4096 else 1, prec=_PREC), ops.colsum(dy) if want_bias else None
+
+
+def _heads_product(mode, a, b, rows, cols):
+    """op(a_h, b_h) of two contiguous batches of per-head matrices -> a fresh [8, rows, cols]."""
+    c = torch.empty((HEADS, rows, cols), device=a.device)
+    _heads_mm(mode, batched(a), batched(b), batched(c), HEADS)
+    return c
+
+
+def _cls_row(qkv, row, lm, z, scale):
+    """u [8, 256] = softmax(scale q_cls k~^T) z, q_cls in row ``row`` of qkv: attn1's cls row times the pseudo-inverse (nystrom:143-150)."""
     m = LANDMARKS
     ld = qkv.shape[1]
     a1c = torch.empty((HEADS, 1, m), device=qkv.device)                    # attn1's cls row: softmax(scale q_cls k~^T)
-    _heads_mm("nt", Op(qkv, pad * ld, DH, ld, 1, DH), Op(lm, INNER, DH, 2 * INNER, m, DH), batched(a1c), HEADS)
+    _heads_mm("nt", Op(qkv, row * ld, DH, ld, 1, DH), Op(lm, INNER, DH, 2 * INNER, m, DH), batched(a1c), HEADS)
     L.check(L.lib().mhimx_softmax_rows(_st(), _ptr(a1c), _ptr(a1c), HEADS, m, float(scale)), "softmax_rows")
-    u = torch.empty((HEADS, 1, m), device=qkv.device)
-    _heads_mm("nn", batched(a1c), batched(z), batched(u), HEADS)
-    return ops.nys_cls_attn(ops.NysOperands(qkv, lm, scale), lse3, u.reshape(HEADS, m))
+    return _heads_product("nn", a1c, z, 1, m).reshape(HEADS, m)
+
+
+def _cls_attention(qkv, lm, z, lse3, pad, scale):
+    """nystrom:143-150: the cls token's attention row [8, T] = (attn1[cls] pinv) attn3, without attn1 / attn3."""
+    return ops.nys_cls_attn(ops.NysOperands(qkv, lm, scale), lse3, _cls_row(qkv, pad, lm, z, scale))
 
 
 class TransLayerFn(torch.autograd.Function):
@@ -632,34 +695,21 @@ class TransLayerFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, ln_w, ln_b, w_qkv, w_out, b_out, conv_w, drop_p, seed, tick, scale, need_attn):
-        lib = L.lib()
         x = x.contiguous()
-        n, E = x.shape
+        n = x.shape[0]
         m, dev = LANDMARKS, x.device
         pad = (m - n % m) % m
         T, l = n + pad, math.ceil(n / m)
-        xn = torch.empty_like(x)
-        mean, rstd = torch.empty(n, device=dev), torch.empty(n, device=dev)
-        L.check(lib.mhimx_layernorm_fwd(_st(), _ptr(x), n, E, _ptr(ln_w), _ptr(ln_b), _ptr(xn), _ptr(mean), _ptr(rstd)), "layernorm_fwd")
+        big = n >= 2048 and _PREC == "bf16x3"              # from the tokens without the padding: the projection kernels see those rows only
+        xn, mean, rstd = _layernorm_fwd(x, ln_w, ln_b)
         qkv = torch.empty((T, 3 * INNER), device=dev)
         if pad:
             qkv[:pad].zero_()
-        if n >= 2048 and _PREC == "bf16x3":
-            # to_qkv on the single-pass projection kernel (one "model" of width 1536: raw fp32 rows split on their way into LDS,
-            # 160 x 256 tiles; 330 -> ~270 us at n = 50 000)
-            ops.bag_project(xn, [ops.ProjHead(ops.pair_planes(w_qkv), None, out=qkv[pad:])], act=0)
-        else:
-            ops.gemm_nt(xn, w_qkv, out=qkv[pad:], prec=_PREC)
+        _to_qkv(xn, w_qkv, qkv[pad:], big)
         out, saved = _core_forward(qkv, conv_w, l, scale)
-        proj = n >= 2048 and _PREC == "bf16x3"
-        if proj:                              # to_out on the projection kernel too (bias + its own dropout stream in the epilogue; 154 -> ~85 us)
-            y = ops.bag_project(out[pad:], [ops.ProjHead(ops.pair_planes(w_out), b_out, drop_p=drop_p, drop_seed=seed, resid=x)], act=0,
-                                drop_tick=tick if drop_p > 0 else None)[0].out                           # y = x + dropout(to_out(.)): one launch
-        else:
-            y = ops.gemm_nt(out[pad:], w_out, bias=b_out, drop_p=drop_p, drop_seed=seed, drop_tick=tick, prec=_PREC)
-            L.check(lib.mhimx_axpby(_st(), _ptr(x), _ptr(y), y.numel(), 1.0, 1.0), "axpby")             # y += x
+        y = _to_out_res(out[pad:], w_out, b_out, x, drop_p, seed, tick, big)
         ctx.saved = (x, xn, mean, rstd, ln_w, w_qkv, w_out, out, saved)
-        ctx.cfg = (pad, drop_p, seed, tick, proj)
+        ctx.cfg = (pad, drop_p, seed, tick, big)
         if not need_attn:
             return y
         lm, z, lse3 = saved[1], saved[3], saved[11]
@@ -670,50 +720,34 @@ class TransLayerFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy, *_):
-        lib = L.lib()
         x, xn, mean, rstd, ln_w, w_qkv, w_out, out, saved = ctx.saved
         ctx.saved = None
-        pad, drop_p, seed, tick, proj = ctx.cfg
+        pad, drop_p, seed, tick, big = ctx.cfg
         dy = dy.contiguous()
         n, E = x.shape
         T, dev = n + pad, x.device
-        g = dy
-        if drop_p > 0:                         # the forward's mask again, from the stream of the kernel that drew it
-            g = torch.empty_like(dy)
-            fn = lib.mhimx_dropout_apply_proj if proj else lib.mhimx_dropout_apply
-            L.check(fn(_st(), _ptr(dy), _ptr(g), n, E, float(drop_p), int(seed) & 0xFFFFFFFFFFFFFFFF, None if tick is None else _ptr(tick)),
-                    "dropout_apply")
+        g = _redraw_mask(dy, drop_p, seed, tick, big)
         dout = torch.empty((T, INNER), device=dev)
         if pad:
             dout[:pad].zero_()
-        if n >= 2048 and _PREC == "bf16x3":        # data gradients as products with the transposed weights on the projection kernel
+        if big:                                    # data gradients as products with the transposed weights on the projection kernel
             ops.bag_project(g, [ops.ProjHead(ops.pair_planes_t(w_out), None, out=dout[pad:])], act=0)
         elif n >= 2048 and _PREC != "f32":
             ops.gemm_nt(g, ops.transpose(w_out), out=dout[pad:], prec=_PREC)
         else:
             _gemm("nn", g, 0, E, w_out, 0, INNER, dout, pad * INNER, INNER, n, INNER, E)
-        big = n >= 2048 and _PREC == "bf16x3" and ops.bag_wgrad_ok(x, INNER, n)      # the matrix-core-image weight-gradient pair (csrc/wgrad.hip)
-        if big:
-            dw_out, db_out = ops.bag_wgrad(g, None, out[pad:], None, n)
-        else:
-            dw_out = ops.gemm_tn(g, out[pad:], splits=8 if n >= 4096 else 1, prec=_PREC)
-            db_out = ops.colsum(g)
+        wg = big and ops.bag_wgrad_ok(x, INNER, n)                                    # the matrix-core-image weight-gradient pair (csrc/wgrad.hip)
+        dw_out, db_out = _linear_wgrad(g, out[pad:], wg)
         dqkv, dwc = _core_backward(saved, dout)
         dxn = torch.empty_like(x)
-        if n >= 2048 and _PREC == "bf16x3":
+        if big:
             ops.bag_project(dqkv[pad:], [ops.ProjHead(ops.pair_planes_t(w_qkv), None, out=dxn)], act=0)
         elif n >= 2048 and _PREC != "f32":
             ops.gemm_nt(dqkv[pad:], ops.transpose(w_qkv), out=dxn, prec=_PREC)
         else:
             _gemm("nn", dqkv, pad * 3 * INNER, 3 * INNER, w_qkv, 0, E, dxn, 0, E, n, E, 3 * INNER)
-        if big:
-            dw_qkv, _ = ops.bag_wgrad(dqkv[pad:], None, xn, None, n, want_bias=False)
-        else:
-            dw_qkv = ops.gemm_tn(dqkv[pad:], xn, splits=8 if n >= 4096 else 1, prec=_PREC)
-        dx, dlw, dlb = torch.empty_like(x), torch.empty_like(ln_w), torch.empty_like(ln_w)
-        ws = torch.empty(2 * 512 * E, device=dev)
-        L.check(lib.mhimx_layernorm_bwd_res(_st(), _ptr(dxn), _ptr(x), n, E, _ptr(ln_w), _ptr(mean), _ptr(rstd), _ptr(dy), _ptr(dx),
-                                            _ptr(dlw), _ptr(dlb), 0, _ptr(ws)), "layernorm_bwd_res")
+        dw_qkv, _ = _linear_wgrad(dqkv[pad:], xn, wg, want_bias=False)
+        dx, dlw, dlb = _layernorm_bwd_res(dxn, x, ln_w, mean, rstd, dy)
         return dx, dlw, dlb, dw_qkv, dw_out, db_out, dwc, None, None, None, None, None
 
 

@@ -109,18 +109,12 @@ class ShardedTransLayerFn(torch.autograd.Function):
         if T % M or M % W or Tr % 64 or Tr % (T // M):
             raise L.MhimxError("sharded TransLayer: T % 256 == 0, world | 256 and aligned shards (T / world a multiple of 64 and of T / 256)")
         l, gl = T // M, M // W
-        xn = torch.empty_like(x)
-        mean, rstd = torch.empty(Tr, device=dev), torch.empty(Tr, device=dev)
-        L.check(lib.mhimx_layernorm_fwd(NY._st(), NY._ptr(x), Tr, E, NY._ptr(ln_w), NY._ptr(ln_b), NY._ptr(xn), NY._ptr(mean), NY._ptr(rstd)),
-                "layernorm_fwd")
+        xn, mean, rstd = NY._layernorm_fwd(x, ln_w, ln_b)
         if npad:
             xn[:npad].zero_()                        # nystrom_attention.py:70-73 pads AFTER the LayerNorm: pad tokens are zero rows of q, k, v
-        big = Tr >= 2048 and NY._PREC == "bf16x3"                                       # (the projection / weight-gradient kernels, as TransLayerFn)
-        if big:
-            qkv = torch.empty((Tr, 3 * INNER), device=dev)
-            ops.bag_project(xn, [ops.ProjHead(ops.pair_planes(w_qkv), None, out=qkv)], act=0)
-        else:
-            qkv = ops.gemm_nt(xn, w_qkv, prec=NY._PREC)                                 # [Tr, 1536]
+        big = Tr >= 2048 and NY._PREC == "bf16x3"                                       # from the block WITH its padding: the kernels see every row
+        qkv = torch.empty((Tr, 3 * INNER), device=dev)
+        NY._to_qkv(xn, w_qkv, qkv, big)
         ld = qkv.shape[1]
         lm_loc = torch.empty((gl, 2 * INNER), device=dev)
         L.check(lib.mhimx_landmark_mean(NY._st(), NY._ptr(qkv), ld, Tr, l, 2 * INNER, NY._ptr(lm_loc)), "landmark_mean")
@@ -135,17 +129,12 @@ class ShardedTransLayerFn(torch.autograd.Function):
             mx = Ls.max(0).values
             lse3 = (mx + torch.log2(torch.exp2(Ls - mx).sum(0))).contiguous()           # fixed rank order: every rank gets the same bits
             a3v = (torch.exp2(Ls - lse3).unsqueeze(-1) * A).sum(0).contiguous()
-        w2 = torch.empty((HEADS, M, DH), device=dev)
-        NY._heads_mm("nn", NY.batched(z), NY.batched(a3v), NY.batched(w2), HEADS)
+        w2 = NY._heads_product("nn", z, a3v, M, DH)                                     # pinv (a3 v)
         out, lse1 = ops.nys_out_fwd(no, w2)
         wc = conv_w.reshape(HEADS, -1).contiguous()
         v_prev, v_next = _edge_halos(comm, qkv[:, 2 * INNER:])                         # the neighbours' 16 boundary rows of v (kept for d conv weight)
         _resconv_sharded(qkv[:, 2 * INNER:], wc, out, 1, 0, v_prev, v_next)              # out += res_conv(v) (nystrom:135-136)
-        if big:                                                                         # y = x + dropout(to_out(.)): one launch
-            y = ops.bag_project(out, [ops.ProjHead(ops.pair_planes(w_out), b_out, drop_p=float(drop_p), drop_seed=int(seed), resid=x)], act=0)[0].out
-        else:
-            y = ops.gemm_nt(out, w_out, bias=b_out, drop_p=float(drop_p), drop_seed=int(seed), prec=NY._PREC)
-            L.check(lib.mhimx_axpby(NY._st(), NY._ptr(x), NY._ptr(y), y.numel(), 1.0, 1.0), "axpby")        # y += x
+        y = NY._to_out_res(out, w_out, b_out, x, float(drop_p), int(seed), None, big)    # (no tick: the by-value seed is the stream position)
         ctx.saved = (x, xn, mean, rstd, ln_w, w_qkv, w_out, out, qkv, lm, a2, z, z0, stats, chain, a3v, w2, wc, lse1, lse3, no.ws, v_prev, v_next)
         ctx.cfg = (l, gl, scale, comm, conv_w.shape, npad, float(drop_p), int(seed), big)
         if not need_attn:
@@ -155,12 +144,7 @@ class ShardedTransLayerFn(torch.autograd.Function):
         g0 = comm.rank * Tr
         u = torch.zeros((HEADS, M), device=dev)
         if g0 <= pad < g0 + Tr:
-            a1c = torch.empty((HEADS, 1, M), device=dev)
-            NY._heads_mm("nt", NY.Op(qkv, (pad - g0) * ld, DH, ld, 1, DH), NY.Op(lm, INNER, DH, 2 * INNER, M, DH), NY.batched(a1c), HEADS)
-            L.check(lib.mhimx_softmax_rows(NY._st(), NY._ptr(a1c), NY._ptr(a1c), HEADS, M, float(scale)), "softmax_rows")
-            u3 = torch.empty((HEADS, 1, M), device=dev)
-            NY._heads_mm("nn", NY.batched(a1c), NY.batched(z), NY.batched(u3), HEADS)
-            u.copy_(u3.view(HEADS, M))
+            u.copy_(NY._cls_row(qkv, pad - g0, lm, z, scale))
         comm.all_reduce_sum(u)
         attn = ops.nys_cls_attn(ops.NysOperands(qkv, lm, scale), lse3, u.contiguous())  # [8, Tr] (a workspace of its own: the backward keeps no.ws)
         v = qkv[:, 2 * INNER:]
@@ -176,22 +160,14 @@ class ShardedTransLayerFn(torch.autograd.Function):
         dy = dy.contiguous()
         Tr, E = x.shape
         dev, ld = x.device, qkv.shape[1]
-        g = dy
-        if drop_p > 0:                          # the forward's mask again (the stream of the kernel that drew it)
-            g = torch.empty_like(dy)
-            fn = lib.mhimx_dropout_apply_proj if big else lib.mhimx_dropout_apply
-            L.check(fn(NY._st(), NY._ptr(dy), NY._ptr(g), Tr, E, drop_p, seed & 0xFFFFFFFFFFFFFFFF, None), "dropout_apply")
+        g = NY._redraw_mask(dy, drop_p, seed, None, big)
         dout = torch.empty((Tr, INNER), device=dev)
         wg = big and ops.bag_wgrad_ok(x, INNER, Tr)
         if big:
             ops.bag_project(g, [ops.ProjHead(ops.pair_planes_t(w_out), None, out=dout)], act=0)
         else:
             NY._gemm("nn", g, 0, E, w_out, 0, INNER, dout, 0, INNER, Tr, INNER, E)
-        if wg:
-            dw_out, db_out = ops.bag_wgrad(g, None, out, None, Tr)
-        else:
-            dw_out = ops.gemm_tn(g, out, splits=8 if Tr >= 4096 else 1, prec=NY._PREC)
-            db_out = ops.colsum(g)
+        dw_out, db_out = NY._linear_wgrad(g, out, wg)
         dqkv = torch.empty_like(qkv)
         # residual convolution: dv = flip-conv(dout) with dout's halo rows; its weight gradient from the local outputs against v with halos
         g_prev, g_next = _edge_halos(comm, dout)
@@ -202,10 +178,8 @@ class ShardedTransLayerFn(torch.autograd.Function):
         dlm = torch.empty_like(lm)
         dw2 = ops.nys_out_bwd(no, w2, dout, lse1, dqkv, dlm)
         comm.all_reduce_sum(dw2)
-        dz = torch.empty_like(z)
-        NY._heads_mm("nt", NY.batched(dw2), NY.batched(a3v), NY.batched(dz), HEADS)
-        da3v = torch.empty_like(a3v)
-        NY._heads_mm("tn", NY.batched(z), NY.batched(dw2), NY.batched(da3v), HEADS)
+        dz = NY._heads_product("nt", dw2, a3v, M, M)                                     # dz = dw2 a3v^T
+        da3v = NY._heads_product("tn", z, dw2, M, DH)                                    # da3v = z^T dw2
         ops.nys_a3v_bwd(no, a3v, da3v, lse3, dqkv, dlm, accumulate_dv=True)              # dk, dv += (local); the token-side term of dq~
         comm.all_reduce_sum(dlm)
         NY._landmark_pinv_backward(lm, scale, a2, z0, stats, chain, dz, dlm)             # + the attn2 terms (replicated: added after the sum)
@@ -218,14 +192,8 @@ class ShardedTransLayerFn(torch.autograd.Function):
             NY._gemm("nn", dqkv, 0, ld, w_qkv, 0, E, dxn, 0, E, Tr, E, ld)
         if npad:
             dxn[:npad].zero_()                       # the pad rows of xn are constants
-        if wg:
-            dw_qkv, _ = ops.bag_wgrad(dqkv, None, xn, None, Tr, want_bias=False)
-        else:
-            dw_qkv = ops.gemm_tn(dqkv, xn, splits=8 if Tr >= 4096 else 1, prec=NY._PREC)
-        dx, dlw, dlb = torch.empty_like(x), torch.empty_like(ln_w), torch.empty_like(ln_w)
-        wsl = torch.empty(2 * 512 * E, device=dev)
-        L.check(lib.mhimx_layernorm_bwd_res(NY._st(), NY._ptr(dxn), NY._ptr(x), Tr, E, NY._ptr(ln_w), NY._ptr(mean), NY._ptr(rstd), NY._ptr(dy),
-                                            NY._ptr(dx), NY._ptr(dlw), NY._ptr(dlb), 0, NY._ptr(wsl)), "layernorm_bwd_res")
+        dw_qkv, _ = NY._linear_wgrad(dqkv, xn, wg, want_bias=False)
+        dx, dlw, dlb = NY._layernorm_bwd_res(dxn, x, ln_w, mean, rstd, dy)
         return dx, dlw, dlb, dw_qkv, dw_out, db_out, dwc.reshape(wshape), None, None, None, None, None, None
 
 
@@ -480,8 +448,10 @@ def sharded_sattention(enc: "NY.SAttention", h_local, pad, n, comm=None, return_
     """mhim_modules/baseline.SAttention (cls token, TransLayer, PPEG, TransLayer, LayerNorm of the cls row: baseline.py:222-288) on a
     sequence sharded over the ranks.  h_local: this rank's block of the PADDED token sequence [zeros(pad) | cls slot | n - 1 token rows]
     (T = pad + n, T % 256 == 0; the cls slot's content is ignored).  Returns the cls feature [512] on every rank.
-    First cut of the encoder level: the two layers are sequence-parallel (ShardedTransLayerFn); the PPEG between them runs REPLICATED on
-    an all-gathered copy of the sequence (one all-gather forward, one all-reduce of its gradient backward), each rank keeping its rows."""
+    The two layers are sequence-parallel (ShardedTransLayerFn).  The PPEG between them runs on a band of its token grid per rank
+    (ShardedPPEGFn: one all-to-all each way); at world 1 the band is the whole grid and the replica path's PPEG runs on the block itself
+    (MHIMX_PPEG_BAND_W1=1 takes the band kernels there too); below 49 tokens (grids under 7 x 7: the zero-padded rule) it runs replicated
+    on an all-gathered copy of the sequence, each rank keeping its rows."""
     comm = comm if comm is not None else _Comm()
     Tr = h_local.shape[0]
     g0 = comm.rank * Tr

@@ -150,6 +150,61 @@ class ShardedBagTrainer:
             part[0] = float("-inf")
         return ops.lse_merge(self.comm.all_gather(part).contiguous())
 
+    # ------------------------------------------------------------------------------------------------- the ends every step body shares
+    def _shard(self, x_local):
+        """This rank's rows and where they sit in the bag: (x, n, dev, E, counts [rows per rank], N = the bag's rows, lo = my first row)."""
+        x = self.s._check_x(x_local)
+        n, dev, E = x.shape[0], x.device, self.s.mlp_dim
+        counts = self.counts if self.counts is not None else [n] * self.comm.world
+        assert counts[self.comm.rank] == n, "counts[rank] must equal the local row count"
+        return x, n, dev, E, counts, sum(counts), sum(counts[:self.comm.rank])
+
+    def _teacher_score(self, st_t, gstats):
+        """The local rows' scores from the teacher's shard-local pool pass and the BAG's softmax statistics."""
+        if self.t.attn2score:
+            return ops.pseudo_score(st_t.s, gstats, st_t.cproj, self.t.predictor.bias.data)
+        return ops.softmax_from_stats(st_t.s, gstats)
+
+    def _head(self, z, t_feat, label, d_wp, d_bp, accumulate=False):
+        """Predictor + CE + distillation against the teacher's row (not read when aux_alpha is 0) and their gradients, replicated:
+        (logits, losses [3], g_z); d_wp / d_bp: where the predictor's gradient goes."""
+        s = self.s
+        logits, losses, g_z, _, _ = ops.head_fwd_bwd(z, t_feat if self.aux_alpha != 0. else None, s.predictor.weight.data, s.predictor.bias.data,
+                                                     label, temp_t=float(s.temp_t), main_alpha=self.main_alpha, aux_alpha=self.aux_alpha,
+                                                     d_wp=d_wp, d_bp=d_bp, accumulate=accumulate)
+        return logits, losses, g_z
+
+    def _merge_grads(self):
+        """Merge's parameter-gradient destinations in the flat buffer, by the names ops.merge_bwd gives them."""
+        gv = self.flat.grad_views
+        return {"d_ln_w": gv["merge.norm.weight"], "d_ln_b": gv["merge.norm.bias"], "d_wkv": gv["merge.attn.to_kv.weight"],
+                "d_wq": gv["merge.attn.to_q.weight"], "d_wo": gv["merge.attn.to_out.0.weight"], "d_bo": gv["merge.attn.to_out.0.bias"]}
+
+    def _zero_replicated(self, merge_sharded=False):
+        """Replicated terms count once in the SUM: what every rank computes alike from identical inputs - the predictor's gradient and,
+        unless Merge is sharded (its gradients are partial sums then), Merge's - is kept on rank 0 and zeroed elsewhere, before _sum_grads."""
+        fl = self.flat
+        if self.comm.rank != 0:
+            for name in fl.train_names:
+                if name.startswith("predictor.") or (name.startswith("merge.") and not merge_sharded):
+                    fl.grad_views[name].zero_()
+
+    def _sum_grads(self):
+        """The flat gradient's all-reduce: parameter gradients are local partial sums."""
+        return self.comm.all_reduce_sum(self.flat.grad[:self.flat.n_train])
+
+    def _update(self):
+        """Adam + EMA teacher, replicated on identical inputs; the caller has moved opt_step (the device step counter)."""
+        fl = self.flat
+        self.step_count += 1
+        ops.adam_ema(fl.student, fl.grad, fl.m, fl.v, None if fl.same_teacher else fl.teacher, fl.n_train, self.step_count, lr=self.lr,
+                     beta1=self.betas[0], beta2=self.betas[1], eps=self.eps, weight_decay=self.wd, grad_scale=1.0, ema_mm=self.mm,
+                     zero_grad=True, step_dev=self.opt_step)
+
+    def _set_last(self, logits, losses, N, Lk, rows, len_keep, score, t_feat):
+        self.last = {"logits": logits, "losses": losses, "patch_num": N, "keep_num": Lk + self.s.merge.k, "rows": rows,
+                     "len_keep": len_keep, "score": score, "teacher_feat": t_feat}
+
     # -------------------------------------------------------------------------------------------------
     def fixed_shape_ok(self, x):
         """The sync-free step needs the one-pass scorer (its ``excl`` flags) and the single-pass projection; train_step also asks for
@@ -190,11 +245,7 @@ class ShardedBagTrainer:
         all n rows (excluded rows carry a zero gradient).  Costs ~3 % more scorer rows than a compacted list, removes both host syncs."""
         s, t, fl, cm = self.s, self.t, self.flat, self.comm
         gv = fl.grad_views
-        x = s._check_x(x_local)
-        n, dev, E = x.shape[0], x.device, s.mlp_dim
-        counts = self.counts if self.counts is not None else [n] * cm.world
-        N, lo = sum(counts), sum(counts[:cm.rank])
-        assert counts[cm.rank] == n, "counts[rank] must equal the local row count"
+        x, n, dev, E, counts, N, lo = self._shard(x_local)
         shared_seed, local_seed = self._seeds()
         k = s.merge.k
         defer = ops.ReduceList()
@@ -224,10 +275,7 @@ class ShardedBagTrainer:
             part[2:].copy_(st_t.z)
             yield lambda: cm.all_gather_into(parts, part)
             gstats, t_feat = ops.lse_merge(parts)
-            if t.attn2score:
-                sc_loc = ops.pseudo_score(st_t.s, gstats, st_t.cproj, t.predictor.bias.data)
-            else:
-                sc_loc = ops.softmax_from_stats(st_t.s, gstats)
+            sc_loc = self._teacher_score(st_t, gstats)
             if cm.world == 1:
                 score = sc_loc
             else:                                                  # ragged shards: gather at the widest shard's length, then one fixed-shape copy per rank
@@ -282,10 +330,7 @@ class ShardedBagTrainer:
             gstats, z = ops.lse_merge(parts2)
 
             # ---- head (replicated)
-            t_in = t_feat if self.aux_alpha != 0. else None
-            logits, losses, g_z, _, _ = ops.head_fwd_bwd(z, t_in, s.predictor.weight.data, s.predictor.bias.data, label,
-                                                         temp_t=float(s.temp_t), main_alpha=self.main_alpha, aux_alpha=self.aux_alpha,
-                                                         d_wp=gv["predictor.weight"], d_bp=gv["predictor.bias"])
+            logits, losses, g_z = self._head(z, t_feat, label, gv["predictor.weight"], gv["predictor.bias"])
 
             # ---- backward: the pool backward sees the BAG's softmax statistics and pooled feature
             st.stats.copy_(gstats)
@@ -297,8 +342,7 @@ class ShardedBagTrainer:
             dT2 = dHbuf[n:]                                        # zero on the ranks whose tokens were excluded
             if cm.world > 1:
                 yield lambda: cm.all_reduce_sum(dT2)               # = broadcast from rank 0
-            mgr = {"d_ln_w": gv["merge.norm.weight"], "d_ln_b": gv["merge.norm.bias"], "d_wkv": gv["merge.attn.to_kv.weight"],
-                   "d_wq": gv["merge.attn.to_q.weight"], "d_wo": gv["merge.attn.to_out.0.weight"], "d_bo": gv["merge.attn.to_out.0.bias"]}
+            mgr = self._merge_grads()
             if shard_merge:
                 # dX for the own rows lands in dHbuf directly (those rows were excluded from the pool: their slots hold zeros); the
                 # parameter gradients are this rank's PARTIAL sums - the flat-gradient all-reduce below adds them (terms every rank
@@ -316,20 +360,13 @@ class ShardedBagTrainer:
                 ops.gemm_tn(dpre, x, out=gv["feature.0.weight"], splits=8 if n >= 2048 else 1, prec="bf16x3", M=n, defer=defer)
             ops.reduce_flush(defer)
             if cm.world > 1:
-                if cm.rank != 0:                                   # replicated terms: counted once in the SUM
-                    for name in fl.train_names:
-                        if name.startswith("predictor.") or (name.startswith("merge.") and not shard_merge):
-                            gv[name].zero_()
-                yield lambda: cm.all_reduce_sum(fl.grad[:fl.n_train])
+                self._zero_replicated(shard_merge)
+                yield self._sum_grads
 
-            self.step_count += 1
-            ops.adam_ema(fl.student, fl.grad, fl.m, fl.v, None if fl.same_teacher else fl.teacher, fl.n_train, self.step_count, lr=self.lr, beta1=self.betas[0],
-                         beta2=self.betas[1], eps=self.eps, weight_decay=self.wd, grad_scale=1.0, ema_mm=self.mm, zero_grad=True,
-                         step_dev=self.opt_step)
+            self._update()                                         # (opt_step moved in the preparation launch)
         finally:
             s._tick = t._tick = None
-        self.last = {"logits": logits, "losses": losses, "patch_num": N, "keep_num": Lk + k, "rows": rows,
-                     "len_keep": len_keep, "score": score, "teacher_feat": t_feat}
+        self._set_last(logits, losses, N, Lk, rows, len_keep, score, t_feat)
 
     # -------------------------------------------------------------------------------------------------
     def capture(self, x_local, label, warmup=2, i=None):
@@ -387,11 +424,7 @@ class ShardedBagTrainer:
         """Any scorer / feature shape: compacted local row lists (ONE host read-back of the data-dependent local counts per step)."""
         s, t, fl, cm = self.s, self.t, self.flat, self.comm
         gv = fl.grad_views
-        x = s._check_x(x_local)
-        n, dev, E = x.shape[0], x.device, s.mlp_dim
-        counts = self.counts if self.counts is not None else [n] * cm.world
-        N, lo = sum(counts), sum(counts[:cm.rank])
-        assert counts[cm.rank] == n, "counts[rank] must equal the local row count"
+        x, n, dev, E, counts, N, lo = self._shard(x_local)
         shared_seed, local_seed = self._seeds()
 
         # ---- teacher: local rows -> partial pool -> global (stats, z); scores need the global denominators
@@ -401,11 +434,7 @@ class ShardedBagTrainer:
             wp = t.predictor.weight.data if t.attn2score else None
             st_t = ops.abmil_pool_fwd(t._scorer(), Ht, None, wp=wp, no_backward=True)
             gstats, t_feat = self._pool_merge(st_t, E, dev)
-            if t.attn2score:
-                sc_loc = ops.pseudo_score(st_t.s, gstats, st_t.cproj, t.predictor.bias.data)
-            else:
-                sc_loc = ops.softmax_from_stats(st_t.s, gstats)
-            score = cm.all_gather_rows(sc_loc, counts)
+            score = cm.all_gather_rows(self._teacher_score(st_t, gstats), counts)
             del Ht, st_t
 
         # ---- select: replicated, identical on every rank (shared generator / injected draws)
@@ -435,10 +464,7 @@ class ShardedBagTrainer:
         gstats, z = self._pool_merge(st, E, dev)
 
         # ---- head (replicated): predictor + CE + distillation and their gradients
-        t_in = t_feat if self.aux_alpha != 0. else None
-        logits, losses, g_z, _, _ = ops.head_fwd_bwd(z, t_in, s.predictor.weight.data, s.predictor.bias.data, label,
-                                                     temp_t=float(s.temp_t), main_alpha=self.main_alpha, aux_alpha=self.aux_alpha,
-                                                     d_wp=gv["predictor.weight"], d_bp=gv["predictor.bias"])
+        logits, losses, g_z = self._head(z, t_feat, label, gv["predictor.weight"], gv["predictor.bias"])
 
         # ---- backward: the pool backward sees the BAG's softmax statistics and pooled feature
         st.stats.copy_(gstats)
@@ -457,27 +483,18 @@ class ShardedBagTrainer:
             g = ops.abmil_pool_bwd(sc, st, g_z, ops.transpose(att.attention[0].weight.data), grads=pool_g)
         dT2 = g["dT2"] if cm.rank == 0 else torch.zeros_like(z_tok)
         cm.all_reduce_sum(dT2)                                     # = broadcast from rank 0
-        mgr = {"d_ln_w": gv["merge.norm.weight"], "d_ln_b": gv["merge.norm.bias"], "d_wkv": gv["merge.attn.to_kv.weight"],
-               "d_wq": gv["merge.attn.to_q.weight"], "d_wo": gv["merge.attn.to_out.0.weight"], "d_bo": gv["merge.attn.to_out.0.bias"]}
-        mg = ops.merge_bwd(s._merge_w(plan, need_t=True, q=q_old), Hm, dT2, mws, grads=mgr)
+        mg = ops.merge_bwd(s._merge_w(plan, need_t=True, q=q_old), Hm, dT2, mws, grads=self._merge_grads())
         if n_merge:
             dH[n_stay:] = mg["dX"].index_select(0, merge_pos)
         ops.act_bwd(dH, H, PRE, L.act_code(s.act, _FEATURE_ACTS), s.dropout_p, local_seed, None, rows_local,
                     colsum_out=gv["feature.0.bias"], want_colsum=True)
         ops.gemm_tn(dH, x, out=gv["feature.0.weight"], rows=rows_local, splits=8 if n_loc >= 2048 else 1,
                     prec="f32" if s.prec == "f32" else "bf16x3", M=n_loc)
-        if cm.rank != 0:                                           # replicated terms: counted once in the SUM
-            for name in fl.train_names:
-                if name.startswith("predictor.") or name.startswith("merge."):
-                    gv[name].zero_()
-        cm.all_reduce_sum(fl.grad[:fl.n_train])
+        self._zero_replicated()
+        self._sum_grads()
 
         # ---- optimiser + EMA teacher (replicated, identical inputs on every rank)
-        self.step_count += 1
         ops.tick(self.opt_step)
-        ops.adam_ema(fl.student, fl.grad, fl.m, fl.v, None if fl.same_teacher else fl.teacher, fl.n_train, self.step_count, lr=self.lr, beta1=self.betas[0],
-                     beta2=self.betas[1], eps=self.eps, weight_decay=self.wd, grad_scale=1.0, ema_mm=self.mm, zero_grad=True,
-                     step_dev=self.opt_step)
-        self.last = {"logits": logits, "losses": losses, "patch_num": N, "keep_num": Lk + s.merge.k, "rows": rows,
-                     "len_keep": len_keep, "score": score, "teacher_feat": t_feat}
+        self._update()
+        self._set_last(logits, losses, N, Lk, rows, len_keep, score, t_feat)
         return logits, losses

@@ -30,10 +30,7 @@ from . import nystrom as NY
 from . import ops
 from .mhim import BagPlan, _FeatureFn, _MergeFn, _FEATURE_ACTS
 from .nystrom_sharded import sharded_sattention
-
-
-def _all_to_all_rows(comm, send, send_counts, recv_counts):
-    return comm.all_to_all_rows(send, send_counts, recv_counts)
+from .sharded import partition_rows
 
 
 class ExchangePlan:
@@ -100,7 +97,7 @@ class _AssembleTokens(torch.autograd.Function):
             block[b:].zero_()
             got = None
         else:
-            got = _all_to_all_rows(comm, rows_local.contiguous(), plan.send_counts, plan.recv_counts)
+            got = comm.all_to_all_rows(rows_local.contiguous(), plan.send_counts, plan.recv_counts)
         if got is None:
             pass
         elif plan.place is None:                             # bag order (or world 1): one contiguous run
@@ -133,7 +130,7 @@ class _AssembleTokens(torch.autograd.Function):
             dgot = dblock[plan.run[0]:plan.run[1]]
         else:
             dgot = dblock.index_select(0, plan.place) if plan.place.numel() else dblock[:0]
-        drows = _all_to_all_rows(comm, dgot, plan.recv_counts, plan.send_counts)
+        drows = comm.all_to_all_rows(dgot, plan.recv_counts, plan.send_counts)
         dtail = None
         if ctx.tail_shape is not None:
             dtail = torch.zeros(ctx.tail_shape, device=dblock.device)
@@ -177,12 +174,8 @@ def transmil_step(tr, x_local, label, perm=None, ids_shuffle=None, i=None):
     Adam + EMA).  Returns (logits [C], losses [3]); identical on every rank."""
     s, t, fl, cm = tr.s, tr.t, tr.flat, tr.comm
     gv = fl.grad_views
-    x = s._check_x(x_local)
-    n, dev, E = x.shape[0], x.device, s.mlp_dim
+    x, n, dev, E, counts, N, lo = tr._shard(x_local)
     W = cm.world
-    counts = tr.counts if tr.counts is not None else [n] * W
-    N, lo = sum(counts), sum(counts[:cm.rank])
-    assert counts[cm.rank] == n, "counts[rank] must equal the local row count"
     bounds = [sum(counts[:q]) for q in range(W + 1)]
     shared_seed, local_seed = tr._seeds()
     mix = lambda a: (local_seed + a * 0x9E3779B97F4A7C15) & 0xFFFFFFFFFFFFFFFF
@@ -225,7 +218,6 @@ def transmil_step(tr, x_local, label, perm=None, ids_shuffle=None, i=None):
 
     # ---- select: replicated
     rows, len_keep, Lk, R = s.student_rows(N, i, score, perm=perm, ids_shuffle=ids_shuffle, generator=None, seed=shared_seed)
-    from .sharded import partition_rows
     if W == 1:                                                                           # (no host sync: every row is local)
         rows_local, n_stay, merge_pos = rows, Lk, torch.arange(rows.numel() - Lk, device=dev)
     else:
@@ -259,12 +251,9 @@ def transmil_step(tr, x_local, label, perm=None, ids_shuffle=None, i=None):
     z = sharded_sattention(s.online_encoder, blk, pad_s, 1 + Lk + k, cm, seeds=(mix(5), mix(6)), training=True)
 
     # ---- head (replicated)
-    t_in = t_feat.view(-1) if tr.aux_alpha != 0. else None
     d_wp = gv["predictor.weight"] if first else torch.empty_like(gv["predictor.weight"])
     d_bp = gv["predictor.bias"] if first else torch.empty_like(gv["predictor.bias"])
-    logits, losses, g_z, _, _ = ops.head_fwd_bwd(z.detach(), t_in, s.predictor.weight.data, s.predictor.bias.data, label,
-                                                 temp_t=float(s.temp_t), main_alpha=tr.main_alpha, aux_alpha=tr.aux_alpha,
-                                                 d_wp=d_wp, d_bp=d_bp, accumulate=first)
+    logits, losses, g_z = tr._head(z.detach(), t_feat.view(-1), label, d_wp, d_bp, accumulate=first)
 
     # ---- backward into the flat buffer, ONE all-reduce, Adam + EMA
     for name in fl.train_names:
@@ -279,11 +268,8 @@ def transmil_step(tr, x_local, label, perm=None, ids_shuffle=None, i=None):
         p_.grad = None
     if grads:
         torch._foreach_add_(views, grads)
-    cm.all_reduce_sum(fl.grad[:fl.n_train])
-    tr.step_count += 1
+    tr._sum_grads()
     ops.tick(tr.opt_step)
-    ops.adam_ema(fl.student, fl.grad, fl.m, fl.v, None if fl.same_teacher else fl.teacher, fl.n_train, tr.step_count, lr=tr.lr, beta1=tr.betas[0], beta2=tr.betas[1],
-                 eps=tr.eps, weight_decay=tr.wd, grad_scale=1.0, ema_mm=tr.mm, zero_grad=True, step_dev=tr.opt_step)
-    tr.last = {"logits": logits, "losses": losses, "patch_num": N, "keep_num": Lk + k, "rows": rows, "len_keep": len_keep,
-               "score": score, "teacher_feat": t_feat}
+    tr._update()
+    tr._set_last(logits, losses, N, Lk, rows, len_keep, score, t_feat)
     return logits, losses

@@ -13,7 +13,7 @@ DEV = "cuda"
 T, E = 2048, 512
 
 
-def _layer_and_input():
+def _layer_and_input(n=T):
     from mhim_mil_amd import nystrom as NY
     torch.manual_seed(11)
     layer = NY.TransLayer(E)
@@ -22,8 +22,8 @@ def _layer_and_input():
         layer.norm.bias.add_(0.1 * torch.randn(E))
         layer.attn.to_out[0].bias.add_(0.05 * torch.randn(E))
     g = torch.Generator().manual_seed(12)
-    x = torch.randn(T, E, generator=g) * 0.7
-    dy = torch.randn(T, E, generator=g) * 0.1
+    x = torch.randn(n, E, generator=g) * 0.7
+    dy = torch.randn(n, E, generator=g) * 0.1
     return layer, x, dy
 
 
@@ -77,6 +77,89 @@ def test_shard_alignment_is_checked():
     layer = NY.TransLayer(E).to(DEV).eval()
     with pytest.raises(L.MhimxError):
         sharded_trans_layer(layer, torch.randn(200, E, device=DEV))            # (a world of one: 200 tokens are not 256 landmarks' worth)
+
+
+# ---------------------------------------------------------------------------------------------------- world 1, in process
+# (512, 0) / (300, 212): both forms on gemm_nt and the strided products, without and with front padding; (2304, 0) / (2100, 204): both on
+# the projection kernel and the weight-gradient pair (the replica decides from n, the block from Tr = n + pad), the second with front
+# padding and the cls row inside the block
+@pytest.mark.parametrize("need_attn", [False, True])
+@pytest.mark.parametrize("n,pad", [(512, 0), (300, 212), (2304, 0), (2100, 204)])
+def test_world1_block_equals_the_replica_layer(n, pad, need_attn):
+    """ShardedTransLayerFn on ONE block [zeros(pad) | x] against TransLayerFn on x (which pads inside): outputs, input gradient, every
+    parameter gradient and, with need_attn, the cls row's attention map and v - at the bounds the multi-rank runs above are held to."""
+    from mhim_mil_amd.nystrom_sharded import sharded_trans_layer
+    layer, x, dy = _layer_and_input(n)
+    layer = layer.to(DEV).eval()
+    params = list(layer.parameters())
+    names = [k for k, _ in layer.named_parameters()]
+    xd, dyd = x.to(DEV).requires_grad_(), dy.to(DEV)
+    r = layer(xd, need_attn, False, 0, None, False)
+    y_ref, rest_ref = (r[0], r[1:]) if need_attn else (r, ())
+    g_ref = torch.autograd.grad(y_ref, [xd] + params, dyd)
+    xs = torch.cat([torch.zeros(pad, E), x]).to(DEV).requires_grad_()
+    r = sharded_trans_layer(layer, xs, pad=pad, need_attn=need_attn)
+    y, rest = (r[0], r[1:]) if need_attn else (r, ())
+    g = torch.autograd.grad(y, [xs] + params, torch.cat([torch.zeros(pad, E, device=DEV), dyd]))
+    y, y_ref = y.detach(), y_ref.detach()
+    rel = lambda a, b: float((a.double() - b.double()).abs().max() / b.double().abs().max())
+    print(f"y {rel(y[pad:], y_ref):.2e} dx {rel(g[0][pad:], g_ref[0]):.2e} " + " ".join(f"{k} {rel(a, b):.2e}" for k, a, b in zip(names, g[1:], g_ref[1:])))
+    assert rel(y[pad:], y_ref) < 2e-5
+    assert rel(g[0][pad:], g_ref[0]) < 2e-4
+    for k, a, b in zip(names, g[1:], g_ref[1:]):
+        assert rel(a, b) < 5e-4, (k, rel(a, b))
+    if need_attn:
+        (attn, v), (attn_ref, v_ref) = rest, rest_ref
+        print(f"v {rel(v[pad + 1:], v_ref):.2e} attn max abs {float((attn[:, pad + 1:] - attn_ref).abs().max()):.2e}")
+        np.testing.assert_allclose(attn[:, pad + 1:].cpu().numpy(), attn_ref.cpu().numpy(), atol=1e-6, rtol=2e-3)
+        assert rel(v[pad + 1:], v_ref) < 2e-5
+
+
+@pytest.mark.parametrize("Tb", [512, 2304])
+def test_world1_block_dropout_redraws_its_mask(Tb):
+    """to_out's dropout in the sharded layer, no tick: Tb = 512 draws in gemm_nt's stream (mhimx_dropout_apply), Tb = 2304 in the projection
+    kernel's (mhimx_dropout_apply_proj), and the backward re-applies that mask.  Built as test_fused_layer_output_dropout_on_projection_kernel
+    (tests/test_nystrom_gpu.py): the same layer with the dropout off, masked by what the matching call gives on a tensor of ones (keep / (1 - p)
+    with the stream's own quantisation of p), through autograd."""
+    from mhim_mil_amd import _lib as L
+    from mhim_mil_amd import nystrom as ny
+    from mhim_mil_amd.nystrom_sharded import sharded_trans_layer
+    torch.manual_seed(3)
+    p, seed = 0.1, 1234
+    layer = ny.TransLayer(E).to(DEV)
+    with torch.no_grad():
+        for q in layer.parameters():
+            q.normal_(0, 0.05)
+        layer.norm.weight.add_(1.0)
+    g = torch.Generator().manual_seed(41)
+    x = (torch.randn(Tb, E, generator=g) * 0.5).to(DEV).requires_grad_()
+    ww = torch.randn(Tb, E, generator=g).to(DEV)
+
+    def close(got, ref, rtol, what):
+        got, ref = got.detach().double(), ref.detach().double()
+        err, scale = (got - ref).abs().max().item(), ref.abs().max().item() + 1e-30
+        print(f"{what}: max err {err:.3e} vs scale {scale:.3e}")
+        assert err <= rtol * scale, f"{what}: max err {err:.3e} vs scale {scale:.3e}"
+
+    y = sharded_trans_layer(layer, x, drop_p=p, seed=seed)
+    y0 = sharded_trans_layer(layer, x)
+    lin, lin0 = (y - x).detach(), (y0 - x)
+    ones, kept = torch.ones_like(ww), torch.empty_like(ww)
+    fn = L.lib().mhimx_dropout_apply_proj if Tb >= 2048 else L.lib().mhimx_dropout_apply
+    L.check(fn(ny._st(), ny._ptr(ones), ny._ptr(kept), Tb, E, float(p), seed, None), "dropout_apply")
+    keep = (kept != 0).float()
+    assert ((lin != 0).float() - keep).abs().sum().item() <= 3 and not ((lin != 0) & (keep == 0)).any()
+    assert abs(keep.mean().item() - (1 - p)) < 0.01
+    close(lin, lin0.detach() * kept, 1e-4, "branch")
+    params = [x] + list(layer.parameters())
+    got = torch.autograd.grad((y * ww).sum(), params)
+    ref = torch.autograd.grad(((x + lin0 * kept) * ww).sum(), params)
+    for nm, gi, ri in zip(["x"] + [k for k, _ in layer.named_parameters()], got, ref):
+        close(gi, ri, 2e-4, nm)
+    # the same seed draws the same mask again; another seed another one
+    assert torch.equal(sharded_trans_layer(layer, x, drop_p=p, seed=seed), y)
+    y3 = sharded_trans_layer(layer, x, drop_p=p, seed=seed + 1)
+    assert not torch.equal((y3 - x) != 0, lin != 0)
 
 
 # ---------------------------------------------------------------------------------------------------- encoder level
