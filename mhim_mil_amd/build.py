@@ -22,7 +22,7 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc", "-Wno-unused-result"]
 # (no -ffp-contract here: hipcc's default, fast-honor-pragmas, is what csrc/optim.hip's mul_rounded relies on to keep a product out of
 # the addition that follows it; a plain -ffp-contract=fast would fuse the two again)
-FLAGS += os.environ.get("MHIMX_EXTRA_FLAGS", "").split()          # side builds only (e.g. -DMHIMX_SEL_PROF)
+FLAGS += os.environ.get("MHIMX_EXTRA_FLAGS", "").split()          # side builds only (e.g. -DPW_PROF=2)
 # The SLP vectorizer pairs scalar fp32 FMAs into v_pk_fma_f32 and, where the two lanes want the ODD register of a pair, sets op_sel
 # to swizzle it into the low half.  That form dropped its term in lanes 48..63 about once per 500 launches of merge2_grads1 when a second
 # process shared the GPU (tools/exp_merge_forensic.py, DESIGN section 5: 38 events in 30 000 passes, 0 in 60 000 without it), so every

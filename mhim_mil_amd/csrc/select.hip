@@ -16,14 +16,6 @@
 
 namespace mhimx {
 
-#ifdef MHIMX_SEL_PROF                                           // phase stamps of select_small_kernel: tools/exp_select.py
-__device__ unsigned long long sel_prof[32];
-#define SEL_STAMP(i) do { __syncthreads(); if (threadIdx.x == 0) sel_prof[i] = wall_clock64(); } while (0)
-#else
-#define SEL_STAMP(i)
-#endif
-
-
 template <bool VOTE>
 __global__ __launch_bounds__(SEL_THREADS) void select_kernel(
     const float* __restrict__ score_all, int64_t N, int k, int n_sel, int largest, const int64_t* __restrict__ perm,
@@ -196,251 +188,24 @@ __global__ __launch_bounds__(SEL_THREADS) void select_kernel(
 
 
 // ------------------------------------------------------------------------------------------------
-// Fast path for N <= 16384 (a bag of one slide at 20x is ~1e4 patches): every thread keeps its <= 16 keys
-// in registers (scores are read from HBM exactly once), flags are an LDS bitmap, the k candidates are ordered
-// by rank counting (k^2/1024 LDS compares per thread, no barriers) when k <= 2048.
+// Fast path for N <= 16384: select_small_body (select_dev.hpp) on one bag - or, blockIdx.z = bag, on every bag of an accumulation window
+// (BagBatch, common.hpp: the bag's pointers and its seed).
 // ------------------------------------------------------------------------------------------------
-
-// Thread t owns the CONTIGUOUS instances [t*KPT, (t+1)*KPT): every order-dependent step (ties lowest index first,
-// ascending compaction) then costs ONE block scan of per-thread counts instead of one per 1024-instance chunk.
-// LEAN: the production call (mhimx_select_rows without a mask-id list: device-drawn subsets, no injected permutation, no earlier
-// mask, no top-k list) - the branches of every other form are compiled out.  The kernel runs ONCE per step on one workgroup: its
-// 4 151 instructions (~25 KB) are fetched cold by 16 waves; the lean instantiation has 3 452.
 template <int KPT, bool LEAN = false>
 __global__ __launch_bounds__(SEL_THREADS) void select_small_kernel(
     const float* __restrict__ score, int N, int k, int n_sel, int largest, const int64_t* __restrict__ perm,
     const int64_t* __restrict__ other, int64_t n_other, int64_t* __restrict__ mask_ids, int64_t* __restrict__ len_keep_dev,
     int64_t* __restrict__ topk_out, int P, int use_rand, uint64_t rand_seed0, const uint64_t* __restrict__ tick, int merge_R,
-    int64_t* __restrict__ rows_out,
-    int64_t* __restrict__ rows_img /* optional (round 6): the same rows in the order of the projection's dPRE image when its producers write it -
-                                      [rows that stay | 0 ... | rows to merge from position img_off | 0 ... to a multiple of 32] */,
-    int img_off, BagBatch bb /* common.hpp: one workgroup per bag of an accumulation window */) {
+    int64_t* __restrict__ rows_out, int64_t* __restrict__ rows_img, int img_off, BagBatch bb) {
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   if (blockIdx.z) {
     MHIMX_BAG(score); MHIMX_BAG(perm); MHIMX_BAG(other); MHIMX_BAG(mask_ids); MHIMX_BAG(len_keep_dev); MHIMX_BAG(topk_out); MHIMX_BAG(rows_out);
     MHIMX_BAG(rows_img);
     rand_seed0 = bag_sel_seed(rand_seed0, bb);
   }
-  const uint64_t rand_seed = eff_seed(rand_seed0, tick);
-  uint64_t* keys = reinterpret_cast<uint64_t*>(smem_raw);               // [P] gathered, [P] sorted / random keys
-  uint64_t* sorted = keys + P;
-  uint32_t* hist = reinterpret_cast<uint32_t*>(sorted + P);             // [4][2048]
-  uint32_t* wave_tot = hist + SEL_COPIES * SEL_BINS;                    // [16]
-  uint32_t* misc = wave_tot + SEL_WAVES;                                // [8]
-  uint32_t* bitmap = misc + 8;                                          // [512] = 16384 bits
-  uint32_t* rank = bitmap + 512;                                        // [P]
-  uint16_t* klist = reinterpret_cast<uint16_t*>(rank + P);              // [N] kept rows in ascending order (the Merge draw indexes it)
-  uint16_t* stage = reinterpret_cast<uint16_t*>(smem_raw);              // [N] row list staging (aliases keys / sorted / hist: last phase)
-  const int tid = threadIdx.x;
-  const bool lg = largest != 0;
-  const int i0 = tid * KPT;
-
-  SEL_STAMP(8);
-  uint32_t key[KPT];
-  bool valid[KPT];
-#pragma unroll
-  for (int j = 0; j < KPT; ++j) {
-    valid[j] = (i0 + j) < N;
-    key[j] = valid[j] ? mono32(score[i0 + j], lg) : 0u;
-  }
-  SEL_STAMP(0);
-  for (int i = tid; i < 512; i += SEL_THREADS) bitmap[i] = 0;
-  if (tid == 0) misc[2] = 0;
-
-  // ---- 1. threshold
-  uint32_t remaining, n_eq;
-  const uint32_t T = radix_select_regs<KPT, false>(key, valid, (uint32_t)k, hist, wave_tot, misc, &remaining, &n_eq);
-
-  SEL_STAMP(1);
-  // ---- 2. gather exactly k keys (ties: lowest index first)
-  uint32_t eq_rank = 0;
-  if (remaining != n_eq) {                 // only some of the T-valued keys belong to the top-k: rank them by index
-    uint32_t neq = 0;
-#pragma unroll
-    for (int j = 0; j < KPT; ++j) neq += (valid[j] && key[j] == T) ? 1u : 0u;
-    uint32_t tot;
-    eq_rank = block_scan_excl(neq, wave_tot, &tot);
-  }
-  // (one LDS atomic per WAVE reserves the wave's slots: k same-address returning atomics would serialise)
-  bool take[KPT];
-  uint32_t ntake = 0;
-#pragma unroll
-  for (int j = 0; j < KPT; ++j) {
-    bool t = valid[j] && key[j] > T;
-    if (valid[j] && key[j] == T) { t = remaining == n_eq || eq_rank < remaining; ++eq_rank; }
-    take[j] = t;
-    ntake += t ? 1u : 0u;
-  }
-  {
-    // positions in THREAD order (one block scan): the device-drawn subset below picks candidates by their position in this list,
-    // so the list must not depend on which wave reserves its slots first
-    uint32_t tot;
-    uint32_t pos = block_scan_excl(ntake, wave_tot, &tot);
-#pragma unroll
-    for (int j = 0; j < KPT; ++j)
-      if (take[j]) keys[pos++] = ((uint64_t)key[j] << 32) | (uint64_t)(0xFFFFFFFFu - (uint32_t)(i0 + j));
-  }
-  __syncthreads();
-
-  SEL_STAMP(2);
-  // ---- 3. order the candidates: (value desc, index asc) == key desc
-  // (the device-drawn random subset below depends on the candidate SET only: no ordering needed unless it is returned)
-  const bool dev_rand = LEAN || (use_rand && !perm && n_sel < k);
-  // The device-drawn subset ALWAYS picks by position in `keys` - the candidates in ascending row index (thread order) - whether or not the
-  // value-ordered list is wanted as well: the same (seed, tick) masks the same rows with and without topk_out / LEAN.
-  const uint64_t* cand = keys;
-  if (LEAN || (dev_rand && !topk_out)) {
-    // (no value-ordered list needed)
-  } else if (k <= 2048) {
-    for (int j = tid; j < k; j += SEL_THREADS) {
-      const uint64_t mine = keys[j];
-      int r = 0;
-      for (int q = 0; q < k; ++q) r += keys[q] > mine ? 1 : 0;
-      sorted[r] = mine;
-    }
-    __syncthreads();
-  } else {
-    for (int j = tid; j < P; j += SEL_THREADS) sorted[j] = j < k ? keys[j] : 0ull;
-    __syncthreads();
-    for (int size = 2; size <= P; size <<= 1)
-      for (int stride = size >> 1; stride > 0; stride >>= 1) {
-        for (int t = tid; t < (P >> 1); t += SEL_THREADS) {
-          const int lo = 2 * t - (t & (stride - 1)), hi = lo + stride;
-          const bool desc = ((lo & size) == 0);
-          const uint64_t a = sorted[lo], b = sorted[hi];
-          if ((a < b) == desc) { sorted[lo] = b; sorted[hi] = a; }
-        }
-        __syncthreads();
-      }
-  }
-  if (!LEAN && topk_out)
-    for (int j = tid; j < k; j += SEL_THREADS) topk_out[j] = (int64_t)(0xFFFFFFFFu - (uint32_t)(sorted[j] & 0xFFFFFFFFull));
-
-  SEL_STAMP(3);
-  // ---- 4. flags (LDS bitmap)
-  const bool has_other = !LEAN && other != nullptr && n_other > 0;
-  const int len_keep_simple = N - n_sel;
-  if (dev_rand) {
-    // masking.py:66-71 keeps a uniformly random n_sel-subset of the k candidates.  Drawn here without a host permutation and without
-    // ranking random keys (k^2 / 1024 compares per thread were 3 us of this kernel): candidate pi(i), i < n_sel, of a keyed
-    // pseudo-random permutation pi of the k list positions (common.hpp: feistel_small) - one short dependent chain per pick.
-    // (both round keys depend on the WHOLE seed: with k1 a function of the high word alone, seeds that differ in the low word only - small
-    // integers - shared it, and the 4-round network on a 6-bit domain masked one of 56 candidates 6.5 sigma off its share over 2000 seeds;
-    // tools/feistel_sim.py, tests/test_round4_gpu.py::test_select_rows_draws_are_fair_on_small_lists)
-    const uint32_t k0 = mix32((uint32_t)rand_seed ^ 0x9E3779B9u), k1 = mix32((uint32_t)(rand_seed >> 32) + 0x85EBCA6Bu + k0 * 0x632BE5ABu);
-    const int bits = small_perm_bits((uint32_t)k);
-    for (int i = tid; i < n_sel; i += SEL_THREADS) {
-      const uint32_t j = feistel_small((uint32_t)i, (uint32_t)k, bits, k0, k1);
-      const uint32_t idx = 0xFFFFFFFFu - (uint32_t)(cand[j] & 0xFFFFFFFFull);
-      atomicOr(&bitmap[idx >> 5], 1u << (idx & 31));
-      if (!LEAN && !has_other && mask_ids) mask_ids[len_keep_simple + i] = (int64_t)idx;
-    }
-  } else if (!LEAN) {
-    for (int j = tid; j < n_sel; j += SEL_THREADS) {
-      const int64_t src = perm ? perm[j] : (int64_t)j;
-      const uint32_t idx = 0xFFFFFFFFu - (uint32_t)(sorted[src] & 0xFFFFFFFFull);
-      atomicOr(&bitmap[idx >> 5], 1u << (idx & 31));
-      if (!has_other && mask_ids) mask_ids[len_keep_simple + j] = (int64_t)idx;
-    }
-  }
-  if (has_other)
-    for (int64_t j = tid; j < n_other; j += SEL_THREADS) {
-      const uint32_t idx = (uint32_t)other[j];
-      atomicOr(&bitmap[idx >> 5], 1u << (idx & 31));
-    }
-  __syncthreads();
-
-  SEL_STAMP(4);
-  // ---- 5. ordered compaction: kept ids ascending (and, for a union with an earlier mask, masked ids ascending)
-  bool kv[KPT];
-  uint32_t nkeep = 0;
-#pragma unroll
-  for (int j = 0; j < KPT; ++j) {
-    const int i = i0 + j;
-    kv[j] = valid[j] && !((bitmap[i >> 5] >> (i & 31)) & 1u);
-    nkeep += kv[j] ? 1u : 0u;
-  }
-  uint32_t kept_total;
-  uint32_t kpos = block_scan_excl(nkeep, wave_tot, &kept_total);
-  const uint32_t kpos0 = kpos;
-  if (!LEAN && mask_ids) {
-#pragma unroll
-    for (int j = 0; j < KPT; ++j)
-      if (kv[j]) mask_ids[kpos++] = i0 + j;
-    if (has_other) {
-      uint32_t nm = 0;
-#pragma unroll
-      for (int j = 0; j < KPT; ++j) nm += (valid[j] && !kv[j]) ? 1u : 0u;
-      uint32_t mt;
-      uint32_t mpos = kept_total + block_scan_excl(nm, wave_tot, &mt);
-#pragma unroll
-      for (int j = 0; j < KPT; ++j)
-        if (valid[j] && !kv[j]) mask_ids[mpos++] = i0 + j;
-    }
-  }
-  if (!LEAN && tid == 0 && len_keep_dev) *len_keep_dev = (int64_t)kept_total;
-  SEL_STAMP(5);
-  if (!LEAN && !rows_out) return;
-
-  // ---- 6. Merge.masking (merge.py:158-176): a uniformly random R-subset of the kept rows is merged away.  Same device, the same
-  // draw as step 4: the kept rows go to an LDS list in ascending order, row klist[pi2(i)], i < R, of a second keyed permutation (of the
-  // Lrows list positions) is merged (flags in the bitmap, which step 5 has finished reading), then ordered compactions ->
-  // rows_out = [kept rows that stay (ascending) | rows to merge (ascending)].  (A random key per kept row + a radix select of the R
-  // largest was 4.1 us of this kernel.)  The pool is order independent, so the reference's random ORDER of the kept rows is not
-  // reproduced (only fp summation order differs).
-  const int Lrows = (int)kept_total;
-  const int Lk = Lrows - merge_R;
-  const bool partial = merge_R > 0 && merge_R < Lrows;
-  if (partial) {
-    uint32_t kp = kpos0;
-#pragma unroll
-    for (int j = 0; j < KPT; ++j)
-      if (kv[j]) klist[kp++] = (uint16_t)(i0 + j);
-    for (int i = tid; i < 512; i += SEL_THREADS) bitmap[i] = 0;
-    __syncthreads();
-    const uint32_t q1 = mix32((uint32_t)rand_seed * 0x9E3779B1u + 0xC2B2AE35u), q0 = mix32(((uint32_t)(rand_seed >> 17) ^ 0x85EBCA6Bu) + q1 * 0x632BE5ABu);
-    const int bits2 = small_perm_bits((uint32_t)Lrows);
-    for (int i = tid; i < merge_R; i += SEL_THREADS) {
-      const uint32_t row = klist[feistel_small((uint32_t)i, (uint32_t)Lrows, bits2, q0, q1)];
-      atomicOr(&bitmap[row >> 5], 1u << (row & 31));
-    }
-    __syncthreads();
-  }
-  SEL_STAMP(6);
-  bool mrg[KPT];
-  uint32_t nstay = 0, nmrg = 0;
-#pragma unroll
-  for (int j = 0; j < KPT; ++j) {
-    const int i = i0 + j;
-    const bool m = kv[j] && (merge_R >= Lrows || (partial && ((bitmap[i >> 5] >> (i & 31)) & 1u)));
-    mrg[j] = m;
-    nmrg += m ? 1u : 0u;
-    nstay += (kv[j] && !m) ? 1u : 0u;
-  }
-  // one scan for both lists (each total <= 16384 fits 16 bits).
-  // use_rand == 2: rows to merge FIRST ([merge | stay]: lets the caller keep [stay rows | merged tokens] contiguous)
-  uint32_t t2;
-  const uint32_t packed = block_scan_excl(nstay | (nmrg << 16), wave_tot, &t2);
-  uint32_t spos = (use_rand == 2 ? (uint32_t)(Lrows - Lk) : 0u) + (packed & 0xFFFFu);
-  uint32_t mpos2 = (use_rand == 2 ? 0u : (uint32_t)Lk) + (packed >> 16);
-  SEL_STAMP(10);
-  // staged in LDS so the 8-byte row ids leave as full coalesced lines (a thread's own rows are 80 B apart from its
-  // neighbour's: 10 scattered store instructions per wave otherwise)
-#pragma unroll
-  for (int j = 0; j < KPT; ++j) {
-    if (!kv[j]) continue;
-    if (mrg[j]) stage[mpos2++] = (uint16_t)(i0 + j);
-    else stage[spos++] = (uint16_t)(i0 + j);
-  }
-  __syncthreads();
-  for (int i = tid; i < Lrows; i += SEL_THREADS) rows_out[i] = (int64_t)stage[i];
-  if (rows_img) {
-    const int mrg_n = Lrows - Lk, stay0 = use_rand == 2 ? mrg_n : 0, mrg0 = use_rand == 2 ? 0 : Lk;
-    const int end = (img_off + mrg_n + 31) / 32 * 32;
-    for (int p = tid; p < end; p += SEL_THREADS)
-      rows_img[p] = p < Lk ? (int64_t)stage[stay0 + p] : ((p >= img_off && p - img_off < mrg_n) ? (int64_t)stage[mrg0 + p - img_off] : (int64_t)0);
-  }
-  SEL_STAMP(7);
+  const SelectArgs a = {score, N, k, n_sel, largest, perm, other, n_other, mask_ids, len_keep_dev, topk_out, P, use_rand,
+                        eff_seed(rand_seed0, tick), merge_R, rows_out, rows_img, img_off};
+  select_small_body<KPT, LEAN>(a, smem_raw);
 }
 
 
@@ -662,10 +427,6 @@ __global__ __launch_bounds__(SEL_THREADS) void selm_compact_kernel(int64_t N, in
   }
 }
 
-static size_t select_small_smem(int P) {          // keys+sorted, hist, wave_tot, misc, bitmap, rank, kept list (the 32 KB row staging aliases the head)
-  return (size_t)2 * P * 8 + (size_t)(SEL_COPIES * SEL_BINS + SEL_WAVES + 8 + 512 + P) * 4 + 16384 * 2;
-}
-
 static int next_pow2(int v) {
   int p = 1;
   while (p < v) p <<= 1;
@@ -677,12 +438,6 @@ static size_t select_smem(int P) { return (size_t)P * 8 + (SEL_WAVES * 256 + SEL
 }  // namespace mhimx
 
 using namespace mhimx;
-
-#ifdef MHIMX_SEL_PROF                                           // phase stamps of select_small_kernel: tools/exp_select.py
-extern "C" int mhimx_sel_prof_read(unsigned long long* out) {
-  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(mhimx::sel_prof), 32 * 8);
-}
-#endif
 
 // flags [N]; large bags also: 3 histograms, per-workgroup counts, the candidate list (select_multi)
 static int64_t selm_extra_bytes() { return 3 * SELM_BINS * 4 + 2 * 16384 * 4 + 4 * SELM_MAXG * 4 + 256 + 16384 * 8; }
@@ -740,32 +495,25 @@ static int select_impl(void* stream, const float* score, int64_t N, int64_t k, i
   MHIMX_CHECK_ARG(ws_bytes >= N, "select_mask: workspace too small");
   const int P = next_pow2((int)k < 2 ? 2 : (int)k);
   if (N <= 16384 && P <= 4096) {                       // registers + LDS fast path
-    const size_t sm = select_small_smem(P);
-#define MHIMX_SEL_SMALL(KPT)                                                                                                   \
-    hipLaunchKernelGGL(select_small_kernel<KPT>, bgrid(1), dim3(SEL_THREADS), sm, (hipStream_t)stream, score, (int)N, (int)k,   \
-                       (int)n_sel, largest, perm, other, n_other, mask_ids, len_keep_dev, topk_sorted, P, g_use_rand,          \
-                       g_rand_seed, g_tick, g_merge_R, g_rows_out, g_rows_img, g_img_off, cur_batch())
-    MHIMX_ONCE_PER_DEVICE(
-        MHIMX_HIP(hipFuncSetAttribute((const void*)select_small_kernel<16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)select_small_smem(4096)));
-        MHIMX_HIP(hipFuncSetAttribute((const void*)select_small_kernel<10>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)select_small_smem(4096)));
-        MHIMX_HIP(hipFuncSetAttribute((const void*)select_small_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)select_small_smem(4096))));
     const bool lean = g_use_rand && g_rows_out && !perm && !other && !mask_ids && !len_keep_dev && !topk_sorted && n_sel < k;
-    if (lean) {
-#define MHIMX_SEL_LEAN(KPT)                                                                                                    \
-      hipLaunchKernelGGL((select_small_kernel<KPT, true>), bgrid(1), dim3(SEL_THREADS), sm, (hipStream_t)stream, score, (int)N, (int)k,   \
-                         (int)n_sel, largest, perm, other, n_other, mask_ids, len_keep_dev, topk_sorted, P, g_use_rand,        \
-                         g_rand_seed, g_tick, g_merge_R, g_rows_out, g_rows_img, g_img_off, cur_batch())
-      MHIMX_ONCE_PER_DEVICE(
-          MHIMX_HIP(hipFuncSetAttribute((const void*)select_small_kernel<16, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)select_small_smem(4096)));
-          MHIMX_HIP(hipFuncSetAttribute((const void*)select_small_kernel<10, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)select_small_smem(4096)));
-          MHIMX_HIP(hipFuncSetAttribute((const void*)select_small_kernel<4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)select_small_smem(4096))));
-      if (N <= 4096) MHIMX_SEL_LEAN(4);
-      else if (N <= 10240) MHIMX_SEL_LEAN(10);
-      else MHIMX_SEL_LEAN(16);
-#undef MHIMX_SEL_LEAN
-    } else if (N <= 4096) MHIMX_SEL_SMALL(4);
-    else if (N <= 10240) MHIMX_SEL_SMALL(10);
-    else MHIMX_SEL_SMALL(16);          // thread t owns instances [t*KPT, (t+1)*KPT)
+    const size_t sm = select_lds_bytes(P, lean);
+#define MHIMX_SEL_ATTR(KPT, LEAN)                                                                                             \
+    MHIMX_HIP(hipFuncSetAttribute((const void*)select_small_kernel<KPT, LEAN>, hipFuncAttributeMaxDynamicSharedMemorySize,      \
+                                  (int)select_lds_bytes(4096, LEAN)))
+    MHIMX_ONCE_PER_DEVICE(MHIMX_SEL_ATTR(16, false); MHIMX_SEL_ATTR(10, false); MHIMX_SEL_ATTR(4, false);
+                          MHIMX_SEL_ATTR(16, true); MHIMX_SEL_ATTR(10, true); MHIMX_SEL_ATTR(4, true));
+#undef MHIMX_SEL_ATTR
+#define MHIMX_SEL_SMALL(KPT, LEAN)                                                                                             \
+    hipLaunchKernelGGL((select_small_kernel<KPT, LEAN>), bgrid(1), dim3(SEL_THREADS), sm, (hipStream_t)stream, score, (int)N,   \
+                       (int)k, (int)n_sel, largest, perm, other, n_other, mask_ids, len_keep_dev, topk_sorted, P, g_use_rand,   \
+                       g_rand_seed, g_tick, g_merge_R, g_rows_out, g_rows_img, g_img_off, cur_batch())
+    if (lean) {                        // thread t owns instances [t*KPT, (t+1)*KPT)
+      if (N <= 4096) MHIMX_SEL_SMALL(4, true);
+      else if (N <= 10240) MHIMX_SEL_SMALL(10, true);
+      else MHIMX_SEL_SMALL(16, true);
+    } else if (N <= 4096) MHIMX_SEL_SMALL(4, false);
+    else if (N <= 10240) MHIMX_SEL_SMALL(10, false);
+    else MHIMX_SEL_SMALL(16, false);
 #undef MHIMX_SEL_SMALL
     MHIMX_LAUNCH_CHECK();
     return 0;

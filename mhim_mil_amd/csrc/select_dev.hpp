@@ -1,7 +1,9 @@
-// select_dev.hpp — the device pieces of the top-k selection that select.hip (one score vector: mhimx_select_mask, mhimx_select_rows)
-// and topk.hip (many vectors of different lengths in one launch chain: mhimx_topk_many) have in common: the order-preserving key,
-// block scans, the register-resident radix select and the digit-histogram threshold search.  Moved here text for text; every kernel of
-// select.hip keeps its code (tools/kernel_meta.py --diff against the build before).
+// select_dev.hpp — the device pieces that select.hip (one score vector: mhimx_select_mask, mhimx_select_rows), select_many.hip (the
+// production select of many bags in one launch: mhimx_select_rows_many) and topk.hip (many vectors of different lengths in one launch
+// chain: mhimx_topk_many) have in common: the order-preserving key, block scans, the register-resident radix select, the candidate stage
+// and the LDS sort of the one-workgroup forms, the whole body of the one-workgroup select (threshold, candidates, both keyed subset draws,
+// compaction, staged stores: select_small_body - one copy for select_small_kernel and select_many_kernel), and the digit-histogram
+// threshold search of the multi-workgroup forms.
 #pragma once
 #include "common.hpp"
 
@@ -209,6 +211,275 @@ MHIMX_DEV uint32_t radix_select_regs(const uint32_t (&key)[KPT], const bool (&va
   *remaining_out = remaining;
   *n_eq_out = n_eq;
   return prefix;
+}
+
+// The candidate stage of every one-workgroup form (select_small_kernel, select_many_kernel, topk_small_kernel): thread t owns the
+// CONTIGUOUS instances [t * KPT, (t + 1) * KPT) - scores are read from HBM exactly once (select_load_keys: the order-preserving keys and
+// valid[j], instance t * KPT + j exists; a step of its own so that a kernel can put LDS set-up under the load's latency) and every
+// order-dependent step costs ONE block scan of per-thread counts.  select_candidates leaves exactly k 64-bit keys
+// (value image << 32 | ~index) in keys[0, k), in ascending row index: the
+// k largest, ties lowest index first.  Ends with a barrier; `keys` may alias `hist`
+// (radix_select_regs ends with one: the histogram is dead by then).
+template <int KPT>
+MHIMX_DEV void select_load_keys(const float* __restrict__ score, int N, bool lg, uint32_t (&key)[KPT], bool (&valid)[KPT]) {
+  const int i0 = threadIdx.x * KPT;
+#pragma unroll
+  for (int j = 0; j < KPT; ++j) {
+    valid[j] = (i0 + j) < N;
+    key[j] = valid[j] ? mono32(score[i0 + j], lg) : 0u;
+  }
+}
+template <int KPT>
+MHIMX_DEV void select_candidates(const uint32_t (&key)[KPT], const bool (&valid)[KPT], uint32_t k, uint64_t* keys, uint32_t* hist,
+                                 uint32_t* wave_tot, uint32_t* misc) {
+  const int i0 = threadIdx.x * KPT;
+  // ---- threshold
+  uint32_t remaining, n_eq;
+  const uint32_t T = radix_select_regs<KPT, false>(key, valid, k, hist, wave_tot, misc, &remaining, &n_eq);
+  // ---- exactly k keys (ties: lowest index first)
+  uint32_t eq_rank = 0;
+  if (remaining != n_eq) {                 // only some of the T-valued keys belong to the top-k: rank them by index
+    uint32_t neq = 0;
+#pragma unroll
+    for (int j = 0; j < KPT; ++j) neq += (valid[j] && key[j] == T) ? 1u : 0u;
+    uint32_t tot;
+    eq_rank = block_scan_excl(neq, wave_tot, &tot);
+  }
+  bool take[KPT];
+  uint32_t ntake = 0;
+#pragma unroll
+  for (int j = 0; j < KPT; ++j) {
+    bool t = valid[j] && key[j] > T;
+    if (valid[j] && key[j] == T) { t = remaining == n_eq || eq_rank < remaining; ++eq_rank; }
+    take[j] = t;
+    ntake += t ? 1u : 0u;
+  }
+  // positions in THREAD order (one block scan): the device-drawn subsets pick candidates by their position in this list, so the list
+  // must not depend on which wave reserves its slots first
+  uint32_t tot;
+  uint32_t pos = block_scan_excl(ntake, wave_tot, &tot);
+#pragma unroll
+  for (int j = 0; j < KPT; ++j)
+    if (take[j]) keys[pos++] = ((uint64_t)key[j] << 32) | (uint64_t)(0xFFFFFFFFu - (uint32_t)(i0 + j));
+  __syncthreads();
+}
+
+// bitonic sort of a[0, P) in LDS, descending, in place; P a power of two; every thread of the workgroup calls it (the caller's barrier
+// stands between its own writes of `a` and the call); ends with a barrier
+MHIMX_DEV void lds_bitonic_desc(uint64_t* a, int P) {
+  for (int size = 2; size <= P; size <<= 1)
+    for (int stride = size >> 1; stride > 0; stride >>= 1) {
+      for (int t = threadIdx.x; t < (P >> 1); t += SEL_THREADS) {
+        const int lo = 2 * t - (t & (stride - 1)), hi = lo + stride;
+        const bool desc = ((lo & size) == 0);
+        const uint64_t x = a[lo], y = a[hi];
+        if ((x < y) == desc) { a[lo] = y; a[hi] = x; }
+      }
+      __syncthreads();
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// The one-workgroup select of a bag of up to 16 384 rows (a bag of one slide at 20x is ~1e4 patches): select_small_kernel<KPT, LEAN>
+// (select.hip: one bag, or one per plane of a bag-batched launch) and select_many_kernel<KPT> (select_many.hip: one bag of a by-value table
+// per workgroup) are this body behind their own argument blocks.  Keys in registers, flags an LDS bitmap, the k candidates ordered by rank
+// counting (k^2 / 1024 LDS compares per thread, no barriers) when k <= 2048.
+// LEAN: the production call (device-drawn subsets, no injected permutation, no earlier mask, no id or top-k list) - the branches of every
+// other form are compiled out, and so are the LDS arrays only they use.  The kernel runs once per step on one workgroup and is fetched cold by
+// 16 waves: the lean instantiation is some 700 instructions shorter.
+// The bits of every form are pinned by oracle/mhim_oracle.py select_rows (tests/test_select_oracle_gpu.py).
+// ------------------------------------------------------------------------------------------------
+struct SelectArgs {
+  const float* score;
+  int N, k, n_sel, largest;
+  const int64_t *perm, *other;                 // full forms: an injected permutation of the candidates, an earlier mask to unite with
+  int64_t n_other;
+  int64_t *mask_ids, *len_keep_dev, *topk_out; // full forms
+  int P;                                       // pow2 >= max(k, 2): places the LDS arrays only
+  int use_rand;                                // 1: device-drawn subsets, rows = [stay | merge]; 2: [merge | stay]
+  uint64_t rand_seed;                          // eff_seed of the launch
+  int merge_R;
+  int64_t* rows_out;
+  int64_t* rows_img;   // optional: the same rows in the order of the projection's dPRE image when its producers write it -
+                       // [rows that stay | 0 ... | rows to merge from position img_off | 0 ... to a multiple of 32]
+  int img_off;
+};
+
+// dynamic LDS of the body: keys [P] u64 (+ sorted [P] u64 in the full forms) | hist [4][2048] | wave_tot [16] | misc [8] | bitmap [512] |
+// klist [16384] u16; the row staging ([N] u16, last phase) aliases keys / hist.  8 P + 67 680 bytes LEAN, 16 P + 67 680 otherwise.
+constexpr size_t select_lds_bytes(int P, bool lean) {
+  return (size_t)(lean ? 1 : 2) * P * 8 + (size_t)(SEL_COPIES * SEL_BINS + SEL_WAVES + 8 + 512) * 4 + 16384 * 2;
+}
+
+template <int KPT, bool LEAN>
+MHIMX_DEV void select_small_body(const SelectArgs& a, char* smem) {
+  const int N = a.N, k = a.k, n_sel = a.n_sel, P = a.P, use_rand = a.use_rand, merge_R = a.merge_R;
+  const int64_t* __restrict__ perm = a.perm;
+  const int64_t* __restrict__ other = a.other;
+  int64_t* __restrict__ mask_ids = a.mask_ids;
+  int64_t* __restrict__ topk_out = a.topk_out;
+  int64_t* __restrict__ rows_out = a.rows_out;
+  int64_t* __restrict__ rows_img = a.rows_img;
+  uint64_t* keys = reinterpret_cast<uint64_t*>(smem);                   // [P] the candidates, in ascending row index
+  uint64_t* sorted = keys + P;                                          // [P] the same by (value desc, index asc): full forms only
+  uint32_t* hist = reinterpret_cast<uint32_t*>(keys + (LEAN ? P : 2 * P));   // [4][2048]
+  uint32_t* wave_tot = hist + SEL_COPIES * SEL_BINS;                    // [16]
+  uint32_t* misc = wave_tot + SEL_WAVES;                                // [8]
+  uint32_t* bitmap = misc + 8;                                          // [512] = 16384 bits
+  uint16_t* klist = reinterpret_cast<uint16_t*>(bitmap + 512);          // [N] kept rows in ascending order (the Merge draw indexes it)
+  uint16_t* stage = reinterpret_cast<uint16_t*>(smem);                  // [N] row list staging (aliases keys / sorted / hist: last phase)
+  const int tid = threadIdx.x;
+  const int i0 = tid * KPT;
+  uint32_t key[KPT];
+  bool valid[KPT];
+  select_load_keys<KPT>(a.score, N, a.largest != 0, key, valid);
+  for (int i = tid; i < 512; i += SEL_THREADS) bitmap[i] = 0;
+
+  // ---- 1, 2. threshold; exactly k candidates in ascending row index
+  select_candidates<KPT>(key, valid, (uint32_t)k, keys, hist, wave_tot, misc);
+
+  // ---- 3. order the candidates: (value desc, index asc) == key desc
+  // The device-drawn subset ALWAYS picks by position in `keys` - the candidates in ascending row index - whether or not the value-ordered
+  // list is wanted as well: the same (seed, tick) masks the same rows with and without topk_out / LEAN.
+  const bool dev_rand = LEAN || (use_rand && !perm && n_sel < k);
+  if (LEAN || (dev_rand && !topk_out)) {
+    // (no value-ordered list needed)
+  } else if (k <= 2048) {
+    for (int j = tid; j < k; j += SEL_THREADS) {
+      const uint64_t mine = keys[j];
+      int r = 0;
+      for (int q = 0; q < k; ++q) r += keys[q] > mine ? 1 : 0;
+      sorted[r] = mine;
+    }
+    __syncthreads();
+  } else {
+    for (int j = tid; j < P; j += SEL_THREADS) sorted[j] = j < k ? keys[j] : 0ull;
+    __syncthreads();
+    lds_bitonic_desc(sorted, P);
+  }
+  if (!LEAN && topk_out)
+    for (int j = tid; j < k; j += SEL_THREADS) topk_out[j] = (int64_t)(0xFFFFFFFFu - (uint32_t)(sorted[j] & 0xFFFFFFFFull));
+
+  // ---- 4. flags (LDS bitmap)
+  const bool has_other = !LEAN && other != nullptr && a.n_other > 0;
+  const int len_keep_simple = N - n_sel;
+  if (dev_rand) {
+    // masking.py:66-71 keeps a uniformly random n_sel-subset of the k candidates.  Drawn here without a host permutation and without
+    // ranking random keys (k^2 / 1024 compares per thread were 3 us of this kernel): candidate pi(i), i < n_sel, of a keyed
+    // pseudo-random permutation pi of the k list positions (common.hpp: feistel_small) - one short dependent chain per pick.
+    // (both round keys depend on the WHOLE seed: with k1 a function of the high word alone, seeds that differ in the low word only - small
+    // integers - shared it, and the 4-round network on a 6-bit domain masked one of 56 candidates 6.5 sigma off its share over 2000 seeds;
+    // tools/feistel_sim.py, tests/test_round4_gpu.py::test_select_rows_draws_are_fair_on_small_lists)
+    const uint32_t k0 = mix32((uint32_t)a.rand_seed ^ 0x9E3779B9u), k1 = mix32((uint32_t)(a.rand_seed >> 32) + 0x85EBCA6Bu + k0 * 0x632BE5ABu);
+    const int bits = small_perm_bits((uint32_t)k);
+    for (int i = tid; i < n_sel; i += SEL_THREADS) {
+      const uint32_t j = feistel_small((uint32_t)i, (uint32_t)k, bits, k0, k1);
+      const uint32_t idx = 0xFFFFFFFFu - (uint32_t)(keys[j] & 0xFFFFFFFFull);
+      atomicOr(&bitmap[idx >> 5], 1u << (idx & 31));
+      if (!LEAN && !has_other && mask_ids) mask_ids[len_keep_simple + i] = (int64_t)idx;
+    }
+  } else if (!LEAN) {
+    for (int j = tid; j < n_sel; j += SEL_THREADS) {
+      const int64_t src = perm ? perm[j] : (int64_t)j;
+      const uint32_t idx = 0xFFFFFFFFu - (uint32_t)(sorted[src] & 0xFFFFFFFFull);
+      atomicOr(&bitmap[idx >> 5], 1u << (idx & 31));
+      if (!has_other && mask_ids) mask_ids[len_keep_simple + j] = (int64_t)idx;
+    }
+  }
+  if (has_other)
+    for (int64_t j = tid; j < a.n_other; j += SEL_THREADS) {
+      const uint32_t idx = (uint32_t)other[j];
+      atomicOr(&bitmap[idx >> 5], 1u << (idx & 31));
+    }
+  __syncthreads();
+
+  // ---- 5. ordered compaction: kept ids ascending (and, for a union with an earlier mask, masked ids ascending)
+  bool kv[KPT];
+  uint32_t nkeep = 0;
+#pragma unroll
+  for (int j = 0; j < KPT; ++j) {
+    const int i = i0 + j;
+    kv[j] = valid[j] && !((bitmap[i >> 5] >> (i & 31)) & 1u);
+    nkeep += kv[j] ? 1u : 0u;
+  }
+  uint32_t kept_total;
+  uint32_t kpos = block_scan_excl(nkeep, wave_tot, &kept_total);
+  const uint32_t kpos0 = kpos;
+  if (!LEAN && mask_ids) {
+#pragma unroll
+    for (int j = 0; j < KPT; ++j)
+      if (kv[j]) mask_ids[kpos++] = i0 + j;
+    if (has_other) {
+      uint32_t nm = 0;
+#pragma unroll
+      for (int j = 0; j < KPT; ++j) nm += (valid[j] && !kv[j]) ? 1u : 0u;
+      uint32_t mt;
+      uint32_t mpos = kept_total + block_scan_excl(nm, wave_tot, &mt);
+#pragma unroll
+      for (int j = 0; j < KPT; ++j)
+        if (valid[j] && !kv[j]) mask_ids[mpos++] = i0 + j;
+    }
+  }
+  if (!LEAN && tid == 0 && a.len_keep_dev) *a.len_keep_dev = (int64_t)kept_total;
+  if (!LEAN && !rows_out) return;
+
+  // ---- 6. Merge.masking (merge.py:158-176): a uniformly random R-subset of the kept rows is merged away.  Same device, the same
+  // draw as step 4: the kept rows go to an LDS list in ascending order, row klist[pi2(i)], i < R, of a second keyed permutation (of the
+  // Lrows list positions) is merged (flags in the bitmap, which step 5 has finished reading), then ordered compactions ->
+  // rows_out = [kept rows that stay (ascending) | rows to merge (ascending)].  (A random key per kept row + a radix select of the R
+  // largest was 4.1 us of this kernel.)  The pool is order independent, so the reference's random ORDER of the kept rows is not
+  // reproduced (only fp summation order differs).
+  const int Lrows = (int)kept_total;
+  const int Lk = Lrows - merge_R;
+  const bool partial = merge_R > 0 && merge_R < Lrows;
+  if (partial) {
+    uint32_t kp = kpos0;
+#pragma unroll
+    for (int j = 0; j < KPT; ++j)
+      if (kv[j]) klist[kp++] = (uint16_t)(i0 + j);
+    for (int i = tid; i < 512; i += SEL_THREADS) bitmap[i] = 0;
+    __syncthreads();
+    const uint32_t q1 = mix32((uint32_t)a.rand_seed * 0x9E3779B1u + 0xC2B2AE35u),
+                   q0 = mix32(((uint32_t)(a.rand_seed >> 17) ^ 0x85EBCA6Bu) + q1 * 0x632BE5ABu);
+    const int bits2 = small_perm_bits((uint32_t)Lrows);
+    for (int i = tid; i < merge_R; i += SEL_THREADS) {
+      const uint32_t row = klist[feistel_small((uint32_t)i, (uint32_t)Lrows, bits2, q0, q1)];
+      atomicOr(&bitmap[row >> 5], 1u << (row & 31));
+    }
+    __syncthreads();
+  }
+  bool mrg[KPT];
+  uint32_t nstay = 0, nmrg = 0;
+#pragma unroll
+  for (int j = 0; j < KPT; ++j) {
+    const int i = i0 + j;
+    const bool m = kv[j] && (merge_R >= Lrows || (partial && ((bitmap[i >> 5] >> (i & 31)) & 1u)));
+    mrg[j] = m;
+    nmrg += m ? 1u : 0u;
+    nstay += (kv[j] && !m) ? 1u : 0u;
+  }
+  // one scan for both lists (each total <= 16384 fits 16 bits).
+  // use_rand == 2: rows to merge FIRST ([merge | stay]: lets the caller keep [stay rows | merged tokens] contiguous)
+  uint32_t t2;
+  const uint32_t packed = block_scan_excl(nstay | (nmrg << 16), wave_tot, &t2);
+  uint32_t spos = (use_rand == 2 ? (uint32_t)(Lrows - Lk) : 0u) + (packed & 0xFFFFu);
+  uint32_t mpos2 = (use_rand == 2 ? 0u : (uint32_t)Lk) + (packed >> 16);
+  // staged in LDS so the 8-byte row ids leave as full coalesced lines (a thread's own rows are 80 B apart from its
+  // neighbour's: 10 scattered store instructions per wave otherwise)
+#pragma unroll
+  for (int j = 0; j < KPT; ++j) {
+    if (!kv[j]) continue;
+    if (mrg[j]) stage[mpos2++] = (uint16_t)(i0 + j);
+    else stage[spos++] = (uint16_t)(i0 + j);
+  }
+  __syncthreads();
+  for (int i = tid; i < Lrows; i += SEL_THREADS) rows_out[i] = (int64_t)stage[i];
+  if (rows_img) {
+    const int mrg_n = Lrows - Lk, stay0 = use_rand == 2 ? mrg_n : 0, mrg0 = use_rand == 2 ? 0 : Lk;
+    const int end = (a.img_off + mrg_n + 31) / 32 * 32;
+    for (int p = tid; p < end; p += SEL_THREADS)
+      rows_img[p] = p < Lk ? (int64_t)stage[stay0 + p] : ((p >= a.img_off && p - a.img_off < mrg_n) ? (int64_t)stage[mrg0 + p - a.img_off] : (int64_t)0);
+  }
 }
 
 constexpr int SELM_BINS = 2048;

@@ -2,7 +2,8 @@
 // vectors of different lengths in one call: the row lists of every bag of a ragged accumulation window, or of a validation chunk
 // (replaces the per-bag loop over mhim_modules/masking.py:9-88 + merge.py:158-176 that modules/mhim.py:341 runs once per slide).
 //
-// Bags of up to 16 384 rows: ONE launch, blockIdx.x = bag, the ragged form of select_small_kernel<KPT, LEAN = true> (select.hip).  The bag
+// Bags of up to 16 384 rows: ONE launch, blockIdx.x = bag, of the device body select_small_kernel<KPT, LEAN = true> runs (select_dev.hpp:
+// select_small_body - one copy of the threshold, the candidate list, both keyed draws, the compaction and the staged stores).  The bag
 // table travels by value (infer_tab.hpp's RG_PICK pattern: constant indices only); nothing is copied to the device, waited for or
 // allocated.  The launch uses ONE KPT - the class of its largest bag (4 / 10 / 16 keys per thread) - and one LDS size - from the largest
 // P = next_pow2(k) - for every bag.  A bag's bits depend on neither: thread t owns the contiguous rows [t * KPT, (t + 1) * KPT), so the
@@ -26,19 +27,14 @@ struct SelManyTab {
   int32_t N[MHIMX_INFER_MAX], k[MHIMX_INFER_MAX], n_sel[MHIMX_INFER_MAX], merge_R[MHIMX_INFER_MAX];
 };
 
-// LDS: keys [P] u64 | hist [4][2048] | wave_tot [16] | misc [8] | bitmap [512] | klist [16384] u16; the row staging ([N] u16, last phase)
-// aliases keys / hist.  (select_small_kernel's layout without the two arrays only its non-LEAN forms use: 100 448 bytes at P = 4096.)
-static size_t select_many_smem(int P) { return (size_t)P * 8 + (size_t)(SEL_COPIES * SEL_BINS + SEL_WAVES + 8 + 512) * 4 + 16384 * 2; }
-
 static int sm_pow2(int v) {
   int p = 2;
   while (p < v) p <<= 1;
   return p;
 }
 
-// select_small_kernel<KPT, true> (select.hip) with plane = bag: the same steps in the same order on the bag's own N, k, n_sel, merge_R and
-// seed - radix threshold, exactly k candidates in thread order (ties lowest index first), the n_sel masked candidates drawn by the first
-// keyed permutation, the kept rows in ascending order, the merge_R rows to merge drawn by the second, ordered compaction, staged stores.
+// select_small_body<KPT, LEAN = true> (select_dev.hpp) with plane = bag: the steps of select_small_kernel's production form on the bag's own
+// N, k, n_sel, merge_R and seed, largest scores first.
 template <int KPT>
 __global__ __launch_bounds__(SEL_THREADS) void select_many_kernel(const float* __restrict__ score_all, SelManyTab tab,
                                                                  const uint64_t* __restrict__ tick, int64_t* __restrict__ rows_all, int P,
@@ -50,127 +46,9 @@ __global__ __launch_bounds__(SEL_THREADS) void select_many_kernel(const float* _
   int N = tab.N[0], k = tab.k[0], n_sel = tab.n_sel[0], merge_R = tab.merge_R[0];
   RG_PICK(row0, tab.row0, bag) RG_PICK(out0, tab.out0, bag) RG_PICK(seed0, tab.seed, bag)
   RG_PICK(N, tab.N, bag) RG_PICK(k, tab.k, bag) RG_PICK(n_sel, tab.n_sel, bag) RG_PICK(merge_R, tab.merge_R, bag)
-  const float* __restrict__ score = score_all + row0;
-  int64_t* __restrict__ rows_out = rows_all + out0;
-  const uint64_t rand_seed = eff_seed(seed0, tick);
-  uint64_t* keys = reinterpret_cast<uint64_t*>(smem_raw);               // [P] the candidates, in ascending row index
-  uint32_t* hist = reinterpret_cast<uint32_t*>(keys + P);               // [4][2048]
-  uint32_t* wave_tot = hist + SEL_COPIES * SEL_BINS;                    // [16]
-  uint32_t* misc = wave_tot + SEL_WAVES;                                // [8]
-  uint32_t* bitmap = misc + 8;                                          // [512] = 16384 bits
-  uint16_t* klist = reinterpret_cast<uint16_t*>(bitmap + 512);          // [N] kept rows in ascending order (the Merge draw indexes it)
-  uint16_t* stage = reinterpret_cast<uint16_t*>(smem_raw);              // [N] row list staging (aliases keys / hist: last phase)
-  const int tid = threadIdx.x;
-  const int i0 = tid * KPT;
-
-  uint32_t key[KPT];
-  bool valid[KPT];
-#pragma unroll
-  for (int j = 0; j < KPT; ++j) {
-    valid[j] = (i0 + j) < N;
-    key[j] = valid[j] ? mono32(score[i0 + j], true) : 0u;
-  }
-  for (int i = tid; i < 512; i += SEL_THREADS) bitmap[i] = 0;
-
-  // ---- 1. threshold
-  uint32_t remaining, n_eq;
-  const uint32_t T = radix_select_regs<KPT, false>(key, valid, (uint32_t)k, hist, wave_tot, misc, &remaining, &n_eq);
-
-  // ---- 2. gather exactly k keys (ties: lowest index first), positions in THREAD order: the draw below picks by list position
-  uint32_t eq_rank = 0;
-  if (remaining != n_eq) {
-    uint32_t neq = 0;
-#pragma unroll
-    for (int j = 0; j < KPT; ++j) neq += (valid[j] && key[j] == T) ? 1u : 0u;
-    uint32_t tot;
-    eq_rank = block_scan_excl(neq, wave_tot, &tot);
-  }
-  bool take[KPT];
-  uint32_t ntake = 0;
-#pragma unroll
-  for (int j = 0; j < KPT; ++j) {
-    bool t = valid[j] && key[j] > T;
-    if (valid[j] && key[j] == T) { t = remaining == n_eq || eq_rank < remaining; ++eq_rank; }
-    take[j] = t;
-    ntake += t ? 1u : 0u;
-  }
-  {
-    uint32_t tot;
-    uint32_t pos = block_scan_excl(ntake, wave_tot, &tot);
-#pragma unroll
-    for (int j = 0; j < KPT; ++j)
-      if (take[j]) keys[pos++] = ((uint64_t)key[j] << 32) | (uint64_t)(0xFFFFFFFFu - (uint32_t)(i0 + j));
-  }
-  __syncthreads();
-
-  // ---- 4. the masked candidates: candidate pi(i), i < n_sel, of the keyed permutation pi of the k list positions (n_sel == k: all of them,
-  // the set mhimx_select_rows masks through its ordered list)
-  {
-    const uint32_t k0 = mix32((uint32_t)rand_seed ^ 0x9E3779B9u), k1 = mix32((uint32_t)(rand_seed >> 32) + 0x85EBCA6Bu + k0 * 0x632BE5ABu);
-    const int bits = small_perm_bits((uint32_t)k);
-    for (int i = tid; i < n_sel; i += SEL_THREADS) {
-      const uint32_t j = feistel_small((uint32_t)i, (uint32_t)k, bits, k0, k1);
-      const uint32_t idx = 0xFFFFFFFFu - (uint32_t)(keys[j] & 0xFFFFFFFFull);
-      atomicOr(&bitmap[idx >> 5], 1u << (idx & 31));
-    }
-  }
-  __syncthreads();
-
-  // ---- 5. the kept rows, ascending
-  bool kv[KPT];
-  uint32_t nkeep = 0;
-#pragma unroll
-  for (int j = 0; j < KPT; ++j) {
-    const int i = i0 + j;
-    kv[j] = valid[j] && !((bitmap[i >> 5] >> (i & 31)) & 1u);
-    nkeep += kv[j] ? 1u : 0u;
-  }
-  uint32_t kept_total;
-  const uint32_t kpos0 = block_scan_excl(nkeep, wave_tot, &kept_total);
-
-  // ---- 6. Merge.masking: row klist[pi2(i)], i < merge_R, of a second keyed permutation (of the Lrows list positions) is merged
-  const int Lrows = (int)kept_total;
-  const int Lk = Lrows - merge_R;
-  const bool partial = merge_R > 0 && merge_R < Lrows;
-  if (partial) {
-    uint32_t kp = kpos0;
-#pragma unroll
-    for (int j = 0; j < KPT; ++j)
-      if (kv[j]) klist[kp++] = (uint16_t)(i0 + j);
-    for (int i = tid; i < 512; i += SEL_THREADS) bitmap[i] = 0;
-    __syncthreads();
-    const uint32_t q1 = mix32((uint32_t)rand_seed * 0x9E3779B1u + 0xC2B2AE35u), q0 = mix32(((uint32_t)(rand_seed >> 17) ^ 0x85EBCA6Bu) + q1 * 0x632BE5ABu);
-    const int bits2 = small_perm_bits((uint32_t)Lrows);
-    for (int i = tid; i < merge_R; i += SEL_THREADS) {
-      const uint32_t row = klist[feistel_small((uint32_t)i, (uint32_t)Lrows, bits2, q0, q1)];
-      atomicOr(&bitmap[row >> 5], 1u << (row & 31));
-    }
-    __syncthreads();
-  }
-  bool mrg[KPT];
-  uint32_t nstay = 0, nmrg = 0;
-#pragma unroll
-  for (int j = 0; j < KPT; ++j) {
-    const int i = i0 + j;
-    const bool m = kv[j] && (merge_R >= Lrows || (partial && ((bitmap[i >> 5] >> (i & 31)) & 1u)));
-    mrg[j] = m;
-    nmrg += m ? 1u : 0u;
-    nstay += (kv[j] && !m) ? 1u : 0u;
-  }
-  // one scan for both lists (each total <= 16384 fits 16 bits); merge_first: rows_out = [merge | stay]
-  uint32_t t2;
-  const uint32_t packed = block_scan_excl(nstay | (nmrg << 16), wave_tot, &t2);
-  uint32_t spos = (merge_first ? (uint32_t)(Lrows - Lk) : 0u) + (packed & 0xFFFFu);
-  uint32_t mpos2 = (merge_first ? 0u : (uint32_t)Lk) + (packed >> 16);
-  // staged in LDS so the 8-byte row ids leave as full coalesced lines
-#pragma unroll
-  for (int j = 0; j < KPT; ++j) {
-    if (!kv[j]) continue;
-    if (mrg[j]) stage[mpos2++] = (uint16_t)(i0 + j);
-    else stage[spos++] = (uint16_t)(i0 + j);
-  }
-  __syncthreads();
-  for (int i = tid; i < Lrows; i += SEL_THREADS) rows_out[i] = (int64_t)stage[i];
+  const SelectArgs a = {score_all + row0, N, k, n_sel, 1, nullptr, nullptr, 0, nullptr, nullptr, nullptr, P, merge_first ? 2 : 1,
+                        eff_seed(seed0, tick), merge_R, rows_all + out0, nullptr, 0};
+  select_small_body<KPT, true>(a, smem_raw);
 }
 
 // ------------------------------------------------------------------------------------------------ a bag above 16 384 rows
@@ -253,11 +131,11 @@ int select_rows_many_launch(hipStream_t st, const float* score, int32_t n_bags, 
   }
   if (n_small) {
     const int P = sm_pow2(kmax);
-    const size_t sm = select_many_smem(P);
+    const size_t sm = select_lds_bytes(P, true);
     MHIMX_ONCE_PER_DEVICE(
-        MHIMX_HIP(hipFuncSetAttribute((const void*)select_many_kernel<16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)select_many_smem(SM_SMALL_K)));
-        MHIMX_HIP(hipFuncSetAttribute((const void*)select_many_kernel<10>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)select_many_smem(SM_SMALL_K)));
-        MHIMX_HIP(hipFuncSetAttribute((const void*)select_many_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)select_many_smem(SM_SMALL_K))));
+        MHIMX_HIP(hipFuncSetAttribute((const void*)select_many_kernel<16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)select_lds_bytes(SM_SMALL_K, true)));
+        MHIMX_HIP(hipFuncSetAttribute((const void*)select_many_kernel<10>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)select_lds_bytes(SM_SMALL_K, true)));
+        MHIMX_HIP(hipFuncSetAttribute((const void*)select_many_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)select_lds_bytes(SM_SMALL_K, true))));
 #define MHIMX_SEL_MANY(KPT) \
     hipLaunchKernelGGL(select_many_kernel<KPT>, dim3((unsigned)n_small), dim3(SEL_THREADS), sm, st, score, tab, tick, rows_out, P, merge_first ? 1 : 0)
     if (nmax <= 4096) MHIMX_SEL_MANY(4);                // every bag of the launch fits 1024 * KPT rows

@@ -5,9 +5,9 @@
 //
 // Plane = segment.  The segment table travels by value (infer_tab.hpp's RG_PICK pattern: constant indices only), nothing is copied to
 // the device, waited for or allocated; the launch count does not depend on n_segs:
-//   small   one 1024-thread workgroup per segment.  N <= 16384: the whole job - keys in registers (scores read from HBM once), threshold
-//           by radix_select_regs (select_dev.hpp), exactly k_b 64-bit keys (value << 32 | ~index) gathered in index order, ordered in LDS,
-//           idx / val / padding written.  A larger segment's workgroup exits at once; n_large further workgroups zero the digit
+//   small   one 1024-thread workgroup per segment.  N <= 16384: the whole job - the select's own candidate stage (select_dev.hpp
+//           select_candidates: keys in registers, scores read from HBM once, threshold by radix_select_regs, exactly k_b 64-bit keys
+//           value << 32 | ~index in index order), ordered in LDS (rank counting, or select_dev.hpp lds_bitonic_desc), idx / val / padding written.  A larger segment's workgroup exits at once; n_large further workgroups zero the digit
 //           histograms of the large segments' workspace slots (a kernel of this stream, not a memset node: select.hip sel_zero_kernel).
 //   Only if a segment is above 16384 rows (one workgroup walking 200 000 keys several times is 0.6 ms: select.hip), on a
 //   (chunk, large segment) grid - up to 256 chunks of >= 4096 keys per segment, a segment's chunking depends on its own N alone:
@@ -83,16 +83,7 @@ MHIMX_DEV void tk_order_write(uint64_t* keys, int kb, int k, bool largest, int64
     while (P < kb) P <<= 1;
     for (int j = kb + tid; j < P; j += SEL_THREADS) keys[j] = 0ull;          // (0 is below every key)
     __syncthreads();
-    for (int size = 2; size <= P; size <<= 1)
-      for (int stride = size >> 1; stride > 0; stride >>= 1) {
-        for (int t = tid; t < (P >> 1); t += SEL_THREADS) {
-          const int lo = 2 * t - (t & (stride - 1)), hi = lo + stride;
-          const bool desc = ((lo & size) == 0);
-          const uint64_t a = keys[lo], b = keys[hi];
-          if ((a < b) == desc) { keys[lo] = b; keys[hi] = a; }
-        }
-        __syncthreads();
-      }
+    lds_bitonic_desc(keys, P);
   }
   for (int j = tid; j < k; j += SEL_THREADS) {
     int64_t id = -1;
@@ -126,42 +117,13 @@ __global__ __launch_bounds__(SEL_THREADS) void topk_small_kernel(const float* __
   const bool lg = largest != 0;
   const int kb = k < N ? k : N;
   const float* s = score + row0;
-  const int i0 = tid * TK_KPT;                // thread t owns the contiguous instances [16 t, 16 t + 16)
+  // thread t owns the contiguous instances [16 t, 16 t + 16): exactly kb keys, in index order (ties: lowest index first), where the
+  // histogram was
+  uint64_t* keys = reinterpret_cast<uint64_t*>(hist);
   uint32_t key[TK_KPT];
   bool valid[TK_KPT];
-#pragma unroll
-  for (int j = 0; j < TK_KPT; ++j) {
-    valid[j] = (i0 + j) < N;
-    key[j] = valid[j] ? mono32(s[i0 + j], lg) : 0u;
-  }
-  // ---- threshold
-  uint32_t remaining, n_eq;
-  const uint32_t T = radix_select_regs<TK_KPT, false>(key, valid, (uint32_t)kb, hist, wave_tot, misc, &remaining, &n_eq);
-  // ---- exactly kb keys, in index order (ties: lowest index first)
-  uint32_t eq_rank = 0;
-  if (remaining != n_eq) {
-    uint32_t neq = 0;
-#pragma unroll
-    for (int j = 0; j < TK_KPT; ++j) neq += (valid[j] && key[j] == T) ? 1u : 0u;
-    uint32_t tot;
-    eq_rank = block_scan_excl(neq, wave_tot, &tot);
-  }
-  bool take[TK_KPT];
-  uint32_t ntake = 0;
-#pragma unroll
-  for (int j = 0; j < TK_KPT; ++j) {
-    bool t = valid[j] && key[j] > T;
-    if (valid[j] && key[j] == T) { t = remaining == n_eq || eq_rank < remaining; ++eq_rank; }
-    take[j] = t;
-    ntake += t ? 1u : 0u;
-  }
-  uint64_t* keys = reinterpret_cast<uint64_t*>(hist);                   // (radix_select_regs ends with a barrier: the histogram is dead)
-  uint32_t tot;
-  uint32_t pos = block_scan_excl(ntake, wave_tot, &tot);
-#pragma unroll
-  for (int j = 0; j < TK_KPT; ++j)
-    if (take[j]) keys[pos++] = ((uint64_t)key[j] << 32) | (uint64_t)(0xFFFFFFFFu - (uint32_t)(i0 + j));
-  __syncthreads();
+  select_load_keys<TK_KPT>(s, N, lg, key, valid);
+  select_candidates<TK_KPT>(key, valid, (uint32_t)kb, keys, hist, wave_tot, misc);
   tk_order_write(keys, kb, k, lg, idx + (int64_t)b * k, val ? val + (int64_t)b * k : nullptr);
 }
 

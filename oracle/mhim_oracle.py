@@ -263,7 +263,102 @@ def get_mask(ps, attn, mask_ratio=0.0, mask_ratio_l=0.0, mask_ratio_h=0.0, mask_
 
 
 # --------------------------------------------------------------------------- #
-# A8  Merge / MCA   (mhim_modules/merge.py)
+# A6b  the device-drawn select (csrc/select_dev.hpp: the production draw of mhimx_select_rows / _img / _many)
+#      -- an exact integer model: the build draws its random subsets itself (keyed Feistel permutations of list
+#      positions), so "the right bits" are defined here and nowhere in the reference.  numpy integers only.
+# --------------------------------------------------------------------------- #
+_M32, _M64 = 0xFFFFFFFF, 0xFFFFFFFFFFFFFFFF
+
+
+def mono32(score: np.ndarray, largest: bool = True) -> np.ndarray:
+    """Order-preserving uint32 image of an fp32 score; the largest key is the smallest value when not `largest`."""
+    b = np.ascontiguousarray(score, dtype=np.float32).view(np.uint32)
+    b = np.where(b & np.uint32(0x80000000), ~b, b | np.uint32(0x80000000)).astype(np.uint32)
+    return b if largest else ~b
+
+
+def mix32(x: int) -> int:
+    x &= _M32
+    x ^= x >> 16; x = x * 0x7FEB352D & _M32
+    x ^= x >> 15; x = x * 0x846CA68B & _M32
+    return x ^ x >> 16
+
+
+def small_perm_bits(n: int) -> int:
+    bits = 2
+    while (1 << bits) < n:
+        bits += 1
+    return bits
+
+
+def feistel_small(j, n: int, bits: int, k0: int, k1: int) -> np.ndarray:
+    """Keyed permutation of 0 .. n-1 at the positions j: four Feistel rounds on the 2^bits domain (halves of floor / ceil(bits / 2)
+    bits), cycle-walked into [0, n)."""
+    rb = bits >> 1
+    lb = bits - rb
+    rm, lm = np.uint64((1 << rb) - 1), np.uint64((1 << lb) - 1)
+    m32 = np.uint64(_M32)
+    x = np.asarray(j, dtype=np.uint64).copy()
+    todo = np.ones(x.shape, dtype=bool)
+    while todo.any():
+        v = x[todo]
+        l, r = v >> np.uint64(rb), v & rm
+        for rd in range(4):
+            f = ((l if rd & 1 else r) * np.uint64(0x9E3779B1) + np.uint64((k1 if rd & 1 else k0) + (rd * 0x7F4A7C15 & _M32))) & m32
+            f ^= f >> np.uint64(15)
+            f = f * np.uint64(0x846CA68B) & m32
+            f ^= f >> np.uint64(13)
+            if rd & 1:
+                r = r ^ (f & rm)
+            else:
+                l = l ^ (f & lm)
+        x[todo] = (l << np.uint64(rb)) | r
+        todo &= x >= np.uint64(n)
+    return x.astype(np.int64)
+
+
+def select_rows_parts(score, k, n_sel, merge_R, seed, tick=0, largest=True):
+    """The pieces of select_rows: top (the k candidates by value descending, then index), cand (the same, ascending row index), masked (the n_sel masked rows in draw order), kept
+    (the other rows, ascending), stay / merged (the two halves of kept, each ascending)."""
+    key = mono32(np.asarray(score).reshape(-1), largest)
+    N = key.shape[0]
+    assert 1 <= k <= N and 0 <= n_sel <= k and 0 <= merge_R <= N - n_sel
+    top = np.argsort(~key, kind="stable")[:k]                         # k largest keys, ties lowest index first (topk_indices)
+    cand = np.sort(top).astype(np.int64)
+    s = (int(seed) + int(tick) * 0x9E3779B97F4A7C15) & _M64
+    lo, hi = s & _M32, s >> 32
+    k0 = mix32(lo ^ 0x9E3779B9)
+    k1 = mix32(hi + 0x85EBCA6B + k0 * 0x632BE5AB)
+    masked = cand[feistel_small(np.arange(n_sel), k, small_perm_bits(k), k0, k1)]
+    flag = np.zeros(N, dtype=bool)
+    flag[masked] = True
+    kept = np.nonzero(~flag)[0].astype(np.int64)
+    L = N - n_sel
+    assert kept.shape[0] == L
+    q1 = mix32(lo * 0x9E3779B1 + 0xC2B2AE35)
+    q0 = mix32((((s >> 17) & _M32) ^ 0x85EBCA6B) + q1 * 0x632BE5AB)
+    if merge_R >= L:
+        merged = kept
+    elif merge_R > 0:
+        merged = np.sort(kept[feistel_small(np.arange(merge_R), L, small_perm_bits(L), q0, q1)])
+    else:
+        merged = kept[:0]
+    mflag = np.zeros(N, dtype=bool)
+    mflag[merged] = True
+    stay = kept[~mflag[kept]]
+    return dict(top=top.astype(np.int64), cand=cand, masked=masked, kept=kept, stay=stay, merged=merged)
+
+
+def select_rows(score, k, n_sel, merge_R, seed, tick=0, largest=True, merge_first=False) -> np.ndarray:
+    """mhimx_select_rows' row list, bit for bit: [rows that stay (ascending) | rows to merge (ascending)], or [merged | stay] with
+    merge_first.  The HAM mask is n_sel of the k top-scored rows, the Merge split merge_R of the N - n_sel others; both subsets are the
+    first entries of a keyed permutation of list positions (seed + tick * 0x9E3779B97F4A7C15)."""
+    p = select_rows_parts(score, k, n_sel, merge_R, seed, tick, largest)
+    return np.concatenate([p["merged"], p["stay"]] if merge_first else [p["stay"], p["merged"]])
+
+
+# --------------------------------------------------------------------------- #
+# A8  Merge / MCA  (mhim_modules/merge.py)
 # --------------------------------------------------------------------------- #
 
 
